@@ -84,6 +84,28 @@ def algorithmic_flops(iters, K, period=20):
     return float(np.sum(it * (4 * K * K + 2 * K) + np.ceil(it / period) * (2 * K * K + 3 * K) + 3 * K * K))
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: the arrays the timed path returned in its last step, as DIR/<name>.npy in float64 (the integer
+    counts convert exactly), so that two builds can be compared output for output on the same seeded inputs.  Beyond
+    DUMP_MAX_BYTES in all, every array keeps the same fixed, seeded sample of rows, sorted; their indices are written too
+    (`sample_rows`)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n_rows = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        row_bytes = total / n_rows + 8                                 # (+ the row's index in sample_rows)
+        keep = int((DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)) // row_bytes)      # (4 KiB per file for the .npy headers)
+        rows = np.sort(np.random.default_rng(seed).choice(n_rows, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 class DevBuf:
     def __init__(self, L, nbytes):
         from pilot_amd import _lib
@@ -106,7 +128,7 @@ def main():
     ap.add_argument("--precision", default="auto", choices=["auto", "fp32", "fp64", "bf16x3", "f16x2"])
     ap.add_argument("--mode", default="sinkhorn", choices=["sinkhorn", "emd", "cellw2"],
                     help="emd: time the exact-OT pair grid (the reference's default mode) instead; cellw2: the cell-level W2 "
-                         "extension at BASELINE config 5 (200 patients x 5000 cells x 30 dims; takes about two minutes)")
+                         "extension at BASELINE config 5 (200 patients x 5000 cells x 30 dims; about two minutes at --steps 1, each further step one more pass)")
     ap.add_argument("--cell-patients", type=int, default=200)
     ap.add_argument("--cell-cells", type=int, default=5000)
     ap.add_argument("--ramp-steps", type=int, default=-1,
@@ -121,7 +143,12 @@ def main():
                          "ranks) with a world of one")
     ap.add_argument("--logical-shards", action="store_true",
                     help="testing on a 1-GPU box: --gpus N becomes N logical shards on device 0 (peer-copy gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all: a fixed, seeded row sample beyond that; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -156,7 +183,7 @@ def main():
         print(json.dumps(out), flush=True)
         return
     if args.mode == "cellw2":
-        print(json.dumps(bench_cellw2(args)), flush=True)
+        print(json.dumps(bench_cellw2(args, steps=args.steps, dump_dir=args.dump_outputs)), flush=True)
         return
 
     per_rank = None
@@ -258,6 +285,11 @@ def main():
                                      "every rank's index"}
         else:
             E = plan.fetch(n_rows=N)[0]
+    if args.dump_outputs and rank == 0:
+        outs = {"emd": E}
+        if iters.shape == E.shape:          # (one process per GPU: a rank holds the iters / err / flags of its own rows only)
+            outs.update(info)
+        dump_outputs(args.dump_outputs, outs)
     assert E.shape == (N, N) and np.isfinite(E).all(), "bench produced a non-finite matrix"
     if args.reg >= 0.05:   # converged entropic costs are symmetric; a bad row interleave would break this
         assert float(np.abs(E - E.T).max()) < 1e-5, "assembled matrix is not symmetric: bad row interleave?"
@@ -925,9 +957,10 @@ def cpu_baseline(P, M, reg, budget_s, E_gpu, iters_gpu):
     return base, eq, allc, upd
 
 
-def bench_cellw2(args, reg=0.1, D=30):
+def bench_cellw2(args, reg=0.1, D=30, steps=1, dump_dir=None):
     """--mode cellw2: BASELINE config 5 (an extension, not in the reference): every ordered pair of `--cell-patients`
-    patients with `--cell-cells` cells each, log-domain Sinkhorn on raw cell clouds, cells resident in HBM."""
+    patients with `--cell-cells` cells each, log-domain Sinkhorn on raw cell clouds, cells resident in HBM.  `steps` timed
+    passes over the whole grid (the `c5_cellw2` key of the default line: one)."""
     from pilot_amd import engine
     from pilot_amd.synthetic import make_cell_clouds
     Np, nc = args.cell_patients, args.cell_cells
@@ -935,12 +968,15 @@ def bench_cellw2(args, reg=0.1, D=30):
     co = engine.CellCohort(X, offs)
     co.w2_grid(scale, reg, row_begin=0, row_end=1, num_iter_max=3)         # warm-up (code objects, clocks)
     t = time.perf_counter()
-    W, info = co.w2_grid(scale, reg, return_info=True)
-    dt = time.perf_counter() - t
+    for _ in range(steps):
+        W, info = co.w2_grid(scale, reg, return_info=True)
+    dt = (time.perf_counter() - t) / steps
     kern_s = co.last_kernel_ms * 1e-3
     pieces = co.last_pieces
     terms = 3 if pieces == 2 else 6
     co.close()
+    if dump_dir:
+        dump_outputs(dump_dir, {"w2": W, **info})
     upd = info["iters"].astype(np.float64)
     flop = float((upd * 2 * 2.0 * nc * nc * D).sum() + 2.0 * nc * nc * D * upd.size)     # two dot-product passes per update + the value pass
     conv = info["iters"] < 1000
@@ -983,7 +1019,7 @@ def bench_cellw2(args, reg=0.1, D=30):
             pass
     return {
         "metric": "cell-level W2 patient-pairs/sec (full NxN matrix; extension, BASELINE config 5)", "value": round(Np * Np / dt, 2),
-        "unit": "pairs/s", "n_gpus": 1, "steps": 1, "warmup": 1, "ms_per_step": round(1e3 * dt, 1), "higher_is_better": True,
+        "unit": "pairs/s", "n_gpus": 1, "steps": steps, "warmup": 1, "ms_per_step": round(1e3 * dt, 1), "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None,
         "dtype": ("f32 potentials; dot products from 2 fp16 pieces per coordinate (22 significant bits) on the f16 MFMA" if pieces == 2 else
                   "f32 potentials; dot products as exact 3-way bf16 splits of the coordinates on the bf16 MFMA"), "data": "synthetic",
@@ -1027,6 +1063,8 @@ def bench_emd(args, L, P, M, cfg):
     _lib.check(L.pilot_ot_memcpy_d2h(E.ctypes.data, plan.dE, 8 * N * N))
     _lib.check(L.pilot_ot_memcpy_d2h(n_aug.ctypes.data, plan.dIt, 4 * N * N))
     plan.close()
+    if args.dump_outputs:                   # (EMD_MIRROR solves the upper triangle only: the rest of n_aug is never written)
+        dump_outputs(args.dump_outputs, {"emd": E, "n_aug": np.triu(n_aug) if mode == 2 else n_aug})
     out = {
         "metric": "exact-EMD patient-pairs/sec (full NxN matrix, reference default mode)", "value": round(N * N / dt, 1),
         "unit": "pairs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt, 4),

@@ -351,7 +351,9 @@ int pilot_ot_diffusion_kernel_of_rows(const double *E, int E_is_device, int N, i
  * Pair (i, j): uniform weights 1/n_i, 1/n_j, cost C = |x - y|^2 / scale, entropic OT solved in the log domain with
  * the control flow of POT's ot.bregman.sinkhorn_log (v-update then u-update; marginal error every check_period
  * updates; stop on err < stop_thr, floored in f32 like the proportion-level kernel, or after num_iter_max updates);
- * the value is <Gamma, C>.  The n_i x n_j cost matrix is never materialised.  D <= 64; patients up to ~13 000 cells.
+ * the value is <Gamma, C>.  The n_i x n_j cost matrix is never materialised.  D <= 64; patients up to 13 637 cells.
+ * PILOT_OT_ENOTSUP when a cell lies so far out that the f32 kernel would miss its 1e-5 relative accuracy:
+ * max_i |x_i - mean(X)| * sqrt(2 log2(e) / (scale * reg)) > 50 (the Euclidean norm of the cell farthest from the mean).
  * w2 / iters / err: n_rows x N (iters, err nullable). */
 int pilot_ot_cell_w2_grid(const float *X, const long long *offsets, int N, int D, double scale, double reg,
                           int num_iter_max, double stop_thr, int check_period, double f32_floor_ulps,

@@ -38,6 +38,16 @@ constexpr int CELL_TILE_CELLS = 16, CELL_PREFETCH_TILES = 1;
 constexpr int CELL_PREFETCH_CELLS = (CELL_PREFETCH_TILES + 1) * CELL_TILE_CELLS;
 constexpr size_t CELL_PAD_BYTES = (size_t)CELL_PREFETCH_CELLS * 32;
 static_assert(CELL_PAD_BYTES >= (size_t)((CELL_PREFETCH_TILES + 1) * CELL_TILE_CELLS - 1) * 32, "operand pad shorter than the sweep's read-ahead");
+// Largest accepted s_max = max_i |x_i - mean| * sqrt(2 log2(e) / (scale * reg)), the largest scaled NORM of a cell of the centred
+// cohort, taken in fp64 at cohort creation (cell_w2_enqueue refuses more with PILOT_OT_ENOTSUP).  Measured on MI355X: one or three
+// cells of a 200 + 200 + 150-cell cohort moved out along an axis or a diagonal, D = 30 and 64, reg 0.1 and 0.02, both operand
+// formats; worst |W - W_fp64| / max(1, |W_fp64|) by s_max: 25: 4.2e-7, 50: 2.3e-6, 75: 4.1e-6, 100: 8.0e-6, 150: 1.9e-5 (D = 30,
+// diagonal), 200: 3.1e-5, 500: 1.1e-4, 2e3: 6.3e-4, 2e4: 9.1.  Cohorts without a far-out cell (D = 1 .. 64, reg down to 0.002)
+// stayed below 2.5e-6 up to s_max 58.  At the limit the error is 4x inside the 1e-5 contract; the first failure is 3x above it.
+// The limit also makes two branches unreachable by an accepted input: the bf16 pieces chosen without PILOT_OT_CELL_BF16 (s >= 3e4),
+// and lse_pass's online-maximum fallback for an fp16 row-shift slot that overflowed (|m_row| ~ s_i s_j > 65 504); that fallback
+// still runs on every pair's first update.
+constexpr double CELL_MAX_SCALED_NORM = 50.0;
 constexpr int CELL_WG = 1024;   // 16 waves share one pair: the self-pairs converge slowly and set the critical path
 constexpr float LOG2E_F = 1.4426950408889634f, LN2_F = 0.6931471805599453f;
 

@@ -1927,6 +1927,7 @@ struct pilot_ot_cell_cohort {
     int xb_half = -1;              // ... and their format: 1 two fp16 pieces, 0 three bf16 pieces
     int xb_one_slot = -1;          // ... and whether the last k-slot of every cell holds 1 (cell_setup_kernel)
     float max_abs = 0.f;           // largest |coordinate| of the centred cohort (decides whether fp16 pieces are safe)
+    double max_norm = 0.0;         // largest |x - mean| of the cohort, in fp64 (bounds the accuracy envelope: CELL_MAX_SCALED_NORM)
     uint4 *dXb = nullptr;          // bf16 operand pieces of every cell (resident)
     float *dnrm = nullptr;
     long long *doffs = nullptr;
@@ -1986,13 +1987,20 @@ PILOT_API int pilot_ot_cell_cohort_create(const float *X, const long long *offse
         for (int d = 0; d < D; ++d) mean[(size_t)d] /= (double)c->C;
         std::vector<float> Xc((size_t)c->C * D);
         float mx = 0.f;
-        for (long long i = 0; i < c->C; ++i)
+        double mn2 = 0.0;
+        for (long long i = 0; i < c->C; ++i) {
+            double n2 = 0.0;
             for (int d = 0; d < D; ++d) {
-                const float v = (float)((double)X[(size_t)i * D + d] - mean[(size_t)d]);
+                const double vd = (double)X[(size_t)i * D + d] - mean[(size_t)d];
+                const float v = (float)vd;
                 Xc[(size_t)i * D + d] = v;
                 mx = fabsf(v) > mx ? fabsf(v) : mx;
+                n2 += vd * vd;
             }
+            mn2 = n2 > mn2 ? n2 : mn2;
+        }
         c->max_abs = mx;
+        c->max_norm = sqrt(mn2);
         e = hipMemcpy(c->dX, Xc.data(), sizeof(float) * (size_t)c->C * D, hipMemcpyHostToDevice);
     }
     if (e == hipSuccess) e = hipMemcpy(c->doffs, offsets, sizeof(long long) * (size_t)(N + 1), hipMemcpyHostToDevice);
@@ -2010,6 +2018,14 @@ int cell_w2_enqueue(pilot_ot_cell_cohort *c, double scale, double reg, int num_i
     if (num_iter_max < 1 || check_period < 1) return fail(PILOT_OT_EINVAL, "num_iter_max / check_period must be >= 1");
     if (row_step < 1 || row_begin < 0 || row_end > c->N || row_begin > row_end)
         return fail(PILOT_OT_EINVAL, "bad row range [%d, %d) step %d for N=%d", row_begin, row_end, row_step, c->N);
+    {
+        // accuracy envelope: the exponent of a pair is an f32 sum of terms of size s_i s_j (s: a cell's scaled norm), so one
+        // far-out cell costs accuracy that the plan does not average away (pilot::CELL_MAX_SCALED_NORM)
+        const double s_max = c->max_norm * sqrt(2.0 * 1.4426950408889634 / (scale * reg));
+        if (s_max > pilot::CELL_MAX_SCALED_NORM)
+            return fail(PILOT_OT_ENOTSUP, "a cell lies too far out for the f32 kernel: max_i |x_i - mean| * sqrt(2 log2(e) / (scale * reg)) "
+                        "= %.4g > %g (drop far-out cells, or raise scale or reg)", s_max, pilot::CELL_MAX_SCALED_NORM);
+    }
     const int n_rows = (row_end - row_begin + row_step - 1) / row_step;
     const size_t n_out = (size_t)n_rows * c->N;
     *n_out_p = n_out;
@@ -2038,7 +2054,8 @@ int cell_w2_enqueue(pilot_ot_cell_cohort *c, double scale, double reg, int num_i
         p.two_alpha2 = op_scale * op_scale;
         p.dot_unscale = 1.f / p.two_alpha2;
         // two fp16 pieces (half the matrix work) while the scaled coordinates stay far inside fp16's range and above the
-        // level where its subnormal spacing (2^-24) would cost accuracy; three bf16 pieces otherwise (PILOT_OT_CELL_BF16=1: always)
+        // level where its subnormal spacing (2^-24) would cost accuracy; three bf16 pieces otherwise (PILOT_OT_CELL_BF16=1: always;
+        // below the CELL_MAX_SCALED_NORM refusal above, only the switch selects them)
         const char *force = pilot::test_switch("PILOT_OT_CELL_BF16");
         half = c->max_abs * op_scale < 3.0e4f && !(force && *force && *force != '0') ? 1 : 0;
         const int one_slot = half && c->D <= 32 * c->KB - 2 && !pilot::test_switch("PILOT_OT_CELL_NO_AUG") ? 1 : 0;

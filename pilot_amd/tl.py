@@ -509,6 +509,10 @@ def cell_level_wasserstein(adata, emb_matrix="X_PCA", sample_col="sampleID", sta
     solved in the log domain on the device for all ordered sample pairs.  Writes ``adata.uns['EMD_cell']`` (ndarray
     N x N of transport costs), ``adata.uns['EMD_cell_df']`` and ``adata.uns['real_labels']``; returns nothing, like
     ``wasserstein_distance``.
+
+    Raises ``NotImplementedError`` when the cell farthest from the global centroid lies beyond the kernel's accuracy
+    envelope, ``max_i |x_i - mean| * sqrt(2 log2(e) / (scale * reg)) > 50`` (include/pilot_ot.h): one stray cell is enough,
+    and so is a reg too small for the spread of the cohort.  Drop the outlier cells, or raise ``scale`` or ``reg``.
     """
     X = np.asarray(adata.obsm[emb_matrix], dtype=np.float32)
     obs = adata.obs[[sample_col, status]].copy()

@@ -373,6 +373,27 @@ int pilot_ot_cell_w2_grid_multi(const float *X, const long long *offsets, int N,
                                 int num_iter_max, double stop_thr, int check_period, double f32_floor_ulps,
                                 const int *devices, int n_devices, double *w2, int *iters, double *err);
 
+/* ---- transport plans (EXTENSION: not in the reference; POT's ot.emd / ot.sinkhorn return them, Trajectory.py keeps the values) */
+/* Optimal couplings Gamma (K x K) of selected ordered pairs (i, j): rows = a = P[i], columns = b = P[j].
+ * regularized 0: exact, the plan of ot.emd(a, b * sum(a) / sum(b), M) (POT's pre-step), solved by the pair grid's exact kernels
+ *                (one wave per pair for K <= 256, one workgroup per pair above).  The LP's optimal VALUE is unique, its plan need
+ *                not be: the plan returned is AN optimum, the one these kernels reach.
+ *             1: entropic, ot.sinkhorn(a, b, M, reg, method="sinkhorn_stabilized") in f64, POT's loop step by step (the pair
+ *                grid's PILOT_OT_PREC_GENERIC kernel), Gamma = exp(-(M - alpha_i - beta_j)/reg + log u_i + log v_j).
+ *                A pair that hits num_iter_max returns the plan of its last iterate; a pair whose scalings went NaN returns
+ *                the plan of its last good iterate, like POT; flags tell which, with the bits the pair grid reports.
+ * pair_group == NULL: plans is n_pairs x K x K.  Otherwise plans is n_groups x K x K, the sum of the plans of the pairs of each
+ * group (pair_group[t] in [0, n_groups)), added in list order in f64 (bit-reproducible; a group without pairs is 0).
+ * values / iters / flags (nullable, n_pairs): what the pair grid returns for that pair -- <M, Gamma>; exact: iters = the
+ * augmentations (negative, and the value NaN, if the solver's guard tripped: that pair's plan is not usable), flags = 0;
+ * entropic: iterations and PILOT_OT_FLAG_* bits.  Pairs go through a device scratch of at most 1 GiB of plans at a time.
+ * Argument errors are reported before the device is touched; K > 2048 -> PILOT_OT_ENOTSUP.  n_pairs = 0 writes nothing. */
+int pilot_ot_transport_plans(const double *P, int N, int K, const double *M, int regularized, double reg,
+                             int num_iter_max, double stop_thr, double tau, int check_period,
+                             const int *pair_i, const int *pair_j, long long n_pairs,
+                             const int *pair_group, int n_groups,
+                             double *plans, double *values, int *iters, int *flags);
+
 /* precision selected by PILOT_OT_PREC_AUTO for a given max(M)/reg (PILOT_OT_PREC_F16X2, PILOT_OT_PREC_BF16X3 or
  * PILOT_OT_PREC_F64; a shape whose split operand image does not fit LDS runs PILOT_OT_PREC_F32 instead) */
 int pilot_ot_auto_precision(double max_cost_over_reg);

@@ -35,7 +35,7 @@ SYMBOLS = [
     "pilot_ot_proportions", "pilot_ot_proportions_ex", "pilot_ot_centroid_medians", "pilot_ot_embedding_upload",
     "pilot_ot_embedding_destroy", "pilot_ot_centroid_medians_dev", "pilot_ot_prepass_dev", "pilot_ot_prepass_device_ms", "pilot_ot_label_codes", "pilot_ot_test_switch", "pilot_ot_cell_w2_grid",
     "pilot_ot_cell_cohort_create", "pilot_ot_cell_cohort_destroy", "pilot_ot_cell_cohort_pieces", "pilot_ot_cell_w2_grid_cohort", "pilot_ot_cell_w2_grid_multi",
-    "pilot_ot_mirror_upper_dev",
+    "pilot_ot_mirror_upper_dev", "pilot_ot_transport_plans",
     "pilot_ot_row_distances", "pilot_ot_row_distances_dev", "pilot_ot_silhouette", "pilot_ot_knn_kernel",
     "pilot_ot_silhouette_dev", "pilot_ot_knn_kernel_dev", "pilot_ot_silhouette_of_rows", "pilot_ot_diffusion_kernel_of_rows",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
@@ -119,6 +119,8 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_emd_grid_dev.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]
     fp = ctypes.POINTER(ctypes.c_float)
     L.pilot_ot_mirror_upper_dev.argtypes = [c_vp, c_int, c_vp]
+    L.pilot_ot_transport_plans.argtypes = [dp, c_int, c_int, dp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_int, ip, ip,
+                                           ctypes.c_longlong, ip, c_int, dp, dp, ip, ip]
     L.pilot_ot_row_distances.argtypes = [dp, c_int, c_int, c_int, dp]
     L.pilot_ot_row_distances_dev.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]
     L.pilot_ot_silhouette.argtypes = [dp, ip, c_int, c_int, dp, dp]

@@ -56,7 +56,17 @@ __device__ inline double block_sum(double v, double *red_v) {
     return s;
 }
 
+// PILOT_PLAN_TU (pilot_ot_plans.hip): emd_generic_plan_kernel, the same source with pairs from the list in `pa`, results at the
+// item's index, and the final pass over F also writing every entry of the pair's K x K block of pa.plans (see emd_grid_kernel)
+#ifndef PILOT_PLAN_TU
 __global__ void __launch_bounds__(EMDG_WG) emd_generic_kernel(EmdParams p, const double *__restrict__ rowmin) {
+    constexpr bool PLAN = false;
+    const PlanArgs *pa = nullptr;
+#else
+__global__ void __launch_bounds__(EMDG_WG) emd_generic_plan_kernel(EmdParams p, const double *__restrict__ rowmin, PlanArgs plan_args) {
+    constexpr bool PLAN = true;
+    const PlanArgs *pa = &plan_args;
+#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char emdg_smem[];
     const int K = p.K, N = p.N, tid = threadIdx.x;
     double *pu = reinterpret_cast<double *>(emdg_smem), *pv = pu + K, *ra = pv + K, *rb = ra + K, *dC = rb + K, *fR = dC + K, *fC = fR + K;
@@ -71,7 +81,7 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_kernel(EmdParams p, const
     const double *M = p.M;
     const double INF = __builtin_inf();
     const long total = (long)p.n_rows * N;
-    const long n_items = p.upper_only ? (long)p.n_rows * (N - p.row_begin) - (long)p.row_step * p.n_rows * (p.n_rows - 1) / 2 : total;
+    const long n_items = PLAN ? pa->n_pairs : p.upper_only ? (long)p.n_rows * (N - p.row_begin) - (long)p.row_step * p.n_rows * (p.n_rows - 1) / 2 : total;
     auto row_offset = [&](long r) { return r * (N - p.row_begin) - (long)p.row_step * r * (r - 1) / 2; };
 
     for (bool first = true;; first = false) {
@@ -81,7 +91,9 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_kernel(EmdParams p, const
         __syncthreads();
         if (t >= n_items) break;
         int r, j_s;
-        if (p.upper_only) {
+        if constexpr (PLAN) {
+            r = 0; j_s = pa->pair_j[t];
+        } else if (p.upper_only) {
             long rr = 0;
             while (rr + 1 < p.n_rows && row_offset(rr + 1) <= t) ++rr;      // (a fallback: the linear walk is fine)
             r = (int)rr;
@@ -89,8 +101,8 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_kernel(EmdParams p, const
         } else {
             r = (int)(t / N); j_s = (int)(t % N);
         }
-        const long q = (long)r * N + j_s;
-        const int i_s = p.row_begin + r * p.row_step;
+        const long q = PLAN ? t : (long)r * N + j_s;
+        const int i_s = PLAN ? pa->pair_i[t] : p.row_begin + r * p.row_step;
 
         // POT pre-step b *= sum(a) / sum(b); potentials; zero flow; diagonal warm start
         double sa = 0.0, sb = 0.0;
@@ -231,7 +243,15 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_kernel(EmdParams p, const
         }
         // cost = sum F_ij M_ij
         double cost = 0.0;
-        for (size_t e = tid; e < (size_t)K * K; e += EMDG_WG) { const double f = F[e]; if (f != 0.0) cost += f * M[e]; }
+        if constexpr (PLAN) {
+            for (size_t e = tid; e < (size_t)K * K; e += EMDG_WG) {
+                const double f = F[e];
+                if (f != 0.0) cost += f * M[e];
+                pa->plans[(size_t)q * K * K + e] = f;
+            }
+        } else {
+            for (size_t e = tid; e < (size_t)K * K; e += EMDG_WG) { const double f = F[e]; if (f != 0.0) cost += f * M[e]; }
+        }
         cost = block_sum(cost, red_v);
         if (tid == 0) {
             p.emd[q] = trip ? __builtin_nan("") : cost;
@@ -241,6 +261,7 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_kernel(EmdParams p, const
     }
 }
 
+#ifndef PILOT_PLAN_TU
 // row minima of M (the initial row potentials), once per call
 __global__ void emd_rowmin_kernel(const double *__restrict__ M, int K, double *__restrict__ rowmin) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K; i += gridDim.x * blockDim.x) {
@@ -249,5 +270,6 @@ __global__ void emd_rowmin_kernel(const double *__restrict__ M, int K, double *_
         rowmin[i] = m;
     }
 }
+#endif
 
 }  // namespace pilot

@@ -22,6 +22,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "plan_args.hpp"
+
 namespace pilot {
 
 
@@ -222,9 +224,23 @@ __host__ __device__ constexpr size_t emd_lds_bytes(int K) {
 constexpr int EMD_NQ = 64, EMD_Q_STRIDE = 32;
 #define EMD_WPE_ATTR __attribute__((amdgpu_waves_per_eu(NK == 1 ? 8 : (NK == 2 ? 8 : 2), 8)))
 
-// MG: the cost matrix is read from global memory (L2) instead of LDS -- K > 128, where K*K doubles no longer fit LDS
+// MG: the cost matrix is read from global memory (L2) instead of LDS -- K > 128, where K*K doubles no longer fit LDS.
+// PILOT_PLAN_TU (pilot_ot_plans.hip) turns the same source into emd_grid_plan_kernel: pairs come from the list in `pa` (item t:
+// rows P[pair_i[t]], columns P[pair_j[t]], results at t), and the support walk at the end of a pair also stores every nonzero
+// flow into the pair's zero-filled K x K block of pa.plans.  The plan code sits behind `if constexpr (PLAN)` and constant
+// conditions, so emd_grid_kernel compiles to what it did before.  (A shared always-inline device function called from both
+// kernels did not: the pair-grid kernels' code changed, with 70 -> 112 SGPR spills at K > 192.)
+#ifndef PILOT_PLAN_TU
 template <int NK, bool MG = false, bool UL = true>
 __global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_kernel(EmdParams p) {
+    constexpr bool PLAN = false;
+    const PlanArgs *pa = nullptr;
+#else
+template <int NK, bool MG, bool UL>
+__global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_plan_kernel(EmdParams p, PlanArgs plan_args) {
+    constexpr bool PLAN = true;
+    const PlanArgs *pa = &plan_args;
+#endif
     constexpr int EMD_WAVES = emd_waves(NK);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int K = p.K, N = p.N;
@@ -289,7 +305,8 @@ __global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_kern
     // unluckiest wave.)  With upper_only the counter runs over the solved pairs alone: local row r = rows row_begin +
     // r row_step holds the N - i_s pairs j >= i_s, so item t sits in the row with offset(r) <= t < offset(r + 1),
     // offset(r) = r (N - row_begin) - row_step r (r - 1) / 2.  Rows are drawn in order: the long rows start first.
-    const long n_items = p.upper_only ? (long)p.n_rows * (N - p.row_begin) - (long)p.row_step * p.n_rows * (p.n_rows - 1) / 2 : total;
+    const long n_items = PLAN ? pa->n_pairs
+                              : p.upper_only ? (long)p.n_rows * (N - p.row_begin) - (long)p.row_step * p.n_rows * (p.n_rows - 1) / 2 : total;
     auto row_offset = [&](long r) { return r * (N - p.row_begin) - (long)p.row_step * r * (r - 1) / 2; };
     // (a wave's first item is its own number -- no burst of atomics on one address at the start of a small grid --, the
     // following ones come from the counter, which starts behind the resident waves)
@@ -322,7 +339,9 @@ __global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_kern
         }
         q_tries = 0;
         int r, j_s;
-        if (p.upper_only) {
+        if constexpr (PLAN) {
+            r = 0; j_s = uni_i32(pa->pair_j[t]);
+        } else if (p.upper_only) {
             const double a = 0.5 * p.row_step, b = (double)(N - p.row_begin) + a;      // offset(r) = b r - a r^2
             const double disc = b * b - 4.0 * a * (double)t;
             long rr = (long)((b - __builtin_sqrt(disc > 0.0 ? disc : 0.0)) / (2.0 * a));
@@ -334,8 +353,8 @@ __global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_kern
         } else {
             r = (int)(t / N); j_s = (int)(t % N);
         }
-        const long q = (long)r * N + j_s;
-        const int i_s = p.row_begin + r * p.row_step;
+        const long q = PLAN ? t : (long)r * N + j_s;
+        const int i_s = PLAN ? uni_i32(pa->pair_i[t]) : p.row_begin + r * p.row_step;
 #ifdef EMD_PROF
         long long prof_t0 = 0, prof_acc = 0;
 #endif
@@ -817,7 +836,13 @@ __global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_kern
                     const int j = __builtin_ctzll(m) + 64 * w;
                     m &= m - 1ull;
                     // (one fused multiply-add per arc in either form: the two forms give the same bits)
-                    cost = __builtin_fma(F[(size_t)idx * K + j], Mrd[(size_t)idx * MP + j], cost);
+                    if constexpr (PLAN) {
+                        const double f = F[(size_t)idx * K + j];
+                        cost = __builtin_fma(f, Mrd[(size_t)idx * MP + j], cost);
+                        pa->plans[((size_t)q * K + idx) * K + j] = f;
+                    } else {
+                        cost = __builtin_fma(F[(size_t)idx * K + j], Mrd[(size_t)idx * MP + j], cost);
+                    }
                     F[(size_t)idx * K + j] = 0.0;           // the slab goes back to all zeros for the wave's next pair
                 }
             }
@@ -842,6 +867,7 @@ __global__ void __launch_bounds__(64 * emd_waves(NK)) EMD_WPE_ATTR emd_grid_kern
     }
 }
 
+#ifndef PILOT_PLAN_TU
 // mirror the strictly-lower triangle from the upper one (full square grids only)
 __global__ void emd_mirror_kernel(double *E, int N) {
     const long total = (long)N * N;
@@ -850,5 +876,6 @@ __global__ void emd_mirror_kernel(double *E, int N) {
         if (j < i) E[t] = E[(size_t)j * N + i];
     }
 }
+#endif
 
 }  // namespace pilot

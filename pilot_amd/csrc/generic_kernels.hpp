@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "plan_args.hpp"
+
 namespace pilot {
 
 struct GenericParams {
@@ -63,7 +65,18 @@ __device__ inline double block_reduce_max(double x, double *red) {
     return s;
 }
 
+// PILOT_PLAN_TU (pilot_ot_plans.hip): sinkhorn_generic_plan_kernel, the same source with pairs from the list in `pa` (p.list is
+// not read), results at the item's index, and the final pass also storing POT's get_Gamma entry by entry into the pair's K x K
+// block of pa.plans (see emd_grid_kernel in emd_kernels.hpp for why it is one source under two signatures)
+#ifndef PILOT_PLAN_TU
 static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_kernel(GenericParams p) {
+    constexpr bool PLAN = false;
+    const PlanArgs *pa = nullptr;
+#else
+static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_plan_kernel(GenericParams p, PlanArgs plan_args) {
+    constexpr bool PLAN = true;
+    const PlanArgs *pa = &plan_args;
+#endif
     extern __shared__ double sm[];
     const int K = p.K, N = p.N;
     double *a = sm, *b = a + K, *u = b + K, *v = u + K, *up = v + K, *vp = up + K, *alpha = vp + K, *beta = alpha + K;
@@ -87,9 +100,9 @@ static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_kernel(Gen
         __syncthreads();
         const int item = qs[0];
         __syncthreads();
-        if (item >= (p.list_len ? *p.list_len : p.n_pairs)) break;
-        const int q = p.list ? p.list[item] : item;
-        const int i_s = p.row_begin + (q / N) * p.row_step, j_s = q % N;
+        if (item >= (PLAN ? pa->n_pairs : (p.list_len ? *p.list_len : p.n_pairs))) break;
+        const int q = PLAN ? item : p.list ? p.list[item] : item;
+        const int i_s = PLAN ? pa->pair_i[item] : p.row_begin + (q / N) * p.row_step, j_s = PLAN ? pa->pair_j[item] : q % N;
         for (int k = threadIdx.x; k < K; k += GENERIC_WG) {
             a[k] = p.P[(size_t)i_s * K + k]; b[k] = p.P[(size_t)j_s * K + k];
             alpha[k] = 0.0; beta[k] = 0.0; u[k] = 1.0 / K; v[k] = 1.0 / K;
@@ -179,7 +192,13 @@ static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_kernel(Gen
         double val = 0.0;
         for (int t = threadIdx.x; t < K * K; t += GENERIC_WG) {
             const int i = t / K, j = t % K;
-            val += p.M[t] * exp(-(p.M[t] - alpha[i] - beta[j]) / reg + log(u[i]) + log(v[j]));
+            if constexpr (PLAN) {
+                const double g = exp(-(p.M[t] - alpha[i] - beta[j]) / reg + log(u[i]) + log(v[j]));
+                pa->plans[(size_t)q * K * K + t] = g;
+                val += p.M[t] * g;
+            } else {
+                val += p.M[t] * exp(-(p.M[t] - alpha[i] - beta[j]) / reg + log(u[i]) + log(v[j]));
+            }
         }
         val = block_reduce_sum(val, red);
         if (threadIdx.x == 0) {

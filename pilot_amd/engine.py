@@ -490,6 +490,63 @@ def emd_grid(P, M, row_begin=0, row_end=None, row_step=1, mode="auto", return_in
     return emd
 
 
+def transport_plans(P, M, pairs, regularized="unreg", reg=0.1, groups=None, return_info=False,
+                    num_iter_max=NUM_ITER_MAX, stop_thr=STOP_THR, tau=TAU, check_period=CHECK_PERIOD):
+    """Optimal couplings Gamma (K x K) of the ordered pairs ``pairs`` (extension: POT's ``ot.emd`` / ``ot.sinkhorn``
+    return them, the pair grid keeps only <M, Gamma>).  Rows of a plan are the cell types of ``P[i]``, columns those of
+    ``P[j]``.
+
+    regularized == "unreg": the plan of ``ot.emd(a, b * sum(a) / sum(b), M)`` -- *an* optimum: the LP's value is unique,
+    its plan need not be.  Anything else: ``ot.sinkhorn(a, b, M, reg, method="sinkhorn_stabilized")`` in f64, POT's
+    loop step by step (the kernel of ``sinkhorn_grid(precision="generic")``), whatever precision a grid would run in.
+
+    pairs : (n, 2) int array of (i, j).  groups : optional int array of length n; with it the result is (G, K, K),
+    G = max(groups) + 1, the sum of the plans of each group's pairs added in list order (bit-reproducible); without it
+    (n, K, K).  ``return_info`` adds a dict: values (<M, Gamma> per pair, what the pair grid returns), iters (exact:
+    augmentations; entropic: iterations) and flags (entropic: the PILOT_OT_FLAG_* bits of the grid; exact: 0).
+    """
+    P = _as_f64(P, "P")
+    M = _as_f64(M, "M")
+    if P.ndim != 2 or M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] != P.shape[1]:
+        raise ValueError("shape mismatch: P %s, M %s" % (P.shape, M.shape))
+    N, K = P.shape
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        pairs = pairs.reshape(0, 2)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError("pairs must be an (n, 2) integer array, got %s %s" % (pairs.shape, pairs.dtype))
+    n = pairs.shape[0]
+    if n and (pairs.min() < -2**31 or pairs.max() >= 2**31):
+        raise ValueError("pair index out of range for N=%d" % N)
+    pi = np.ascontiguousarray(pairs[:, 0], dtype=np.int32)
+    pj = np.ascontiguousarray(pairs[:, 1], dtype=np.int32)
+    if groups is not None:
+        groups = np.asarray(groups)
+        if groups.shape != (n,) or not np.issubdtype(groups.dtype, np.integer):
+            raise ValueError("groups must be an integer array of length %d, got %s %s" % (n, groups.shape, groups.dtype))
+        if n and (groups.min() < -2**31 or groups.max() >= 2**31 - 1):
+            raise ValueError("group id out of range")
+        G = max(int(groups.max()) + 1, 1) if n else 0
+        gp = np.ascontiguousarray(groups, dtype=np.int32)
+        plans = np.zeros((G, K, K), dtype=np.float64)
+    else:
+        G, gp = 0, None
+        plans = np.zeros((n, K, K), dtype=np.float64)
+    values = np.zeros(n, dtype=np.float64)
+    iters = np.zeros(n, dtype=np.int32)
+    flags = np.zeros(n, dtype=np.int32)
+    exact = regularized == "unreg"
+    _lib.check(_lib.load().pilot_ot_transport_plans(
+        _lib.dptr(P), N, K, _lib.dptr(M), 0 if exact else 1, float(reg), int(num_iter_max), float(stop_thr), float(tau),
+        int(check_period), _lib.iptr(pi), _lib.iptr(pj), n, None if gp is None else _lib.iptr(gp), max(G, 1),
+        _lib.dptr(plans), _lib.dptr(values), _lib.iptr(iters), _lib.iptr(flags)))
+    if exact and (iters < 0).any():
+        raise _lib.PilotOTError("exact-EMD kernel: augmentation guard tripped on %d pairs" % int((iters < 0).sum()))
+    if return_info:
+        return plans, dict(values=values, iters=iters, flags=flags)
+    return plans
+
+
 # ---- consumers of the finished matrix (SURVEY.md section 8 f-4) ------------------------------------------------------------
 def row_distances(E, metric="euclidean", normalize_by_max=False):
     """Distances between the ROWS of the N x N matrix E (of E / E.max() with ``normalize_by_max``) on the device: the points

@@ -479,6 +479,63 @@ def wasserstein_distance(adata, emb_matrix="X_PCA", clusters_col="cell_types", s
     adata.uns["real_labels"] = real_labels
 
 
+def _plan_inputs(adata):
+    """P (samples in uns['proportions'] order), the cost handed to the pair loop (uns['cost'] / its max, Trajectory.py:101)
+    and the cell-type labels, from what wasserstein_distance left in adata.uns."""
+    uns = adata.uns
+    if "proportions" not in uns or "cost" not in uns:
+        raise ValueError("adata.uns has no 'proportions' / 'cost': run wasserstein_distance first")
+    samples = list(uns["proportions"].keys())
+    P = np.stack([np.asarray(uns["proportions"][s], dtype=np.float64) for s in samples])
+    cost_df = uns["cost"]
+    cost = np.asarray(cost_df, dtype=np.float64)
+    return samples, P, cost / cost.max(), list(cost_df.index), list(cost_df.columns)
+
+
+def transport_plans(adata, pairs, regularized="unreg", reg=0.1):
+    """Optimal couplings of sample pairs: how much of each cell type of the source sample moves to each cell type of the
+    target.  EXTENSION, not in pilotpy (its pair loop keeps only the value of ``ot.emd`` / ``ot.sinkhorn``).
+
+    Uses what ``wasserstein_distance`` left in ``adata.uns`` and writes nothing to it.  ``pairs``: list of
+    (source sampleID, target sampleID).  The cost is ``uns['cost'] / uns['cost'].max()``, the one the pair loop gets
+    (Trajectory.py:101).  ``regularized == "unreg"``: an exact optimal plan (the optimum's value is unique, its plan need not
+    be); otherwise POT's ``sinkhorn_stabilized`` plan in f64 with ``reg``.  Returns a list of K x K DataFrames, index = the
+    source's cell types, columns = the target's, in ``uns['cost']`` order; <cost / max, plan> is ``uns['EMD']`` at the pair.
+    """
+    samples, P, M, rows, cols = _plan_inputs(adata)
+    where = {s: k for k, s in enumerate(samples)}
+    try:
+        idx = np.array([(where[a], where[b]) for a, b in pairs], dtype=np.int64).reshape(-1, 2)
+    except KeyError as e:
+        raise ValueError("unknown sampleID %r" % (e.args[0],)) from None
+    plans = engine.transport_plans(P, M, idx, regularized=regularized, reg=reg)
+    return [pd.DataFrame(G, index=list(rows), columns=list(cols)) for G in plans]
+
+
+def group_transport(adata, source, target, regularized="unreg", reg=0.1):
+    """Mean optimal coupling from the samples of status ``source`` to those of status ``target``: the mean of the plans of
+    every ordered pair (i, j), i of status ``source``, j of status ``target`` (statuses from ``uns['real_labels']``).
+    EXTENSION, not in pilotpy.
+
+    Writes nothing to ``adata.uns``.  Plans as in ``transport_plans``; the sum runs on the device in a fixed order (the
+    result is the same bits on every run).  Rows sum to the mean source proportions; columns to the mean target proportions
+    (exactly so for exact plans of equal-mass samples).  Returns a K x K DataFrame labelled like ``transport_plans``'.
+    A status without samples raises ValueError.
+    """
+    samples, P, M, rows, cols = _plan_inputs(adata)
+    labels = np.asarray(adata.uns["real_labels"], dtype=object)
+    if len(labels) != len(samples):
+        raise ValueError("uns['real_labels'] has %d entries for %d samples" % (len(labels), len(samples)))
+    src = np.flatnonzero(labels == source)
+    dst = np.flatnonzero(labels == target)
+    for name, sel in ((source, src), (target, dst)):
+        if sel.size == 0:
+            raise ValueError("no sample has status %r (statuses: %s)" % (name, sorted(set(map(str, labels)))))
+    idx = np.stack(np.meshgrid(src, dst, indexing="ij"), axis=-1).reshape(-1, 2)
+    total = engine.transport_plans(P, M, idx, regularized=regularized, reg=reg, groups=np.zeros(len(idx), dtype=np.int32))[0]
+    return pd.DataFrame(total / len(idx), index=list(rows), columns=list(cols))
+
+
 def Precomputed_distance(adata, distances, cost_df, features_matrix, emb_matrix="X_PCA",
                          clusters_col="cell_types", sample_col="sampleID", status="status", data_type="scRNA"):
     """Store externally computed distances in ``adata.uns`` (Trajectory.py:1687-1727; the reference

@@ -345,6 +345,27 @@ int pilot_ot_silhouette_of_rows(const double *E, int E_is_device, int N, int nor
                                 int n_clusters, double *score, double *samples);
 int pilot_ot_diffusion_kernel_of_rows(const double *E, int E_is_device, int N, int k, double epsilon, double *D_out, double *Kmat);
 
+/* ---- diffusion map: pl.trajectory's embedding, pydiffmap's DiffusionMap.from_sklearn(n_evecs, epsilon, alpha, k)
+ * .fit_transform(E / max(E)) (pilotpy/plot/ploting.py:95-110) with a numeric epsilon, no weight function, no bandwidth
+ * normalisation.  From a non-negative N x N kernel K (e.g. what pilot_ot_knn_kernel_dev left): Ks = max(K, K^T), q = Ks.sum(1),
+ * A = diag(q^-alpha) Ks diag(q^-alpha), P = diag(1 / A.sum(1)) A, L = (P - I) / epsilon.  The n_evecs + 1 eigenpairs of L of
+ * largest real part come from a symmetric Lanczos run (full re-orthogonalisation) on the matrix similar to P; the first
+ * (lambda = 0) is dropped.  evals (n_evecs, descending): lambda of L; evecs (N x n_evecs row-major, nullable): the right
+ * eigenvectors of P, unit 2-norm, the entry of largest magnitude of each column positive (lowest index on ties); dmap
+ * (N x n_evecs row-major) = evecs * sqrt(-1 / evals).  Every row of K must have a positive sum.
+ * info[0] = Lanczos steps, info[1] = PILOT_OT_DIFFMAP_* flags.  All in f64, fixed-order sums: repeated calls give identical bits.
+ * PILOT_OT_EINVAL (before any HIP call): N < 2, n_evecs outside [1, min(N - 1, 64)], epsilon not positive and finite, alpha not
+ * finite, k < 1, a required pointer NULL.  N beyond the kNN kernel's LDS sort: PILOT_OT_ENOTSUP.
+ * _dev: device pointers, synchronises `stream` (the tridiagonal problem is solved on the host); info on the host.
+ * _of_rows: the whole chain from E (on the host, or in HBM when E_is_device): E / max(E) -> Euclidean row distances -> k-nn
+ * Gaussian kernel -> the above; dmap / evecs / evals / info on the host. */
+#define PILOT_OT_DIFFMAP_NOT_CONVERGED 1  /* the basis cap (min(N, 1024) vectors) was reached before every wanted Ritz pair converged */
+#define PILOT_OT_DIFFMAP_DEGENERATE 2     /* more than one eigenvalue mu of P with mu >= 1 - 1e-10: a (nearly) disconnected graph */
+int pilot_ot_diffusion_map_dev(const double *d_K, int N, double epsilon, double alpha, int n_evecs, double *d_dmap, double *d_evecs,
+                               double *d_evals, int *info, void *stream);
+int pilot_ot_diffusion_map_of_rows(const double *E, int E_is_device, int N, int k, double epsilon, double alpha, int n_evecs,
+                                   double *dmap, double *evecs, double *evals, int *info);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

@@ -22,6 +22,7 @@ METRICS = {"cosine": 0, "euclidean": 1, "sqeuclidean": 2, "cityblock": 3, "cheby
 
 EMD_ALL, EMD_UPPER, EMD_MIRROR = 0, 1, 2
 FLAG_CONVERGED, FLAG_NAN, FLAG_ABSORB_LAST, FLAG_ABSORBED, FLAG_F64 = 1, 2, 4, 8, 16
+DIFFMAP_NOT_CONVERGED, DIFFMAP_DEGENERATE = 1, 2
 
 # every symbol include/pilot_ot.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -38,6 +39,7 @@ SYMBOLS = [
     "pilot_ot_mirror_upper_dev", "pilot_ot_transport_plans",
     "pilot_ot_row_distances", "pilot_ot_row_distances_dev", "pilot_ot_silhouette", "pilot_ot_knn_kernel",
     "pilot_ot_silhouette_dev", "pilot_ot_knn_kernel_dev", "pilot_ot_silhouette_of_rows", "pilot_ot_diffusion_kernel_of_rows",
+    "pilot_ot_diffusion_map_dev", "pilot_ot_diffusion_map_of_rows",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -129,6 +131,8 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_knn_kernel_dev.argtypes = [c_vp, c_int, c_int, c_dbl, c_vp, c_vp]
     L.pilot_ot_silhouette_of_rows.argtypes = [c_vp, c_int, c_int, c_int, c_int, ip, c_int, dp, dp]
     L.pilot_ot_diffusion_kernel_of_rows.argtypes = [c_vp, c_int, c_int, c_int, c_dbl, dp, dp]
+    L.pilot_ot_diffusion_map_dev.argtypes = [c_vp, c_int, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ip, c_vp]
+    L.pilot_ot_diffusion_map_of_rows.argtypes = [c_vp, c_int, c_int, c_int, c_dbl, c_dbl, c_int, dp, dp, dp, ip]
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

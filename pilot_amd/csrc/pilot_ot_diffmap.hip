@@ -1,0 +1,233 @@
+// C ABI of the diffusion map (include/pilot_ot.h, section "diffusion map"; kernels: diffmap_kernels.hpp).  The eigen-part of
+// pl.trajectory (pilotpy/plot/ploting.py:109-110) on the device: symmetrised, alpha-normalised kNN kernel -> symmetric Lanczos with
+// full re-orthogonalisation -> Ritz vectors -> pydiffmap's diffusion coordinates.  The tridiagonal Ritz problem is solved here on
+// the host (implicit QL), so the entry points synchronise their stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+#include <numeric>
+#include <vector>
+
+#include "abi_common.hpp"
+#include "diffmap_kernels.hpp"
+
+#define fail(...) pilot::abi_fail(__VA_ARGS__)
+
+namespace {
+
+constexpr int MAX_BASIS = 1024;         // B = min(N, MAX_BASIS) Lanczos vectors (V: B x N f64)
+constexpr int MAX_EVECS = 64;
+constexpr int CHECK_EVERY = 8;          // Lanczos steps between two looks at the tridiagonal problem
+constexpr double RESID_TOL = 1e-12;     // |beta_j s_ji| of every wanted Ritz pair
+constexpr double BREAKDOWN_TOL = 1e-12; // |w| after re-orthogonalisation below which the Krylov space counts as invariant (|S| = 1)
+constexpr double DEGENERATE_MU = 1.0 - 1e-10;
+
+// temporaries: slots 36 .. 47 of the calling thread's pool (no hipMalloc / hipFree per call)
+template <typename T> hipError_t ws(int slot, size_t n, T **p) {
+    void *v = nullptr;
+    const hipError_t e = pilot::ws_buffer(slot, sizeof(T) * (n ? n : 1), &v);
+    *p = static_cast<T *>(v);
+    return e;
+}
+
+// Implicit QL with Wilkinson shifts on the symmetric tridiagonal matrix with diagonal d[0..n) and off-diagonal e[0..n-1)
+// (e[i] couples i and i + 1; e must have n entries, e[n-1] is scratch).  Eigenvalues overwrite d (unsorted); every rotation is
+// applied to the nrows rows of z (row-major nrows x n): start from the identity for the eigenvectors as columns, or from the
+// last unit row alone for just their last components.  false if an eigenvalue needed more than 60 iterations.
+bool tridiag_ql(int n, double *d, double *e, double *z, int nrows) {
+    e[n - 1] = 0.0;
+    for (int l = 0; l < n; ++l) {
+        int iter = 0, m;
+        do {
+            for (m = l; m < n - 1; ++m)
+                if (std::fabs(e[m]) <= DBL_EPSILON * (std::fabs(d[m]) + std::fabs(d[m + 1]))) break;
+            if (m == l) break;
+            if (++iter > 60) return false;
+            double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+            double r = std::hypot(g, 1.0);
+            g = d[m] - d[l] + e[l] / (g + std::copysign(r, g));          // the shift: the eigenvalue of the leading 2 x 2 nearer d[l]
+            double s = 1.0, c = 1.0, p = 0.0;
+            int i;
+            for (i = m - 1; i >= l; --i) {
+                double f = s * e[i];
+                const double b = c * e[i];
+                r = std::hypot(f, g);
+                e[i + 1] = r;
+                if (r == 0.0) { d[i + 1] -= p; e[m] = 0.0; break; }   // (underflow: the block splits, sweep again)
+                s = f / r;
+                c = g / r;
+                g = d[i + 1] - p;
+                r = (d[i] - g) * s + 2.0 * c * b;
+                p = s * r;
+                d[i + 1] = g + p;
+                g = c * r - b;
+                for (int k = 0; k < nrows; ++k) {
+                    double *zk = z + (size_t)k * n;
+                    f = zk[i + 1];
+                    zk[i + 1] = s * zk[i] + c * f;
+                    zk[i] = c * zk[i] - s * f;
+                }
+            }
+            if (r == 0.0 && i >= l) continue;
+            d[l] -= p;
+            e[l] = g;
+            e[m] = 0.0;
+        } while (true);
+    }
+    return true;
+}
+
+// indices of d sorted by value, largest first (ties: lower index first)
+std::vector<int> order_desc(const std::vector<double> &d) {
+    std::vector<int> ix(d.size());
+    std::iota(ix.begin(), ix.end(), 0);
+    std::stable_sort(ix.begin(), ix.end(), [&](int a, int b) { return d[a] > d[b]; });
+    return ix;
+}
+
+int check_args(int N, double epsilon, double alpha, int n_evecs) {
+    if (N < 2) return fail(PILOT_OT_EINVAL, "N=%d: a diffusion map needs at least 2 points", N);
+    const int cap = std::min(N - 1, MAX_EVECS);
+    if (n_evecs < 1 || n_evecs > cap) return fail(PILOT_OT_EINVAL, "n_evecs=%d outside [1, min(N - 1, %d)] = [1, %d]", n_evecs, MAX_EVECS, cap);
+    if (!(epsilon > 0.0) || !std::isfinite(epsilon)) return fail(PILOT_OT_EINVAL, "epsilon=%g must be positive and finite", epsilon);
+    if (!std::isfinite(alpha)) return fail(PILOT_OT_EINVAL, "alpha=%g must be finite", alpha);
+    return PILOT_OT_OK;
+}
+
+}  // namespace
+
+PILOT_API int pilot_ot_diffusion_map_dev(const double *d_K, int N, double epsilon, double alpha, int n_evecs, double *d_dmap,
+                                         double *d_evecs, double *d_evals, int *info, void *stream) {
+    if (!d_K || !d_dmap || !d_evals || !info) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    int rc = check_args(N, epsilon, alpha, n_evecs);
+    if (rc != PILOT_OT_OK) return rc;
+    info[0] = 0;
+    info[1] = 0;
+    const int m = n_evecs + 1;                                 // wanted Ritz pairs: the trivial mu = 1 and n_evecs more
+    int B = std::min(N, MAX_BASIS);
+    if (const char *sw = pilot::test_switch("PILOT_OT_DIFFMAP_BASIS")) {      // (tests: a basis too small to converge)
+        const int b = atoi(sw);
+        if (b > 0 && b < B) B = b;
+    }
+    B = std::max(B, m);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+
+    double *S, *V, *vec, *Zs, *psi;
+    HIP_TRY(ws(36, (size_t)N * N, &S));
+    HIP_TRY(ws(37, (size_t)B * N, &V));
+    HIP_TRY(ws(38, 5 * (size_t)N + 4 * (size_t)B + 1, &vec));
+    HIP_TRY(ws(39, (size_t)B * n_evecs + n_evecs, &Zs));
+    HIP_TRY(ws(40, (size_t)N * n_evecs, &psi));
+    double *w = vec, *qa = w + N, *wsc = qa + N, *dis = wsc + N, *phi = dis + N;
+    double *h1 = phi + N, *h2 = h1 + B, *al = h2 + B, *be = al + B;
+    int *n_restart = reinterpret_cast<int *>(be + B);
+
+    // S from K (K itself is only read)
+    const unsigned tg = (unsigned)((N + pilot::DM_TILE - 1) / pilot::DM_TILE);
+    hipLaunchKernelGGL(pilot::dm_symmetrize_kernel, dim3(tg, tg), dim3(pilot::DM_TILE, 8), 0, s, d_K, N, S);
+    hipLaunchKernelGGL(pilot::dm_row_kernel, dim3(N), dim3(pilot::DM_RED), 0, s, S, N, 0, alpha, qa, wsc, dis, phi);
+    hipLaunchKernelGGL(pilot::dm_row_kernel, dim3(N), dim3(pilot::DM_RED), 0, s, S, N, 1, alpha, qa, wsc, dis, phi);
+    const size_t nn = (size_t)N * N;
+    const unsigned sb = (unsigned)std::min<size_t>((nn + 255) / 256, 4096);
+    hipLaunchKernelGGL(pilot::dm_scale_kernel, dim3(sb), dim3(256), 0, s, S, N, wsc);
+    hipLaunchKernelGGL(pilot::lz_start_kernel, dim3(1), dim3(pilot::DM_FIN), 0, s, phi, N, V);
+    HIP_TRY(hipMemsetAsync(n_restart, 0, sizeof(int), s));
+    HIP_TRY(hipGetLastError());
+
+    // Lanczos: step j extends the basis V[0..j] by V[j + 1]; every CHECK_EVERY steps T is read back and its Ritz pairs tested
+    std::vector<double> ha(B), hb(B), d, e, z;
+    int steps = 0, next_check = m;
+    bool converged = false;
+    while (steps < B) {
+        const int j = steps, nk = j + 1;
+        const double *vj = V + (size_t)j * N;
+        hipLaunchKernelGGL(pilot::lz_gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, s, S, N, vj, w);
+        hipLaunchKernelGGL(pilot::lz_dots_kernel, dim3(nk), dim3(pilot::DM_RED), 0, s, V, N, w, h1);
+        hipLaunchKernelGGL(pilot::lz_update_kernel, dim3((N + 63) / 64), dim3(64 * pilot::LZ_UPD_WAVES), 0, s, V, N, nk, h1, w);
+        hipLaunchKernelGGL(pilot::lz_dots_kernel, dim3(nk), dim3(pilot::DM_RED), 0, s, V, N, w, h2);
+        hipLaunchKernelGGL(pilot::lz_update_kernel, dim3((N + 63) / 64), dim3(64 * pilot::LZ_UPD_WAVES), 0, s, V, N, nk, h2, w);
+        hipLaunchKernelGGL(pilot::lz_finish_kernel, dim3(1), dim3(pilot::DM_FIN), 0, s, V, N, j, B, w, h1, h2, BREAKDOWN_TOL, al, be,
+                           n_restart);
+        HIP_TRY(hipGetLastError());
+        steps = nk;
+        if (steps < next_check && steps < B) continue;
+        next_check = steps + CHECK_EVERY;
+        HIP_TRY(hipMemcpyAsync(ha.data(), al, sizeof(double) * steps, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(hb.data(), be, sizeof(double) * steps, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (steps == N) { converged = true; break; }           // a complete basis: T is similar to S
+        // a breakdown after step 0 (step 0 always breaks down: V[0] is an eigenvector) means the Krylov space of a restart
+        // vector was exhausted; what lies outside it is unexplored, so only a complete basis is accepted from then on
+        bool late_breakdown = false;
+        for (int k = 1; k < steps; ++k) late_breakdown |= hb[k] == 0.0;
+        if (late_breakdown) continue;
+        d.assign(ha.begin(), ha.begin() + steps);
+        e.assign(hb.begin(), hb.begin() + steps);
+        z.assign(steps, 0.0);
+        z[steps - 1] = 1.0;
+        if (!tridiag_ql(steps, d.data(), e.data(), z.data(), 1)) continue;
+        const std::vector<int> ix = order_desc(d);
+        bool ok = true;
+        for (int c = 0; c < m; ++c) ok &= std::fabs(hb[steps - 1] * z[ix[c]]) <= RESID_TOL;
+        if (ok) { converged = true; break; }
+    }
+
+    // the Ritz pairs of the final basis: eigenvectors of T as columns
+    const int nk = steps;
+    d.assign(ha.begin(), ha.begin() + nk);
+    e.assign(hb.begin(), hb.begin() + nk);
+    z.assign((size_t)nk * nk, 0.0);
+    for (int k = 0; k < nk; ++k) z[(size_t)k * nk + k] = 1.0;
+    if (!tridiag_ql(nk, d.data(), e.data(), z.data(), nk)) return fail(PILOT_OT_EHIP, "tridiagonal QL did not converge (%d steps)", nk);
+    const std::vector<int> ix = order_desc(d);
+    int n_one = 0;
+    for (int k = 0; k < nk; ++k) n_one += d[k] >= DEGENERATE_MU;
+    std::vector<double> zs((size_t)nk * n_evecs + n_evecs);
+    for (int c = 0; c < n_evecs; ++c) {                        // drop the first (mu = 1, lambda = 0): pydiffmap's evecs[:, 1:]
+        const int col = ix[c + 1];
+        for (int k = 0; k < nk; ++k) zs[(size_t)k * n_evecs + c] = z[(size_t)k * nk + col];
+        zs[(size_t)nk * n_evecs + c] = (d[col] - 1.0) / epsilon;      // lambda of L = (P - I) / epsilon
+    }
+    double *lam_dev = Zs + (size_t)nk * n_evecs;                   // (Z: nk x n_evecs, then the n_evecs lambdas)
+    HIP_TRY(hipMemcpyAsync(Zs, zs.data(), sizeof(double) * zs.size(), hipMemcpyHostToDevice, s));
+    const long nt = (long)N * n_evecs;
+    hipLaunchKernelGGL(pilot::lz_ritz_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, V, N, nk, Zs, n_evecs, dis, psi);
+    hipLaunchKernelGGL(pilot::dm_finalize_kernel, dim3(n_evecs), dim3(pilot::DM_RED), 0, s, psi, N, n_evecs, lam_dev, d_dmap, d_evecs);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d_evals, lam_dev, sizeof(double) * n_evecs, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    info[0] = steps;
+    info[1] = (converged ? 0 : PILOT_OT_DIFFMAP_NOT_CONVERGED) | (n_one > 1 ? PILOT_OT_DIFFMAP_DEGENERATE : 0);
+    return PILOT_OT_OK;
+}
+
+// pl.trajectory's embedding from E (ploting.py:95-110): E / max(E) -> Euclidean row distances -> k-nn Gaussian kernel (K7) -> the
+// diffusion map above.  E on the host or (E_is_device) already in HBM; dmap / evecs (nullable) / evals / info on the host.
+PILOT_API int pilot_ot_diffusion_map_of_rows(const double *E, int E_is_device, int N, int k, double epsilon, double alpha, int n_evecs,
+                                             double *dmap, double *evecs, double *evals, int *info) {
+    if (!E || !dmap || !evals || !info) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    int rc = check_args(N, epsilon, alpha, n_evecs);
+    if (rc != PILOT_OT_OK) return rc;
+    if (k < 1) return fail(PILOT_OT_EINVAL, "k=%d must be positive", k);
+    const size_t nn = (size_t)N * N, no = (size_t)N * n_evecs;
+    double *dE = nullptr, *dD, *dK, *dM, *dOut;
+    HIP_TRY(ws(42, nn, &dD));
+    HIP_TRY(ws(43, nn, &dK));
+    HIP_TRY(ws(44, 1, &dM));
+    HIP_TRY(ws(45, 2 * no + n_evecs, &dOut));
+    if (!E_is_device) {
+        HIP_TRY(ws(41, nn, &dE));
+        HIP_TRY(hipMemcpy(dE, E, sizeof(double) * nn, hipMemcpyHostToDevice));
+    }
+    rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);
+    if (rc == PILOT_OT_OK) rc = pilot_ot_knn_kernel_dev(dD, N, k, epsilon, dK, nullptr);
+    if (rc == PILOT_OT_OK) rc = pilot_ot_diffusion_map_dev(dK, N, epsilon, alpha, n_evecs, dOut, dOut + no, dOut + 2 * no, info, nullptr);
+    if (rc != PILOT_OT_OK) return rc;
+    HIP_TRY(hipMemcpy(dmap, dOut, sizeof(double) * no, hipMemcpyDeviceToHost));
+    if (evecs) HIP_TRY(hipMemcpy(evecs, dOut + no, sizeof(double) * no, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(evals, dOut + 2 * no, sizeof(double) * n_evecs, hipMemcpyDeviceToHost));
+    return PILOT_OT_OK;
+}

@@ -641,3 +641,94 @@ def knn_gaussian_kernel(D, k=64, epsilon=1.0):
     Kmat = np.empty_like(D)
     _lib.check(_lib.load().pilot_ot_knn_kernel(_lib.dptr(D), D.shape[0], int(k), float(epsilon), _lib.dptr(Kmat)))
     return Kmat
+
+
+# ---- diffusion map (pl.trajectory's embedding, pilotpy/plot/ploting.py:95-110) ---------------------------------------------
+def _diffmap_check(N, n_evecs, epsilon, alpha):
+    """pydiffmap's epsilon may be a bandwidth-selection rule ('bgh', 'bgh_generous'); only a number is implemented.  The numeric
+    ranges are the library's (PILOT_OT_EINVAL), checked here too so a host kernel is refused before it is uploaded."""
+    if isinstance(epsilon, (str, bytes)) or isinstance(epsilon, bool) or not np.isscalar(epsilon) or not np.isreal(epsilon):
+        raise NotImplementedError("epsilon=%r: only a numeric epsilon is implemented (no bandwidth selection)" % (epsilon,))
+    epsilon, alpha = float(epsilon), float(alpha)
+    if N < 2:
+        raise ValueError("a diffusion map needs at least 2 points, got N=%d" % N)
+    if not 1 <= int(n_evecs) <= min(N - 1, 64):
+        raise ValueError("n_evecs=%d outside [1, min(N - 1, 64)]" % n_evecs)
+    if not (epsilon > 0.0 and np.isfinite(epsilon)):
+        raise ValueError("epsilon=%g must be positive and finite" % epsilon)
+    if not np.isfinite(alpha):
+        raise ValueError("alpha=%g must be finite" % alpha)
+    return int(n_evecs), epsilon, alpha
+
+
+def _diffmap_result(dmap, evecs, evals, info, return_info):
+    steps, flags = int(info[0]), int(info[1])
+    out = dict(steps=steps, flags=flags, converged=not flags & _lib.DIFFMAP_NOT_CONVERGED,
+               degenerate=bool(flags & _lib.DIFFMAP_DEGENERATE))
+    if return_info:
+        return dmap, evecs, evals, out
+    if flags & _lib.DIFFMAP_DEGENERATE:
+        raise ValueError("diffusion map: eigenvalue 1 of the Markov matrix is repeated (a disconnected neighbour graph)")
+    if flags & _lib.DIFFMAP_NOT_CONVERGED:
+        raise ValueError("diffusion map: Lanczos did not converge in %d steps" % steps)
+    return dmap, evecs, evals
+
+
+def diffusion_map_of_rows(E, n_evecs=2, epsilon=1.0, alpha=0.5, k=64, return_info=False):
+    """pl.trajectory's embedding (pilotpy/plot/ploting.py:95-110) on the device: pydiffmap's
+    ``DiffusionMap.from_sklearn(n_evecs, epsilon, alpha, k).fit_transform(E / E.max())`` -- row distances, k-nearest-neighbour
+    Gaussian kernel, alpha-normalised Markov matrix, its leading eigenpairs (Lanczos) and the diffusion coordinates.
+    E: numpy array or :class:`DeviceMatrix`.  Returns ``(dmap, evecs, evals)``: N x n_evecs, N x n_evecs, n_evecs (eigenvalues
+    of (P - I) / epsilon, descending, the trivial 0 dropped).  A repeated eigenvalue 1 (disconnected graph) or no convergence
+    raises ValueError; with ``return_info`` nothing is raised and a fourth item, ``dict(steps, flags, converged, degenerate)``,
+    tells."""
+    ptr, on_dev, N, keep = _matrix_arg(E)
+    n_evecs, epsilon, alpha = _diffmap_check(N, n_evecs, epsilon, alpha)
+    dmap = np.empty((N, n_evecs), dtype=np.float64)
+    evecs = np.empty((N, n_evecs), dtype=np.float64)
+    evals = np.empty(n_evecs, dtype=np.float64)
+    info = np.zeros(2, dtype=np.int32)
+    _lib.check(_lib.load().pilot_ot_diffusion_map_of_rows(ptr, on_dev, N, int(k), epsilon, float(alpha), n_evecs, _lib.dptr(dmap),
+                                                          _lib.dptr(evecs), _lib.dptr(evals), _lib.iptr(info)))
+    return _diffmap_result(dmap, evecs, evals, info, return_info)
+
+
+def diffusion_map_from_kernel(Kmat, n_evecs=2, epsilon=1.0, alpha=0.5, return_info=False):
+    """The eigen-part of the diffusion map from a non-negative N x N kernel matrix (numpy array or :class:`DeviceMatrix`), e.g.
+    :func:`knn_gaussian_kernel`'s: symmetrised max(K, K^T), alpha-normalised, Lanczos on the device.  Same returns as
+    :func:`diffusion_map_of_rows`."""
+    on_dev = isinstance(Kmat, DeviceMatrix)
+    N = Kmat.N if on_dev else np.asarray(Kmat).shape[0]
+    if not on_dev:
+        Kmat = _as_f64(Kmat, "Kmat")
+        if Kmat.ndim != 2 or Kmat.shape[0] != Kmat.shape[1]:
+            raise ValueError("Kmat must be square, got %s" % (Kmat.shape,))
+    n_evecs, epsilon, alpha = _diffmap_check(N, n_evecs, epsilon, alpha)
+    L = _lib.load()
+    bufs = []
+
+    def alloc(nbytes):
+        p = ctypes.c_void_p()
+        _lib.check(L.pilot_ot_dev_alloc(ctypes.byref(p), int(nbytes)))
+        bufs.append(p)
+        return p
+
+    try:
+        if on_dev:
+            dK = ctypes.c_void_p(Kmat.ptr)
+        else:
+            dK = alloc(Kmat.nbytes)
+            _lib.check(L.pilot_ot_memcpy_h2d(dK, Kmat.ctypes.data, Kmat.nbytes))
+        dmap = np.empty((N, n_evecs), dtype=np.float64)
+        evecs = np.empty((N, n_evecs), dtype=np.float64)
+        evals = np.empty(n_evecs, dtype=np.float64)
+        info = np.zeros(2, dtype=np.int32)
+        d_dmap, d_evecs, d_evals = alloc(dmap.nbytes), alloc(evecs.nbytes), alloc(evals.nbytes)
+        _lib.check(L.pilot_ot_diffusion_map_dev(dK, N, epsilon, alpha, n_evecs, d_dmap, d_evecs, d_evals, _lib.iptr(info), None))
+        _lib.check(L.pilot_ot_memcpy_d2h(dmap.ctypes.data, d_dmap, dmap.nbytes))
+        _lib.check(L.pilot_ot_memcpy_d2h(evecs.ctypes.data, d_evecs, evecs.nbytes))
+        _lib.check(L.pilot_ot_memcpy_d2h(evals.ctypes.data, d_evals, evals.nbytes))
+    finally:
+        for p in bufs:
+            L.pilot_ot_dev_free(p)
+    return _diffmap_result(dmap, evecs, evals, info, return_info)

@@ -19,6 +19,7 @@ return_real_labels                             Trajectory.py:617-642
 Sil_computing                                  Trajectory.py:592-612
 Precomputed_distance                           Trajectory.py:1687-1727
 diffusion_kernel                               plot/ploting.py:95-110 (the dense part of pl.trajectory)
+diffusion_map                                  plot/ploting.py:95-110 (pl.trajectory's embedding, without the plot)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -366,6 +367,24 @@ def diffusion_kernel(adata, epsilon=1, knn=64):
     rows, and pydiffmap's k-nearest-neighbour Gaussian kernel ``exp(-d^2 / (4 epsilon))``, all on the device.  Returns
     ``(EMD_normalised_row_distances, kernel_matrix)``; the eigen-decomposition stays with pydiffmap / scipy."""
     return engine.diffusion_kernel_of_rows(adata.uns["EMD"], k=knn, epsilon=epsilon)
+
+
+def diffusion_map(adata, n_evecs=2, epsilon=1, alpha=0.5, knn=64):
+    """What ``pl.trajectory`` (plot/ploting.py:95-110) stores before it plots: pydiffmap's
+    ``DiffusionMap.from_sklearn(n_evecs, epsilon, alpha, k=knn).fit_transform(EMD / EMD.max())`` in ``adata.uns['embedding']``
+    (float64, N x n_evecs, sample order), computed on the device from ``adata.uns['EMD']`` (a numpy array or an
+    ``engine.DeviceMatrix``).  Returns the embedding.  A disconnected neighbour graph (eigenvalue 1 repeated: the coordinates
+    sqrt(-1 / lambda) are meaningless) or an eigensolver that did not converge raises ValueError and leaves ``adata.uns``
+    alone.  Pseudotime (ElPiGraph) and the plot itself are not part of this."""
+    E = adata.uns["EMD"]
+    dmap, _, _, info = engine.diffusion_map_of_rows(E, n_evecs=n_evecs, epsilon=epsilon, alpha=alpha, k=knn, return_info=True)
+    if info["degenerate"]:
+        raise ValueError("diffusion map: the %d-nearest-neighbour graph of the samples is (nearly) disconnected -- eigenvalue 1 "
+                         "of the Markov matrix is repeated; raise knn" % knn)
+    if not info["converged"]:
+        raise ValueError("diffusion map: the eigensolver did not converge in %d Lanczos steps" % info["steps"])
+    adata.uns["embedding"] = dmap
+    return dmap
 
 
 def wasserstein_distance(adata, emb_matrix="X_PCA", clusters_col="cell_types", sample_col="sampleID",

@@ -1,0 +1,202 @@
+"""Diffusion map on the device (K8: pilot_ot_diffusion_map_dev / _of_rows, engine.diffusion_map_*, tl.diffusion_map) against the
+numpy / scipy restatement of pydiffmap (tests/diffmap_restatement.py) and a dense eigensolver."""
+import numpy as np
+import pytest
+
+import diffmap_restatement as R
+from conftest import GOLDEN_REAL, golden_adata, load_golden
+from pilot_amd import _lib, engine, tl
+from pilot_amd.synthetic import CONFIGS, make_problem
+
+pytestmark = pytest.mark.gpu
+
+GAP = 1e-4          # eigenvectors are compared only where mu is this far from its neighbours (asserted, never skipped)
+
+
+@pytest.fixture(scope="module")
+def kidney():
+    """The reference test's own cohort at PILOT's defaults: all 634 rows of its exact matrix (the fixture stores every third)."""
+    g = load_golden(GOLDEN_REAL)
+    ad, cell_col = golden_adata(g)
+    tl.wasserstein_distance(ad, clusters_col=cell_col, sample_col="sampleID", status="status", data_type="Pathomics")
+    assert np.abs(ad.uns["EMD"][::int(g["row_step"])] - g["emd_unreg"]).max() <= 1e-12
+    return ad
+
+
+@pytest.fixture(scope="module")
+def matrices(kidney):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            if name == "c1":
+                cache[name] = load_golden("c1_20x10x10")["emd_unreg"]
+            elif name == "kidney":
+                cache[name] = kidney.uns["EMD"]
+            else:
+                cache[name] = engine.emd_grid(*make_problem(**CONFIGS[name]))
+        return cache[name]
+    return get
+
+
+def column_gaps(mu, n_evecs):
+    """distance of mu[c + 1] (the c-th returned pair) to its neighbours in the descending spectrum"""
+    out = []
+    for c in range(n_evecs):
+        lo = mu[c + 1] - mu[c + 2] if c + 2 < len(mu) else np.inf
+        out.append(min(mu[c] - mu[c + 1], lo))
+    return np.array(out)
+
+
+def check_sign_rule(evecs):
+    for c in range(evecs.shape[1]):
+        a = int(np.argmax(np.abs(evecs[:, c])))            # (the first of equal magnitudes)
+        assert evecs[a, c] > 0.0, "column %d: largest entry %d is negative" % (c, a)
+
+
+def check_against_restatement(K, dmap, evecs, evals, eps, alpha, n_evecs):
+    rd, re, rl = R.diffusion_map_from_kernel(K, eps, alpha, n_evecs)
+    assert np.abs(evals - rl).max() <= 1e-10 / eps, (evals, rl)
+    P, _ = R.markov_operator(K, alpha)
+    mu = 1.0 + eps * evals
+    res = np.abs(P @ evecs - evecs * mu[None, :]).max()
+    assert res <= 1e-10, "residual |P psi - mu psi| = %.3e" % res
+    np.testing.assert_allclose(np.linalg.norm(evecs, axis=0), 1.0, rtol=0, atol=1e-12)
+    check_sign_rule(evecs)
+    gaps = column_gaps(R.mu_spectrum(K, alpha), n_evecs)
+    assert gaps.min() >= GAP, "fixture gap %.2e < %.0e: pick another case rather than loosening the tolerance" % (gaps.min(), GAP)
+    re = R.align_signs(evecs, re)
+    rd = R.align_signs(dmap, rd)
+    assert (np.abs(evecs - re).max(0) / np.abs(re).max(0)).max() <= 1e-6
+    assert (np.abs(dmap - rd).max(0) / np.abs(rd).max(0)).max() <= 1e-6
+
+
+# (matrix, knn, epsilon, alpha, n_evecs): every value of each parameter appears; knn >= N is the full Gaussian kernel
+CASES = [
+    ("c1", 5, 1.0, 0.5, 2), ("c1", 16, 0.3, 0.0, 5), ("c1", 64, 1.0, 1.0, 10), ("c1", 20, 0.3, 0.5, 1),
+    ("kidney", 64, 1.0, 0.5, 2), ("kidney", 5, 0.3, 1.0, 1), ("kidney", 16, 1.0, 0.0, 10), ("kidney", 634, 0.3, 0.5, 5),
+    ("c2", 64, 1.0, 0.5, 2), ("c2", 5, 1.0, 0.0, 5), ("c2", 16, 0.3, 1.0, 10), ("c2", 100, 1.0, 0.5, 1),
+    ("c3", 64, 1.0, 0.5, 2), ("c3", 16, 0.3, 0.5, 5), ("c3", 5, 1.0, 1.0, 1), ("c3", 600, 0.3, 0.0, 2),
+]
+
+
+@pytest.mark.parametrize("name,knn,eps,alpha,n_evecs", CASES)
+def test_matches_the_pydiffmap_restatement(matrices, name, knn, eps, alpha, n_evecs):
+    E = matrices(name)
+    _, K = engine.diffusion_kernel_of_rows(E, k=knn, epsilon=eps, return_distances=False)     # step 1: K7's kernel
+    dmap, evecs, evals, info = engine.diffusion_map_of_rows(E, n_evecs=n_evecs, epsilon=eps, alpha=alpha, k=knn, return_info=True)
+    assert info["flags"] == 0 and info["converged"] and not info["degenerate"], info
+    assert dmap.shape == evecs.shape == (E.shape[0], n_evecs) and evals.shape == (n_evecs,)
+    assert (np.diff(evals) <= 0).all() and (evals < 0).all()
+    check_against_restatement(K, dmap, evecs, evals, eps, alpha, n_evecs)
+
+
+@pytest.mark.parametrize("N", [2, 3, 64, 65, 333, 1025])
+def test_full_gaussian_kernel_against_a_dense_eigensolver(N):
+    """k >= N: the full Gaussian kernel of a random planar cloud; the eigenpairs of S = D^-1/2 A D^-1/2 from numpy's eigh.
+    N = 1025 is above the Lanczos basis cap (1024 vectors)."""
+    rng = np.random.default_rng(N)
+    X = rng.random((N, 2))
+    eps, alpha = 0.02, 0.5
+    K = np.exp(-((X[:, None, :] - X[None, :, :]) ** 2).sum(-1) / (4 * eps))
+    n_evecs = min(N - 1, 4)
+    dmap, evecs, evals, info = engine.diffusion_map_from_kernel(K, n_evecs=n_evecs, epsilon=eps, alpha=alpha, return_info=True)
+    assert info["flags"] == 0, info
+    assert info["steps"] <= min(N, 1024)
+    qa = K.sum(1) ** -alpha
+    A = qa[:, None] * K * qa[None, :]
+    d = A.sum(1)
+    S = A / np.sqrt(d)[:, None] / np.sqrt(d)[None, :]
+    mu, phi = np.linalg.eigh(0.5 * (S + S.T))
+    mu, phi = mu[::-1], phi[:, ::-1]
+    assert np.abs(evals - (mu[1:n_evecs + 1] - 1.0) / eps).max() <= 1e-10 / eps
+    assert column_gaps(mu, n_evecs).min() >= GAP
+    psi = phi[:, 1:n_evecs + 1] / np.sqrt(d)[:, None]
+    psi /= np.linalg.norm(psi, axis=0)
+    psi = R.align_signs(evecs, psi)
+    assert (np.abs(evecs - psi).max(0) / np.abs(psi).max(0)).max() <= 1e-6
+    np.testing.assert_allclose(dmap, evecs * np.sqrt(-1.0 / evals), rtol=1e-14, atol=0)
+    check_sign_rule(evecs)
+
+
+def test_repeated_calls_and_both_routes_give_identical_bits():
+    """Fixed-order sums, no float atomics: the same call twice, and the host-array route against the DeviceMatrix route (the
+    matrix where the pair grid left it)."""
+    P, M = make_problem(**CONFIGS["c2"])
+    plan = engine.DevicePlan(P, M)
+    plan.run(0.1)
+    plan.sync()
+    E = plan.fetch()[0]
+    a = engine.diffusion_map_of_rows(E, n_evecs=5, return_info=True)
+    b = engine.diffusion_map_of_rows(E, n_evecs=5, return_info=True)
+    c = engine.diffusion_map_of_rows(plan.device_matrix(), n_evecs=5, return_info=True)
+    plan.close()
+    for x in (b, c):
+        for u, v in zip(a[:3], x[:3]):
+            np.testing.assert_array_equal(u, v)
+        assert a[3] == x[3]
+
+
+def _two_clusters(n1=40, n2=30, seed=5):
+    rng = np.random.default_rng(seed)
+    X = np.r_[rng.random((n1, 2)), rng.random((n2, 2)) + 50.0]
+    return np.sqrt(((X[:, None, :] - X[None, :, :]) ** 2).sum(-1))
+
+
+def test_disconnected_kernel_is_degenerate():
+    """Block-diagonal kernel: eigenvalue 1 twice.  The Lanczos basis opens with the known eigenvector sqrt(d); its breakdown
+    restarts orthogonally to it, where the second eigenvalue 1 is found."""
+    D = _two_clusters()
+    K = np.exp(-D ** 2 / 4.0)
+    K[D > 10.0] = 0.0
+    dmap, evecs, evals, info = engine.diffusion_map_from_kernel(K, n_evecs=2, epsilon=1.0, return_info=True)
+    assert info["degenerate"] and info["flags"] & _lib.DIFFMAP_DEGENERATE
+    assert abs(evals[0]) <= 1e-10                              # the repeated mu = 1: lambda = 0
+    with pytest.raises(ValueError):
+        engine.diffusion_map_from_kernel(K, n_evecs=2, epsilon=1.0)
+    ad = type("A", (), {})()
+    ad.uns = {"EMD": D}
+    with pytest.raises(ValueError, match="knn"):
+        tl.diffusion_map(ad, knn=5)
+    assert set(ad.uns) == {"EMD"}
+
+
+def test_small_basis_is_not_converged(matrices, switches):
+    E = matrices("c2")
+    switches.setenv("PILOT_OT_DIFFMAP_BASIS", "4")
+    dmap, evecs, evals, info = engine.diffusion_map_of_rows(E, n_evecs=2, return_info=True)
+    assert not info["converged"] and info["flags"] & _lib.DIFFMAP_NOT_CONVERGED and info["steps"] == 4
+    with pytest.raises(ValueError):
+        engine.diffusion_map_of_rows(E, n_evecs=2)
+    ad = type("A", (), {})()
+    ad.uns = {"EMD": E}
+    with pytest.raises(ValueError, match="converge"):
+        tl.diffusion_map(ad)
+    switches.delenv("PILOT_OT_DIFFMAP_BASIS")
+    assert engine.diffusion_map_of_rows(E, n_evecs=2, return_info=True)[3]["converged"]
+
+
+@pytest.mark.parametrize("cohort", ["c1", "kidney"])
+def test_tl_diffusion_map_fills_the_embedding(kidney, cohort, tmp_path, monkeypatch):
+    """tl.diffusion_map after tl.wasserstein_distance: uns['embedding'] is what pl.trajectory computes (ploting.py:95-110, its
+    defaults n_evecs=2, epsilon=1, alpha=0.5, knn=64), engine's dmap bit for bit; nothing else in uns changes."""
+    monkeypatch.chdir(tmp_path)
+    if cohort == "c1":
+        g = load_golden("c1_20x10x10")
+        ad, cell_col = golden_adata(g)
+        tl.wasserstein_distance(ad, emb_matrix="X_pca", clusters_col=cell_col, sample_col="sampleID", status="status")
+        knn = 64
+    else:
+        ad, knn = kidney, 64
+    before = dict(ad.uns)
+    emb = tl.diffusion_map(ad)
+    assert set(ad.uns) == set(before) | {"embedding"}
+    assert all(ad.uns[k] is before[k] for k in before)
+    assert ad.uns["embedding"] is emb
+    E = ad.uns["EMD"]
+    assert isinstance(emb, np.ndarray) and emb.dtype == np.float64 and emb.shape == (E.shape[0], 2)
+    dmap, evecs, evals = engine.diffusion_map_of_rows(E, n_evecs=2, epsilon=1.0, alpha=0.5, k=knn)
+    np.testing.assert_array_equal(emb, dmap)
+    _, K = engine.diffusion_kernel_of_rows(E, k=knn, epsilon=1.0, return_distances=False)
+    check_against_restatement(K, dmap, evecs, evals, 1.0, 0.5, 2)
+    del ad.uns["embedding"]

@@ -366,6 +366,46 @@ int pilot_ot_diffusion_map_dev(const double *d_K, int N, double epsilon, double 
 int pilot_ot_diffusion_map_of_rows(const double *E, int E_is_device, int N, int k, double epsilon, double alpha, int n_evecs,
                                    double *dmap, double *evecs, double *evals, int *info);
 
+/* ---- trajectory model fits: pilotpy's fit_best_model / fit_model_activity (tools/Cell_gene_selection.py),
+ * the regression engine of cell_importance and genes_importance.  Y: n observations x n_targets, row-major with leading dimension
+ * ld (elements), float32 (dtype 0) or float64 (dtype 1), on the host or (Y_is_device) in HBM; x: the n time values (host).
+ * For every target column y, three models with an intercept, in this order: linear [x], linear_quadratic [x, x^2], quadratic
+ * [x^2]; OLS (model OLS, LinearRegression), or (model HUBER) the optimum of scikit-learn's HuberRegressor objective over
+ * (w, c, sigma >= 10 DBL_EPSILON)
+ *   n sigma + sum_{|r| <= eps sigma} r^2 / sigma + sum_{|r| > eps sigma} (2 eps |r| - eps^2 sigma) + 1e-4 ||w||^2
+ * found by Newton steps with a bracketing line search, stopped when (sum of |projected gradient|) * sigma <= 1e-12 * objective
+ * (gradient over the fit in a scaled basis and sigma) or when no lower objective exists in floating point along a descent
+ * direction; after 100 steps the (target, model) is PILOT_OT_TRAJFIT_NOT_CONVERGED and ineligible.  Per (target, model):
+ * params (c, w) (3 slots, the third NaN for the two-coefficient models), t-test p-values 2 (1 - Tcdf(|t|, n - p)) with
+ * t_j = params_j / sqrt(SSE / (n - p) diag((Z^T Z)^-1)_j) for both models (third slot NaN likewise), rsquared_adj (r2_score's rule
+ * when SST = 0), mod_rsquared_adj (modified SSE with the fixed threshold 1.35, IEEE division), and sigma (NaN for OLS), Newton steps,
+ * flags.  Per target: chosen model (0 / 1 / 2 in the order above, -1 none: eligible = not flagged and every p-value <= pval_thr,
+ * the largest adjusted R^2 -- the modified one with modify_r2 -- wins on a strict >), slope over [min x, max x], pattern (bit 0:
+ * params[1] < 0, bit 1: params[2] < 0 for linear_quadratic; -1 when none is chosen), Pearson r and its two-sided p, zero fraction,
+ * mean.  A constant target has SST = 0 and NaN Pearson results.  Arrays are n_targets x 3 x 3 (params, pvalues), n_targets x 3
+ * (R^2, sigma, steps, flags) and n_targets; every output pointer may be NULL.  All in f64 with fixed-order sums: bit-reproducible.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL Y / x / out, n < 4, n_targets < 0, ld < n_targets, dtype not 0 / 1, model not
+ * OLS / HUBER, epsilon not finite or < 1 (checked for both models), pval_thr NaN, x not finite or with fewer than 3 distinct values.
+ * A host Y moves through the device in chunks of columns of at most 256 MiB.  n_not_converged (nullable): the flagged count. */
+#define PILOT_OT_TRAJFIT_OLS 0
+#define PILOT_OT_TRAJFIT_HUBER 1
+#define PILOT_OT_TRAJFIT_NOT_CONVERGED 1
+typedef struct pilot_ot_trajfit_out {
+    double *params, *pvalues;                 /* n_targets x 3 x 3 */
+    double *rsquared_adj, *mod_rsquared_adj;  /* n_targets x 3 */
+    double *sigma;                            /* n_targets x 3: Huber scale (NaN for OLS) */
+    int *steps, *flags;                       /* n_targets x 3: Huber Newton steps, PILOT_OT_TRAJFIT_* flags */
+    int *chosen, *pattern;                    /* n_targets */
+    double *slope, *pearson_r, *pearson_p, *zero_fraction, *mean;   /* n_targets */
+} pilot_ot_trajfit_out;
+int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype, int n, int n_targets, long long ld, const double *x,
+                             int model, double epsilon, double pval_thr, int modify_r2, pilot_ot_trajfit_out *out,
+                             int *n_not_converged);
+/* genes_importance's optional normalisation (scanpy's normalize_total(target_sum) then log1p, restated): X n x n_genes dense
+ * row-major float32 / float64 on the host; out (n x n_cols, same dtype, host) = log1p(X[i, cols[j]] * target_sum / sum_g X[i, g]),
+ * the row total in f64 over every gene; a row without counts stays 0. */
+int pilot_ot_normalize_log1p(const void *X, int dtype, int n, int n_genes, double target_sum, const int *cols, int n_cols, void *out);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

@@ -23,6 +23,7 @@ METRICS = {"cosine": 0, "euclidean": 1, "sqeuclidean": 2, "cityblock": 3, "cheby
 EMD_ALL, EMD_UPPER, EMD_MIRROR = 0, 1, 2
 FLAG_CONVERGED, FLAG_NAN, FLAG_ABSORB_LAST, FLAG_ABSORBED, FLAG_F64 = 1, 2, 4, 8, 16
 DIFFMAP_NOT_CONVERGED, DIFFMAP_DEGENERATE = 1, 2
+TRAJFIT_OLS, TRAJFIT_HUBER, TRAJFIT_NOT_CONVERGED = 0, 1, 1
 
 # every symbol include/pilot_ot.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -39,7 +40,8 @@ SYMBOLS = [
     "pilot_ot_mirror_upper_dev", "pilot_ot_transport_plans",
     "pilot_ot_row_distances", "pilot_ot_row_distances_dev", "pilot_ot_silhouette", "pilot_ot_knn_kernel",
     "pilot_ot_silhouette_dev", "pilot_ot_knn_kernel_dev", "pilot_ot_silhouette_of_rows", "pilot_ot_diffusion_kernel_of_rows",
-    "pilot_ot_diffusion_map_dev", "pilot_ot_diffusion_map_of_rows",
+    "pilot_ot_diffusion_map_dev", "pilot_ot_diffusion_map_of_rows", "pilot_ot_trajectory_fits",
+    "pilot_ot_normalize_log1p",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -49,6 +51,14 @@ SYMBOLS = [
 GATHER = {"auto": 0, "rccl": 1, "copy": 2}
 ROW_METRICS = {"euclidean": 0, "cosine": 1}
 UNIQUE_ID_BYTES = 128
+
+
+class TrajfitOut(ctypes.Structure):
+    """``pilot_ot_trajfit_out``: where pilot_ot_trajectory_fits writes (every pointer nullable)."""
+    _dp, _ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    _fields_ = [("params", _dp), ("pvalues", _dp), ("rsquared_adj", _dp), ("mod_rsquared_adj", _dp), ("sigma", _dp),
+                ("steps", _ip), ("flags", _ip), ("chosen", _ip), ("pattern", _ip), ("slope", _dp), ("pearson_r", _dp),
+                ("pearson_p", _dp), ("zero_fraction", _dp), ("mean", _dp)]
 
 _lib = None
 
@@ -133,6 +143,9 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_diffusion_kernel_of_rows.argtypes = [c_vp, c_int, c_int, c_int, c_dbl, dp, dp]
     L.pilot_ot_diffusion_map_dev.argtypes = [c_vp, c_int, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ip, c_vp]
     L.pilot_ot_diffusion_map_of_rows.argtypes = [c_vp, c_int, c_int, c_int, c_dbl, c_dbl, c_int, dp, dp, dp, ip]
+    L.pilot_ot_trajectory_fits.argtypes = [c_vp, c_int, c_int, c_int, c_int, ctypes.c_longlong, dp, c_int, c_dbl, c_dbl, c_int,
+                                            ctypes.POINTER(TrajfitOut), ip]
+    L.pilot_ot_normalize_log1p.argtypes = [c_vp, c_int, c_int, c_int, c_dbl, ip, c_int, c_vp]
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

@@ -589,6 +589,7 @@ def _label_codes(labels, n):
 def _matrix_arg(E):
     """(pointer, is_device, N) of a square matrix given as a numpy array or as a device-resident result (DeviceMatrix)."""
     if isinstance(E, DeviceMatrix):
+        _square_f64(E, "E")
         return ctypes.c_void_p(E.ptr), 1, E.N, None
     E = _as_f64(E, "E")
     if E.ndim != 2 or E.shape[0] != E.shape[1]:
@@ -596,14 +597,46 @@ def _matrix_arg(E):
     return ctypes.c_void_p(E.ctypes.data), 0, E.shape[0], E
 
 
+def _square_f64(D, name):
+    """the consumers of the pair-grid matrix read an N x N float64 DeviceMatrix"""
+    if D.shape != (D.N, D.N) or D.dtype != np.float64:
+        raise ValueError("%s: an N x N float64 DeviceMatrix, got %s %s" % (name, D.shape, D.dtype))
+
+
 class DeviceMatrix:
     """An N x N fp64 matrix that lives in HBM (e.g. ``DevicePlan.device_matrix()`` after a full-grid run, or
     ``multi.MultiPlan.device_matrix()``): the consumers below take it without a trip through host memory."""
 
-    def __init__(self, ptr, N, owner=None):
+    def __init__(self, ptr, N, owner=None, shape=None, dtype=np.float64):
         self.ptr = int(ptr.value if isinstance(ptr, ctypes.c_void_p) else ptr)
         self.N = int(N)
         self.owner = owner            # keeps the allocation alive
+        self.shape = (self.N, self.N) if shape is None else tuple(int(v) for v in shape)   # (rows, columns), row-major, dense
+        self.dtype = np.dtype(dtype)
+
+    @classmethod
+    def upload(cls, A):
+        """A copy of the 2-D float32 / float64 array A in HBM (freed with the returned object)."""
+        A = np.asarray(A)
+        if A.ndim != 2 or A.dtype not in (np.float32, np.float64):
+            raise ValueError("upload: a 2-D float32 / float64 array, got %s %s" % (A.shape, A.dtype))
+        A = np.ascontiguousarray(A)
+        buf = _DeviceBuffer(A.nbytes)
+        _lib.check(_lib.load().pilot_ot_memcpy_h2d(buf.ptr, A.ctypes.data, A.nbytes))
+        return cls(buf.ptr, A.shape[0], owner=buf, shape=A.shape, dtype=A.dtype)
+
+
+class _DeviceBuffer:
+    """One pilot_ot_dev_alloc allocation, released when the object goes."""
+
+    def __init__(self, nbytes):
+        self.ptr = ctypes.c_void_p()
+        _lib.check(_lib.load().pilot_ot_dev_alloc(ctypes.byref(self.ptr), max(int(nbytes), 1)))
+
+    def __del__(self):
+        if self.ptr:
+            _lib.load().pilot_ot_dev_free(self.ptr)
+            self.ptr = ctypes.c_void_p()
 
 
 def silhouette_of_rows(E, labels, metric="cosine", normalize_by_max=False, return_samples=False):
@@ -698,6 +731,8 @@ def diffusion_map_from_kernel(Kmat, n_evecs=2, epsilon=1.0, alpha=0.5, return_in
     :func:`knn_gaussian_kernel`'s: symmetrised max(K, K^T), alpha-normalised, Lanczos on the device.  Same returns as
     :func:`diffusion_map_of_rows`."""
     on_dev = isinstance(Kmat, DeviceMatrix)
+    if on_dev:
+        _square_f64(Kmat, "Kmat")
     N = Kmat.N if on_dev else np.asarray(Kmat).shape[0]
     if not on_dev:
         Kmat = _as_f64(Kmat, "Kmat")
@@ -732,3 +767,60 @@ def diffusion_map_from_kernel(Kmat, n_evecs=2, epsilon=1.0, alpha=0.5, return_in
         for p in bufs:
             L.pilot_ot_dev_free(p)
     return _diffmap_result(dmap, evecs, evals, info, return_info)
+
+
+# ---- trajectory model fits (pilotpy's fit_best_model, tools/Cell_gene_selection.py) --------------------------
+TRAJFIT_MODELS = ("linear", "linear_quadratic", "quadratic")
+
+
+def trajectory_fits(Y, x, model="ols", epsilon=1.35, pval_thr=0.05, modify_r2=False, return_info=False):
+    """The three trajectory models of every target column of ``Y`` (n observations x targets, float32 / float64, a numpy
+    array or a :class:`DeviceMatrix`) against the time ``x`` (n values), on the device: ``linear`` [x], ``linear_quadratic``
+    [x, x^2] and ``quadratic`` [x^2], each with an intercept, fitted by OLS (``model="ols"``, LinearRegression) or to the
+    optimum of scikit-learn's HuberRegressor objective (``model="huber"``, ``epsilon``, alpha 1e-4), then pilotpy's statistics
+    and model choice (include/pilot_ot.h, "trajectory model fits").  Returns a dict of arrays: ``params`` and ``pvalues``
+    (targets x 3 models x 3; the third slot NaN for the two-coefficient models), ``rsquared_adj``, ``mod_rsquared_adj``
+    (targets x 3), ``chosen`` (index into :data:`TRAJFIT_MODELS`, -1 when no model is eligible), ``slope``, ``pattern``
+    (bit 0: params[1] < 0, bit 1: params[2] < 0; -1 with no choice), ``pearson_r``, ``pearson_p``, ``zero_fraction``,
+    ``mean``.  With ``return_info`` a second dict: ``sigma``, ``steps``, ``flags`` (targets x 3; Huber scale, Newton steps,
+    ``_lib.TRAJFIT_NOT_CONVERGED`` bits) and ``not_converged`` (the flagged count)."""
+    if model not in ("ols", "huber"):
+        raise ValueError("model=%r must be 'ols' or 'huber'" % (model,))
+    x = _as_f64(np.ravel(x), "x")
+    if isinstance(Y, DeviceMatrix):
+        if len(Y.shape) != 2 or Y.dtype not in (np.float32, np.float64):
+            raise ValueError("Y: a 2-D float32 / float64 DeviceMatrix, got %s %s" % (Y.shape, Y.dtype))
+        n, T = Y.shape
+        ptr, on_dev, ld, dtype, keep = ctypes.c_void_p(Y.ptr), 1, T, Y.dtype, None
+    else:
+        Y = np.asarray(Y)
+        if Y.ndim != 2:
+            raise ValueError("Y must be 2-D (observations x targets), got %s" % (Y.shape,))
+        if Y.dtype not in (np.float32, np.float64):
+            Y = Y.astype(np.float64)
+        if Y.strides[1] != Y.itemsize or Y.strides[0] % Y.itemsize or Y.strides[0] < 0:
+            Y = np.ascontiguousarray(Y)
+        n, T = Y.shape
+        ld = Y.strides[0] // Y.itemsize if n > 1 else T
+        ptr, on_dev, dtype, keep = ctypes.c_void_p(Y.ctypes.data), 0, Y.dtype, Y
+    if x.size != n:
+        raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
+    fits = dict(params=np.empty((T, 3, 3)), pvalues=np.empty((T, 3, 3)), rsquared_adj=np.empty((T, 3)),
+                mod_rsquared_adj=np.empty((T, 3)), chosen=np.empty(T, dtype=np.int32), slope=np.empty(T),
+                pattern=np.empty(T, dtype=np.int32), pearson_r=np.empty(T), pearson_p=np.empty(T), zero_fraction=np.empty(T),
+                mean=np.empty(T))
+    info = dict(sigma=np.empty((T, 3)), steps=np.empty((T, 3), dtype=np.int32), flags=np.empty((T, 3), dtype=np.int32))
+    out = _lib.TrajfitOut()
+    for name, arr in list(fits.items()) + list(info.items()):
+        ct = ctypes.c_int if arr.dtype == np.int32 else ctypes.c_double
+        setattr(out, name, arr.ctypes.data_as(ctypes.POINTER(ct)))
+    nnc = ctypes.c_int(0)
+    _lib.check(_lib.load().pilot_ot_trajectory_fits(
+        ptr, on_dev, 0 if dtype == np.float32 else 1, n, T, ld, _lib.dptr(x),
+        _lib.TRAJFIT_HUBER if model == "huber" else _lib.TRAJFIT_OLS, float(epsilon), float(pval_thr), int(bool(modify_r2)),
+        ctypes.byref(out), ctypes.byref(nnc)))
+    del keep
+    if return_info:
+        info["not_converged"] = nnc.value
+        return fits, info
+    return fits

@@ -20,6 +20,8 @@ Sil_computing                                  Trajectory.py:592-612
 Precomputed_distance                           Trajectory.py:1687-1727
 diffusion_kernel                               plot/ploting.py:95-110 (the dense part of pl.trajectory)
 diffusion_map                                  plot/ploting.py:95-110 (pl.trajectory's embedding, without the plot)
+cell_importance                                Trajectory.py:646-800 (the table and uns keys, without plots or files)
+genes_importance                               Trajectory.py:860-995 (the table, without plots or files)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -612,3 +614,131 @@ def cell_level_wasserstein(adata, emb_matrix="X_PCA", sample_col="sampleID", sta
     adata.uns["EMD_cell_df"] = df
     adata.uns["EMD_cell_scale"] = scale
     adata.uns["real_labels"] = return_real_labels(pd.DataFrame({"cell_type": 0, "sampleID": obs["sampleID"], "status": obs["status"]}))
+
+
+# ---- trajectory model fits: cell_importance / genes_importance (Trajectory.py:646-995) -------------------------------------
+_PATTERNS = {0: ("linear up", "linear down"),
+             1: ("linear up quadratic up", "linear down quadratic up", "linear up quadratic down", "linear down quadratic down"),
+             2: ("quadratic up", "quadratic down")}
+
+
+def _bh_adjust(p):
+    """Benjamini-Hochberg adjusted p-values (statsmodels' multipletests(method='fdr_bh')[1])."""
+    p = np.asarray(p, dtype=np.float64)
+    m = p.size
+    if m == 0:
+        return p.copy()
+    order = np.argsort(p, kind="stable")
+    scaled = p[order] * m / np.arange(1, m + 1)
+    adj = np.minimum(np.minimum.accumulate(scaled[::-1])[::-1], 1.0)
+    out = np.empty(m)
+    out[order] = adj
+    return out
+
+
+def _fits_table(fits, names, id_col, p_val, modify_r2):
+    """fit_best_model's sorted dict -> save_data's table (Cell_gene_selection.py:680-760) with numeric columns: targets with a
+    chosen model, sorted by the deciding adjusted R^2 (descending, ties in target order), BH-adjusted Pearson p-values, rows
+    with adjusted p <= p_val.  Returns (table, names of every selected target in sorted order)."""
+    chosen = fits["chosen"]
+    sel = np.flatnonzero(chosen >= 0)
+    key = (fits["mod_rsquared_adj"] if modify_r2 else fits["rsquared_adj"])[sel, chosen[sel]]
+    sel = sel[np.argsort(-key, kind="stable")]
+    m = chosen[sel]
+    params = fits["params"][sel, m]
+    names = np.asarray(names, dtype=object)
+    table = pd.DataFrame({
+        id_col: names[sel],
+        "Expression pattern": [_PATTERNS[int(a)][int(b)] for a, b in zip(m, fits["pattern"][sel])],
+        "Slope": fits["slope"][sel],
+        "Fitted function": [engine.TRAJFIT_MODELS[int(a)] for a in m],
+        "Intercept": params[:, 0],
+        "Treat": params[:, 1],
+        "Treat2": params[:, 2],
+        "adjusted P-value": _bh_adjust(fits["pearson_p"][sel]),
+        "R-squared": fits["rsquared_adj"][sel, m],
+        "mod_rsquared_adj": fits["mod_rsquared_adj"][sel, m],
+    })
+    if not (m == 1).any():                       # the reference drops Treat2 when no selected fit has three coefficients
+        table = table.drop(columns="Treat2")
+    return table[table["adjusted P-value"] <= p_val], list(names[sel])
+
+
+def cell_importance(adata, pseudotime=None, p_val=1):
+    """cell_importance (Trajectory.py:646-800) without plots or files: the cell-type proportions of ``adata.uns['proportions']``
+    against the samples' rank in pseudotime, OLS fits of the three trajectory models per cell type on the device
+    (``engine.trajectory_fits``, every p-value <= ``p_val`` to be eligible), and the report table (numeric columns).  Writes
+    ``adata.uns['cellnames']`` (the selected cell types, best R^2 first) and ``adata.uns['orders']`` (sampleID, Time_score
+    1..N in pseudotime order).  ``pseudotime``: one value per sample in ``uns['proportions']`` order; default
+    ``adata.uns['pseudotime']`` (pilotpy's fit_pricipla_graph)."""
+    if pseudotime is None:
+        if "pseudotime" not in adata.uns:
+            raise KeyError("cell_importance needs a pseudotime: pass pseudotime= (one value per sample, e.g. a diffusion "
+                           "coordinate) or set adata.uns['pseudotime'] (pilotpy's fit_pricipla_graph)")
+        pseudotime = adata.uns["pseudotime"]
+    bins = adata.uns["proportions"]
+    samples = list(bins.keys())
+    P = np.stack([np.asarray(bins[k], dtype=np.float64) for k in samples])
+    cell_types = adata.uns["annot"]["cell_type"].unique()
+    pseudotime = np.asarray(pseudotime, dtype=np.float64).ravel()
+    if pseudotime.size != len(samples):
+        raise ValueError("pseudotime has %d values for %d samples" % (pseudotime.size, len(samples)))
+    order = np.argsort(pseudotime, kind="stable")
+    N = len(samples)
+    fits = engine.trajectory_fits(P[order], np.arange(1, N + 1, dtype=np.float64), model="ols", pval_thr=p_val)
+    table, cellnames = _fits_table(fits, cell_types, "Cell name", p_val, False)
+    adata.uns["cellnames"] = cellnames
+    adata.uns["orders"] = pd.DataFrame({"sampleID": np.asarray(samples, dtype=object)[order],
+                                        "Time_score": np.arange(1, N + 1, dtype=np.int64)})
+    return table
+
+
+def _cell_rows(adata, name_cell, sample_col, col_cell, orders, col):
+    """The reference's ``orders.merge(cells, on='sampleID')``: the cells of ``name_cell`` ordered by their sample's row in
+    ``orders`` (cells of one sample in obs order; cells of samples missing from ``orders`` dropped).  (rows, time)"""
+    obs = adata.obs
+    cells = np.flatnonzero(np.asarray(obs[col_cell].isin([name_cell])))
+    pos = {s: i for i, s in enumerate(orders["sampleID"])}
+    rank = np.array([pos.get(s, -1) for s in np.asarray(obs[sample_col])[cells]], dtype=np.int64)
+    keep = rank >= 0
+    cells, rank = cells[keep], rank[keep]
+    o = np.argsort(rank, kind="stable")
+    return cells[o], np.asarray(orders[col], dtype=np.float64)[rank[o]]
+
+
+def genes_importance(adata, name_cell, col="Time_score", p_value=0.05, model_type="HuberRegressor", epsilon_huber=1.35,
+                     modify_r2=False, sample_col="sampleID", col_cell="cell_types", normalize=True):
+    """genes_importance (Trajectory.py:860-995) without plots or files: the cells of ``name_cell`` in the order of
+    ``adata.uns['orders']`` (what cell_importance wrote), optionally normalize_total(1e4) + log1p on the device (a restatement of
+    scanpy's, unpinned), genes with a zero fraction > 0.95 dropped, then fits of the three trajectory models per gene
+    against the cells' ``col``, the report table with numeric columns and each gene's ``proportion`` (zero fraction) and
+    ``mean``.  ``adata.X`` may be dense or scipy CSR.  ``model_type``: 'HuberRegressor' (the OPTIMUM of its objective with
+    ``epsilon_huber``; scikit-learn's own fit stops early on some fits with an x^2 feature) or 'LinearRegression'.  A
+    (gene, model) whose Huber solve did not converge is ineligible, as the engine flags it."""
+    if model_type not in ("HuberRegressor", "LinearRegression"):
+        raise ValueError("model_type=%r must be 'HuberRegressor' or 'LinearRegression'" % (model_type,))
+    rows, x = _cell_rows(adata, name_cell, sample_col, col_cell, adata.uns["orders"], col)
+    X = adata.X[rows]
+    X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float32)
+    X = np.ascontiguousarray(X)
+    genes = np.asarray(list(adata.var_names), dtype=object)
+    zero = (X == 0).mean(axis=0) if X.shape[0] else np.zeros(X.shape[1])
+    cols = np.flatnonzero(~(zero > 0.95)).astype(np.int32)
+    if normalize:
+        Y = np.empty((X.shape[0], cols.size), dtype=X.dtype)
+        _lib_check_normalize(X, cols, Y)
+    else:
+        Y = X[:, cols]
+    fits = engine.trajectory_fits(Y, x, model="huber" if model_type == "HuberRegressor" else "ols", epsilon=epsilon_huber,
+                                  pval_thr=p_value, modify_r2=modify_r2)
+    table, _ = _fits_table(fits, genes[cols], "Gene ID", p_value, modify_r2)
+    pro = pd.DataFrame({"Gene ID": genes[cols], "proportion": fits["zero_fraction"], "mean": fits["mean"]})
+    return pd.merge(table, pro, on="Gene ID")
+
+
+def _lib_check_normalize(X, cols, out):
+    from . import _lib
+    _lib.check(_lib.load().pilot_ot_normalize_log1p(X.ctypes.data, 0 if X.dtype == np.float32 else 1, X.shape[0], X.shape[1],
+                                                    1e4, _lib.iptr(cols), int(cols.size), out.ctypes.data))

@@ -406,6 +406,25 @@ int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype, int n, i
  * the row total in f64 over every gene; a row without counts stays 0. */
 int pilot_ot_normalize_log1p(const void *X, int dtype, int n, int n_genes, double target_sum, const int *cols, int n_cols, void *out);
 
+/* ---- bootstrap Huber fits: the 2 x 50 HuberRegressor fits behind every row of pilotpy's
+ * gene_cluster_differentiation (tools/Gene_cluster_specific.py).  Y: n observations x n_cols, row-major with leading dimension ld
+ * (elements), float32 (dtype 0) or float64 (dtype 1), on the host (copied whole) or (Y_is_device) in HBM; x: the n base times
+ * (host).  Problem q fits column cols[q] of Y with model models[q] (0 linear [x], 1 linear_quadratic [x, x^2], 2 quadratic [x^2],
+ * each with an intercept) B times: fit b regresses y (in its own order) on x[idx[q][i][b]], i = 0 .. n-1 -- only the times are
+ * resampled.  idx: n_problems x n x B ints in [0, n), observation-major (host; streamed through the device in chunks of at most
+ * 256 MiB).  Every fit goes to the optimum of scikit-learn's HuberRegressor objective (alpha 1e-4, sigma >= 10 DBL_EPSILON) by the
+ * method of pilot_ot_trajectory_fits: Newton steps from the penalised least-squares fit, bracketing line search, the same stop rule,
+ * after 100 steps PILOT_OT_TRAJFIT_NOT_CONVERGED.  A resample with fewer distinct times than coefficients still has one optimum
+ * (alpha > 0) and gets it.  Out, per (problem, bootstrap), problem-major: params (n_problems x B x 3, on [1, f(x)]; the third slot
+ * NaN for the two-coefficient models), and the nullable sigma, steps (Newton steps), flags (PILOT_OT_TRAJFIT_* bits).
+ * n_not_converged (nullable): the flagged count.  All in f64 with fixed-order sums: bit-reproducible across routes and chunkings.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL Y / x / params (cols / models / idx when n_problems > 0), n < 1, n_cols < 1,
+ * ld < n_cols, dtype not 0 / 1, n_problems < 0, B outside [1, 64 * 65535], epsilon not finite or < 1, x not finite, cols[q] outside
+ * [0, n_cols), models[q] not 0 / 1 / 2, idx values outside [0, n). */
+int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int dtype, int n, int n_cols, long long ld, const double *x,
+                                  int n_problems, const int *cols, const int *models, int B, const int *idx, double epsilon,
+                                  double *params, double *sigma, int *steps, int *flags, int *n_not_converged);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

@@ -17,7 +17,7 @@ const char *test_switch(const char *name);
 void abi_multi_release();
 // a buffer of the calling thread's pool of device temporaries (grown on demand, released by pilot_ot_shutdown); slots 0 .. 11
 // belong to pilot_ot.hip, 12 .. 19 to pilot_ot_consumers.hip, 20 .. 35 to pilot_ot_plans.hip, 36 .. 47 to pilot_ot_diffmap.hip, 48 .. 51 to
-// pilot_ot_trajfit.hip
+// pilot_ot_trajfit.hip, 52 .. 55 to pilot_ot_bootfit.hip
 hipError_t ws_buffer(int slot, size_t bytes, void **out);
 // cell-level cohort, internal face used by the multi-device form (pilot_ot_multi.hip)
 int cell_enqueue_rows(pilot_ot_cell_cohort *c, double scale, double reg, int num_iter_max, double stop_thr, int check_period,

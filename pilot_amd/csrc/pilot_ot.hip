@@ -1078,7 +1078,7 @@ namespace {
 // millisecond a pair and hipFree synchronises the device: nine of them were most of a 22 ms medians call); released by
 // pilot_ot_shutdown().  Slot i of the pool backs the i-th DevBuf a call declares.
 struct WsPool {
-    static constexpr int SLOTS = 52;
+    static constexpr int SLOTS = 56;
     void *p[SLOTS] = {};
     size_t cap[SLOTS] = {};
     int device = -1;

@@ -1,0 +1,172 @@
+// C ABI of the batched bootstrap Huber fits (include/pilot_ot.h, section "bootstrap Huber fits"; kernel: bootfit_kernels.hpp).
+// The host maps the base times once (K9's scaled basis, back-transform and penalty; no Gram: each resample forms its own in the
+// kernel), copies Y once and streams the index vectors through the device in bounded chunks of problems.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "abi_common.hpp"
+#include "bootfit_kernels.hpp"
+
+#define fail(...) pilot::abi_fail(__VA_ARGS__)
+
+namespace {
+
+constexpr size_t CHUNK_BYTES = size_t(256) << 20;      // index vectors on the device: at most this many bytes at a time
+constexpr int MAX_ITER = 100;                          // Newton steps per fit before PILOT_OT_TRAJFIT_NOT_CONVERGED (as K9)
+constexpr double HUBER_ALPHA = 1e-4;                   // scikit-learn's HuberRegressor default penalty
+
+// temporaries: slots 52 .. 55 of the calling thread's pool
+template <typename T> hipError_t ws(int slot, size_t n, T **p) {
+    void *v = nullptr;
+    const hipError_t e = pilot::ws_buffer(slot, sizeof(T) * (n ? n : 1), &v);
+    *p = static_cast<T *>(v);
+    return e;
+}
+
+// u = (x - m) / s of the base times and, per model, K9's basis (C, quad_k, quad_scale), coefficients on [1, f(x)] (R) and the
+// penalty alpha ||w||^2 written on gamma (pen) -- the parts of pilot_ot_trajfit.hip's prepare() that do not depend on the Gram.
+// s = max |x - m|, 1 when every time is the same.
+void prepare_map(const double *x, int n, std::vector<double> &u, pilot::TrajfitArgs &a) {
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum += x[i];
+    const double m = sum / n;
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) s = std::max(s, std::fabs(x[i] - m));
+    if (!(s > 0.0)) s = 1.0;
+    u.resize(n);
+    for (int i = 0; i < n; ++i) u[i] = (x[i] - m) / s;
+    const double kappa = 2.0 * m / s, qs = 1.0 / (1.0 + std::fabs(kappa));
+    const double E[3][3] = {{1.0, -m / s, m * m / (s * s)}, {0.0, 1.0 / s, -2.0 * m / (s * s)}, {0.0, 0.0, 1.0 / (s * s)}};
+    std::memset(&a, 0, sizeof(a));
+    for (int md = 0; md < 3; ++md) {
+        pilot::TrajfitModel &M = a.mod[md];
+        const int p = md == 1 ? 3 : 2;
+        double C[3][3] = {};
+        C[0][0] = 1.0;
+        if (md == 0) C[1][1] = 1.0;
+        else if (md == 1) { C[1][1] = 1.0; C[2][2] = 1.0; }
+        else { C[1][1] = kappa * qs; C[2][1] = qs; }
+        std::memcpy(M.C, C, sizeof(C));
+        double EC[3][3] = {};
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < p; ++j)
+                for (int k = 0; k < 3; ++k) EC[i][j] += E[i][k] * C[k][j];
+        const int rows[3] = {0, md == 2 ? 2 : 1, 2};                                   // quadratic: [1, x^2]
+        for (int i = 0; i < p; ++i)
+            for (int j = 0; j < p; ++j) M.R[i][j] = EC[rows[i]][j];
+        for (int i = 0; i < p; ++i)
+            for (int j = 0; j < p; ++j)
+                for (int r = 1; r < p; ++r) M.pen[i][j] += HUBER_ALPHA * M.R[r][i] * M.R[r][j];
+    }
+    a.quad_k = kappa;
+    a.quad_scale = qs;
+    a.sigma_min = 10.0 * DBL_EPSILON;
+    a.n = n;
+}
+
+int check_args(const void *Y, int dtype, int n, int n_cols, long long ld, const double *x, int n_problems, const int *cols,
+               const int *models, int B, const int *idx, double epsilon, const double *params) {
+    if (!Y || !x || !params || (n_problems > 0 && (!cols || !models || !idx))) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    if (n < 1) return fail(PILOT_OT_EINVAL, "n=%d: the fits need at least 1 observation", n);
+    if (n_cols < 1) return fail(PILOT_OT_EINVAL, "n_cols=%d must be positive", n_cols);
+    if (ld < n_cols) return fail(PILOT_OT_EINVAL, "ld=%lld is smaller than n_cols=%d", ld, n_cols);
+    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (n_problems < 0) return fail(PILOT_OT_EINVAL, "n_problems=%d is negative", n_problems);
+    if (B < 1 || B > 64 * 65535) return fail(PILOT_OT_EINVAL, "B=%d must be in [1, %d]", B, 64 * 65535);
+    if (!(epsilon >= 1.0) || !std::isfinite(epsilon)) return fail(PILOT_OT_EINVAL, "epsilon=%g must be finite and >= 1", epsilon);
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(x[i])) return fail(PILOT_OT_EINVAL, "x[%d]=%g is not finite", i, x[i]);
+    for (int q = 0; q < n_problems; ++q) {
+        if (cols[q] < 0 || cols[q] >= n_cols) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", q, cols[q], n_cols);
+        if (models[q] < 0 || models[q] > 2) return fail(PILOT_OT_EINVAL, "models[%d]=%d must be 0, 1 or 2", q, models[q]);
+    }
+    const size_t total = (size_t)n_problems * n * B;
+    for (size_t j = 0; j < total; ++j)
+        if ((unsigned)idx[j] >= (unsigned)n)
+            return fail(PILOT_OT_EINVAL, "idx[%zu]=%d outside [0, %d) (problem %zu, observation %zu, bootstrap %zu)", j, idx[j], n,
+                        j / ((size_t)n * B), j / B % n, j % B);
+    return PILOT_OT_OK;
+}
+
+}  // namespace
+
+PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int dtype, int n, int n_cols, long long ld, const double *x,
+                                            int n_problems, const int *cols, const int *models, int B, const int *idx, double epsilon,
+                                            double *params, double *sigma, int *steps, int *flags, int *n_not_converged) {
+    int rc = check_args(Y, dtype, n, n_cols, ld, x, n_problems, cols, models, B, idx, epsilon, params);
+    if (rc != PILOT_OT_OK) return rc;
+    if (n_not_converged) *n_not_converged = 0;
+    if (n_problems == 0) return PILOT_OT_OK;
+    pilot::TrajfitArgs a;
+    std::vector<double> u;
+    prepare_map(x, n, u, a);
+    a.huber = 1;
+    a.epsilon = epsilon;
+    a.max_iter = MAX_ITER;
+    if (const char *sw = pilot::test_switch("PILOT_OT_TRAJFIT_MAX_ITER")) {      // (tests: the NOT_CONVERGED path)
+        const int v = atoi(sw);
+        if (v >= 0 && v < a.max_iter) a.max_iter = v;
+    }
+    const size_t per_problem = (size_t)n * B * sizeof(int);
+    long long pc = (long long)std::max<size_t>(1, CHUNK_BYTES / per_problem);
+    if (const char *sw = pilot::test_switch("PILOT_OT_BOOTFIT_CHUNK_PROBLEMS")) {  // (tests: many chunks)
+        const long long v = atoll(sw);
+        if (v > 0) pc = v;
+    }
+    pc = std::min<long long>(pc, n_problems);
+    const size_t es = dtype == 0 ? sizeof(float) : sizeof(double);
+
+    double *d_u, *d_out;
+    int *d_idx, *d_pm;
+    unsigned char *d_y = nullptr;
+    const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
+    HIP_TRY(ws(52, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
+    const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
+    HIP_TRY(ws(53, (size_t)pc * B * pilot::BF_NOUT, &d_out));
+    HIP_TRY(ws(54, (size_t)pc * n * B + 2 * (size_t)n_problems, &d_idx));    // the chunk's indices, then cols and models
+    d_pm = d_idx + (size_t)pc * n * B;
+    HIP_TRY(hipMemcpy(d_u, u.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pm, cols, sizeof(int) * n_problems, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pm + n_problems, models, sizeof(int) * n_problems, hipMemcpyHostToDevice));
+    const void *yd = Y;
+    long long ldd = ld;
+    if (!Y_is_device) {                                          // a host Y is copied whole (its n x n_cols part)
+        HIP_TRY(ws(55, (size_t)n * n_cols * es, &d_y));
+        HIP_TRY(hipMemcpy2D(d_y, (size_t)n_cols * es, Y, (size_t)ld * es, (size_t)n_cols * es, (size_t)n, hipMemcpyHostToDevice));
+        yd = d_y;
+        ldd = n_cols;
+    }
+    std::vector<double> rec((size_t)pc * B * pilot::BF_NOUT);
+    int not_conv = 0;
+    for (long long q0 = 0; q0 < n_problems; q0 += pc) {
+        const int nq = (int)std::min<long long>(pc, n_problems - q0);
+        HIP_TRY(hipMemcpy(d_idx, idx + (size_t)q0 * n * B, (size_t)nq * per_problem, hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)nq, (unsigned)((B + 63) / 64));
+        if (dtype == 0)
+            hipLaunchKernelGGL(pilot::bootfit_kernel<float>, grid, dim3(pilot::TF_BLOCK), 0, nullptr, static_cast<const float *>(yd), ldd,
+                               d_u, d_idx, d_pm + q0, d_pm + n_problems + q0, B, d_args, d_out);
+        else
+            hipLaunchKernelGGL(pilot::bootfit_kernel<double>, grid, dim3(pilot::TF_BLOCK), 0, nullptr, static_cast<const double *>(yd),
+                               ldd, d_u, d_idx, d_pm + q0, d_pm + n_problems + q0, B, d_args, d_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(rec.data(), d_out, sizeof(double) * (size_t)nq * B * pilot::BF_NOUT, hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < (size_t)nq * B; ++j) {
+            const double *r = rec.data() + j * pilot::BF_NOUT;
+            const size_t f = (size_t)q0 * B + j;
+            for (int c = 0; c < 3; ++c) params[f * 3 + c] = r[pilot::BF_O_PARAMS + c];
+            if (sigma) sigma[f] = r[pilot::BF_O_SIGMA];
+            if (steps) steps[f] = (int)r[pilot::BF_O_STEPS];
+            if (flags) flags[f] = (int)r[pilot::BF_O_FLAGS];
+            not_conv += ((int)r[pilot::BF_O_FLAGS] & PILOT_OT_TRAJFIT_NOT_CONVERGED) != 0;
+        }
+    }
+    if (n_not_converged) *n_not_converged = not_conv;
+    return PILOT_OT_OK;
+}

@@ -824,3 +824,54 @@ def trajectory_fits(Y, x, model="ols", epsilon=1.35, pval_thr=0.05, modify_r2=Fa
         info["not_converged"] = nnc.value
         return fits, info
     return fits
+
+
+def bootstrap_huber_fits(Y, x, cols, models, idx, epsilon=1.35, return_info=False):
+    """Batched bootstrap Huber fits on the device (K10; include/pilot_ot.h, "bootstrap Huber fits"): problem q fits column
+    ``cols[q]`` of ``Y`` (n observations x targets, float32 / float64, a numpy array or a :class:`DeviceMatrix`) with the
+    trajectory model ``models[q]`` (an index into :data:`TRAJFIT_MODELS`) B times, fit b regressing that column, in its own
+    order, on the resampled times ``x[idx[q, :, b]]`` (``idx``: problems x n x B ints in [0, n), observation-major; only x is
+    resampled, as in pilotpy's gene_cluster_differentiation).  Each fit is the optimum of scikit-learn's HuberRegressor objective
+    (``epsilon``, alpha 1e-4) by K9's method.  Returns ``params`` (problems x B x 3, on [1, f(x)]; the third slot NaN for the
+    two-coefficient models); with ``return_info`` also a dict of ``sigma``, ``steps``, ``flags`` (problems x B) and
+    ``not_converged`` (the count flagged ``_lib.TRAJFIT_NOT_CONVERGED``)."""
+    x = _as_f64(np.ravel(x), "x")
+    if isinstance(Y, DeviceMatrix):
+        if len(Y.shape) != 2 or Y.dtype not in (np.float32, np.float64):
+            raise ValueError("Y: a 2-D float32 / float64 DeviceMatrix, got %s %s" % (Y.shape, Y.dtype))
+        n, T = Y.shape
+        ptr, on_dev, ld, dtype, keep = ctypes.c_void_p(Y.ptr), 1, T, Y.dtype, None
+    else:
+        Y = np.asarray(Y)
+        if Y.ndim != 2:
+            raise ValueError("Y must be 2-D (observations x targets), got %s" % (Y.shape,))
+        if Y.dtype not in (np.float32, np.float64):
+            Y = Y.astype(np.float64)
+        if Y.strides[1] != Y.itemsize or Y.strides[0] % Y.itemsize or Y.strides[0] < 0:
+            Y = np.ascontiguousarray(Y)
+        n, T = Y.shape
+        ld = Y.strides[0] // Y.itemsize if n > 1 else T
+        ptr, on_dev, dtype, keep = ctypes.c_void_p(Y.ctypes.data), 0, Y.dtype, Y
+    if x.size != n:
+        raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
+    cols = np.ascontiguousarray(np.ravel(cols), dtype=np.int32)
+    models = np.ascontiguousarray(np.ravel(models), dtype=np.int32)
+    idx = np.asarray(idx)
+    if idx.ndim != 3 or idx.shape[0] != cols.size or idx.shape[1] != n:
+        raise ValueError("idx must be problems x n x B = %d x %d x B, got %s" % (cols.size, n, idx.shape))
+    if models.size != cols.size:
+        raise ValueError("models has %d entries for %d problems" % (models.size, cols.size))
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    P, B = cols.size, idx.shape[2]
+    params = np.empty((P, B, 3))
+    info = dict(sigma=np.empty((P, B)), steps=np.empty((P, B), dtype=np.int32), flags=np.empty((P, B), dtype=np.int32))
+    nnc = ctypes.c_int(0)
+    _lib.check(_lib.load().pilot_ot_bootstrap_huber_fits(
+        ptr, on_dev, 0 if dtype == np.float32 else 1, n, T, ld, _lib.dptr(x), P, _lib.iptr(cols), _lib.iptr(models), B,
+        _lib.iptr(idx), float(epsilon), _lib.dptr(params), _lib.dptr(info["sigma"]), _lib.iptr(info["steps"]),
+        _lib.iptr(info["flags"]), ctypes.byref(nnc)))
+    del keep
+    if return_info:
+        info["not_converged"] = nnc.value
+        return params, info
+    return params

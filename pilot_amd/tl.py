@@ -742,3 +742,300 @@ def _lib_check_normalize(X, cols, out):
     from . import _lib
     _lib.check(_lib.load().pilot_ot_normalize_log1p(X.ctypes.data, 0 if X.dtype == np.float32 else 1, X.shape[0], X.shape[1],
                                                     1e4, _lib.iptr(cols), int(cols.size), out.ctypes.data))
+
+
+# ---- gene-cluster differentiation (Gene_cluster_specific.py:8-201, Trajectory.py:1129-1172) --------------------------------
+_GCD_COLUMNS = ["gene", "cluster", "waldStat", "df", "pvalue", "FC", "Expression pattern", "fit-pvalue", "fit-rsquared",
+                "fit-mod-rsquared"]
+_GCD_TABLE_COLUMNS = ("Gene ID", "Fitted function", "Intercept", "Treat", "Expression pattern", "adjusted P-value", "R-squared",
+                      "mod_rsquared_adj")
+
+
+def _gcd_features(model, x, fill):
+    """[1, f(x)] (generate_feature) or, with ``fill``, [1, x or 0, x^2 or 0] (generate_feature_by_fill_empty), as the reference
+    builds them (np.append of a ones column)."""
+    x = np.asarray(x, dtype=np.float64)
+    if fill:
+        f = {"linear": np.column_stack((x, np.zeros(x.shape[0]))), "linear_quadratic": np.column_stack((x, np.power(x, 2))),
+             "quadratic": np.column_stack((np.zeros(x.shape[0]), np.power(x, 2)))}[model]
+    else:
+        f = {"linear": x.reshape(-1, 1), "linear_quadratic": np.column_stack((x, np.power(x, 2))),
+             "quadratic": np.power(x, 2).reshape(-1, 1)}[model]
+    return np.append(np.ones((len(f), 1)), f, axis=1)
+
+
+def _gcd_params(row):
+    """a table row's coefficients on [1, f(x)]: Intercept, Treat and, for linear_quadratic, Treat2 (the table may lack Treat2)"""
+    names = ["Intercept", "Treat", "Treat2"] if row["Fitted function"] == "linear_quadratic" else ["Intercept", "Treat"]
+    return np.asarray([float(row[k]) for k in names], dtype=np.float64)
+
+
+def _gcd_fill_betas(model, params):
+    """get_betas_by_table / get_betas_by_model: (Intercept, Feature, Feature2) with the model's missing slot 0"""
+    if model == "linear":
+        return [float(params[0]), float(params[1]), 0.0]
+    if model == "quadratic":
+        return [float(params[0]), 0.0, float(params[1])]
+    return [float(params[0]), float(params[1]), float(params[2])]
+
+
+def _gcd_draws(rs, sizes, n_bootstraps):
+    """make_bootstraps' resamples in call order: for each size n, ``n_bootstraps`` times np.random.choice(range(n), n,
+    replace=True) -- the same legacy stream as rs.randint(0, n, n) -- as an n x n_bootstraps int32 array (observation-major)."""
+    out = []
+    for n in sizes:
+        a = np.empty((n, n_bootstraps), dtype=np.int32)
+        for b in range(n_bootstraps):
+            a[:, b] = rs.randint(0, n, n)
+        out.append(a)
+    return out
+
+
+def _gcd_wald(polyline1, polyline2, betas, boot, log_fc_cutoff, eigen_thresh):
+    """The reference's Wald step for one row, with its numpy / scipy calls: betas (6), boot (B x 6 bootstrap betas).
+    Returns (waldStat, df, pvalue)."""
+    from scipy import stats
+    gene_covs = np.cov(np.ascontiguousarray(np.asarray(boot, dtype=np.float64).T), ddof=1)    # pandas' .cov() on the same layout
+    CC = np.concatenate((polyline1, polyline2 * -1), axis=1)
+    estFC = np.matmul(CC, np.array(betas, dtype=np.float64).reshape(6, 1))
+    est = np.sign(estFC) * np.maximum(0, np.abs(estFC) - log_fc_cutoff)
+    sigma = np.matmul(np.matmul(CC, gene_covs), CC.transpose())
+    ev, V = np.linalg.eig(sigma)
+    keep = ev / np.max(ev) > eigen_thresh
+    r = int(np.sum(keep))
+    half = np.matmul(V[keep].transpose(), np.diag(1 / np.sqrt(ev[keep])))      # rows of V: the reference's indexing
+    hs = np.matmul(est.transpose(), half)
+    stat = float(np.matmul(hs, hs.transpose()).ravel()[0].real)
+    return stat, r, float(stats.chi2.sf(stat, r))
+
+
+def _gcd_check_tables(tables, cluster_names):
+    for c in cluster_names:
+        if c not in tables:
+            raise KeyError("cluster %r has no table in `tables` (%s)" % (c, sorted(map(str, tables))))
+        missing = [k for k in _GCD_TABLE_COLUMNS if k not in tables[c].columns]
+        if missing:
+            raise ValueError("table of %r lacks the genes_importance columns %s" % (c, missing))
+        bad = set(tables[c]["Fitted function"]) - set(engine.TRAJFIT_MODELS)
+        if bad:
+            raise ValueError("table of %r: unknown fitted functions %s" % (c, sorted(map(str, bad))))
+
+
+def infer_gene_cluster_differentiation(adata, tables, gene_list=None, cluster_names=None, col="Time_score", fc_thr=1.5,
+                                       eigenThresh=1e-8, n_points=20, start=1, end=20, n_bootstraps=50, random_state=None,
+                                       sample_col="sampleID", col_cell="cell_types", normalize=True, return_info=False):
+    """infer_gene_cluster_differentiation (Gene_cluster_specific.py:8-201) without plots or files: for every gene of
+    ``gene_list`` and every cell type whose ``tables`` entry (cell type -> ``genes_importance`` table) lists it, a Wald test of
+    its trend there against the mean trend of the other cell types listing it, with a bootstrap covariance.  Returns the
+    ``extend_stats`` frame (columns ``gene, cluster, waldStat, df, pvalue, FC, Expression pattern, fit-pvalue, fit-rsquared,
+    fit-mod-rsquared``; numeric columns numeric).  A gene in one cell type gives the row (1, 1, 0.0, 0.0).
+
+    Cells come as in ``genes_importance`` (the cells of the type in ``adata.uns['orders']`` order, normalize_total(1e4) + log1p
+    on the device with ``normalize``), then sorted by ``col`` with numpy's quicksort as the reference's sort_values does.  The
+    mean curve's fit (``_fit_best_model_``, pval_thr 1) is ``engine.trajectory_fits(model="huber", pval_thr=1)``; each side's
+    ``n_bootstraps`` Huber fits regress the expression, in its own order, on resampled times (only x is resampled, as in the
+    reference) and run on the device (``engine.bootstrap_huber_fits``).  Every fit is the optimum of HuberRegressor's objective,
+    which scikit-learn can stop short of.  Resamples are drawn on the host in the reference's order: ``random_state=None`` uses
+    numpy's global legacy stream (``np.random.seed(s)`` then this call draws what the reference draws), an int seeds a private
+    ``np.random.RandomState``.  The Wald step runs on the host with the reference's numpy / scipy calls.  A row whose bootstrap
+    fits did not all converge, or whose mean curve has no eligible model (the reference crashes there), gets NaN ``waldStat`` and
+    ``pvalue`` and ``df`` 0 (the latter also a NaN ``FC``); ``return_info`` adds a dict with their counts and timings, each Wald
+    row's mean-curve model (``table2``, its params ``table2_params``), the bootstrap betas (``boot``, rows x B x 6) and which of
+    its three mean-curve fits were flagged not converged (ineligible).  The mean
+    curve is a polynomial of degree <= 2, so linear_quadratic (and often another model) fits it exactly: the choice among exact
+    fits follows K9's rule, the first of linear, linear_quadratic, quadratic on a tie, a fit flagged not converged excluded."""
+    import time
+    from . import _lib
+    t_all = time.perf_counter()
+    n_points = int(n_points)
+    n_bootstraps = int(n_bootstraps)
+    if n_points < 3:
+        raise ValueError("n_points=%d: the mean-curve fit needs at least 3 distinct points" % n_points)
+    if n_bootstraps < 2:
+        raise ValueError("n_bootstraps=%d: the covariance needs at least 2 bootstraps" % n_bootstraps)
+    if not (np.isfinite(start) and np.isfinite(end)) or not end > start:
+        raise ValueError("start=%r, end=%r: need finite start < end" % (start, end))
+    if not (fc_thr > 0 and np.isfinite(fc_thr)):
+        raise ValueError("fc_thr=%r must be positive" % (fc_thr,))
+    cluster_names = list(tables) if cluster_names is None else list(cluster_names)
+    _gcd_check_tables(tables, cluster_names)
+    if gene_list is None:
+        gene_list = np.unique(np.concatenate([np.asarray(tables[c]["Gene ID"], dtype=object) for c in cluster_names])
+                              if cluster_names else np.array([], dtype=object))
+    gene_list = list(gene_list)
+    rows_of = {c: {g: i for i, g in reversed(list(enumerate(tables[c]["Gene ID"])))} for c in cluster_names}   # first row per gene
+    gene_dict = {g: [c for c in cluster_names if g in rows_of[c]] for g in gene_list}
+    if random_state is None:
+        rs = np.random.mtrand._rand
+    elif isinstance(random_state, np.random.RandomState):
+        rs = random_state
+    else:
+        rs = np.random.RandomState(random_state)
+    l2fc = np.log2(fc_thr)
+    log_fc_cutoff = np.log(np.power(2, l2fc))
+    pline = np.linspace(start, end, n_points)
+    orders = adata.uns["orders"]
+
+    # the rows, in the reference's order; the cells of every cell type that has a row
+    def trow(c, g):
+        return tables[c].iloc[rows_of[c][g]]
+    rows = []
+    for g in gene_list:
+        cl = gene_dict[g]
+        if len(cl) == 1:
+            rows.append((g, cl[0], None))
+        elif len(cl) > 1:
+            rows.extend((g, c, [o for o in cl if o != c]) for c in cl)
+    multi = [k for k, r in enumerate(rows) if r[2] is not None]
+    cells = {}
+    for k in multi:
+        c = rows[k][1]
+        if c not in cells:
+            rws, x = _cell_rows(adata, c, sample_col, col_cell, orders, col)
+            key = x.astype(orders[col].dtype) if np.asarray(orders[col]).dtype.kind in "iu" else x
+            o = np.argsort(key, kind="quicksort")           # data.sort_values(col): numpy's quicksort on the column
+            cells[c] = dict(rows=rws[o], x=x[o], genes=[])
+        if rows[k][0] not in cells[c]["genes"]:
+            cells[c]["genes"].append(rows[k][0])
+    for c, d in cells.items():
+        if d["x"].size < 1:
+            raise ValueError("cell type %r has no cells in adata.uns['orders']" % (c,))
+
+    # curves on pline: curve1 (the row's own fit) and the mean of the others' (table2's target)
+    curve1, ybar, model1 = [], [], []
+    for k in multi:
+        g, c, others = rows[k]
+        r1 = trow(c, g)
+        model1.append(r1["Fitted function"])
+        curve1.append(np.matmul(_gcd_features(model1[-1], pline, False), _gcd_params(r1)))
+        cs = []
+        for o in others:
+            ro = trow(o, g)
+            cs.append(np.matmul(_gcd_features(ro["Fitted function"], pline, False), _gcd_params(ro)))
+        ybar.append(np.mean(np.stack(cs), axis=0))
+
+    # host draws, in the reference's order (per row: the cell type's n, then n_points)
+    t0 = time.perf_counter()
+    sizes = []
+    for k in multi:
+        sizes += [cells[rows[k][1]]["x"].size, n_points]
+    draws = _gcd_draws(rs, sizes, n_bootstraps)
+    t_draw = time.perf_counter() - t0
+
+    # device: the mean curves' fits, then the bootstrap fits (per cell type, then all mean curves at once)
+    t0 = time.perf_counter()
+    R = len(multi)
+    ok = np.ones(R, dtype=bool)
+    no_t2 = np.zeros(R, dtype=bool)
+    boot = np.full((R, n_bootstraps, 6), np.nan)
+    model2 = [None] * R
+    params2 = np.full((R, 3), np.nan)
+    n_nc = 0
+    if R:
+        Ybar = np.ascontiguousarray(np.stack(ybar, axis=1))
+        t2, t2_info = engine.trajectory_fits(Ybar, pline, model="huber", pval_thr=1, return_info=True)
+        for j in range(R):
+            ch = int(t2["chosen"][j])
+            if ch < 0:
+                no_t2[j] = True
+                continue
+            model2[j] = engine.TRAJFIT_MODELS[ch]
+            params2[j] = t2["params"][j, ch]
+        for c, d in cells.items():
+            js = [j for j, k in enumerate(multi) if rows[k][1] == c]
+            gcol = np.asarray([list(adata.var_names).index(g) for g in d["genes"]], dtype=np.int32)
+            X = adata.X[d["rows"]]
+            X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
+            if X.dtype not in (np.float32, np.float64):
+                X = X.astype(np.float32)
+            X = np.ascontiguousarray(X)
+            if normalize:
+                Y = np.empty((X.shape[0], gcol.size), dtype=X.dtype)
+                _lib_check_normalize(X, gcol, Y)
+            else:
+                Y = np.ascontiguousarray(X[:, gcol])
+            pos = {g: i for i, g in enumerate(d["genes"])}
+            idx = np.stack([draws[2 * j] for j in js])
+            prm, inf = engine.bootstrap_huber_fits(
+                Y, d["x"], [pos[rows[multi[j]][0]] for j in js], [engine.TRAJFIT_MODELS.index(model1[j]) for j in js], idx,
+                return_info=True)
+            for q, j in enumerate(js):
+                boot[j, :, :3] = [_gcd_fill_betas(model1[j], p) for p in prm[q]]
+                ok[j] &= not (inf["flags"][q] & _lib.TRAJFIT_NOT_CONVERGED).any()
+            n_nc += inf["not_converged"]
+        js = [j for j in range(R) if not no_t2[j]]
+        if js:
+            prm, inf = engine.bootstrap_huber_fits(Ybar, pline, js, [engine.TRAJFIT_MODELS.index(model2[j]) for j in js],
+                                                   np.stack([draws[2 * j + 1] for j in js]), return_info=True)
+            for q, j in enumerate(js):
+                boot[j, :, 3:] = [_gcd_fill_betas(model2[j], p) for p in prm[q]]
+                ok[j] &= not (inf["flags"][q] & _lib.TRAJFIT_NOT_CONVERGED).any()
+            n_nc += inf["not_converged"]
+    t_dev = time.perf_counter() - t0
+
+    # host: the Wald step per row, then extend_stats
+    t0 = time.perf_counter()
+    out = []
+    j_of = {k: j for j, k in enumerate(multi)}
+    for k, (g, c, others) in enumerate(rows):
+        if others is None:
+            stat = [1.0, 1, 0.0, 0.0]
+        else:
+            j = j_of[k]
+            if no_t2[j]:
+                stat = [np.nan, 0, np.nan, np.nan]
+            else:
+                c2 = np.matmul(_gcd_features(model2[j], pline, False), params2[j][:3 if model2[j] == "linear_quadratic" else 2])
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    fc = float(np.log2(curve1[j].mean()) - np.log2(c2.mean()))
+                if not ok[j]:
+                    stat = [np.nan, 0, np.nan, fc]
+                else:
+                    betas = _gcd_fill_betas(model1[j], _gcd_params(trow(c, g))) + _gcd_fill_betas(model2[j], params2[j])
+                    w, r, pv = _gcd_wald(_gcd_features(model1[j], pline, True), _gcd_features(model2[j], pline, True), betas,
+                                         boot[j], log_fc_cutoff, eigenThresh)
+                    stat = [w, r, pv, fc]
+        tr = trow(c, g)
+        out.append([str(g), str(c)] + stat + [tr["Expression pattern"], float(tr["adjusted P-value"]), float(tr["R-squared"]),
+                                              float(tr["mod_rsquared_adj"])])
+    frame = pd.DataFrame(out, columns=_GCD_COLUMNS)
+    frame = frame.astype({"waldStat": np.float64, "df": np.int64, "pvalue": np.float64, "FC": np.float64,
+                          "fit-pvalue": np.float64, "fit-rsquared": np.float64, "fit-mod-rsquared": np.float64})
+    t_host = time.perf_counter() - t0
+    if not return_info:
+        return frame
+    info = dict(rows=len(rows), wald_rows=R, not_converged_rows=int((~ok & ~no_t2).sum()), no_table2_rows=int(no_t2.sum()),
+                not_converged_fits=int(n_nc), draw_s=t_draw, device_s=t_dev, wald_s=t_host,
+                total_s=time.perf_counter() - t_all, table2=list(model2), table2_params=params2, boot=boot,
+                table2_not_converged=(t2_info["flags"] & _lib.TRAJFIT_NOT_CONVERGED).astype(bool) if R else np.zeros((0, 3), bool))
+    return frame, info
+
+
+def _gcd_select_genes(tables, cellnames, sort, number_genes):
+    """gene_cluster_differentiation's gene list: per cell type, its table sorted by ``sort`` (ascending True, True, False) and
+    the first ``number_genes`` rows of every expression pattern; np.unique of them all."""
+    genes = []
+    for c in cellnames:
+        sel = tables[c].sort_values(sort, ascending=[True, True, False]).groupby("Expression pattern").head(number_genes)
+        genes.extend(sel["Gene ID"].tolist())
+    return np.unique(genes)
+
+
+def gene_cluster_differentiation(adata, tables, cellnames=(), sort=("Expression pattern", "adjusted P-value", "R-squared"),
+                                 number_genes=10, gene_list=(), **kw):
+    """gene_cluster_differentiation (Trajectory.py:1129-1172) without plots or files: the gene list from the ``tables`` of
+    ``cellnames`` (each sorted by ``sort``, the first ``number_genes`` genes of every expression pattern), or np.unique of
+    ``gene_list`` when given; start / end from min / max of ``adata.uns['orders']['Time_score']``; then
+    :func:`infer_gene_cluster_differentiation` (``**kw``: its other arguments).  Returns its frame."""
+    sort = list(sort)
+    if len(sort) != 3:
+        raise ValueError("sort=%r: three columns, sorted ascending, ascending, descending" % (sort,))
+    for c in cellnames:
+        if c not in tables:
+            raise KeyError("cell type %r has no table in `tables`" % (c,))
+    if len(gene_list) == 0:
+        genes = _gcd_select_genes(tables, list(cellnames), sort, number_genes)
+    else:
+        genes = np.unique(list(gene_list))
+    ts = adata.uns["orders"]["Time_score"]
+    return infer_gene_cluster_differentiation(adata, tables, gene_list=genes, start=min(ts), end=max(ts), **kw)

@@ -384,8 +384,10 @@ PILOT_API int pilot_ot_cost_matrix_dev_ex(const double *d_centroids, int K, int 
         return fail(PILOT_OT_EINVAL, "unknown metric id %d", metric);
     if (metric == PILOT_OT_METRIC_MAHALANOBIS && !d_aux) return fail(PILOT_OT_EINVAL, "mahalanobis needs the D x D inverse covariance (aux)");
     if (K > 4096 || D > 4096) return fail(PILOT_OT_ENOTSUP, "K=%d D=%d: at most 4096 centroids / dimensions", K, D);
-    hipLaunchKernelGGL(cost_matrix_kernel, dim3(1), dim3(1024), sizeof(double) * (2 * K + D),
-                       static_cast<hipStream_t>(stream), d_centroids, K, D, metric, d_aux, d_cost);
+    const size_t lds = sizeof(double) * (2 * (size_t)K + D);     // beyond 64 KiB whenever 2 K + D > 8192 (at most 96 KiB)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(cost_matrix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(cost_matrix_kernel, dim3(1), dim3(1024), lds, static_cast<hipStream_t>(stream), d_centroids, K, D, metric, d_aux,
+                       d_cost);
     HIP_TRY(hipGetLastError());
     return PILOT_OT_OK;
 }
@@ -399,6 +401,7 @@ PILOT_API int pilot_ot_cost_matrix_ex(const double *centroids, int K, int D, int
     if (K <= 0 || D <= 0) return fail(PILOT_OT_EINVAL, "K=%d D=%d must be positive", K, D);
     const bool has_aux = metric == PILOT_OT_METRIC_MAHALANOBIS;
     if (has_aux && !aux) return fail(PILOT_OT_EINVAL, "mahalanobis needs the D x D inverse covariance (aux)");
+    if (K > 4096 || D > 4096) return fail(PILOT_OT_ENOTSUP, "K=%d D=%d: at most 4096 centroids / dimensions", K, D);   // before any staging
     // staging from the calling thread's pool (slots 9 .. 11: the pre-pass calls use 0 .. 8)
     void *dx = nullptr, *dc = nullptr, *da = nullptr;
     HIP_TRY(ws_get(9, sizeof(double) * (size_t)K * D, &dx));

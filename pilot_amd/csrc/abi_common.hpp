@@ -1,4 +1,5 @@
-// Shared by the translation units that implement the C ABI (pilot_ot.hip, pilot_ot_multi.hip).
+// Shared by the translation units that implement the C ABI: error reporting, test switches, the per-thread pool of device
+// temporaries and the device limits every launch decision reads.  Host-side only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,10 +16,59 @@ int abi_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)
 const char *test_switch(const char *name);
 // release every cached multi-GPU context of the host-buffer entry points (called by pilot_ot_shutdown)
 void abi_multi_release();
-// a buffer of the calling thread's pool of device temporaries (grown on demand, released by pilot_ot_shutdown); slots 0 .. 11
-// belong to pilot_ot.hip, 12 .. 19 to pilot_ot_consumers.hip, 20 .. 35 to pilot_ot_plans.hip, 36 .. 47 to pilot_ot_diffmap.hip, 48 .. 51 to
-// pilot_ot_trajfit.hip, 52 .. 55 to pilot_ot_bootfit.hip
-hipError_t ws_buffer(int slot, size_t bytes, void **out);
+
+// The calling thread's pool of device temporaries: one buffer per slot, grown on demand, released by pilot_ot_shutdown.  Every
+// buffer of every translation unit has a slot of its own here, so two buffers that are live together (diffmap chains into the
+// consumer entry points) never share one.
+enum WsSlot {
+    WS_PREPASS_X, WS_PREPASS,                                                   // pilot_ot_prepass.hip
+    WS_COST_X, WS_COST_C, WS_COST_AUX,                                          // pilot_ot_cost.hip
+    WS_CONS_E, WS_CONS_D, WS_CONS_MAX, WS_CONS_LABELS, WS_CONS_SIZES, WS_CONS_SCORES, WS_CONS_K,   // pilot_ot_consumers.hip
+    WS_PLAN_P, WS_PLAN_M, WS_PLAN_PI, WS_PLAN_PJ, WS_PLAN_VAL, WS_PLAN_IT, WS_PLAN_FL, WS_PLAN_Q,    // pilot_ot_plans.hip
+    WS_PLAN_PLANS, WS_PLAN_SLAB, WS_PLAN_ROWMIN, WS_PLAN_KWS, WS_PLAN_ACC, WS_PLAN_GOFF, WS_PLAN_GIDX,
+    WS_DM_S, WS_DM_V, WS_DM_VEC, WS_DM_Z, WS_DM_PSI, WS_DM_E, WS_DM_D, WS_DM_K, WS_DM_MAX, WS_DM_OUT,  // pilot_ot_diffmap.hip
+    WS_TF_U, WS_TF_Y, WS_TF_OUT, WS_TF_COLS,                                    // pilot_ot_trajfit.hip
+    WS_BOOT_U, WS_BOOT_OUT, WS_BOOT_IDX, WS_BOOT_Y,                             // pilot_ot_bootfit.hip
+    WS_SLOTS
+};
+hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);
+// n elements of T (at least one) from `slot`
+template <typename T> hipError_t ws(WsSlot slot, size_t n, T **out) {
+    void *p = nullptr;
+    const hipError_t e = ws_buffer(slot, sizeof(T) * (n ? n : 1), &p);
+    *out = static_cast<T *>(p);
+    return e;
+}
+
+// device time of the calling thread's last pre-pass (pilot_ot_prepass_device_ms): two events on the launch stream
+struct PrepassClock {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false;
+    void release() { for (auto &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; } valid = false; }
+    void start() {
+        valid = false;
+        if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) { release(); return; }
+        (void)hipEventRecord(ev[0], nullptr);
+    }
+    void stop() { if (ev[1]) valid = hipEventRecord(ev[1], nullptr) == hipSuccess; }
+};
+PrepassClock &thread_clock();
+
+// compute units of the current device (256 if the runtime cannot tell)
+int cu_count();
+// blocks of `block` threads for n items, at most 8 per CU
+inline int grid_for(long n, int block, int n_cu) {
+    long g = (n + block - 1) / block;
+    const long cap = (long)n_cu * 8;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+constexpr size_t LDS_BYTES = 160 * 1024;
+constexpr int MAX_K = 128;          // the MFMA pair-grid kernels (8 row-tiles of 16 cell types)
+constexpr int GENERIC_MAX_K = 2048;  // the reference-semantics fallback kernel (vectors in LDS)
+constexpr int EMD_MAX_K = 256;       // exact-OT kernel: 4 rows / columns per lane
+constexpr int WIDE_MAX_K = 256;      // sinkhorn_wide_kernel: 128 < K <= 256, eight waves per 16-pair tile
+
 // cell-level cohort, internal face used by the multi-device form (pilot_ot_multi.hip)
 int cell_enqueue_rows(pilot_ot_cell_cohort *c, double scale, double reg, int num_iter_max, double stop_thr, int check_period,
                       double f32_floor_ulps, int row_begin, int row_end, int row_step, size_t *n_out);
@@ -26,6 +76,8 @@ int cell_collect(pilot_ot_cell_cohort *c, size_t n_out, double *w2 /* nullable *
 void cell_buffers(pilot_ot_cell_cohort *c, double **d_w2, hipStream_t *stream);
 
 }  // namespace pilot
+
+#define fail(...) pilot::abi_fail(__VA_ARGS__)
 
 #define HIP_TRY(expr)                                                                                      \
     do {                                                                                                   \

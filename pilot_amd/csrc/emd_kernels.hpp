@@ -22,6 +22,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
+#include "abi_common.hpp"
 #include "plan_args.hpp"
 
 namespace pilot {
@@ -202,6 +205,26 @@ __host__ __device__ constexpr int emd_m_pitch(int K) { return K <= 64 ? 64 : K; 
 __host__ __device__ constexpr size_t emd_lds_bytes(int K) {
     return K > 128 ? sizeof(double) * (size_t)K
                    : sizeof(double) * ((size_t)K * emd_m_pitch(K) + K) + (K <= 64 ? (size_t)K * K + (size_t)K * emd_m_pitch(K) : 0);
+}
+// Launch geometry of the exact-OT kernels (host side; pilot_ot_emd.hip and the plan variants of pilot_ot_plans.hip).
+// emd_grid_kernel: workgroups of emd_waves(emd_nk(K)) waves, M (+ row minima) in LDS; resident workgroups per CU
+inline int emd_nk(int K) { return K <= 64 ? 1 : (K <= 128 ? 2 : (K <= 192 ? 3 : 4)); }
+inline int emd_wgs_per_cu(int K) {
+    if (K > 128) return 1;                      // cost matrix in global memory, 3-4 rows per lane: one workgroup per CU
+    const size_t lds = emd_lds_bytes(K);        // (M, row minima; K <= 64: + the per-column source order and its inverse)
+    int by_lds = (int)(LDS_BYTES / lds);
+    const int by_regs = K <= 64 ? 4 : 2;        // <= 64 VGPRs per lane: 4 x 8 or 2 x 16 waves = 8 per SIMD
+    if (by_lds > by_regs) by_lds = by_regs;
+    return by_lds < 1 ? 1 : by_lds;
+}
+// K <= 16: four pairs per wavefront (emd_multi_kernels.hpp).  PILOT_OT_EMD_MULTI=0: the one-pair-per-wave kernel instead (A/B and the
+// parity test between the two); =1 / =2 force the flow values into LDS / the global slab (default: LDS up to K = 15, where five or six
+// waves per SIMD still fit beside them; profiles/r05/emd_multi_probe.txt)
+constexpr int EMD_MULTI_MAX_K = 16;
+inline int emd_multi_mode(int K) {
+    const char *e = test_switch("PILOT_OT_EMD_MULTI");
+    if (e && *e) return atoi(e);
+    return K <= 15 ? 1 : 2;
 }
 #define EMD_FENCE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup")
 // Build switches (diagnostics and experiments only):

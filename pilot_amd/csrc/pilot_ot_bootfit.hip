@@ -13,21 +13,11 @@
 #include "abi_common.hpp"
 #include "bootfit_kernels.hpp"
 
-#define fail(...) pilot::abi_fail(__VA_ARGS__)
-
 namespace {
 
 constexpr size_t CHUNK_BYTES = size_t(256) << 20;      // index vectors on the device: at most this many bytes at a time
 constexpr int MAX_ITER = 100;                          // Newton steps per fit before PILOT_OT_TRAJFIT_NOT_CONVERGED (as K9)
 constexpr double HUBER_ALPHA = 1e-4;                   // scikit-learn's HuberRegressor default penalty
-
-// temporaries: slots 52 .. 55 of the calling thread's pool
-template <typename T> hipError_t ws(int slot, size_t n, T **p) {
-    void *v = nullptr;
-    const hipError_t e = pilot::ws_buffer(slot, sizeof(T) * (n ? n : 1), &v);
-    *p = static_cast<T *>(v);
-    return e;
-}
 
 // u = (x - m) / s of the base times and, per model, K9's basis (C, quad_k, quad_scale), coefficients on [1, f(x)] (R) and the
 // penalty alpha ||w||^2 written on gamma (pen) -- the parts of pilot_ot_trajfit.hip's prepare() that do not depend on the Gram.
@@ -126,10 +116,10 @@ PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int 
     int *d_idx, *d_pm;
     unsigned char *d_y = nullptr;
     const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
-    HIP_TRY(ws(52, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
+    HIP_TRY(pilot::ws(pilot::WS_BOOT_U, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
     const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
-    HIP_TRY(ws(53, (size_t)pc * B * pilot::BF_NOUT, &d_out));
-    HIP_TRY(ws(54, (size_t)pc * n * B + 2 * (size_t)n_problems, &d_idx));    // the chunk's indices, then cols and models
+    HIP_TRY(pilot::ws(pilot::WS_BOOT_OUT, (size_t)pc * B * pilot::BF_NOUT, &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_BOOT_IDX, (size_t)pc * n * B + 2 * (size_t)n_problems, &d_idx));    // the chunk's indices, then cols and models
     d_pm = d_idx + (size_t)pc * n * B;
     HIP_TRY(hipMemcpy(d_u, u.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
@@ -138,7 +128,7 @@ PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int 
     const void *yd = Y;
     long long ldd = ld;
     if (!Y_is_device) {                                          // a host Y is copied whole (its n x n_cols part)
-        HIP_TRY(ws(55, (size_t)n * n_cols * es, &d_y));
+        HIP_TRY(pilot::ws(pilot::WS_BOOT_Y, (size_t)n * n_cols * es, &d_y));
         HIP_TRY(hipMemcpy2D(d_y, (size_t)n_cols * es, Y, (size_t)ld * es, (size_t)n_cols * es, (size_t)n, hipMemcpyHostToDevice));
         yd = d_y;
         ldd = n_cols;

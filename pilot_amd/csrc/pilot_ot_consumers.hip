@@ -11,17 +11,7 @@
 #include "abi_common.hpp"
 #include "consumer_kernels.hpp"
 
-#define fail(...) pilot::abi_fail(__VA_ARGS__)
-
 namespace {
-// temporaries of the host entry points: slots 12 .. 19 of the calling thread's pool (no hipMalloc / hipFree per call)
-struct DevMem {
-    void *p = nullptr;
-    int slot;
-    explicit DevMem(int slot_) : slot(slot_) {}
-    hipError_t alloc(size_t bytes) { return pilot::ws_buffer(slot, bytes ? bytes : 1, &p); }
-    template <typename T> T *as() { return static_cast<T *>(p); }
-};
 int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 }  // namespace
 
@@ -96,16 +86,18 @@ int check_labels(const int *labels, int N, int n_clusters) {
 int silhouette_of_device_matrix(const double *d_D, const int *labels, int N, int n_clusters, double *score, double *samples, hipStream_t st) {
     int rc = check_labels(labels, N, n_clusters);
     if (rc != PILOT_OT_OK) return rc;
-    DevMem dL(15), dS(16), dO(17);
-    hipError_t e = dL.alloc(sizeof(int) * N);
-    if (e == hipSuccess) e = dS.alloc(sizeof(int) * n_clusters);
-    if (e == hipSuccess) e = dO.alloc(sizeof(double) * N);
-    if (e == hipSuccess) e = hipMemcpyAsync(dL.p, labels, sizeof(int) * N, hipMemcpyHostToDevice, st);
+    // temporaries of the host entry points come from the calling thread's pool (no hipMalloc / hipFree per call)
+    int *dL = nullptr, *dS = nullptr;
+    double *dO = nullptr;
+    hipError_t e = pilot::ws(pilot::WS_CONS_LABELS, N, &dL);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_SIZES, n_clusters, &dS);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_SCORES, N, &dO);
+    if (e == hipSuccess) e = hipMemcpyAsync(dL, labels, sizeof(int) * N, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    rc = pilot_ot_silhouette_dev(d_D, dL.as<int>(), N, n_clusters, dS.as<int>(), dO.as<double>(), st);
+    rc = pilot_ot_silhouette_dev(d_D, dL, N, n_clusters, dS, dO, st);
     if (rc != PILOT_OT_OK) return rc;
     std::vector<double> s(N);
-    HIP_TRY(hipMemcpyAsync(s.data(), dO.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s.data(), dO, sizeof(double) * N, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     double sum = 0.0;
     for (int i = 0; i < N; ++i) sum += s[i];          // np.mean order
@@ -118,16 +110,16 @@ int silhouette_of_device_matrix(const double *d_D, const int *labels, int N, int
 PILOT_API int pilot_ot_row_distances(const double *E, int N, int normalize_by_max, int metric, double *D) {
     if (!E || !D) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0) return fail(PILOT_OT_EINVAL, "N=%d must be positive", N);
-    DevMem dE(12), dD(13), dM(14);
+    double *dE = nullptr, *dD = nullptr, *dM = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = dE.alloc(bytes);
-    if (e == hipSuccess) e = dD.alloc(bytes);
-    if (e == hipSuccess) e = dM.alloc(8);
-    if (e == hipSuccess) e = hipMemcpy(dE.p, E, bytes, hipMemcpyHostToDevice);
+    hipError_t e = pilot::ws(pilot::WS_CONS_E, (size_t)N * N, &dE);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_MAX, 1, &dM);
+    if (e == hipSuccess) e = hipMemcpy(dE, E, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    int rc = pilot_ot_row_distances_dev(dE.as<double>(), N, normalize_by_max, metric, dD.as<double>(), dM.as<double>(), nullptr);
+    int rc = pilot_ot_row_distances_dev(dE, N, normalize_by_max, metric, dD, dM, nullptr);
     if (rc != PILOT_OT_OK) return rc;
-    HIP_TRY(hipMemcpy(D, dD.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(D, dD, bytes, hipMemcpyDeviceToHost));
     return PILOT_OT_OK;
 }
 
@@ -136,26 +128,26 @@ PILOT_API int pilot_ot_silhouette(const double *D, const int *labels, int N, int
     if (N <= 0 || n_clusters <= 0 || n_clusters > 4096) return fail(PILOT_OT_EINVAL, "N=%d n_clusters=%d out of range", N, n_clusters);
     int rc = check_labels(labels, N, n_clusters);
     if (rc != PILOT_OT_OK) return rc;
-    DevMem dD(13);
+    double *dD = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = dD.alloc(bytes);
-    if (e == hipSuccess) e = hipMemcpy(dD.p, D, bytes, hipMemcpyHostToDevice);
+    hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
+    if (e == hipSuccess) e = hipMemcpy(dD, D, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    return silhouette_of_device_matrix(dD.as<double>(), labels, N, n_clusters, score, samples, nullptr);
+    return silhouette_of_device_matrix(dD, labels, N, n_clusters, score, samples, nullptr);
 }
 
 PILOT_API int pilot_ot_knn_kernel(const double *D, int N, int k, double epsilon, double *Kmat) {
     if (!D || !Kmat) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0) return fail(PILOT_OT_EINVAL, "N=%d must be positive", N);
-    DevMem dD(13), dK(18);
+    double *dD = nullptr, *dK = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = dD.alloc(bytes);
-    if (e == hipSuccess) e = dK.alloc(bytes);
-    if (e == hipSuccess) e = hipMemcpy(dD.p, D, bytes, hipMemcpyHostToDevice);
+    hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_K, (size_t)N * N, &dK);
+    if (e == hipSuccess) e = hipMemcpy(dD, D, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    int rc = pilot_ot_knn_kernel_dev(dD.as<double>(), N, k, epsilon, dK.as<double>(), nullptr);
+    int rc = pilot_ot_knn_kernel_dev(dD, N, k, epsilon, dK, nullptr);
     if (rc != PILOT_OT_OK) return rc;
-    HIP_TRY(hipMemcpy(Kmat, dK.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(Kmat, dK, bytes, hipMemcpyDeviceToHost));
     return PILOT_OT_OK;
 }
 
@@ -166,15 +158,15 @@ PILOT_API int pilot_ot_silhouette_of_rows(const double *E, int E_is_device, int 
                                           int n_clusters, double *score, double *samples) {
     if (!E || !labels || !score) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0 || n_clusters <= 0 || n_clusters > 4096) return fail(PILOT_OT_EINVAL, "N=%d n_clusters=%d out of range", N, n_clusters);
-    DevMem dE(12), dD(13), dM(14);
+    double *dE = nullptr, *dD = nullptr, *dM = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = dD.alloc(bytes);
-    if (e == hipSuccess) e = dM.alloc(8);
-    if (e == hipSuccess && !E_is_device) { e = dE.alloc(bytes); if (e == hipSuccess) e = hipMemcpy(dE.p, E, bytes, hipMemcpyHostToDevice); }
+    hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_MAX, 1, &dM);
+    if (e == hipSuccess && !E_is_device) { e = pilot::ws(pilot::WS_CONS_E, (size_t)N * N, &dE); if (e == hipSuccess) e = hipMemcpy(dE, E, bytes, hipMemcpyHostToDevice); }
     if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    int rc = pilot_ot_row_distances_dev(E_is_device ? E : dE.as<double>(), N, normalize_by_max, metric, dD.as<double>(), dM.as<double>(), nullptr);
+    int rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, normalize_by_max, metric, dD, dM, nullptr);
     if (rc != PILOT_OT_OK) return rc;
-    return silhouette_of_device_matrix(dD.as<double>(), labels, N, n_clusters, score, samples, nullptr);
+    return silhouette_of_device_matrix(dD, labels, N, n_clusters, score, samples, nullptr);
 }
 
 // the dense part of pl.trajectory (pilotpy/plot/ploting.py:95-110): E / max(E) -> Euclidean row distances -> pydiffmap's k-nearest-
@@ -182,17 +174,17 @@ PILOT_API int pilot_ot_silhouette_of_rows(const double *E, int E_is_device, int 
 PILOT_API int pilot_ot_diffusion_kernel_of_rows(const double *E, int E_is_device, int N, int k, double epsilon, double *D_out, double *Kmat) {
     if (!E || !Kmat) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0) return fail(PILOT_OT_EINVAL, "N=%d must be positive", N);
-    DevMem dE(12), dD(13), dK(18), dM(14);
+    double *dE = nullptr, *dD = nullptr, *dK = nullptr, *dM = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = dD.alloc(bytes);
-    if (e == hipSuccess) e = dK.alloc(bytes);
-    if (e == hipSuccess) e = dM.alloc(8);
-    if (e == hipSuccess && !E_is_device) { e = dE.alloc(bytes); if (e == hipSuccess) e = hipMemcpy(dE.p, E, bytes, hipMemcpyHostToDevice); }
+    hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_K, (size_t)N * N, &dK);
+    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_MAX, 1, &dM);
+    if (e == hipSuccess && !E_is_device) { e = pilot::ws(pilot::WS_CONS_E, (size_t)N * N, &dE); if (e == hipSuccess) e = hipMemcpy(dE, E, bytes, hipMemcpyHostToDevice); }
     if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    int rc = pilot_ot_row_distances_dev(E_is_device ? E : dE.as<double>(), N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD.as<double>(), dM.as<double>(), nullptr);
-    if (rc == PILOT_OT_OK) rc = pilot_ot_knn_kernel_dev(dD.as<double>(), N, k, epsilon, dK.as<double>(), nullptr);
+    int rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);
+    if (rc == PILOT_OT_OK) rc = pilot_ot_knn_kernel_dev(dD, N, k, epsilon, dK, nullptr);
     if (rc != PILOT_OT_OK) return rc;
-    if (D_out) HIP_TRY(hipMemcpy(D_out, dD.p, bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(Kmat, dK.p, bytes, hipMemcpyDeviceToHost));
+    if (D_out) HIP_TRY(hipMemcpy(D_out, dD, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(Kmat, dK, bytes, hipMemcpyDeviceToHost));
     return PILOT_OT_OK;
 }

@@ -14,8 +14,6 @@
 #include "abi_common.hpp"
 #include "diffmap_kernels.hpp"
 
-#define fail(...) pilot::abi_fail(__VA_ARGS__)
-
 namespace {
 
 constexpr int MAX_BASIS = 1024;         // B = min(N, MAX_BASIS) Lanczos vectors (V: B x N f64)
@@ -24,14 +22,6 @@ constexpr int CHECK_EVERY = 8;          // Lanczos steps between two looks at th
 constexpr double RESID_TOL = 1e-12;     // |beta_j s_ji| of every wanted Ritz pair
 constexpr double BREAKDOWN_TOL = 1e-12; // |w| after re-orthogonalisation below which the Krylov space counts as invariant (|S| = 1)
 constexpr double DEGENERATE_MU = 1.0 - 1e-10;
-
-// temporaries: slots 36 .. 47 of the calling thread's pool (no hipMalloc / hipFree per call)
-template <typename T> hipError_t ws(int slot, size_t n, T **p) {
-    void *v = nullptr;
-    const hipError_t e = pilot::ws_buffer(slot, sizeof(T) * (n ? n : 1), &v);
-    *p = static_cast<T *>(v);
-    return e;
-}
 
 // Implicit QL with Wilkinson shifts on the symmetric tridiagonal matrix with diagonal d[0..n) and off-diagonal e[0..n-1)
 // (e[i] couples i and i + 1; e must have n entries, e[n-1] is scratch).  Eigenvalues overwrite d (unsorted); every rotation is
@@ -116,11 +106,11 @@ PILOT_API int pilot_ot_diffusion_map_dev(const double *d_K, int N, double epsilo
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     double *S, *V, *vec, *Zs, *psi;
-    HIP_TRY(ws(36, (size_t)N * N, &S));
-    HIP_TRY(ws(37, (size_t)B * N, &V));
-    HIP_TRY(ws(38, 5 * (size_t)N + 4 * (size_t)B + 1, &vec));
-    HIP_TRY(ws(39, (size_t)B * n_evecs + n_evecs, &Zs));
-    HIP_TRY(ws(40, (size_t)N * n_evecs, &psi));
+    HIP_TRY(pilot::ws(pilot::WS_DM_S, (size_t)N * N, &S));
+    HIP_TRY(pilot::ws(pilot::WS_DM_V, (size_t)B * N, &V));
+    HIP_TRY(pilot::ws(pilot::WS_DM_VEC, 5 * (size_t)N + 4 * (size_t)B + 1, &vec));
+    HIP_TRY(pilot::ws(pilot::WS_DM_Z, (size_t)B * n_evecs + n_evecs, &Zs));
+    HIP_TRY(pilot::ws(pilot::WS_DM_PSI, (size_t)N * n_evecs, &psi));
     double *w = vec, *qa = w + N, *wsc = qa + N, *dis = wsc + N, *phi = dis + N;
     double *h1 = phi + N, *h2 = h1 + B, *al = h2 + B, *be = al + B;
     int *n_restart = reinterpret_cast<int *>(be + B);
@@ -214,12 +204,12 @@ PILOT_API int pilot_ot_diffusion_map_of_rows(const double *E, int E_is_device, i
     if (k < 1) return fail(PILOT_OT_EINVAL, "k=%d must be positive", k);
     const size_t nn = (size_t)N * N, no = (size_t)N * n_evecs;
     double *dE = nullptr, *dD, *dK, *dM, *dOut;
-    HIP_TRY(ws(42, nn, &dD));
-    HIP_TRY(ws(43, nn, &dK));
-    HIP_TRY(ws(44, 1, &dM));
-    HIP_TRY(ws(45, 2 * no + n_evecs, &dOut));
+    HIP_TRY(pilot::ws(pilot::WS_DM_D, nn, &dD));
+    HIP_TRY(pilot::ws(pilot::WS_DM_K, nn, &dK));
+    HIP_TRY(pilot::ws(pilot::WS_DM_MAX, 1, &dM));
+    HIP_TRY(pilot::ws(pilot::WS_DM_OUT, 2 * no + n_evecs, &dOut));
     if (!E_is_device) {
-        HIP_TRY(ws(41, nn, &dE));
+        HIP_TRY(pilot::ws(pilot::WS_DM_E, nn, &dE));
         HIP_TRY(hipMemcpy(dE, E, sizeof(double) * nn, hipMemcpyHostToDevice));
     }
     rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);

@@ -34,8 +34,6 @@
 
 namespace {
 
-#define fail(...) pilot::abi_fail(__VA_ARGS__)
-
 struct RcclApi {
     void *h = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;

@@ -3,7 +3,7 @@
 // The pair grid computes every pair's plan and keeps only <M, Gamma>.  This translation unit compiles the same kernel sources
 // once more with PILOT_PLAN_TU defined, which turns them into plan-emitting variants with their own names (emd_grid_plan_kernel,
 // emd_generic_plan_kernel, sinkhorn_generic_plan_kernel) and an explicit pair list; the pair-grid kernels themselves are
-// defined in pilot_ot.hip only and their code does not depend on this file.
+// defined in pilot_ot_emd.hip / pilot_ot_sinkhorn.hip only and their code does not depend on this file.
 //
 // Pairs run in chunks: a chunk's plans land in a device scratch of at most PLAN_CHUNK_BYTES, and then either go to the host
 // (per-pair mode) or are added into the group accumulators (group mode, plan_group_sum_kernel) before the next chunk reuses it.
@@ -19,8 +19,6 @@
 #include "emd_kernels.hpp"
 #include "emd_generic_kernel.hpp"
 #include "generic_kernels.hpp"
-
-#define fail(...) pilot::abi_fail(__VA_ARGS__)
 
 namespace pilot {
 
@@ -61,34 +59,8 @@ namespace {
 
 // at most this many bytes of plans on the device at a time (the pool adds a quarter on top: under 1 GiB in all)
 constexpr size_t PLAN_CHUNK_BYTES = (size_t)768 << 20;
-constexpr size_t LDS_BYTES = 160 * 1024;
-constexpr int EMD_MAX_K = 256, GENERIC_MAX_K = 2048;
-
-// the launch geometry of pilot_ot_emd_grid_dev's one-wave-per-pair kernel (pilot_ot.hip)
-int emd_nk(int K) { return K <= 64 ? 1 : (K <= 128 ? 2 : (K <= 192 ? 3 : 4)); }
-int emd_wgs_per_cu(int K) {
-    if (K > 128) return 1;
-    int by_lds = (int)(LDS_BYTES / pilot::emd_lds_bytes(K));
-    const int by_regs = K <= 64 ? 4 : 2;
-    if (by_lds > by_regs) by_lds = by_regs;
-    return by_lds < 1 ? 1 : by_lds;
-}
-
-// device temporaries: slots 20 .. 35 of the calling thread's pool (grown on demand, released by pilot_ot_shutdown)
-enum Slot { S_P = 20, S_M, S_PI, S_PJ, S_VAL, S_IT, S_FL, S_Q, S_PLANS, S_SLAB, S_ROWMIN, S_KWS, S_ACC, S_GOFF, S_GIDX };
-template <typename T> hipError_t buf(int slot, size_t n, T **out) {
-    void *p = nullptr;
-    const hipError_t e = pilot::ws_buffer(slot, sizeof(T) * (n ? n : 1), &p);
-    *out = static_cast<T *>(p);
-    return e;
-}
-
-int n_cu() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
-    return n;
-}
+// the device limits and the launch geometry of pilot_ot_emd_grid_dev's one-wave-per-pair kernel (emd_kernels.hpp)
+using pilot::LDS_BYTES, pilot::EMD_MAX_K, pilot::GENERIC_MAX_K, pilot::emd_nk, pilot::emd_wgs_per_cu;
 
 }  // namespace
 
@@ -125,19 +97,19 @@ PILOT_API int pilot_ot_transport_plans(const double *P, int N, int K, const doub
     if (chunk < 1) chunk = 1;
     if (const char *e = pilot::test_switch("PILOT_OT_PLAN_CHUNK_PAIRS")) { const long v = atol(e); if (v > 0 && v < chunk) chunk = v; }   // (tests)
     if (chunk > n) chunk = n;
-    const int cus = n_cu();
+    const int cus = pilot::cu_count();
 
     double *dP, *dM, *dVal, *dPlans;
     int *dPI, *dPJ, *dIt, *dFl, *dQ;
-    HIP_TRY(buf(S_P, (size_t)N * K, &dP));
-    HIP_TRY(buf(S_M, (size_t)KK, &dM));
-    HIP_TRY(buf(S_PI, (size_t)n, &dPI));
-    HIP_TRY(buf(S_PJ, (size_t)n, &dPJ));
-    HIP_TRY(buf(S_VAL, (size_t)n, &dVal));
-    HIP_TRY(buf(S_IT, (size_t)n, &dIt));
-    HIP_TRY(buf(S_FL, (size_t)n, &dFl));
-    HIP_TRY(buf(S_Q, (size_t)pilot::EMD_NQ * pilot::EMD_Q_STRIDE, &dQ));
-    HIP_TRY(buf(S_PLANS, (size_t)chunk * KK, &dPlans));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_P, (size_t)N * K, &dP));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_M, (size_t)KK, &dM));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_PI, (size_t)n, &dPI));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_PJ, (size_t)n, &dPJ));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_VAL, (size_t)n, &dVal));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_IT, (size_t)n, &dIt));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_FL, (size_t)n, &dFl));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_Q, (size_t)pilot::EMD_NQ * pilot::EMD_Q_STRIDE, &dQ));
+    HIP_TRY(pilot::ws(pilot::WS_PLAN_PLANS, (size_t)chunk * KK, &dPlans));
     HIP_TRY(hipMemcpy(dP, P, sizeof(double) * (size_t)N * K, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dM, M, sizeof(double) * (size_t)KK, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dPI, pair_i, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
@@ -153,9 +125,9 @@ PILOT_API int pilot_ot_transport_plans(const double *P, int N, int K, const doub
         for (int g = 0; g < n_groups; ++g) goff[(size_t)g + 1] += goff[(size_t)g];
         std::vector<int> cur(goff.begin(), goff.end() - 1);
         for (long t = 0; t < n; ++t) gidx[(size_t)cur[(size_t)pair_group[t]]++] = (int)t;
-        HIP_TRY(buf(S_ACC, (size_t)n_groups * KK, &dAcc));
-        HIP_TRY(buf(S_GOFF, goff.size(), &dGoff));
-        HIP_TRY(buf(S_GIDX, (size_t)n, &dGidx));
+        HIP_TRY(pilot::ws(pilot::WS_PLAN_ACC, (size_t)n_groups * KK, &dAcc));
+        HIP_TRY(pilot::ws(pilot::WS_PLAN_GOFF, goff.size(), &dGoff));
+        HIP_TRY(pilot::ws(pilot::WS_PLAN_GIDX, (size_t)n, &dGidx));
         HIP_TRY(hipMemcpy(dGoff, goff.data(), sizeof(int) * goff.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dGidx, gidx.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(dAcc, 0, sizeof(double) * (size_t)n_groups * KK, nullptr));
@@ -178,21 +150,21 @@ PILOT_API int pilot_ot_transport_plans(const double *P, int N, int K, const doub
             wgs = (chunk + waves - 1) / waves;
             const long cap = (long)cus * emd_wgs_per_cu(K);
             if (wgs > cap) wgs = cap;
-            HIP_TRY(buf(S_SLAB, (size_t)wgs * waves * KK, &ep.f_slab));   // (each wave zeroes its own block first)
+            HIP_TRY(pilot::ws(pilot::WS_PLAN_SLAB, (size_t)wgs * waves * KK, &ep.f_slab));   // (each wave zeroes its own block first)
         } else {
             const size_t per_wg = sizeof(double) * pilot::emdg_slab_doubles(K);
             wgs = 2L * cus;
             while (wgs > 1 && per_wg * (size_t)wgs > ((size_t)8 << 30)) wgs /= 2;
             if (wgs > chunk) wgs = chunk;
             lds = pilot::emdg_lds_bytes(K);
-            HIP_TRY(buf(S_SLAB, pilot::emdg_slab_doubles(K) * (size_t)wgs, &ep.f_slab));
+            HIP_TRY(pilot::ws(pilot::WS_PLAN_SLAB, pilot::emdg_slab_doubles(K) * (size_t)wgs, &ep.f_slab));
             std::vector<double> rowmin((size_t)K);         // the initial row potentials min_j M_ij (exact on the host)
             for (int i = 0; i < K; ++i) {
                 double m = INFINITY;
                 for (int j = 0; j < K; ++j) m = M[(size_t)i * K + j] < m ? M[(size_t)i * K + j] : m;
                 rowmin[(size_t)i] = m;
             }
-            HIP_TRY(buf(S_ROWMIN, (size_t)K, &dRowmin));
+            HIP_TRY(pilot::ws(pilot::WS_PLAN_ROWMIN, (size_t)K, &dRowmin));
             HIP_TRY(hipMemcpy(dRowmin, rowmin.data(), sizeof(double) * (size_t)K, hipMemcpyHostToDevice));
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::emd_generic_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
@@ -209,7 +181,7 @@ PILOT_API int pilot_ot_transport_plans(const double *P, int N, int K, const doub
         gp.P = dP; gp.M = dM; gp.N = N; gp.K = K; gp.n_pairs = 0; gp.row_begin = 0; gp.row_step = 1;
         gp.reg = reg; gp.tau = tau; gp.stop_thr = stop_thr; gp.max_iter = num_iter_max; gp.period = check_period;
         gp.err = nullptr; gp.queue = dQ; gp.list = nullptr; gp.list_len = nullptr; gp.nsplit = nsplit;
-        HIP_TRY(buf(S_KWS, per / sizeof(double) * (size_t)wgs, &gp.kws));
+        HIP_TRY(pilot::ws(pilot::WS_PLAN_KWS, per / sizeof(double) * (size_t)wgs, &gp.kws));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::sinkhorn_generic_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
 

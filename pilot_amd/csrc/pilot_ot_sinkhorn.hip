@@ -1,0 +1,738 @@
+// Entropic OT over the pair grid (C ABI: precision selection, plans, pilot_ot_sinkhorn_grid*, graph replay and kernel timing;
+// include/pilot_ot.h).  Kernels: sinkhorn_kernels.hpp and its instantiations (sk_inst.hip, sk_wide.hip), generic_kernels.hpp.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <new>
+
+#include "abi_common.hpp"
+#include "grid_plan.hpp"
+#include "sinkhorn_launch.hpp"
+#include "generic_kernels.hpp"
+
+namespace {
+using pilot::LDS_BYTES, pilot::MAX_K, pilot::GENERIC_MAX_K, pilot::WIDE_MAX_K;
+constexpr int CTRL_INTS = pilot::CTRL_INTS;      // control block of a call: see pilot_ot_plan::track_count
+// ... followed by the two order histograms and, from a 128-byte boundary, the ticket counters of the fast launch's work queue
+constexpr int CTRL_SHARDS_AT = (CTRL_INTS + 2 * pilot::ORDER_NB + 31) / 32 * 32;
+constexpr int CTRL_SHARDS_TRACK_AT = CTRL_SHARDS_AT + pilot::QUEUE_SHARDS * pilot::QUEUE_SHARD_STRIDE;      // (the tracking launch's)
+constexpr int CTRL_BLOCK_INTS = CTRL_SHARDS_TRACK_AT + pilot::QUEUE_SHARDS * pilot::QUEUE_SHARD_STRIDE;
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// range of the fp16-split configuration (PILOT_OT_H_MAX_COST_OVER_REG: experiment switch of tools/f16x2_range_probe.py)
+static double h_max_cost_over_reg() {
+    const char *e = pilot::test_switch("PILOT_OT_H_MAX_COST_OVER_REG");
+    return e && *e ? atof(e) : pilot::H_MAX_COST_OVER_REG;
+}
+
+PILOT_API int pilot_ot_auto_precision(double max_cost_over_reg) {
+    // f32 keeps every Gibbs-kernel entry exp(-M/reg) a well-scaled normal number only while
+    // max(M)/reg stays clear of the f32 exponent range (ln FLT_MIN = -87.3); beyond ~60 the
+    // far-transport entries lose bits, so AUTO switches to the f64 kernel.
+    // Inside that range the f32 values are iterated with bf16-split products (PILOT_OT_PREC_BF16X3: f32-level rounding on
+    // the bf16 matrix pipe, measured 1.3x the f32-input MFMA path).
+    // While max(M)/reg <= 16 (PILOT's default reg = 0.1 on the max-normalised cost gives 10) every entry of 2^15 exp(-M/reg)
+    // is a fp16 pair good to <= 2^-15.9 relative (22 bits down to 11.8; see H_MAX_COST_OVER_REG) and the products run on 2-way fp16 splits (PILOT_OT_PREC_F16X2: half the MFMAs, a third of
+    // the split instructions of BF16X3; same stopping checks, same 1e-7 class distance to the fp64 oracle).
+    if (max_cost_over_reg <= h_max_cost_over_reg()) return PILOT_OT_PREC_F16X2;
+    return max_cost_over_reg <= 60.0 ? PILOT_OT_PREC_BF16X3 : PILOT_OT_PREC_F64;
+}
+
+namespace { bool split_fits_lds(int K, bool sym, int bands); }
+PILOT_API int pilot_ot_auto_precision_for(double max_cost_over_reg, int K, int cost_is_symmetric) {
+    int prec = pilot_ot_auto_precision(max_cost_over_reg);
+    if ((prec == PILOT_OT_PREC_BF16X3 || prec == PILOT_OT_PREC_F16X2) && !split_fits_lds(K, cost_is_symmetric != 0, 1)) prec = PILOT_OT_PREC_F32;
+    return prec;
+}
+
+// The one place where a requested precision becomes the precision a call runs (host, multi-device and device entry points):
+//  * exp(-max(M)/reg) outside the f64 range, or on request -> POT-literal kernel;
+//  * AUTO -> F16X2 / BF16X3 by range (F32 where the split images do not fit LDS), AUTO_MIXED beyond the f32 range;
+//  * an explicit f32-class precision beyond the f32 range (max(M)/reg > 60) would be off by up to 1e-4 on this path's
+//    distributions: it runs AUTO_MIXED as well -- explicit precisions are honoured inside their valid range only;
+//  * F16X2 outside its scaled domain (cost range, tau) -> BF16X3.
+PILOT_API int pilot_ot_resolve_precision(int precision, double max_cost_over_reg, int K, int cost_is_symmetric, double tau) {
+    if (precision == PILOT_OT_PREC_GENERIC || max_cost_over_reg > PILOT_OT_MAX_COST_OVER_REG) return PILOT_OT_PREC_GENERIC;
+    const bool f32_class = precision == PILOT_OT_PREC_F32 || precision == PILOT_OT_PREC_BF16X3 || precision == PILOT_OT_PREC_F16X2;
+    // (PILOT_OT_RAW_PRECISION=1, tests only: run an explicit f32-class precision outside its range as asked)
+    const char *raw = pilot::test_switch("PILOT_OT_RAW_PRECISION");
+    const bool promote = f32_class && max_cost_over_reg > 60.0 && !(raw && *raw && *raw != '0');
+    if (precision == PILOT_OT_PREC_AUTO || promote) {
+        precision = pilot_ot_auto_precision_for(max_cost_over_reg, K, cost_is_symmetric);
+        if (precision == PILOT_OT_PREC_F64) precision = PILOT_OT_PREC_AUTO_MIXED;    // f32 first, f64 for the pairs that need it
+    }
+    if (precision == PILOT_OT_PREC_F16X2 &&
+        (max_cost_over_reg > h_max_cost_over_reg() || tau > pilot::H_MAX_TAU || !split_fits_lds(K, cost_is_symmetric != 0, 1)))
+        precision = split_fits_lds(K, cost_is_symmetric != 0, 1) ? PILOT_OT_PREC_BF16X3 : PILOT_OT_PREC_F32;
+    return precision;
+}
+
+PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
+    if (!plan) return fail(PILOT_OT_EINVAL, "plan is NULL");
+    if (N <= 0 || K <= 0) return fail(PILOT_OT_EINVAL, "N=%d K=%d must be positive", N, K);
+    if (K > GENERIC_MAX_K) return fail(PILOT_OT_ENOTSUP, "K=%d > %d cell types", K, GENERIC_MAX_K);
+    if ((long long)N * N > 0x7fffffffLL) return fail(PILOT_OT_ENOTSUP, "N=%d: N*N overflows the pair index", N);
+    pilot_ot_plan *pl = new (std::nothrow) pilot_ot_plan();
+    if (!pl) return fail(PILOT_OT_EINVAL, "out of host memory");
+    pl->N = N; pl->K = K; pl->max_cost = 1.0;
+    pl->img = nullptr; pl->p_slot = nullptr; pl->track_list = nullptr; pl->track_count = nullptr;
+    pl->emd_counter = nullptr; pl->f_slab = nullptr; pl->f_slab_bytes = 0; pl->emdg_slab = nullptr; pl->emdg_wgs = 0; pl->n_cu = 256; pl->kws = nullptr; pl->generic_wgs = 0; pl->nan_list = nullptr; pl->nan_list_n = 0;
+    pl->wide_rec = nullptr; pl->wide_rec_n = 0;
+    pl->order_list = nullptr; pl->order_bucket = nullptr; pl->order_hist = nullptr;
+    pl->flags_ws = nullptr; pl->flags_ws_n = 0;
+    pl->timing = 0; pl->n_timed = 0; pl->n_calls = 0;
+    pl->graph_mode = 0; pl->gkey_seen = 0; pl->gstream = nullptr; pl->gexec = nullptr;
+    for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 4; ++j) pl->ev[i][j] = nullptr;
+    hipError_t e = hipGetDevice(&pl->device);
+    if (e == hipSuccess) pl->n_cu = pilot::cu_count();
+    const int kp = ((K + 31) / 32) * 32;
+    if (K <= MAX_K) {
+        const int rt = (K + 15) / 16;
+        size_t img_bytes = pilot::img_elems(pilot::CFG_F64, rt) * sizeof(double);
+        const size_t b32 = pilot::img_elems(pilot::CFG_F32, rt) * sizeof(float), bs = pilot::img_elems(pilot::CFG_S32, rt) * sizeof(float);
+        const size_t bh = pilot::img_elems(pilot::CFG_H32, rt) * sizeof(float);
+        if (b32 > img_bytes) img_bytes = b32;
+        if (bs > img_bytes) img_bytes = bs;
+        if (bh > img_bytes) img_bytes = bh;
+        if (e == hipSuccess) e = hipMalloc(&pl->img, img_bytes);
+    } else if (K <= WIDE_MAX_K) {       // the 8-waves-per-tile kernel: the fp16-split operand block at 16 row-tiles
+        if (e == hipSuccess) e = hipMalloc(&pl->img, pilot::img_elems(pilot::CFG_H32, 16) * sizeof(float));
+    }
+    {
+        // proportions in slot order + one stop threshold per patient: sized for f64 at the padded K; the fp16-split configuration keeps
+        // TWO f32 copies there (plain, and in its scaled domain) -- the same bytes up to K = 128, more with the 16 row-tiles of the
+        // eight-waves-per-tile kernel
+        size_t p_bytes = sizeof(double) * ((size_t)N * kp + N);
+        if (K > MAX_K && K <= WIDE_MAX_K) { const size_t two = 2 * sizeof(float) * ((size_t)N * 256 + N); p_bytes = two > p_bytes ? two : p_bytes; }
+        if (e == hipSuccess) e = hipMalloc(&pl->p_slot, p_bytes);
+    }
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->track_list), sizeof(int) * (size_t)N * N);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->track_count), CTRL_BLOCK_INTS * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_list), sizeof(int) * (size_t)N * N);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_bucket), (size_t)N * N);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->emd_counter), pilot::emd_counter_bytes());
+    // per-pair work lists of the full grid, so that no grid call allocates (the POT-literal kernel's scratch, 2 K^2 doubles per
+    // resident workgroup, is the exception: allocated by the first call that needs that kernel)
+    // (two lists of N^2: pairs that ended in NaN, and pairs the f32 passes hand to the f64 pass)
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->nan_list), 2 * sizeof(int) * (size_t)N * N);
+    if (e == hipSuccess) pl->nan_list_n = (size_t)N * N;
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)N * N);
+    if (e == hipSuccess) pl->flags_ws_n = (size_t)N * N;
+    if (e != hipSuccess) {
+        pilot_ot_plan_destroy(pl);
+        return fail(PILOT_OT_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
+    }
+    *plan = pl;
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_plan_set_max_cost(pilot_ot_plan *pl, double max_cost) {
+    if (!pl) return fail(PILOT_OT_EINVAL, "plan is NULL");
+    if (!(max_cost > 0.0) || !std::isfinite(max_cost)) return fail(PILOT_OT_EINVAL, "max_cost=%g must be positive and finite", max_cost);
+    pl->max_cost = max_cost;
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_plan_destroy(pilot_ot_plan *pl) {
+    if (!pl) return PILOT_OT_OK;
+    if (pl->img) (void)hipFree(pl->img);
+    if (pl->p_slot) (void)hipFree(pl->p_slot);
+    if (pl->track_list) (void)hipFree(pl->track_list);
+    if (pl->track_count) (void)hipFree(pl->track_count);
+    if (pl->order_list) (void)hipFree(pl->order_list);
+    if (pl->order_bucket) (void)hipFree(pl->order_bucket);
+    if (pl->flags_ws) (void)hipFree(pl->flags_ws);
+    if (pl->emd_counter) (void)hipFree(pl->emd_counter);
+    if (pl->f_slab) (void)hipFree(pl->f_slab);
+    if (pl->emdg_slab) (void)hipFree(pl->emdg_slab);
+    if (pl->kws) (void)hipFree(pl->kws);
+    if (pl->nan_list) (void)hipFree(pl->nan_list);
+    if (pl->wide_rec) (void)hipFree(pl->wide_rec);
+    if (pl->gexec) (void)hipGraphExecDestroy(pl->gexec);
+    if (pl->gstream) (void)hipStreamDestroy(pl->gstream);
+    for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 4; ++j) if (pl->ev[i][j]) (void)hipEventDestroy(pl->ev[i][j]);
+    delete pl;
+    return PILOT_OT_OK;
+}
+
+namespace {
+
+int check_grid_args(int N, int K, double reg, int num_iter_max, double stop_thr, double tau, int check_period,
+                    int precision, int row_begin, int row_end, int row_step) {
+    if (N <= 0 || K <= 0) return fail(PILOT_OT_EINVAL, "N=%d K=%d must be positive", N, K);
+    if (!(reg > 0.0) || !std::isfinite(reg)) return fail(PILOT_OT_EINVAL, "reg=%g must be positive and finite", reg);
+    if (num_iter_max < 1) return fail(PILOT_OT_EINVAL, "num_iter_max=%d must be >= 1", num_iter_max);
+    if (check_period < 1) return fail(PILOT_OT_EINVAL, "check_period=%d must be >= 1", check_period);
+    if (!(stop_thr >= 0.0) || !(stop_thr < 1.0)) return fail(PILOT_OT_EINVAL, "stop_thr=%g must be in [0, 1)", stop_thr);
+    if (!(tau > 1.0)) return fail(PILOT_OT_EINVAL, "tau=%g must be > 1", tau);
+    if (precision < PILOT_OT_PREC_AUTO || precision > PILOT_OT_PREC_F16X2)
+        return fail(PILOT_OT_EINVAL, "unknown precision id %d", precision);
+    if (row_step < 1 || row_begin < 0 || row_end > N || row_begin > row_end)
+        return fail(PILOT_OT_EINVAL, "bad row range [%d, %d) step %d for N=%d", row_begin, row_end, row_step, N);
+    if (K > GENERIC_MAX_K) return fail(PILOT_OT_ENOTSUP, "K=%d > %d cell types", K, GENERIC_MAX_K);
+    return PILOT_OT_OK;
+}
+
+// The MFMA kernels iterate TOTAL scalings against the fixed Gibbs image exp(-M/reg) (POT's log-absorption is value-neutral
+// and only its bookkeeping is tracked), so max(M)/reg must stay inside the exponent range of the widest type: beyond ~600
+// an f64 Gibbs entry underflows / a total scaling overflows where POT's absorbed kernel would not.  Such calls, and K > 128,
+// go to the reference-semantics kernel (generic_kernels.hpp), which rebuilds the absorbed kernel like POT.
+constexpr double MAX_COST_OVER_REG = PILOT_OT_MAX_COST_OVER_REG;
+
+// list / list_len (device, nullable): only the listed pairs (NaN hand-over of the fast kernels); queue: zeroed counter
+int run_generic(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
+                int check_period, int row_begin, int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err, int *d_flags,
+                hipStream_t s, const int *list = nullptr, const int *list_len = nullptr, int *queue = nullptr) {
+    const int N = pl->N, K = pl->K;
+    const int n_pairs = n_rows * N;
+    if (n_pairs == 0) return PILOT_OT_OK;
+    // 8 vectors + nsplit rows of partial sums (as many as fit, a power of two <= the waves of a workgroup) + reduction scratch + queue slot
+    int nsplit = pilot::GENERIC_WAVES;
+    auto lds_for = [&](int ns) { return sizeof(double) * ((8 + (size_t)ns) * (size_t)K + pilot::GENERIC_WAVES) + 16; };
+    while (nsplit > 1 && lds_for(nsplit) > LDS_BYTES) nsplit /= 2;
+    const size_t lds = lds_for(nsplit);
+    if (lds > LDS_BYTES) return fail(PILOT_OT_ENOTSUP, "K=%d does not fit the generic kernel's LDS vectors", K);
+    if (!pl->kws) {
+        // two workgroups per CU, fewer when K' and its transpose would take more than 8 GB in all
+        int wgs = 3 * pl->n_cu;
+        const size_t per = sizeof(double) * 2 * (size_t)K * K;
+        while (wgs > 1 && per * wgs > ((size_t)8 << 30)) wgs /= 2;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->kws), per * wgs));
+        pl->generic_wgs = wgs;
+    }
+    if (!d_flags) {
+        if ((size_t)n_pairs > pl->flags_ws_n) {
+            if (pl->flags_ws) HIP_TRY(hipFree(pl->flags_ws));
+            pl->flags_ws = nullptr; pl->flags_ws_n = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)n_pairs));
+            pl->flags_ws_n = (size_t)n_pairs;
+        }
+        d_flags = pl->flags_ws;
+    }
+    if (!queue) { queue = pl->track_count; HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), s)); }
+    pilot::GenericParams g;
+    g.P = d_P; g.M = d_M; g.N = N; g.K = K; g.n_pairs = n_pairs; g.row_begin = row_begin; g.row_step = row_step;
+    g.reg = reg; g.tau = tau; g.stop_thr = stop_thr; g.max_iter = num_iter_max; g.period = check_period;
+    g.emd = d_emd; g.iters = d_iters; g.err = d_err; g.flags = d_flags; g.kws = pl->kws; g.queue = queue; g.nsplit = nsplit;
+    g.list = list; g.list_len = list_len;
+    int wgs = pl->generic_wgs < n_pairs ? pl->generic_wgs : n_pairs;
+    if (list && wgs > 64) wgs = 64;          // a hand-over list is short (usually empty)
+    if (const char *e = pilot::test_switch("PILOT_OT_GENERIC_WGS")) { const int w = atoi(e); if (w > 0 && w < wgs) wgs = w; }      // experiment switch
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::sinkhorn_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(pilot::sinkhorn_generic_kernel, dim3(wgs), dim3(pilot::GENERIC_WG), lds, s, g);
+    HIP_TRY(hipGetLastError());
+    return PILOT_OT_OK;
+}
+
+// resident workgroups per CU of the single-tile stream kernel (mirrors pilot::min_waves_per_simd)
+int stream_min_waves(int w /* sizeof(T)/4 */, int RT, bool sym, bool track, int tv, bool split, bool half = false) {
+    if (half && !track && RT <= pilot::HALF_OCC4_MAX_RT) return 4;
+    if (split) return RT <= (track ? pilot::SPLIT_OCC2_MAX_RT_TRACK : (half ? pilot::HALF_OCC2_MAX_RT : pilot::SPLIT_OCC2_MAX_RT)) ? 2 : 1;
+    const int na = RT * 4 * RT * w;
+    const bool greg = !split && sym && na <= pilot::GREG_MAX;
+    const int regs = (track ? 7 : 5) * RT * 4 * w + 4 * w + 56 + (tv ? 24 * w : 0) + (split ? 3 * ((RT + 1) / 2) * 4 + 24 : 0) +
+                     (greg ? na + 2 * tv * ((RT - 1) * 4 + 1) * w : 0);
+    return regs <= 128 ? 4 : (regs <= 168 ? 3 : (regs <= 256 ? 2 : 1));
+}
+// mirrors pilot::solo_in_stream: does the fast launch of this configuration carry the one-wave-per-pair path?
+bool stream_has_solo(int w, int RT, bool sym, int tv, bool split, bool half) {
+    const int mw = stream_min_waves(w, RT, sym, false, tv, split, half);
+    const int budget = mw >= 4 ? 128 : (mw == 3 ? 168 : 256);
+    return sym && RT <= 4 && !(half && RT < pilot::HALF_SOLO_MIN_RT) && (64 + 45) * w <= budget;
+}
+
+// LDS of one stream-kernel workgroup: operand image(s) + first-product table + tail weights + one ring of finished pairs
+// per wave.  The ring gets as many slots (<= 16) as fit while `want` workgroups stay resident per CU; at least 4.
+struct StreamLds { size_t bytes; int ring, wgs_per_cu; };
+StreamLds stream_lds(size_t fixed, size_t slot_bytes, int want, int min_ring = 4) {
+    StreamLds r;
+    for (;;) {
+        const size_t budget = LDS_BYTES / (size_t)want;
+        long ring = budget > fixed ? (long)((budget - fixed) / ((size_t)pilot::WAVES_PER_WG * slot_bytes)) : 0;
+        if (ring >= min_ring || want == 1) {
+            if (ring > pilot::RING_MAX) ring = pilot::RING_MAX;
+            if (ring < 1) ring = 0;
+            r.ring = (int)ring; r.wgs_per_cu = want;
+            r.bytes = fixed + (size_t)pilot::WAVES_PER_WG * slot_bytes * (size_t)ring;
+            return r;
+        }
+        --want;
+    }
+}
+
+// does the bf16-split configuration fit LDS at this K (operand image(s) + table + a minimal ring)?
+// (the fp16-split configuration needs less for its fast pass and the same for its tracking pass)
+bool split_fits_lds(int K, bool sym, int bands = 1) {
+    const int RT = (K + 15) / 16, KP = RT * 16;
+    const size_t fixed = (size_t)(sym ? 1 : 2) * pilot::form_elems_rt(pilot::CFG_S32, RT) * 4 * bands + (size_t)KP * 4 +
+                         (size_t)pilot::WAVES_PER_WG * pilot::HANDOVER_BUF * sizeof(int);
+    return fixed + (size_t)4 * pilot::WAVES_PER_WG * (2 * KP + 4) * 4 <= LDS_BYTES;
+}
+
+// cfg: pilot::CFG_F32 / CFG_F64 / CFG_S32 / CFG_H32 (all 16-pair tiles: TILE = 16, 4 accumulator registers, 4 lane groups)
+// CFG_H32 (fp16-split): the fast pass only; its tracking pass is the bf16-split kernel on the second operand block.
+// mixed (cfg == CFG_S32 only): small reg under PILOT_OT_PREC_AUTO -- every pair is first iterated in f32 (bf16-split
+// products, tau-tracking kernel); pairs whose plan may touch Gibbs entries outside the f32-safe range, or that went NaN, are
+// collected (ring_flush) and solved again by the f64 tracking kernel.
+int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg, int num_iter_max,
+             double stop_thr, double tau, int check_period, double floor_ulps, bool sym, int row_begin,
+             int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err, int *d_flags, hipStream_t s,
+             bool mixed = false) {
+    const bool f64 = cfg == pilot::CFG_F64, half = cfg == pilot::CFG_H32, split = cfg == pilot::CFG_S32 || half;
+    const size_t ts = f64 ? sizeof(double) : sizeof(float);
+    const int w = (int)(ts / 4);
+    constexpr int TILE = 16;
+    const int N = pl->N, K = pl->K;
+    const int RT = (K + TILE - 1) / TILE;
+    const int KP = RT * TILE;
+    const char *dbg = pilot::test_switch("PILOT_OT_DEBUG");
+    const int debug = dbg ? atoi(dbg) : 0;
+    const size_t form = pilot::form_elems_rt(cfg, RT);
+    // the per-wave hand-over buffers of the fast kernels
+    const size_t hb_bytes = (size_t)pilot::WAVES_PER_WG * pilot::HANDOVER_BUF * sizeof(int);
+    size_t fixed = (size_t)(sym ? 1 : 2) * form * ts + (size_t)KP * ts + hb_bytes;   // operand image(s) + first-product table + hand-over buffers
+    // K mod 16 in 1..4: the (at most four) cell types of the last row-tile are computed on the VALU (tail_rows)
+    int tv = 0;
+    // split: skip the dead registers of the last tile (beyond 4 row-tiles those variants run out of registers and spill
+    // 600-980 B per lane; the plain variants do not, and measure the same there)
+    const int live1 = (split && RT >= 2 && RT <= 4 && K - (RT - 1) * TILE <= 4) ? 1 : 0;
+    if (!split) {
+        const int n_tail = K - (RT - 1) * TILE;
+        // (RT = 8 variants spill: left on the MFMA path)
+        if (RT >= 2 && RT <= 7 && n_tail <= 4 && !(debug & 256)) tv = n_tail <= 2 ? 1 : 2;
+        const size_t tail_lds = (size_t)(sym ? 1 : 2) * tv * ((RT - 1) * 4 + 1) * 64 * 2 * ts;
+        if (tv && fixed + tail_lds + 4 * pilot::WAVES_PER_WG * (2 * KP + 4) * ts > LDS_BYTES) tv = 0;   // no room: MFMA path
+        if (tv) fixed += tail_lds;
+    }
+    const size_t slot_bytes = (size_t)(2 * KP + 4) * ts;
+    if (fixed + pilot::WAVES_PER_WG * slot_bytes > LDS_BYTES)
+        return fail(PILOT_OT_ENOTSUP, "K=%d with a %ssymmetric cost needs %zu B of LDS (> %zu) in this precision", K, sym ? "" : "non-",
+                    fixed + pilot::WAVES_PER_WG * slot_bytes, LDS_BYTES);
+    pl->order_hist = pl->track_count + CTRL_INTS;     // one control block, one memset per call
+    HIP_TRY(hipMemsetAsync(pl->track_count, 0, CTRL_BLOCK_INTS * sizeof(int), s));
+    void *img = pl->img;
+    void *Pt = pl->p_slot;
+    if (n_rows == 0) return PILOT_OT_OK;
+
+    const int n_pairs = n_rows * N;
+    if (!d_flags) {
+        if ((size_t)n_pairs > pl->flags_ws_n) {
+            if (pl->flags_ws) HIP_TRY(hipFree(pl->flags_ws));
+            pl->flags_ws = nullptr; pl->flags_ws_n = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)n_pairs));
+            pl->flags_ws_n = (size_t)n_pairs;
+        }
+        d_flags = pl->flags_ws;
+    }
+
+    pilot::GridParams p;
+    p.P = Pt; p.img = img; p.N = N; p.K = K;
+    p.n_pairs = n_pairs;
+    p.list = nullptr; p.list_len = nullptr;
+    p.solo_len = nullptr; p.solo_head = nullptr; p.solo_blocks = 0;
+    p.row_begin = row_begin; p.row_step = row_step;
+    p.max_iter = num_iter_max; p.period = check_period;
+    p.stop_thr = stop_thr; p.tau = tau; p.floor_ulps = floor_ulps;
+    p.emd = d_emd; p.iters = d_iters; p.err = d_err; p.flags = d_flags;
+    p.track_list = pl->track_list; p.track_count = pl->track_count; p.queue_head = pl->track_count + 1;
+    p.queue_shards = pl->track_count + CTRL_SHARDS_AT;       // (the fast launch up to two row-tiles; the tracking launch has its own, CTRL_SHARDS_TRACK_AT)
+    p.ring = 0;
+    p.fb_list = nullptr; p.fb_count = nullptr; p.bands = 1;
+    // pairs that end in NaN ("Numerical errors" in POT) are collected and re-solved by the POT-literal kernel, which
+    // returns the last good iterate like POT does
+    if ((size_t)n_pairs > pl->nan_list_n) {
+        if (pl->nan_list) HIP_TRY(hipFree(pl->nan_list));
+        pl->nan_list = nullptr; pl->nan_list_n = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->nan_list), 2 * sizeof(int) * (size_t)n_pairs));
+        pl->nan_list_n = (size_t)n_pairs;
+    }
+    p.nan_list = pl->nan_list; p.nan_count = pl->track_count + 10;
+    p.unequal = pl->track_count + pilot::CTRL_UNEQUAL;
+    // Between the fp16-split range and the two-band path (12 < max(M)/reg <= 60) a few pairs per matrix leave the f32 range in
+    // the single-band kernels (a scaling jumps past the fp16 domain within one update; products underflow at reg <= 0.025).
+    // They used to go to the POT-literal kernel with the other NaN pairs -- one workgroup per pair, 12.5 us per update: 3 to 13
+    // pairs cost 12 ms of a 30 ms call at reg 0.025 .. 0.0175.  They are collected like the small-reg path collects its
+    // hand-over and solved again by the f64 tracking kernel (symmetric cost, K <= 64: one wave per pair, 1.1 us per update).
+    const bool redo64 = !mixed && split && pl->max_cost / reg > 12.0 && !(debug & 4096);
+    // From max(M)/reg = 24 on nearly every pair tau-absorbs (c3: 28 % at 20, 94 % at 25) and the fast pass only hands its pairs
+    // over after a few dozen wasted updates (3.7 of 11.6 ms at reg 0.04): every pair goes to the tracking kernel at once, as
+    // in the two-band path.
+    const bool track_all = mixed || (split && !half && pl->max_cost / reg > 24.0 && !(debug & 8192));
+    int *const fb_list = pl->nan_list + pl->nan_list_n;
+    if (redo64) { p.fb_list = fb_list; p.fb_count = pl->track_count + 8; }
+    p.debug = debug;
+    const int tiles = (n_pairs + TILE - 1) / TILE;
+    // exact duplicates (a == b): one wave per pair in the leading workgroups of the fast launch (symmetric cost, K <= 64)
+    // ... while the grid is small.  A wave that iterates ONE pair has the shorter update (K = 50: 0.57 us against 0.77 us for a lone
+    // 16-pair wave), which is what a launch with fewer tiles than wave slots waits for (c2; the row shards of a multi-device call);
+    // on a full device the 600 diagonal pairs of c3 (165 updates on average, up to 301) on 600 waves of their own are a tail instead:
+    // main kernel 0.617 -> 0.584 ms with the duplicates in the tiles (tools/solo_probe.py; crossover between 5 600 and 7 500 tiles at 2 048
+    // wave slots).  The rule reads the FULL grid (N x N), not the rows of this call: a row shard and the full grid send the same pair
+    // down the same path, so their bits agree.
+    const long full_tiles = ((long)N * N + TILE - 1) / TILE;
+    const long wave_slots = (long)pl->n_cu * stream_min_waves(w, RT, sym, false, tv, split, half) * pilot::WAVES_PER_WG;
+    const bool solo = stream_has_solo(w, RT, sym, tv, split, half) && !(p.debug & 512) && !track_all && full_tiles < 3 * wave_slots;
+    int solo_blocks = 0;
+    {
+        // longest-first work order (see order_bucket_kernel)
+        int ob = (n_pairs + 1023) / 1024;
+        if (ob > pl->n_cu) ob = pl->n_cu;
+        int *split_ctl = pl->track_count + 4;
+        const int mode = (solo ? 2 : 0) | ((p.debug & 2) ? 4 : 0);   // bit 2: natural order (experiment)
+        HIP_TRY(pilot::launch_prep(cfg, d_M, K, RT, reg, img, d_P, Pt, N, (tv ? 1 : 0) | 2 | (mixed ? 4 : 0), stop_thr, floor_ulps, n_rows, row_begin, row_step,
+                                   pl->order_bucket, pl->order_hist, pl->order_list, split_ctl, pl->track_count + 1, mode, ob, s));
+        p.list = pl->order_list;
+        if (solo) {
+            solo_blocks = (n_rows + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;     // the diagonal; more duplicates queue up
+            if (solo_blocks > pl->n_cu) solo_blocks = pl->n_cu;
+            p.solo_len = split_ctl + 3; p.solo_head = pl->track_count + 3; p.solo_blocks = solo_blocks;
+        }
+    }
+    hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
+    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    // (fp16-split configuration, 112 < K <= 128, symmetric cost: four waves per tile, one tile per workgroup, two workgroups per CU)
+    const bool quad = half && pilot::quad_covers(K, sym) && !pilot::test_switch("PILOT_OT_NO_QUAD");
+    auto launch = [&](int tvv, bool track, int wgs, const StreamLds &L) -> hipError_t {
+        p.ring = L.ring;
+        if (tvv) return pilot::launch_stream_tv(cfg, tvv, RT, sym, track, dim3(wgs), L.bytes, s, p);
+        if (half && !track && quad) return pilot::launch_quad(dim3(wgs), s, p);
+        if (half && !track) return pilot::launch_stream_h32(RT, sym, live1, dim3(wgs), L.bytes, s, p);
+        if (split) return pilot::launch_stream_s32(RT, sym, track, live1, dim3(wgs), L.bytes, s, p);
+        return f64 ? pilot::launch_stream_f64(RT, sym, track, dim3(wgs), L.bytes, s, p)
+                   : pilot::launch_stream_f32(RT, sym, track, dim3(wgs), L.bytes, s, p);
+    };
+    // first pass: throughput kernel (pairs that would tau-absorb are handed to the second pass)
+    if (!track_all && quad) {
+        int wgs = 2 * pl->n_cu;
+        if (wgs > tiles) wgs = tiles;
+        HIP_TRY(launch(tv, false, wgs, StreamLds{}));
+    } else if (!track_all) {
+        int want = stream_min_waves(w, RT, sym, false, tv, split, half);
+        // (K <= 4: a third of the pairs tau-absorb and are handed over, and the hand-over's atomics and list stores are what more resident
+        // waves contend for -- K = 3 / 4 at N = 600: 0.60 / 0.64 ms at two workgroups per CU, 0.69 / 0.72 at four; from K = 5 on four win)
+        if (half && K <= 4 && want > 2) want = 2;
+        if ((p.debug >> 4) & 7) want = (p.debug >> 4) & 7;           // experiment: resident workgroups per CU
+        // split configurations up to 4 row-tiles flush their ring inline and park U in LDS meanwhile (pilot::parked_flush):
+        // one 16-byte line per lane and row-tile
+        const bool park = split && RT <= 4;
+        // (fp16-split configuration: ring slots and the park area hold packed pieces -- whole k-blocks, so an odd row-tile
+        // count rounds up)
+        const size_t slot_fast = half ? (size_t)pilot::ring_slot_stride<pilot::CfgH32x16>(RT) * ts : slot_bytes;
+        const size_t park_lane = half ? (size_t)pilot::park_lane_elems<pilot::CfgH32x16>(RT) : (size_t)RT * 4;
+        const size_t park_bytes = park ? (size_t)pilot::WAVES_PER_WG * park_lane * 64 * ts : 0;
+        if (fixed + park_bytes + pilot::WAVES_PER_WG * slot_fast > LDS_BYTES)
+            return fail(PILOT_OT_ENOTSUP, "K=%d: operand images + ring + park area exceed LDS", K);
+        const StreamLds L = stream_lds(fixed + park_bytes, slot_fast, want);
+        int wgs = pl->n_cu * L.wgs_per_cu;
+        const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
+        if (wgs > need) wgs = need;
+        wgs += solo_blocks;
+        HIP_TRY(launch(tv, false, wgs, L));
+    }
+    if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
+    // second pass: pairs in which POT would tau-absorb, with the absorption iterations tracked
+    p.list = pl->track_list; p.list_len = pl->track_count; p.queue_head = pl->track_count + 2;
+    p.queue_shards = pl->track_count + CTRL_SHARDS_TRACK_AT;     // (used by the tracking kernels up to two row-tiles)
+    p.solo_blocks = 0;
+    size_t fixed_t = fixed;
+    if (half) {     // tracking pass of the fp16-split configuration: the bf16-split kernel on its own operand block
+        p.img = static_cast<float *>(img) + pilot::track_img_elems(cfg, RT);
+        fixed_t = (size_t)(sym ? 1 : 2) * pilot::form_elems_rt(pilot::CFG_S32, RT) * ts + (size_t)KP * ts + hb_bytes;
+    }
+    if (track_all) { p.list = pl->order_list; p.list_len = nullptr; }     // EVERY pair goes through the tracking kernel (longest first)
+    if (mixed) {
+        // small reg: the Gibbs kernel in two exponent bands; pairs that still leave the f32 range are collected in track_list
+        // for the f64 pass
+        p.bands = 2;
+        p.fb_list = pl->track_list; p.fb_count = pl->track_count + 8;
+        fixed_t = (size_t)(sym ? 1 : 2) * form * ts * 2 + (size_t)KP * ts + hb_bytes;
+    }
+    {
+        // (the tracking kernel's result need not match the fast kernels' bits: a pair is always solved by one of them)
+        const int tv_t = RT <= 4 ? tv : 0;          // larger tracking variants spill with the tail rows
+        const StreamLds L = stream_lds(fixed_t, slot_bytes, stream_min_waves(w, RT, sym, true, tv_t, split));
+        int wgs_t = pl->n_cu * L.wgs_per_cu;
+        const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
+        if (wgs_t > need) wgs_t = need;
+        HIP_TRY(launch(tv_t, true, wgs_t, L));
+    }
+    if (mixed || redo64) {
+        // third pass: the collected pairs in f64 (operand images and proportions rebuilt for the f64 configuration in the
+        // same buffers -- the f32 passes are complete in stream order; no ordering, the list is short)
+        const int RT64 = RT;
+        const size_t form64 = pilot::form_elems_rt(pilot::CFG_F64, RT64);
+        const size_t fixed64 = (size_t)(sym ? 1 : 2) * form64 * sizeof(double) + (size_t)KP * sizeof(double);
+        const size_t slot64 = (size_t)(2 * KP + 4) * sizeof(double);
+        if (fixed64 + pilot::WAVES_PER_WG * slot64 > LDS_BYTES)
+            return fail(PILOT_OT_ENOTSUP, "K=%d: the f64 fallback needs %zu B of LDS", K, fixed64 + pilot::WAVES_PER_WG * slot64);
+        HIP_TRY(pilot::launch_prep(pilot::CFG_F64, d_M, K, RT64, reg, img, d_P, Pt, N, 2, stop_thr, floor_ulps, 0, row_begin, row_step,
+                                   pl->order_bucket, pl->order_hist, pl->order_list, pl->track_count + 4, pl->track_count + 1, 0, 1, s));
+        pilot::GridParams q = p;
+        q.list = mixed ? pl->track_list : fb_list; q.list_len = pl->track_count + 8; q.queue_head = pl->track_count + 9; q.queue_shards = nullptr;
+        q.img = img;                        // (the fp16-split configuration's tracking pass had moved it to its own block)
+        q.fb_list = nullptr; q.fb_count = nullptr; q.bands = 1;
+        q.nan_list = pl->nan_list; q.nan_count = pl->track_count + 10;
+        if (sym && K <= 64 && !(p.debug & 2048)) {
+            // the list is short (tens of pairs) and every pair on it runs long: one wave per pair, not 16-pair MFMA tiles
+            HIP_TRY(pilot::launch_solo_track_f64(dim3(64), s, q));
+        } else {
+            const StreamLds L = stream_lds(fixed64, slot64, stream_min_waves(2, RT64, sym, true, 0, false));
+            q.ring = L.ring;
+            int wgs_t = pl->n_cu * L.wgs_per_cu;
+            const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
+            if (wgs_t > need) wgs_t = need;
+            HIP_TRY(pilot::launch_stream_f64(RT64, sym, true, dim3(wgs_t), L.bytes, s, q));
+        }
+    }
+    if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
+    if (!(p.debug & 1024)) {
+        const int rc = run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters,
+                                   d_err, d_flags, s, pl->nan_list, pl->track_count + 10, pl->track_count + 11);
+        if (rc != PILOT_OT_OK) return rc;
+    }
+    return PILOT_OT_OK;
+}
+
+// 128 < K <= 256 with a symmetric cost inside the fp16-split range: sinkhorn_wide_kernel (wide_kernels.hpp) on the operand
+// block the ordinary prep kernel writes for 16 row-tiles, then the value kernel; hand-overs (tau-absorbing / NaN pairs, or
+// every pair when the histograms carry unequal mass) are solved by the POT-literal kernel like those of the stream kernels.
+int run_wide(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
+             int check_period, double floor_ulps, int row_begin, int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err,
+             int *d_flags, hipStream_t s) {
+    const int N = pl->N, K = pl->K, RT = 16;
+    // the records are 2 KB per pair: a big grid is solved in row chunks of at most WIDE_CHUNK_PAIRS pairs (1 GB of records),
+    // each a complete call of its own (same kernels, same pair -> same bits whatever the chunking)
+    long WIDE_CHUNK_PAIRS = 512L * 1024;
+    if (const char *e = pilot::test_switch("PILOT_OT_WIDE_CHUNK")) { const long v = atol(e); if (v > 0) WIDE_CHUNK_PAIRS = v; }     // (tests)
+    if ((long)n_rows * N > WIDE_CHUNK_PAIRS && n_rows > 1) {
+        const int rows_per = (int)(WIDE_CHUNK_PAIRS / N) > 0 ? (int)(WIDE_CHUNK_PAIRS / N) : 1;
+        for (int r0 = 0; r0 < n_rows; r0 += rows_per) {
+            const int nr = n_rows - r0 < rows_per ? n_rows - r0 : rows_per;
+            const size_t off = (size_t)r0 * N;
+            const int rc = run_wide(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, floor_ulps, row_begin + r0 * row_step, nr, row_step,
+                                    d_emd + off, d_iters ? d_iters + off : nullptr, d_err ? d_err + off : nullptr, d_flags ? d_flags + off : nullptr, s);
+            if (rc != PILOT_OT_OK) return rc;
+        }
+        return PILOT_OT_OK;
+    }
+    pl->order_hist = pl->track_count + CTRL_INTS;
+    HIP_TRY(hipMemsetAsync(pl->track_count, 0, (CTRL_INTS + 2 * pilot::ORDER_NB) * sizeof(int), s));
+    if (n_rows == 0) return PILOT_OT_OK;
+    const int n_pairs = n_rows * N;
+    if (!d_flags) {
+        if ((size_t)n_pairs > pl->flags_ws_n) {
+            if (pl->flags_ws) HIP_TRY(hipFree(pl->flags_ws));
+            pl->flags_ws = nullptr; pl->flags_ws_n = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)n_pairs));
+            pl->flags_ws_n = (size_t)n_pairs;
+        }
+        d_flags = pl->flags_ws;
+    }
+    if ((size_t)n_pairs > pl->nan_list_n) {
+        if (pl->nan_list) HIP_TRY(hipFree(pl->nan_list));
+        pl->nan_list = nullptr; pl->nan_list_n = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->nan_list), 2 * sizeof(int) * (size_t)n_pairs));
+        pl->nan_list_n = (size_t)n_pairs;
+    }
+    if ((size_t)n_pairs > pl->wide_rec_n) {     // (first call of this size: the one allocation of the path)
+        if (pl->wide_rec) HIP_TRY(hipFree(pl->wide_rec));
+        pl->wide_rec = nullptr; pl->wide_rec_n = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->wide_rec), sizeof(float) * pilot::wide_rec_elems() * (size_t)n_pairs));
+        pl->wide_rec_n = (size_t)n_pairs;
+    }
+    int ob = (n_pairs + 1023) / 1024;
+    if (ob > pl->n_cu) ob = pl->n_cu;
+    HIP_TRY(pilot::launch_prep(pilot::CFG_H32, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, 0, stop_thr, floor_ulps, n_rows, row_begin, row_step,
+                               pl->order_bucket, pl->order_hist, pl->order_list, pl->track_count + 4, pl->track_count + 1, 0, ob, s));
+    pilot::GridParams p;
+    p.P = pl->p_slot; p.img = pl->img; p.N = N; p.K = K;
+    p.n_pairs = n_pairs;
+    p.list = pl->order_list; p.list_len = nullptr;
+    p.solo_len = nullptr; p.solo_head = nullptr; p.solo_blocks = 0;
+    p.row_begin = row_begin; p.row_step = row_step;
+    p.max_iter = num_iter_max; p.period = check_period;
+    p.stop_thr = stop_thr; p.tau = tau; p.floor_ulps = floor_ulps;
+    p.emd = d_emd; p.iters = d_iters; p.err = d_err; p.flags = d_flags;
+    p.track_list = pl->track_list; p.track_count = pl->track_count; p.queue_head = pl->track_count + 1; p.queue_shards = nullptr;
+    p.ring = 0; p.bands = 1;
+    p.fb_list = nullptr; p.fb_count = nullptr;
+    p.nan_list = pl->nan_list; p.nan_count = pl->track_count + 10;
+    p.unequal = pl->track_count + pilot::CTRL_UNEQUAL;
+    p.debug = 0;
+    hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
+    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    const int tiles = (n_pairs + 15) / 16;
+    int wgs = pl->n_cu < tiles ? pl->n_cu : tiles;            // one 512-thread workgroup per CU (230 VGPRs: two waves per SIMD)
+    HIP_TRY(pilot::launch_wide(dim3(wgs), s, p, pl->wide_rec));
+    if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
+    int vwgs = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
+    if (vwgs > 2 * pl->n_cu) vwgs = 2 * pl->n_cu;
+    HIP_TRY(pilot::launch_wide_value(dim3(vwgs), s, p, pl->wide_rec));
+    if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
+    return run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
+                       d_flags, s, pl->nan_list, pl->track_count + 10, pl->track_count + 11);
+}
+
+}  // namespace
+
+PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg,
+                                         int num_iter_max, double stop_thr, double tau, int check_period,
+                                         int precision, double f32_floor_ulps, int cost_is_symmetric,
+                                         int row_begin, int row_end, int row_step, double *d_emd, int *d_iters,
+                                         double *d_err, int *d_flags, void *stream) {
+    if (!pl || !d_P || !d_M || !d_emd) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    int rc = check_grid_args(pl->N, pl->K, reg, num_iter_max, stop_thr, tau, check_period, precision, row_begin,
+                             row_end, row_step);
+    if (rc != PILOT_OT_OK) return rc;
+    {
+        const int n_rows_g = (row_end - row_begin + row_step - 1) / row_step;
+        // K beyond the MFMA kernels, a reg beyond the f64 range of exp(-M/reg) (judged by the plan's max_cost), or on request: POT's loop literally, absorbed kernel rebuilt per pair
+        // 128 < K <= 256 (the fixed Gibbs image no longer fits one wave's registers and LDS): eight waves per tile while the
+        // call is inside the fp16-split range with a symmetric cost; an explicit f64 / POT-literal request, a non-symmetric cost
+        // or a smaller reg keep the POT-literal kernel
+        if (pl->K > MAX_K && pl->K <= WIDE_MAX_K && cost_is_symmetric && precision != PILOT_OT_PREC_GENERIC && precision != PILOT_OT_PREC_F64 &&
+            pl->max_cost / reg <= h_max_cost_over_reg() && tau <= pilot::H_MAX_TAU && !pilot::test_switch("PILOT_OT_NO_WIDE")) {
+            if (!(f32_floor_ulps > 0.0)) f32_floor_ulps = 8.0;
+            return run_wide(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, row_begin, n_rows_g, row_step, d_emd,
+                            d_iters, d_err, d_flags, static_cast<hipStream_t>(stream));
+        }
+        if (precision == PILOT_OT_PREC_GENERIC || pl->K > MAX_K || pl->max_cost / reg > MAX_COST_OVER_REG)
+            return run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows_g, row_step, d_emd,
+                               d_iters, d_err, d_flags, static_cast<hipStream_t>(stream));
+    }
+    // (the range is judged by the plan's max_cost / reg: 1 / reg for Trajectory.py:101's normalised cost unless the caller said
+    // otherwise with pilot_ot_plan_set_max_cost; the host and multi-device entry points set it from the M they copy in)
+    precision = pilot_ot_resolve_precision(precision, pl->max_cost / reg, pl->K, cost_is_symmetric, tau);
+    bool mixed = false;
+    if (precision == PILOT_OT_PREC_AUTO_MIXED) {
+        precision = PILOT_OT_PREC_F64;
+        mixed = true;
+    }
+    // beyond the f32 range AUTO still tries f32 first, pair by pair, where the split images fit and POT's defaults hold
+    mixed = mixed && split_fits_lds(pl->K, cost_is_symmetric != 0, 2) && pl->max_cost / reg <= 140.0 && !pilot::test_switch("PILOT_OT_NO_MIXED");
+    if (!(f32_floor_ulps > 0.0)) f32_floor_ulps = 8.0;
+    const int n_rows = (row_end - row_begin + row_step - 1) / row_step;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int cfg = mixed ? pilot::CFG_S32
+                          : (precision == PILOT_OT_PREC_F32 ? pilot::CFG_F32
+                             : (precision == PILOT_OT_PREC_BF16X3 ? pilot::CFG_S32 : (precision == PILOT_OT_PREC_F16X2 ? pilot::CFG_H32 : pilot::CFG_F64)));
+    auto run = [&](hipStream_t on) {
+        int r = run_grid(cfg, pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, cost_is_symmetric != 0,
+                         row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags, on, mixed);
+        // a shape whose operand images do not fit LDS in this precision (non-symmetric cost at large K): the POT-literal
+        // kernel takes the whole grid -- the reference has no such limit
+        if (r == PILOT_OT_ENOTSUP)
+            r = run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
+                            d_flags, on);
+        return r;
+    };
+    if (!pl->graph_mode || pl->timing || n_rows == 0) return run(s);
+    // graph replay: the first call with a new argument set runs as usual (and grows the work buffers), the second one is
+    // captured, later ones replay the instantiated graph
+    const char *dbg = pilot::test_switch("PILOT_OT_DEBUG");
+    const pilot_ot_plan::GraphKey key = {d_P, d_M, d_emd, d_iters, d_err, d_flags, reg, stop_thr, tau, f32_floor_ulps, pl->max_cost, num_iter_max,
+                                         check_period, cfg, mixed ? 1 : 0, cost_is_symmetric != 0 ? 1 : 0, row_begin, n_rows, row_step,
+                                         dbg ? atoi(dbg) : 0};
+    if (pl->gexec && key == pl->gkey) {
+        HIP_TRY(hipGraphLaunch(pl->gexec, s));
+        return PILOT_OT_OK;
+    }
+    if (pl->gexec) { (void)hipGraphExecDestroy(pl->gexec); pl->gexec = nullptr; }
+    if (!(pl->gkey_seen && key == pl->gkey)) {
+        pl->gkey = key; pl->gkey_seen = 1;
+        return run(s);
+    }
+    if (!pl->gstream) HIP_TRY(hipStreamCreateWithFlags(&pl->gstream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamBeginCapture(pl->gstream, hipStreamCaptureModeThreadLocal));
+    rc = run(pl->gstream);
+    hipGraph_t graph = nullptr;
+    const hipError_t ce = hipStreamEndCapture(pl->gstream, &graph);
+    if (rc != PILOT_OT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (ce != hipSuccess) { (void)hipGetLastError(); return fail(PILOT_OT_EHIP, "graph capture failed: %s", hipGetErrorString(ce)); }
+    const hipError_t ie = hipGraphInstantiate(&pl->gexec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) { (void)hipGetLastError(); pl->gexec = nullptr; return fail(PILOT_OT_EHIP, "graph instantiation failed: %s", hipGetErrorString(ie)); }
+    HIP_TRY(hipGraphLaunch(pl->gexec, s));
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_plan_enable_graph(pilot_ot_plan *pl, int enable) {
+    if (!pl) return fail(PILOT_OT_EINVAL, "plan is NULL");
+    pl->graph_mode = enable ? 1 : 0;
+    if (!enable) {
+        if (pl->gexec) { (void)hipGraphExecDestroy(pl->gexec); pl->gexec = nullptr; }
+        pl->gkey_seen = 0;
+    }
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_sinkhorn_grid(const double *P, int N, int K, const double *M, double reg, int num_iter_max,
+                                     double stop_thr, double tau, int check_period, int precision,
+                                     double f32_floor_ulps, int cost_is_symmetric, int row_begin, int row_end,
+                                     int row_step, double *emd, int *iters, double *err, int *flags) {
+    if (!P || !M || !emd) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    int rc = check_grid_args(N, K, reg, num_iter_max, stop_thr, tau, check_period, precision, row_begin, row_end,
+                             row_step);
+    if (rc != PILOT_OT_OK) return rc;
+    double mx = 0.0;
+    for (size_t t = 0; t < (size_t)K * K; ++t) mx = M[t] > mx ? M[t] : mx;
+    precision = pilot_ot_resolve_precision(precision, mx / reg, K, cost_is_symmetric, tau);     // (max(M) is known here)
+    const int n_rows = (row_end - row_begin + row_step - 1) / row_step;
+    const size_t n_out = (size_t)n_rows * N;
+    if (n_out == 0) return PILOT_OT_OK;
+
+    const bool trace = pilot::test_switch("PILOT_OT_HOST_TRACE") != nullptr;       // (stage stamps on stderr: tools/host_to_host_probe.py)
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const auto t0 = now();
+    rc = pilot::host_ctx_prepare(N, K, n_out);
+    if (rc != PILOT_OT_OK) return rc;
+    pilot::HostCtx &h = pilot::thread_host();
+    hipError_t e = hipMemcpy(h.dP, P, sizeof(double) * (size_t)N * K, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h.dM, M, sizeof(double) * (size_t)K * K, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(PILOT_OT_EHIP, "H2D copy failed: %s", hipGetErrorString(e));
+    const auto t1 = now();
+    h.plan->max_cost = mx > 0.0 ? mx : 1.0;
+    rc = pilot_ot_sinkhorn_grid_dev(h.plan, h.dP, h.dM, reg, num_iter_max, stop_thr, tau, check_period, precision,
+                                    f32_floor_ulps, cost_is_symmetric, row_begin, row_end, row_step, h.dE,
+                                    iters ? h.dIt : nullptr, err ? h.dErr : nullptr, h.dFl, nullptr);
+    if (rc != PILOT_OT_OK) return rc;
+    const auto t2 = now();
+    if (trace) (void)hipStreamSynchronize(nullptr);
+    const auto t3 = now();
+    const pilot::Fetch f[4] = {{emd, h.dE, sizeof(double) * n_out}, {iters, h.dIt, sizeof(int) * n_out},
+                        {err, h.dErr, sizeof(double) * n_out}, {flags, h.dFl, sizeof(int) * n_out}};
+    rc = pilot::host_fetch(f, 4);
+    if (trace) fprintf(stderr, "pilot_ot_sinkhorn_grid: prepare + H2D %.0f us, enqueue %.0f us, device %.0f us, fetch %.0f us\n", us(t0, t1), us(t1, t2), us(t2, t3), us(t3, now()));
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+PILOT_API int pilot_ot_plan_enable_timing(pilot_ot_plan *pl, int enable) {
+    if (!pl) return fail(PILOT_OT_EINVAL, "plan is NULL");
+    if (enable)
+        for (int i = 0; i < TIMING_RING; ++i)
+            for (int j = 0; j < 4; ++j)
+                if (!pl->ev[i][j]) HIP_TRY(hipEventCreate(&pl->ev[i][j]));
+    pl->timing = enable > 0 ? enable : 0;       // n > 1: every n-th call is timed (four event records cost a 0.7 ms call 2 %)
+    pl->n_timed = 0; pl->n_calls = 0;
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_plan_kernel_times(pilot_ot_plan *pl, int max_n, float *main_ms, float *track_ms, int *n_out) {
+    if (!pl || !main_ms || !track_ms || !n_out) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    long n = pl->n_timed < TIMING_RING ? pl->n_timed : TIMING_RING;
+    if (n > max_n) n = max_n;
+    for (long t = 0; t < n; ++t) {
+        const long call = pl->n_timed - n + t;
+        hipEvent_t *ev = pl->ev[call % TIMING_RING];
+        HIP_TRY(hipEventElapsedTime(&main_ms[t], ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&track_ms[t], ev[2], ev[3]));
+    }
+    *n_out = (int)n;
+    return PILOT_OT_OK;
+}

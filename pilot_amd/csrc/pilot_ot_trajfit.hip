@@ -14,21 +14,11 @@
 #include "abi_common.hpp"
 #include "trajfit_kernels.hpp"
 
-#define fail(...) pilot::abi_fail(__VA_ARGS__)
-
 namespace {
 
 constexpr size_t CHUNK_BYTES = size_t(256) << 20;      // device copy of a host Y: at most this many bytes of columns at a time
 constexpr int MAX_ITER = 100;                          // Newton steps per (target, model) before PILOT_OT_TRAJFIT_NOT_CONVERGED
 constexpr double HUBER_ALPHA = 1e-4;                   // scikit-learn's HuberRegressor default penalty
-
-// temporaries: slots 48 .. 51 of the calling thread's pool
-template <typename T> hipError_t ws(int slot, size_t n, T **p) {
-    void *v = nullptr;
-    const hipError_t e = pilot::ws_buffer(slot, sizeof(T) * (n ? n : 1), &v);
-    *p = static_cast<T *>(v);
-    return e;
-}
 
 // inverse of a small symmetric positive definite matrix (Gauss-Jordan with partial pivoting; k <= 3)
 bool invert(int k, const double A[3][3], double X[3][3]) {
@@ -187,10 +177,10 @@ PILOT_API int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype
     double *d_u, *d_out;
     unsigned char *d_y = nullptr;
     const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
-    HIP_TRY(ws(48, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
+    HIP_TRY(pilot::ws(pilot::WS_TF_U, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
     const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
-    HIP_TRY(ws(50, (size_t)tc * pilot::TF_NOUT, &d_out));
-    if (!Y_is_device) HIP_TRY(ws(49, (size_t)n * tc * es, &d_y));
+    HIP_TRY(pilot::ws(pilot::WS_TF_OUT, (size_t)tc * pilot::TF_NOUT, &d_out));
+    if (!Y_is_device) HIP_TRY(pilot::ws(pilot::WS_TF_Y, (size_t)n * tc * es, &d_y));
     HIP_TRY(hipMemcpy(d_u, u.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
     std::vector<double> rec((size_t)tc * pilot::TF_NOUT);
@@ -255,9 +245,9 @@ PILOT_API int pilot_ot_normalize_log1p(const void *X, int dtype, int n, int n_ge
     const long long rows = std::max<long long>(1, std::min<long long>(n, (long long)(CHUNK_BYTES / ((size_t)(n_genes + n_cols) * es))));
     unsigned char *d_x, *d_o;
     int *d_cols;
-    HIP_TRY(ws(49, (size_t)rows * n_genes * es, &d_x));
-    HIP_TRY(ws(50, (size_t)rows * n_cols * es, &d_o));
-    HIP_TRY(ws(51, (size_t)n_cols, &d_cols));
+    HIP_TRY(pilot::ws(pilot::WS_TF_Y, (size_t)rows * n_genes * es, &d_x));
+    HIP_TRY(pilot::ws(pilot::WS_TF_OUT, (size_t)rows * n_cols * es, &d_o));
+    HIP_TRY(pilot::ws(pilot::WS_TF_COLS, (size_t)n_cols, &d_cols));
     HIP_TRY(hipMemcpy(d_cols, cols, sizeof(int) * n_cols, hipMemcpyHostToDevice));
     for (long long r0 = 0; r0 < n; r0 += rows) {
         const long long nr = std::min<long long>(rows, n - r0);

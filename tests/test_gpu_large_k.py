@@ -54,7 +54,7 @@ GENERIC_WAVES, LDS_BYTES = 16, 160 * 1024
 
 
 def _nsplit(K):
-    """run_generic (pilot_ot.hip): 8 vectors of K doubles, nsplit rows of K partial sums, GENERIC_WAVES reduction doubles and a
+    """run_generic (pilot_ot_sinkhorn.hip): 8 vectors of K doubles, nsplit rows of K partial sums, GENERIC_WAVES reduction doubles and a
     16-byte queue slot must fit 160 KiB of LDS -- lds(ns) = 8 ((8 + ns) K + 16) + 16 -- with nsplit the largest power of two
     <= 16 that fits.  16 -> 8 after K = 852, 8 -> 4 after 1278, 4 -> 2 after 1705, 2 -> 1 after 2046."""
     ns = GENERIC_WAVES

@@ -1,9 +1,10 @@
 #!/bin/bash
 # A/B builds of the Sinkhorn stream kernels: each argument is one set of -D flags for the translation units K2_PARTS
 # (default "8 9": the fp16-split configuration; "6 7": bf16-split).  GPU box.  K2_CFGS: bench configs (default "c2 c3").
-# K2_HOST=1: pilot_ot.hip is rebuilt with the same flags.
+# K2_HOST=1: pilot_ot_sinkhorn.hip is rebuilt with the same flags.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R/pilot_amd/csrc
+shopt -s extglob      # (build/!(X).o: every object of the library but the ones rebuilt here)
 PARTS=${K2_PARTS:-8 9}
 KEEP=$(mktemp /tmp/libpilot_ot.keep.XXXXXX.so)
 cp ../libpilot_ot.so "$KEEP"
@@ -19,12 +20,12 @@ for v in "$@"; do
       objs="$objs /tmp/sk_var_$part.o"
     else objs="$objs build/sk_inst_$part.o"; fi
   done
-  host=build/pilot_ot.o
+  host=build/pilot_ot_sinkhorn.o
   if [ -n "$K2_HOST" ]; then      # the flags also change constants the host mirrors (occupancy rules)
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 $v -c -o /tmp/pilot_ot_var.o pilot_ot.hip 2>/dev/null &
+    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 $v -c -o /tmp/pilot_ot_var.o pilot_ot_sinkhorn.hip 2>/dev/null &
     host=/tmp/pilot_ot_var.o
   fi
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libpilot_ot.so $host build/pilot_ot_multi.o build/pilot_ot_consumers.o build/sk_wide.o $objs -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libpilot_ot.so $host $objs build/!(pilot_ot_sinkhorn|sk_inst_*).o -ldl -lpthread
   run "$v"
 done

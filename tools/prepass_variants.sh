@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of pre-pass tuning constants (GPU): every build_variants/lib_*.so (pilot_ot.hip rebuilt with -DPILOT_GROUP_ROWS / -DPILOT_SELECT_*)
+# A/B of pre-pass tuning constants (GPU): every build_variants/lib_*.so (pilot_ot_prepass.hip rebuilt with -DPILOT_GROUP_ROWS / -DPILOT_SELECT_*)
 # under rocprofv3 --kernel-trace --stats with tools/prepass_probe.py; prints the kernels' average times per variant.
 #   tools/prepass_variants.sh <out dir> [probe args...]
 O=$1; shift

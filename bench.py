@@ -14,15 +14,20 @@ WORLD_SIZE, and the RCCL unique id travels through a temp file (pilot_amd/multi.
 
 Workload: BASELINE configs[2] at reg = 0.1 -- 600 patients x 50 cell types x 30 PCA dims, the configuration the metric
 is quoted on (it fits one GPU).  Total work is fixed as GPUs are added (the 600^2 pair grid is row-sharded
-round-robin), hence "scaling": "strong".  The line also carries, as extra keys: `value_host_to_host` (numpy in ->
-numpy out, SURVEY.md 8(d)'s definition of t), `reg_sweep` (reg 0.01 / 0.1 / 1.0 with parity against the oracle on a row
-sample), `exact_emd` (the reference's DEFAULT mode on the same cohort) and `c4` (2000 x 100, the shape that scales).
+round-robin), hence "scaling": "strong".
 
-`roofline` is for the dominant kernel (the MFMA pair-grid kernel): achieved = algorithmic flop of one launch / its mean
-duration (HIP events on the launch stream, recorded inside the timed region).  `cpu_baseline` is the CPU oracle (C fp64
-restatement of POT's loop) timed on this box's host cores on a bounded sample of the same workload (rank 0, 1 GPU);
-its all-cores leg covers the whole grid when that takes seconds (c3 does), and `parity` is then max|step output - oracle|
-over EVERY pair the step produced.
+A plain run does what the headline needs and no more: set up, warm up, time the steps, write --dump-outputs, print the
+line.  `roofline` is for the dominant kernel (the MFMA pair-grid kernel): achieved = algorithmic flop of one launch / its
+mean duration (HIP events on the launch stream, recorded inside the timed region), so it costs no run of its own.
+
+--full adds everything else the benchmark measures or checks, as extra keys: `value_host_to_host` (numpy in -> numpy
+out, SURVEY.md 8(d)'s definition of t), `precision_ladder`, `reg_sweep` (reg 0.01 / 0.1 / 1.0 with parity against the
+oracle on a row sample), `exact_emd` (the reference's DEFAULT mode on the same cohort), `c4` (2000 x 100, the shape
+that scales), `c5_cellw2`, `e2e_tl_s`, `prepass`, the collective's own `gather_ms`, and `cpu_baseline`: the CPU oracle
+(C fp64 restatement of POT's loop) timed on the host cores on a bounded sample of the same workload (rank 0, 1 GPU); its
+all-cores leg covers the whole grid when that takes seconds (c3 does), and `parity` is then max|step output - oracle|
+over EVERY pair the step produced.  --mode emd / cellw2 likewise time their CPU baselines only with --full.
+--no-extras / --no-cpu-baseline / --no-c5 leave parts of --full out.
 """
 from __future__ import annotations
 
@@ -128,15 +133,22 @@ def main():
     ap.add_argument("--precision", default="auto", choices=["auto", "fp32", "fp64", "bf16x3", "f16x2"])
     ap.add_argument("--mode", default="sinkhorn", choices=["sinkhorn", "emd", "cellw2"],
                     help="emd: time the exact-OT pair grid (the reference's default mode) instead; cellw2: the cell-level W2 "
-                         "extension at BASELINE config 5 (200 patients x 5000 cells x 30 dims; about two minutes at --steps 1, each further step one more pass)")
+                         "extension at BASELINE config 5 (200 patients x 5000 cells x 30 dims; each step one pass over the grid; "
+                         "--full adds the CPU oracle on a few of its pairs)")
     ap.add_argument("--cell-patients", type=int, default=200)
     ap.add_argument("--cell-cells", type=int, default=5000)
     ap.add_argument("--ramp-steps", type=int, default=-1,
                     help="untimed calls before the warm-up steps that bring the GPU clocks up from idle (0 to disable; "
                          "default: 150 for grids up to the size of c3, 5 beyond -- about 0.2 s either way)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_host_to_host / reg_sweep / exact_emd / c4 / c5_cellw2")
-    ap.add_argument("--no-c5", action="store_true", help="skip the c5_cellw2 key of the default line (one 35 s pass over BASELINE config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: CPU baselines and parity against the "
+                         "oracle, other precisions, regs, modes and configs, end-to-end and per-call figures (see the module "
+                         "docstring); off: the run does only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity legs they carry")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip value_host_to_host / precision_ladder / reg_sweep / exact_emd / c4 / c5_cellw2 / "
+                         "e2e_tl_s / prepass")
+    ap.add_argument("--no-c5", action="store_true", help="with --full: skip the c5_cellw2 key (one 35 s pass over BASELINE config 5)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU work budget of the baseline sample")
     ap.add_argument("--force-comm", action="store_true",
                     help="testing on a 1-GPU box: run the one-process-per-GPU path (RCCL communicator, all-gather, max over "
@@ -149,6 +161,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras
+    with_cpu = args.full and not args.no_cpu_baseline
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -179,11 +193,11 @@ def main():
         run_prec = "auto" if prec == "mixed" else prec
 
     if args.mode == "emd":
-        out = bench_emd(args, L, P, M, cfg)
+        out = bench_emd(args, L, P, M, cfg, with_cpu=with_cpu)
         print(json.dumps(out), flush=True)
         return
     if args.mode == "cellw2":
-        print(json.dumps(bench_cellw2(args, steps=args.steps, dump_dir=args.dump_outputs)), flush=True)
+        print(json.dumps(bench_cellw2(args, steps=args.steps, dump_dir=args.dump_outputs, with_cpu=with_cpu)), flush=True)
         return
 
     per_rank = None
@@ -270,19 +284,19 @@ def main():
             E = np.empty((N, N))
             _lib.check(L.pilot_ot_memcpy_d2h(E.ctypes.data, d_full.p, 8 * N * N))
             cnt, urank = comm.info()
-            # the collective alone (all-gather + row interleave of this rank's block), host-timed over a few calls
-            fence()
-            tg = time.perf_counter()
-            for _ in range(10):
-                comm.all_gather_rows(plan.dE, n_pad, N, d_stage.p, d_full.p)
-            fence()
-            gather_ms = 1e2 * (time.perf_counter() - tg)
             per_rank = {"rank0_kernel_ms": round(kern_ms, 4), "rank0_step_minus_kernel_ms": round(ms_per_step - kern_ms, 4),
                         "max_kernel_ms_over_ranks": round(comm.all_reduce_max(kern_ms), 4),
-                        "gather_ms": round(comm.all_reduce_max(gather_ms), 4),
                         "rccl_ranks": cnt, "rccl_user_rank": urank, "max_rank_seen": int(comm.all_reduce_max(float(rank))),
                         "rccl_note": "ncclCommCount / ncclCommUserRank of rank 0's communicator; max_rank_seen = all-reduce(max) of "
                                      "every rank's index"}
+            if args.full:
+                # the collective alone (all-gather + row interleave of this rank's block), host-timed over a few calls
+                fence()
+                tg = time.perf_counter()
+                for _ in range(10):
+                    comm.all_gather_rows(plan.dE, n_pad, N, d_stage.p, d_full.p)
+                fence()
+                per_rank["gather_ms"] = round(comm.all_reduce_max(1e2 * (time.perf_counter() - tg)), 4)
         else:
             E = plan.fetch(n_rows=N)[0]
     if args.dump_outputs and rank == 0:
@@ -321,7 +335,7 @@ def main():
         "value_device_resident": round(value, 1),
         "timed_region": "`value` (= value_device_resident): P, M resident in HBM -> N x N matrix resident in HBM on every rank, "
                         "as the bench contract prescribes; SURVEY 8(d)'s t (host arrays in -> host matrix out, PCIe inclusive) "
-                        "is `value_host_to_host`, measured in the same run",
+                        "is `value_host_to_host`, measured by the same command with --full",
         "clock_ramp_s": round(ramp_s, 3), "clock_ramp_steps": args.ramp_steps,
     }
     if per_rank:
@@ -330,10 +344,9 @@ def main():
         if fl:
             per_rank["predicted_floor"] = fl
         per_rank["scaling_note"] = ("strong scaling: total work fixed.  c3 (this line) is bounded by the serial update chain of its slowest "
-                                    "pairs, not by the collective (see predicted_floor); the `c4` key is the shape whose shards stay "
-                                    "long enough to scale linearly")
+                                    "pairs, not by the collective (see predicted_floor); the `c4` key (--full) is the shape whose shards "
+                                    "stay long enough to scale linearly")
 
-    extras = not args.no_extras
     if extras:
         # the shape that scales: every rank takes part, so it is measured at every N
         out["c4"] = bench_c4(L, rank, world, comm, args, single_process_multi)
@@ -342,16 +355,16 @@ def main():
             out["value_host_to_host"] = host_to_host(P, M, args.reg, run_prec)
             out["precision_ladder"] = precision_ladder(P, M, args.reg, args.config)
             out["reg_sweep"] = reg_sweep(P, M, K)
-            out["exact_emd"] = exact_emd_record(L, P, M, args.config, with_cpu=not args.no_cpu_baseline)
+            out["exact_emd"] = exact_emd_record(L, P, M, args.config, with_cpu=with_cpu)
             if args.config == "c3" and not args.no_c5:
-                c5 = bench_cellw2(args)       # BASELINE configs[4] (an extension): one pass over its 40 000 pairs, ~35 s
+                c5 = bench_cellw2(args, with_cpu=with_cpu)       # BASELINE configs[4] (an extension): one pass over its 40 000 pairs, ~35 s
                 out["c5_cellw2"] = {k: c5[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "roofline", "checks", "cpu_baseline", "parity")}
             if args.config in ("c2", "c3"):
                 from pilot_amd.synthetic import make_cells
                 cohort = make_cells(cfg["n_patients"], cfg["n_types"], cfg["n_dims"], cfg["seed"], cfg["cells_per_patient"])
                 out["e2e_tl_s"] = e2e_tl(cohort)
-                out["prepass"] = prepass_record(L, cohort, with_cpu=not args.no_cpu_baseline)
-        if not args.no_cpu_baseline:
+                out["prepass"] = prepass_record(L, cohort, with_cpu=with_cpu)
+        if with_cpu:
             cb, cb_eq, cb_all, upd = cpu_baseline(P, M, args.reg, args.cpu_seconds, E, iters)
             out["cpu_baseline"], out["cpu_baseline_equal_updates"], out["cpu_baseline_all_cores"] = cb, cb_eq, cb_all
             out["equal_work_note"] = upd
@@ -957,10 +970,10 @@ def cpu_baseline(P, M, reg, budget_s, E_gpu, iters_gpu):
     return base, eq, allc, upd
 
 
-def bench_cellw2(args, reg=0.1, D=30, steps=1, dump_dir=None):
+def bench_cellw2(args, reg=0.1, D=30, steps=1, dump_dir=None, with_cpu=False):
     """--mode cellw2: BASELINE config 5 (an extension, not in the reference): every ordered pair of `--cell-patients`
     patients with `--cell-cells` cells each, log-domain Sinkhorn on raw cell clouds, cells resident in HBM.  `steps` timed
-    passes over the whole grid (the `c5_cellw2` key of the default line: one)."""
+    passes over the whole grid (the `c5_cellw2` key of the --full line: one); with_cpu adds the CPU oracle on a few pairs."""
     from pilot_amd import engine
     from pilot_amd.synthetic import make_cell_clouds
     Np, nc = args.cell_patients, args.cell_cells
@@ -985,7 +998,7 @@ def bench_cellw2(args, reg=0.1, D=30, steps=1, dump_dir=None):
     # CPU baseline: the C / OpenMP fp64 oracle (kind "port": the extension has no reference implementation) on a few pairs of the
     # SAME cohort, all cores inside a pair; also the parity check of those pairs
     cpu, errs = None, []
-    if not args.no_cpu_baseline:
+    if with_cpu:
         from oracle import oracle as O
         ncpu = host_cores()
         pairs = [(0, 1), (2, 3), (5, 4)][:max(1, min(3, Np // 2))]
@@ -1041,8 +1054,8 @@ def bench_cellw2(args, reg=0.1, D=30, steps=1, dump_dir=None):
     }
 
 
-def bench_emd(args, L, P, M, cfg):
-    """--mode emd: the exact-OT pair grid (reference default), its own line with its own cpu_baseline."""
+def bench_emd(args, L, P, M, cfg, with_cpu=False):
+    """--mode emd: the exact-OT pair grid (reference default), its own line; with_cpu adds its own cpu_baseline."""
     from oracle import oracle as O
     from pilot_amd import _lib, engine
     N, K = P.shape
@@ -1080,7 +1093,7 @@ def bench_emd(args, L, P, M, cfg):
     acc = emd_instruction_accounting(args.config)
     if acc:
         out["instructions"] = acc
-    if not args.no_cpu_baseline:
+    if with_cpu:
         ncpu = host_cores()
         step = max(1, N // 4)
         t = time.perf_counter()

@@ -8,18 +8,18 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q 2>&1 | tail -6 > $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
-python bench.py > $O/bench_c3_reg0.1_n1.json 2> $O/bench.err
-python bench.py --mode emd > $O/bench_emd_c3.json 2>> $O/bench.err
+python bench.py --full > $O/bench_c3_reg0.1_n1.json 2> $O/bench.err
+python bench.py --mode emd --full > $O/bench_emd_c3.json 2>> $O/bench.err
 python bench.py --mode emd --config c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_emd_c4.json 2>> $O/bench.err
 python bench.py --config c4 --steps 5 --warmup 1 --no-extras --no-cpu-baseline > $O/bench_c4_reg0.1_n1.json 2>> $O/bench.err
 python bench.py --config c2 --no-extras --no-cpu-baseline > $O/bench_c2_reg0.1_n1.json 2>> $O/bench.err
 python bench.py --precision fp32 --no-extras --no-cpu-baseline > $O/bench_c3_reg0.1_fp32_mfma.json 2>> $O/bench.err
 python bench.py --precision bf16x3 --no-extras --no-cpu-baseline > $O/bench_c3_reg0.1_bf16x3.json 2>> $O/bench.err
 python bench.py --precision fp64 --no-extras --no-cpu-baseline > $O/bench_c3_reg0.1_fp64_mfma.json 2>> $O/bench.err
-python bench.py --mode cellw2 > $O/bench_cellw2_c5.json 2>> $O/bench.err
-python bench.py --gpus 2 --logical-shards --no-cpu-baseline > $O/bench_two_logical_shards_one_process.json 2>> $O/bench.err
-python bench.py --gpus 8 --logical-shards --no-cpu-baseline > $O/bench_eight_logical_shards_one_gpu.json 2>> $O/bench.err
-RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29544 python bench.py --gpus 1 --force-comm --no-cpu-baseline > $O/bench_one_rank_rccl_comm.json 2>> $O/bench.err
+python bench.py --mode cellw2 --full > $O/bench_cellw2_c5.json 2>> $O/bench.err
+python bench.py --gpus 2 --logical-shards --full --no-cpu-baseline > $O/bench_two_logical_shards_one_process.json 2>> $O/bench.err
+python bench.py --gpus 8 --logical-shards --full --no-cpu-baseline > $O/bench_eight_logical_shards_one_gpu.json 2>> $O/bench.err
+RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29544 python bench.py --gpus 1 --force-comm --full --no-cpu-baseline > $O/bench_one_rank_rccl_comm.json 2>> $O/bench.err
 python tools/e2e_profile.py c3 > $O/e2e_tl_wasserstein_distance_c3.txt 2>&1
 python tools/cellw2_parity_c5.py 4 8 $O/cellw2_parity_c5.json > $O/cellw2_parity_c5.txt 2>&1
 python tools/shard_floor.py $O/shard_floor.json > $O/shard_floor_one_gpu.txt 2>&1

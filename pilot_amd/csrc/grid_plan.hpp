@@ -7,6 +7,28 @@
 
 constexpr int TIMING_RING = 64;
 
+namespace pilot {
+// Bits of the PILOT_OT_DEBUG test switch (experiments and tests of the Sinkhorn grid call; tools/ and tests set the numbers)
+enum : int {
+    DBG_NATURAL_ORDER = 2,        // no longest-first work order, only the duplicates are told apart
+    DBG_WGS_SHIFT = 4,            // bits 4..6: resident workgroups per CU of the fast launch (0: its own occupancy)
+    DBG_NO_TAIL_ROWS = 256,       // the last row-tile on the MFMA path (no VALU tail-row variant)
+    DBG_NO_SOLO = 512,            // exact duplicates in the tiles, no one-wave-per-pair path in the fast launch
+    DBG_NO_NAN_PASS = 1024,       // no POT-literal pass for the pairs that end in NaN
+    DBG_NO_SOLO_F64 = 2048,       // the f64 fallback pass on 16-pair tiles, not one wave per pair
+    DBG_NO_REDO64 = 4096,         // single-band pairs that leave the f32 range go to the POT-literal pass, not the f64 one
+    DBG_NO_TRACK_ALL = 8192,      // the fast pass runs first beyond max(M)/reg = 24 too
+};
+// The test switches that act inside the launch sequence of a Sinkhorn grid call: read once per call (pilot_ot_sinkhorn_grid_dev)
+// and part of the graph-replay key, so a changed switch is captured anew, never replayed from the old sequence
+struct SinkhornSwitches {
+    int debug;          // PILOT_OT_DEBUG (DBG_* bits)
+    int no_quad;        // PILOT_OT_NO_QUAD set: 112 < K <= 128 on the one-wave kernel
+    int generic_wgs;    // PILOT_OT_GENERIC_WGS: fewer workgroups for the POT-literal kernel (0: unset)
+    bool operator==(const SinkhornSwitches &o) const { return debug == o.debug && no_quad == o.no_quad && generic_wgs == o.generic_wgs; }
+};
+}  // namespace pilot
+
 struct pilot_ot_plan {
     int N, K, device;
     double max_cost;   // max(M) of the cost the caller keeps on the device (pilot_ot_plan_set_max_cost; 1 = Trajectory.py:101's
@@ -14,16 +36,11 @@ struct pilot_ot_plan {
     void *img;         // 3 operand images, sized for f64 at this K
     void *p_slot;      // N x KP proportions in accumulator-slot order (f32 or f64; sized for f64)
     int *track_list;   // N x N
-    int *track_count;  // [0] track-list length, [1] queue head of the fast launch, [2] queue head of the tracking launch,
-                       // [3] queue head of the solo waves, [4..7] split of the ordered list: n_top, (unused copy), n_dup,
-                       // n_dup = number of leading exact-duplicate pairs, [8] length of the f64 fallback list (mixed precision
-                       // at small reg), [9] its queue head, [10] length of the NaN list (pairs re-solved by the POT-literal
-                       // kernel), [11] its queue head
+    int *ctrl;         // control block of a call: CTRL_BLOCK_INTS ints, slots named next to CTRL_INTS in sinkhorn_kernels.hpp
     int *order_list;   // N x N: longest-first work order of the fast launch
     unsigned char *order_bucket;  // N x N
-    int *order_hist;   // 2 * ORDER_NB: histogram + scatter cursors
-    int *flags_ws;     // per-pair flags when the caller passes none
-    size_t flags_ws_n;
+    int *order_hist;   // ctrl + CTRL_ORDER_HIST
+    int *flags_ws;     // N x N per-pair flags when the caller passes none
     int *emd_counter;  // 1: dynamic pair queue of the exact-EMD kernel
     double *f_slab;    // exact-EMD flow values: one K*K block per resident wave (per 16-lane group of a wave for K <= 16); allocated by the
     size_t f_slab_bytes;  // first exact-mode call that needs it -- a Sinkhorn-only plan never pays for it (164 MB at K = 50)
@@ -33,8 +50,7 @@ struct pilot_ot_plan {
     int generic_wgs;
     float *wide_rec;   // 128 < K <= 256: one record per pair of the grid for sinkhorn_wide_kernel (allocated on first use)
     size_t wide_rec_n; //   pairs it holds
-    int *nan_list;     // pairs that ended in NaN (grown on demand)
-    size_t nan_list_n;
+    int *nan_list;     // 2 x N x N: pairs that ended in NaN, then pairs the f32 passes hand to the f64 pass
     int n_cu;
     // event ring for per-launch kernel timing (bench.py roofline)
     int timing;                       // 0 off
@@ -48,12 +64,13 @@ struct pilot_ot_plan {
     struct GraphKey {
         const void *P, *M, *emd, *iters, *err, *flags;
         double reg, stop_thr, tau, floor_ulps, max_cost;
-        int num_iter_max, check_period, cfg, mixed, sym, row_begin, n_rows, row_step, debug;
+        int num_iter_max, check_period, cfg, mixed, sym, row_begin, n_rows, row_step;
+        pilot::SinkhornSwitches sw;
         bool operator==(const GraphKey &o) const {
             return P == o.P && M == o.M && emd == o.emd && iters == o.iters && err == o.err && flags == o.flags && reg == o.reg &&
                    stop_thr == o.stop_thr && tau == o.tau && floor_ulps == o.floor_ulps && max_cost == o.max_cost && num_iter_max == o.num_iter_max &&
                    check_period == o.check_period && cfg == o.cfg && mixed == o.mixed && sym == o.sym && row_begin == o.row_begin &&
-                   n_rows == o.n_rows && row_step == o.row_step && debug == o.debug;
+                   n_rows == o.n_rows && row_step == o.row_step && sw == o.sw;
         }
     } gkey;
     hipStream_t gstream;

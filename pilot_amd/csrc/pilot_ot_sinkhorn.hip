@@ -15,11 +15,6 @@
 
 namespace {
 using pilot::LDS_BYTES, pilot::MAX_K, pilot::GENERIC_MAX_K, pilot::WIDE_MAX_K;
-constexpr int CTRL_INTS = pilot::CTRL_INTS;      // control block of a call: see pilot_ot_plan::track_count
-// ... followed by the two order histograms and, from a 128-byte boundary, the ticket counters of the fast launch's work queue
-constexpr int CTRL_SHARDS_AT = (CTRL_INTS + 2 * pilot::ORDER_NB + 31) / 32 * 32;
-constexpr int CTRL_SHARDS_TRACK_AT = CTRL_SHARDS_AT + pilot::QUEUE_SHARDS * pilot::QUEUE_SHARD_STRIDE;      // (the tracking launch's)
-constexpr int CTRL_BLOCK_INTS = CTRL_SHARDS_TRACK_AT + pilot::QUEUE_SHARDS * pilot::QUEUE_SHARD_STRIDE;
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -79,11 +74,11 @@ PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
     pilot_ot_plan *pl = new (std::nothrow) pilot_ot_plan();
     if (!pl) return fail(PILOT_OT_EINVAL, "out of host memory");
     pl->N = N; pl->K = K; pl->max_cost = 1.0;
-    pl->img = nullptr; pl->p_slot = nullptr; pl->track_list = nullptr; pl->track_count = nullptr;
-    pl->emd_counter = nullptr; pl->f_slab = nullptr; pl->f_slab_bytes = 0; pl->emdg_slab = nullptr; pl->emdg_wgs = 0; pl->n_cu = 256; pl->kws = nullptr; pl->generic_wgs = 0; pl->nan_list = nullptr; pl->nan_list_n = 0;
+    pl->img = nullptr; pl->p_slot = nullptr; pl->track_list = nullptr; pl->ctrl = nullptr;
+    pl->emd_counter = nullptr; pl->f_slab = nullptr; pl->f_slab_bytes = 0; pl->emdg_slab = nullptr; pl->emdg_wgs = 0; pl->n_cu = 256; pl->kws = nullptr; pl->generic_wgs = 0; pl->nan_list = nullptr;
     pl->wide_rec = nullptr; pl->wide_rec_n = 0;
     pl->order_list = nullptr; pl->order_bucket = nullptr; pl->order_hist = nullptr;
-    pl->flags_ws = nullptr; pl->flags_ws_n = 0;
+    pl->flags_ws = nullptr;
     pl->timing = 0; pl->n_timed = 0; pl->n_calls = 0;
     pl->graph_mode = 0; pl->gkey_seen = 0; pl->gstream = nullptr; pl->gexec = nullptr;
     for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 4; ++j) pl->ev[i][j] = nullptr;
@@ -111,21 +106,21 @@ PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
         if (e == hipSuccess) e = hipMalloc(&pl->p_slot, p_bytes);
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->track_list), sizeof(int) * (size_t)N * N);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->track_count), CTRL_BLOCK_INTS * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->ctrl), pilot::CTRL_BLOCK_INTS * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_list), sizeof(int) * (size_t)N * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_bucket), (size_t)N * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->emd_counter), pilot::emd_counter_bytes());
-    // per-pair work lists of the full grid, so that no grid call allocates (the POT-literal kernel's scratch, 2 K^2 doubles per
-    // resident workgroup, is the exception: allocated by the first call that needs that kernel)
+    // per-pair work lists and flags of the full grid: a call has at most N x N pairs, so no grid call grows them (the POT-literal
+    // kernel's scratch, 2 K^2 doubles per resident workgroup, and the wide kernel's records are allocated by the first call that
+    // needs them)
     // (two lists of N^2: pairs that ended in NaN, and pairs the f32 passes hand to the f64 pass)
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->nan_list), 2 * sizeof(int) * (size_t)N * N);
-    if (e == hipSuccess) pl->nan_list_n = (size_t)N * N;
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)N * N);
-    if (e == hipSuccess) pl->flags_ws_n = (size_t)N * N;
     if (e != hipSuccess) {
         pilot_ot_plan_destroy(pl);
         return fail(PILOT_OT_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
     }
+    pl->order_hist = pl->ctrl + pilot::CTRL_ORDER_HIST;
     *plan = pl;
     return PILOT_OT_OK;
 }
@@ -142,7 +137,7 @@ PILOT_API int pilot_ot_plan_destroy(pilot_ot_plan *pl) {
     if (pl->img) (void)hipFree(pl->img);
     if (pl->p_slot) (void)hipFree(pl->p_slot);
     if (pl->track_list) (void)hipFree(pl->track_list);
-    if (pl->track_count) (void)hipFree(pl->track_count);
+    if (pl->ctrl) (void)hipFree(pl->ctrl);
     if (pl->order_list) (void)hipFree(pl->order_list);
     if (pl->order_bucket) (void)hipFree(pl->order_bucket);
     if (pl->flags_ws) (void)hipFree(pl->flags_ws);
@@ -184,7 +179,7 @@ int check_grid_args(int N, int K, double reg, int num_iter_max, double stop_thr,
 constexpr double MAX_COST_OVER_REG = PILOT_OT_MAX_COST_OVER_REG;
 
 // list / list_len (device, nullable): only the listed pairs (NaN hand-over of the fast kernels); queue: zeroed counter
-int run_generic(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
+int run_generic(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
                 int check_period, int row_begin, int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err, int *d_flags,
                 hipStream_t s, const int *list = nullptr, const int *list_len = nullptr, int *queue = nullptr) {
     const int N = pl->N, K = pl->K;
@@ -204,16 +199,7 @@ int run_generic(pilot_ot_plan *pl, const double *d_P, const double *d_M, double 
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->kws), per * wgs));
         pl->generic_wgs = wgs;
     }
-    if (!d_flags) {
-        if ((size_t)n_pairs > pl->flags_ws_n) {
-            if (pl->flags_ws) HIP_TRY(hipFree(pl->flags_ws));
-            pl->flags_ws = nullptr; pl->flags_ws_n = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)n_pairs));
-            pl->flags_ws_n = (size_t)n_pairs;
-        }
-        d_flags = pl->flags_ws;
-    }
-    if (!queue) { queue = pl->track_count; HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), s)); }
+    if (!queue) { queue = pl->ctrl + pilot::CTRL_GENERIC_HEAD; HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), s)); }
     pilot::GenericParams g;
     g.P = d_P; g.M = d_M; g.N = N; g.K = K; g.n_pairs = n_pairs; g.row_begin = row_begin; g.row_step = row_step;
     g.reg = reg; g.tau = tau; g.stop_thr = stop_thr; g.max_iter = num_iter_max; g.period = check_period;
@@ -221,28 +207,11 @@ int run_generic(pilot_ot_plan *pl, const double *d_P, const double *d_M, double 
     g.list = list; g.list_len = list_len;
     int wgs = pl->generic_wgs < n_pairs ? pl->generic_wgs : n_pairs;
     if (list && wgs > 64) wgs = 64;          // a hand-over list is short (usually empty)
-    if (const char *e = pilot::test_switch("PILOT_OT_GENERIC_WGS")) { const int w = atoi(e); if (w > 0 && w < wgs) wgs = w; }      // experiment switch
+    if (sw.generic_wgs > 0 && sw.generic_wgs < wgs) wgs = sw.generic_wgs;      // experiment switch
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::sinkhorn_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(pilot::sinkhorn_generic_kernel, dim3(wgs), dim3(pilot::GENERIC_WG), lds, s, g);
     HIP_TRY(hipGetLastError());
     return PILOT_OT_OK;
-}
-
-// resident workgroups per CU of the single-tile stream kernel (mirrors pilot::min_waves_per_simd)
-int stream_min_waves(int w /* sizeof(T)/4 */, int RT, bool sym, bool track, int tv, bool split, bool half = false) {
-    if (half && !track && RT <= pilot::HALF_OCC4_MAX_RT) return 4;
-    if (split) return RT <= (track ? pilot::SPLIT_OCC2_MAX_RT_TRACK : (half ? pilot::HALF_OCC2_MAX_RT : pilot::SPLIT_OCC2_MAX_RT)) ? 2 : 1;
-    const int na = RT * 4 * RT * w;
-    const bool greg = !split && sym && na <= pilot::GREG_MAX;
-    const int regs = (track ? 7 : 5) * RT * 4 * w + 4 * w + 56 + (tv ? 24 * w : 0) + (split ? 3 * ((RT + 1) / 2) * 4 + 24 : 0) +
-                     (greg ? na + 2 * tv * ((RT - 1) * 4 + 1) * w : 0);
-    return regs <= 128 ? 4 : (regs <= 168 ? 3 : (regs <= 256 ? 2 : 1));
-}
-// mirrors pilot::solo_in_stream: does the fast launch of this configuration carry the one-wave-per-pair path?
-bool stream_has_solo(int w, int RT, bool sym, int tv, bool split, bool half) {
-    const int mw = stream_min_waves(w, RT, sym, false, tv, split, half);
-    const int budget = mw >= 4 ? 128 : (mw == 3 ? 168 : 256);
-    return sym && RT <= 4 && !(half && RT < pilot::HALF_SOLO_MIN_RT) && (64 + 45) * w <= budget;
 }
 
 // LDS of one stream-kernel workgroup: operand image(s) + first-product table + tail weights + one ring of finished pairs
@@ -273,24 +242,52 @@ bool split_fits_lds(int K, bool sym, int bands = 1) {
     return fixed + (size_t)4 * pilot::WAVES_PER_WG * (2 * KP + 4) * 4 <= LDS_BYTES;
 }
 
+// workgroups of a launch of WAVES_PER_WG tiles each: per_cu resident per CU, no more than the tiles fill
+int clamp_wgs(const pilot_ot_plan *pl, int per_cu, int tiles) {
+    const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
+    return pl->n_cu * per_cu < need ? pl->n_cu * per_cu : need;
+}
+
+// The launch parameters run_grid and run_wide share: the whole call on the plan's buffers, in the longest-first order, drawn from
+// the fast launch's queue head.  Pairs that end in NaN ("Numerical errors" in POT) are collected and re-solved by the POT-literal
+// kernel, which returns the last good iterate like POT does.
+pilot::GridParams call_params(const pilot_ot_plan *pl, int n_pairs, int row_begin, int row_step, int num_iter_max, int check_period,
+                              double stop_thr, double tau, double floor_ulps, double *d_emd, int *d_iters, double *d_err, int *d_flags) {
+    pilot::GridParams p;
+    p.P = pl->p_slot; p.img = pl->img; p.N = pl->N; p.K = pl->K;
+    p.n_pairs = n_pairs;
+    p.list = pl->order_list; p.list_len = nullptr;
+    p.solo_len = nullptr; p.solo_head = nullptr; p.solo_blocks = 0;
+    p.row_begin = row_begin; p.row_step = row_step;
+    p.max_iter = num_iter_max; p.period = check_period;
+    p.stop_thr = stop_thr; p.tau = tau; p.floor_ulps = floor_ulps;
+    p.emd = d_emd; p.iters = d_iters; p.err = d_err; p.flags = d_flags;
+    p.track_list = pl->track_list; p.track_count = pl->ctrl + pilot::CTRL_TRACK_LEN;
+    p.queue_head = pl->ctrl + pilot::CTRL_HEAD_FAST; p.queue_shards = nullptr;
+    p.ring = 0; p.bands = 1;
+    p.fb_list = nullptr; p.fb_count = nullptr;
+    p.nan_list = pl->nan_list; p.nan_count = pl->ctrl + pilot::CTRL_NAN_LEN;
+    p.unequal = pl->ctrl + pilot::CTRL_UNEQUAL;
+    p.debug = 0;
+    return p;
+}
+
 // cfg: pilot::CFG_F32 / CFG_F64 / CFG_S32 / CFG_H32 (all 16-pair tiles: TILE = 16, 4 accumulator registers, 4 lane groups)
 // CFG_H32 (fp16-split): the fast pass only; its tracking pass is the bf16-split kernel on the second operand block.
 // mixed (cfg == CFG_S32 only): small reg under PILOT_OT_PREC_AUTO -- every pair is first iterated in f32 (bf16-split
 // products, tau-tracking kernel); pairs whose plan may touch Gibbs entries outside the f32-safe range, or that went NaN, are
 // collected (ring_flush) and solved again by the f64 tracking kernel.
-int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg, int num_iter_max,
+int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double *d_P, const double *d_M, double reg, int num_iter_max,
              double stop_thr, double tau, int check_period, double floor_ulps, bool sym, int row_begin,
              int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err, int *d_flags, hipStream_t s,
              bool mixed = false) {
     const bool f64 = cfg == pilot::CFG_F64, half = cfg == pilot::CFG_H32, split = cfg == pilot::CFG_S32 || half;
     const size_t ts = f64 ? sizeof(double) : sizeof(float);
-    const int w = (int)(ts / 4);
     constexpr int TILE = 16;
     const int N = pl->N, K = pl->K;
     const int RT = (K + TILE - 1) / TILE;
     const int KP = RT * TILE;
-    const char *dbg = pilot::test_switch("PILOT_OT_DEBUG");
-    const int debug = dbg ? atoi(dbg) : 0;
+    const int debug = sw.debug;
     const size_t form = pilot::form_elems_rt(cfg, RT);
     // the per-wave hand-over buffers of the fast kernels
     const size_t hb_bytes = (size_t)pilot::WAVES_PER_WG * pilot::HANDOVER_BUF * sizeof(int);
@@ -303,7 +300,7 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
     if (!split) {
         const int n_tail = K - (RT - 1) * TILE;
         // (RT = 8 variants spill: left on the MFMA path)
-        if (RT >= 2 && RT <= 7 && n_tail <= 4 && !(debug & 256)) tv = n_tail <= 2 ? 1 : 2;
+        if (RT >= 2 && RT <= 7 && n_tail <= 4 && !(debug & pilot::DBG_NO_TAIL_ROWS)) tv = n_tail <= 2 ? 1 : 2;
         const size_t tail_lds = (size_t)(sym ? 1 : 2) * tv * ((RT - 1) * 4 + 1) * 64 * 2 * ts;
         if (tv && fixed + tail_lds + 4 * pilot::WAVES_PER_WG * (2 * KP + 4) * ts > LDS_BYTES) tv = 0;   // no room: MFMA path
         if (tv) fixed += tail_lds;
@@ -312,59 +309,28 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
     if (fixed + pilot::WAVES_PER_WG * slot_bytes > LDS_BYTES)
         return fail(PILOT_OT_ENOTSUP, "K=%d with a %ssymmetric cost needs %zu B of LDS (> %zu) in this precision", K, sym ? "" : "non-",
                     fixed + pilot::WAVES_PER_WG * slot_bytes, LDS_BYTES);
-    pl->order_hist = pl->track_count + CTRL_INTS;     // one control block, one memset per call
-    HIP_TRY(hipMemsetAsync(pl->track_count, 0, CTRL_BLOCK_INTS * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(pl->ctrl, 0, pilot::CTRL_BLOCK_INTS * sizeof(int), s));     // one control block, one memset per call
     void *img = pl->img;
     void *Pt = pl->p_slot;
     if (n_rows == 0) return PILOT_OT_OK;
 
     const int n_pairs = n_rows * N;
-    if (!d_flags) {
-        if ((size_t)n_pairs > pl->flags_ws_n) {
-            if (pl->flags_ws) HIP_TRY(hipFree(pl->flags_ws));
-            pl->flags_ws = nullptr; pl->flags_ws_n = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)n_pairs));
-            pl->flags_ws_n = (size_t)n_pairs;
-        }
-        d_flags = pl->flags_ws;
-    }
-
-    pilot::GridParams p;
-    p.P = Pt; p.img = img; p.N = N; p.K = K;
-    p.n_pairs = n_pairs;
-    p.list = nullptr; p.list_len = nullptr;
-    p.solo_len = nullptr; p.solo_head = nullptr; p.solo_blocks = 0;
-    p.row_begin = row_begin; p.row_step = row_step;
-    p.max_iter = num_iter_max; p.period = check_period;
-    p.stop_thr = stop_thr; p.tau = tau; p.floor_ulps = floor_ulps;
-    p.emd = d_emd; p.iters = d_iters; p.err = d_err; p.flags = d_flags;
-    p.track_list = pl->track_list; p.track_count = pl->track_count; p.queue_head = pl->track_count + 1;
-    p.queue_shards = pl->track_count + CTRL_SHARDS_AT;       // (the fast launch up to two row-tiles; the tracking launch has its own, CTRL_SHARDS_TRACK_AT)
-    p.ring = 0;
-    p.fb_list = nullptr; p.fb_count = nullptr; p.bands = 1;
-    // pairs that end in NaN ("Numerical errors" in POT) are collected and re-solved by the POT-literal kernel, which
-    // returns the last good iterate like POT does
-    if ((size_t)n_pairs > pl->nan_list_n) {
-        if (pl->nan_list) HIP_TRY(hipFree(pl->nan_list));
-        pl->nan_list = nullptr; pl->nan_list_n = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->nan_list), 2 * sizeof(int) * (size_t)n_pairs));
-        pl->nan_list_n = (size_t)n_pairs;
-    }
-    p.nan_list = pl->nan_list; p.nan_count = pl->track_count + 10;
-    p.unequal = pl->track_count + pilot::CTRL_UNEQUAL;
+    pilot::GridParams p = call_params(pl, n_pairs, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd, d_iters,
+                                      d_err, d_flags);
+    p.queue_shards = pl->ctrl + pilot::CTRL_SHARDS_AT;       // (the fast launch up to two row-tiles; the tracking launch has its own)
+    p.debug = debug;
     // Between the fp16-split range and the two-band path (12 < max(M)/reg <= 60) a few pairs per matrix leave the f32 range in
     // the single-band kernels (a scaling jumps past the fp16 domain within one update; products underflow at reg <= 0.025).
     // They used to go to the POT-literal kernel with the other NaN pairs -- one workgroup per pair, 12.5 us per update: 3 to 13
     // pairs cost 12 ms of a 30 ms call at reg 0.025 .. 0.0175.  They are collected like the small-reg path collects its
     // hand-over and solved again by the f64 tracking kernel (symmetric cost, K <= 64: one wave per pair, 1.1 us per update).
-    const bool redo64 = !mixed && split && pl->max_cost / reg > 12.0 && !(debug & 4096);
+    const bool redo64 = !mixed && split && pl->max_cost / reg > 12.0 && !(debug & pilot::DBG_NO_REDO64);
     // From max(M)/reg = 24 on nearly every pair tau-absorbs (c3: 28 % at 20, 94 % at 25) and the fast pass only hands its pairs
     // over after a few dozen wasted updates (3.7 of 11.6 ms at reg 0.04): every pair goes to the tracking kernel at once, as
     // in the two-band path.
-    const bool track_all = mixed || (split && !half && pl->max_cost / reg > 24.0 && !(debug & 8192));
-    int *const fb_list = pl->nan_list + pl->nan_list_n;
-    if (redo64) { p.fb_list = fb_list; p.fb_count = pl->track_count + 8; }
-    p.debug = debug;
+    const bool track_all = mixed || (split && !half && pl->max_cost / reg > 24.0 && !(debug & pilot::DBG_NO_TRACK_ALL));
+    int *const fb_list = pl->nan_list + (size_t)N * N;
+    if (redo64) { p.fb_list = fb_list; p.fb_count = pl->ctrl + pilot::CTRL_FB_LEN; }
     const int tiles = (n_pairs + TILE - 1) / TILE;
     // exact duplicates (a == b): one wave per pair in the leading workgroups of the fast launch (symmetric cost, K <= 64)
     // ... while the grid is small.  A wave that iterates ONE pair has the shorter update (K = 50: 0.57 us against 0.77 us for a lone
@@ -373,29 +339,32 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
     // main kernel 0.617 -> 0.584 ms with the duplicates in the tiles (tools/solo_probe.py; crossover between 5 600 and 7 500 tiles at 2 048
     // wave slots).  The rule reads the FULL grid (N x N), not the rows of this call: a row shard and the full grid send the same pair
     // down the same path, so their bits agree.
+    // (the shape rules read the configuration as its fast pass is instantiated: the split variants with live1 as their TV)
+    const pilot::CfgShape fast = pilot::shape_of(cfg);
+    const int tv_fast = split ? live1 : tv;
     const long full_tiles = ((long)N * N + TILE - 1) / TILE;
-    const long wave_slots = (long)pl->n_cu * stream_min_waves(w, RT, sym, false, tv, split, half) * pilot::WAVES_PER_WG;
-    const bool solo = stream_has_solo(w, RT, sym, tv, split, half) && !(p.debug & 512) && !track_all && full_tiles < 3 * wave_slots;
+    const long wave_slots = (long)pl->n_cu * pilot::min_waves_per_simd(fast, RT, sym, false, tv_fast) * pilot::WAVES_PER_WG;
+    const bool solo = pilot::solo_in_stream(fast, RT, sym, false, tv_fast) && !(debug & pilot::DBG_NO_SOLO) && !track_all &&
+                      full_tiles < 3 * wave_slots;
     int solo_blocks = 0;
     {
         // longest-first work order (see order_bucket_kernel)
         int ob = (n_pairs + 1023) / 1024;
         if (ob > pl->n_cu) ob = pl->n_cu;
-        int *split_ctl = pl->track_count + 4;
-        const int mode = (solo ? 2 : 0) | ((p.debug & 2) ? 4 : 0);   // bit 2: natural order (experiment)
+        const int mode = (solo ? 2 : 0) | ((debug & pilot::DBG_NATURAL_ORDER) ? 4 : 0);   // bit 2: natural order (experiment)
         HIP_TRY(pilot::launch_prep(cfg, d_M, K, RT, reg, img, d_P, Pt, N, (tv ? 1 : 0) | 2 | (mixed ? 4 : 0), stop_thr, floor_ulps, n_rows, row_begin, row_step,
-                                   pl->order_bucket, pl->order_hist, pl->order_list, split_ctl, pl->track_count + 1, mode, ob, s));
-        p.list = pl->order_list;
+                                   pl->order_bucket, pl->order_hist, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT, pl->ctrl + pilot::CTRL_HEAD_FAST,
+                                   mode, ob, s));
         if (solo) {
             solo_blocks = (n_rows + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;     // the diagonal; more duplicates queue up
             if (solo_blocks > pl->n_cu) solo_blocks = pl->n_cu;
-            p.solo_len = split_ctl + 3; p.solo_head = pl->track_count + 3; p.solo_blocks = solo_blocks;
+            p.solo_len = pl->ctrl + pilot::CTRL_SOLO_LEN; p.solo_head = pl->ctrl + pilot::CTRL_HEAD_SOLO; p.solo_blocks = solo_blocks;
         }
     }
     hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     // (fp16-split configuration, 112 < K <= 128, symmetric cost: four waves per tile, one tile per workgroup, two workgroups per CU)
-    const bool quad = half && pilot::quad_covers(K, sym) && !pilot::test_switch("PILOT_OT_NO_QUAD");
+    const bool quad = half && pilot::quad_covers(K, sym) && !sw.no_quad;
     auto launch = [&](int tvv, bool track, int wgs, const StreamLds &L) -> hipError_t {
         p.ring = L.ring;
         if (tvv) return pilot::launch_stream_tv(cfg, tvv, RT, sym, track, dim3(wgs), L.bytes, s, p);
@@ -411,11 +380,11 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
         if (wgs > tiles) wgs = tiles;
         HIP_TRY(launch(tv, false, wgs, StreamLds{}));
     } else if (!track_all) {
-        int want = stream_min_waves(w, RT, sym, false, tv, split, half);
+        int want = pilot::min_waves_per_simd(fast, RT, sym, false, tv_fast);
         // (K <= 4: a third of the pairs tau-absorb and are handed over, and the hand-over's atomics and list stores are what more resident
         // waves contend for -- K = 3 / 4 at N = 600: 0.60 / 0.64 ms at two workgroups per CU, 0.69 / 0.72 at four; from K = 5 on four win)
         if (half && K <= 4 && want > 2) want = 2;
-        if ((p.debug >> 4) & 7) want = (p.debug >> 4) & 7;           // experiment: resident workgroups per CU
+        if ((debug >> pilot::DBG_WGS_SHIFT) & 7) want = (debug >> pilot::DBG_WGS_SHIFT) & 7;      // experiment: resident workgroups per CU
         // split configurations up to 4 row-tiles flush their ring inline and park U in LDS meanwhile (pilot::parked_flush):
         // one 16-byte line per lane and row-tile
         const bool park = split && RT <= 4;
@@ -427,16 +396,12 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
         if (fixed + park_bytes + pilot::WAVES_PER_WG * slot_fast > LDS_BYTES)
             return fail(PILOT_OT_ENOTSUP, "K=%d: operand images + ring + park area exceed LDS", K);
         const StreamLds L = stream_lds(fixed + park_bytes, slot_fast, want);
-        int wgs = pl->n_cu * L.wgs_per_cu;
-        const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
-        if (wgs > need) wgs = need;
-        wgs += solo_blocks;
-        HIP_TRY(launch(tv, false, wgs, L));
+        HIP_TRY(launch(tv, false, clamp_wgs(pl, L.wgs_per_cu, tiles) + solo_blocks, L));
     }
     if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
     // second pass: pairs in which POT would tau-absorb, with the absorption iterations tracked
-    p.list = pl->track_list; p.list_len = pl->track_count; p.queue_head = pl->track_count + 2;
-    p.queue_shards = pl->track_count + CTRL_SHARDS_TRACK_AT;     // (used by the tracking kernels up to two row-tiles)
+    p.list = pl->track_list; p.list_len = pl->ctrl + pilot::CTRL_TRACK_LEN; p.queue_head = pl->ctrl + pilot::CTRL_HEAD_TRACK;
+    p.queue_shards = pl->ctrl + pilot::CTRL_SHARDS_TRACK_AT;     // (used by the tracking kernels up to two row-tiles)
     p.solo_blocks = 0;
     size_t fixed_t = fixed;
     if (half) {     // tracking pass of the fp16-split configuration: the bf16-split kernel on its own operand block
@@ -448,17 +413,16 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
         // small reg: the Gibbs kernel in two exponent bands; pairs that still leave the f32 range are collected in track_list
         // for the f64 pass
         p.bands = 2;
-        p.fb_list = pl->track_list; p.fb_count = pl->track_count + 8;
+        p.fb_list = pl->track_list; p.fb_count = pl->ctrl + pilot::CTRL_FB_LEN;
         fixed_t = (size_t)(sym ? 1 : 2) * form * ts * 2 + (size_t)KP * ts + hb_bytes;
     }
     {
         // (the tracking kernel's result need not match the fast kernels' bits: a pair is always solved by one of them)
         const int tv_t = RT <= 4 ? tv : 0;          // larger tracking variants spill with the tail rows
-        const StreamLds L = stream_lds(fixed_t, slot_bytes, stream_min_waves(w, RT, sym, true, tv_t, split));
-        int wgs_t = pl->n_cu * L.wgs_per_cu;
-        const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
-        if (wgs_t > need) wgs_t = need;
-        HIP_TRY(launch(tv_t, true, wgs_t, L));
+        // (the split configurations track on the bf16-split kernel, the fp16-split one too)
+        const pilot::CfgShape tracking = split ? pilot::shape_of(pilot::CFG_S32) : fast;
+        const StreamLds L = stream_lds(fixed_t, slot_bytes, pilot::min_waves_per_simd(tracking, RT, sym, true, split ? live1 : tv_t));
+        HIP_TRY(launch(tv_t, true, clamp_wgs(pl, L.wgs_per_cu, tiles), L));
     }
     if (mixed || redo64) {
         // third pass: the collected pairs in f64 (operand images and proportions rebuilt for the f64 configuration in the
@@ -470,28 +434,25 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
         if (fixed64 + pilot::WAVES_PER_WG * slot64 > LDS_BYTES)
             return fail(PILOT_OT_ENOTSUP, "K=%d: the f64 fallback needs %zu B of LDS", K, fixed64 + pilot::WAVES_PER_WG * slot64);
         HIP_TRY(pilot::launch_prep(pilot::CFG_F64, d_M, K, RT64, reg, img, d_P, Pt, N, 2, stop_thr, floor_ulps, 0, row_begin, row_step,
-                                   pl->order_bucket, pl->order_hist, pl->order_list, pl->track_count + 4, pl->track_count + 1, 0, 1, s));
+                                   pl->order_bucket, pl->order_hist, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT, pl->ctrl + pilot::CTRL_HEAD_FAST, 0, 1, s));
         pilot::GridParams q = p;
-        q.list = mixed ? pl->track_list : fb_list; q.list_len = pl->track_count + 8; q.queue_head = pl->track_count + 9; q.queue_shards = nullptr;
+        q.list = mixed ? pl->track_list : fb_list; q.list_len = pl->ctrl + pilot::CTRL_FB_LEN; q.queue_head = pl->ctrl + pilot::CTRL_FB_HEAD;
+        q.queue_shards = nullptr;
         q.img = img;                        // (the fp16-split configuration's tracking pass had moved it to its own block)
         q.fb_list = nullptr; q.fb_count = nullptr; q.bands = 1;
-        q.nan_list = pl->nan_list; q.nan_count = pl->track_count + 10;
-        if (sym && K <= 64 && !(p.debug & 2048)) {
+        if (sym && K <= 64 && !(debug & pilot::DBG_NO_SOLO_F64)) {
             // the list is short (tens of pairs) and every pair on it runs long: one wave per pair, not 16-pair MFMA tiles
             HIP_TRY(pilot::launch_solo_track_f64(dim3(64), s, q));
         } else {
-            const StreamLds L = stream_lds(fixed64, slot64, stream_min_waves(2, RT64, sym, true, 0, false));
+            const StreamLds L = stream_lds(fixed64, slot64, pilot::min_waves_per_simd(pilot::shape_of(pilot::CFG_F64), RT64, sym, true, 0));
             q.ring = L.ring;
-            int wgs_t = pl->n_cu * L.wgs_per_cu;
-            const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
-            if (wgs_t > need) wgs_t = need;
-            HIP_TRY(pilot::launch_stream_f64(RT64, sym, true, dim3(wgs_t), L.bytes, s, q));
+            HIP_TRY(pilot::launch_stream_f64(RT64, sym, true, dim3(clamp_wgs(pl, L.wgs_per_cu, tiles)), L.bytes, s, q));
         }
     }
     if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
-    if (!(p.debug & 1024)) {
-        const int rc = run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters,
-                                   d_err, d_flags, s, pl->nan_list, pl->track_count + 10, pl->track_count + 11);
+    if (!(debug & pilot::DBG_NO_NAN_PASS)) {
+        const int rc = run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters,
+                                   d_err, d_flags, s, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);
         if (rc != PILOT_OT_OK) return rc;
     }
     return PILOT_OT_OK;
@@ -500,7 +461,7 @@ int run_grid(int cfg, pilot_ot_plan *pl, const double *d_P, const double *d_M, d
 // 128 < K <= 256 with a symmetric cost inside the fp16-split range: sinkhorn_wide_kernel (wide_kernels.hpp) on the operand
 // block the ordinary prep kernel writes for 16 row-tiles, then the value kernel; hand-overs (tau-absorbing / NaN pairs, or
 // every pair when the histograms carry unequal mass) are solved by the POT-literal kernel like those of the stream kernels.
-int run_wide(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
+int run_wide(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
              int check_period, double floor_ulps, int row_begin, int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err,
              int *d_flags, hipStream_t s) {
     const int N = pl->N, K = pl->K, RT = 16;
@@ -513,31 +474,15 @@ int run_wide(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg
         for (int r0 = 0; r0 < n_rows; r0 += rows_per) {
             const int nr = n_rows - r0 < rows_per ? n_rows - r0 : rows_per;
             const size_t off = (size_t)r0 * N;
-            const int rc = run_wide(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, floor_ulps, row_begin + r0 * row_step, nr, row_step,
-                                    d_emd + off, d_iters ? d_iters + off : nullptr, d_err ? d_err + off : nullptr, d_flags ? d_flags + off : nullptr, s);
+            const int rc = run_wide(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, floor_ulps, row_begin + r0 * row_step, nr, row_step,
+                                    d_emd + off, d_iters ? d_iters + off : nullptr, d_err ? d_err + off : nullptr, d_flags + off, s);
             if (rc != PILOT_OT_OK) return rc;
         }
         return PILOT_OT_OK;
     }
-    pl->order_hist = pl->track_count + CTRL_INTS;
-    HIP_TRY(hipMemsetAsync(pl->track_count, 0, (CTRL_INTS + 2 * pilot::ORDER_NB) * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(pl->ctrl, 0, (pilot::CTRL_ORDER_HIST + 2 * pilot::ORDER_NB) * sizeof(int), s));
     if (n_rows == 0) return PILOT_OT_OK;
     const int n_pairs = n_rows * N;
-    if (!d_flags) {
-        if ((size_t)n_pairs > pl->flags_ws_n) {
-            if (pl->flags_ws) HIP_TRY(hipFree(pl->flags_ws));
-            pl->flags_ws = nullptr; pl->flags_ws_n = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->flags_ws), sizeof(int) * (size_t)n_pairs));
-            pl->flags_ws_n = (size_t)n_pairs;
-        }
-        d_flags = pl->flags_ws;
-    }
-    if ((size_t)n_pairs > pl->nan_list_n) {
-        if (pl->nan_list) HIP_TRY(hipFree(pl->nan_list));
-        pl->nan_list = nullptr; pl->nan_list_n = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->nan_list), 2 * sizeof(int) * (size_t)n_pairs));
-        pl->nan_list_n = (size_t)n_pairs;
-    }
     if ((size_t)n_pairs > pl->wide_rec_n) {     // (first call of this size: the one allocation of the path)
         if (pl->wide_rec) HIP_TRY(hipFree(pl->wide_rec));
         pl->wide_rec = nullptr; pl->wide_rec_n = 0;
@@ -547,34 +492,27 @@ int run_wide(pilot_ot_plan *pl, const double *d_P, const double *d_M, double reg
     int ob = (n_pairs + 1023) / 1024;
     if (ob > pl->n_cu) ob = pl->n_cu;
     HIP_TRY(pilot::launch_prep(pilot::CFG_H32, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, 0, stop_thr, floor_ulps, n_rows, row_begin, row_step,
-                               pl->order_bucket, pl->order_hist, pl->order_list, pl->track_count + 4, pl->track_count + 1, 0, ob, s));
-    pilot::GridParams p;
-    p.P = pl->p_slot; p.img = pl->img; p.N = N; p.K = K;
-    p.n_pairs = n_pairs;
-    p.list = pl->order_list; p.list_len = nullptr;
-    p.solo_len = nullptr; p.solo_head = nullptr; p.solo_blocks = 0;
-    p.row_begin = row_begin; p.row_step = row_step;
-    p.max_iter = num_iter_max; p.period = check_period;
-    p.stop_thr = stop_thr; p.tau = tau; p.floor_ulps = floor_ulps;
-    p.emd = d_emd; p.iters = d_iters; p.err = d_err; p.flags = d_flags;
-    p.track_list = pl->track_list; p.track_count = pl->track_count; p.queue_head = pl->track_count + 1; p.queue_shards = nullptr;
-    p.ring = 0; p.bands = 1;
-    p.fb_list = nullptr; p.fb_count = nullptr;
-    p.nan_list = pl->nan_list; p.nan_count = pl->track_count + 10;
-    p.unequal = pl->track_count + pilot::CTRL_UNEQUAL;
-    p.debug = 0;
+                               pl->order_bucket, pl->order_hist, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT, pl->ctrl + pilot::CTRL_HEAD_FAST, 0, ob, s));
+    const pilot::GridParams p = call_params(pl, n_pairs, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd,
+                                            d_iters, d_err, d_flags);
     hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     const int tiles = (n_pairs + 15) / 16;
     int wgs = pl->n_cu < tiles ? pl->n_cu : tiles;            // one 512-thread workgroup per CU (230 VGPRs: two waves per SIMD)
     HIP_TRY(pilot::launch_wide(dim3(wgs), s, p, pl->wide_rec));
     if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
-    int vwgs = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
-    if (vwgs > 2 * pl->n_cu) vwgs = 2 * pl->n_cu;
-    HIP_TRY(pilot::launch_wide_value(dim3(vwgs), s, p, pl->wide_rec));
+    HIP_TRY(pilot::launch_wide_value(dim3(clamp_wgs(pl, 2, tiles)), s, p, pl->wide_rec));
     if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
-    return run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
-                       d_flags, s, pl->nan_list, pl->track_count + 10, pl->track_count + 11);
+    return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
+                       d_flags, s, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);
+}
+
+pilot::SinkhornSwitches read_switches() {
+    const char *dbg = pilot::test_switch("PILOT_OT_DEBUG");       // (a lookup's value lasts until the next lookup)
+    const int debug = dbg ? atoi(dbg) : 0;
+    const int no_quad = pilot::test_switch("PILOT_OT_NO_QUAD") ? 1 : 0;
+    const char *gw = pilot::test_switch("PILOT_OT_GENERIC_WGS");
+    return {debug, no_quad, gw ? atoi(gw) : 0};
 }
 
 }  // namespace
@@ -588,6 +526,9 @@ PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, c
     int rc = check_grid_args(pl->N, pl->K, reg, num_iter_max, stop_thr, tau, check_period, precision, row_begin,
                              row_end, row_step);
     if (rc != PILOT_OT_OK) return rc;
+    // the test switches that act inside the launch sequence, read once: every lookup takes a lock, and the graph key holds them
+    const pilot::SinkhornSwitches sw = read_switches();
+    if (!d_flags) d_flags = pl->flags_ws;
     {
         const int n_rows_g = (row_end - row_begin + row_step - 1) / row_step;
         // K beyond the MFMA kernels, a reg beyond the f64 range of exp(-M/reg) (judged by the plan's max_cost), or on request: POT's loop literally, absorbed kernel rebuilt per pair
@@ -597,11 +538,11 @@ PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, c
         if (pl->K > MAX_K && pl->K <= WIDE_MAX_K && cost_is_symmetric && precision != PILOT_OT_PREC_GENERIC && precision != PILOT_OT_PREC_F64 &&
             pl->max_cost / reg <= h_max_cost_over_reg() && tau <= pilot::H_MAX_TAU && !pilot::test_switch("PILOT_OT_NO_WIDE")) {
             if (!(f32_floor_ulps > 0.0)) f32_floor_ulps = 8.0;
-            return run_wide(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, row_begin, n_rows_g, row_step, d_emd,
+            return run_wide(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, row_begin, n_rows_g, row_step, d_emd,
                             d_iters, d_err, d_flags, static_cast<hipStream_t>(stream));
         }
         if (precision == PILOT_OT_PREC_GENERIC || pl->K > MAX_K || pl->max_cost / reg > MAX_COST_OVER_REG)
-            return run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows_g, row_step, d_emd,
+            return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows_g, row_step, d_emd,
                                d_iters, d_err, d_flags, static_cast<hipStream_t>(stream));
     }
     // (the range is judged by the plan's max_cost / reg: 1 / reg for Trajectory.py:101's normalised cost unless the caller said
@@ -621,22 +562,20 @@ PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, c
                           : (precision == PILOT_OT_PREC_F32 ? pilot::CFG_F32
                              : (precision == PILOT_OT_PREC_BF16X3 ? pilot::CFG_S32 : (precision == PILOT_OT_PREC_F16X2 ? pilot::CFG_H32 : pilot::CFG_F64)));
     auto run = [&](hipStream_t on) {
-        int r = run_grid(cfg, pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, cost_is_symmetric != 0,
+        int r = run_grid(cfg, pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, cost_is_symmetric != 0,
                          row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags, on, mixed);
         // a shape whose operand images do not fit LDS in this precision (non-symmetric cost at large K): the POT-literal
         // kernel takes the whole grid -- the reference has no such limit
         if (r == PILOT_OT_ENOTSUP)
-            r = run_generic(pl, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
-                            d_flags, on);
+            r = run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters,
+                            d_err, d_flags, on);
         return r;
     };
     if (!pl->graph_mode || pl->timing || n_rows == 0) return run(s);
     // graph replay: the first call with a new argument set runs as usual (and grows the work buffers), the second one is
     // captured, later ones replay the instantiated graph
-    const char *dbg = pilot::test_switch("PILOT_OT_DEBUG");
     const pilot_ot_plan::GraphKey key = {d_P, d_M, d_emd, d_iters, d_err, d_flags, reg, stop_thr, tau, f32_floor_ulps, pl->max_cost, num_iter_max,
-                                         check_period, cfg, mixed ? 1 : 0, cost_is_symmetric != 0 ? 1 : 0, row_begin, n_rows, row_step,
-                                         dbg ? atoi(dbg) : 0};
+                                         check_period, cfg, mixed ? 1 : 0, cost_is_symmetric != 0 ? 1 : 0, row_begin, n_rows, row_step, sw};
     if (pl->gexec && key == pl->gkey) {
         HIP_TRY(hipGraphLaunch(pl->gexec, s));
         return PILOT_OT_OK;

@@ -295,7 +295,8 @@ __device__ inline void panel_product(const AOp &aop, const typename C::acc_t (&I
 // the three all-padding registers of that tile as well.  Every kernel variant (stream, tracking) uses
 // this one function, so a pair's bits still do not depend on which kernel solves it.
 template <typename T> using pair_of = T __attribute__((ext_vector_type(2)));
-template <int RT> __host__ __device__ constexpr int tail_steps() { return (RT - 1) * 4 + 1; }   // k-steps when only register 0 of the last tile is live
+__host__ __device__ constexpr int tail_steps(int RT) { return (RT - 1) * 4 + 1; }   // k-steps when only register 0 of the last tile is live
+template <int RT> __host__ __device__ constexpr int tail_steps() { return tail_steps(RT); }
 // global tail image (f32, written by sinkhorn_setup_kernel behind the first-product table): [form 0: G^T-form, 1: G-form]
 // [chain 0..1][k-step][lane] pairs (X[row 2c][k], X[row 2c+1][k]), row h = cell type 16 (RT-1) + h, k = lidx(step, lane / 16)
 template <int RT> __host__ __device__ constexpr int tail_form_stride() { return 2 * tail_steps<RT>() * WAVE; }  // in pairs
@@ -788,7 +789,7 @@ struct GridParams {
     int *fb_count;        //   instead of being written out, and the f64 kernel solves them again (see ring_flush)
     int *nan_list;        // nullable: pairs that end in NaN are appended here and re-solved by the POT-literal kernel, which
     int *nan_count;       //   reverts to the last good iterate like POT does (generic_kernels.hpp)
-    int debug;            // experiment switches (PILOT_OT_DEBUG): bit0 no priority, bit1 no longest-first order
+    int debug;            // PILOT_OT_DEBUG of the call (read by no kernel; the host acts on its bits, DBG_* in grid_plan.hpp)
     const int *unequal;   // fp16-split configuration: control slot CTRL_UNEQUAL (see the refill of the stream kernel)
 };
 
@@ -1176,37 +1177,47 @@ constexpr int GREG_MAX = 64;
 constexpr int HALF_SOLO_MIN_RT = PILOT_HALF_SOLO_MIN_RT;
 constexpr int HALF_OCC4_MAX_RT = 2;
 constexpr int SPLIT_OCC2_MAX_RT = PILOT_SPLIT_OCC2_MAX_RT, SPLIT_OCC2_MAX_RT_TRACK = PILOT_SPLIT_OCC2_MAX_RT_TRACK, HALF_OCC2_MAX_RT = PILOT_HALF_OCC2_MAX_RT;
-// live panel registers per lane: A, B, U, V, ACC (+ RU, RV when tracking)
+// The register and occupancy rules of the stream kernel, as functions of a configuration's traits: the kernel's
+// __launch_bounds__ and body instantiate them through the template forms, the host sizes its launches with the same functions.
+struct CfgShape { int w, nreg; bool split, half; };       // w = sizeof(T) / 4
+template <class C> __host__ __device__ constexpr CfgShape shape_of() { return {int(sizeof(typename C::T) / 4), C::NREG, C::SPLIT, C::HALF}; }
 // the operand image is kept in registers when it needs <= 64 VGPRs per lane and the cost is symmetric
-template <class C, int RT, bool SYM> constexpr bool operands_in_regs() {
-    return !C::SPLIT && SYM && RT * C::NREG * RT * int(sizeof(typename C::T) / 4) <= GREG_MAX;
+__host__ __device__ constexpr bool operands_in_regs(CfgShape c, int RT, bool sym) { return !c.split && sym && RT * c.nreg * RT * c.w <= GREG_MAX; }
+template <class C, int RT, bool SYM> constexpr bool operands_in_regs() { return operands_in_regs(shape_of<C>(), RT, SYM); }
+// live panel registers per lane: A, B, U, V, ACC (+ RU, RV when tracking)
+__host__ __device__ constexpr int panel_regs(CfgShape c, int RT, bool sym, bool track, int tv) {
+    return (track ? 7 : 5) * RT * c.nreg * c.w + c.nreg * c.w + 56 +
+           (tv > 0 ? 24 * c.w : 0) +                         // tail accumulators, broadcast pairs, weights in flight
+           (c.split ? 3 * ((RT + 1) / 2) * 4 + 24 : 0) +     // split panel parts + operand parts in flight
+           (operands_in_regs(c, RT, sym) ? (RT * c.nreg * RT + 2 * tv * tail_steps(RT)) * c.w : 0);
 }
-template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int panel_regs() {
-    return (TRACK ? 7 : 5) * RT * C::NREG * int(sizeof(typename C::T) / 4) + C::NREG * int(sizeof(typename C::T) / 4) + 56 +
-           (TV > 0 ? 24 * int(sizeof(typename C::T) / 4) : 0) +     // tail accumulators, broadcast pairs, weights in flight
-           (C::SPLIT ? 3 * ((RT + 1) / 2) * 4 + 24 : 0) +           // split panel parts + operand parts in flight
-           (operands_in_regs<C, RT, SYM>() ? (RT * C::NREG * RT + 2 * TV * tail_steps<RT>()) * int(sizeof(typename C::T) / 4) : 0);
-}
-template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int min_waves_per_simd() {
+template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int panel_regs() { return panel_regs(shape_of<C>(), RT, SYM, TRACK, TV); }
+__host__ __device__ constexpr int min_waves_per_simd(CfgShape c, int RT, bool sym, bool track, int tv) {
     // split variants: two waves per SIMD up to SPLIT_OCC2_MAX_RT row tiles (tracking variants: SPLIT_OCC2_MAX_RT_TRACK), one wave
     // with the whole register file beyond (3 waves per SIMD at RT <= 4: slower)
     // (fp16-split fast kernel at one / two row-tiles: four -- 82 / 116 registers; with the sharded work queue the 634 x 14 cohort runs
     // 0.242 / 0.195 / 0.185 / 0.193 ms at 2 / 3 / 4 / 6 workgroups per CU, K = 16 .. 32 -12 .. -22 %: tools/small_k_occupancy_probe.py)
-    if (C::HALF && !TRACK && RT <= HALF_OCC4_MAX_RT) return 4;
-    if (C::SPLIT) return RT <= (TRACK ? SPLIT_OCC2_MAX_RT_TRACK : (C::HALF ? HALF_OCC2_MAX_RT : SPLIT_OCC2_MAX_RT)) ? 2 : 1;
-    return panel_regs<C, RT, SYM, TRACK, TV>() <= 128 ? 4 : (panel_regs<C, RT, SYM, TRACK, TV>() <= 168 ? 3 : (panel_regs<C, RT, SYM, TRACK, TV>() <= 256 ? 2 : 1));
+    if (c.half && !track && RT <= HALF_OCC4_MAX_RT) return 4;
+    if (c.split) return RT <= (track ? SPLIT_OCC2_MAX_RT_TRACK : (c.half ? HALF_OCC2_MAX_RT : SPLIT_OCC2_MAX_RT)) ? 2 : 1;
+    const int regs = panel_regs(c, RT, sym, track, tv);
+    return regs <= 128 ? 4 : (regs <= 168 ? 3 : (regs <= 256 ? 2 : 1));
+}
+template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int min_waves_per_simd() {
+    return min_waves_per_simd(shape_of<C>(), RT, SYM, TRACK, TV);
 }
 
 // solo_pairs (64 + ~45 registers of T per lane) rides in the fast launch when the cost is symmetric (PILOT's always is),
 // K <= 64, and the launch's register budget holds it without spilling
-template <class C, int RT, bool SYM, bool TRACK, int TV> constexpr bool solo_in_stream() {
-    constexpr int budget = min_waves_per_simd<C, RT, SYM, TRACK, TV>() >= 4 ? 128 : (min_waves_per_simd<C, RT, SYM, TRACK, TV>() == 3 ? 168 : 256);
+__host__ __device__ constexpr bool solo_in_stream(CfgShape c, int RT, bool sym, bool track, int tv) {
+    const int mw = min_waves_per_simd(c, RT, sym, track, tv);
+    const int budget = mw >= 4 ? 128 : (mw == 3 ? 168 : 256);
     // (round 3 had the fp16-split configuration keep its duplicates in tiles up to K = 32, when a tile's update was shorter
     // than the one-wave-per-pair update; with the straight-line matrix-vector product it is the other way round again:
     // c2 kernel 0.154 -> 0.136 ms, the 1/8 shard of c3 0.253 -> 0.186 ms.  A rule by SHAPE, never by load: the same pair takes
     // the same path in every shard.)
-    return !TRACK && SYM && RT <= 4 && !(C::HALF && RT < HALF_SOLO_MIN_RT) && (64 + 45) * int(sizeof(typename C::T) / 4) <= budget;
+    return !track && sym && RT <= 4 && !(c.half && RT < HALF_SOLO_MIN_RT) && (64 + 45) * c.w <= budget;
 }
+template <class C, int RT, bool SYM, bool TRACK, int TV> constexpr bool solo_in_stream() { return solo_in_stream(shape_of<C>(), RT, SYM, TRACK, TV); }
 
 // TRACK = false: plain scaling iterations; a pair whose POT residual scaling would exceed tau (i.e. POT
 //                would absorb) is handed to the TRACK = true kernel via track_list.
@@ -2052,9 +2063,28 @@ __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT
 // duplicates in the last one) and the work list is emitted from the highest bucket down.  Three tiny
 // launches: bucket ids + histogram, (prefix is folded into) scatter.
 constexpr int ORDER_NB = 48;
-// control block of a call (ints, zeroed per call by the host): [0 .. CTRL_INTS) counters and queue heads, then the order
-// histograms.  Slot CTRL_UNEQUAL is set by the prep kernel when the rows of P do not all carry the same mass.
-constexpr int CTRL_INTS = 16, CTRL_UNEQUAL = 12;
+// Control block of a call (pilot_ot_plan::ctrl; ints, zeroed per call by the host): CTRL_INTS counters and queue heads, then the
+// order histograms and, from a 128-byte boundary, the ticket counters of the two sharded work queues.
+enum : int {
+    CTRL_TRACK_LEN = 0,          // length of track_list: the fast launch's hand-overs to the tracking launch
+    CTRL_GENERIC_HEAD = 0,       // queue head of a POT-literal call of its own (run_generic without a list)
+    CTRL_HEAD_FAST = 1,          // queue heads of the fast launch, the tracking launch and the solo waves
+    CTRL_HEAD_TRACK = 2,
+    CTRL_HEAD_SOLO = 3,
+    CTRL_SPLIT = 4,              // CTRL_SPLIT_INTS ints written by order_scatter_kernel, each the number of leading exact duplicates;
+    CTRL_SPLIT_INTS = 4,         //   the solo waves read the last one
+    CTRL_SOLO_LEN = CTRL_SPLIT + 3,
+    CTRL_FB_LEN = 8,             // length of the f64 fallback list (small reg, or pairs that left the f32 range) and its queue head
+    CTRL_FB_HEAD = 9,
+    CTRL_NAN_LEN = 10,           // length of the NaN list (pairs re-solved by the POT-literal kernel) and its queue head
+    CTRL_NAN_HEAD = 11,
+    CTRL_UNEQUAL = 12,           // set by the prep kernel when the rows of P do not all carry the same mass
+    CTRL_INTS = 16,
+    CTRL_ORDER_HIST = CTRL_INTS,                                              // 2 * ORDER_NB: histogram + scatter cursors
+    CTRL_SHARDS_AT = (CTRL_ORDER_HIST + 2 * ORDER_NB + 31) / 32 * 32,         // QUEUE_SHARDS counters of the fast launch
+    CTRL_SHARDS_TRACK_AT = CTRL_SHARDS_AT + QUEUE_SHARDS * QUEUE_SHARD_STRIDE,  // ... and of the tracking launch
+    CTRL_BLOCK_INTS = CTRL_SHARDS_TRACK_AT + QUEUE_SHARDS * QUEUE_SHARD_STRIDE,
+};
 
 // wave-aggregated LDS counter: lanes with equal `b` share one atomic; returns the lane's slot (base + rank among equals)
 __device__ inline int lds_count_aggregated(int *counters, int b, bool valid) {
@@ -2159,7 +2189,7 @@ __global__ void __launch_bounds__(256) sinkhorn_prep_kernel(const double *__rest
     } else {
         setup_body<C>(Msrc, K, RT, reg, img, Psrc, Pdst, (long)N * RT * C::TILE, write_tail, stop_thr, floor_ulps,
                       ((int)blockIdx.x - n_tiles) * (int)blockDim.x + (int)threadIdx.x, PREP_SETUP_BLOCKS * (int)blockDim.x,
-                      hist - (CTRL_INTS - CTRL_UNEQUAL));
+                      hist - (CTRL_ORDER_HIST - CTRL_UNEQUAL));
     }
 }
 
@@ -2167,9 +2197,9 @@ __global__ void __launch_bounds__(256) sinkhorn_prep_kernel(const double *__rest
 // Every workgroup owns a contiguous chunk of items: LDS histogram of the chunk, ONE global atomic per
 // (workgroup, bucket) to reserve the range, then LDS cursors -- a handful of hot global addresses would
 // otherwise serialise all N^2 atomics.
-// `split` (4 ints, written by workgroup 0): [0], [1] = n_dup, the number of leading list items that the solo waves take (the
-// exact duplicates a == b: top bucket, first in the list) and the initial head of the tile queue; [2], [3] the same count for
-// the solo waves' own queue.  solo_mode bit 1: the launch carries solo waves.
+// `split` (control slots CTRL_SPLIT.., written by workgroup 0): n_dup, the number of leading list items that the solo waves take
+// (the exact duplicates a == b: top bucket, first in the list); the tile queue (`main_queue_head`) starts behind them.
+// solo_mode bit 1: the launch carries solo waves.
 static __global__ void order_scatter_kernel(const unsigned char *__restrict__ bucket, int n_items, const int *__restrict__ hist,
                                      int *__restrict__ cursor, int *__restrict__ list, int *__restrict__ split,
                                      int *__restrict__ main_queue_head, int solo_mode) {
@@ -2183,7 +2213,7 @@ static __global__ void order_scatter_kernel(const unsigned char *__restrict__ bu
     }
     if (blockIdx.x == 0 && threadIdx.x == 64) {
         const int n_dup = (solo_mode & 2) ? gh[ORDER_NB - 1] : 0;
-        split[0] = n_dup; split[1] = n_dup; split[2] = n_dup; split[3] = n_dup;
+        for (int i = 0; i < CTRL_SPLIT_INTS; ++i) split[i] = n_dup;
         *main_queue_head = n_dup;          // the tile queue starts behind the duplicates
     }
     __syncthreads();

@@ -8,6 +8,11 @@
 namespace pilot {
 
 enum { CFG_F32 = 0, CFG_F64 = 1, CFG_S32 = 2, CFG_H32 = 3 };   // CfgF32x16, CfgF64x16, CfgS32x16 (bf16-split products, f32 values), CfgH32x16 (fp16-split)
+// the traits of configuration cfg that the stream kernel's shape rules read (min_waves_per_simd, solo_in_stream)
+inline CfgShape shape_of(int cfg) {
+    if (cfg == CFG_H32) return shape_of<CfgH32x16>();
+    return cfg == CFG_S32 ? shape_of<CfgS32x16>() : (cfg == CFG_F64 ? shape_of<CfgF64x16>() : shape_of<CfgF32x16>());
+}
 
 // persistent stream kernel (one tile per wave); track: tau-tracking variant
 hipError_t launch_stream_f32(int RT, bool sym, bool track, dim3 grid, size_t lds, hipStream_t s, const GridParams &p);

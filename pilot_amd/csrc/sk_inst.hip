@@ -14,22 +14,27 @@ hipError_t stream_one(dim3 grid, size_t lds, hipStream_t s, const GridParams &p)
     hipLaunchKernelGGL(kern, grid, dim3(WAVE * WAVES_PER_WG), lds, s, p);
     return hipGetLastError();
 }
-template <class C, int RT, int TV = 0>
+// variants of RT row-tiles up to MAX_RT (the VALU-tail ones, TV > 0, from two); the fp16-split configuration has no tracking variant
+template <class C, int RT, int TV, int MAX_RT>
 hipError_t stream_rt(bool sym, bool track, dim3 grid, size_t lds, hipStream_t s, const GridParams &p) {
-    if (track) return sym ? stream_one<C, RT, true, true, TV>(grid, lds, s, p) : stream_one<C, RT, false, true, TV>(grid, lds, s, p);
-    return sym ? stream_one<C, RT, true, false, TV>(grid, lds, s, p) : stream_one<C, RT, false, false, TV>(grid, lds, s, p);
+    if constexpr (RT > MAX_RT || (TV > 0 && RT == 1)) return hipErrorInvalidValue;
+    else {
+        if constexpr (C::HALF) { if (track) return hipErrorInvalidValue; }
+        else if (track) return sym ? stream_one<C, RT, true, true, TV>(grid, lds, s, p) : stream_one<C, RT, false, true, TV>(grid, lds, s, p);
+        return sym ? stream_one<C, RT, true, false, TV>(grid, lds, s, p) : stream_one<C, RT, false, false, TV>(grid, lds, s, p);
+    }
 }
-template <class C, int TV = 0>
+template <class C, int TV = 0, int MAX_RT = 8>
 hipError_t stream_any(int RT, bool sym, bool track, dim3 grid, size_t lds, hipStream_t s, const GridParams &p) {
     switch (RT) {
-    case 1: if constexpr (TV == 0) return stream_rt<C, 1, TV>(sym, track, grid, lds, s, p); else return hipErrorInvalidValue;
-    case 2: return stream_rt<C, 2, TV>(sym, track, grid, lds, s, p);
-    case 3: return stream_rt<C, 3, TV>(sym, track, grid, lds, s, p);
-    case 4: return stream_rt<C, 4, TV>(sym, track, grid, lds, s, p);
-    case 5: return stream_rt<C, 5, TV>(sym, track, grid, lds, s, p);
-    case 6: return stream_rt<C, 6, TV>(sym, track, grid, lds, s, p);
-    case 7: return stream_rt<C, 7, TV>(sym, track, grid, lds, s, p);
-    case 8: return stream_rt<C, 8, TV>(sym, track, grid, lds, s, p);
+    case 1: return stream_rt<C, 1, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 2: return stream_rt<C, 2, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 3: return stream_rt<C, 3, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 4: return stream_rt<C, 4, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 5: return stream_rt<C, 5, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 6: return stream_rt<C, 6, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 7: return stream_rt<C, 7, TV, MAX_RT>(sym, track, grid, lds, s, p);
+    case 8: return stream_rt<C, 8, TV, MAX_RT>(sym, track, grid, lds, s, p);
     default: return hipErrorInvalidValue;
     }
 }
@@ -127,30 +132,15 @@ hipError_t launch_stream_s32_l1(int RT, bool sym, bool track, dim3 grid, size_t 
     return stream_any<CfgS32x16, 1>(RT, sym, track, grid, lds, s, p);
 }
 #elif SK_PART == 9
-// fp16-split configuration (fast pass only: no tracking variant), dead registers of the last row-tile skipped
+// fp16-split configuration (fast pass only: no tracking variant), dead registers of the last row-tile skipped (RT 2 .. 4)
 hipError_t launch_stream_h32_l1(int RT, bool sym, dim3 grid, size_t lds, hipStream_t s, const GridParams &p) {
-    switch (RT) {
-    case 2: return sym ? stream_one<CfgH32x16, 2, true, false, 1>(grid, lds, s, p) : stream_one<CfgH32x16, 2, false, false, 1>(grid, lds, s, p);
-    case 3: return sym ? stream_one<CfgH32x16, 3, true, false, 1>(grid, lds, s, p) : stream_one<CfgH32x16, 3, false, false, 1>(grid, lds, s, p);
-    case 4: return sym ? stream_one<CfgH32x16, 4, true, false, 1>(grid, lds, s, p) : stream_one<CfgH32x16, 4, false, false, 1>(grid, lds, s, p);
-    default: return hipErrorInvalidValue;
-    }
+    return stream_any<CfgH32x16, 1, 4>(RT, sym, false, grid, lds, s, p);
 }
 #elif SK_PART == 8
 hipError_t launch_stream_h32_l1(int RT, bool sym, dim3 grid, size_t lds, hipStream_t s, const GridParams &p);
 hipError_t launch_stream_h32(int RT, bool sym, int live1, dim3 grid, size_t lds, hipStream_t s, const GridParams &p) {
     if (live1) return launch_stream_h32_l1(RT, sym, grid, lds, s, p);
-    switch (RT) {
-    case 1: return sym ? stream_one<CfgH32x16, 1, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 1, false, false>(grid, lds, s, p);
-    case 2: return sym ? stream_one<CfgH32x16, 2, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 2, false, false>(grid, lds, s, p);
-    case 3: return sym ? stream_one<CfgH32x16, 3, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 3, false, false>(grid, lds, s, p);
-    case 4: return sym ? stream_one<CfgH32x16, 4, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 4, false, false>(grid, lds, s, p);
-    case 5: return sym ? stream_one<CfgH32x16, 5, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 5, false, false>(grid, lds, s, p);
-    case 6: return sym ? stream_one<CfgH32x16, 6, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 6, false, false>(grid, lds, s, p);
-    case 7: return sym ? stream_one<CfgH32x16, 7, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 7, false, false>(grid, lds, s, p);
-    case 8: return sym ? stream_one<CfgH32x16, 8, true, false>(grid, lds, s, p) : stream_one<CfgH32x16, 8, false, false>(grid, lds, s, p);
-    default: return hipErrorInvalidValue;
-    }
+    return stream_any<CfgH32x16>(RT, sym, false, grid, lds, s, p);
 }
 hipError_t launch_prep_h32(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
                            double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,

@@ -589,6 +589,31 @@ def test_graph_replay_gives_the_same_bits_and_follows_argument_and_content_chang
     plan.close()
 
 
+def test_graph_replay_follows_a_changed_test_switch(switches):
+    """A test switch that changes the launch sequence (PILOT_OT_NO_QUAD: 112 < K <= 128 on the one-wave kernel instead of the
+    four-waves-per-tile one) is part of the graph key: a plan in graph mode captures anew instead of replaying the old kernels."""
+    P, M = make_problem(60, 120, 6, seed=120, cells_per_patient=3000)
+    plain = engine.DevicePlan(P, M)
+    plain.run(0.1, precision="f16x2")
+    E_quad = plain.fetch()[0]
+    switches.setenv("PILOT_OT_NO_QUAD", "1")
+    plain.run(0.1, precision="f16x2")
+    E_one = plain.fetch()[0]
+    switches.delenv("PILOT_OT_NO_QUAD")
+    plain.close()
+    assert np.any(E_quad != E_one)                      # the two kernels' bits differ, so the check below can tell them apart
+    plan = engine.DevicePlan(P, M)
+    plan.enable_graph(True)
+    for _ in range(3):                                  # plain, capture, replay
+        plan.run(0.1, precision="f16x2")
+        np.testing.assert_array_equal(plan.fetch()[0], E_quad)
+    switches.setenv("PILOT_OT_NO_QUAD", "1")
+    for _ in range(3):
+        plan.run(0.1, precision="f16x2")
+        np.testing.assert_array_equal(plan.fetch()[0], E_one)
+    plan.close()
+
+
 @pytest.mark.parametrize("reg,tau,lo,hi", [(0.1, 25.0, 0.1, 0.6), (0.05, 30.0, 0.8, 1.0)])
 def test_tau_tracking_path_mixes_with_the_fast_path(reg, tau, lo, hi):
     """A small tau makes a fraction of the pairs tau-absorb, so within one call some pairs finish in the

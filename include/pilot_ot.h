@@ -323,7 +323,10 @@ int pilot_ot_comm_all_reduce_max(pilot_ot_comm *comm, double *d_vals, int n, voi
  * silhouette:    sklearn.metrics.silhouette_score(D, labels, metric="precomputed"); labels in [0, n_clusters);
  *                samples (nullable, N) receives silhouette_samples.
  * knn_kernel:    Kmat[i][j] = exp(-D[i][j]^2 / (4 epsilon)) for the k smallest entries of row i (the point itself included,
- *                like sklearn's kneighbors_graph on the fitted data), 0 elsewhere: the kernel matrix pydiffmap builds. */
+ *                like sklearn's kneighbors_graph on the fitted data), 0 elsewhere: the kernel matrix pydiffmap builds.
+ *                A row is sorted in LDS: N > PILOT_OT_KNN_MAX_N -> PILOT_OT_ENOTSUP, from every entry point that reaches the
+ *                kNN kernel, before anything is allocated or copied. */
+#define PILOT_OT_KNN_MAX_N 16384
 #define PILOT_OT_ROWMETRIC_EUCLIDEAN 0
 #define PILOT_OT_ROWMETRIC_COSINE 1
 int pilot_ot_row_distances(const double *E, int N, int normalize_by_max, int metric, double *D);

@@ -69,6 +69,13 @@ constexpr int GENERIC_MAX_K = 2048;  // the reference-semantics fallback kernel 
 constexpr int EMD_MAX_K = 256;       // exact-OT kernel: 4 rows / columns per lane
 constexpr int WIDE_MAX_K = 256;      // sinkhorn_wide_kernel: 128 < K <= 256, eight waves per 16-pair tile
 
+// the kNN kernel sorts a row in LDS, padded to the next power of two: 16384 doubles = 128 KiB is the largest that fits.  Every
+// entry point that reaches the kernel asks this first, the host forms before they stage their N x N buffers.
+inline int knn_rows_supported(int N) {
+    return N <= PILOT_OT_KNN_MAX_N ? PILOT_OT_OK
+                                   : abi_fail(PILOT_OT_ENOTSUP, "N=%d rows do not fit the LDS sort (at most %d)", N, PILOT_OT_KNN_MAX_N);
+}
+
 // cell-level cohort, internal face used by the multi-device form (pilot_ot_multi.hip)
 int cell_enqueue_rows(pilot_ot_cell_cohort *c, double scale, double reg, int num_iter_max, double stop_thr, int check_period,
                       double f32_floor_ulps, int row_begin, int row_end, int row_step, size_t *n_out);

@@ -56,9 +56,9 @@ PILOT_API int pilot_ot_silhouette_dev(const double *d_D, const int *d_labels, in
 PILOT_API int pilot_ot_knn_kernel_dev(const double *d_D, int N, int k, double epsilon, double *d_Kmat, void *stream) {
     if (!d_D || !d_Kmat) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0 || k < 1 || !(epsilon > 0.0)) return fail(PILOT_OT_EINVAL, "N=%d k=%d epsilon=%g out of range", N, k, epsilon);
+    if (int rc = pilot::knn_rows_supported(N)) return rc;
     if (k > N) k = N;
     const int np2 = next_pow2(N);
-    if (sizeof(double) * (size_t)np2 > 150 * 1024) return fail(PILOT_OT_ENOTSUP, "N=%d rows do not fit the LDS sort", N);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::knn_kernel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(sizeof(double) * np2)));
     hipLaunchKernelGGL(pilot::knn_kernel_kernel, dim3(N), dim3(256), sizeof(double) * np2, static_cast<hipStream_t>(stream), d_D, N, np2, k,
@@ -139,6 +139,7 @@ PILOT_API int pilot_ot_silhouette(const double *D, const int *labels, int N, int
 PILOT_API int pilot_ot_knn_kernel(const double *D, int N, int k, double epsilon, double *Kmat) {
     if (!D || !Kmat) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0) return fail(PILOT_OT_EINVAL, "N=%d must be positive", N);
+    if (int rc = pilot::knn_rows_supported(N)) return rc;
     double *dD = nullptr, *dK = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
     hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
@@ -174,6 +175,7 @@ PILOT_API int pilot_ot_silhouette_of_rows(const double *E, int E_is_device, int 
 PILOT_API int pilot_ot_diffusion_kernel_of_rows(const double *E, int E_is_device, int N, int k, double epsilon, double *D_out, double *Kmat) {
     if (!E || !Kmat) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0) return fail(PILOT_OT_EINVAL, "N=%d must be positive", N);
+    if (int rc = pilot::knn_rows_supported(N)) return rc;
     double *dE = nullptr, *dD = nullptr, *dK = nullptr, *dM = nullptr;
     const size_t bytes = sizeof(double) * (size_t)N * N;
     hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);

@@ -202,6 +202,7 @@ PILOT_API int pilot_ot_diffusion_map_of_rows(const double *E, int E_is_device, i
     int rc = check_args(N, epsilon, alpha, n_evecs);
     if (rc != PILOT_OT_OK) return rc;
     if (k < 1) return fail(PILOT_OT_EINVAL, "k=%d must be positive", k);
+    if ((rc = pilot::knn_rows_supported(N)) != PILOT_OT_OK) return rc;
     const size_t nn = (size_t)N * N, no = (size_t)N * n_evecs;
     double *dE = nullptr, *dD, *dK, *dM, *dOut;
     HIP_TRY(pilot::ws(pilot::WS_DM_D, nn, &dD));

@@ -2,7 +2,9 @@
 numpy / scipy restatement of pydiffmap (tests/diffmap_restatement.py) and a dense eigensolver."""
 import numpy as np
 import pytest
+from scipy.spatial.distance import cdist
 
+import consumers_restatement as C
 import diffmap_restatement as R
 from conftest import GOLDEN_REAL, golden_adata, load_golden
 from pilot_amd import _lib, engine, tl
@@ -71,6 +73,31 @@ def check_against_restatement(K, dmap, evecs, evals, eps, alpha, n_evecs):
     assert (np.abs(dmap - rd).max(0) / np.abs(rd).max(0)).max() <= 1e-6
 
 
+def check_kernel_against_stable_argsort(K, E, knn, eps):
+    """The device's kNN kernel matrix K (K7) against an independent one: scipy's row distances of E / E.max(), the k smallest
+    of every row by a stable argsort (ties in index order), exp(-d^2 / (4 eps)) there and 0 elsewhere.  The device rounds its
+    distances differently from scipy (each within (N/2 + 3) u relative of the exact one, tests/consumers_restatement.py), so an
+    entry whose distance lies within that of the row's k-th may fall on either side of the cut: such rows are counted on the
+    reference alone and must be at most 1 % of the rows (a condition on the fixture, not a tolerance); everywhere else the zero
+    pattern is exact.  A kept value is exp of a distance with relative error e = 2 (N/2 + 3) u: 2 e d^2 / (4 eps) relative,
+    plus the 4 u of the two exps."""
+    N = E.shape[0]
+    X = E / E.max()
+    D = cdist(X, X)
+    want = C.knn_kernel_reference(D, knn, eps)
+    e = 2 * C.euclid_bound(N)
+    near = C.near_cut_entries(D, knn, e)
+    n_close = int(near.any(1).sum())
+    print("    [measured] N=%d knn=%d: %d rows with an entry within the rounding bound of the k-th distance" % (N, knn, n_close))
+    assert n_close <= 0.01 * N, "%d of %d rows are tied at the cut within rounding: pick another knn for this fixture" % (n_close, N)
+    assert ((K > 0).sum(1) == min(knn, N)).all()
+    assert (((K > 0) == (want > 0)) | near).all(), "kept neighbours differ from the stable-argsort rule away from the cut"
+    kept = K > 0
+    G = np.exp(-D ** 2 / (4.0 * eps))
+    tol = C.KNN_VALUE_BOUND + 2 * e * D ** 2 / (4.0 * eps)
+    assert (np.abs(K - G)[kept] <= (tol * G)[kept]).all()
+
+
 # (matrix, knn, epsilon, alpha, n_evecs): every value of each parameter appears; knn >= N is the full Gaussian kernel
 CASES = [
     ("c1", 5, 1.0, 0.5, 2), ("c1", 16, 0.3, 0.0, 5), ("c1", 64, 1.0, 1.0, 10), ("c1", 20, 0.3, 0.5, 1),
@@ -84,6 +111,7 @@ CASES = [
 def test_matches_the_pydiffmap_restatement(matrices, name, knn, eps, alpha, n_evecs):
     E = matrices(name)
     _, K = engine.diffusion_kernel_of_rows(E, k=knn, epsilon=eps, return_distances=False)     # step 1: K7's kernel
+    check_kernel_against_stable_argsort(K, E, knn, eps)                                       # ... held to an independent one
     dmap, evecs, evals, info = engine.diffusion_map_of_rows(E, n_evecs=n_evecs, epsilon=eps, alpha=alpha, k=knn, return_info=True)
     assert info["flags"] == 0 and info["converged"] and not info["degenerate"], info
     assert dmap.shape == evecs.shape == (E.shape[0], n_evecs) and evals.shape == (n_evecs,)

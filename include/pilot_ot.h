@@ -428,6 +428,39 @@ int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int dtype, int
                                   int n_problems, const int *cols, const int *models, int B, const int *idx, double epsilon,
                                   double *params, double *sigma, int *steps, int *flags, int *n_not_converged);
 
+/* ---- gene curve clustering (K11): the numerical core of pilotpy's genes_selection_analysis (plot/gene_selection_analysis.py:
+ * get_noised_curves, cluster_genes_curves, compute_curves_activities; plot/curve_activity.py).  All in f64 with fixed-order sums
+ * and no floating-point atomics: a repeated call, and the host and device routes of an argument, return the same bits.  A matrix
+ * argument with an *_is_device flag is a host array or a dense row-major buffer in HBM; vectors are host arrays. */
+#define PILOT_OT_LINKAGE_MAX_G 32768   /* rows of a linkage: its G x G float64 distance matrix (8 GiB here) is held in HBM */
+#define PILOT_OT_LINKAGE_SINGLE 0
+#define PILOT_OT_LINKAGE_COMPLETE 1
+#define PILOT_OT_LINKAGE_AVERAGE 2
+#define PILOT_OT_LINKAGE_WEIGHTED 3
+/* Sample standard deviation (ddof 1, two passes: mean, then squared deviations) of column cols[j] (cols NULL: every column,
+ * n_sel = n_cols) of Y over each row segment offsets[s] .. offsets[s + 1] (n_segments + 1 non-decreasing entries in [0, n];
+ * n_segments <= 65535).  Y: n x n_cols, leading dimension ld (elements), float32 (dtype 0) or float64 (1).  out: n_segments x
+ * n_sel; a segment of one row (or none) gives NaN. */
+int pilot_ot_segment_std(const void *Y, int Y_is_device, int dtype, long long n, int n_cols, long long ld, const long long *offsets,
+                         int n_segments, const int *cols, int n_sel, double *out, int out_is_device);
+/* out[g][t] = design(models[g], times[t]) . params[g] (params: G x 3 = Intercept, Treat, Treat2; model 0 linear [1, t],
+ * 1 linear_quadratic [1, t, t^2], 2 quadratic [1, t^2]) + (sd, nullable, T x G) sd[t][g] / 10 * (Treat + Treat2 - Intercept), a
+ * NaN entry then set to 0; each row standardised over its T values like scikit-learn's StandardScaler (population variance, a
+ * scale below 10 DBL_EPSILON becomes 1).  out: G x T. */
+int pilot_ot_fitted_curves(const double *params, const int *models, int G, const double *times, int T, const double *sd,
+                           int sd_is_device, double *out, int out_is_device);
+/* scipy.cluster.hierarchy.linkage(pdist(Y), method) of the G rows of Y (G x T): Euclidean distances in the direct form
+ * sqrt(sum (a - b)^2), the nearest-neighbour chain over the full distance matrix in HBM (one persistent workgroup; ties towards
+ * the previous chain element, then the lowest index; exactly G - 1 merges and at most 4 G chain steps, PILOT_OT_EHIP if that cap
+ * is ever reached), then scipy's stable sort by height and labelling.  Z (host): (G - 1) x 4 = smaller root id, larger root id,
+ * height, size; new clusters are numbered G + i.  dmax (nullable): the largest pairwise distance; chain_steps (nullable).
+ * PILOT_OT_EINVAL: G < 2, G > PILOT_OT_LINKAGE_MAX_G, T < 1, a non-finite value; PILOT_OT_ENOTSUP: any other method. */
+int pilot_ot_linkage_of_rows(const double *Y, int Y_is_device, int G, int T, int method, double *Z, double *dmax, int *chain_steps);
+/* Per row of curves (G x T) over the strictly increasing times (T >= 2, else PILOT_OT_EINVAL): out (host, G x 4) = terminal logFC,
+ * transient logFC, switching time, area, as plot/curve_activity.py defines them (median-of-three clamp, trapezoid rule over the
+ * times scaled to [0, 1], + 1e-300 in the switching time's denominator), unrounded. */
+int pilot_ot_curve_activities(const double *curves, int curves_is_device, int G, int T, const double *times, double *out);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

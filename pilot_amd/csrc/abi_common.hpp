@@ -29,6 +29,7 @@ enum WsSlot {
     WS_DM_S, WS_DM_V, WS_DM_VEC, WS_DM_Z, WS_DM_PSI, WS_DM_E, WS_DM_D, WS_DM_K, WS_DM_MAX, WS_DM_OUT,  // pilot_ot_diffmap.hip
     WS_TF_U, WS_TF_Y, WS_TF_OUT, WS_TF_COLS,                                    // pilot_ot_trajfit.hip
     WS_BOOT_U, WS_BOOT_OUT, WS_BOOT_IDX, WS_BOOT_Y,                             // pilot_ot_bootfit.hip
+    WS_CV_Y, WS_CV_IN, WS_CV_AUX, WS_CV_OUT, WS_CV_BMAX, WS_CV_CHAIN, WS_CV_Z,   // pilot_ot_curves.hip
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

@@ -875,3 +875,180 @@ def bootstrap_huber_fits(Y, x, cols, models, idx, epsilon=1.35, return_info=Fals
         info["not_converged"] = nnc.value
         return params, info
     return params
+
+
+# ---- gene curve clustering (K11; pilotpy's genes_selection_analysis, plot/gene_selection_analysis.py) ------------------------
+LINKAGE_METHODS = tuple(_lib.LINKAGE_METHODS)
+_LINKAGE_UNSUPPORTED = ("centroid", "median", "ward")
+
+
+def _dense_arg(Y, name, dtypes=(np.float32, np.float64)):
+    """(pointer, is_device, rows, columns, leading dimension, dtype, keep-alive) of a 2-D matrix: numpy array or DeviceMatrix"""
+    if isinstance(Y, DeviceMatrix):
+        if len(Y.shape) != 2 or Y.dtype not in dtypes:
+            raise ValueError("%s: a 2-D %s DeviceMatrix, got %s %s" % (name, " / ".join(np.dtype(d).name for d in dtypes), Y.shape, Y.dtype))
+        return ctypes.c_void_p(Y.ptr), 1, Y.shape[0], Y.shape[1], Y.shape[1], Y.dtype, Y
+    Y = np.asarray(Y)
+    if Y.ndim != 2:
+        raise ValueError("%s must be 2-D, got %s" % (name, Y.shape))
+    if Y.dtype not in dtypes:
+        Y = Y.astype(np.float64)
+    Y = np.ascontiguousarray(Y)
+    return ctypes.c_void_p(Y.ctypes.data), 0, Y.shape[0], Y.shape[1], Y.shape[1], Y.dtype, Y
+
+
+def _device_result(rows, cols):
+    buf = _DeviceBuffer(rows * cols * 8)
+    return DeviceMatrix(buf.ptr, rows, owner=buf, shape=(rows, cols), dtype=np.float64)
+
+
+def download(D):
+    """The contents of a :class:`DeviceMatrix` as a numpy array."""
+    out = np.empty(D.shape, dtype=D.dtype)
+    if out.size:
+        _lib.check(_lib.load().pilot_ot_memcpy_d2h(out.ctypes.data, ctypes.c_void_p(D.ptr), out.nbytes))
+    return out
+
+
+def segment_std(Y, offsets, cols=None, device=False):
+    """K11a: the sample standard deviation (ddof 1, what pandas' ``groupby(...).std()`` gives) of every selected column of ``Y``
+    (rows x columns, float32 / float64, numpy array or :class:`DeviceMatrix`) over each contiguous row segment
+    ``offsets[s]:offsets[s + 1]``.  Returns segments x columns float64 (a :class:`DeviceMatrix` with ``device=True``); a segment
+    of one row gives NaN.  Two passes in f64 (mean, then squared deviations), sums in a fixed order."""
+    ptr, on_dev, n, n_cols, ld, dtype, keep = _dense_arg(Y, "Y")
+    offsets = np.ascontiguousarray(np.ravel(offsets), dtype=np.int64)
+    if offsets.size < 1:
+        raise ValueError("offsets needs at least one entry")
+    S = offsets.size - 1
+    if cols is not None:
+        cols = np.ascontiguousarray(np.ravel(cols), dtype=np.int32)
+    n_sel = n_cols if cols is None else cols.size
+    out = _device_result(S, n_sel) if device else np.empty((S, n_sel), dtype=np.float64)
+    _lib.check(_lib.load().pilot_ot_segment_std(
+        ptr, on_dev, 0 if dtype == np.float32 else 1, n, n_cols, ld, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), S,
+        None if cols is None else _lib.iptr(cols), n_sel, ctypes.c_void_p(out.ptr if device else out.ctypes.data), int(device)))
+    del keep
+    return out
+
+
+def fitted_curves(params, model, times, noise=None, device=False):
+    """One standardised curve per gene over ``times``: ``design(model[g], t) @ params[g]`` (``params``: G x 3 = Intercept, Treat,
+    Treat2; ``model``: indices into :data:`TRAJFIT_MODELS`, or their names), plus, with ``noise`` (T x G per-time-point spreads,
+    :func:`segment_std`'s output, numpy or :class:`DeviceMatrix`), ``noise[t, g] / 10 * (Treat + Treat2 - Intercept)`` with NaN
+    sums set to 0; then scikit-learn's StandardScaler per gene (make_curves and the scaling of get_noised_curves,
+    gene_selection_analysis.py:52-165).  Returns G x T float64 (a :class:`DeviceMatrix` with ``device=True``)."""
+    params = _as_f64(params, "params")
+    if params.ndim != 2 or params.shape[1] != 3:
+        raise ValueError("params must be G x 3 (Intercept, Treat, Treat2), got %s" % (params.shape,))
+    G = params.shape[0]
+    model = np.ravel(np.asarray(model))
+    if model.dtype.kind in "OUS":
+        model = np.array([TRAJFIT_MODELS.index(str(m)) for m in model], dtype=np.int32)
+    model = np.ascontiguousarray(model, dtype=np.int32)
+    if model.size != G:
+        raise ValueError("model has %d entries for %d genes" % (model.size, G))
+    times = _as_f64(np.ravel(times), "times")
+    T = times.size
+    if noise is None:
+        sp, s_dev, keep = None, 0, None
+    else:
+        sp, s_dev, r, c, _, _, keep = _dense_arg(noise, "noise", (np.float64,))
+        if (r, c) != (T, G):
+            raise ValueError("noise must be T x G = %d x %d, got %d x %d" % (T, G, r, c))
+    out = _device_result(G, T) if device else np.empty((G, T), dtype=np.float64)
+    _lib.check(_lib.load().pilot_ot_fitted_curves(_lib.dptr(params), _lib.iptr(model), G, _lib.dptr(times), T, sp, s_dev,
+                                                  ctypes.c_void_p(out.ptr if device else out.ctypes.data), int(device)))
+    del keep
+    return out
+
+
+def linkage_of_rows(Y, method="complete", return_info=False):
+    """K11b: ``scipy.cluster.hierarchy.linkage(pdist(Y), method)`` of the rows of ``Y`` (G x T float64, numpy array or
+    :class:`DeviceMatrix`) on the device, and ``pdist(Y).max()``: Euclidean distances in the direct form, the nearest-neighbour
+    chain over the G x G matrix in HBM, scipy's ordering and labelling of Z.  Returns ``(Z, dmax)``; the distances never reach
+    the host.  ``method``: single, complete, average or weighted; G at most ``_lib.LINKAGE_MAX_G`` (the matrix is G^2 x 8 bytes
+    of HBM)."""
+    if method in _LINKAGE_UNSUPPORTED:
+        raise NotImplementedError("linkage method %r needs centroids: only %s run on the device" % (method, ", ".join(LINKAGE_METHODS)))
+    if method not in _lib.LINKAGE_METHODS:
+        raise ValueError("Invalid method: %r" % (method,))
+    ptr, on_dev, G, T, _, _, keep = _dense_arg(Y, "Y", (np.float64,))
+    if G < 2:
+        raise ValueError("The number of observations cannot be determined on an empty distance matrix.")
+    if G > _lib.LINKAGE_MAX_G:
+        raise ValueError("G=%d rows: the G x G float64 distance matrix would take %.1f GiB of HBM; at most %d rows"
+                         % (G, G * G * 8 / 2.0 ** 30, _lib.LINKAGE_MAX_G))
+    if not on_dev and not np.all(np.isfinite(keep)):
+        raise ValueError("Y contains NaN or inf")
+    Z = np.empty((G - 1, 4), dtype=np.float64)
+    dmax, steps = ctypes.c_double(0.0), ctypes.c_int(0)
+    _lib.check(_lib.load().pilot_ot_linkage_of_rows(ptr, on_dev, G, T, _lib.LINKAGE_METHODS[method], _lib.dptr(Z), ctypes.byref(dmax),
+                                                    ctypes.byref(steps)))
+    del keep
+    if return_info:
+        return Z, dmax.value, dict(chain_steps=steps.value)
+    return Z, dmax.value
+
+
+def flat_clusters(Z, t):
+    """``scipy.cluster.hierarchy.fcluster(Z, t, 'distance')`` restated on the host (Z is small): a node whose height and whose
+    descendants' heights are all <= t is one cluster; numbers are handed out depth-first from the root, left child first.
+    The loop is scipy's cluster_monocrit (cluster/_hierarchy.pyx) step by step, so the numbering is scipy's."""
+    Z = np.asarray(Z, dtype=np.float64)
+    if Z.ndim != 2 or Z.shape[1] != 4:
+        raise ValueError("Z must be a (G - 1) x 4 linkage matrix, got %s" % (Z.shape,))
+    n = Z.shape[0] + 1
+    left, right = Z[:, 0].astype(np.int64), Z[:, 1].astype(np.int64)
+    md = Z[:, 2].copy()                                   # the largest height in each node's subtree (children come first in Z)
+    for i in range(n - 1):
+        for c in (left[i], right[i]):
+            if c >= n and md[c - n] > md[i]:
+                md[i] = md[c - n]
+    T = np.zeros(n, dtype=np.int32)
+    if n == 1:
+        T[0] = 1
+        return T
+    # scipy's cluster_monocrit: inner children first (left, then right), then the node's own leaves; a leaf outside every
+    # cluster is a cluster of its own, numbered when its parent is finished
+    nc, leader = 0, -1
+    visited = np.zeros(n - 1, dtype=bool)
+    stack = [n - 2]
+    while stack:
+        i = stack[-1]
+        lc, rc = left[i], right[i]
+        if leader == -1 and md[i] <= t:
+            leader = i
+            nc += 1
+        if lc >= n and not visited[lc - n]:
+            visited[lc - n] = True
+            stack.append(lc - n)
+            continue
+        if rc >= n and not visited[rc - n]:
+            visited[rc - n] = True
+            stack.append(rc - n)
+            continue
+        for c in (lc, rc):
+            if c < n:
+                if leader == -1:
+                    nc += 1
+                T[c] = nc
+        if leader == i:
+            leader = -1
+        stack.pop()
+    return T
+
+
+def curve_activities(curves, times):
+    """G x 4 unrounded float64: terminal logFC, transient logFC, switching time and area of every row of ``curves`` (G x T
+    float64, numpy array or :class:`DeviceMatrix`) over ``times`` (plot/curve_activity.py: median-of-three clamp, trapezoid
+    rule).  ``times`` must be strictly increasing with at least two values (ValueError otherwise, as the reference)."""
+    times = np.ascontiguousarray(np.ravel(times), dtype=np.float64)
+    if times.size < 2 or not (times[1:] > times[:-1]).all():
+        raise ValueError("times must be increasing and have at least 2 values.")
+    ptr, on_dev, G, T, _, _, keep = _dense_arg(curves, "curves", (np.float64,))
+    if T != times.size:
+        raise ValueError("curves has %d columns for %d times" % (T, times.size))
+    out = np.empty((G, 4), dtype=np.float64)
+    _lib.check(_lib.load().pilot_ot_curve_activities(ptr, on_dev, G, T, _lib.dptr(times), _lib.dptr(out)))
+    del keep
+    return out

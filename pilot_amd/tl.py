@@ -22,6 +22,9 @@ diffusion_kernel                               plot/ploting.py:95-110 (the dense
 diffusion_map                                  plot/ploting.py:95-110 (pl.trajectory's embedding, without the plot)
 cell_importance                                Trajectory.py:646-800 (the table and uns keys, without plots or files)
 genes_importance                               Trajectory.py:860-995 (the table, without plots or files)
+get_noised_curves, cluster_genes_curves,       plot/gene_selection_analysis.py:86-203, 360-415, 850-955 and
+compute_curves_activities,                     plot/curve_activity.py (the frames, without plots, files or
+genes_selection_analysis                       enrichment)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -1039,3 +1042,149 @@ def gene_cluster_differentiation(adata, tables, cellnames=(), sort=("Expression 
         genes = np.unique(list(gene_list))
     ts = adata.uns["orders"]["Time_score"]
     return infer_gene_cluster_differentiation(adata, tables, gene_list=genes, start=min(ts), end=max(ts), **kw)
+
+
+# ---- gene curve clustering (plot/gene_selection_analysis.py:86-203, 360-415, 850-955; plot/curve_activity.py) ----------------
+_ACTIVITY_COLUMNS = ["Terminal_logFC", "Terminal_pvalue", "Terminal_adjPvalue", "Transient_logFC", "Switching_time", "area", "cluster"]
+
+
+class _Curves:
+    """Standardised curves that live on the device (genes x time points) with their frame labels."""
+
+    def __init__(self, matrix, index, columns, columns_name=None):
+        self.matrix, self.index, self.columns, self.columns_name = matrix, list(index), columns, columns_name
+
+    def frame(self):
+        df = pd.DataFrame(engine.download(self.matrix), index=pd.Index(self.index, name="Gene ID"), columns=self.columns)
+        df.columns.name = self.columns_name
+        return df
+
+
+def _noised_curves(adata, cell_type, table, filter_table_feature, filter_table_feature_pval, table_filter_thr,
+                   table_filter_pval_thr, col, sample_col, col_cell, normalize):
+    """get_noised_curves with its two curve matrices left on the device: (curves, noised curves, pseudotime_sample_names)"""
+    rows, x = _cell_rows(adata, cell_type, sample_col, col_cell, adata.uns["orders"], col)
+    if rows.size == 0:
+        raise ValueError("no cells of %r in adata.uns['orders']" % (cell_type,))
+    o = np.argsort(x, kind="stable")                 # cells of one time point contiguous (already so after cell_importance)
+    rows, x = rows[o], x[o]
+    times, first = np.unique(x, return_index=True)
+    kind = np.asarray(adata.uns["orders"][col]).dtype        # the frames carry the time points in the dtype of orders[col]
+    labels = times.astype(kind) if kind.kind in "iu" else times
+    names = pd.DataFrame({sample_col: np.asarray(adata.obs[sample_col])[rows[first]]}, index=pd.Index(labels, name=col))
+    offsets = np.r_[first, x.size].astype(np.int64)
+
+    table = table.fillna(0)
+    if "Treat2" not in table.columns:                # genes_importance drops it when no fit has three coefficients
+        table = table.assign(Treat2=0.0)
+    sel = table[(np.abs(table[filter_table_feature]) >= table_filter_thr) & (table[filter_table_feature_pval] <= table_filter_pval_thr)]
+    genes = list(sel["Gene ID"])
+    pos = {g: i for i, g in enumerate(adata.var_names)}
+    missing = [g for g in genes if g not in pos]
+    if missing:
+        raise KeyError("genes of the table that adata.var_names lacks: %s" % missing[:5])
+    cols = np.array([pos[g] for g in genes], dtype=np.int32)
+    params = sel[["Intercept", "Treat", "Treat2"]].to_numpy(dtype=np.float64).reshape(-1, 3)
+    model = np.array([engine.TRAJFIT_MODELS.index(f) for f in sel["Fitted function"]], dtype=np.int32)
+
+    X = adata.X[rows]
+    X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float32)
+    X = np.ascontiguousarray(X)
+    if normalize:
+        Y = np.empty((X.shape[0], cols.size), dtype=X.dtype)
+        _lib_check_normalize(X, cols, Y)
+        sd = engine.segment_std(Y, offsets, device=True) if cols.size else None
+    else:
+        sd = engine.segment_std(X, offsets, cols=cols, device=True) if cols.size else None
+    plain = engine.fitted_curves(params, model, times, device=True)
+    noised = engine.fitted_curves(params, model, times, noise=sd, device=True)
+    return (_Curves(plain, genes, labels), _Curves(noised, genes, list(names[sample_col]), sample_col), names)
+
+
+def get_noised_curves(adata, cell_type, table, filter_table_feature="R-squared", filter_table_feature_pval="adjusted P-value",
+                      table_filter_thr=0.1, table_filter_pval_thr=0.05, col="Time_score", sample_col="sampleID",
+                      col_cell="cell_types", normalize=True):
+    """get_noised_curves (plot/gene_selection_analysis.py:86-165) without files: ``table`` is the frame ``genes_importance``
+    returned (the reference reads Markers/<cell>/Whole_expressions.csv), the cells are those of ``genes_importance``
+    (``adata.uns['orders']``, normalised the same way on the device).  Rows of ``table.fillna(0)`` with
+    ``|table[feature]| >= thr`` and ``table[pval] <= pthr`` are kept; each gene's fitted curve over the sorted time points of the
+    cell type's cells, the same curve plus ``std(cells of the time point, ddof 1) / 10 * (Treat + Treat2 - Intercept)`` (a time
+    point with one cell: the whole entry 0), both standardised per gene like StandardScaler -- all on the device
+    (``engine.segment_std``, ``engine.fitted_curves``).  Returns ``(scaled_curves, scaled_noised_curves,
+    pseudotime_sample_names)`` as the reference's frames.  One deviation: a table without a ``Treat2`` column (genes_importance
+    drops it when no fit has three coefficients) is read as Treat2 = 0; the reference raises KeyError there."""
+    curves, noised, names = _noised_curves(adata, cell_type, table, filter_table_feature, filter_table_feature_pval, table_filter_thr,
+                                           table_filter_pval_thr, col, sample_col, col_cell, normalize)
+    return curves.frame(), noised.frame(), names
+
+
+def _curve_matrix(curves):
+    """(matrix for the engine, gene ids) of a curves frame or of curves left on the device"""
+    if isinstance(curves, _Curves):
+        return curves.matrix, curves.index
+    return np.ascontiguousarray(curves.to_numpy(dtype=np.float64)), list(curves.index)
+
+
+def cluster_genes_curves(curves, cluster_method="complete", cluster_metric="correlation", scaler_value=0.65):
+    """cluster_genes_curves (plot/gene_selection_analysis.py:167-203): Euclidean distances between the curves, agglomerative
+    linkage and ``fcluster(Z, scaler_value * d.max(), 'distance')``; distances and linkage on the device
+    (``engine.linkage_of_rows``), the flat clusters on the host (``engine.flat_clusters``).  ``cluster_metric`` is accepted and
+    ignored: the reference hands scipy's ``linkage`` a condensed Euclidean ``pdist``, for which scipy ignores ``metric``.
+    ``cluster_method``: complete, average, weighted or single; centroid, median and ward raise NotImplementedError.  Fewer than two
+    genes: every gene gets cluster 1 (the reference's ``except ValueError`` path).  Returns a frame ``Gene ID``, ``cluster``."""
+    if cluster_method in engine._LINKAGE_UNSUPPORTED:
+        raise NotImplementedError("cluster_method=%r: the device linkage implements %s" % (cluster_method, ", ".join(engine.LINKAGE_METHODS)))
+    if cluster_method not in engine.LINKAGE_METHODS:
+        raise ValueError("Invalid method: %r" % (cluster_method,))
+    M, genes = _curve_matrix(curves)
+    if len(genes) < 2:
+        clusters = [1] * len(genes)
+    else:
+        Z, dmax = engine.linkage_of_rows(M, cluster_method)
+        clusters = engine.flat_clusters(Z, scaler_value * dmax)
+    return pd.DataFrame({"Gene ID": genes, "cluster": clusters})
+
+
+def compute_curves_activities(curves, genes_clusters, pseudotime_sample_names):
+    """compute_curves_activities (plot/gene_selection_analysis.py:360-415) without files: terminal and transient logFC, switching
+    time and area of every curve on the device (``engine.curve_activities``, unrounded), then on the host, in the reference's
+    order: ``np.round(., 2)``, the z-score of the rounded terminal logFC, ``2 * norm.sf(|z|)`` and the reference's
+    ``adjust_p_values``.  Times that are not strictly increasing, or fewer than two, raise ValueError."""
+    from scipy.stats import norm, zscore
+    M, genes = _curve_matrix(curves)
+    raw = engine.curve_activities(M, np.asarray(pseudotime_sample_names.index, dtype=np.float64))
+    out = pd.DataFrame(index=pd.Index(genes, name="Gene ID"), columns=_ACTIVITY_COLUMNS[:-1])
+    out["Terminal_logFC"] = np.round(raw[:, 0], 2)
+    p = norm.sf(abs(zscore(out["Terminal_logFC"]))) * 2
+    out["Terminal_pvalue"] = p
+    p = np.asarray(p, dtype=np.float64)              # adjust_p_values (gene_selection_analysis.py:352-358)
+    by_descend = p.argsort()[::-1]
+    by_orig = by_descend.argsort()
+    steps = float(len(p)) / np.arange(len(p), 0, -1)
+    out["Terminal_adjPvalue"] = np.minimum(1, np.minimum.accumulate(steps * p[by_descend]))[by_orig]
+    out["Transient_logFC"] = np.round(raw[:, 1], 2)
+    out["Switching_time"] = np.round(raw[:, 2], 2)
+    out["area"] = np.round(raw[:, 3], 2)
+    gc = genes_clusters.set_index(genes_clusters["Gene ID"].values)
+    out["cluster"] = gc.loc[out.index, "cluster"].to_numpy()
+    return out
+
+
+def genes_selection_analysis(adata, cell_type, table, filter_table_feature="R-squared", filter_table_feature_pval="adjusted P-value",
+                             table_filter_thr=0.05, table_filter_pval_thr=0.05, cluster_method="complete",
+                             cluster_metric="correlation", scaler_value=0.4, col="Time_score", sample_col="sampleID",
+                             col_cell="cell_types", normalize=True):
+    """genes_selection_analysis (plot/gene_selection_analysis.py:850-955) without plots, files or enrichment:
+    :func:`get_noised_curves`, then :func:`cluster_genes_curves` and :func:`compute_curves_activities` on the noised curves, which
+    stay on the device between the three steps.  Returns a dict: ``curves``, ``noised_curves``, ``pseudotime_sample_names``,
+    ``genes_clusters``, ``curves_activities`` (rows in the order of the filtered table)."""
+    if cluster_method in engine._LINKAGE_UNSUPPORTED:
+        raise NotImplementedError("cluster_method=%r: the device linkage implements %s" % (cluster_method, ", ".join(engine.LINKAGE_METHODS)))
+    curves, noised, names = _noised_curves(adata, cell_type, table, filter_table_feature, filter_table_feature_pval, table_filter_thr,
+                                           table_filter_pval_thr, col, sample_col, col_cell, normalize)
+    genes_clusters = cluster_genes_curves(noised, cluster_method, cluster_metric, scaler_value)
+    activities = compute_curves_activities(noised, genes_clusters, names)
+    return dict(curves=curves.frame(), noised_curves=noised.frame(), pseudotime_sample_names=names, genes_clusters=genes_clusters,
+                curves_activities=activities)

@@ -461,6 +461,25 @@ int pilot_ot_linkage_of_rows(const double *Y, int Y_is_device, int G, int T, int
  * times scaled to [0, 1], + 1e-300 in the switching time's denominator), unrounded. */
 int pilot_ot_curve_activities(const double *curves, int curves_is_device, int G, int T, const double *times, double *out);
 
+/* ---- group moments (K12): what pilotpy's patient sub-group workflow needs of a cells x genes matrix (tools/patients_sub_clustering.py:
+ * compute_diff_expressions hands two groups of cells to limma; scanpy's highly_variable_genes; plot/ploting.py's Welch t-test).  For
+ * a two-group design all of limma's arithmetic, scanpy's dispersion statistics and Welch's t follow from per-group count, mean and
+ * centred sum of squares, which one pass over Y gives.
+ * Y: n x n_cols_total, row-major with leading dimension ld (elements), float32 (dtype 0) or float64 (1), on the host (copied whole)
+ * or (Y_is_device) in HBM.  codes (host, n): the group of every row, 0 .. n_groups - 1, or negative for a row that is skipped;
+ * n_groups in [1, 8].  cols (host, nullable): the n_cols selected columns, any order, repeats allowed; NULL: every column
+ * (n_cols = n_cols_total).  transform: 0 t(y) = y, 1 t(y) = expm1(y) in f64.
+ * Out (host): count[g] = rows with codes == g; mean[g][j] = their mean of t(y) and m2[g][j] = sum (t(y) - mean)^2 over column
+ * cols[j], both n_groups x n_cols in f64.  A group without rows: count 0, NaN, NaN; a group of one row: m2 = 0 exactly.
+ * The squares are centred throughout (per chunk of rows about the chunk's mean, chunks and row slices joined by Chan's update in a
+ * fixed order); no sum(y^2) - n mean^2 is formed and nothing uses a floating-point atomic: the same bits from every run and
+ * from the host and device routes.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n < 0, n_cols_total < 1, ld < n_cols_total, dtype not 0 / 1, n_groups
+ * outside [1, 8], transform not 0 / 1, n_cols < 0 (or != n_cols_total without cols), a column outside [0, n_cols_total), a code
+ * >= n_groups. */
+int pilot_ot_group_moments(const void *Y, int Y_is_device, int dtype, long long n, int n_cols_total, long long ld, const int *codes,
+                           int n_groups, const int *cols, int n_cols, int transform, long long *count, double *mean, double *m2);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

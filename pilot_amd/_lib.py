@@ -43,6 +43,7 @@ SYMBOLS = [
     "pilot_ot_diffusion_map_dev", "pilot_ot_diffusion_map_of_rows", "pilot_ot_trajectory_fits",
     "pilot_ot_normalize_log1p", "pilot_ot_bootstrap_huber_fits",
     "pilot_ot_segment_std", "pilot_ot_fitted_curves", "pilot_ot_linkage_of_rows", "pilot_ot_curve_activities",
+    "pilot_ot_group_moments",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -156,6 +157,8 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_fitted_curves.argtypes = [dp, ip, c_int, dp, c_int, c_vp, c_int, c_vp, c_int]
     L.pilot_ot_linkage_of_rows.argtypes = [c_vp, c_int, c_int, c_int, c_int, dp, dp, ip]
     L.pilot_ot_curve_activities.argtypes = [c_vp, c_int, c_int, c_int, dp, dp]
+    L.pilot_ot_group_moments.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, ip, c_int, c_int,
+                                         ctypes.POINTER(ctypes.c_longlong), dp, dp]
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

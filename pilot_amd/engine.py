@@ -931,6 +931,82 @@ def segment_std(Y, offsets, cols=None, device=False):
     return out
 
 
+# ---- group moments (K12; what pilotpy's patient sub-group workflow needs of a cells x genes matrix) ---------------------------
+GROUP_MOMENTS_MAX_GROUPS = 8
+_GM_TRANSFORMS = {None: 0, "expm1": 1}
+
+
+class _DeviceColumns:
+    """Columns ``start:stop`` of a 2-D :class:`DeviceMatrix`, in place: the same rows with the parent's leading dimension.  Only
+    :func:`group_moments` reads one (made by :func:`device_columns`)."""
+
+    def __init__(self, parent, start, stop):
+        if len(parent.shape) != 2 or not 0 <= start < stop <= parent.shape[1]:
+            raise ValueError("columns %d:%d of a DeviceMatrix of shape %s" % (start, stop, parent.shape))
+        self.parent, self.ld = parent, parent.shape[1]
+        self.ptr = parent.ptr + int(start) * parent.dtype.itemsize
+        self.shape, self.dtype = (parent.shape[0], int(stop - start)), parent.dtype
+
+
+def device_columns(D, start, stop):
+    """A view of the columns ``start:stop`` of the :class:`DeviceMatrix` D for :func:`group_moments` (no copy; the leading
+    dimension stays D's)."""
+    return _DeviceColumns(D, int(start), int(stop))
+
+
+def group_moments(Y, codes, n_groups, transform=None, cols=None):
+    """K12: per group and selected column, the count, the float64 mean and the centred sum of squares ``sum (t(y) - mean)^2`` of
+    the rows of ``Y`` with ``codes == g`` (include/pilot_ot.h, "group moments").  ``Y``: rows x columns, a C-contiguous float32 /
+    float64 numpy array, a :class:`DeviceMatrix` (one upload can serve several calls) or :func:`device_columns` of one.
+    ``codes``: one int per row, ``0 .. n_groups - 1`` or negative for a row to skip; ``n_groups`` in 1..8.  ``transform``: None or
+    ``"expm1"`` (taken in float64).  ``cols``: the selected columns in any order (default: all).  Returns ``(count, mean, m2)``:
+    ``n_groups`` int64 and two ``n_groups x columns`` float64 arrays; an empty group gives 0 and NaN, a group of one row m2 = 0.
+    One pass over Y; sums in a fixed order, so a repeated call and the host and device routes return the same bits.  Every
+    argument is checked before any device work (ValueError)."""
+    if transform not in _GM_TRANSFORMS:
+        raise ValueError("transform=%r must be None or 'expm1'" % (transform,))
+    if isinstance(n_groups, bool) or int(n_groups) != n_groups or not 1 <= n_groups <= GROUP_MOMENTS_MAX_GROUPS:
+        raise ValueError("n_groups=%r must be an integer in 1..%d" % (n_groups, GROUP_MOMENTS_MAX_GROUPS))
+    n_groups = int(n_groups)
+    if isinstance(Y, (DeviceMatrix, _DeviceColumns)):
+        if len(Y.shape) != 2 or Y.dtype not in (np.float32, np.float64):
+            raise ValueError("Y: a 2-D float32 / float64 DeviceMatrix, got %s %s" % (Y.shape, Y.dtype))
+        ptr, on_dev, (n, n_total), dtype = ctypes.c_void_p(Y.ptr), 1, Y.shape, Y.dtype
+        ld = Y.ld if isinstance(Y, _DeviceColumns) else n_total
+    else:
+        if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.dtype not in (np.float32, np.float64):
+            raise ValueError("Y: a 2-D float32 / float64 numpy array or a DeviceMatrix, got %s %s"
+                             % (getattr(Y, "shape", type(Y).__name__), getattr(Y, "dtype", "")))
+        if not Y.flags.c_contiguous:
+            raise ValueError("Y must be C-contiguous (np.ascontiguousarray), got strides %s" % (Y.strides,))
+        ptr, on_dev, (n, n_total), dtype, ld = ctypes.c_void_p(Y.ctypes.data), 0, Y.shape, Y.dtype, Y.shape[1]
+    if n_total < 1:
+        raise ValueError("Y has no columns")
+    codes = np.asarray(codes)
+    if codes.ndim != 1 or codes.size != n:
+        raise ValueError("codes has shape %s for %d rows" % (codes.shape, n))
+    if codes.dtype.kind not in "iu":
+        raise ValueError("codes must be integers, got %s" % codes.dtype)
+    if n and int(codes.max()) >= n_groups:
+        raise ValueError("codes reach %d with n_groups=%d" % (int(codes.max()), n_groups))
+    codes = np.ascontiguousarray(np.maximum(codes, -1), dtype=np.int32)
+    if cols is not None:
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or cols.dtype.kind not in "iu":
+            raise ValueError("cols: a 1-D array of column indices, got %s %s" % (cols.shape, cols.dtype))
+        if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= n_total):
+            raise ValueError("cols outside [0, %d)" % n_total)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+    n_sel = n_total if cols is None else cols.size
+    count = np.empty(n_groups, dtype=np.int64)
+    mean, m2 = np.empty((n_groups, n_sel)), np.empty((n_groups, n_sel))
+    _lib.check(_lib.load().pilot_ot_group_moments(
+        ptr, on_dev, 0 if dtype == np.float32 else 1, n, n_total, ld, _lib.iptr(codes), n_groups,
+        None if cols is None else _lib.iptr(cols), n_sel, _GM_TRANSFORMS[transform],
+        count.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.dptr(mean), _lib.dptr(m2)))
+    return count, mean, m2
+
+
 def fitted_curves(params, model, times, noise=None, device=False):
     """One standardised curve per gene over ``times``: ``design(model[g], t) @ params[g]`` (``params``: G x 3 = Intercept, Treat,
     Treat2; ``model``: indices into :data:`TRAJFIT_MODELS`, or their names), plus, with ``noise`` (T x G per-time-point spreads,

@@ -25,6 +25,10 @@ genes_importance                               Trajectory.py:860-995 (the table,
 get_noised_curves, cluster_genes_curves,       plot/gene_selection_analysis.py:86-203, 360-415, 850-955 and
 compute_curves_activities,                     plot/curve_activity.py (the frames, without plots, files or
 genes_selection_analysis                       enrichment)
+compute_diff_expressions,                      patients_sub_clustering.py:15-240 (limma's lmFit / eBayes / topTable
+extract_cells_from_gene_expression_for_...,    restated from device moments, without R, plots or files) and
+highly_variable_genes,                         scanpy's pp.highly_variable_genes(flavor='seurat') restated;
+cell_type_diff_two_sub_patient_groups          plot/ploting.py:460-556 (the table, without the plot or the file)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -1188,3 +1192,255 @@ def genes_selection_analysis(adata, cell_type, table, filter_table_feature="R-sq
     activities = compute_curves_activities(noised, genes_clusters, names)
     return dict(curves=curves.frame(), noised_curves=noised.frame(), pseudotime_sample_names=names, genes_clusters=genes_clusters,
                 curves_activities=activities)
+
+
+# ---- patient sub-group detection: HVG, moderated t, Welch t (tools/patients_sub_clustering.py:15-240, plot/ploting.py:460-556) --
+_DE_DESIGNS = ("reference", "two_group")
+
+
+def highly_variable_genes(X, n_top_genes=2000):
+    """scanpy's ``pp.highly_variable_genes(flavor='seurat')`` for one batch, restated (scanpy is not installed where this
+    library is built and tested, so the rule is UNPINNED here, like ``normalize_total``).  ``X``: the cells x genes log1p values, a
+    C-contiguous float32 / float64 array or an ``engine.DeviceMatrix``.  Mean and ddof-1 variance of ``expm1(X)`` per gene come
+    from one device pass (``engine.group_moments``); the tail is scanpy's, on the host with pandas: a mean of 0 becomes 1e-12,
+    dispersion = var / mean with 0 -> NaN, then its log; log1p of the mean; ``pd.cut`` of the means into 20 bins; per bin the mean
+    and ddof-1 std of the dispersions, a one-gene bin getting std = its mean and mean = 0; the normalised dispersion; the cut-off
+    is the ``n_top_genes``-th largest non-NaN value (all of them when there are fewer) and a gene is selected when
+    ``nan_to_num(value) >= cutoff``.  Returns a frame (one row per gene, in gene order) with ``means``, ``dispersions``,
+    ``dispersions_norm``, ``highly_variable``."""
+    n_top_genes = int(n_top_genes)
+    if n_top_genes < 1:
+        raise ValueError("n_top_genes=%d must be positive" % n_top_genes)
+    n = X.shape[0]
+    count, mean, m2 = engine.group_moments(X, np.zeros(n, dtype=np.int32), 1, transform="expm1")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean, var = mean[0].copy(), m2[0] / (n - 1.0)
+        mean[mean == 0] = 1e-12
+        dispersion = var / mean
+        dispersion[dispersion == 0] = np.nan
+        dispersion = np.log(dispersion)
+        mean = np.log1p(mean)
+    df = pd.DataFrame({"means": mean, "dispersions": dispersion})
+    df["mean_bin"] = pd.cut(df["means"], bins=20)
+    grouped = df.groupby("mean_bin", observed=False)["dispersions"]
+    bin_mean, bin_std = grouped.mean(), grouped.std(ddof=1)
+    single = bin_std.isnull()
+    bin_std[single] = bin_mean[single].values
+    bin_mean[single] = 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = (df["dispersions"].values - bin_mean[df["mean_bin"]].values) / bin_std[df["mean_bin"]].values
+    ranked = np.sort(norm[~np.isnan(norm)])[::-1]
+    if ranked.size == 0:
+        raise ValueError("highly_variable_genes: no gene has a finite normalised dispersion")
+    cutoff = ranked[min(n_top_genes, ranked.size) - 1]
+    return pd.DataFrame({"means": mean, "dispersions": dispersion, "dispersions_norm": norm,
+                         "highly_variable": np.nan_to_num(norm) >= cutoff})
+
+
+def _cell_type_rows(adata, col_cell, cell):
+    return np.flatnonzero(np.asarray(adata.obs[col_cell].isin([cell])))
+
+
+def _cell_type_values(adata, rows, normalization):
+    """The rows ``rows`` of adata.X (dense or CSR) as a dense float32 / float64 array, optionally normalize_total(1e4) + log1p on
+    the device"""
+    X = adata.X[rows]
+    X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float32)
+    X = np.ascontiguousarray(X)
+    if normalization and X.size:
+        out = np.empty_like(X)
+        _lib_check_normalize(X, np.arange(X.shape[1], dtype=np.int32), out)
+        X = out
+    return X
+
+
+def extract_cells_from_gene_expression_for_clustering(adata, sample_col, col_cell, cell_list, normalization=True, n_top_genes=2000,
+                                                      highly_variable_genes_=False):
+    """extract_cells_from_gene_expression_for_clustering (tools/patients_sub_clustering.py:15-76) without the CSV file: the
+    expression frame of the FIRST cell type of ``cell_list`` (the reference returns inside its loop) -- one row per cell, one
+    column per gene (every gene, or the highly variable ones of :func:`highly_variable_genes` in gene order) plus ``sampleID``.
+    ``normalization``: normalize_total(1e4) + log1p on the device (``pilot_ot_normalize_log1p``)."""
+    if len(cell_list) < 1:
+        raise ValueError("cell_list is empty")
+    rows = _cell_type_rows(adata, col_cell, cell_list[0])
+    X = _cell_type_values(adata, rows, normalization)
+    genes = np.asarray(list(adata.var_names), dtype=object)
+    if highly_variable_genes_:
+        keep = np.flatnonzero(highly_variable_genes(X, n_top_genes)["highly_variable"].values)
+        X, genes = X[:, keep], genes[keep]
+    df = pd.DataFrame(X, columns=list(genes))
+    df["sampleID"] = list(np.asarray(adata.obs[sample_col])[rows])
+    return df
+
+
+def _sample_labels(proportions, label_name):
+    """sample id -> sub-group label of a proportions frame: ids from its 'sampIeD' column (sic, the reference's name), else
+    'sampleID', else the index"""
+    ids = proportions["sampIeD"] if "sampIeD" in proportions.columns else \
+        proportions["sampleID"] if "sampleID" in proportions.columns else proportions.index
+    return dict(zip(list(ids), list(proportions[label_name])))
+
+
+def _trigamma_inverse(x):
+    """limma's trigammaInverse for one positive value: Newton on 1 / trigamma from 0.5 + 1 / x, at most 50 steps"""
+    from scipy.special import polygamma
+    if x > 1e7:
+        return 1.0 / np.sqrt(x)
+    if x < 1e-6:
+        return 1.0 / x
+    y = 0.5 + 1.0 / x
+    for _ in range(50):
+        tri = float(polygamma(1, y))
+        dif = tri * (1.0 - tri / x) / float(polygamma(2, y))
+        y += dif
+        if -dif / y < 1e-8:
+            break
+    return y
+
+
+def _ebayes_prior(s2, df):
+    """limma's fitFDist for one residual df: (s0^2, df0) from the per-gene variances"""
+    from scipy.special import digamma, polygamma
+    med = np.median(s2)
+    if not med > 0:
+        raise ValueError("compute_diff_expressions: the median residual variance is %g; the prior cannot be estimated" % med)
+    e = np.log(np.maximum(s2, 1e-5 * med)) - digamma(df / 2.0) + np.log(df / 2.0)
+    emean = e.mean()
+    evar = e.var(ddof=1) - float(polygamma(1, df / 2.0)) if e.size > 1 else np.nan
+    if evar > 0:
+        df0 = 2.0 * _trigamma_inverse(evar)
+        return float(np.exp(emean + digamma(df0 / 2.0) - np.log(df0 / 2.0))), df0
+    return float(np.exp(emean)), np.inf
+
+
+def _two_group_fit(count, mean, m2, design, first):
+    """lmFit's results for two groups from their moments (count: 2; mean, m2: 2 x genes; group 0 is group1):
+    (logFC, AveExpr, RSS, residual df, unscaled stdev).  ``design='reference'``: ONE column x = 1 for group ``first`` and 2 for the
+    other, beta = (S_a + 2 S_b) / (n_a + 4 n_b), RSS = m2_a + m2_b + n_a (m_a - beta)^2 + n_b (m_b - 2 beta)^2, df = n - 1;
+    ``'two_group'``: intercept + indicator of group1, logFC = m_1 - m_2, RSS = m2_1 + m2_2, df = n - 2."""
+    n1, n2 = float(count[0]), float(count[1])
+    n = n1 + n2
+    ave = (n1 * mean[0] + n2 * mean[1]) / n
+    if design == "reference":
+        a, b = first, 1 - first
+        na, nb = float(count[a]), float(count[b])
+        xtx = na + 4.0 * nb
+        logfc = (na * mean[a] + 2.0 * nb * mean[b]) / xtx
+        rss = m2[a] + m2[b] + na * (mean[a] - logfc) ** 2 + nb * (mean[b] - 2.0 * logfc) ** 2
+        return logfc, ave, rss, n - 1.0, xtx ** -0.5
+    return mean[0] - mean[1], ave, m2[0] + m2[1], n - 2.0, np.sqrt(1.0 / n1 + 1.0 / n2)
+
+
+def compute_diff_expressions(adata, cell_type, proportions, selected_genes=None, group1="Tumor 1", group2="Tumor 2",
+                             label_name="Predicted_Labels", sample_col="sampleID", col_cell="cell_types", normalization=False,
+                             n_top_genes=2000, highly_variable_genes_=True, design="reference"):
+    """compute_diff_expressions (tools/patients_sub_clustering.py:77-240) without R, plots or files: limma's ``lmFit`` ->
+    ``eBayes`` -> ``topTable`` for the cells of ``cell_type`` in two patient sub-groups, from per-gene, per-group count, mean and
+    centred sum of squares taken in one device pass (``engine.group_moments``); the O(genes) tail runs on the host.  limma is not
+    installed where this library is built and tested, so its arithmetic is restated and UNPINNED here.
+
+    The cells of ``cell_type`` (``adata.X`` dense or CSR) are optionally normalised, uploaded once, reduced to the highly
+    variable genes over ALL the cell type's cells (:func:`highly_variable_genes`) as the reference does, and each cell takes the
+    ``label_name`` of its sample in ``proportions`` (sample ids from its ``sampIeD`` column -- sic -- else ``sampleID``, else the
+    index); cells of other labels are left out.  ``selected_genes`` restricts (and orders) the genes.
+
+    ``design='reference'`` is what the reference's call computes: ``design = unclass(as.factor(labels))`` is ONE column x in
+    {1, 2}, 1 for the name that sorts first (Python's string ordering here; R's locale collation can order mixed-case names
+    differently).  That is a regression through the origin, not a group contrast: logFC = beta = (S1 + 2 S2) / (n1 + 4 n2),
+    RSS = m2_1 + m2_2 + n1 (m1 - beta)^2 + n2 (m2 - 2 beta)^2, df = n - 1, unscaled stdev (n1 + 4 n2)^-1/2.
+    ``design='two_group'`` (not in PILOT) is an intercept plus an indicator: logFC = mean(group1) - mean(group2), positive =
+    higher in group1 as in :func:`cell_type_diff_two_sub_patient_groups`; RSS = m2_1 + m2_2, df = n - 2, unscaled stdev
+    sqrt(1 / n1 + 1 / n2).
+
+    eBayes: s^2 = RSS / df; e = log s^2 - digamma(df / 2) + log(df / 2) with zero variances floored at 1e-5 median(s^2) for the
+    prior only (median 0: ValueError); evar = var(e, ddof 1) - trigamma(df / 2); evar > 0: df0 = 2 trigammaInverse(evar) (limma's
+    Newton iteration), s0^2 = exp(mean(e) + digamma(df0 / 2) - log(df0 / 2)), else df0 = inf, s0^2 = exp(mean(e)); posterior
+    variance (df0 s0^2 + df s^2) / (df0 + df); t = logFC / (unscaled stdev * posterior sd); total df = min(df + df0, G df);
+    two-sided p; Benjamini-Hochberg.
+
+    Returns a frame indexed by gene, in gene order: ``logFC``, ``AveExpr`` (mean over the selected cells), ``t``, ``P.Value``,
+    ``adj.P.Val``; ``attrs['df_prior']``, ``attrs['s2_prior']``.  Deviations from the reference: no ``B`` column; every gene is
+    returned (the reference's ``topTable(n=2000)`` leaves genes beyond 2 000 as NaN); the reference's ``cells.iloc[:, 1:-1]``
+    silently drops the first gene, this does not.  Raised before any device work: ValueError for an unknown ``design`` or a group
+    without cells (named), KeyError for a sample of the cell type that ``proportions`` lacks."""
+    from scipy import stats
+    if design not in _DE_DESIGNS:
+        raise ValueError("design=%r must be one of %s" % (design, ", ".join(map(repr, _DE_DESIGNS))))
+    if group1 == group2:
+        raise ValueError("group1 and group2 are both %r" % (group1,))
+    genes = np.asarray(list(adata.var_names), dtype=object)
+    if selected_genes is not None:
+        pos = {g: i for i, g in enumerate(genes)}
+        unknown = [g for g in selected_genes if g not in pos]
+        if unknown:
+            raise KeyError("compute_diff_expressions: selected_genes not in adata.var_names: %s" % unknown)
+    label_of = _sample_labels(proportions, label_name)
+    rows = _cell_type_rows(adata, col_cell, cell_type)
+    samples = np.asarray(adata.obs[sample_col])[rows]
+    missing = [s for s in pd.unique(samples) if s not in label_of]
+    if missing:
+        raise KeyError("compute_diff_expressions: samples of %r missing from proportions: %s" % (cell_type, missing))
+    labels = np.asarray([label_of[s] for s in samples], dtype=object)
+    codes = np.where(labels == group1, 0, np.where(labels == group2, 1, -1)).astype(np.int32)
+    for g, name in enumerate((group1, group2)):
+        if not (codes == g).any():
+            raise ValueError("compute_diff_expressions: group %r has no cells of %r" % (name, cell_type))
+
+    X = _cell_type_values(adata, rows, normalization)
+    D = engine.DeviceMatrix.upload(X)
+    cols = np.arange(genes.size)
+    if highly_variable_genes_:
+        cols = np.flatnonzero(highly_variable_genes(D, n_top_genes)["highly_variable"].values)
+    if selected_genes is not None:
+        among = set(cols.tolist())
+        outside = [g for g in selected_genes if pos[g] not in among]
+        if outside:
+            raise KeyError("compute_diff_expressions: selected_genes outside the highly variable genes: %s" % outside)
+        cols = np.asarray([pos[g] for g in selected_genes], dtype=np.int64)
+    every = cols.size == genes.size and np.array_equal(cols, np.arange(genes.size))      # (every column in order: the 16-byte reads)
+    count, mean, m2 = engine.group_moments(D, codes, 2, cols=None if every else cols.astype(np.int32))
+    del D
+
+    G = cols.size
+    logfc, ave, rss, df, unscaled = _two_group_fit(count, mean, m2, design, 0 if str(group1) < str(group2) else 1)
+    if df < 1:
+        raise ValueError("compute_diff_expressions: %d cells leave no residual degrees of freedom" % int(count.sum()))
+    s2 = rss / df
+    s2_prior, df_prior = _ebayes_prior(s2, df)
+    s2_post = np.full(G, s2_prior) if np.isinf(df_prior) else (df_prior * s2_prior + df * s2) / (df_prior + df)
+    t = logfc / (unscaled * np.sqrt(s2_post))
+    df_total = min(df + df_prior, G * df)
+    p = 2.0 * (stats.norm.sf(np.abs(t)) if np.isinf(df_total) else stats.t.sf(np.abs(t), df_total))
+    res = pd.DataFrame({"logFC": logfc, "AveExpr": ave, "t": t, "P.Value": p, "adj.P.Val": _bh_adjust(p)},
+                       index=pd.Index(genes[cols], name="gene"))
+    res.attrs["df_prior"], res.attrs["s2_prior"] = float(df_prior), float(s2_prior)
+    return res
+
+
+def cell_type_diff_two_sub_patient_groups(proportions, cell_types, labels="Predicted_Labels", group1="Tumor 1", group2="Tumor 2"):
+    """cell_type_diff_two_sub_patient_groups (plot/ploting.py:460-556) without the plot, the CSV file or the p-value filter:
+    Welch's t-test per cell type on the proportions of the samples labelled ``group1`` against ``group2`` (``labels``: the
+    column of sub-group labels; the reference reads 'Predicted_Labels' whatever its own argument says).  Group means and centred
+    sums of squares of the samples x cell-types columns come from ``engine.group_moments``; the statistic, the Satterthwaite
+    degrees of freedom and the two-sided p-value are formed on the host, the p-values Benjamini-Hochberg adjusted.  Returns the
+    reference's unfiltered table ``cell_type``, ``adjPval``, ``-logPval``, ``score`` (positive: higher in ``group1``), sorted by
+    ``score`` then ``-logPval``, both descending."""
+    from scipy import stats
+    cell_types = list(cell_types)
+    lab = np.asarray(proportions[labels], dtype=object)
+    codes = np.where(lab == group1, 0, np.where(lab == group2, 1, -1)).astype(np.int32)
+    for g, name in enumerate((group1, group2)):
+        if not (codes == g).any():
+            raise ValueError("cell_type_diff_two_sub_patient_groups: group %r has no samples" % (name,))
+    P = np.ascontiguousarray(proportions[cell_types].to_numpy(dtype=np.float64))
+    count, mean, m2 = engine.group_moments(P, codes, 2)
+    n1, n2 = float(count[0]), float(count[1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v1, v2 = m2[0] / (n1 - 1.0) / n1, m2[1] / (n2 - 1.0) / n2
+        score = (mean[0] - mean[1]) / np.sqrt(v1 + v2)
+        dof = (v1 + v2) ** 2 / (v1 ** 2 / (n1 - 1.0) + v2 ** 2 / (n2 - 1.0))
+        adj = _bh_adjust(2.0 * stats.t.sf(np.abs(score), dof))
+        out = pd.DataFrame({"cell_type": cell_types, "adjPval": adj, "-logPval": -np.log(adj), "score": score})
+    return out.sort_values(by=["score", "-logPval"], ascending=[False, False])

@@ -480,6 +480,37 @@ int pilot_ot_curve_activities(const double *curves, int curves_is_device, int G,
 int pilot_ot_group_moments(const void *Y, int Y_is_device, int dtype, long long n, int n_cols_total, long long ld, const int *codes,
                            int n_groups, const int *cols, int n_cols, int transform, long long *count, double *mean, double *m2);
 
+/* ---- sparse matrices (K13): a cells x genes matrix resident in HBM as CSR, for the gene-level consumers above.  scRNA-seq counts
+ * are a few percent non-zero; the handle keeps indptr (int64, n_rows + 1), indices (int32) and data (float32: dtype 0, float64: 1)
+ * on the current device and never forms the dense matrix unless pilot_ot_csr_densify is asked for some columns.
+ * pilot_ot_csr_upload copies the three host arrays.  Indices within a row may come in any order; a row must not store a column
+ * twice.  PILOT_OT_EINVAL (before any HIP call): a NULL pointer, dtype not 0 / 1, n_rows < 0 or > INT_MAX, n_cols < 1,
+ * indptr[0] != 0, indptr not non-decreasing, an index outside [0, n_cols), a duplicate entry.
+ * Every sum below is taken in f64 in a fixed order and nothing uses a floating-point atomic: the same bits from every run. */
+typedef struct pilot_ot_csr pilot_ot_csr;
+int pilot_ot_csr_upload(const long long *indptr, const int *indices, const void *data, int dtype, long long n_rows, int n_cols,
+                        pilot_ot_csr **csr);
+int pilot_ot_csr_destroy(pilot_ot_csr *csr);
+/* In place: every stored value v of a row becomes log1p(v * target_sum / total) with total the row's sum over its stored values
+ * (pilot_ot_normalize_log1p's expressions; a row without counts stays 0; zeros stay implicit).  Drops the column form.
+ * PILOT_OT_EINVAL: target_sum not positive and finite, a NULL handle. */
+int pilot_ot_csr_normalize_log1p(pilot_ot_csr *csr, double target_sum);
+/* The column-major copy (per column its entries in ascending row order) the per-column calls read.  It is built on the device
+ * by the first call that needs it and kept until the values change; this call only builds it ahead of time.  The build cuts the
+ * rows into slices of pilot_ot_csr_slice_rows() rows. */
+int pilot_ot_csr_build_columns(pilot_ot_csr *csr);
+int pilot_ot_csr_slice_rows(void);
+/* nnz (host, n_cols): per column the stored values that are != 0 (an explicitly stored 0 is a zero). */
+int pilot_ot_csr_column_nnz(pilot_ot_csr *csr, long long *nnz);
+/* pilot_ot_group_moments of the matrix (same codes, n_groups, cols, transform, outputs and error cases), from the column form:
+ * mean = sum over the stored entries / count, m2 = sum over the stored entries of (t(y) - mean)^2 + (count - stored) mean^2, every
+ * term non-negative.  cols NULL: every column (n_cols = the matrix's). */
+int pilot_ot_csr_group_moments(pilot_ot_csr *csr, const int *codes, int n_groups, const int *cols, int n_cols, int transform,
+                               long long *count, double *mean, double *m2);
+/* out (DEVICE, n_rows x n_cols elements of the matrix's dtype, row-major): the dense copy of the columns cols (host; NULL: every
+ * column), zero-filled and every stored entry written once.  PILOT_OT_EINVAL: a column out of range or named twice. */
+int pilot_ot_csr_densify(pilot_ot_csr *csr, const int *cols, int n_cols, void *out);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

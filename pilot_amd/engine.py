@@ -954,6 +954,144 @@ def device_columns(D, start, stop):
     return _DeviceColumns(D, int(start), int(stop))
 
 
+def _moment_args(n, n_total, codes, n_groups, transform, cols):
+    """group_moments' arguments checked on the host: (codes int32, n_groups, cols int32 or None)"""
+    if transform not in _GM_TRANSFORMS:
+        raise ValueError("transform=%r must be None or 'expm1'" % (transform,))
+    if isinstance(n_groups, bool) or int(n_groups) != n_groups or not 1 <= n_groups <= GROUP_MOMENTS_MAX_GROUPS:
+        raise ValueError("n_groups=%r must be an integer in 1..%d" % (n_groups, GROUP_MOMENTS_MAX_GROUPS))
+    n_groups = int(n_groups)
+    if n_total < 1:
+        raise ValueError("Y has no columns")
+    codes = np.asarray(codes)
+    if codes.ndim != 1 or codes.size != n:
+        raise ValueError("codes has shape %s for %d rows" % (codes.shape, n))
+    if codes.dtype.kind not in "iu":
+        raise ValueError("codes must be integers, got %s" % codes.dtype)
+    if n and int(codes.max()) >= n_groups:
+        raise ValueError("codes reach %d with n_groups=%d" % (int(codes.max()), n_groups))
+    codes = np.ascontiguousarray(np.maximum(codes, -1), dtype=np.int32)
+    if cols is not None:
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or cols.dtype.kind not in "iu":
+            raise ValueError("cols: a 1-D array of column indices, got %s %s" % (cols.shape, cols.dtype))
+        if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= n_total):
+            raise ValueError("cols outside [0, %d)" % n_total)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+    return codes, n_groups, cols
+
+
+class DeviceCSR:
+    """K13: a sparse rows x columns matrix resident in HBM as CSR (include/pilot_ot.h, "sparse matrices"): what ``adata.X`` is in
+    real scRNA-seq data.  Made by :meth:`upload`; the dense matrix is never formed unless :meth:`densify` is asked for some
+    columns.  ``shape``, ``dtype`` (float32 / float64) and ``nnz`` (stored entries) describe it.  The column-major copy the
+    per-column calls read is built on the device by the first of them and dropped by :meth:`normalize_log1p`."""
+
+    def __init__(self, handle, shape, dtype, nnz):
+        self.h, self.shape, self.dtype, self.nnz = handle, tuple(int(v) for v in shape), np.dtype(dtype), int(nnz)
+
+    @classmethod
+    def upload(cls, X, rows=None):
+        """``X``: a scipy CSR matrix or array (anything else: ValueError); ``rows``: an optional row selection, taken on the host
+        (``X[rows]``).  Integer and bool data become float32.  Duplicate entries are summed in a copy, the caller's matrix is never
+        modified; indices within a row may come unsorted."""
+        import scipy.sparse as sp
+        if not sp.issparse(X) or X.format != "csr":
+            raise ValueError("DeviceCSR.upload: a scipy CSR matrix or array, got %s" % type(X).__name__)
+        if rows is not None:
+            X = X[np.asarray(rows)]
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise ValueError("DeviceCSR.upload: a 2-D matrix with at least one column, got shape %s" % (X.shape,))
+        if X.shape[0] >= 2 ** 31 or X.shape[1] >= 2 ** 31:
+            raise ValueError("DeviceCSR.upload: shape %s needs more than 32-bit row / column indices" % (X.shape,))
+        if not X.has_canonical_format:           # unsorted rows go up as they are; duplicates are summed, in a copy
+            summed = X.copy()
+            summed.sum_duplicates()
+            if summed.nnz != X.nnz:
+                X = summed
+        data = X.data
+        if data.dtype not in (np.float32, np.float64):
+            if data.dtype.kind not in "biuf":
+                raise ValueError("DeviceCSR.upload: numeric data, got %s" % data.dtype)
+            data = data.astype(np.float32)
+        data = np.ascontiguousarray(data)
+        indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(X.indices, dtype=np.int32)
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().pilot_ot_csr_upload(
+            indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.iptr(indices), ctypes.c_void_p(data.ctypes.data),
+            0 if data.dtype == np.float32 else 1, X.shape[0], X.shape[1], ctypes.byref(h)))
+        return cls(h, X.shape, data.dtype, indices.size)
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the DeviceCSR was closed")
+        return self.h
+
+    def normalize_log1p(self, target_sum=1e4):
+        """In place: scanpy's ``normalize_total(target_sum)`` then ``log1p`` on the stored values (zeros stay implicit), with the
+        expressions of the dense ``pilot_ot_normalize_log1p``: counts give the same bits by either route."""
+        if not (float(target_sum) > 0.0 and np.isfinite(target_sum)):
+            raise ValueError("target_sum=%r must be positive" % (target_sum,))
+        _lib.check(_lib.load().pilot_ot_csr_normalize_log1p(self._handle(), float(target_sum)))
+        return self
+
+    def build_columns(self):
+        """Build the column-major copy now (the per-column calls build it on first use)."""
+        _lib.check(_lib.load().pilot_ot_csr_build_columns(self._handle()))
+
+    def column_nnz(self):
+        """int64 per column: the stored values that are != 0 (``(dense != 0).sum(0)``)."""
+        out = np.empty(self.shape[1], dtype=np.int64)
+        _lib.check(_lib.load().pilot_ot_csr_column_nnz(self._handle(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return out
+
+    def group_moments(self, codes, n_groups, transform=None, cols=None):
+        """:func:`group_moments` of the matrix, read from the column form: ``(count, mean, m2)``."""
+        codes, n_groups, cols = _moment_args(self.shape[0], self.shape[1], codes, n_groups, transform, cols)
+        n_sel = self.shape[1] if cols is None else cols.size
+        count = np.empty(n_groups, dtype=np.int64)
+        mean, m2 = np.empty((n_groups, n_sel)), np.empty((n_groups, n_sel))
+        _lib.check(_lib.load().pilot_ot_csr_group_moments(
+            self._handle(), _lib.iptr(codes), n_groups, None if cols is None else _lib.iptr(cols), n_sel, _GM_TRANSFORMS[transform],
+            count.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.dptr(mean), _lib.dptr(m2)))
+        return count, mean, m2
+
+    def densify(self, cols=None):
+        """A rows x len(cols) :class:`DeviceMatrix` of the matrix's dtype holding the columns ``cols`` (distinct, any order;
+        default: all), dense in HBM."""
+        if cols is not None:
+            cols = np.asarray(cols)
+            if cols.ndim != 1 or (cols.size and cols.dtype.kind not in "iu"):
+                raise ValueError("cols: a 1-D array of column indices, got %s %s" % (cols.shape, cols.dtype))
+            if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= self.shape[1]):
+                raise ValueError("cols outside [0, %d)" % self.shape[1])
+            if np.unique(cols).size != cols.size:
+                raise ValueError("cols names a column twice")
+            cols = np.ascontiguousarray(cols, dtype=np.int32)
+        n, n_sel = self.shape[0], self.shape[1] if cols is None else cols.size
+        h = self._handle()
+        buf = _DeviceBuffer(n * n_sel * self.dtype.itemsize)
+        _lib.check(_lib.load().pilot_ot_csr_densify(h, None if cols is None else _lib.iptr(cols), n_sel, buf.ptr))
+        return DeviceMatrix(buf.ptr, n, owner=buf, shape=(n, n_sel), dtype=self.dtype)
+
+    def close(self):
+        if self.h:
+            _lib.load().pilot_ot_csr_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csr_slice_rows():
+    """Rows per slice of :class:`DeviceCSR`'s column-form build."""
+    return int(_lib.load().pilot_ot_csr_slice_rows())
+
+
 def group_moments(Y, codes, n_groups, transform=None, cols=None):
     """K12: per group and selected column, the count, the float64 mean and the centred sum of squares ``sum (t(y) - mean)^2`` of
     the rows of ``Y`` with ``codes == g`` (include/pilot_ot.h, "group moments").  ``Y``: rows x columns, a C-contiguous float32 /
@@ -962,7 +1100,9 @@ def group_moments(Y, codes, n_groups, transform=None, cols=None):
     ``"expm1"`` (taken in float64).  ``cols``: the selected columns in any order (default: all).  Returns ``(count, mean, m2)``:
     ``n_groups`` int64 and two ``n_groups x columns`` float64 arrays; an empty group gives 0 and NaN, a group of one row m2 = 0.
     One pass over Y; sums in a fixed order, so a repeated call and the host and device routes return the same bits.  Every
-    argument is checked before any device work (ValueError)."""
+    argument is checked before any device work (ValueError).  A :class:`DeviceCSR` is forwarded to its own method."""
+    if isinstance(Y, DeviceCSR):
+        return Y.group_moments(codes, n_groups, transform=transform, cols=cols)
     if transform not in _GM_TRANSFORMS:
         raise ValueError("transform=%r must be None or 'expm1'" % (transform,))
     if isinstance(n_groups, bool) or int(n_groups) != n_groups or not 1 <= n_groups <= GROUP_MOMENTS_MAX_GROUPS:

@@ -719,30 +719,57 @@ def genes_importance(adata, name_cell, col="Time_score", p_value=0.05, model_typ
     ``adata.uns['orders']`` (what cell_importance wrote), optionally normalize_total(1e4) + log1p on the device (a restatement of
     scanpy's, unpinned), genes with a zero fraction > 0.95 dropped, then fits of the three trajectory models per gene
     against the cells' ``col``, the report table with numeric columns and each gene's ``proportion`` (zero fraction) and
-    ``mean``.  ``adata.X`` may be dense or scipy CSR.  ``model_type``: 'HuberRegressor' (the OPTIMUM of its objective with
+    ``mean``.  A dense ``adata.X`` is normalised through the host-in, host-out ``pilot_ot_normalize_log1p``; a scipy sparse one
+    goes up once as an ``engine.DeviceCSR`` (the chosen rows, taken with scipy), is counted and normalised there, and only the kept
+    genes are made dense, in HBM, for the fits -- no dense copy exists on the host.  ``model_type``: 'HuberRegressor' (the OPTIMUM of its objective with
     ``epsilon_huber``; scikit-learn's own fit stops early on some fits with an x^2 feature) or 'LinearRegression'.  A
     (gene, model) whose Huber solve did not converge is ineligible, as the engine flags it."""
     if model_type not in ("HuberRegressor", "LinearRegression"):
         raise ValueError("model_type=%r must be 'HuberRegressor' or 'LinearRegression'" % (model_type,))
     rows, x = _cell_rows(adata, name_cell, sample_col, col_cell, adata.uns["orders"], col)
-    X = adata.X[rows]
-    X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float32)
-    X = np.ascontiguousarray(X)
     genes = np.asarray(list(adata.var_names), dtype=object)
-    zero = (X == 0).mean(axis=0) if X.shape[0] else np.zeros(X.shape[1])
-    cols = np.flatnonzero(~(zero > 0.95)).astype(np.int32)
-    if normalize:
-        Y = np.empty((X.shape[0], cols.size), dtype=X.dtype)
-        _lib_check_normalize(X, cols, Y)
+    if _is_sparse(adata.X):
+        S = _sparse_rows(adata.X, rows)
+        n = S.shape[0]
+        zero = (n - S.column_nnz()) / n if n else np.zeros(S.shape[1])
+        cols = np.flatnonzero(~(zero > 0.95)).astype(np.int32)
+        if normalize:
+            S.normalize_log1p(1e4)
+        Y = S.densify(cols)
+        del S
     else:
-        Y = X[:, cols]
+        X = _dense_rows(adata.X, rows)
+        zero = (X == 0).mean(axis=0) if X.shape[0] else np.zeros(X.shape[1])
+        cols = np.flatnonzero(~(zero > 0.95)).astype(np.int32)
+        if normalize:
+            Y = np.empty((X.shape[0], cols.size), dtype=X.dtype)
+            _lib_check_normalize(X, cols, Y)
+        else:
+            Y = X[:, cols]
     fits = engine.trajectory_fits(Y, x, model="huber" if model_type == "HuberRegressor" else "ols", epsilon=epsilon_huber,
                                   pval_thr=p_value, modify_r2=modify_r2)
     table, _ = _fits_table(fits, genes[cols], "Gene ID", p_value, modify_r2)
     pro = pd.DataFrame({"Gene ID": genes[cols], "proportion": fits["zero_fraction"], "mean": fits["mean"]})
     return pd.merge(table, pro, on="Gene ID")
+
+
+def _is_sparse(X):
+    import scipy.sparse as sp
+    return sp.issparse(X)
+
+
+def _sparse_rows(X, rows):
+    """The rows ``rows`` of the scipy sparse matrix X as an ``engine.DeviceCSR`` (any other sparse format is converted to CSR on
+    the host first; nothing dense is formed)"""
+    return engine.DeviceCSR.upload(X if X.format == "csr" else X.tocsr(), rows)
+
+
+def _dense_rows(X, rows):
+    """The rows ``rows`` of the dense matrix X as a C-contiguous float32 / float64 array"""
+    X = np.asarray(X[rows])
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float32)
+    return np.ascontiguousarray(X)
 
 
 def _lib_check_normalize(X, cols, out):
@@ -951,16 +978,19 @@ def infer_gene_cluster_differentiation(adata, tables, gene_list=None, cluster_na
         for c, d in cells.items():
             js = [j for j, k in enumerate(multi) if rows[k][1] == c]
             gcol = np.asarray([list(adata.var_names).index(g) for g in d["genes"]], dtype=np.int32)
-            X = adata.X[d["rows"]]
-            X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float32)
-            X = np.ascontiguousarray(X)
-            if normalize:
-                Y = np.empty((X.shape[0], gcol.size), dtype=X.dtype)
-                _lib_check_normalize(X, gcol, Y)
+            if _is_sparse(adata.X):                    # sparse: up once, normalised in HBM, the cell type's genes made dense there
+                S = _sparse_rows(adata.X, d["rows"])
+                if normalize:
+                    S.normalize_log1p(1e4)
+                Y = S.densify(gcol)
+                del S
             else:
-                Y = np.ascontiguousarray(X[:, gcol])
+                X = _dense_rows(adata.X, d["rows"])
+                if normalize:
+                    Y = np.empty((X.shape[0], gcol.size), dtype=X.dtype)
+                    _lib_check_normalize(X, gcol, Y)
+                else:
+                    Y = np.ascontiguousarray(X[:, gcol])
             pos = {g: i for i, g in enumerate(d["genes"])}
             idx = np.stack([draws[2 * j] for j in js])
             prm, inf = engine.bootstrap_huber_fits(
@@ -1091,17 +1121,22 @@ def _noised_curves(adata, cell_type, table, filter_table_feature, filter_table_f
     params = sel[["Intercept", "Treat", "Treat2"]].to_numpy(dtype=np.float64).reshape(-1, 3)
     model = np.array([engine.TRAJFIT_MODELS.index(f) for f in sel["Fitted function"]], dtype=np.int32)
 
-    X = adata.X[rows]
-    X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float32)
-    X = np.ascontiguousarray(X)
-    if normalize:
-        Y = np.empty((X.shape[0], cols.size), dtype=X.dtype)
-        _lib_check_normalize(X, cols, Y)
-        sd = engine.segment_std(Y, offsets, device=True) if cols.size else None
+    if not cols.size:
+        sd = None
+    elif _is_sparse(adata.X):                          # sparse: up once, normalised in HBM, the table's genes made dense there
+        S = _sparse_rows(adata.X, rows)
+        if normalize:
+            S.normalize_log1p(1e4)
+        sd = engine.segment_std(S.densify(cols), offsets, device=True)
+        del S
     else:
-        sd = engine.segment_std(X, offsets, cols=cols, device=True) if cols.size else None
+        X = _dense_rows(adata.X, rows)
+        if normalize:
+            Y = np.empty((X.shape[0], cols.size), dtype=X.dtype)
+            _lib_check_normalize(X, cols, Y)
+            sd = engine.segment_std(Y, offsets, device=True)
+        else:
+            sd = engine.segment_std(X, offsets, cols=cols, device=True)
     plain = engine.fitted_curves(params, model, times, device=True)
     noised = engine.fitted_curves(params, model, times, noise=sd, device=True)
     return (_Curves(plain, genes, labels), _Curves(noised, genes, list(names[sample_col]), sample_col), names)
@@ -1201,7 +1236,7 @@ _DE_DESIGNS = ("reference", "two_group")
 def highly_variable_genes(X, n_top_genes=2000):
     """scanpy's ``pp.highly_variable_genes(flavor='seurat')`` for one batch, restated (scanpy is not installed where this
     library is built and tested, so the rule is UNPINNED here, like ``normalize_total``).  ``X``: the cells x genes log1p values, a
-    C-contiguous float32 / float64 array or an ``engine.DeviceMatrix``.  Mean and ddof-1 variance of ``expm1(X)`` per gene come
+    C-contiguous float32 / float64 array, an ``engine.DeviceMatrix`` or an ``engine.DeviceCSR``.  Mean and ddof-1 variance of ``expm1(X)`` per gene come
     from one device pass (``engine.group_moments``); the tail is scanpy's, on the host with pandas: a mean of 0 becomes 1e-12,
     dispersion = var / mean with 0 -> NaN, then its log; log1p of the mean; ``pd.cut`` of the means into 20 bins; per bin the mean
     and ddof-1 std of the dispersions, a one-gene bin getting std = its mean and mean = 0; the normalised dispersion; the cut-off
@@ -1241,14 +1276,20 @@ def _cell_type_rows(adata, col_cell, cell):
     return np.flatnonzero(np.asarray(adata.obs[col_cell].isin([cell])))
 
 
+def _cell_type_matrix(adata, rows, normalization):
+    """The rows ``rows`` of adata.X on the device, optionally normalize_total(1e4) + log1p: a sparse adata.X as an
+    ``engine.DeviceCSR`` (normalised in place there), a dense one as an ``engine.DeviceMatrix`` of :func:`_cell_type_values`"""
+    if _is_sparse(adata.X):
+        S = _sparse_rows(adata.X, rows)
+        if normalization and S.nnz:
+            S.normalize_log1p(1e4)
+        return S
+    return engine.DeviceMatrix.upload(_cell_type_values(adata, rows, normalization))
+
+
 def _cell_type_values(adata, rows, normalization):
-    """The rows ``rows`` of adata.X (dense or CSR) as a dense float32 / float64 array, optionally normalize_total(1e4) + log1p on
-    the device"""
-    X = adata.X[rows]
-    X = np.asarray(X.toarray() if hasattr(X, "toarray") else X)
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float32)
-    X = np.ascontiguousarray(X)
+    """The rows ``rows`` of the dense adata.X as a float32 / float64 array, optionally normalize_total(1e4) + log1p on the device"""
+    X = _dense_rows(adata.X, rows)
     if normalization and X.size:
         out = np.empty_like(X)
         _lib_check_normalize(X, np.arange(X.shape[1], dtype=np.int32), out)
@@ -1261,15 +1302,26 @@ def extract_cells_from_gene_expression_for_clustering(adata, sample_col, col_cel
     """extract_cells_from_gene_expression_for_clustering (tools/patients_sub_clustering.py:15-76) without the CSV file: the
     expression frame of the FIRST cell type of ``cell_list`` (the reference returns inside its loop) -- one row per cell, one
     column per gene (every gene, or the highly variable ones of :func:`highly_variable_genes` in gene order) plus ``sampleID``.
-    ``normalization``: normalize_total(1e4) + log1p on the device (``pilot_ot_normalize_log1p``)."""
+    ``normalization``: normalize_total(1e4) + log1p on the device (``pilot_ot_normalize_log1p``).  A scipy sparse ``adata.X`` goes
+    up as an ``engine.DeviceCSR``: normalisation and the HVG moments run on the sparse form in HBM, and only the columns of the
+    frame are made dense and downloaded."""
     if len(cell_list) < 1:
         raise ValueError("cell_list is empty")
     rows = _cell_type_rows(adata, col_cell, cell_list[0])
-    X = _cell_type_values(adata, rows, normalization)
     genes = np.asarray(list(adata.var_names), dtype=object)
-    if highly_variable_genes_:
-        keep = np.flatnonzero(highly_variable_genes(X, n_top_genes)["highly_variable"].values)
-        X, genes = X[:, keep], genes[keep]
+    if _is_sparse(adata.X):
+        S = _cell_type_matrix(adata, rows, normalization)
+        keep = None
+        if highly_variable_genes_:
+            keep = np.flatnonzero(highly_variable_genes(S, n_top_genes)["highly_variable"].values)
+            genes = genes[keep]
+        X = engine.download(S.densify(keep))           # the one dense copy: the frame this returns
+        del S
+    else:
+        X = _cell_type_values(adata, rows, normalization)
+        if highly_variable_genes_:
+            keep = np.flatnonzero(highly_variable_genes(X, n_top_genes)["highly_variable"].values)
+            X, genes = X[:, keep], genes[keep]
     df = pd.DataFrame(X, columns=list(genes))
     df["sampleID"] = list(np.asarray(adata.obs[sample_col])[rows])
     return df
@@ -1341,8 +1393,9 @@ def compute_diff_expressions(adata, cell_type, proportions, selected_genes=None,
     centred sum of squares taken in one device pass (``engine.group_moments``); the O(genes) tail runs on the host.  limma is not
     installed where this library is built and tested, so its arithmetic is restated and UNPINNED here.
 
-    The cells of ``cell_type`` (``adata.X`` dense or CSR) are optionally normalised, uploaded once, reduced to the highly
-    variable genes over ALL the cell type's cells (:func:`highly_variable_genes`) as the reference does, and each cell takes the
+    The cells of ``cell_type`` are optionally normalised, uploaded once (a dense ``adata.X`` as an ``engine.DeviceMatrix``; a
+    scipy sparse one as an ``engine.DeviceCSR``, normalised in HBM, whose column form serves both moment calls: nothing dense is
+    ever formed), reduced to the highly variable genes over ALL the cell type's cells (:func:`highly_variable_genes`) as the reference does, and each cell takes the
     ``label_name`` of its sample in ``proportions`` (sample ids from its ``sampIeD`` column -- sic -- else ``sampleID``, else the
     index); cells of other labels are left out.  ``selected_genes`` restricts (and orders) the genes.
 
@@ -1388,8 +1441,7 @@ def compute_diff_expressions(adata, cell_type, proportions, selected_genes=None,
         if not (codes == g).any():
             raise ValueError("compute_diff_expressions: group %r has no cells of %r" % (name, cell_type))
 
-    X = _cell_type_values(adata, rows, normalization)
-    D = engine.DeviceMatrix.upload(X)
+    D = _cell_type_matrix(adata, rows, normalization)
     cols = np.arange(genes.size)
     if highly_variable_genes_:
         cols = np.flatnonzero(highly_variable_genes(D, n_top_genes)["highly_variable"].values)

@@ -466,8 +466,8 @@ int pilot_ot_curve_activities(const double *curves, int curves_is_device, int G,
  * a two-group design all of limma's arithmetic, scanpy's dispersion statistics and Welch's t follow from per-group count, mean and
  * centred sum of squares, which one pass over Y gives.
  * Y: n x n_cols_total, row-major with leading dimension ld (elements), float32 (dtype 0) or float64 (1), on the host (copied whole)
- * or (Y_is_device) in HBM.  codes (host, n): the group of every row, 0 .. n_groups - 1, or negative for a row that is skipped;
- * n_groups in [1, 8].  cols (host, nullable): the n_cols selected columns, any order, repeats allowed; NULL: every column
+ * or (Y_is_device) in HBM.  codes (host, n): the group of every row, 0 .. n_groups - 1, or negative for a row that is skipped
+ * (its values, finite or not and on whatever scale, enter no result); n_groups in [1, 8].  cols (host, nullable): the n_cols selected columns, any order, repeats allowed; NULL: every column
  * (n_cols = n_cols_total).  transform: 0 t(y) = y, 1 t(y) = expm1(y) in f64.
  * Out (host): count[g] = rows with codes == g; mean[g][j] = their mean of t(y) and m2[g][j] = sum (t(y) - mean)^2 over column
  * cols[j], both n_groups x n_cols in f64.  A group without rows: count 0, NaN, NaN; a group of one row: m2 = 0 exactly.

@@ -10,8 +10,9 @@
 // by Chan's update
 //     delta = mean_c - mean;  mean += delta * n_c / (n + n_c);  m2 += m2_c + delta^2 * n * n_c / (n + n_c).
 // The counts are wave-uniform, so the two weights cost one division each per chunk and group, not per column.  Every value is
-// taken relative to a per-slice, per-column shift (the transformed first row of the slice when finite), which keeps the running
-// means small beside the spread when mean / std is large; the shift goes back into the slice's mean at the end.  No raw
+// taken relative to a per-slice, per-column shift (the transformed value of the slice's first USED row, code >= 0, when finite,
+// else 0; a skipped row never sets it), which keeps the running means small beside the spread when mean / std is large and the
+// groups of the call lie within a few spreads of each other; the shift goes back into the slice's mean at the end.  No raw
 // sum(y^2) - n mean^2 is formed anywhere.  A second kernel joins the slice partials by the same update IN SLICE ORDER, one
 // thread per (group, column): no atomics, the same bits on every run and whatever the route Y came by.
 #pragma once
@@ -65,9 +66,21 @@ __global__ void __launch_bounds__(64) group_moments_kernel(const T *__restrict__
 
     double shift[GM_V] = {}, mean[NG][GM_V] = {}, m2[NG][GM_V] = {};
     long long cnt[NG] = {};
-    if (i0 < i1) {
+    // The shift comes from the slice's first USED row: a skipped row's values may lie on another scale altogether, and as the
+    // origin of every d they would cost the digits the shift is there to keep.  The codes are wave-uniform, so this is a scalar
+    // walk, GM_R codes per step, that never touches Y; a slice without a used row keeps shift 0 and every count 0.
+    long long ik = i1;
+    for (long long ib = i0; ib < i1 && ik == i1; ib += GM_R) {
+        int c[GM_R];
+#pragma unroll
+        for (int r = 0; r < GM_R; ++r) c[r] = ib + r < i1 ? __builtin_amdgcn_readfirstlane(codes[ib + r]) : -1;
+#pragma unroll
+        for (int r = GM_R - 1; r >= 0; --r)
+            if (c[r] >= 0) ik = ib + r;
+    }
+    if (ik < i1) {
         T first[GM_V];
-        load_row(i0, first);
+        load_row(ik, first);
 #pragma unroll
         for (int v = 0; v < GM_V; ++v) {
             const double k = value(first[v]);

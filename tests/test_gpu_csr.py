@@ -198,6 +198,53 @@ def test_expm1_transform(dtype):
     _check(one, LR.group_moments(Y, np.zeros(n, dtype=int), 1, transform="expm1"), np.expm1(Y.astype(np.float64)).max(), "expm1, one group", n)
 
 
+# K12's slice rule, restated as in tests/test_gpu_group_moments.py (not imported from the code under test): for n <= 1031 and at
+# most two column tiles, S = max(1, n // 128) slices, slice s starting at n // S * s + n % S * s // S
+def _slice_starts(n):
+    assert n <= 1031
+    S = max(1, n // 128)
+    return np.array([n // S * s + n % S * s // S for s in range(S)])
+
+
+# (id, storage, transform, the value stored in every skipped row, its least ratio to the used rows' largest |t(y)|)
+POISONS = [("f64-1e12", np.float64, None, 1e12, 1e10), ("f32-1e6", np.float32, None, 1e6, 1e4),
+           ("f32-max", np.float32, None, float(np.finfo(np.float32).max), 1e36),
+           ("f64-expm1-700", np.float64, "expm1", 700.0, 1e12), ("f32-expm1-88", np.float32, "expm1", 88.0, 1e12)]
+POISON_IDS = [p[0] for p in POISONS]
+
+
+@pytest.mark.parametrize("n_groups", [2, 5])
+@pytest.mark.parametrize("n,G", [(257, 255), (1024, 256), (1031, 257)])
+@pytest.mark.parametrize("poison", POISONS, ids=POISON_IDS)
+def test_skipped_rows_on_another_scale(poison, n, G, n_groups):
+    """the matrix of tests/test_gpu_group_moments.py::test_skipped_rows_on_another_scale as CSR: the used rows at about 10 % fill,
+    every skipped row (the first row of each of K12's slices among them) stored in full with a finite value far above the used
+    ones.  K13 is two-pass about the true mean and reads a skipped row's value only to discard it, so the bounds above hold
+    unchanged; the dense kernel on the same matrix is held to the same reference, so the two routes agree within twice the bound."""
+    _, dtype, transform, value, factor = poison
+    rng = np.random.default_rng([n, G, n_groups, POISON_IDS.index(poison[0])])
+    codes = rng.integers(-1, n_groups, n)
+    codes[_slice_starts(n)] = -1
+    skipped = codes < 0
+    vals = np.log1p(rng.poisson(3.0, (n, G)) + 1.0) if transform == "expm1" else rng.standard_normal((n, G)) * 2.0 + 1.0
+    Y = np.where(rng.random((n, G)) < 0.1, vals, 0.0).astype(dtype)
+    Y[skipped] = value
+    X = sp.csr_matrix(Y)
+    assert X.dtype == dtype and X.nnz == (Y != 0).sum() and skipped[_slice_starts(n)].all() and (~skipped).any()
+    assert 0.05 < (Y[~skipped] != 0).mean() < 0.15 and (np.diff(X.indptr)[skipped] == G).all()     # the poison is stored
+    t = np.expm1(Y.astype(np.float64)) if transform == "expm1" else Y.astype(np.float64)
+    scale = np.abs(t[~skipped]).max()
+    assert np.isfinite(t).all() and scale > 0 and np.abs(t[skipped]).min() >= factor * scale
+    want = LR.group_moments(Y, codes, n_groups, transform=transform)
+    what = "%s %d x %d, %d groups" % (poison[0], n, G, n_groups)
+    C = engine.DeviceCSR.upload(X)
+    got = C.group_moments(codes, n_groups, transform=transform)
+    _check(got, want, scale, what + ", CSR", n)
+    assert _same(C.group_moments(codes, n_groups, transform=transform), got)
+    _check(engine.group_moments(Y, codes, n_groups, transform=transform), want, scale, what + ", dense", n)
+    _check(engine.group_moments(C.densify(), codes, n_groups, transform=transform), want, scale, what + ", densified", n)
+
+
 def test_cancellation_at_mean_over_std_1e4():
     """float32 columns at 50 % fill over 70 001 rows whose stored values have mean / std = 1e4: a raw-moment form is off by
     (mean / std)^2 u = 1e-8 on the m2 of the groups that hold the stored rows"""

@@ -96,6 +96,30 @@ def test_designs_against_restatement(design, sparse):
         assert np.array_equal(back["logFC"].values, res["logFC"].values)
 
 
+def test_cells_left_out_lie_on_another_scale(design="two_group"):
+    """the cells a call leaves out -- the other cell types, and within the cell type the patients of neither group -- hold values
+    1e6 times the others' (raw counts beside log1p values): the table is the restatement's on the same matrix within the bounds
+    above.  The other cell types never reach the device; the third label's cells do, as skipped rows of K12, and two of the 30
+    row slices the host makes of these 3 963 cells (n // 128 on any device of 8 or more CUs, the rule restated in
+    tests/test_gpu_group_moments.py) begin with one."""
+    adata, props, _, _ = _cohort()
+    lab = S.cohort(seed=COHORT_SEED)[2]
+    rows = S.cell_values(adata)[1]
+    out = np.asarray(adata.obs["cell_types"]) != S.CELL
+    out |= (lab != G1) & (lab != G2)
+    X = adata.X.copy()
+    X[out] *= np.float32(1e6)
+    scaled = S.Cohort(X, adata.obs, adata.var_names)
+    n, skipped = rows.size, out[rows]
+    starts = [n // (n // 128) * s + n % (n // 128) * s // (n // 128) for s in range(n // 128)]
+    assert out.sum() > 600 and skipped.sum() > 300 and skipped[starts].sum() >= 2
+    assert np.isfinite(X).all() and X[out].max() >= 1e5 * X[~out].max() and np.array_equal(X[~out], adata.X[~out])
+    want = LR.diff_expressions(X[rows], lab[rows], G1, G2, design)
+    assert all(np.array_equal(want[k], _restated(design)[k]) for k in ("logFC", "t"))     # the restatement never sees those cells
+    res = tl.compute_diff_expressions(scaled, S.CELL, props, highly_variable_genes_=False, design=design)
+    _check_table(res, want, adata.var_names, design + ", cells left out scaled by 1e6")
+
+
 @pytest.mark.parametrize("id_column", ["sampleID", None])
 def test_sample_ids_from_the_other_places(id_column):
     adata, props, _, _ = _cohort()

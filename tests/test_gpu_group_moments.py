@@ -3,7 +3,7 @@ moments (tests/limma_restatement.py::group_moments).
 
 Bounds, from the summation order the kernels implement (moments_kernels.hpp), u = 2^-53 = 1.1e-16.  A wave owns one row slice of
 one column tile and walks it in chunks of R = 8 rows; every value is first taken relative to the slice's shift K (its first
-row), d = t(y) - K.  Per chunk and group: the sum of at most 8 terms (7 u), its mean (2 u more), the squared deviations from that
+USED row, code >= 0; a skipped row never sets it), d = t(y) - K.  Per chunk and group: the sum of at most 8 terms (7 u), its mean (2 u more), the squared deviations from that
 mean (at most 8 terms: 10 u relative on a sum of non-negative terms), and Chan's update of the running (n, mean, m2).  The slices
 are joined by the same update in slice order.  With C chunks per slice and S slices a column's result has passed through at most
 C + S updates, each adding at most 3 u |mean - K| to the running mean and 4 u relative to the running m2 (a sum of non-negative
@@ -13,8 +13,12 @@ terms, so relative errors do not amplify); the shift returns with one rounding, 
     m2 relative  <= (14 + 4 (C + S)) u + 2 (C + S) 3 u rho,   rho = max|running mean - K| / (between-chunk spread),
 
 where the second m2 term is the running mean's error entering delta^2 n_a n_c / (n_a + n_c); the between-chunk terms carry only
-about 1 / R of m2, and with K a row of the data rho is O(1) whatever mean / std is -- that is what the shift is for (a raw
-sum(y^2) - n mean^2 would lose (mean / std)^2 u = 1e-8 at mean / std = 1e4).  The host makes slices of at least 128 rows, so
+about 1 / R of m2.  K is the slice's first used row and rho is measured between that row and each group's running mean, so rho
+is O(1), whatever mean / std is, only when the groups of one call lie within a few standard deviations of each other's scale
+(one shift serves every group; groups that lie far apart are outside these bounds and are not tested) -- that is what the shift
+is for (a raw sum(y^2) - n mean^2 would lose (mean / std)^2 u = 1e-8 at mean / std = 1e4).  A skipped row may hold anything,
+on any scale: the tests below fill the skipped rows, every slice's first row among them, with values 1e4 to 1e36 times the
+used ones and hold the results to the same bounds.  The host makes slices of at least 128 rows, so
 C <= ceil(n / (8 S)) + 1, and S <= 8 CUs / tiles: at the largest case here, n = 70 001 with 2 column tiles, S = 546 and C = 17,
 which gives 1.9e-13 max|d| for the mean and 2.5e-13 + 3.7e-13 rho for m2 -- below the worst-case bound of a plain sequential
 float64 sum, n u = 7.8e-12.  The tests hold mean to tol max|t(y)| absolute and m2 to tol relative with tol = min(1e-11,
@@ -186,3 +190,144 @@ def test_cancellation_at_mean_over_std_1e4():
     assert (np.abs(raw - want[2]) / want[2]).max() > 1e-10        # the raw form fails this very bound on the host
     got = engine.group_moments(Y, codes, 2)
     _check(got, want, np.abs(Y).max(), "mean / std = 1e4", n)
+
+
+# ---- skipped rows on another scale ---------------------------------------------------------------------------------------------
+# The host's slice rule, restated (not imported): min(n // 128, ceil(8 CUs / column tiles)) slices, so for n <= 1031 and at most
+# two column tiles (<= 512 selected columns) S = max(1, n // 128) on any device of two or more CUs; slice s starts at
+# n // S * s + n % S * s // S.
+def _slice_starts(n):
+    assert n <= 1031
+    S = max(1, n // 128)
+    return np.array([n // S * s + n % S * s // S for s in range(S)] + [n])
+
+
+# (id, storage, transform, the value in every skipped row, its least ratio to the used rows' largest |t(y)|)
+POISONS = [("f64-1e12", np.float64, None, 1e12, 1e10), ("f32-1e6", np.float32, None, 1e6, 1e4),
+           ("f32-max", np.float32, None, float(np.finfo(np.float32).max), 1e36),
+           ("f64-expm1-700", np.float64, "expm1", 700.0, 1e12), ("f32-expm1-88", np.float32, "expm1", 88.0, 1e12)]
+POISON_IDS = [p[0] for p in POISONS]
+
+
+def _t(Y, transform):
+    V = np.asarray(Y, dtype=np.float64)
+    return np.expm1(V) if transform == "expm1" else V
+
+
+def _used_values(rng, n, G, dtype, transform):
+    if transform == "expm1":                                       # log1p-scale counts, as highly_variable_genes sees them
+        return np.ascontiguousarray(np.log1p(rng.poisson(rng.lognormal(0.5, 1.2, G), (n, G))), dtype=dtype)
+    return _data(rng, n, G, dtype)
+
+
+def _poisoned(rng, n, G, dtype, transform, poison, factor, codes):
+    """used rows from the module's distributions, every skipped row filled with ``poison``; the premises asserted; returns
+    (Y, the largest |t(y)| over the used rows)"""
+    Y = _used_values(rng, n, G, dtype, transform)
+    skipped = codes < 0
+    Y[skipped] = poison
+    assert skipped[_slice_starts(n)[:-1]].all() and (~skipped).any()                 # every slice's first row is a skipped one
+    t = _t(Y, transform)
+    scale = np.abs(t[~skipped]).max()
+    assert np.isfinite(t).all() and scale > 0 and np.abs(t[skipped]).min() >= factor * scale
+    return Y, scale
+
+
+@pytest.mark.parametrize("n_groups", [1, 2, 3, 5])                 # the 1-, 2-, 4- and 8-group kernels
+@pytest.mark.parametrize("n,G", [(n, G) for n in (257, 1024, 1031) for G in (255, 256, 257)])
+@pytest.mark.parametrize("poison", POISONS, ids=POISON_IDS)
+def test_skipped_rows_on_another_scale(poison, n, G, n_groups):
+    """every skipped row, each slice's first row among them, holds a finite value far above the used rows: by every route Y can
+    arrive the result is the two-pass reference's within the module's bounds.  A shift taken from the slice's first row whatever
+    its code fails this: replayed on the host, 1e-5 on the mean and on m2 for 1e12 in float64 storage, 5e-12 / 1.5e-11 for 1e6
+    in float32 storage at n = 257 (tol 2.9e-14), and nothing left at all of float32's largest value."""
+    _, dtype, transform, value, factor = poison
+    rng = np.random.default_rng([n, G, n_groups, POISON_IDS.index(poison[0])])
+    codes = rng.integers(-1, n_groups, n)
+    codes[_slice_starts(n)[:-1]] = -1
+    Y, scale = _poisoned(rng, n, G, dtype, transform, value, factor, codes)
+    what = "%s %d x %d, %d groups" % (poison[0], n, G, n_groups)
+    want = LR.group_moments(Y, codes, n_groups, transform=transform)
+    got = engine.group_moments(Y, codes, n_groups, transform=transform)
+    _check(got, want, scale, what + ", host array", n)
+    D = engine.DeviceMatrix.upload(Y)
+    assert _same(engine.group_moments(D, codes, n_groups, transform=transform), got)
+    assert _same(engine.group_moments(Y, codes, n_groups, transform=transform), got)
+    # a window of a wider matrix: ld = G + 11 > G, the window's start 3 elements (12 or 24 bytes) off a 16-byte boundary
+    W = np.ascontiguousarray(rng.standard_normal((n, G + 11)), dtype=dtype)
+    W[codes < 0] = value
+    W[:, 3:3 + G] = Y
+    V = engine.device_columns(engine.DeviceMatrix.upload(W), 3, 3 + G)
+    assert V.ld > G and (3 * np.dtype(dtype).itemsize) % 16 != 0
+    win = engine.group_moments(V, codes, n_groups, transform=transform)
+    _check(win, want, scale, what + ", window", n)
+    assert _same(win, got)                                         # the same n and columns: the same slices
+    cols = rng.permutation(G)[:G // 2 + 3]
+    assert (np.diff(cols) < 0).any()
+    sub = engine.group_moments(D, codes, n_groups, transform=transform, cols=cols)
+    _check(sub, LR.group_moments(Y, codes, n_groups, transform=transform, cols=cols), scale, what + ", cols", n)
+    assert _same(engine.group_moments(Y, codes, n_groups, transform=transform, cols=cols), sub)
+    # one column tile here against two above, yet the same max(1, n // 128) slices by the rule restated above: the same bits
+    assert _same(sub, tuple([got[0]] + [a[:, cols] for a in got[1:]]))
+
+
+@pytest.mark.parametrize("poison", POISONS[:3], ids=POISON_IDS[:3])
+def test_runs_of_skipped_rows(poison):
+    """n = 1031, 8 slices starting at 0, 128, 257, 386, 515, 644, 773, 902.  Rows 250:390 are skipped: slice 2 contributes nothing
+    and the run spills into both neighbours.  Slice 4 has only its last row used, slice 6 only its second.  Group 2 is that second
+    row alone (m2 == 0.0 exactly, the mean the row itself), group 3 is empty (NaN)."""
+    _, dtype, transform, value, factor = poison
+    n, G, n_groups = 1031, 257, 4
+    starts = _slice_starts(n)
+    assert list(starts) == [0, 128, 257, 386, 515, 644, 773, 902, 1031]
+    rng = np.random.default_rng(POISON_IDS.index(poison[0]))
+    codes = rng.integers(-1, 2, n)
+    codes[starts[:-1]] = -1
+    codes[250:390], codes[249], codes[390] = -1, 0, 1
+    codes[starts[4]:starts[5]] = -1
+    codes[starts[5] - 1] = 0
+    codes[starts[6]:starts[7]] = -1
+    codes[starts[6] + 1] = 2
+    assert (codes[250:390] < 0).all() and codes[249] >= 0 and codes[390] >= 0 and 250 < starts[2] and starts[3] < 390
+    assert (codes[starts[4]:starts[5]] >= 0).sum() == 1 and (codes[starts[6]:starts[7]] >= 0).sum() == 1
+    Y, scale = _poisoned(rng, n, G, dtype, transform, value, factor, codes)
+    want = LR.group_moments(Y, codes, n_groups)
+    assert want[0][2] == 1 and want[0][3] == 0 and want[0][0] > 100 and want[0][1] > 100
+    got = engine.group_moments(Y, codes, n_groups)
+    _check(got, want, scale, "runs of skipped rows, %s" % poison[0], n)
+    assert (got[2][2] == 0.0).all() and np.array_equal(got[1][2], Y[starts[6] + 1].astype(np.float64))
+    assert np.isnan(got[1][3]).all() and np.isnan(got[2][3]).all()
+    assert _same(engine.group_moments(engine.DeviceMatrix.upload(Y), codes, n_groups), got)
+    # the single row as a group of its own in the 2-group kernel, everything else skipped but one far slice
+    lone = np.full(n, -1)
+    lone[starts[6] + 1] = 1
+    lone[5:100] = 0
+    Y2 = Y.copy()
+    Y2[lone < 0] = value
+    got = engine.group_moments(Y2, lone, 2)
+    _check(got, LR.group_moments(Y2, lone, 2), np.abs(Y2[lone >= 0].astype(np.float64)).max(), "a lone row, %s" % poison[0], n)
+    assert got[0][1] == 1 and (got[2][1] == 0.0).all() and np.array_equal(got[1][1], Y2[starts[6] + 1].astype(np.float64))
+
+
+@pytest.mark.parametrize("poison", POISONS[:2], ids=POISON_IDS[:2])
+def test_first_used_row_not_finite_in_one_column(poison):
+    """the first used row of slice 3 holds +inf in column 100 alone, below poisoned skipped rows: that column's shift is 0 and
+    its results are not asserted (a non-finite value in a used row is outside the contract); every other column, the three that
+    share its lane included, is held to the bounds"""
+    _, dtype, transform, value, factor = poison
+    n, G, n_groups, j = 1031, 257, 2, 100
+    starts = _slice_starts(n)
+    rng = np.random.default_rng(7 + POISON_IDS.index(poison[0]))
+    codes = rng.integers(-1, n_groups, n)
+    codes[starts[:-1]] = -1
+    codes[starts[3]:starts[3] + 3] = -1
+    first = starts[3] + 3
+    codes[first] = 1
+    Y, scale = _poisoned(rng, n, G, dtype, transform, value, factor, codes)
+    Y[first, j] = np.inf
+    assert (codes[starts[3]:first] < 0).all() and (Y[starts[3]:first] == dtype(value)).all() and np.isinf(Y[first]).sum() == 1
+    keep = np.arange(G) != j
+    want = LR.group_moments(np.ascontiguousarray(Y[:, keep]), codes, n_groups)
+    for route in (Y, engine.DeviceMatrix.upload(Y)):
+        count, mean, m2 = engine.group_moments(route, codes, n_groups)
+        _check((count, mean[:, keep], m2[:, keep]), want, scale, "+inf in a first used row, %s" % poison[0], n)

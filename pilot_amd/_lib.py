@@ -233,3 +233,12 @@ def dptr(x: np.ndarray):
 
 def iptr(x: np.ndarray):
     return x.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def lptr(x: np.ndarray):
+    return x.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+
+
+def dtype_code(dtype) -> int:
+    """the ABI's dtype argument: 0 = float32, 1 = float64"""
+    return 0 if dtype == np.float32 else 1

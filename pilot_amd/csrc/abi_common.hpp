@@ -43,6 +43,20 @@ template <typename T> hipError_t ws(WsSlot slot, size_t n, T **out) {
     return e;
 }
 
+// ---- dense matrix arguments: what every entry point that takes a row-major matrix (dtype code, columns, leading dimension, an
+// optional column selection; on the host or in HBM) checks and stages.  The checks make no HIP call.
+inline size_t elem_size(int dtype) { return dtype == 0 ? sizeof(float) : sizeof(double); }
+int check_dtype(int dtype);
+int check_ld(long long ld, int n_cols);
+// a selection of n_sel columns out of n_cols: every cols[j] in range; without cols the selection is all of them
+int check_cols(const int *cols, int n_sel, int n_cols);
+// `rows` x `n_cols` elements of `es` bytes at Y, leading dimension ld, as a device pointer: Y and ld themselves when Y is in HBM,
+// else a packed copy (leading dimension n_cols) in `slot`.  Chunked callers pass each chunk's first element and row count.
+int stage_dense(const void *Y, int is_device, size_t es, long long rows, long long n_cols, long long ld, WsSlot slot, const void **ptr,
+                long long *ld_out);
+// the same for a whole packed float64 matrix of `count` elements
+int stage_f64(const double *src, int is_device, size_t count, WsSlot slot, const double **out);
+
 // device time of the calling thread's last pre-pass (pilot_ot_prepass_device_ms): two events on the launch stream
 struct PrepassClock {
     hipEvent_t ev[2] = {nullptr, nullptr};

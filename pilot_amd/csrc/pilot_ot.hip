@@ -198,6 +198,43 @@ int cu_count() {
     return n;
 }
 
+int check_dtype(int dtype) {
+    return dtype == 0 || dtype == 1 ? PILOT_OT_OK : fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+}
+
+int check_ld(long long ld, int n_cols) {
+    return ld >= n_cols ? PILOT_OT_OK : fail(PILOT_OT_EINVAL, "ld=%lld is smaller than n_cols=%d", ld, n_cols);
+}
+
+int check_cols(const int *cols, int n_sel, int n_cols) {
+    if (n_sel < 0 || (!cols && n_sel != n_cols))
+        return fail(PILOT_OT_EINVAL, "n_sel=%d columns selected (without cols it must be all n_cols=%d)", n_sel, n_cols);
+    for (int j = 0; cols && j < n_sel; ++j)
+        if (cols[j] < 0 || cols[j] >= n_cols) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", j, cols[j], n_cols);
+    return PILOT_OT_OK;
+}
+
+int stage_dense(const void *Y, int is_device, size_t es, long long rows, long long n_cols, long long ld, WsSlot slot, const void **ptr,
+                long long *ld_out) {
+    if (is_device) { *ptr = Y; *ld_out = ld; return PILOT_OT_OK; }
+    unsigned char *d;
+    HIP_TRY(ws(slot, (size_t)(rows > 0 ? rows : 1) * n_cols * es, &d));
+    if (rows > 0)
+        HIP_TRY(hipMemcpy2D(d, (size_t)n_cols * es, Y, (size_t)ld * es, (size_t)n_cols * es, (size_t)rows, hipMemcpyHostToDevice));
+    *ptr = d;
+    *ld_out = n_cols;
+    return PILOT_OT_OK;
+}
+
+int stage_f64(const double *src, int is_device, size_t count, WsSlot slot, const double **out) {
+    if (is_device) { *out = src; return PILOT_OT_OK; }
+    double *d;
+    HIP_TRY(ws(slot, count, &d));
+    HIP_TRY(hipMemcpy(d, src, sizeof(double) * count, hipMemcpyHostToDevice));
+    *out = d;
+    return PILOT_OT_OK;
+}
+
 int host_ctx_prepare(int N, int K, size_t n_out) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));

@@ -65,17 +65,17 @@ int check_args(const void *Y, int dtype, int n, int n_cols, long long ld, const 
     if (!Y || !x || !params || (n_problems > 0 && (!cols || !models || !idx))) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (n < 1) return fail(PILOT_OT_EINVAL, "n=%d: the fits need at least 1 observation", n);
     if (n_cols < 1) return fail(PILOT_OT_EINVAL, "n_cols=%d must be positive", n_cols);
-    if (ld < n_cols) return fail(PILOT_OT_EINVAL, "ld=%lld is smaller than n_cols=%d", ld, n_cols);
-    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (int rc = pilot::check_ld(ld, n_cols)) return rc;
+    if (int rc = pilot::check_dtype(dtype)) return rc;
     if (n_problems < 0) return fail(PILOT_OT_EINVAL, "n_problems=%d is negative", n_problems);
     if (B < 1 || B > 64 * 65535) return fail(PILOT_OT_EINVAL, "B=%d must be in [1, %d]", B, 64 * 65535);
     if (!(epsilon >= 1.0) || !std::isfinite(epsilon)) return fail(PILOT_OT_EINVAL, "epsilon=%g must be finite and >= 1", epsilon);
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(x[i])) return fail(PILOT_OT_EINVAL, "x[%d]=%g is not finite", i, x[i]);
-    for (int q = 0; q < n_problems; ++q) {
-        if (cols[q] < 0 || cols[q] >= n_cols) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", q, cols[q], n_cols);
+    if (n_problems > 0)                                          // (one column per problem; none given: nothing to judge)
+        if (int rc = pilot::check_cols(cols, n_problems, n_cols)) return rc;
+    for (int q = 0; q < n_problems; ++q)
         if (models[q] < 0 || models[q] > 2) return fail(PILOT_OT_EINVAL, "models[%d]=%d must be 0, 1 or 2", q, models[q]);
-    }
     const size_t total = (size_t)n_problems * n * B;
     for (size_t j = 0; j < total; ++j)
         if ((unsigned)idx[j] >= (unsigned)n)
@@ -110,11 +110,9 @@ PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int 
         if (v > 0) pc = v;
     }
     pc = std::min<long long>(pc, n_problems);
-    const size_t es = dtype == 0 ? sizeof(float) : sizeof(double);
 
     double *d_u, *d_out;
     int *d_idx, *d_pm;
-    unsigned char *d_y = nullptr;
     const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
     HIP_TRY(pilot::ws(pilot::WS_BOOT_U, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
     const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
@@ -125,14 +123,10 @@ PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int 
     HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_pm, cols, sizeof(int) * n_problems, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_pm + n_problems, models, sizeof(int) * n_problems, hipMemcpyHostToDevice));
-    const void *yd = Y;
-    long long ldd = ld;
-    if (!Y_is_device) {                                          // a host Y is copied whole (its n x n_cols part)
-        HIP_TRY(pilot::ws(pilot::WS_BOOT_Y, (size_t)n * n_cols * es, &d_y));
-        HIP_TRY(hipMemcpy2D(d_y, (size_t)n_cols * es, Y, (size_t)ld * es, (size_t)n_cols * es, (size_t)n, hipMemcpyHostToDevice));
-        yd = d_y;
-        ldd = n_cols;
-    }
+    const void *yd;                                              // a host Y is copied whole (its n x n_cols part)
+    long long ldd;
+    rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), n, n_cols, ld, pilot::WS_BOOT_Y, &yd, &ldd);
+    if (rc != PILOT_OT_OK) return rc;
     std::vector<double> rec((size_t)pc * B * pilot::BF_NOUT);
     int not_conv = 0;
     for (long long q0 = 0; q0 < n_problems; q0 += pc) {

@@ -159,13 +159,12 @@ PILOT_API int pilot_ot_silhouette_of_rows(const double *E, int E_is_device, int 
                                           int n_clusters, double *score, double *samples) {
     if (!E || !labels || !score) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0 || n_clusters <= 0 || n_clusters > 4096) return fail(PILOT_OT_EINVAL, "N=%d n_clusters=%d out of range", N, n_clusters);
-    double *dE = nullptr, *dD = nullptr, *dM = nullptr;
-    const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
-    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_MAX, 1, &dM);
-    if (e == hipSuccess && !E_is_device) { e = pilot::ws(pilot::WS_CONS_E, (size_t)N * N, &dE); if (e == hipSuccess) e = hipMemcpy(dE, E, bytes, hipMemcpyHostToDevice); }
-    if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    int rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, normalize_by_max, metric, dD, dM, nullptr);
+    const double *dE;
+    double *dD, *dM;
+    HIP_TRY(pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD));
+    HIP_TRY(pilot::ws(pilot::WS_CONS_MAX, 1, &dM));
+    int rc = pilot::stage_f64(E, E_is_device, (size_t)N * N, pilot::WS_CONS_E, &dE);
+    if (rc == PILOT_OT_OK) rc = pilot_ot_row_distances_dev(dE, N, normalize_by_max, metric, dD, dM, nullptr);
     if (rc != PILOT_OT_OK) return rc;
     return silhouette_of_device_matrix(dD, labels, N, n_clusters, score, samples, nullptr);
 }
@@ -176,14 +175,14 @@ PILOT_API int pilot_ot_diffusion_kernel_of_rows(const double *E, int E_is_device
     if (!E || !Kmat) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (N <= 0) return fail(PILOT_OT_EINVAL, "N=%d must be positive", N);
     if (int rc = pilot::knn_rows_supported(N)) return rc;
-    double *dE = nullptr, *dD = nullptr, *dK = nullptr, *dM = nullptr;
+    const double *dE;
+    double *dD, *dK, *dM;
     const size_t bytes = sizeof(double) * (size_t)N * N;
-    hipError_t e = pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD);
-    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_K, (size_t)N * N, &dK);
-    if (e == hipSuccess) e = pilot::ws(pilot::WS_CONS_MAX, 1, &dM);
-    if (e == hipSuccess && !E_is_device) { e = pilot::ws(pilot::WS_CONS_E, (size_t)N * N, &dE); if (e == hipSuccess) e = hipMemcpy(dE, E, bytes, hipMemcpyHostToDevice); }
-    if (e != hipSuccess) return fail(PILOT_OT_EHIP, "device staging failed: %s", hipGetErrorString(e));
-    int rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);
+    HIP_TRY(pilot::ws(pilot::WS_CONS_D, (size_t)N * N, &dD));
+    HIP_TRY(pilot::ws(pilot::WS_CONS_K, (size_t)N * N, &dK));
+    HIP_TRY(pilot::ws(pilot::WS_CONS_MAX, 1, &dM));
+    int rc = pilot::stage_f64(E, E_is_device, (size_t)N * N, pilot::WS_CONS_E, &dE);
+    if (rc == PILOT_OT_OK) rc = pilot_ot_row_distances_dev(dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);
     if (rc == PILOT_OT_OK) rc = pilot_ot_knn_kernel_dev(dD, N, k, epsilon, dK, nullptr);
     if (rc != PILOT_OT_OK) return rc;
     if (D_out) HIP_TRY(hipMemcpy(D_out, dD, bytes, hipMemcpyDeviceToHost));

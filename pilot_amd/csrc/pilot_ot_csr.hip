@@ -27,7 +27,7 @@ struct pilot_ot_csr {
 
 namespace {
 
-size_t elem(const pilot_ot_csr *c) { return c->dtype == 0 ? sizeof(float) : sizeof(double); }
+size_t elem(const pilot_ot_csr *c) { return pilot::elem_size(c->dtype); }
 unsigned row_blocks(long long n) { return (unsigned)((n + pilot::CSR_ROW_WAVES - 1) / pilot::CSR_ROW_WAVES); }
 
 int build_columns(pilot_ot_csr *c) {
@@ -101,7 +101,7 @@ PILOT_API int pilot_ot_csr_slice_rows(void) { return pilot::CSR_SLICE_ROWS; }
 PILOT_API int pilot_ot_csr_upload(const long long *indptr, const int *indices, const void *data, int dtype, long long n_rows, int n_cols,
                                   pilot_ot_csr **csr) {
     if (!indptr || !csr) return fail(PILOT_OT_EINVAL, "NULL pointer (indptr or csr)");
-    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (int rc = pilot::check_dtype(dtype)) return rc;
     if (n_rows < 0 || n_rows > INT_MAX || n_cols < 1) return fail(PILOT_OT_EINVAL, "n_rows=%lld (at most %d), n_cols=%d", n_rows, INT_MAX, n_cols);
     if (indptr[0] != 0) return fail(PILOT_OT_EINVAL, "indptr[0]=%lld must be 0", indptr[0]);
     for (long long i = 0; i < n_rows; ++i)
@@ -192,10 +192,7 @@ PILOT_API int pilot_ot_csr_group_moments(pilot_ot_csr *c, const int *codes, int 
     if (n_groups < 1 || n_groups > pilot::CSR_MAX_GROUPS) return fail(PILOT_OT_EINVAL, "n_groups=%d must be in [1, %d]", n_groups, pilot::CSR_MAX_GROUPS);
     if (transform != 0 && transform != 1) return fail(PILOT_OT_EINVAL, "transform=%d must be 0 (none) or 1 (expm1)", transform);
     if (!c || !count || !mean || !m2 || (!codes && c->n > 0)) return fail(PILOT_OT_EINVAL, "NULL pointer (csr, codes, count, mean or m2)");
-    if (n_cols < 0 || (!cols && n_cols != c->n_cols))
-        return fail(PILOT_OT_EINVAL, "n_cols=%d (without cols it must be the matrix's %d)", n_cols, c->n_cols);
-    for (int j = 0; cols && j < n_cols; ++j)
-        if (cols[j] < 0 || cols[j] >= c->n_cols) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", j, cols[j], c->n_cols);
+    if (int rc = pilot::check_cols(cols, n_cols, c->n_cols)) return rc;
     MomentsArgs a;
     a.c = c;
     for (long long &v : a.rows.n) v = 0;
@@ -234,12 +231,10 @@ PILOT_API int pilot_ot_csr_group_moments(pilot_ot_csr *c, const int *codes, int 
 
 PILOT_API int pilot_ot_csr_densify(pilot_ot_csr *c, const int *cols, int n_cols, void *out) {
     if (!c || (!out && n_cols > 0)) return fail(PILOT_OT_EINVAL, "NULL pointer (csr or out)");
-    if (n_cols < 0 || (!cols && n_cols != c->n_cols))
-        return fail(PILOT_OT_EINVAL, "n_cols=%d (without cols it must be the matrix's %d)", n_cols, c->n_cols);
+    if (int rc = pilot::check_cols(cols, n_cols, c->n_cols)) return rc;
     std::vector<int> pos((size_t)c->n_cols, -1);
     for (int j = 0; j < n_cols; ++j) {
         const int col = cols ? cols[j] : j;
-        if (col < 0 || col >= c->n_cols) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", j, col, c->n_cols);
         if (pos[col] >= 0) return fail(PILOT_OT_EINVAL, "cols[%d]=%d repeats cols[%d]: a column is written once", j, col, pos[col]);
         pos[col] = j;
     }

@@ -14,16 +14,6 @@
 
 namespace {
 
-// `src` (rows x cols doubles) as a device pointer: itself, or a copy in `slot`
-int stage_f64(const double *src, int is_device, size_t count, pilot::WsSlot slot, const double **out) {
-    if (is_device) { *out = src; return PILOT_OT_OK; }
-    double *d;
-    HIP_TRY(pilot::ws(slot, count, &d));
-    HIP_TRY(hipMemcpy(d, src, sizeof(double) * count, hipMemcpyHostToDevice));
-    *out = d;
-    return PILOT_OT_OK;
-}
-
 int check_times(const double *times, int T) {
     if (T < 2) return fail(PILOT_OT_EINVAL, "times must be increasing and have at least 2 values (got %d)", T);
     for (int t = 0; t < T; ++t)
@@ -39,31 +29,24 @@ PILOT_API int pilot_ot_segment_std(const void *Y, int Y_is_device, int dtype, lo
                                    const long long *offsets, int n_segments, const int *cols, int n_sel, double *out,
                                    int out_is_device) {
     if (!Y || !offsets || !out) return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (n < 0 || n_cols < 1 || ld < n_cols) return fail(PILOT_OT_EINVAL, "n=%lld, n_cols=%d, ld=%lld", n, n_cols, ld);
-    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (n < 0 || n_cols < 1) return fail(PILOT_OT_EINVAL, "n=%lld, n_cols=%d", n, n_cols);
+    if (int rc = pilot::check_ld(ld, n_cols)) return rc;
+    if (int rc = pilot::check_dtype(dtype)) return rc;
     if (n_segments < 0 || n_segments > 65535) return fail(PILOT_OT_EINVAL, "n_segments=%d must be in [0, 65535]", n_segments);
-    if (n_sel < 0 || (!cols && n_sel != n_cols)) return fail(PILOT_OT_EINVAL, "n_sel=%d (without cols it must be n_cols=%d)", n_sel, n_cols);
     if (offsets[0] < 0 || offsets[n_segments] > n) return fail(PILOT_OT_EINVAL, "offsets must lie in [0, n=%lld]", n);
     for (int s = 0; s < n_segments; ++s)
         if (offsets[s + 1] < offsets[s]) return fail(PILOT_OT_EINVAL, "offsets[%d]=%lld after %lld: must not decrease", s + 1, offsets[s + 1], offsets[s]);
-    for (int j = 0; cols && j < n_sel; ++j)
-        if (cols[j] < 0 || cols[j] >= n_cols) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", j, cols[j], n_cols);
+    if (int rc = pilot::check_cols(cols, n_sel, n_cols)) return rc;
     if (n_segments == 0 || n_sel == 0) return PILOT_OT_OK;
-    const size_t es = dtype == 0 ? sizeof(float) : sizeof(double);
-    const void *yd = Y;
-    long long ldd = ld;
+    const size_t es = pilot::elem_size(dtype);
     std::vector<long long> off(offsets, offsets + n_segments + 1);
-    if (!Y_is_device) {                                          // a host Y: the rows the segments cover, copied whole
-        unsigned char *d_y;
-        const long long r0 = offsets[0], nr = offsets[n_segments] - r0;
-        for (long long &o : off) o -= r0;
-        HIP_TRY(pilot::ws(pilot::WS_CV_Y, (size_t)std::max<long long>(nr, 1) * n_cols * es, &d_y));
-        if (nr > 0)
-            HIP_TRY(hipMemcpy2D(d_y, (size_t)n_cols * es, static_cast<const unsigned char *>(Y) + (size_t)r0 * ld * es, (size_t)ld * es,
-                                (size_t)n_cols * es, (size_t)nr, hipMemcpyHostToDevice));
-        yd = d_y;
-        ldd = n_cols;
-    }
+    const long long r0 = Y_is_device ? 0 : offsets[0];           // a host Y: only the rows the segments cover go up
+    for (long long &o : off) o -= r0;
+    const void *yd;
+    long long ldd;
+    if (int rc = pilot::stage_dense(static_cast<const unsigned char *>(Y) + (size_t)r0 * ld * es, Y_is_device, es, offsets[n_segments] - r0,
+                                    n_cols, ld, pilot::WS_CV_Y, &yd, &ldd))
+        return rc;
     long long *d_off;
     int *d_cols = nullptr;
     HIP_TRY(pilot::ws(pilot::WS_CV_AUX, (size_t)n_segments + 1 + (size_t)(n_sel + 1) / 2, &d_off));
@@ -107,7 +90,7 @@ PILOT_API int pilot_ot_fitted_curves(const double *params, const int *models, in
     HIP_TRY(hipMemcpy(d_models, models, sizeof(int) * (size_t)G, hipMemcpyHostToDevice));
     const double *d_sd = nullptr;
     if (sd) {
-        int rc = stage_f64(sd, sd_is_device, (size_t)T * G, pilot::WS_CV_Y, &d_sd);
+        int rc = pilot::stage_f64(sd, sd_is_device, (size_t)T * G, pilot::WS_CV_Y, &d_sd);
         if (rc != PILOT_OT_OK) return rc;
     }
     double *d_out = out;
@@ -133,7 +116,7 @@ PILOT_API int pilot_ot_linkage_of_rows(const double *Y, int Y_is_device, int G, 
         for (size_t j = 0; j < (size_t)G * T; ++j)
             if (!std::isfinite(Y[j])) return fail(PILOT_OT_EINVAL, "Y[%zu]=%g is not finite", j, Y[j]);
     const double *d_y;
-    int rc = stage_f64(Y, Y_is_device, (size_t)G * T, pilot::WS_CV_Y, &d_y);
+    int rc = pilot::stage_f64(Y, Y_is_device, (size_t)G * T, pilot::WS_CV_Y, &d_y);
     if (rc != PILOT_OT_OK) return rc;
     const unsigned nb = (unsigned)((G + pilot::CV_D_TILE - 1) / pilot::CV_D_TILE);
     double *d_bmax, *d_z;
@@ -191,7 +174,7 @@ PILOT_API int pilot_ot_curve_activities(const double *curves, int curves_is_devi
     if (rc != PILOT_OT_OK) return rc;
     if (G == 0) return PILOT_OT_OK;
     const double *d_c;
-    rc = stage_f64(curves, curves_is_device, (size_t)G * T, pilot::WS_CV_Y, &d_c);
+    rc = pilot::stage_f64(curves, curves_is_device, (size_t)G * T, pilot::WS_CV_Y, &d_c);
     if (rc != PILOT_OT_OK) return rc;
     double *d_times, *d_out;
     HIP_TRY(pilot::ws(pilot::WS_CV_IN, (size_t)T, &d_times));

@@ -204,16 +204,14 @@ PILOT_API int pilot_ot_diffusion_map_of_rows(const double *E, int E_is_device, i
     if (k < 1) return fail(PILOT_OT_EINVAL, "k=%d must be positive", k);
     if ((rc = pilot::knn_rows_supported(N)) != PILOT_OT_OK) return rc;
     const size_t nn = (size_t)N * N, no = (size_t)N * n_evecs;
-    double *dE = nullptr, *dD, *dK, *dM, *dOut;
+    const double *dE;
+    double *dD, *dK, *dM, *dOut;
     HIP_TRY(pilot::ws(pilot::WS_DM_D, nn, &dD));
     HIP_TRY(pilot::ws(pilot::WS_DM_K, nn, &dK));
     HIP_TRY(pilot::ws(pilot::WS_DM_MAX, 1, &dM));
     HIP_TRY(pilot::ws(pilot::WS_DM_OUT, 2 * no + n_evecs, &dOut));
-    if (!E_is_device) {
-        HIP_TRY(pilot::ws(pilot::WS_DM_E, nn, &dE));
-        HIP_TRY(hipMemcpy(dE, E, sizeof(double) * nn, hipMemcpyHostToDevice));
-    }
-    rc = pilot_ot_row_distances_dev(E_is_device ? E : dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);
+    rc = pilot::stage_f64(E, E_is_device, nn, pilot::WS_DM_E, &dE);
+    if (rc == PILOT_OT_OK) rc = pilot_ot_row_distances_dev(dE, N, 1, PILOT_OT_ROWMETRIC_EUCLIDEAN, dD, dM, nullptr);
     if (rc == PILOT_OT_OK) rc = pilot_ot_knn_kernel_dev(dD, N, k, epsilon, dK, nullptr);
     if (rc == PILOT_OT_OK) rc = pilot_ot_diffusion_map_dev(dK, N, epsilon, alpha, n_evecs, dOut, dOut + no, dOut + 2 * no, info, nullptr);
     if (rc != PILOT_OT_OK) return rc;

@@ -44,14 +44,12 @@ PILOT_API int pilot_ot_group_moments(const void *Y, int Y_is_device, int dtype, 
                                      const int *codes, int n_groups, const int *cols, int n_cols, int transform, long long *count,
                                      double *mean, double *m2) {
     if (!Y || !count || !mean || !m2 || (!codes && n > 0)) return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (n < 0 || n_cols_total < 1 || ld < n_cols_total) return fail(PILOT_OT_EINVAL, "n=%lld, n_cols_total=%d, ld=%lld", n, n_cols_total, ld);
-    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (n < 0 || n_cols_total < 1) return fail(PILOT_OT_EINVAL, "n=%lld, n_cols_total=%d", n, n_cols_total);
+    if (int rc = pilot::check_ld(ld, n_cols_total)) return rc;
+    if (int rc = pilot::check_dtype(dtype)) return rc;
     if (n_groups < 1 || n_groups > pilot::GM_MAX_GROUPS) return fail(PILOT_OT_EINVAL, "n_groups=%d must be in [1, %d]", n_groups, pilot::GM_MAX_GROUPS);
     if (transform != 0 && transform != 1) return fail(PILOT_OT_EINVAL, "transform=%d must be 0 (none) or 1 (expm1)", transform);
-    if (n_cols < 0 || (!cols && n_cols != n_cols_total))
-        return fail(PILOT_OT_EINVAL, "n_cols=%d (without cols it must be n_cols_total=%d)", n_cols, n_cols_total);
-    for (int j = 0; cols && j < n_cols; ++j)
-        if (cols[j] < 0 || cols[j] >= n_cols_total) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", j, cols[j], n_cols_total);
+    if (int rc = pilot::check_cols(cols, n_cols, n_cols_total)) return rc;
     for (long long i = 0; i < n; ++i)
         if (codes[i] >= n_groups) return fail(PILOT_OT_EINVAL, "codes[%lld]=%d: a code is negative (row skipped) or below n_groups=%d", i, codes[i], n_groups);
     if (n_cols == 0) {
@@ -60,20 +58,11 @@ PILOT_API int pilot_ot_group_moments(const void *Y, int Y_is_device, int dtype, 
             if (codes[i] >= 0) ++count[codes[i]];
         return PILOT_OT_OK;
     }
-    const size_t es = dtype == 0 ? sizeof(float) : sizeof(double);
+    const size_t es = pilot::elem_size(dtype);
     MomentsArgs a;
-    a.y = Y;
-    a.ld = ld;
     a.n = n;
     a.n_sel = n_cols;
-    if (!Y_is_device) {
-        unsigned char *d_y;
-        HIP_TRY(pilot::ws(pilot::WS_GM_Y, (size_t)std::max<long long>(n, 1) * n_cols_total * es, &d_y));
-        if (n > 0)
-            HIP_TRY(hipMemcpy2D(d_y, (size_t)n_cols_total * es, Y, (size_t)ld * es, (size_t)n_cols_total * es, (size_t)n, hipMemcpyHostToDevice));
-        a.y = d_y;
-        a.ld = n_cols_total;
-    }
+    if (int rc = pilot::stage_dense(Y, Y_is_device, es, n, n_cols_total, ld, pilot::WS_GM_Y, &a.y, &a.ld)) return rc;
     // 16-byte row reads: every row start and every lane's first column on a 16-byte boundary
     const long long per16 = (long long)(16 / es);
     a.vec = !cols && a.ld % per16 == 0 && reinterpret_cast<uintptr_t>(a.y) % 16 == 0;

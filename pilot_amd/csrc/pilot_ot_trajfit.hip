@@ -125,8 +125,8 @@ int check_args(const void *Y, int dtype, int n, int n_targets, long long ld, con
     if (!Y || !x || !out) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (n < 4) return fail(PILOT_OT_EINVAL, "n=%d: the fits need at least 4 observations", n);
     if (n_targets < 0) return fail(PILOT_OT_EINVAL, "n_targets=%d is negative", n_targets);
-    if (ld < n_targets) return fail(PILOT_OT_EINVAL, "ld=%lld is smaller than n_targets=%d", ld, n_targets);
-    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (int rc = pilot::check_ld(ld, n_targets)) return rc;
+    if (int rc = pilot::check_dtype(dtype)) return rc;
     if (model != PILOT_OT_TRAJFIT_OLS && model != PILOT_OT_TRAJFIT_HUBER)
         return fail(PILOT_OT_EINVAL, "model=%d must be PILOT_OT_TRAJFIT_OLS or PILOT_OT_TRAJFIT_HUBER", model);
     if (!(epsilon >= 1.0) || !std::isfinite(epsilon)) return fail(PILOT_OT_EINVAL, "epsilon=%g must be finite and >= 1", epsilon);
@@ -165,7 +165,7 @@ PILOT_API int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype
         const int v = atoi(sw);
         if (v >= 0 && v < a.max_iter) a.max_iter = v;
     }
-    const size_t es = dtype == 0 ? sizeof(float) : sizeof(double);
+    const size_t es = pilot::elem_size(dtype);
     long long tc = (long long)(CHUNK_BYTES / ((size_t)n * es)) / 64 * 64;
     if (const char *sw = pilot::test_switch("PILOT_OT_TRAJFIT_CHUNK_TARGETS")) {   // (tests: many chunks)
         const long long v = atoll(sw);
@@ -175,33 +175,27 @@ PILOT_API int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype
     tc = std::min(tc, ((long long)n_targets + 63) / 64 * 64);
 
     double *d_u, *d_out;
-    unsigned char *d_y = nullptr;
     const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
     HIP_TRY(pilot::ws(pilot::WS_TF_U, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
     const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
     HIP_TRY(pilot::ws(pilot::WS_TF_OUT, (size_t)tc * pilot::TF_NOUT, &d_out));
-    if (!Y_is_device) HIP_TRY(pilot::ws(pilot::WS_TF_Y, (size_t)n * tc * es, &d_y));
     HIP_TRY(hipMemcpy(d_u, u.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
     std::vector<double> rec((size_t)tc * pilot::TF_NOUT);
     int not_conv = 0;
     for (long long t0 = 0; t0 < n_targets; t0 += tc) {
         const int nt = (int)std::min<long long>(tc, n_targets - t0);
-        const unsigned char *src = static_cast<const unsigned char *>(Y) + (size_t)t0 * es;
-        const unsigned char *yc = src;
-        long long ldc = ld;
-        if (!Y_is_device) {
-            HIP_TRY(hipMemcpy2D(d_y, (size_t)nt * es, src, (size_t)ld * es, (size_t)nt * es, (size_t)n, hipMemcpyHostToDevice));
-            yc = d_y;
-            ldc = nt;
-        }
+        const void *yc;                                          // a host Y: this chunk's columns, packed (the first chunk is the widest)
+        long long ldc;
+        rc = pilot::stage_dense(static_cast<const unsigned char *>(Y) + (size_t)t0 * es, Y_is_device, es, n, nt, ld, pilot::WS_TF_Y, &yc, &ldc);
+        if (rc != PILOT_OT_OK) return rc;
         const unsigned blocks = (unsigned)((nt + 63) / 64);
         if (dtype == 0)
             hipLaunchKernelGGL(pilot::trajfit_kernel<float>, dim3(blocks), dim3(pilot::TF_BLOCK), 0, nullptr,
-                               reinterpret_cast<const float *>(yc), ldc, nt, d_u, d_args, d_out);
+                               static_cast<const float *>(yc), ldc, nt, d_u, d_args, d_out);
         else
             hipLaunchKernelGGL(pilot::trajfit_kernel<double>, dim3(blocks), dim3(pilot::TF_BLOCK), 0, nullptr,
-                               reinterpret_cast<const double *>(yc), ldc, nt, d_u, d_args, d_out);
+                               static_cast<const double *>(yc), ldc, nt, d_u, d_args, d_out);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(rec.data(), d_out, sizeof(double) * (size_t)nt * pilot::TF_NOUT, hipMemcpyDeviceToHost));
         for (int j = 0; j < nt; ++j) {
@@ -236,12 +230,11 @@ PILOT_API int pilot_ot_normalize_log1p(const void *X, int dtype, int n, int n_ge
                                        void *out) {
     if (!X || !cols || !out) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (n < 0 || n_genes < 1 || n_cols < 0) return fail(PILOT_OT_EINVAL, "n=%d, n_genes=%d, n_cols=%d", n, n_genes, n_cols);
-    if (dtype != 0 && dtype != 1) return fail(PILOT_OT_EINVAL, "dtype=%d must be 0 (float32) or 1 (float64)", dtype);
+    if (int rc = pilot::check_dtype(dtype)) return rc;
     if (!(target_sum > 0.0) || !std::isfinite(target_sum)) return fail(PILOT_OT_EINVAL, "target_sum=%g must be positive", target_sum);
-    for (int j = 0; j < n_cols; ++j)
-        if (cols[j] < 0 || cols[j] >= n_genes) return fail(PILOT_OT_EINVAL, "cols[%d]=%d outside [0, %d)", j, cols[j], n_genes);
+    if (int rc = pilot::check_cols(cols, n_cols, n_genes)) return rc;
     if (n == 0 || n_cols == 0) return PILOT_OT_OK;
-    const size_t es = dtype == 0 ? sizeof(float) : sizeof(double);
+    const size_t es = pilot::elem_size(dtype);
     const long long rows = std::max<long long>(1, std::min<long long>(n, (long long)(CHUNK_BYTES / ((size_t)(n_genes + n_cols) * es))));
     unsigned char *d_x, *d_o;
     int *d_cols;

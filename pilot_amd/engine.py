@@ -5,6 +5,7 @@ straight to ``libpilot_ot.so`` through ctypes.  No torch, no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -26,6 +27,52 @@ def _as_f64(x, name):
     return a
 
 
+class _Closing:
+    """``close()`` when the object goes, whatever a constructor that failed half-way left behind"""
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _square(A, name):
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("%s must be square, got %s" % (name, A.shape))
+    return A
+
+
+def _pair_inputs(P, M):
+    """the pair grid's inputs: ``(P, M, N, K)`` with P (N x K) and M (K x K) finite float64"""
+    P, M = _as_f64(P, "P"), _as_f64(M, "M")
+    if P.ndim != 2 or M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] != P.shape[1]:
+        raise ValueError("shape mismatch: P %s, M %s" % (P.shape, M.shape))
+    return (P, M) + P.shape
+
+
+def _code_columns(cell_code, sample_code, n_total, n_rows=None):
+    """the two per-cell code columns as int32 (one entry per row of the embedding where ``n_rows`` is given) and n_total"""
+    cc = np.ascontiguousarray(cell_code, dtype=np.int32)
+    sc = np.ascontiguousarray(sample_code, dtype=np.int32)
+    if n_rows is None:
+        if cc.shape != sc.shape or cc.ndim != 1:
+            raise ValueError("cell_code and sample_code must be 1-D arrays of equal length")
+    elif cc.shape != (n_rows,) or sc.shape != cc.shape:
+        raise ValueError("cell_code and sample_code must have one entry per row of X")
+    return cc, sc, cc.size if n_total is None else int(n_total)
+
+
+def _embedding_arg(X):
+    """``(X, dtype code)``: the C x D embedding contiguous in its own dtype if that is float32, else as float64"""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("X must be 2-D (cells, dims)")
+    if X.dtype != np.float32:
+        X = X.astype(np.float64, copy=False)
+    return np.ascontiguousarray(X), _lib.dtype_code(X.dtype)
+
+
 def n_rows_of(N, row_begin, row_end, row_step):
     return len(range(row_begin, N if row_end is None else row_end, row_step))
 
@@ -41,11 +88,7 @@ def sinkhorn_grid(P, M, reg, num_iter_max=NUM_ITER_MAX, stop_thr=STOP_THR, tau=T
     P : (N, K) proportion vectors; M : (K, K) cost (already divided by its max).
     Returns float64 (n_rows, N) and, with ``return_info``, a dict of iters / err / flags arrays.
     """
-    P = _as_f64(P, "P")
-    M = _as_f64(M, "M")
-    if P.ndim != 2 or M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] != P.shape[1]:
-        raise ValueError("shape mismatch: P %s, M %s" % (P.shape, M.shape))
-    N, K = P.shape
+    P, M, N, K = _pair_inputs(P, M)
     if precision not in _lib.PREC:
         raise ValueError("precision must be one of %s" % sorted(_lib.PREC))
     row_end = N if row_end is None else int(row_end)
@@ -94,11 +137,7 @@ def pdist_square(centroids, metric="cosine"):
 def proportions(cell_code, sample_code, n_samples, n_types, regulizer=0.2, normalization=True, n_total=None):
     """N x K smoothed cell-type proportions from per-cell integer codes (device histogram; replaces the pandas
     loops of Cluster_Representations, pilotpy/tools/Trajectory.py:400-430).  Bit-identical to the reference."""
-    cc = np.ascontiguousarray(cell_code, dtype=np.int32)
-    sc = np.ascontiguousarray(sample_code, dtype=np.int32)
-    if cc.shape != sc.shape or cc.ndim != 1:
-        raise ValueError("cell_code and sample_code must be 1-D arrays of equal length")
-    n_total = cc.size if n_total is None else int(n_total)
+    cc, sc, n_total = _code_columns(cell_code, sample_code, n_total)
     P = np.zeros((n_samples, n_types), dtype=np.float64)
     _lib.check(_lib.load().pilot_ot_proportions(_lib.iptr(cc), _lib.iptr(sc), cc.size, n_total, int(n_samples),
                                                 int(n_types), float(regulizer), int(bool(normalization)), _lib.dptr(P)))
@@ -108,16 +147,12 @@ def proportions(cell_code, sample_code, n_samples, n_types, regulizer=0.2, norma
 def proportions_and_first_rows(cell_code, sample_code, n_samples, n_types, regulizer=0.2, normalization=True, n_total=None):
     """:func:`proportions` plus, from the same pass over the codes, the first row of every sample (int64, -1: none) --
     the row ``return_real_labels`` reads (pilotpy/tools/Trajectory.py:617-642)."""
-    cc = np.ascontiguousarray(cell_code, dtype=np.int32)
-    sc = np.ascontiguousarray(sample_code, dtype=np.int32)
-    if cc.shape != sc.shape or cc.ndim != 1:
-        raise ValueError("cell_code and sample_code must be 1-D arrays of equal length")
-    n_total = cc.size if n_total is None else int(n_total)
+    cc, sc, n_total = _code_columns(cell_code, sample_code, n_total)
     P = np.zeros((n_samples, n_types), dtype=np.float64)
     first = np.full(n_samples, -1, dtype=np.int64)
     _lib.check(_lib.load().pilot_ot_proportions_ex(
         _lib.iptr(cc), _lib.iptr(sc), cc.size, n_total, int(n_samples), int(n_types), float(regulizer), int(bool(normalization)),
-        _lib.dptr(P), first.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        _lib.dptr(P), _lib.lptr(first)))
     return P, first
 
 
@@ -136,14 +171,14 @@ def label_codes(ids, max_uniques=1 << 16, n_threads=None):
     first = np.empty(int(max_uniques), dtype=np.int64)
     n_u = ctypes.c_int(0)
     rc = _lib.load().pilot_ot_label_codes(ctypes.c_void_p(ids.ctypes.data), ids.itemsize, ids.size, int(max_uniques), int(n_threads),
-                                          _lib.iptr(codes), first.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), ctypes.byref(n_u))
+                                          _lib.iptr(codes), _lib.lptr(first), ctypes.byref(n_u))
     if rc == _lib.ENOTSUP:
         return None
     _lib.check(rc)
     return codes, first[:n_u.value]
 
 
-class EmbeddingUpload:
+class EmbeddingUpload(_Closing):
     """The C x D embedding on its way to the device: the copy runs on a helper thread (ctypes releases the GIL) while the
     caller factorises the label columns; :meth:`medians` joins it and runs the device radix select.
 
@@ -155,15 +190,7 @@ class EmbeddingUpload:
 
     def __init__(self, X):
         import threading
-        X = np.asarray(X)
-        if X.ndim != 2:
-            raise ValueError("X must be 2-D (cells, dims)")
-        if X.dtype == np.float32:
-            self.dt = 0
-        else:
-            X = X.astype(np.float64, copy=False)
-            self.dt = 1
-        self.X = np.ascontiguousarray(X)
+        self.X, self.dt = _embedding_arg(X)
         self.L = _lib.load()
         self.h = ctypes.c_void_p()
         self.err = None
@@ -208,17 +235,13 @@ class EmbeddingUpload:
         self.thread.join()
         if self.err is not None:
             raise self.err
-        cc = np.ascontiguousarray(cell_code, dtype=np.int32)
-        sc = np.ascontiguousarray(sample_code, dtype=np.int32)
-        if cc.shape != (self.X.shape[0],) or sc.shape != cc.shape:
-            raise ValueError("cell_code and sample_code must have one entry per row of X")
-        n_total = cc.size if n_total is None else int(n_total)
+        cc, sc, n_total = _code_columns(cell_code, sample_code, n_total, n_rows=self.X.shape[0])
         P = np.zeros((int(n_samples), int(n_types)), dtype=np.float64)
         first = np.full(int(n_samples), -1, dtype=np.int64)
         cen = np.zeros((int(n_types), self.X.shape[1]), dtype=np.float64)
         _lib.check(self.L.pilot_ot_prepass_dev(self.h, _lib.iptr(cc), _lib.iptr(sc), n_total, int(n_samples), int(n_types),
-                                               float(regulizer), int(bool(normalization)), _lib.dptr(P),
-                                               first.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.dptr(cen)))
+                                               float(regulizer), int(bool(normalization)), _lib.dptr(P), _lib.lptr(first),
+                                               _lib.dptr(cen)))
         return P, first, cen
 
     def close(self):
@@ -228,26 +251,12 @@ class EmbeddingUpload:
             self.L.pilot_ot_embedding_destroy(self.h)
             self.h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def centroid_medians(X, cell_code, n_types):
     """K x D per-cell-type column-wise medians of the C x D embedding (device radix select; replaces
     ``data[annot.cell_type == k].median(axis=0)``, pilotpy/tools/Trajectory.py:465-466).  float32 / float64 input is
     processed in its own dtype, like pandas."""
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise ValueError("X must be 2-D (cells, dims)")
-    if X.dtype == np.float32:
-        dt = 0
-    else:
-        X = X.astype(np.float64, copy=False)
-        dt = 1
-    X = np.ascontiguousarray(X)
+    X, dt = _embedding_arg(X)
     cc = np.ascontiguousarray(cell_code, dtype=np.int32)
     if cc.shape != (X.shape[0],):
         raise ValueError("cell_code must have one entry per row of X")
@@ -267,7 +276,7 @@ def _cell_inputs(X, offsets):
     return X, offsets
 
 
-class CellCohort:
+class CellCohort(_Closing):
     """Device-resident cell clouds for the cell-level W2 extension (``pilot_ot_cell_cohort_*``): the cells stay in HBM as
     fp16 / bf16 operand pieces across calls, a call moves only result rows."""
 
@@ -306,12 +315,6 @@ class CellCohort:
             self.L.pilot_ot_cell_cohort_destroy(self.h)
             self.h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def cell_w2_grid(X, offsets, scale, reg, num_iter_max=1000, stop_thr=1e-9, check_period=10, f32_floor_ulps=0.0,
                  row_begin=0, row_end=None, row_step=1, return_info=False, devices=None):
@@ -343,7 +346,7 @@ def cell_w2_grid(X, offsets, scale, reg, num_iter_max=1000, stop_thr=1e-9, check
         co.close()
 
 
-class DevicePlan:
+class DevicePlan(_Closing):
     """Device-resident pair-grid problem: P, M and the outputs live in HBM across calls.
 
     Used by ``bench.py`` (inputs resident before the timed region) and by the multi-GPU driver.
@@ -352,9 +355,7 @@ class DevicePlan:
     """
 
     def __init__(self, P, M, n_rows_max=None):
-        P = _as_f64(P, "P")
-        M = _as_f64(M, "M")
-        self.N, self.K = P.shape
+        P, M, self.N, self.K = _pair_inputs(P, M)
         self.sym = int(np.array_equal(M, M.T))
         self.L = _lib.load()
         self._bufs = []
@@ -368,20 +369,8 @@ class DevicePlan:
         _lib.check(self.L.pilot_ot_plan_set_max_cost(self.plan, self.max_cost))
         self.n_rows_max = self.N if n_rows_max is None else n_rows_max
         n_out = self.n_rows_max * self.N
-        self.dP = self._alloc(P.nbytes)
-        self.dM = self._alloc(M.nbytes)
-        self.dE = self._alloc(8 * n_out)
-        self.dErr = self._alloc(8 * n_out)
-        self.dIt = self._alloc(4 * n_out)
-        self.dFl = self._alloc(4 * n_out)
-        _lib.check(self.L.pilot_ot_memcpy_h2d(self.dP, P.ctypes.data, P.nbytes))
-        _lib.check(self.L.pilot_ot_memcpy_h2d(self.dM, M.ctypes.data, M.nbytes))
-
-    def _alloc(self, nbytes):
-        p = ctypes.c_void_p()
-        _lib.check(self.L.pilot_ot_dev_alloc(ctypes.byref(p), int(nbytes)))
-        self._bufs.append(p)
-        return p
+        self._bufs = [_DeviceBuffer.holding(P), _DeviceBuffer.holding(M)] + [_DeviceBuffer(b * n_out) for b in (8, 8, 4, 4)]
+        self.dP, self.dM, self.dE, self.dErr, self.dIt, self.dFl = (buf.ptr for buf in self._bufs)
 
     def run(self, reg, row_begin=0, row_end=None, row_step=1, precision="auto", num_iter_max=NUM_ITER_MAX,
             stop_thr=STOP_THR, tau=TAU, check_period=CHECK_PERIOD, f32_floor_ulps=0.0, stream=None,
@@ -424,30 +413,19 @@ class DevicePlan:
 
     def fetch(self, n_rows=None):
         n_rows = self.n_rows_max if n_rows is None else n_rows
-        n = n_rows * self.N
-        emd = np.empty((n_rows, self.N), dtype=np.float64)
-        iters = np.empty((n_rows, self.N), dtype=np.int32)
-        err = np.empty((n_rows, self.N), dtype=np.float64)
-        flags = np.empty((n_rows, self.N), dtype=np.int32)
-        _lib.check(self.L.pilot_ot_memcpy_d2h(emd.ctypes.data, self.dE, 8 * n))
-        _lib.check(self.L.pilot_ot_memcpy_d2h(iters.ctypes.data, self.dIt, 4 * n))
-        _lib.check(self.L.pilot_ot_memcpy_d2h(err.ctypes.data, self.dErr, 8 * n))
-        _lib.check(self.L.pilot_ot_memcpy_d2h(flags.ctypes.data, self.dFl, 4 * n))
-        return emd, dict(iters=iters, err=err, flags=flags)
+
+        def rows(ptr, dtype):
+            return download(DeviceMatrix(ptr, self.N, shape=(n_rows, self.N), dtype=dtype))
+        return rows(self.dE, np.float64), dict(iters=rows(self.dIt, np.int32), err=rows(self.dErr, np.float64),
+                                               flags=rows(self.dFl, np.int32))
 
     def close(self):
-        for p in self._bufs:
-            self.L.pilot_ot_dev_free(p)
+        for buf in self._bufs:
+            buf.free()
         self._bufs = []
         if self.plan:
             self.L.pilot_ot_plan_destroy(self.plan)
             self.plan = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def equal_masses(P, rtol=1e-12):
@@ -466,11 +444,7 @@ def emd_grid(P, M, row_begin=0, row_end=None, row_step=1, mode="auto", return_in
     when M is exactly symmetric, all histograms carry the same mass (see equal_masses) and the full grid is requested,
     else "all".
     """
-    P = _as_f64(P, "P")
-    M = _as_f64(M, "M")
-    if P.ndim != 2 or M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] != P.shape[1]:
-        raise ValueError("shape mismatch: P %s, M %s" % (P.shape, M.shape))
-    N, K = P.shape
+    P, M, N, K = _pair_inputs(P, M)
     row_end = N if row_end is None else int(row_end)
     full = (row_begin == 0 and row_end == N and row_step == 1)
     if mode == "auto":
@@ -505,11 +479,7 @@ def transport_plans(P, M, pairs, regularized="unreg", reg=0.1, groups=None, retu
     (n, K, K).  ``return_info`` adds a dict: values (<M, Gamma> per pair, what the pair grid returns), iters (exact:
     augmentations; entropic: iterations) and flags (entropic: the PILOT_OT_FLAG_* bits of the grid; exact: 0).
     """
-    P = _as_f64(P, "P")
-    M = _as_f64(M, "M")
-    if P.ndim != 2 or M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] != P.shape[1]:
-        raise ValueError("shape mismatch: P %s, M %s" % (P.shape, M.shape))
-    N, K = P.shape
+    P, M, N, K = _pair_inputs(P, M)
     pairs = np.asarray(pairs)
     if pairs.size == 0:
         pairs = pairs.reshape(0, 2)
@@ -552,9 +522,7 @@ def row_distances(E, metric="euclidean", normalize_by_max=False):
     """Distances between the ROWS of the N x N matrix E (of E / E.max() with ``normalize_by_max``) on the device: the points
     pilotpy's diffusion map (pilotpy/plot/ploting.py:95-110) and silhouette scores (pilotpy/tools/Trajectory.py:592-612)
     work with.  metric: "euclidean" (scipy cdist) or "cosine" (sklearn cosine_distances)."""
-    E = _as_f64(E, "E")
-    if E.ndim != 2 or E.shape[0] != E.shape[1]:
-        raise ValueError("E must be square, got %s" % (E.shape,))
+    E = _square(_as_f64(E, "E"), "E")
     if metric not in _lib.ROW_METRICS:
         raise NotImplementedError("row metric %r: the device kernel implements %s" % (metric, sorted(_lib.ROW_METRICS)))
     D = np.empty_like(E)
@@ -565,16 +533,11 @@ def row_distances(E, metric="euclidean", normalize_by_max=False):
 
 def silhouette_precomputed(D, labels, return_samples=False):
     """``sklearn.metrics.silhouette_score(D, labels, metric="precomputed")`` on the device (labels of any hashable type)."""
-    D = _as_f64(D, "D")
-    if D.ndim != 2 or D.shape[0] != D.shape[1]:
-        raise ValueError("D must be square, got %s" % (D.shape,))
-    uniq, codes = np.unique(np.asarray(labels), return_inverse=True)
-    if codes.shape != (D.shape[0],):
-        raise ValueError("one label per sample expected")
-    codes = np.ascontiguousarray(codes, dtype=np.int32)
+    D = _square(_as_f64(D, "D"), "D")
+    codes, n_clusters = _label_codes(labels, D.shape[0])
     score = ctypes.c_double(0.0)
     samples = np.empty(D.shape[0], dtype=np.float64)
-    _lib.check(_lib.load().pilot_ot_silhouette(_lib.dptr(D), _lib.iptr(codes), D.shape[0], len(uniq), ctypes.byref(score),
+    _lib.check(_lib.load().pilot_ot_silhouette(_lib.dptr(D), _lib.iptr(codes), D.shape[0], n_clusters, ctypes.byref(score),
                                                _lib.dptr(samples)))
     return (score.value, samples) if return_samples else score.value
 
@@ -586,15 +549,45 @@ def _label_codes(labels, n):
     return np.ascontiguousarray(codes, dtype=np.int32), len(uniq)
 
 
-def _matrix_arg(E):
-    """(pointer, is_device, N) of a square matrix given as a numpy array or as a device-resident result (DeviceMatrix)."""
+_Dense = collections.namedtuple("_Dense", "ptr on_dev rows cols ld dtype keep")
+
+
+def _dense_arg(Y, name, dtypes=(np.float32, np.float64), mode="packed", axes=""):
+    """The one place a matrix argument becomes ABI arguments: pointer, is_device, rows, columns, leading dimension, dtype and
+    what keeps the pointer valid, of a 2-D numpy array or :class:`DeviceMatrix` of one of ``dtypes``.  A host array of another
+    dtype is converted to float64; then ``mode="packed"`` passes it C-contiguous and ``"strided"`` leaves a view with a unit
+    column stride and a row stride of whole items as it is, with its own ``ld``.  ``"strict"`` converts and copies nothing:
+    anything but a C-contiguous ndarray of ``dtypes`` is refused, and :func:`device_columns` of a DeviceMatrix is taken too."""
+    kinds = " / ".join(np.dtype(d).name for d in dtypes)
+    if isinstance(Y, (DeviceMatrix, _DeviceColumns) if mode == "strict" else DeviceMatrix):
+        if len(Y.shape) != 2 or Y.dtype not in dtypes:
+            raise ValueError("%s: a 2-D %s DeviceMatrix, got %s %s" % (name, kinds, Y.shape, Y.dtype))
+        return _Dense(ctypes.c_void_p(Y.ptr), 1, Y.shape[0], Y.shape[1], getattr(Y, "ld", Y.shape[1]), Y.dtype, Y)
+    if mode == "strict":
+        if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.dtype not in dtypes:
+            raise ValueError("%s: a 2-D %s numpy array or a DeviceMatrix, got %s %s"
+                             % (name, kinds, getattr(Y, "shape", type(Y).__name__), getattr(Y, "dtype", "")))
+        if not Y.flags.c_contiguous:
+            raise ValueError("%s must be C-contiguous (np.ascontiguousarray), got strides %s" % (name, Y.strides))
+    else:
+        Y = np.asarray(Y)
+        if Y.ndim != 2:
+            raise ValueError("%s must be 2-D%s, got %s" % (name, axes, Y.shape))
+        if Y.dtype not in dtypes:
+            Y = Y.astype(np.float64)
+        if mode != "strided" or Y.strides[1] != Y.itemsize or Y.strides[0] % Y.itemsize or Y.strides[0] < 0:
+            Y = np.ascontiguousarray(Y)
+    ld = Y.strides[0] // Y.itemsize if mode == "strided" and Y.shape[0] > 1 else Y.shape[1]
+    return _Dense(ctypes.c_void_p(Y.ctypes.data), 0, Y.shape[0], Y.shape[1], ld, Y.dtype, Y)
+
+
+def _matrix_arg(E, name="E"):
+    """:func:`_dense_arg` of a square float64 matrix: a finite numpy array or a device-resident result (DeviceMatrix)"""
     if isinstance(E, DeviceMatrix):
-        _square_f64(E, "E")
-        return ctypes.c_void_p(E.ptr), 1, E.N, None
-    E = _as_f64(E, "E")
-    if E.ndim != 2 or E.shape[0] != E.shape[1]:
-        raise ValueError("E must be square, got %s" % (E.shape,))
-    return ctypes.c_void_p(E.ctypes.data), 0, E.shape[0], E
+        _square_f64(E, name)
+    else:
+        E = _square(_as_f64(E, name), name)
+    return _dense_arg(E, name, (np.float64,))
 
 
 def _square_f64(D, name):
@@ -620,36 +613,45 @@ class DeviceMatrix:
         A = np.asarray(A)
         if A.ndim != 2 or A.dtype not in (np.float32, np.float64):
             raise ValueError("upload: a 2-D float32 / float64 array, got %s %s" % (A.shape, A.dtype))
-        A = np.ascontiguousarray(A)
-        buf = _DeviceBuffer(A.nbytes)
-        _lib.check(_lib.load().pilot_ot_memcpy_h2d(buf.ptr, A.ctypes.data, A.nbytes))
+        buf = _DeviceBuffer.holding(A)
         return cls(buf.ptr, A.shape[0], owner=buf, shape=A.shape, dtype=A.dtype)
 
 
-class _DeviceBuffer:
-    """One pilot_ot_dev_alloc allocation, released when the object goes."""
+class _DeviceBuffer(_Closing):
+    """The owner of a pilot_ot_dev_alloc allocation, released by :meth:`free` or when the object goes."""
 
     def __init__(self, nbytes):
         self.ptr = ctypes.c_void_p()
         _lib.check(_lib.load().pilot_ot_dev_alloc(ctypes.byref(self.ptr), max(int(nbytes), 1)))
 
-    def __del__(self):
+    @classmethod
+    def holding(cls, A):
+        """a buffer that holds the bytes of the array A (made C-contiguous): this module's host-to-device copy"""
+        A = np.ascontiguousarray(A)
+        buf = cls(A.nbytes)
+        _lib.check(_lib.load().pilot_ot_memcpy_h2d(buf.ptr, A.ctypes.data, A.nbytes))
+        return buf
+
+    def free(self):
         if self.ptr:
             _lib.load().pilot_ot_dev_free(self.ptr)
             self.ptr = ctypes.c_void_p()
+
+    close = free
 
 
 def silhouette_of_rows(E, labels, metric="cosine", normalize_by_max=False, return_samples=False):
     """``sklearn.metrics.silhouette_score(E, labels, metric=metric)`` with the ROWS of E as the points -- what
     ``Sil_computing`` does (pilotpy/tools/Trajectory.py:592-612): row distances and silhouette chained on the device, only the
     N per-sample scores come back.  E: numpy array or :class:`DeviceMatrix`."""
-    ptr, on_dev, N, keep = _matrix_arg(E)
+    E = _matrix_arg(E)
+    N = E.rows
     if metric not in _lib.ROW_METRICS:
         raise NotImplementedError("row metric %r: the device kernel implements %s" % (metric, sorted(_lib.ROW_METRICS)))
     codes, n_clusters = _label_codes(labels, N)
     score = ctypes.c_double(0.0)
     samples = np.empty(N, dtype=np.float64)
-    _lib.check(_lib.load().pilot_ot_silhouette_of_rows(ptr, on_dev, N, int(bool(normalize_by_max)), _lib.ROW_METRICS[metric],
+    _lib.check(_lib.load().pilot_ot_silhouette_of_rows(E.ptr, E.on_dev, N, int(bool(normalize_by_max)), _lib.ROW_METRICS[metric],
                                                        _lib.iptr(codes), n_clusters, ctypes.byref(score), _lib.dptr(samples)))
     return (score.value, samples) if return_samples else score.value
 
@@ -657,10 +659,11 @@ def silhouette_of_rows(E, labels, metric="cosine", normalize_by_max=False, retur
 def diffusion_kernel_of_rows(E, k=64, epsilon=1.0, return_distances=True):
     """The dense part of ``pl.trajectory`` (pilotpy/plot/ploting.py:95-110) chained on the device: E / E.max() -> Euclidean row
     distances -> pydiffmap's k-nearest-neighbour Gaussian kernel.  Returns ``(D, Kmat)`` (``D`` None unless asked for)."""
-    ptr, on_dev, N, keep = _matrix_arg(E)
+    E = _matrix_arg(E)
+    N = E.rows
     D = np.empty((N, N), dtype=np.float64) if return_distances else None
     Kmat = np.empty((N, N), dtype=np.float64)
-    _lib.check(_lib.load().pilot_ot_diffusion_kernel_of_rows(ptr, on_dev, N, int(k), float(epsilon),
+    _lib.check(_lib.load().pilot_ot_diffusion_kernel_of_rows(E.ptr, E.on_dev, N, int(k), float(epsilon),
                                                              _lib.dptr(D) if D is not None else None, _lib.dptr(Kmat)))
     return D, Kmat
 
@@ -668,9 +671,7 @@ def diffusion_kernel_of_rows(E, k=64, epsilon=1.0, return_distances=True):
 def knn_gaussian_kernel(D, k=64, epsilon=1.0):
     """Kernel matrix of pydiffmap's ``DiffusionMap.from_sklearn(epsilon=, k=)`` from row distances D: exp(-d^2 / (4 eps)) on
     every row's k nearest rows (itself included), 0 elsewhere (pilotpy/plot/ploting.py:109-110)."""
-    D = _as_f64(D, "D")
-    if D.ndim != 2 or D.shape[0] != D.shape[1]:
-        raise ValueError("D must be square, got %s" % (D.shape,))
+    D = _square(_as_f64(D, "D"), "D")
     Kmat = np.empty_like(D)
     _lib.check(_lib.load().pilot_ot_knn_kernel(_lib.dptr(D), D.shape[0], int(k), float(epsilon), _lib.dptr(Kmat)))
     return Kmat
@@ -715,13 +716,14 @@ def diffusion_map_of_rows(E, n_evecs=2, epsilon=1.0, alpha=0.5, k=64, return_inf
     of (P - I) / epsilon, descending, the trivial 0 dropped).  A repeated eigenvalue 1 (disconnected graph) or no convergence
     raises ValueError; with ``return_info`` nothing is raised and a fourth item, ``dict(steps, flags, converged, degenerate)``,
     tells."""
-    ptr, on_dev, N, keep = _matrix_arg(E)
+    E = _matrix_arg(E)
+    N = E.rows
     n_evecs, epsilon, alpha = _diffmap_check(N, n_evecs, epsilon, alpha)
     dmap = np.empty((N, n_evecs), dtype=np.float64)
     evecs = np.empty((N, n_evecs), dtype=np.float64)
     evals = np.empty(n_evecs, dtype=np.float64)
     info = np.zeros(2, dtype=np.int32)
-    _lib.check(_lib.load().pilot_ot_diffusion_map_of_rows(ptr, on_dev, N, int(k), epsilon, float(alpha), n_evecs, _lib.dptr(dmap),
+    _lib.check(_lib.load().pilot_ot_diffusion_map_of_rows(E.ptr, E.on_dev, N, int(k), epsilon, float(alpha), n_evecs, _lib.dptr(dmap),
                                                           _lib.dptr(evecs), _lib.dptr(evals), _lib.iptr(info)))
     return _diffmap_result(dmap, evecs, evals, info, return_info)
 
@@ -730,42 +732,24 @@ def diffusion_map_from_kernel(Kmat, n_evecs=2, epsilon=1.0, alpha=0.5, return_in
     """The eigen-part of the diffusion map from a non-negative N x N kernel matrix (numpy array or :class:`DeviceMatrix`), e.g.
     :func:`knn_gaussian_kernel`'s: symmetrised max(K, K^T), alpha-normalised, Lanczos on the device.  Same returns as
     :func:`diffusion_map_of_rows`."""
-    on_dev = isinstance(Kmat, DeviceMatrix)
-    if on_dev:
-        _square_f64(Kmat, "Kmat")
-    N = Kmat.N if on_dev else np.asarray(Kmat).shape[0]
-    if not on_dev:
-        Kmat = _as_f64(Kmat, "Kmat")
-        if Kmat.ndim != 2 or Kmat.shape[0] != Kmat.shape[1]:
-            raise ValueError("Kmat must be square, got %s" % (Kmat.shape,))
+    K = _matrix_arg(Kmat, "Kmat")
+    N = K.rows
     n_evecs, epsilon, alpha = _diffmap_check(N, n_evecs, epsilon, alpha)
-    L = _lib.load()
+    info = np.zeros(2, dtype=np.int32)
     bufs = []
-
-    def alloc(nbytes):
-        p = ctypes.c_void_p()
-        _lib.check(L.pilot_ot_dev_alloc(ctypes.byref(p), int(nbytes)))
-        bufs.append(p)
-        return p
-
     try:
-        if on_dev:
-            dK = ctypes.c_void_p(Kmat.ptr)
-        else:
-            dK = alloc(Kmat.nbytes)
-            _lib.check(L.pilot_ot_memcpy_h2d(dK, Kmat.ctypes.data, Kmat.nbytes))
-        dmap = np.empty((N, n_evecs), dtype=np.float64)
-        evecs = np.empty((N, n_evecs), dtype=np.float64)
-        evals = np.empty(n_evecs, dtype=np.float64)
-        info = np.zeros(2, dtype=np.int32)
-        d_dmap, d_evecs, d_evals = alloc(dmap.nbytes), alloc(evecs.nbytes), alloc(evals.nbytes)
-        _lib.check(L.pilot_ot_diffusion_map_dev(dK, N, epsilon, alpha, n_evecs, d_dmap, d_evecs, d_evals, _lib.iptr(info), None))
-        _lib.check(L.pilot_ot_memcpy_d2h(dmap.ctypes.data, d_dmap, dmap.nbytes))
-        _lib.check(L.pilot_ot_memcpy_d2h(evecs.ctypes.data, d_evecs, evecs.nbytes))
-        _lib.check(L.pilot_ot_memcpy_d2h(evals.ctypes.data, d_evals, evals.nbytes))
+        dK = K.ptr
+        if not K.on_dev:
+            bufs.append(_DeviceBuffer.holding(K.keep))
+            dK = bufs[0].ptr
+        out = [_device_result(N, n_evecs), _device_result(N, n_evecs), _device_result(1, n_evecs)]
+        bufs += [D.owner for D in out]
+        _lib.check(_lib.load().pilot_ot_diffusion_map_dev(dK, N, epsilon, alpha, n_evecs, *(ctypes.c_void_p(D.ptr) for D in out),
+                                                          _lib.iptr(info), None))
+        dmap, evecs, evals = download(out[0]), download(out[1]), download(out[2])[0]
     finally:
-        for p in bufs:
-            L.pilot_ot_dev_free(p)
+        for buf in bufs:
+            buf.free()
     return _diffmap_result(dmap, evecs, evals, info, return_info)
 
 
@@ -787,22 +771,8 @@ def trajectory_fits(Y, x, model="ols", epsilon=1.35, pval_thr=0.05, modify_r2=Fa
     if model not in ("ols", "huber"):
         raise ValueError("model=%r must be 'ols' or 'huber'" % (model,))
     x = _as_f64(np.ravel(x), "x")
-    if isinstance(Y, DeviceMatrix):
-        if len(Y.shape) != 2 or Y.dtype not in (np.float32, np.float64):
-            raise ValueError("Y: a 2-D float32 / float64 DeviceMatrix, got %s %s" % (Y.shape, Y.dtype))
-        n, T = Y.shape
-        ptr, on_dev, ld, dtype, keep = ctypes.c_void_p(Y.ptr), 1, T, Y.dtype, None
-    else:
-        Y = np.asarray(Y)
-        if Y.ndim != 2:
-            raise ValueError("Y must be 2-D (observations x targets), got %s" % (Y.shape,))
-        if Y.dtype not in (np.float32, np.float64):
-            Y = Y.astype(np.float64)
-        if Y.strides[1] != Y.itemsize or Y.strides[0] % Y.itemsize or Y.strides[0] < 0:
-            Y = np.ascontiguousarray(Y)
-        n, T = Y.shape
-        ld = Y.strides[0] // Y.itemsize if n > 1 else T
-        ptr, on_dev, dtype, keep = ctypes.c_void_p(Y.ctypes.data), 0, Y.dtype, Y
+    Y = _dense_arg(Y, "Y", mode="strided", axes=" (observations x targets)")
+    n, T = Y.rows, Y.cols
     if x.size != n:
         raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
     fits = dict(params=np.empty((T, 3, 3)), pvalues=np.empty((T, 3, 3)), rsquared_adj=np.empty((T, 3)),
@@ -816,10 +786,9 @@ def trajectory_fits(Y, x, model="ols", epsilon=1.35, pval_thr=0.05, modify_r2=Fa
         setattr(out, name, arr.ctypes.data_as(ctypes.POINTER(ct)))
     nnc = ctypes.c_int(0)
     _lib.check(_lib.load().pilot_ot_trajectory_fits(
-        ptr, on_dev, 0 if dtype == np.float32 else 1, n, T, ld, _lib.dptr(x),
+        Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), n, T, Y.ld, _lib.dptr(x),
         _lib.TRAJFIT_HUBER if model == "huber" else _lib.TRAJFIT_OLS, float(epsilon), float(pval_thr), int(bool(modify_r2)),
         ctypes.byref(out), ctypes.byref(nnc)))
-    del keep
     if return_info:
         info["not_converged"] = nnc.value
         return fits, info
@@ -836,22 +805,8 @@ def bootstrap_huber_fits(Y, x, cols, models, idx, epsilon=1.35, return_info=Fals
     two-coefficient models); with ``return_info`` also a dict of ``sigma``, ``steps``, ``flags`` (problems x B) and
     ``not_converged`` (the count flagged ``_lib.TRAJFIT_NOT_CONVERGED``)."""
     x = _as_f64(np.ravel(x), "x")
-    if isinstance(Y, DeviceMatrix):
-        if len(Y.shape) != 2 or Y.dtype not in (np.float32, np.float64):
-            raise ValueError("Y: a 2-D float32 / float64 DeviceMatrix, got %s %s" % (Y.shape, Y.dtype))
-        n, T = Y.shape
-        ptr, on_dev, ld, dtype, keep = ctypes.c_void_p(Y.ptr), 1, T, Y.dtype, None
-    else:
-        Y = np.asarray(Y)
-        if Y.ndim != 2:
-            raise ValueError("Y must be 2-D (observations x targets), got %s" % (Y.shape,))
-        if Y.dtype not in (np.float32, np.float64):
-            Y = Y.astype(np.float64)
-        if Y.strides[1] != Y.itemsize or Y.strides[0] % Y.itemsize or Y.strides[0] < 0:
-            Y = np.ascontiguousarray(Y)
-        n, T = Y.shape
-        ld = Y.strides[0] // Y.itemsize if n > 1 else T
-        ptr, on_dev, dtype, keep = ctypes.c_void_p(Y.ctypes.data), 0, Y.dtype, Y
+    Y = _dense_arg(Y, "Y", mode="strided", axes=" (observations x targets)")
+    n, T = Y.rows, Y.cols
     if x.size != n:
         raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
     cols = np.ascontiguousarray(np.ravel(cols), dtype=np.int32)
@@ -867,10 +822,9 @@ def bootstrap_huber_fits(Y, x, cols, models, idx, epsilon=1.35, return_info=Fals
     info = dict(sigma=np.empty((P, B)), steps=np.empty((P, B), dtype=np.int32), flags=np.empty((P, B), dtype=np.int32))
     nnc = ctypes.c_int(0)
     _lib.check(_lib.load().pilot_ot_bootstrap_huber_fits(
-        ptr, on_dev, 0 if dtype == np.float32 else 1, n, T, ld, _lib.dptr(x), P, _lib.iptr(cols), _lib.iptr(models), B,
+        Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), n, T, Y.ld, _lib.dptr(x), P, _lib.iptr(cols), _lib.iptr(models), B,
         _lib.iptr(idx), float(epsilon), _lib.dptr(params), _lib.dptr(info["sigma"]), _lib.iptr(info["steps"]),
         _lib.iptr(info["flags"]), ctypes.byref(nnc)))
-    del keep
     if return_info:
         info["not_converged"] = nnc.value
         return params, info
@@ -880,21 +834,6 @@ def bootstrap_huber_fits(Y, x, cols, models, idx, epsilon=1.35, return_info=Fals
 # ---- gene curve clustering (K11; pilotpy's genes_selection_analysis, plot/gene_selection_analysis.py) ------------------------
 LINKAGE_METHODS = tuple(_lib.LINKAGE_METHODS)
 _LINKAGE_UNSUPPORTED = ("centroid", "median", "ward")
-
-
-def _dense_arg(Y, name, dtypes=(np.float32, np.float64)):
-    """(pointer, is_device, rows, columns, leading dimension, dtype, keep-alive) of a 2-D matrix: numpy array or DeviceMatrix"""
-    if isinstance(Y, DeviceMatrix):
-        if len(Y.shape) != 2 or Y.dtype not in dtypes:
-            raise ValueError("%s: a 2-D %s DeviceMatrix, got %s %s" % (name, " / ".join(np.dtype(d).name for d in dtypes), Y.shape, Y.dtype))
-        return ctypes.c_void_p(Y.ptr), 1, Y.shape[0], Y.shape[1], Y.shape[1], Y.dtype, Y
-    Y = np.asarray(Y)
-    if Y.ndim != 2:
-        raise ValueError("%s must be 2-D, got %s" % (name, Y.shape))
-    if Y.dtype not in dtypes:
-        Y = Y.astype(np.float64)
-    Y = np.ascontiguousarray(Y)
-    return ctypes.c_void_p(Y.ctypes.data), 0, Y.shape[0], Y.shape[1], Y.shape[1], Y.dtype, Y
 
 
 def _device_result(rows, cols):
@@ -915,7 +854,8 @@ def segment_std(Y, offsets, cols=None, device=False):
     (rows x columns, float32 / float64, numpy array or :class:`DeviceMatrix`) over each contiguous row segment
     ``offsets[s]:offsets[s + 1]``.  Returns segments x columns float64 (a :class:`DeviceMatrix` with ``device=True``); a segment
     of one row gives NaN.  Two passes in f64 (mean, then squared deviations), sums in a fixed order."""
-    ptr, on_dev, n, n_cols, ld, dtype, keep = _dense_arg(Y, "Y")
+    Y = _dense_arg(Y, "Y")
+    n_cols = Y.cols
     offsets = np.ascontiguousarray(np.ravel(offsets), dtype=np.int64)
     if offsets.size < 1:
         raise ValueError("offsets needs at least one entry")
@@ -925,9 +865,8 @@ def segment_std(Y, offsets, cols=None, device=False):
     n_sel = n_cols if cols is None else cols.size
     out = _device_result(S, n_sel) if device else np.empty((S, n_sel), dtype=np.float64)
     _lib.check(_lib.load().pilot_ot_segment_std(
-        ptr, on_dev, 0 if dtype == np.float32 else 1, n, n_cols, ld, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), S,
+        Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_cols, Y.ld, _lib.lptr(offsets), S,
         None if cols is None else _lib.iptr(cols), n_sel, ctypes.c_void_p(out.ptr if device else out.ctypes.data), int(device)))
-    del keep
     return out
 
 
@@ -981,7 +920,7 @@ def _moment_args(n, n_total, codes, n_groups, transform, cols):
     return codes, n_groups, cols
 
 
-class DeviceCSR:
+class DeviceCSR(_Closing):
     """K13: a sparse rows x columns matrix resident in HBM as CSR (include/pilot_ot.h, "sparse matrices"): what ``adata.X`` is in
     real scRNA-seq data.  Made by :meth:`upload`; the dense matrix is never formed unless :meth:`densify` is asked for some
     columns.  ``shape``, ``dtype`` (float32 / float64) and ``nnz`` (stored entries) describe it.  The column-major copy the
@@ -1019,8 +958,8 @@ class DeviceCSR:
         indices = np.ascontiguousarray(X.indices, dtype=np.int32)
         h = ctypes.c_void_p()
         _lib.check(_lib.load().pilot_ot_csr_upload(
-            indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.iptr(indices), ctypes.c_void_p(data.ctypes.data),
-            0 if data.dtype == np.float32 else 1, X.shape[0], X.shape[1], ctypes.byref(h)))
+            _lib.lptr(indptr), _lib.iptr(indices), ctypes.c_void_p(data.ctypes.data), _lib.dtype_code(data.dtype), X.shape[0], X.shape[1],
+            ctypes.byref(h)))
         return cls(h, X.shape, data.dtype, indices.size)
 
     def _handle(self):
@@ -1043,7 +982,7 @@ class DeviceCSR:
     def column_nnz(self):
         """int64 per column: the stored values that are != 0 (``(dense != 0).sum(0)``)."""
         out = np.empty(self.shape[1], dtype=np.int64)
-        _lib.check(_lib.load().pilot_ot_csr_column_nnz(self._handle(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        _lib.check(_lib.load().pilot_ot_csr_column_nnz(self._handle(), _lib.lptr(out)))
         return out
 
     def group_moments(self, codes, n_groups, transform=None, cols=None):
@@ -1054,7 +993,7 @@ class DeviceCSR:
         mean, m2 = np.empty((n_groups, n_sel)), np.empty((n_groups, n_sel))
         _lib.check(_lib.load().pilot_ot_csr_group_moments(
             self._handle(), _lib.iptr(codes), n_groups, None if cols is None else _lib.iptr(cols), n_sel, _GM_TRANSFORMS[transform],
-            count.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.dptr(mean), _lib.dptr(m2)))
+            _lib.lptr(count), _lib.dptr(mean), _lib.dptr(m2)))
         return count, mean, m2
 
     def densify(self, cols=None):
@@ -1080,12 +1019,6 @@ class DeviceCSR:
             _lib.load().pilot_ot_csr_destroy(self.h)
             self.h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def csr_slice_rows():
     """Rows per slice of :class:`DeviceCSR`'s column-form build."""
@@ -1103,47 +1036,15 @@ def group_moments(Y, codes, n_groups, transform=None, cols=None):
     argument is checked before any device work (ValueError).  A :class:`DeviceCSR` is forwarded to its own method."""
     if isinstance(Y, DeviceCSR):
         return Y.group_moments(codes, n_groups, transform=transform, cols=cols)
-    if transform not in _GM_TRANSFORMS:
-        raise ValueError("transform=%r must be None or 'expm1'" % (transform,))
-    if isinstance(n_groups, bool) or int(n_groups) != n_groups or not 1 <= n_groups <= GROUP_MOMENTS_MAX_GROUPS:
-        raise ValueError("n_groups=%r must be an integer in 1..%d" % (n_groups, GROUP_MOMENTS_MAX_GROUPS))
-    n_groups = int(n_groups)
-    if isinstance(Y, (DeviceMatrix, _DeviceColumns)):
-        if len(Y.shape) != 2 or Y.dtype not in (np.float32, np.float64):
-            raise ValueError("Y: a 2-D float32 / float64 DeviceMatrix, got %s %s" % (Y.shape, Y.dtype))
-        ptr, on_dev, (n, n_total), dtype = ctypes.c_void_p(Y.ptr), 1, Y.shape, Y.dtype
-        ld = Y.ld if isinstance(Y, _DeviceColumns) else n_total
-    else:
-        if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.dtype not in (np.float32, np.float64):
-            raise ValueError("Y: a 2-D float32 / float64 numpy array or a DeviceMatrix, got %s %s"
-                             % (getattr(Y, "shape", type(Y).__name__), getattr(Y, "dtype", "")))
-        if not Y.flags.c_contiguous:
-            raise ValueError("Y must be C-contiguous (np.ascontiguousarray), got strides %s" % (Y.strides,))
-        ptr, on_dev, (n, n_total), dtype, ld = ctypes.c_void_p(Y.ctypes.data), 0, Y.shape, Y.dtype, Y.shape[1]
-    if n_total < 1:
-        raise ValueError("Y has no columns")
-    codes = np.asarray(codes)
-    if codes.ndim != 1 or codes.size != n:
-        raise ValueError("codes has shape %s for %d rows" % (codes.shape, n))
-    if codes.dtype.kind not in "iu":
-        raise ValueError("codes must be integers, got %s" % codes.dtype)
-    if n and int(codes.max()) >= n_groups:
-        raise ValueError("codes reach %d with n_groups=%d" % (int(codes.max()), n_groups))
-    codes = np.ascontiguousarray(np.maximum(codes, -1), dtype=np.int32)
-    if cols is not None:
-        cols = np.asarray(cols)
-        if cols.ndim != 1 or cols.dtype.kind not in "iu":
-            raise ValueError("cols: a 1-D array of column indices, got %s %s" % (cols.shape, cols.dtype))
-        if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= n_total):
-            raise ValueError("cols outside [0, %d)" % n_total)
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
+    Y = _dense_arg(Y, "Y", mode="strict")
+    n_total = Y.cols
+    codes, n_groups, cols = _moment_args(Y.rows, n_total, codes, n_groups, transform, cols)
     n_sel = n_total if cols is None else cols.size
     count = np.empty(n_groups, dtype=np.int64)
     mean, m2 = np.empty((n_groups, n_sel)), np.empty((n_groups, n_sel))
     _lib.check(_lib.load().pilot_ot_group_moments(
-        ptr, on_dev, 0 if dtype == np.float32 else 1, n, n_total, ld, _lib.iptr(codes), n_groups,
-        None if cols is None else _lib.iptr(cols), n_sel, _GM_TRANSFORMS[transform],
-        count.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), _lib.dptr(mean), _lib.dptr(m2)))
+        Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_total, Y.ld, _lib.iptr(codes), n_groups,
+        None if cols is None else _lib.iptr(cols), n_sel, _GM_TRANSFORMS[transform], _lib.lptr(count), _lib.dptr(mean), _lib.dptr(m2)))
     return count, mean, m2
 
 
@@ -1166,15 +1067,15 @@ def fitted_curves(params, model, times, noise=None, device=False):
     times = _as_f64(np.ravel(times), "times")
     T = times.size
     if noise is None:
-        sp, s_dev, keep = None, 0, None
+        sp, s_dev = None, 0
     else:
-        sp, s_dev, r, c, _, _, keep = _dense_arg(noise, "noise", (np.float64,))
-        if (r, c) != (T, G):
-            raise ValueError("noise must be T x G = %d x %d, got %d x %d" % (T, G, r, c))
+        noise = _dense_arg(noise, "noise", (np.float64,))
+        if (noise.rows, noise.cols) != (T, G):
+            raise ValueError("noise must be T x G = %d x %d, got %d x %d" % (T, G, noise.rows, noise.cols))
+        sp, s_dev = noise.ptr, noise.on_dev
     out = _device_result(G, T) if device else np.empty((G, T), dtype=np.float64)
     _lib.check(_lib.load().pilot_ot_fitted_curves(_lib.dptr(params), _lib.iptr(model), G, _lib.dptr(times), T, sp, s_dev,
                                                   ctypes.c_void_p(out.ptr if device else out.ctypes.data), int(device)))
-    del keep
     return out
 
 
@@ -1188,19 +1089,19 @@ def linkage_of_rows(Y, method="complete", return_info=False):
         raise NotImplementedError("linkage method %r needs centroids: only %s run on the device" % (method, ", ".join(LINKAGE_METHODS)))
     if method not in _lib.LINKAGE_METHODS:
         raise ValueError("Invalid method: %r" % (method,))
-    ptr, on_dev, G, T, _, _, keep = _dense_arg(Y, "Y", (np.float64,))
+    Y = _dense_arg(Y, "Y", (np.float64,))
+    G, T = Y.rows, Y.cols
     if G < 2:
         raise ValueError("The number of observations cannot be determined on an empty distance matrix.")
     if G > _lib.LINKAGE_MAX_G:
         raise ValueError("G=%d rows: the G x G float64 distance matrix would take %.1f GiB of HBM; at most %d rows"
                          % (G, G * G * 8 / 2.0 ** 30, _lib.LINKAGE_MAX_G))
-    if not on_dev and not np.all(np.isfinite(keep)):
+    if not Y.on_dev and not np.all(np.isfinite(Y.keep)):
         raise ValueError("Y contains NaN or inf")
     Z = np.empty((G - 1, 4), dtype=np.float64)
     dmax, steps = ctypes.c_double(0.0), ctypes.c_int(0)
-    _lib.check(_lib.load().pilot_ot_linkage_of_rows(ptr, on_dev, G, T, _lib.LINKAGE_METHODS[method], _lib.dptr(Z), ctypes.byref(dmax),
+    _lib.check(_lib.load().pilot_ot_linkage_of_rows(Y.ptr, Y.on_dev, G, T, _lib.LINKAGE_METHODS[method], _lib.dptr(Z), ctypes.byref(dmax),
                                                     ctypes.byref(steps)))
-    del keep
     if return_info:
         return Z, dmax.value, dict(chain_steps=steps.value)
     return Z, dmax.value
@@ -1261,10 +1162,10 @@ def curve_activities(curves, times):
     times = np.ascontiguousarray(np.ravel(times), dtype=np.float64)
     if times.size < 2 or not (times[1:] > times[:-1]).all():
         raise ValueError("times must be increasing and have at least 2 values.")
-    ptr, on_dev, G, T, _, _, keep = _dense_arg(curves, "curves", (np.float64,))
+    curves = _dense_arg(curves, "curves", (np.float64,))
+    G, T = curves.rows, curves.cols
     if T != times.size:
         raise ValueError("curves has %d columns for %d times" % (T, times.size))
     out = np.empty((G, 4), dtype=np.float64)
-    _lib.check(_lib.load().pilot_ot_curve_activities(ptr, on_dev, G, T, _lib.dptr(times), _lib.dptr(out)))
-    del keep
+    _lib.check(_lib.load().pilot_ot_curve_activities(curves.ptr, curves.on_dev, G, T, _lib.dptr(times), _lib.dptr(out)))
     return out

@@ -165,6 +165,22 @@ def test_repeated_calls_and_both_routes_give_identical_bits():
         assert a[3] == x[3]
 
 
+def test_from_kernel_host_and_device_routes_release_their_buffers():
+    """diffusion_map_from_kernel of a host kernel matrix (uploaded into a buffer of the call's own) and of a DeviceMatrix of it give
+    the same bits; so does a second call, which takes its device buffers anew after the first released them."""
+    rng = np.random.default_rng(6)
+    X = rng.standard_normal((6, 3))
+    Kmat = engine.knn_gaussian_kernel(cdist(X, X), k=4, epsilon=1.0)
+    first = engine.diffusion_map_from_kernel(Kmat, n_evecs=2, return_info=True)
+    dev = engine.diffusion_map_from_kernel(engine.DeviceMatrix.upload(Kmat), n_evecs=2, return_info=True)
+    again = engine.diffusion_map_from_kernel(Kmat, n_evecs=2, return_info=True)
+    assert first[0].shape == first[1].shape == (6, 2) and first[2].shape == (2,)
+    for other in (dev, again):
+        for u, v in zip(first[:3], other[:3]):
+            assert np.array_equal(np.ascontiguousarray(u).view(np.uint64), np.ascontiguousarray(v).view(np.uint64))
+        assert first[3] == other[3]
+
+
 def _two_clusters(n1=40, n2=30, seed=5):
     rng = np.random.default_rng(seed)
     X = np.r_[rng.random((n1, 2)), rng.random((n2, 2)) + 50.0]

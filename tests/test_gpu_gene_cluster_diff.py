@@ -83,6 +83,26 @@ def test_bootfit_bit_identical_routes():
         assert np.array_equal(a.view(np.uint64), other.view(np.uint64))
 
 
+def test_bootfit_host_view_gives_the_bits_of_its_copy():
+    """a row-strided host view (its own leading dimension, copied packed by the library), its contiguous copy and an upload of
+    that copy: the kernel reads the same values each time"""
+    rng = np.random.default_rng(10)
+    Y, x, cols, models, idx = _problem(rng, 10, 3, np.float64, n_cols=7, models=(0, 1, 2, 1))
+    W = rng.standard_normal((10, 12))
+    W[:, 2:9] = Y
+    view = W[:, 2:9]
+    assert not view.flags.c_contiguous and engine._dense_arg(view, "Y", mode="strided").ld == 12
+    copy = np.ascontiguousarray(view)
+    a, ia = engine.bootstrap_huber_fits(view, x, cols, models, idx, return_info=True)
+    b, ib = engine.bootstrap_huber_fits(copy, x, cols, models, idx, return_info=True)
+    c, ic = engine.bootstrap_huber_fits(engine.DeviceMatrix.upload(copy), x, cols, models, idx, return_info=True)
+    assert a.shape == (4, 3, 3) and np.isfinite(a[:, :, :2]).all()
+    for other, info in ((b, ib), (c, ic)):
+        assert np.array_equal(a.view(np.uint64), other.view(np.uint64))
+        assert np.array_equal(ia["sigma"].view(np.uint64), info["sigma"].view(np.uint64))
+        assert np.array_equal(ia["steps"], info["steps"]) and np.array_equal(ia["flags"], info["flags"])
+
+
 def test_bootfit_not_converged_flag():
     rng = np.random.default_rng(3)
     Y, x, cols, models, idx = _problem(rng, 40, 8, np.float64)

@@ -80,6 +80,21 @@ def test_segment_std_against_groupby(dtype, n_cells, T, n_genes):
     assert _same(part, got[3:7])
 
 
+def test_segment_std_host_rows_from_an_offset():
+    """segments that start at row 3 with a column selection: the host route copies rows 3..10 only and shifts the offsets, the
+    DeviceMatrix route reads them in place -- the same bits, NaN for the one-row segment in both"""
+    rng = np.random.default_rng(3)
+    Y = rng.standard_normal((12, 9)).astype(np.float32)
+    offsets, cols = [3, 5, 6, 11], [8, 0, 4]
+    host = engine.segment_std(Y, offsets, cols=cols)
+    dev = engine.segment_std(engine.DeviceMatrix.upload(Y), offsets, cols=cols)
+    assert host.shape == (3, 3) and _same(host, dev)
+    assert np.isnan(host[1]).all() and np.isfinite(host[[0, 2]]).all()
+    want = np.stack([Y[3:5].astype(np.float64).std(axis=0, ddof=1), Y[6:11].astype(np.float64).std(axis=0, ddof=1)])[:, cols]
+    assert np.abs(host[[0, 2]] - want).max() <= 1e-12
+    assert _same(engine.download(engine.segment_std(Y, offsets, cols=cols, device=True)), host)
+
+
 # ---- curves ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("G,T", [(1, 2), (50, 24), (2000, 120), (4000, 300)])
 def test_fitted_curves_against_standard_scaler(G, T):

@@ -744,3 +744,21 @@ def test_diagonal_of_a_large_grid_stays_in_the_tiles_and_row_shards_agree_bit_fo
     switches.setenv("PILOT_OT_DEBUG", "512")
     Et = engine.sinkhorn_grid(P, M, 0.1)
     np.testing.assert_array_equal(Et, Eg)                    # (already in the tiles: the switch changes nothing at this size)
+
+
+def test_device_plan_closes_twice_and_then_goes():
+    """close() frees the plan's device buffers at once and may be called again; deleting the closed plan frees nothing twice"""
+    P, M = make_problem(**CONFIGS["c2"])
+    plan = engine.DevicePlan(P, M, n_rows_max=2)
+    plan.run(0.1, row_end=2)
+    plan.sync()
+    assert plan.fetch()[0].shape == (2, P.shape[0])
+    bufs = list(plan._bufs)
+    plan.close()
+    assert plan._bufs == [] and not plan.plan and len(bufs) == 6 and not any(b.ptr for b in bufs)
+    plan.close()
+    del plan
+    buf = engine._DeviceBuffer(64)
+    buf.free()
+    buf.free()
+    assert not buf.ptr

@@ -238,6 +238,35 @@ def test_repeated_calls_routes_and_chunks_give_identical_bits(dtype, model):
                 np.testing.assert_array_equal(u[k], v[k], err_msg=k)
 
 
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+@pytest.mark.parametrize("model", ["ols", "huber"])
+def test_host_view_staged_in_chunks_gives_the_bits_of_its_copy(model):
+    """A row-strided host view goes to the library where it lies, with its own leading dimension; with 64 targets per chunk its 70
+    columns are staged twice, the second time from an offset.  The kernel receives the packed values of the contiguous copy either
+    way, so every output has the copy's bits (NaNs by position: the comparison is of the bit patterns)."""
+    rng = np.random.default_rng(12)
+    x = np.array([1, 1, 2, 3, 3, 4, 5, 6, 6, 7, 8, 9], dtype=np.float64)
+    W = np.log1p(rng.poisson(1.0 + 0.3 * x[:, None], (12, 96))).astype(np.float32)
+    view = W[:, 5:5 + 70]
+    assert not view.flags.c_contiguous and engine._dense_arg(view, "Y", mode="strided").ld == 96
+    kw = dict(model=model, return_info=True)
+    _lib.test_switch("PILOT_OT_TRAJFIT_CHUNK_TARGETS", 64)
+    try:
+        got = engine.trajectory_fits(view, x, **kw)
+        want = engine.trajectory_fits(np.ascontiguousarray(view), x, **kw)
+    finally:
+        _lib.test_switch("PILOT_OT_TRAJFIT_CHUNK_TARGETS", None)
+    assert got[1].pop("not_converged") == want[1].pop("not_converged")
+    for u, v in zip(got, want):
+        for k in u:
+            assert np.array_equal(_bits(u[k]), _bits(v[k])), k
+    assert got[0]["params"].shape == (70, 3, 3) and np.isnan(got[0]["params"][:, 0, 2]).all()
+
+
 # ---- the AnnData level ---------------------------------------------------------------------------------------------------
 class _Uns:
     def __init__(self, uns):

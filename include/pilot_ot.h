@@ -511,6 +511,30 @@ int pilot_ot_csr_group_moments(pilot_ot_csr *csr, const int *codes, int n_groups
  * column), zero-filled and every stored entry written once.  PILOT_OT_EINVAL: a column out of range or named twice. */
 int pilot_ot_csr_densify(pilot_ot_csr *csr, const int *cols, int n_cols, void *out);
 
+/* ---- group sums (K14): per-group column sums for many groups -- the (cell type, sample) pseudobulk counts that pilotpy's
+ * get_pseudobulk_DE forms with groupby().sum() on the densified matrix (plot/pseudobulk_DE_analysis.py:590-594).  Y, dtype, n,
+ * n_cols_total, ld, codes, cols and n_cols are pilot_ot_group_moments's; n_groups in [1, 2^20].
+ * Out (host): count[g] = rows with codes == g; sum[g][j] = the sum of y over those rows in column cols[j], n_groups x n_cols in
+ * f64.  A row with a negative code enters nothing, whatever it holds, and is never read.  A group without rows: count 0, sum 0.0.
+ * The used rows are sorted stably by group on the host and every group is cut into slices of pilot_ot_group_sums_slice_rows()
+ * rows; a slice adds its rows one after another in ascending row order, a group's slices are added in slice order: the order
+ * depends on (n, codes) and that constant alone, nothing uses a floating-point atomic, and the same bits come from every run and
+ * from the host and device routes.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n < 0, n_cols_total < 1, ld < n_cols_total, dtype not 0 / 1, n_groups
+ * outside [1, 2^20], n_cols < 0 (or != n_cols_total without cols), a column outside [0, n_cols_total), a code >= n_groups.
+ * PILOT_OT_ENOTSUP: n > INT_MAX. */
+int pilot_ot_group_sums(const void *Y, int Y_is_device, int dtype, long long n, int n_cols_total, long long ld, const int *codes,
+                        int n_groups, const int *cols, int n_cols, long long *count, double *sum);
+/* The same of a sparse matrix, from its row form: the column form is neither needed nor built, so the call also serves a matrix
+ * whose values were just changed (pilot_ot_csr_normalize_log1p).  One wave takes a slice's rows in order and adds the stored
+ * entries of pilot_ot_group_sums_col_block() selected columns into f64 accumulators in LDS; implicit zeros add nothing.  The
+ * slices are the dense call's, so the two agree to the bit wherever the matrices do.  cols NULL: every column (n_cols = the
+ * matrix's).  Same error cases (n_groups and n_cols < 0 are judged before the handle). */
+int pilot_ot_csr_group_sums(pilot_ot_csr *csr, const int *codes, int n_groups, const int *cols, int n_cols, long long *count,
+                            double *sum);
+int pilot_ot_group_sums_slice_rows(void);
+int pilot_ot_group_sums_col_block(void);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

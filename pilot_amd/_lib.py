@@ -46,6 +46,7 @@ SYMBOLS = [
     "pilot_ot_group_moments",
     "pilot_ot_csr_upload", "pilot_ot_csr_destroy", "pilot_ot_csr_normalize_log1p", "pilot_ot_csr_build_columns", "pilot_ot_csr_slice_rows",
     "pilot_ot_csr_column_nnz", "pilot_ot_csr_group_moments", "pilot_ot_csr_densify",
+    "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -170,6 +171,10 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_csr_column_nnz.argtypes = [c_vp, llp]
     L.pilot_ot_csr_group_moments.argtypes = [c_vp, ip, c_int, ip, c_int, c_int, llp, dp, dp]
     L.pilot_ot_csr_densify.argtypes = [c_vp, ip, c_int, c_vp]
+    L.pilot_ot_group_sums.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, ip, c_int, llp, dp]
+    L.pilot_ot_csr_group_sums.argtypes = [c_vp, ip, c_int, ip, c_int, llp, dp]
+    L.pilot_ot_group_sums_slice_rows.argtypes = []
+    L.pilot_ot_group_sums_col_block.argtypes = []
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

@@ -32,6 +32,7 @@ enum WsSlot {
     WS_CV_Y, WS_CV_IN, WS_CV_AUX, WS_CV_OUT, WS_CV_BMAX, WS_CV_CHAIN, WS_CV_Z,   // pilot_ot_curves.hip
     WS_GM_Y, WS_GM_AUX, WS_GM_PART, WS_GM_COUNT, WS_GM_OUT,                      // pilot_ot_moments.hip
     WS_CSR_COUNTS, WS_CSR_TOTAL, WS_CSR_CODES, WS_CSR_COLS, WS_CSR_OUT,          // pilot_ot_csr.hip
+    WS_GS_Y, WS_GS_AUX, WS_GS_PART, WS_GS_OUT,                                   // pilot_ot_group_sums.hip
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

@@ -10,20 +10,8 @@
 #include <vector>
 
 #include "abi_common.hpp"
+#include "csr_handle.hpp"
 #include "csr_kernels.hpp"
-
-struct pilot_ot_csr {
-    long long n = 0, nnz = 0;
-    int n_cols = 0, dtype = 0, device = 0;
-    long long *indptr = nullptr;
-    int *indices = nullptr;
-    void *data = nullptr;
-    // the column form: built by the first call that needs it, dropped when the values change
-    bool columns = false;
-    long long *colptr = nullptr;
-    int *rowidx = nullptr;
-    void *cdata = nullptr;
-};
 
 namespace {
 

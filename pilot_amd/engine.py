@@ -893,12 +893,12 @@ def device_columns(D, start, stop):
     return _DeviceColumns(D, int(start), int(stop))
 
 
-def _moment_args(n, n_total, codes, n_groups, transform, cols):
-    """group_moments' arguments checked on the host: (codes int32, n_groups, cols int32 or None)"""
+def _moment_args(n, n_total, codes, n_groups, transform, cols, max_groups=GROUP_MOMENTS_MAX_GROUPS):
+    """group_moments' and group_sums' arguments checked on the host: (codes int32, n_groups, cols int32 or None)"""
     if transform not in _GM_TRANSFORMS:
         raise ValueError("transform=%r must be None or 'expm1'" % (transform,))
-    if isinstance(n_groups, bool) or int(n_groups) != n_groups or not 1 <= n_groups <= GROUP_MOMENTS_MAX_GROUPS:
-        raise ValueError("n_groups=%r must be an integer in 1..%d" % (n_groups, GROUP_MOMENTS_MAX_GROUPS))
+    if isinstance(n_groups, bool) or int(n_groups) != n_groups or not 1 <= n_groups <= max_groups:
+        raise ValueError("n_groups=%r must be an integer in 1..%d" % (n_groups, max_groups))
     n_groups = int(n_groups)
     if n_total < 1:
         raise ValueError("Y has no columns")
@@ -996,6 +996,16 @@ class DeviceCSR(_Closing):
             _lib.lptr(count), _lib.dptr(mean), _lib.dptr(m2)))
         return count, mean, m2
 
+    def group_sums(self, codes, n_groups, cols=None):
+        """:func:`group_sums` of the matrix, read from the row form (the column form is not needed and not built, so this also
+        follows :meth:`normalize_log1p` at no extra cost): ``(count, sums)``."""
+        codes, n_groups, cols = _moment_args(self.shape[0], self.shape[1], codes, n_groups, None, cols, GROUP_SUMS_MAX_GROUPS)
+        n_sel = self.shape[1] if cols is None else cols.size
+        count, sums = np.empty(n_groups, dtype=np.int64), np.empty((n_groups, n_sel))
+        _lib.check(_lib.load().pilot_ot_csr_group_sums(
+            self._handle(), _lib.iptr(codes), n_groups, None if cols is None else _lib.iptr(cols), n_sel, _lib.lptr(count), _lib.dptr(sums)))
+        return count, sums
+
     def densify(self, cols=None):
         """A rows x len(cols) :class:`DeviceMatrix` of the matrix's dtype holding the columns ``cols`` (distinct, any order;
         default: all), dense in HBM."""
@@ -1046,6 +1056,41 @@ def group_moments(Y, codes, n_groups, transform=None, cols=None):
         Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_total, Y.ld, _lib.iptr(codes), n_groups,
         None if cols is None else _lib.iptr(cols), n_sel, _GM_TRANSFORMS[transform], _lib.lptr(count), _lib.dptr(mean), _lib.dptr(m2)))
     return count, mean, m2
+
+
+# ---- group sums (K14; the pseudobulk counts of pilotpy's get_pseudobulk_DE) ----------------------------------------------------
+GROUP_SUMS_MAX_GROUPS = 2 ** 20
+
+
+def group_sums_slice_rows():
+    """Rows per slice of :func:`group_sums`: a group's rows are added in ascending order within slices of this many, the slices
+    in order."""
+    return int(_lib.load().pilot_ot_group_sums_slice_rows())
+
+
+def group_sums_col_block():
+    """Selected columns per wave of :meth:`DeviceCSR.group_sums` (its float64 accumulators in LDS)."""
+    return int(_lib.load().pilot_ot_group_sums_col_block())
+
+
+def group_sums(Y, codes, n_groups, cols=None):
+    """K14: per group and selected column, the float64 sum of the rows of ``Y`` with ``codes == g``, and the number of such rows
+    (include/pilot_ot.h, "group sums").  ``Y``, ``codes`` and ``cols`` are :func:`group_moments`'s; ``n_groups`` in 1..2^20.
+    Returns ``(count, sums)``: ``n_groups`` int64 and an ``n_groups x columns`` float64 array.  A row with a negative code enters
+    nothing, whatever it holds; a group without rows gives count 0 and sums 0.0.  One pass over the used rows, added in an order
+    that depends on ``codes`` alone: a repeated call and the host and device routes return the same bits.  Every argument is
+    checked before any device work (ValueError).  A :class:`DeviceCSR` is forwarded to its own method."""
+    if isinstance(Y, DeviceCSR):
+        return Y.group_sums(codes, n_groups, cols=cols)
+    Y = _dense_arg(Y, "Y", mode="strict")
+    n_total = Y.cols
+    codes, n_groups, cols = _moment_args(Y.rows, n_total, codes, n_groups, None, cols, GROUP_SUMS_MAX_GROUPS)
+    n_sel = n_total if cols is None else cols.size
+    count, sums = np.empty(n_groups, dtype=np.int64), np.empty((n_groups, n_sel))
+    _lib.check(_lib.load().pilot_ot_group_sums(
+        Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_total, Y.ld, _lib.iptr(codes), n_groups,
+        None if cols is None else _lib.iptr(cols), n_sel, _lib.lptr(count), _lib.dptr(sums)))
+    return count, sums
 
 
 def fitted_curves(params, model, times, noise=None, device=False):

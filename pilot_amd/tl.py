@@ -29,6 +29,8 @@ compute_diff_expressions,                      patients_sub_clustering.py:15-240
 extract_cells_from_gene_expression_for_...,    restated from device moments, without R, plots or files) and
 highly_variable_genes,                         scanpy's pp.highly_variable_genes(flavor='seurat') restated;
 cell_type_diff_two_sub_patient_groups          plot/ploting.py:460-556 (the table, without the plot or the file)
+pseudobulk_counts, pseudobulk_inputs,          plot/pseudobulk_DE_analysis.py:590-610 (get_pseudobulk_DE's aggregation and the
+deseq2_size_factors                            inputs of its R calls) and DESeq2's median-of-ratios size factors restated
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -1496,3 +1498,90 @@ def cell_type_diff_two_sub_patient_groups(proportions, cell_types, labels="Predi
         adj = _bh_adjust(2.0 * stats.t.sf(np.abs(score), dof))
         out = pd.DataFrame({"cell_type": cell_types, "adjPval": adj, "-logPval": -np.log(adj), "score": score})
     return out.sort_values(by=["score", "-logPval"], ascending=[False, False])
+
+
+# ---- pseudobulk counts: per-sample gene sums, size factors (plot/pseudobulk_DE_analysis.py:590-610) -----------------------------
+def _pseudobulk_matrix(adata, rows):
+    """adata.X (its rows ``rows``, or all of them) for ``engine.group_sums``: a sparse one as an ``engine.DeviceCSR``, a dense one
+    as a C-contiguous float32 / float64 array (other dtypes become float64, which holds every integer count below 2^53)"""
+    if _is_sparse(adata.X):
+        return _sparse_rows(adata.X, rows)
+    X = np.asarray(adata.X if rows is None else adata.X[rows])
+    if X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    return np.ascontiguousarray(X)
+
+
+def pseudobulk_counts(adata, cell_type=None, celltype_col="cell_types", sample_col="sampleID"):
+    """The aggregation that opens ``get_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:590-597) without the dense frame:
+    ``adata.to_df()`` with the two label columns, ``groupby([celltype_col, sample_col]).sum()`` -- and, with ``cell_type``, its
+    ``.loc[cell_type]``.  The labels are grouped on the host as the reference groups them (the object values of the two ``obs``
+    columns; observed combinations only, sorted; a cell with a missing label belongs to no group); the sums over the cells x
+    genes matrix come from one device pass (``engine.group_sums``), a scipy sparse ``adata.X`` as an ``engine.DeviceCSR`` that is
+    never made dense.  With ``cell_type`` only that type's cells are uploaded.
+
+    Returns a frame of float64 sums with ``adata.var_names`` as columns, indexed by the MultiIndex ``(celltype_col, sample_col)``,
+    or by the samples of ``cell_type``.  ``attrs['n_cells']``: a dict, row label -> number of cells, in row order (what
+    ``plot_cell_numbers`` draws).  Deviation: the sums are float64, where the reference's float32 frames stop being exact above
+    2^24.  An unknown ``cell_type`` raises ValueError before any device work."""
+    labels = pd.DataFrame(adata.obs[[celltype_col, sample_col]].values, columns=[celltype_col, sample_col])
+    rows = None
+    if cell_type is not None:
+        rows = np.flatnonzero((labels[celltype_col] == cell_type).to_numpy())
+        if rows.size == 0:
+            raise ValueError("pseudobulk_counts: no cell of %r in obs[%r]" % (cell_type, celltype_col))
+        grouped = labels[sample_col].iloc[rows].groupby(labels[sample_col].iloc[rows], sort=True)
+    else:
+        grouped = labels.groupby([celltype_col, sample_col], sort=True)
+    index = grouped.size().index
+    if len(index) == 0:
+        raise ValueError("pseudobulk_counts: no cell carries both labels")
+    codes = grouped.ngroup().to_numpy().astype(np.int32)           # the rank of every cell's group in `index`, -1: a missing label
+    count, sums = engine.group_sums(_pseudobulk_matrix(adata, rows), codes, len(index))
+    out = pd.DataFrame(sums, index=index, columns=pd.Index(list(adata.var_names)))
+    out.attrs["n_cells"] = dict(zip(index.tolist(), count.tolist()))
+    return out
+
+
+def pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
+                      remove_samples=()):
+    """``(cluster_counts, cluster_metadata)`` as ``get_pseudobulk_DE`` hands them to DESeq2 (plot/pseudobulk_DE_analysis.py:
+    597-610): the samples x genes sums of ``cell_type`` (:func:`pseudobulk_counts`), the rows of ``proportion_df`` for those
+    samples with the ``stage`` column (a copy of ``cluster_col``), ``remove_samples`` dropped from both, the metadata in the
+    counts' order, and the genes that are zero in every remaining sample dropped.  No plots, CSV files or R: ``rlog``, ``DESeq()``
+    and ``lfcShrink`` stay in R, and this pair is what the reference's ``compute_pseudobulk_DE`` takes, unchanged.  A sample of the
+    cell type that ``proportion_df`` lacks raises KeyError, as in the reference."""
+    cluster_counts = pseudobulk_counts(adata, cell_type, celltype_col, sample_col)
+    n_cells = cluster_counts.attrs["n_cells"]
+    cluster_metadata = proportion_df.loc[cluster_counts.index.values].copy()
+    cluster_metadata["stage"] = cluster_metadata[cluster_col].values
+    for sample in (remove_samples if remove_samples is not None else ()):
+        if sample in cluster_metadata.index:
+            cluster_metadata = cluster_metadata.drop(index=sample)
+        if sample in cluster_counts.index:
+            cluster_counts = cluster_counts.drop(index=sample)
+    cluster_metadata = cluster_metadata.loc[cluster_counts.index]
+    cluster_counts = cluster_counts.loc[:, (cluster_counts != 0).any(axis=0)]
+    cluster_counts.attrs["n_cells"] = {s: n_cells[s] for s in cluster_counts.index}
+    return cluster_counts, cluster_metadata
+
+
+def deseq2_size_factors(cluster_counts):
+    """DESeq2's median-of-ratios size factors of a samples x genes count frame: ``estimateSizeFactorsForMatrix`` with its
+    defaults on ``round(t(cluster_counts))``, as ``compute_pseudobulk_PCA`` / ``compute_pseudobulk_DE`` reach it through
+    ``DESeqDataSetFromMatrix`` (DESeq2 is not installed where this library is built and tested, so the rule is restated and
+    UNPINNED here, like limma's).  With c = rint(counts): the log geometric mean of a gene is the mean over the samples of log c,
+    finite only where every sample's count is positive; a sample's factor is exp(median over those genes of log c - that mean).
+    No gene with all counts positive: ValueError (DESeq2 stops there too).  The O(samples x genes) tail of the pseudobulk step, on
+    the host.  Returns a Series indexed by sample."""
+    c = np.rint(np.asarray(cluster_counts, dtype=np.float64))
+    if c.ndim != 2:
+        raise ValueError("deseq2_size_factors: a samples x genes frame, got shape %s" % (c.shape,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        logc = np.log(c)
+        lg = logc.mean(axis=0) if c.shape[0] else np.full(c.shape[1], np.nan)
+    use = np.isfinite(lg)
+    if not use.any():
+        raise ValueError("deseq2_size_factors: every gene contains at least one zero, cannot compute log geometric means")
+    sf = np.exp(np.median(logc[:, use] - lg[use], axis=1))
+    return pd.Series(sf, index=getattr(cluster_counts, "index", None))

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pilot_ot.h"
+#include "sinkhorn_layout.hpp"     // LDS_BYTES
 
 #define PILOT_API extern "C" __attribute__((visibility("default")))
 
@@ -81,7 +82,6 @@ inline int grid_for(long n, int block, int n_cu) {
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-constexpr size_t LDS_BYTES = 160 * 1024;
 constexpr int MAX_K = 128;          // the MFMA pair-grid kernels (8 row-tiles of 16 cell types)
 constexpr int GENERIC_MAX_K = 2048;  // the reference-semantics fallback kernel (vectors in LDS)
 constexpr int EMD_MAX_K = 256;       // exact-OT kernel: 4 rows / columns per lane

@@ -4,30 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include "abi_common.hpp"
+#include "sinkhorn_layout.hpp"
 
 constexpr int TIMING_RING = 64;
-
-namespace pilot {
-// Bits of the PILOT_OT_DEBUG test switch (experiments and tests of the Sinkhorn grid call; tools/ and tests set the numbers)
-enum : int {
-    DBG_NATURAL_ORDER = 2,        // no longest-first work order, only the duplicates are told apart
-    DBG_WGS_SHIFT = 4,            // bits 4..6: resident workgroups per CU of the fast launch (0: its own occupancy)
-    DBG_NO_TAIL_ROWS = 256,       // the last row-tile on the MFMA path (no VALU tail-row variant)
-    DBG_NO_SOLO = 512,            // exact duplicates in the tiles, no one-wave-per-pair path in the fast launch
-    DBG_NO_NAN_PASS = 1024,       // no POT-literal pass for the pairs that end in NaN
-    DBG_NO_SOLO_F64 = 2048,       // the f64 fallback pass on 16-pair tiles, not one wave per pair
-    DBG_NO_REDO64 = 4096,         // single-band pairs that leave the f32 range go to the POT-literal pass, not the f64 one
-    DBG_NO_TRACK_ALL = 8192,      // the fast pass runs first beyond max(M)/reg = 24 too
-};
-// The test switches that act inside the launch sequence of a Sinkhorn grid call: read once per call (pilot_ot_sinkhorn_grid_dev)
-// and part of the graph-replay key, so a changed switch is captured anew, never replayed from the old sequence
-struct SinkhornSwitches {
-    int debug;          // PILOT_OT_DEBUG (DBG_* bits)
-    int no_quad;        // PILOT_OT_NO_QUAD set: 112 < K <= 128 on the one-wave kernel
-    int generic_wgs;    // PILOT_OT_GENERIC_WGS: fewer workgroups for the POT-literal kernel (0: unset)
-    bool operator==(const SinkhornSwitches &o) const { return debug == o.debug && no_quad == o.no_quad && generic_wgs == o.generic_wgs; }
-};
-}  // namespace pilot
 
 struct pilot_ot_plan {
     int N, K, device;
@@ -36,7 +15,7 @@ struct pilot_ot_plan {
     void *img;         // 3 operand images, sized for f64 at this K
     void *p_slot;      // N x KP proportions in accumulator-slot order (f32 or f64; sized for f64)
     int *track_list;   // N x N
-    int *ctrl;         // control block of a call: CTRL_BLOCK_INTS ints, slots named next to CTRL_INTS in sinkhorn_kernels.hpp
+    int *ctrl;         // control block of a call: CTRL_BLOCK_INTS ints, slots named next to CTRL_INTS in sinkhorn_layout.hpp
     int *order_list;   // N x N: longest-first work order of the fast launch
     unsigned char *order_bucket;  // N x N
     int *order_hist;   // ctrl + CTRL_ORDER_HIST

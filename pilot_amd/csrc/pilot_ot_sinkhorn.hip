@@ -15,6 +15,13 @@
 
 namespace {
 using pilot::LDS_BYTES, pilot::MAX_K, pilot::GENERIC_MAX_K, pilot::WIDE_MAX_K;
+
+// does the bf16-split tracking kernel fit LDS at this K with a ring of four and the hand-over buffers its launch reserves?
+// (the fp16-split configuration needs less for its fast pass and the same for its tracking pass)
+bool split_fits_lds(int K, bool sym, int bands = 1) {
+    const pilot::CfgShape c = pilot::shape_of(pilot::CFG_S32);
+    return pilot::stream_layout(c, (K + 15) / 16, sym, true, 0, bands, 4).bytes + (size_t)pilot::handover_elems(c) * 4 <= LDS_BYTES;
+}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -37,7 +44,6 @@ PILOT_API int pilot_ot_auto_precision(double max_cost_over_reg) {
     return max_cost_over_reg <= 60.0 ? PILOT_OT_PREC_BF16X3 : PILOT_OT_PREC_F64;
 }
 
-namespace { bool split_fits_lds(int K, bool sym, int bands); }
 PILOT_API int pilot_ot_auto_precision_for(double max_cost_over_reg, int K, int cost_is_symmetric) {
     int prec = pilot_ot_auto_precision(max_cost_over_reg);
     if ((prec == PILOT_OT_PREC_BF16X3 || prec == PILOT_OT_PREC_F16X2) && !split_fits_lds(K, cost_is_symmetric != 0, 1)) prec = PILOT_OT_PREC_F32;
@@ -214,40 +220,6 @@ int run_generic(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const doub
     return PILOT_OT_OK;
 }
 
-// LDS of one stream-kernel workgroup: operand image(s) + first-product table + tail weights + one ring of finished pairs
-// per wave.  The ring gets as many slots (<= 16) as fit while `want` workgroups stay resident per CU; at least 4.
-struct StreamLds { size_t bytes; int ring, wgs_per_cu; };
-StreamLds stream_lds(size_t fixed, size_t slot_bytes, int want, int min_ring = 4) {
-    StreamLds r;
-    for (;;) {
-        const size_t budget = LDS_BYTES / (size_t)want;
-        long ring = budget > fixed ? (long)((budget - fixed) / ((size_t)pilot::WAVES_PER_WG * slot_bytes)) : 0;
-        if (ring >= min_ring || want == 1) {
-            if (ring > pilot::RING_MAX) ring = pilot::RING_MAX;
-            if (ring < 1) ring = 0;
-            r.ring = (int)ring; r.wgs_per_cu = want;
-            r.bytes = fixed + (size_t)pilot::WAVES_PER_WG * slot_bytes * (size_t)ring;
-            return r;
-        }
-        --want;
-    }
-}
-
-// does the bf16-split configuration fit LDS at this K (operand image(s) + table + a minimal ring)?
-// (the fp16-split configuration needs less for its fast pass and the same for its tracking pass)
-bool split_fits_lds(int K, bool sym, int bands = 1) {
-    const int RT = (K + 15) / 16, KP = RT * 16;
-    const size_t fixed = (size_t)(sym ? 1 : 2) * pilot::form_elems_rt(pilot::CFG_S32, RT) * 4 * bands + (size_t)KP * 4 +
-                         (size_t)pilot::WAVES_PER_WG * pilot::HANDOVER_BUF * sizeof(int);
-    return fixed + (size_t)4 * pilot::WAVES_PER_WG * (2 * KP + 4) * 4 <= LDS_BYTES;
-}
-
-// workgroups of a launch of WAVES_PER_WG tiles each: per_cu resident per CU, no more than the tiles fill
-int clamp_wgs(const pilot_ot_plan *pl, int per_cu, int tiles) {
-    const int need = (tiles + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;
-    return pl->n_cu * per_cu < need ? pl->n_cu * per_cu : need;
-}
-
 // The launch parameters run_grid and run_wide share: the whole call on the plan's buffers, in the longest-first order, drawn from
 // the fast launch's queue head.  Pairs that end in NaN ("Numerical errors" in POT) are collected and re-solved by the POT-literal
 // kernel, which returns the last good iterate like POT does.
@@ -272,190 +244,54 @@ pilot::GridParams call_params(const pilot_ot_plan *pl, int n_pairs, int row_begi
     return p;
 }
 
-// cfg: pilot::CFG_F32 / CFG_F64 / CFG_S32 / CFG_H32 (all 16-pair tiles: TILE = 16, 4 accumulator registers, 4 lane groups)
-// CFG_H32 (fp16-split): the fast pass only; its tracking pass is the bf16-split kernel on the second operand block.
-// mixed (cfg == CFG_S32 only): small reg under PILOT_OT_PREC_AUTO -- every pair is first iterated in f32 (bf16-split
-// products, tau-tracking kernel); pairs whose plan may touch Gibbs entries outside the f32-safe range, or that went NaN, are
-// collected (ring_flush) and solved again by the f64 tracking kernel.
+// The passes that plan_grid (sinkhorn_layout.hpp) lays out for this call, launched in order: every decision is taken there, the
+// pointers are bound here.
 int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double *d_P, const double *d_M, double reg, int num_iter_max,
-             double stop_thr, double tau, int check_period, double floor_ulps, bool sym, int row_begin,
-             int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err, int *d_flags, hipStream_t s,
-             bool mixed = false) {
-    const bool f64 = cfg == pilot::CFG_F64, half = cfg == pilot::CFG_H32, split = cfg == pilot::CFG_S32 || half;
-    const size_t ts = f64 ? sizeof(double) : sizeof(float);
-    constexpr int TILE = 16;
-    const int N = pl->N, K = pl->K;
-    const int RT = (K + TILE - 1) / TILE;
-    const int KP = RT * TILE;
-    const int debug = sw.debug;
-    const size_t form = pilot::form_elems_rt(cfg, RT);
-    // the per-wave hand-over buffers of the fast kernels
-    const size_t hb_bytes = (size_t)pilot::WAVES_PER_WG * pilot::HANDOVER_BUF * sizeof(int);
-    size_t fixed = (size_t)(sym ? 1 : 2) * form * ts + (size_t)KP * ts + hb_bytes;   // operand image(s) + first-product table + hand-over buffers
-    // K mod 16 in 1..4: the (at most four) cell types of the last row-tile are computed on the VALU (tail_rows)
-    int tv = 0;
-    // split: skip the dead registers of the last tile (beyond 4 row-tiles those variants run out of registers and spill
-    // 600-980 B per lane; the plain variants do not, and measure the same there)
-    const int live1 = (split && RT >= 2 && RT <= 4 && K - (RT - 1) * TILE <= 4) ? 1 : 0;
-    if (!split) {
-        const int n_tail = K - (RT - 1) * TILE;
-        // (RT = 8 variants spill: left on the MFMA path)
-        if (RT >= 2 && RT <= 7 && n_tail <= 4 && !(debug & pilot::DBG_NO_TAIL_ROWS)) tv = n_tail <= 2 ? 1 : 2;
-        const size_t tail_lds = (size_t)(sym ? 1 : 2) * tv * ((RT - 1) * 4 + 1) * 64 * 2 * ts;
-        if (tv && fixed + tail_lds + 4 * pilot::WAVES_PER_WG * (2 * KP + 4) * ts > LDS_BYTES) tv = 0;   // no room: MFMA path
-        if (tv) fixed += tail_lds;
-    }
-    const size_t slot_bytes = (size_t)(2 * KP + 4) * ts;
-    if (fixed + pilot::WAVES_PER_WG * slot_bytes > LDS_BYTES)
-        return fail(PILOT_OT_ENOTSUP, "K=%d with a %ssymmetric cost needs %zu B of LDS (> %zu) in this precision", K, sym ? "" : "non-",
-                    fixed + pilot::WAVES_PER_WG * slot_bytes, LDS_BYTES);
+             double stop_thr, double tau, int check_period, double floor_ulps, bool sym, int row_begin, int n_rows, int row_step,
+             double *d_emd, int *d_iters, double *d_err, int *d_flags, hipStream_t s, bool mixed = false) {
+    const int N = pl->N, K = pl->K, RT = (K + 15) / 16;
+    const pilot::GridPasses g = pilot::plan_grid(cfg, N, K, n_rows, sym, mixed, pl->max_cost / reg, pl->n_cu, sw);
+    if (g.rc != PILOT_OT_OK) return fail(g.rc, "%s", g.msg);
     HIP_TRY(hipMemsetAsync(pl->ctrl, 0, pilot::CTRL_BLOCK_INTS * sizeof(int), s));     // one control block, one memset per call
-    void *img = pl->img;
-    void *Pt = pl->p_slot;
     if (n_rows == 0) return PILOT_OT_OK;
-
-    const int n_pairs = n_rows * N;
-    pilot::GridParams p = call_params(pl, n_pairs, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd, d_iters,
+    pilot::GridParams p = call_params(pl, n_rows * N, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd, d_iters,
                                       d_err, d_flags);
-    p.queue_shards = pl->ctrl + pilot::CTRL_SHARDS_AT;       // (the fast launch up to two row-tiles; the tracking launch has its own)
-    p.debug = debug;
-    // Between the fp16-split range and the two-band path (12 < max(M)/reg <= 60) a few pairs per matrix leave the f32 range in
-    // the single-band kernels (a scaling jumps past the fp16 domain within one update; products underflow at reg <= 0.025).
-    // They used to go to the POT-literal kernel with the other NaN pairs -- one workgroup per pair, 12.5 us per update: 3 to 13
-    // pairs cost 12 ms of a 30 ms call at reg 0.025 .. 0.0175.  They are collected like the small-reg path collects its
-    // hand-over and solved again by the f64 tracking kernel (symmetric cost, K <= 64: one wave per pair, 1.1 us per update).
-    const bool redo64 = !mixed && split && pl->max_cost / reg > 12.0 && !(debug & pilot::DBG_NO_REDO64);
-    // From max(M)/reg = 24 on nearly every pair tau-absorbs (c3: 28 % at 20, 94 % at 25) and the fast pass only hands its pairs
-    // over after a few dozen wasted updates (3.7 of 11.6 ms at reg 0.04): every pair goes to the tracking kernel at once, as
-    // in the two-band path.
-    const bool track_all = mixed || (split && !half && pl->max_cost / reg > 24.0 && !(debug & pilot::DBG_NO_TRACK_ALL));
-    int *const fb_list = pl->nan_list + (size_t)N * N;
-    if (redo64) { p.fb_list = fb_list; p.fb_count = pl->ctrl + pilot::CTRL_FB_LEN; }
-    const int tiles = (n_pairs + TILE - 1) / TILE;
-    // exact duplicates (a == b): one wave per pair in the leading workgroups of the fast launch (symmetric cost, K <= 64)
-    // ... while the grid is small.  A wave that iterates ONE pair has the shorter update (K = 50: 0.57 us against 0.77 us for a lone
-    // 16-pair wave), which is what a launch with fewer tiles than wave slots waits for (c2; the row shards of a multi-device call);
-    // on a full device the 600 diagonal pairs of c3 (165 updates on average, up to 301) on 600 waves of their own are a tail instead:
-    // main kernel 0.617 -> 0.584 ms with the duplicates in the tiles (tools/solo_probe.py; crossover between 5 600 and 7 500 tiles at 2 048
-    // wave slots).  The rule reads the FULL grid (N x N), not the rows of this call: a row shard and the full grid send the same pair
-    // down the same path, so their bits agree.
-    // (the shape rules read the configuration as its fast pass is instantiated: the split variants with live1 as their TV)
-    const pilot::CfgShape fast = pilot::shape_of(cfg);
-    const int tv_fast = split ? live1 : tv;
-    const long full_tiles = ((long)N * N + TILE - 1) / TILE;
-    const long wave_slots = (long)pl->n_cu * pilot::min_waves_per_simd(fast, RT, sym, false, tv_fast) * pilot::WAVES_PER_WG;
-    const bool solo = pilot::solo_in_stream(fast, RT, sym, false, tv_fast) && !(debug & pilot::DBG_NO_SOLO) && !track_all &&
-                      full_tiles < 3 * wave_slots;
-    int solo_blocks = 0;
-    {
-        // longest-first work order (see order_bucket_kernel)
-        int ob = (n_pairs + 1023) / 1024;
-        if (ob > pl->n_cu) ob = pl->n_cu;
-        const int mode = (solo ? 2 : 0) | ((debug & pilot::DBG_NATURAL_ORDER) ? 4 : 0);   // bit 2: natural order (experiment)
-        HIP_TRY(pilot::launch_prep(cfg, d_M, K, RT, reg, img, d_P, Pt, N, (tv ? 1 : 0) | 2 | (mixed ? 4 : 0), stop_thr, floor_ulps, n_rows, row_begin, row_step,
-                                   pl->order_bucket, pl->order_hist, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT, pl->ctrl + pilot::CTRL_HEAD_FAST,
-                                   mode, ob, s));
-        if (solo) {
-            solo_blocks = (n_rows + pilot::WAVES_PER_WG - 1) / pilot::WAVES_PER_WG;     // the diagonal; more duplicates queue up
-            if (solo_blocks > pl->n_cu) solo_blocks = pl->n_cu;
-            p.solo_len = pl->ctrl + pilot::CTRL_SOLO_LEN; p.solo_head = pl->ctrl + pilot::CTRL_HEAD_SOLO; p.solo_blocks = solo_blocks;
-        }
-    }
+    p.debug = sw.debug;
+    int *const lists[] = {pl->order_list, pl->track_list, pl->nan_list + (size_t)N * N};       // (PairList)
+    auto slot = [&](int at) { return at == pilot::CTRL_NONE ? nullptr : pl->ctrl + at; };
+    if (g.f64.run) { p.fb_list = lists[g.f64.list]; p.fb_count = slot(pilot::CTRL_FB_LEN); }
+    if (g.fast.solo_blocks) { p.solo_len = slot(pilot::CTRL_SOLO_LEN); p.solo_head = slot(pilot::CTRL_HEAD_SOLO); }
+    auto launch = [&](const pilot::PassPlan &v) -> hipError_t {
+        p.list = lists[v.list]; p.list_len = slot(v.len_slot); p.queue_head = slot(v.head_slot); p.queue_shards = slot(v.shards_at);
+        p.solo_blocks = v.solo_blocks; p.ring = v.lds.ring; p.bands = v.bands;
+        const dim3 wgs(v.wgs);
+        if (v.solo_f64) return pilot::launch_solo_track_f64(wgs, s, p);
+        if (v.tv) return pilot::launch_stream_tv(v.cfg, v.tv, RT, sym, v.track, wgs, v.lds.bytes, s, p);
+        if (v.quad) return pilot::launch_quad(wgs, s, p);
+        if (v.cfg == pilot::CFG_H32) return pilot::launch_stream_h32(RT, sym, v.live1, wgs, v.lds.bytes, s, p);
+        if (v.cfg == pilot::CFG_S32) return pilot::launch_stream_s32(RT, sym, v.track, v.live1, wgs, v.lds.bytes, s, p);
+        return v.cfg == pilot::CFG_F64 ? pilot::launch_stream_f64(RT, sym, v.track, wgs, v.lds.bytes, s, p)
+                                       : pilot::launch_stream_f32(RT, sym, v.track, wgs, v.lds.bytes, s, p);
+    };
+    HIP_TRY(pilot::launch_prep(cfg, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, g.write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step,
+                               pl->order_bucket, pl->order_hist, pl->order_list, slot(pilot::CTRL_SPLIT), slot(pilot::CTRL_HEAD_FAST), g.mode, g.ob, s));
     hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
-    // (fp16-split configuration, 112 < K <= 128, symmetric cost: four waves per tile, one tile per workgroup, two workgroups per CU)
-    const bool quad = half && pilot::quad_covers(K, sym) && !sw.no_quad;
-    auto launch = [&](int tvv, bool track, int wgs, const StreamLds &L) -> hipError_t {
-        p.ring = L.ring;
-        if (tvv) return pilot::launch_stream_tv(cfg, tvv, RT, sym, track, dim3(wgs), L.bytes, s, p);
-        if (half && !track && quad) return pilot::launch_quad(dim3(wgs), s, p);
-        if (half && !track) return pilot::launch_stream_h32(RT, sym, live1, dim3(wgs), L.bytes, s, p);
-        if (split) return pilot::launch_stream_s32(RT, sym, track, live1, dim3(wgs), L.bytes, s, p);
-        return f64 ? pilot::launch_stream_f64(RT, sym, track, dim3(wgs), L.bytes, s, p)
-                   : pilot::launch_stream_f32(RT, sym, track, dim3(wgs), L.bytes, s, p);
-    };
-    // first pass: throughput kernel (pairs that would tau-absorb are handed to the second pass)
-    if (!track_all && quad) {
-        int wgs = 2 * pl->n_cu;
-        if (wgs > tiles) wgs = tiles;
-        HIP_TRY(launch(tv, false, wgs, StreamLds{}));
-    } else if (!track_all) {
-        int want = pilot::min_waves_per_simd(fast, RT, sym, false, tv_fast);
-        // (K <= 4: a third of the pairs tau-absorb and are handed over, and the hand-over's atomics and list stores are what more resident
-        // waves contend for -- K = 3 / 4 at N = 600: 0.60 / 0.64 ms at two workgroups per CU, 0.69 / 0.72 at four; from K = 5 on four win)
-        if (half && K <= 4 && want > 2) want = 2;
-        if ((debug >> pilot::DBG_WGS_SHIFT) & 7) want = (debug >> pilot::DBG_WGS_SHIFT) & 7;      // experiment: resident workgroups per CU
-        // split configurations up to 4 row-tiles flush their ring inline and park U in LDS meanwhile (pilot::parked_flush):
-        // one 16-byte line per lane and row-tile
-        const bool park = split && RT <= 4;
-        // (fp16-split configuration: ring slots and the park area hold packed pieces -- whole k-blocks, so an odd row-tile
-        // count rounds up)
-        const size_t slot_fast = half ? (size_t)pilot::ring_slot_stride<pilot::CfgH32x16>(RT) * ts : slot_bytes;
-        const size_t park_lane = half ? (size_t)pilot::park_lane_elems<pilot::CfgH32x16>(RT) : (size_t)RT * 4;
-        const size_t park_bytes = park ? (size_t)pilot::WAVES_PER_WG * park_lane * 64 * ts : 0;
-        if (fixed + park_bytes + pilot::WAVES_PER_WG * slot_fast > LDS_BYTES)
-            return fail(PILOT_OT_ENOTSUP, "K=%d: operand images + ring + park area exceed LDS", K);
-        const StreamLds L = stream_lds(fixed + park_bytes, slot_fast, want);
-        HIP_TRY(launch(tv, false, clamp_wgs(pl, L.wgs_per_cu, tiles) + solo_blocks, L));
-    }
+    if (g.fast.run) HIP_TRY(launch(g.fast));
     if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
-    // second pass: pairs in which POT would tau-absorb, with the absorption iterations tracked
-    p.list = pl->track_list; p.list_len = pl->ctrl + pilot::CTRL_TRACK_LEN; p.queue_head = pl->ctrl + pilot::CTRL_HEAD_TRACK;
-    p.queue_shards = pl->ctrl + pilot::CTRL_SHARDS_TRACK_AT;     // (used by the tracking kernels up to two row-tiles)
-    p.solo_blocks = 0;
-    size_t fixed_t = fixed;
-    if (half) {     // tracking pass of the fp16-split configuration: the bf16-split kernel on its own operand block
-        p.img = static_cast<float *>(img) + pilot::track_img_elems(cfg, RT);
-        fixed_t = (size_t)(sym ? 1 : 2) * pilot::form_elems_rt(pilot::CFG_S32, RT) * ts + (size_t)KP * ts + hb_bytes;
-    }
-    if (track_all) { p.list = pl->order_list; p.list_len = nullptr; }     // EVERY pair goes through the tracking kernel (longest first)
-    if (mixed) {
-        // small reg: the Gibbs kernel in two exponent bands; pairs that still leave the f32 range are collected in track_list
-        // for the f64 pass
-        p.bands = 2;
-        p.fb_list = pl->track_list; p.fb_count = pl->ctrl + pilot::CTRL_FB_LEN;
-        fixed_t = (size_t)(sym ? 1 : 2) * form * ts * 2 + (size_t)KP * ts + hb_bytes;
-    }
-    {
-        // (the tracking kernel's result need not match the fast kernels' bits: a pair is always solved by one of them)
-        const int tv_t = RT <= 4 ? tv : 0;          // larger tracking variants spill with the tail rows
-        // (the split configurations track on the bf16-split kernel, the fp16-split one too)
-        const pilot::CfgShape tracking = split ? pilot::shape_of(pilot::CFG_S32) : fast;
-        const StreamLds L = stream_lds(fixed_t, slot_bytes, pilot::min_waves_per_simd(tracking, RT, sym, true, split ? live1 : tv_t));
-        HIP_TRY(launch(tv_t, true, clamp_wgs(pl, L.wgs_per_cu, tiles), L));
-    }
-    if (mixed || redo64) {
-        // third pass: the collected pairs in f64 (operand images and proportions rebuilt for the f64 configuration in the
-        // same buffers -- the f32 passes are complete in stream order; no ordering, the list is short)
-        const int RT64 = RT;
-        const size_t form64 = pilot::form_elems_rt(pilot::CFG_F64, RT64);
-        const size_t fixed64 = (size_t)(sym ? 1 : 2) * form64 * sizeof(double) + (size_t)KP * sizeof(double);
-        const size_t slot64 = (size_t)(2 * KP + 4) * sizeof(double);
-        if (fixed64 + pilot::WAVES_PER_WG * slot64 > LDS_BYTES)
-            return fail(PILOT_OT_ENOTSUP, "K=%d: the f64 fallback needs %zu B of LDS", K, fixed64 + pilot::WAVES_PER_WG * slot64);
-        HIP_TRY(pilot::launch_prep(pilot::CFG_F64, d_M, K, RT64, reg, img, d_P, Pt, N, 2, stop_thr, floor_ulps, 0, row_begin, row_step,
-                                   pl->order_bucket, pl->order_hist, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT, pl->ctrl + pilot::CTRL_HEAD_FAST, 0, 1, s));
-        pilot::GridParams q = p;
-        q.list = mixed ? pl->track_list : fb_list; q.list_len = pl->ctrl + pilot::CTRL_FB_LEN; q.queue_head = pl->ctrl + pilot::CTRL_FB_HEAD;
-        q.queue_shards = nullptr;
-        q.img = img;                        // (the fp16-split configuration's tracking pass had moved it to its own block)
-        q.fb_list = nullptr; q.fb_count = nullptr; q.bands = 1;
-        if (sym && K <= 64 && !(debug & pilot::DBG_NO_SOLO_F64)) {
-            // the list is short (tens of pairs) and every pair on it runs long: one wave per pair, not 16-pair MFMA tiles
-            HIP_TRY(pilot::launch_solo_track_f64(dim3(64), s, q));
-        } else {
-            const StreamLds L = stream_lds(fixed64, slot64, pilot::min_waves_per_simd(pilot::shape_of(pilot::CFG_F64), RT64, sym, true, 0));
-            q.ring = L.ring;
-            HIP_TRY(pilot::launch_stream_f64(RT64, sym, true, dim3(clamp_wgs(pl, L.wgs_per_cu, tiles)), L.bytes, s, q));
-        }
+    // (the fp16-split configuration tracks on the bf16-split operand block behind its own)
+    p.img = static_cast<float *>(pl->img) + pilot::track_img_elems(cfg, RT);
+    HIP_TRY(launch(g.track));
+    if (g.f64.run) {
+        HIP_TRY(pilot::launch_prep(pilot::CFG_F64, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, 2, stop_thr, floor_ulps, 0, row_begin, row_step,
+                                   pl->order_bucket, pl->order_hist, pl->order_list, slot(pilot::CTRL_SPLIT), slot(pilot::CTRL_HEAD_FAST), 0, 1, s));
+        p.img = pl->img; p.fb_list = nullptr; p.fb_count = nullptr;
+        HIP_TRY(launch(g.f64));
     }
     if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
-    if (!(debug & pilot::DBG_NO_NAN_PASS)) {
-        const int rc = run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters,
-                                   d_err, d_flags, s, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);
-        if (rc != PILOT_OT_OK) return rc;
-    }
-    return PILOT_OT_OK;
+    if (sw.debug & pilot::DBG_NO_NAN_PASS) return PILOT_OT_OK;
+    return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags,
+                       s, pl->nan_list, slot(pilot::CTRL_NAN_LEN), slot(pilot::CTRL_NAN_HEAD));
 }
 
 // 128 < K <= 256 with a symmetric cost inside the fp16-split range: sinkhorn_wide_kernel (wide_kernels.hpp) on the operand
@@ -501,7 +337,7 @@ int run_wide(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double 
     int wgs = pl->n_cu < tiles ? pl->n_cu : tiles;            // one 512-thread workgroup per CU (230 VGPRs: two waves per SIMD)
     HIP_TRY(pilot::launch_wide(dim3(wgs), s, p, pl->wide_rec));
     if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
-    HIP_TRY(pilot::launch_wide_value(dim3(clamp_wgs(pl, 2, tiles)), s, p, pl->wide_rec));
+    HIP_TRY(pilot::launch_wide_value(dim3(pilot::clamp_wgs(pl->n_cu, 2, tiles)), s, p, pl->wide_rec));
     if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
     return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
                        d_flags, s, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);

@@ -29,7 +29,7 @@
 
 namespace pilot {
 
-constexpr int QUAD_WAVES = 4, QUAD_KB = 4, QUAD_RING = 32, QUAD_MIN_K = 113, QUAD_MAX_K = 128;
+constexpr int QUAD_WAVES = 4, QUAD_KB = 4, QUAD_RING = 32;       // (QUAD_MIN_K, QUAD_MAX_K: sinkhorn_layout.hpp)
 
 // Workgroup barrier for data that travels through LDS only.  __syncthreads() also waits for the wave's outstanding GLOBAL stores
 // (s_waitcnt vmcnt(0): the outputs of finished pairs, a microsecond or two until L2 acknowledges them) -- in a kernel that meets at

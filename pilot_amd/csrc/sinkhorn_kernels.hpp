@@ -2,7 +2,7 @@
 // pilot_ot.hip.  Replaces the per-pair POT loop of pilotpy/tools/Trajectory.py:512-515.
 //
 // Mapping (see DESIGN.md "Kernel K2"):
-//   * one wavefront iterates TILE ordered pairs at once (TILE = 32 in f32, 16 in f64): the scalings
+//   * one wavefront iterates TILE ordered pairs at once (TILE = 16): the scalings
 //     u, v of its pairs form K x TILE panels and one Sinkhorn update is two panel products  G^T U  and
 //     G V  with the SHARED K x K Gibbs kernel G = exp(-M/reg);
 //   * G is the stationary MFMA "A" operand, pre-arranged once per launch in LDS in exactly the lane
@@ -28,10 +28,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace pilot {
+#include "sinkhorn_layout.hpp"
 
-constexpr int WAVE = 64;
-constexpr int WAVES_PER_WG = 4;
+namespace pilot {
 
 // flag bits, identical to include/pilot_ot.h
 constexpr int FLAG_CONVERGED = 1, FLAG_NAN = 2, FLAG_ABSORB_LAST = 4, FLAG_ABSORBED = 8, FLAG_F64 = 16;
@@ -42,24 +41,6 @@ constexpr int FLAG_CONVERGED = 1, FLAG_NAN = 2, FLAG_ABSORB_LAST = 4, FLAG_ABSOR
 // row-tile t in lane group g; cell types are dealt to slots in (tile, register, group) order, so k-step
 // (t, r) covers NGRP consecutive cell types and the first ceil(K / NGRP) k-steps hold all of them.
 // lidx_of_row(t, p): cell type of HARDWARE row p of row-tile t (the A operand is addressed by hardware row).
-
-struct CfgF32x32 {   // v_mfma_f32_32x32x2_f32: hardware row of register r in group g = (r&3) + 8*(r>>2) + 4*g
-    using T = float;
-    static constexpr bool SPLIT = false, HALF = false;
-    static constexpr int NP = 0;
-    static constexpr int TILE = 32, NREG = 16, NGRP = 2, VEC = 4;
-    using acc_t = float __attribute__((ext_vector_type(16)));
-    using vec4_t = float __attribute__((ext_vector_type(4)));
-    __host__ __device__ static constexpr int lidx(int t, int r, int g) { return 2 * (16 * t + r) + g; }
-    __host__ __device__ static constexpr int lidx_of_row(int t, int p) {
-        return lidx(t, (p & 3) + 4 * (p >> 3), (p >> 2) & 1);
-    }
-    __device__ static inline acc_t mfma(float a, float b, acc_t c) {
-        return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-    }
-    __device__ static inline float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-    __device__ static inline float eps() { return 1.1920929e-07f; }
-};
 
 struct CfgF32x16 {   // v_mfma_f32_16x16x4_f32: hardware row of register r in group g = 4*g + r
     using T = float;
@@ -142,21 +123,11 @@ struct CfgF64x16 {   // v_mfma_f64_16x16x4_f64 has its own C/D map: hardware row
     __device__ static inline double eps() { return 2.220446049250313e-16; }
 };
 
-// index of the LDS/global "A image" element read by `lane` for k-step (tp, r) and output row-tile t
-template <class C>
-__host__ __device__ constexpr int img_index(int RT, int tp, int r, int t, int lane) {
-    return (((tp * C::NREG + r) * RT + t) * WAVE) + lane;
-}
-// finished pairs wait in a wave-private LDS ring for their cost product: per slot the u panel and the v panel (KP values
-// each, [tile][group][reg] order) + 4 elements of padding (a lane's 16-byte reads of consecutive slots then fall on
-// different banks); ring_meta: per slot the output index, the flags and POT's plan scale (1, or 1/K^2)
-// (fp16-split configuration: the panels are parked as packed pieces, [part][k-block][lane group] x 16 bytes per column --
-// an odd row-tile count rounds up to whole k-blocks)
-template <class C> __host__ __device__ constexpr int ring_panel_elems(int RT) { return C::HALF ? 2 * ((RT + 1) / 2) * C::NGRP * 4 : RT * C::TILE; }
-template <class C> __host__ __device__ constexpr int ring_slot_stride(int RT) { return 2 * ring_panel_elems<C>(RT) + 4; }
-// (parked flush) 4-byte words a lane parks: its U registers, or its packed U pieces
-template <class C> __host__ __device__ constexpr int park_lane_elems(int RT) { return C::HALF ? 2 * ((RT + 1) / 2) * 4 : RT * C::NREG; }
-constexpr int RING_MAX = 16;
+// The traits of configuration C that the shape rules and the LDS layout of sinkhorn_layout.hpp read; the template forms forward to it.
+template <class C> constexpr CfgShape shape_of() { return {int(sizeof(typename C::T) / 4), C::NREG, C::SPLIT, C::HALF, C::NP, C::TILE, C::NGRP}; }
+template <class C> constexpr int ring_panel_elems(int RT) { return ring_panel_elems(shape_of<C>(), RT); }
+template <class C> constexpr int ring_slot_stride(int RT) { return ring_slot_stride(shape_of<C>(), RT); }
+template <class C> constexpr int park_lane_elems(int RT) { return park_lane_elems(shape_of<C>(), RT); }
 
 // Cross-lane exchanges between the lane groups of a column (lanes l, l^16, l^32, l^48) with gfx950's
 // v_permlane32_swap / v_permlane16_swap: VALU-rate, no LDS crossbar round trip (ds_bpermute costs ~100+ cycles of
@@ -215,7 +186,6 @@ template <class C> __device__ inline unsigned long long column_any_mask(bool pre
     if constexpr (C::NGRP == 4) f |= f >> 16;
     return f & ((1ull << C::TILE) - 1ull);
 }
-template <typename T> __device__ inline T abs_t(T x) { return x < T(0) ? -x : x; }
 
 // Where the stationary A operand of a product comes from: the lane-ordered image in LDS / global memory
 // (one ds_read / global load per MFMA), or -- when the whole image fits in <= 64 registers per lane (small K,
@@ -295,8 +265,7 @@ __device__ inline void panel_product(const AOp &aop, const typename C::acc_t (&I
 // the three all-padding registers of that tile as well.  Every kernel variant (stream, tracking) uses
 // this one function, so a pair's bits still do not depend on which kernel solves it.
 template <typename T> using pair_of = T __attribute__((ext_vector_type(2)));
-__host__ __device__ constexpr int tail_steps(int RT) { return (RT - 1) * 4 + 1; }   // k-steps when only register 0 of the last tile is live
-template <int RT> __host__ __device__ constexpr int tail_steps() { return tail_steps(RT); }
+template <int RT> constexpr int tail_steps() { return tail_steps(RT); }
 // global tail image (f32, written by sinkhorn_setup_kernel behind the first-product table): [form 0: G^T-form, 1: G-form]
 // [chain 0..1][k-step][lane] pairs (X[row 2c][k], X[row 2c+1][k]), row h = cell type 16 (RT-1) + h, k = lidx(step, lane / 16)
 template <int RT> __host__ __device__ constexpr int tail_form_stride() { return 2 * tail_steps<RT>() * WAVE; }  // in pairs
@@ -309,7 +278,6 @@ template <typename T, int RT, int TV> struct TailFromRegs {
     pair_of<T> a[(TV > 0 ? TV : 1) * tail_steps<RT>()];
     __device__ inline pair_of<T> operator()(int c, int st) const { return a[c * tail_steps<RT>() + st]; }
 };
-struct TailNone {};
 
 template <class C, int RT, int TV, class WOp>
 __device__ inline typename C::acc_t tail_rows(const WOp &w, const typename C::acc_t (&IN)[RT], const typename C::acc_t &last_init, int grp) {
@@ -759,7 +727,6 @@ __device__ inline void panel_product_split(const typename C::T *form, const type
 // fewer waves), and a variant that flags empty counters and steals from any live one cost the small kernels a wave per SIMD in
 // registers (profiles/r06/ab_experiments.md section 9).
 constexpr int QUEUE_SHARD_MAX_RT = 2;
-constexpr int QUEUE_SHARDS = 32, QUEUE_SHARD_STRIDE = 32;
 struct GridParams {
     const void *P;        // N x KP, element type T, every row in accumulator-slot order [tile][group][reg], 0 in padding;
                           // then N stop thresholds (one per column patient)
@@ -789,7 +756,7 @@ struct GridParams {
     int *fb_count;        //   instead of being written out, and the f64 kernel solves them again (see ring_flush)
     int *nan_list;        // nullable: pairs that end in NaN are appended here and re-solved by the POT-literal kernel, which
     int *nan_count;       //   reverts to the last good iterate like POT does (generic_kernels.hpp)
-    int debug;            // PILOT_OT_DEBUG of the call (read by no kernel; the host acts on its bits, DBG_* in grid_plan.hpp)
+    int debug;            // PILOT_OT_DEBUG of the call (read by no kernel; the host acts on its bits, DBG_* in sinkhorn_layout.hpp)
     const int *unequal;   // fp16-split configuration: control slot CTRL_UNEQUAL (see the refill of the stream kernel)
 };
 
@@ -798,9 +765,7 @@ struct GridParams {
 //   [first-product table: KP]                  (G^T u0)[slot], u0 = 1/K
 //   [tail-row weights]                         2 forms x 2 chains x tail_steps x WAVE pairs (VALU tail rows)
 //   [plain tables: 3 x 64 x WAVE]              G[lane][k], G[k][lane], (G o M)[lane][k] for solo_pairs
-template <class C> __host__ __device__ constexpr int form_elems(int RT) {
-    return C::SPLIT ? C::NP * ((RT + 1) / 2) * RT * WAVE * 4 : RT * C::TILE * RT * C::TILE;
-}
+template <class C> constexpr int form_elems(int RT) { return form_elems(shape_of<C>(), RT); }
 template <class C> __host__ __device__ constexpr int acc0_offset(int RT) { return 3 * form_elems<C>(RT); }
 template <class C> __host__ __device__ constexpr int tail_offset(int RT) { return acc0_offset<C>(RT) + RT * C::TILE; }
 template <class C> __host__ __device__ constexpr int plain_offset(int RT) { return tail_offset<C>(RT) + 2 * 2 * ((RT - 1) * 4 + 1) * WAVE * 2; }
@@ -1014,8 +979,8 @@ __device__ inline __attribute__((always_inline)) void ring_flush_body(const type
     using T = typename C::T;
     using acc_t = typename C::acc_t;
     constexpr int TILE = C::TILE, NREG = C::NREG, NGRP = C::NGRP;
-    constexpr int KP = RT * TILE;
-    constexpr int RSTRIDE = ring_slot_stride<C>(RT);
+    constexpr StreamLayout L = stream_layout(shape_of<C>(), RT, true, false, 0, 1, 0);     // (a slot is the same in every variant)
+    constexpr int RSTRIDE = L.slot, PE = L.panel;
     const int lane = threadIdx.x % WAVE;
     const int col = lane % TILE, grp = lane / TILE;
     const T *img_gm = static_cast<const T *>(p.img) + 2 * form_elems<C>(RT);     // read from L2, once per 16 finished pairs
@@ -1024,7 +989,6 @@ __device__ inline __attribute__((always_inline)) void ring_flush_body(const type
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const int s = col < cnt ? col : cnt - 1;        // columns beyond the fill level redo the last slot, unused
     const T *rec = ring + s * RSTRIDE;
-    constexpr int PE = ring_panel_elems<C>(RT);
     const T scale = rec[2 * PE];
     // one output row-tile at a time: only the v panel (or its bf16 pieces) is live
     T val = T(0), val1 = T(0);
@@ -1074,7 +1038,7 @@ __device__ inline __attribute__((always_inline)) void ring_flush_body(const type
         {
             acc_t Vr[RT];
 #pragma unroll
-            for (int t = 0; t < RT; ++t) load_regs<C>(rec + KP + (t * NGRP + grp) * NREG, Vr[t]);
+            for (int t = 0; t < RT; ++t) load_regs<C>(rec + PE + (t * NGRP + grp) * NREG, Vr[t]);
             split_panel<C, RT>(Vr, Bv);
         }
         const T *img_gm1 = static_cast<const T *>(p.img) + band1_offset<C>(RT) + 2 * form_elems<C>(RT);
@@ -1100,7 +1064,7 @@ __device__ inline __attribute__((always_inline)) void ring_flush_body(const type
     } else {
         acc_t Vr[RT];
 #pragma unroll
-        for (int t = 0; t < RT; ++t) load_regs<C>(rec + KP + (t * NGRP + grp) * NREG, Vr[t]);
+        for (int t = 0; t < RT; ++t) load_regs<C>(rec + PE + (t * NGRP + grp) * NREG, Vr[t]);
         const int n_last = (p.K - M::lidx(RT - 1, 0, 0) + NGRP - 1) / NGRP;     // live k-steps of the last row-tile
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
@@ -1155,68 +1119,14 @@ __device__ __attribute__((noinline)) void ring_flush(const typename C::T *ring, 
 // instead and the wave makes room for it itself: U goes to a wave-private LDS line, A and B are read again from the slot-
 // ordered proportions (L2) and ACC = G^T u is recomputed with one more product (bit-identical: same inputs, same
 // instruction sequence), V is dead at the flush point.  No scratch memory at all.
-template <class C, int RT, bool TRACK> constexpr bool parked_flush() { return C::SPLIT && !TRACK && RT <= 4; }
+template <class C, int RT, bool TRACK> constexpr bool parked_flush() { return parked_flush(shape_of<C>(), RT, TRACK); }
 
-constexpr int HANDOVER_BUF = 32, HANDOVER_FLUSH = 16;      // per-wave hand-over buffer of the fast kernels (ints), flush level
-constexpr int GREG_MAX = 64;
 #ifndef PILOT_AREG_MAX_RT
 #define PILOT_AREG_MAX_RT 4
 #endif
-#ifndef PILOT_SPLIT_OCC2_MAX_RT
-#define PILOT_SPLIT_OCC2_MAX_RT 4
-#endif
-#ifndef PILOT_SPLIT_OCC2_MAX_RT_TRACK
-#define PILOT_SPLIT_OCC2_MAX_RT_TRACK 4      // (K = 80 / 96 at reg 0.01: 160 -> 134 ms, 189 -> 146 ms with one wave and no spills; RT = 4: 32.5 -> 47.5 ms)
-#endif
-#ifndef PILOT_HALF_OCC2_MAX_RT
-#define PILOT_HALF_OCC2_MAX_RT 7             // (fp16-split, piece state: c4 at K = 100 26.85 -> 26.07 ms with two waves and 144 B of spills)
-#endif
-#ifndef PILOT_HALF_SOLO_MIN_RT
-#define PILOT_HALF_SOLO_MIN_RT 1         // (3: duplicates of the fp16-split configuration stay in tiles up to K = 32)
-#endif
-constexpr int HALF_SOLO_MIN_RT = PILOT_HALF_SOLO_MIN_RT;
-constexpr int HALF_OCC4_MAX_RT = 2;
-constexpr int SPLIT_OCC2_MAX_RT = PILOT_SPLIT_OCC2_MAX_RT, SPLIT_OCC2_MAX_RT_TRACK = PILOT_SPLIT_OCC2_MAX_RT_TRACK, HALF_OCC2_MAX_RT = PILOT_HALF_OCC2_MAX_RT;
-// The register and occupancy rules of the stream kernel, as functions of a configuration's traits: the kernel's
-// __launch_bounds__ and body instantiate them through the template forms, the host sizes its launches with the same functions.
-struct CfgShape { int w, nreg; bool split, half; };       // w = sizeof(T) / 4
-template <class C> __host__ __device__ constexpr CfgShape shape_of() { return {int(sizeof(typename C::T) / 4), C::NREG, C::SPLIT, C::HALF}; }
-// the operand image is kept in registers when it needs <= 64 VGPRs per lane and the cost is symmetric
-__host__ __device__ constexpr bool operands_in_regs(CfgShape c, int RT, bool sym) { return !c.split && sym && RT * c.nreg * RT * c.w <= GREG_MAX; }
+// The register and occupancy rules of the stream kernel (sinkhorn_layout.hpp), instantiated for the kernel's __launch_bounds__ and body
 template <class C, int RT, bool SYM> constexpr bool operands_in_regs() { return operands_in_regs(shape_of<C>(), RT, SYM); }
-// live panel registers per lane: A, B, U, V, ACC (+ RU, RV when tracking)
-__host__ __device__ constexpr int panel_regs(CfgShape c, int RT, bool sym, bool track, int tv) {
-    return (track ? 7 : 5) * RT * c.nreg * c.w + c.nreg * c.w + 56 +
-           (tv > 0 ? 24 * c.w : 0) +                         // tail accumulators, broadcast pairs, weights in flight
-           (c.split ? 3 * ((RT + 1) / 2) * 4 + 24 : 0) +     // split panel parts + operand parts in flight
-           (operands_in_regs(c, RT, sym) ? (RT * c.nreg * RT + 2 * tv * tail_steps(RT)) * c.w : 0);
-}
-template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int panel_regs() { return panel_regs(shape_of<C>(), RT, SYM, TRACK, TV); }
-__host__ __device__ constexpr int min_waves_per_simd(CfgShape c, int RT, bool sym, bool track, int tv) {
-    // split variants: two waves per SIMD up to SPLIT_OCC2_MAX_RT row tiles (tracking variants: SPLIT_OCC2_MAX_RT_TRACK), one wave
-    // with the whole register file beyond (3 waves per SIMD at RT <= 4: slower)
-    // (fp16-split fast kernel at one / two row-tiles: four -- 82 / 116 registers; with the sharded work queue the 634 x 14 cohort runs
-    // 0.242 / 0.195 / 0.185 / 0.193 ms at 2 / 3 / 4 / 6 workgroups per CU, K = 16 .. 32 -12 .. -22 %: tools/small_k_occupancy_probe.py)
-    if (c.half && !track && RT <= HALF_OCC4_MAX_RT) return 4;
-    if (c.split) return RT <= (track ? SPLIT_OCC2_MAX_RT_TRACK : (c.half ? HALF_OCC2_MAX_RT : SPLIT_OCC2_MAX_RT)) ? 2 : 1;
-    const int regs = panel_regs(c, RT, sym, track, tv);
-    return regs <= 128 ? 4 : (regs <= 168 ? 3 : (regs <= 256 ? 2 : 1));
-}
-template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int min_waves_per_simd() {
-    return min_waves_per_simd(shape_of<C>(), RT, SYM, TRACK, TV);
-}
-
-// solo_pairs (64 + ~45 registers of T per lane) rides in the fast launch when the cost is symmetric (PILOT's always is),
-// K <= 64, and the launch's register budget holds it without spilling
-__host__ __device__ constexpr bool solo_in_stream(CfgShape c, int RT, bool sym, bool track, int tv) {
-    const int mw = min_waves_per_simd(c, RT, sym, track, tv);
-    const int budget = mw >= 4 ? 128 : (mw == 3 ? 168 : 256);
-    // (round 3 had the fp16-split configuration keep its duplicates in tiles up to K = 32, when a tile's update was shorter
-    // than the one-wave-per-pair update; with the straight-line matrix-vector product it is the other way round again:
-    // c2 kernel 0.154 -> 0.136 ms, the 1/8 shard of c3 0.253 -> 0.186 ms.  A rule by SHAPE, never by load: the same pair takes
-    // the same path in every shard.)
-    return !track && sym && RT <= 4 && !(c.half && RT < HALF_SOLO_MIN_RT) && (64 + 45) * c.w <= budget;
-}
+template <class C, int RT, bool SYM, bool TRACK, int TV = 0> constexpr int min_waves_per_simd() { return min_waves_per_simd(shape_of<C>(), RT, SYM, TRACK, TV); }
 template <class C, int RT, bool SYM, bool TRACK, int TV> constexpr bool solo_in_stream() { return solo_in_stream(shape_of<C>(), RT, SYM, TRACK, TV); }
 
 // TRACK = false: plain scaling iterations; a pair whose POT residual scaling would exceed tau (i.e. POT
@@ -1232,9 +1142,11 @@ sinkhorn_stream_kernel(GridParams p) {
     using acc_t = typename M::acc_t;
     static_assert(!(C::HALF && TRACK), "the fp16-split configuration has no tracking variant (scalings beyond tau leave its scaled domain)");
     constexpr int TILE = M::TILE, NREG = M::NREG, NGRP = M::NGRP;
-    constexpr int KP = RT * TILE;
-    constexpr int FORM = form_elems<C>(RT);
-    constexpr int RSTRIDE = ring_slot_stride<C>(RT);
+    constexpr int KP = RT * TILE, FORM = form_elems<C>(RT);
+    // the workgroup's LDS with one exponent band and no ring slot (sinkhorn_layout.hpp).  A launch with two bands moves the table and
+    // what lies behind it alike, by the second band's images; its p.ring slots per wave move what lies behind the rings.
+    constexpr StreamLayout L0 = stream_layout(shape_of<C>(), RT, SYM, TRACK, TV, 1, 0);
+    constexpr int RSTRIDE = L0.slot;
     // fp16-split configuration: panels are 32 u, 32 v; a, b, the threshold and the error carry 2^25 (see CfgH32x16)
     constexpr T PANEL_SCALE = C::HALF ? T(H_PANEL_SCALE) : T(1), IN_SCALE = C::HALF ? T(H_IN_SCALE) : T(1);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1253,11 +1165,10 @@ sinkhorn_stream_kernel(GridParams p) {
     // stage the stationary operand: image 0 (and image 1 unless G is symmetric) + first-product table
     // (bf16-split tracking kernel with two exponent bands: the band-1 images follow the band-0 ones)
     const bool two_bands = C::SPLIT && TRACK && p.bands == 2;
-    const int n_img = (SYM ? 1 : 2) * FORM * (two_bands ? 2 : 1);
-    constexpr int n_tail = (TV > 0 && !C::SPLIT) ? (SYM ? 1 : 2) * TV * tail_steps<RT>() * WAVE * 2 : 0;
+    const int n_img = two_bands ? stream_layout(shape_of<C>(), RT, SYM, TRACK, TV, 2, 0).table : L0.table;
     {
         const T *g = static_cast<const T *>(p.img);
-        constexpr int n_b0 = (SYM ? 1 : 2) * FORM;
+        constexpr int n_b0 = L0.table;
         for (int i = threadIdx.x; i < n_b0; i += WAVE * WAVES_PER_WG) lds[i] = g[i];
         if (two_bands)
             for (int i = threadIdx.x; i < n_b0; i += WAVE * WAVES_PER_WG) lds[n_b0 + i] = g[band1_offset<C>(RT) + i];
@@ -1266,8 +1177,8 @@ sinkhorn_stream_kernel(GridParams p) {
             constexpr int n_form = TV * tail_steps<RT>() * WAVE * 2;           // floats per form actually used
             const T *tg = g + tail_offset<C>(RT);
             for (int i = threadIdx.x; i < n_form; i += WAVE * WAVES_PER_WG) {
-                lds[n_img + KP + i] = tg[i];
-                if constexpr (!SYM) lds[n_img + KP + n_form + i] = tg[2 * tail_form_stride<RT>() + i];
+                lds[n_img + (L0.tail - L0.table) + i] = tg[i];
+                if constexpr (!SYM) lds[n_img + (L0.tail - L0.table) + n_form + i] = tg[2 * tail_form_stride<RT>() + i];
             }
         }
     }
@@ -1275,19 +1186,18 @@ sinkhorn_stream_kernel(GridParams p) {
     const T *img_gt = lds;                                         // out = G^T in
     const T *img_g = SYM ? lds : lds + FORM;                       // out = G in
     // wave-private ring of finished pairs (u, v panels + scale / output index / flags in the slot's padding)
-    T *ring = lds + n_img + KP + n_tail + (threadIdx.x / WAVE) * p.ring * RSTRIDE;
+    T *ring = lds + n_img + (L0.rings - L0.table) + (threadIdx.x / WAVE) * p.ring * RSTRIDE;
     constexpr bool PARK = parked_flush<C, RT, TRACK>();
     // (PARK) one 16-byte line per lane and row-tile behind the rings: U while the inlined flush runs
     // (fp16-split configuration: the packed pieces of U, [part][k-block] x 16 bytes per lane)
     constexpr int PARK_LANE = park_lane_elems<C>(RT);
-    T *park = lds + n_img + KP + n_tail + WAVES_PER_WG * p.ring * RSTRIDE + (threadIdx.x / WAVE) * (PARK_LANE * WAVE) + (threadIdx.x % WAVE) * 4;
+    T *park = lds + n_img + (L0.park - L0.table) + WAVES_PER_WG * p.ring * RSTRIDE + (threadIdx.x / WAVE) * (PARK_LANE * WAVE) + (threadIdx.x % WAVE) * 4;
     // hand-over buffer (fast kernels): pairs in which POT would tau-absorb wait here, HANDOVER_BUF to a wave, and go to the
     // tracking list HANDOVER_FLUSH or more at a time.  One atomic on track_count per hand-over was 11 ns of one L2 atomic
     // unit per pair -- at K = 2, where a third of the 360 000 pairs absorb, 1.2 of the fast launch's 1.27 ms
     // (profiles/r04/small_k_scaling.txt).
     static_assert(HANDOVER_FLUSH - 1 + C::TILE <= HANDOVER_BUF, "a wave's hand-over buffer must hold one flush level plus one tile of pairs");
-    int *hb = reinterpret_cast<int *>(lds + n_img + KP + n_tail + WAVES_PER_WG * p.ring * RSTRIDE + (PARK ? WAVES_PER_WG * PARK_LANE * WAVE : 0)) +
-              (threadIdx.x / WAVE) * HANDOVER_BUF;
+    int *hb = reinterpret_cast<int *>(lds + n_img + (L0.hb - L0.table) + WAVES_PER_WG * p.ring * RSTRIDE) + (threadIdx.x / WAVE) * HANDOVER_BUF;
     int hb_cnt = 0;
     auto hb_flush = [&]() {
         int base = 0;
@@ -1309,7 +1219,7 @@ sinkhorn_stream_kernel(GridParams p) {
     const int col = lane % TILE, grp = lane / TILE;
     // tail-row weights: LDS images, or registers next to the register-resident operand image
     constexpr int NTF = (TV > 0 ? TV : 1) * tail_steps<RT>() * WAVE;            // pairs per form in LDS
-    const pair_of<T> *tl_base = reinterpret_cast<const pair_of<T> *>(acc0 + KP);
+    const pair_of<T> *tl_base = reinterpret_cast<const pair_of<T> *>(acc0 + (L0.tail - L0.table));
     const TailFromImage<T, RT> w_gt{tl_base, lane}, w_g{SYM ? tl_base : tl_base + NTF, lane};
     TailFromRegs<T, RT, (GREG && TV > 0) ? TV : 0> wreg;
     if constexpr (GREG && TV > 0 && !C::SPLIT) {
@@ -1321,7 +1231,7 @@ sinkhorn_stream_kernel(GridParams p) {
     auto product = [&](const AFromImage<C> &a_img, const TailFromImage<T, RT> &w_img, const acc_t (&IN)[RT], acc_t (&OUT)[RT],
                        const acc_t &init) {
         if constexpr (C::SPLIT) {
-            if constexpr (TRACK) panel_product_split<C, RT, (TV > 0)>(a_img.img, two_bands ? a_img.img + (SYM ? 1 : 2) * FORM : nullptr, lane, IN, OUT, init);
+            if constexpr (TRACK) panel_product_split<C, RT, (TV > 0)>(a_img.img, two_bands ? a_img.img + L0.table : nullptr, lane, IN, OUT, init);
             else panel_product_split<C, RT, (TV > 0)>(a_img.img, nullptr, lane, IN, OUT, init);
         } else if constexpr (TV > 0) {
             if constexpr (GREG) panel_product_tail<C, RT, TV>(areg, wreg, IN, OUT, init, grp);
@@ -1825,7 +1735,7 @@ sinkhorn_stream_kernel(GridParams p) {
                     const bool put = fin && ((fmask >> col) & 1ull) && rank < space;
                     if (put) {
                         T *rec = ring + (ring_cnt + rank) * RSTRIDE;
-                        constexpr int PE = ring_panel_elems<C>(RT);
+                        constexpr int PE = L0.panel;
                         if constexpr (C::HALF) {
 #pragma unroll
                             for (int part = 0; part < 2; ++part)
@@ -1839,7 +1749,7 @@ sinkhorn_stream_kernel(GridParams p) {
 #pragma unroll
                         for (int t = 0; t < RT; ++t) {
                             store_regs<C>(rec + (t * NGRP + grp) * NREG, U[t]);
-                            store_regs<C>(rec + KP + (t * NGRP + grp) * NREG, V[t]);
+                            store_regs<C>(rec + PE + (t * NGRP + grp) * NREG, V[t]);
                         }
                         }
                         if (grp == 0) {
@@ -2062,29 +1972,6 @@ __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT
 // tail of the launch.  Pairs are bucketed by -log2 of their L1 distance (NB buckets, 4 per octave, exact
 // duplicates in the last one) and the work list is emitted from the highest bucket down.  Three tiny
 // launches: bucket ids + histogram, (prefix is folded into) scatter.
-constexpr int ORDER_NB = 48;
-// Control block of a call (pilot_ot_plan::ctrl; ints, zeroed per call by the host): CTRL_INTS counters and queue heads, then the
-// order histograms and, from a 128-byte boundary, the ticket counters of the two sharded work queues.
-enum : int {
-    CTRL_TRACK_LEN = 0,          // length of track_list: the fast launch's hand-overs to the tracking launch
-    CTRL_GENERIC_HEAD = 0,       // queue head of a POT-literal call of its own (run_generic without a list)
-    CTRL_HEAD_FAST = 1,          // queue heads of the fast launch, the tracking launch and the solo waves
-    CTRL_HEAD_TRACK = 2,
-    CTRL_HEAD_SOLO = 3,
-    CTRL_SPLIT = 4,              // CTRL_SPLIT_INTS ints written by order_scatter_kernel, each the number of leading exact duplicates;
-    CTRL_SPLIT_INTS = 4,         //   the solo waves read the last one
-    CTRL_SOLO_LEN = CTRL_SPLIT + 3,
-    CTRL_FB_LEN = 8,             // length of the f64 fallback list (small reg, or pairs that left the f32 range) and its queue head
-    CTRL_FB_HEAD = 9,
-    CTRL_NAN_LEN = 10,           // length of the NaN list (pairs re-solved by the POT-literal kernel) and its queue head
-    CTRL_NAN_HEAD = 11,
-    CTRL_UNEQUAL = 12,           // set by the prep kernel when the rows of P do not all carry the same mass
-    CTRL_INTS = 16,
-    CTRL_ORDER_HIST = CTRL_INTS,                                              // 2 * ORDER_NB: histogram + scatter cursors
-    CTRL_SHARDS_AT = (CTRL_ORDER_HIST + 2 * ORDER_NB + 31) / 32 * 32,         // QUEUE_SHARDS counters of the fast launch
-    CTRL_SHARDS_TRACK_AT = CTRL_SHARDS_AT + QUEUE_SHARDS * QUEUE_SHARD_STRIDE,  // ... and of the tracking launch
-    CTRL_BLOCK_INTS = CTRL_SHARDS_TRACK_AT + QUEUE_SHARDS * QUEUE_SHARD_STRIDE,
-};
 
 // wave-aggregated LDS counter: lanes with equal `b` share one atomic; returns the lane's slot (base + rank among equals)
 __device__ inline int lds_count_aggregated(int *counters, int b, bool valid) {

@@ -1,18 +1,21 @@
-// Launch entry points of the Sinkhorn kernels.  The template instantiations are spread over several translation
-// units (sk_inst.hip compiled with -DSK_PART=0 for f32, 1 for f64, 2..5 for the VALU-tail variants: f32 tv1, f32 tv2,
-// f64 tv1, f64 tv2, 6 for the bf16-split configuration) so that `make -j` builds them in parallel.
+// Launch entry points of the Sinkhorn kernels: what pilot_ot_sinkhorn.hip calls to run the passes that plan_grid
+// (sinkhorn_layout.hpp) lays out.  The configuration ids, shape rules, LDS layout and control slots are stated there; this header
+// only checks that the kernels' configuration structs agree with them.  The template instantiations are spread over several
+// translation units (sk_inst.hip compiled with -DSK_PART=0 for f32, 1 for f64, 2..5 for the VALU-tail variants: f32 tv1, f32 tv2,
+// f64 tv1, f64 tv2, 6 / 7 for the bf16-split configuration, 8 / 9 for the fp16-split one; sk_wide.hip for the quad and wide kernels)
+// so that `make -j` builds them in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sinkhorn_kernels.hpp"
 
 namespace pilot {
 
-enum { CFG_F32 = 0, CFG_F64 = 1, CFG_S32 = 2, CFG_H32 = 3 };   // CfgF32x16, CfgF64x16, CfgS32x16 (bf16-split products, f32 values), CfgH32x16 (fp16-split)
-// the traits of configuration cfg that the stream kernel's shape rules read (min_waves_per_simd, solo_in_stream)
-inline CfgShape shape_of(int cfg) {
-    if (cfg == CFG_H32) return shape_of<CfgH32x16>();
-    return cfg == CFG_S32 ? shape_of<CfgS32x16>() : (cfg == CFG_F64 ? shape_of<CfgF64x16>() : shape_of<CfgF32x16>());
+constexpr bool same_shape(CfgShape a, CfgShape b) {
+    return a.w == b.w && a.nreg == b.nreg && a.split == b.split && a.half == b.half && a.np == b.np && a.tile == b.tile && a.ngrp == b.ngrp;
 }
+static_assert(same_shape(shape_of(CFG_F32), shape_of<CfgF32x16>()) && same_shape(shape_of(CFG_F64), shape_of<CfgF64x16>()) &&
+              same_shape(shape_of(CFG_S32), shape_of<CfgS32x16>()) && same_shape(shape_of(CFG_H32), shape_of<CfgH32x16>()),
+              "shape_of(cfg) in sinkhorn_layout.hpp must state the traits of the kernels' configuration structs");
 
 // persistent stream kernel (one tile per wave); track: tau-tracking variant
 hipError_t launch_stream_f32(int RT, bool sym, bool track, dim3 grid, size_t lds, hipStream_t s, const GridParams &p);
@@ -38,10 +41,8 @@ size_t wide_rec_elems();
 // 112 < K <= 128, symmetric cost: the fast pass of the fp16-split configuration with four waves per 16-pair tile (quad_kernels.hpp);
 // same GridParams, work list, hand-over and NaN lists as launch_stream_h32, one tile per 256-thread workgroup, costs formed in the kernel
 hipError_t launch_quad(dim3 grid, hipStream_t s, const GridParams &p);
-bool quad_covers(int K, bool sym);
 // elements of T in the operand block of a call (see img_layout in sinkhorn_kernels.hpp)
 size_t img_elems(int cfg, int RT);
-size_t form_elems_rt(int cfg, int RT);
 // offset (in 4-byte elements) of the tracking kernel's operand block inside the call's block; 0: the block itself
 size_t track_img_elems(int cfg, int RT);
 

@@ -95,10 +95,6 @@ hipError_t launch_prep(int cfg, const double *M, int K, int RT, double reg, void
     return prep_any<CfgF32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
                                main_queue_head, mode, n_blocks, s);
 }
-size_t form_elems_rt(int cfg, int RT) {
-    if (cfg == CFG_H32) return (size_t)form_elems<CfgH32x16>(RT);
-    return cfg == CFG_S32 ? (size_t)form_elems<CfgS32x16>(RT) : (cfg == CFG_F64 ? (size_t)form_elems<CfgF64x16>(RT) : (size_t)form_elems<CfgF32x16>(RT));
-}
 size_t track_img_elems(int cfg, int RT) { return cfg == CFG_H32 ? (size_t)track_img_offset<CfgH32x16>(RT) : 0; }
 size_t img_elems(int cfg, int RT) {
     if (cfg == CFG_H32) return (size_t)img_total<CfgH32x16>(RT);

@@ -19,6 +19,5 @@ hipError_t launch_quad(dim3 grid, hipStream_t s, const GridParams &p) {
     hipLaunchKernelGGL(sinkhorn_quad_kernel<8>, grid, dim3(WAVE * QUAD_WAVES), 0, s, p);
     return hipGetLastError();
 }
-bool quad_covers(int K, bool sym) { return sym && K >= QUAD_MIN_K && K <= QUAD_MAX_K; }
 
 }  // namespace pilot

@@ -535,6 +535,31 @@ int pilot_ot_csr_group_sums(pilot_ot_csr *csr, const int *codes, int n_groups, c
 int pilot_ot_group_sums_slice_rows(void);
 int pilot_ot_group_sums_col_block(void);
 
+/* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
+ * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
+ * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).
+ * Per column, in f64 whatever the storage dtype: mu the mean, sigma = sqrt(m2 / (n - 1)) with 0 -> 1; scale = 1:
+ * z = min((y - mu) / sigma, max_value), clipped on the upper side only (max_value = INFINITY: no clip); scale = 0: z = y
+ * (max_value is only checked).  The columns of Z are centred again and the eigenpairs of Zc^T Zc come from a symmetric Lanczos run
+ * with full re-orthogonalisation on the implicit operator v -> Zc^T (Zc v) (basis of min(n_sel, 1024) vectors, a fixed start
+ * vector, every sum in f64 in a fixed order, no floating-point atomic: the same bits from every run and from float32 and float64
+ * storage of the same values).
+ * Out (host, f64), k = n_comps in [1, min(n - 1, n_sel - 1, 64)], largest eigenvalue first: scores n x k = Zc V; pcs n_sel x k = V;
+ * variance[c] = lambda_c / (n - 1); variance_ratio[c] = variance[c] / the summed ddof-1 column variances of Z.  Sign: in every
+ * component the score of largest magnitude (lowest row on ties) is positive.  info[0] = Lanczos steps, info[1] = PILOT_OT_PCA_*.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, scale not 0 / 1, max_value not positive, a column out of range or named
+ * twice, n < 2, n_comps out of range, for the dense call dtype / ld / n_cols_total as in pilot_ot_group_moments; after the moments
+ * pass: a non-finite value in a selected column.  PILOT_OT_ENOTSUP: n > INT_MAX. */
+#define PILOT_OT_PCA_NOT_CONVERGED 1   /* the basis cap was reached before every wanted Ritz pair converged */
+#define PILOT_OT_PCA_RANK_DEFICIENT 2  /* the Krylov space ended before n_comps pairs, or a wanted lambda <= n_sel * DBL_EPSILON * lambda_0 */
+/* of a sparse matrix: the forward product reads the row form, the transposed one the column form (built if need be) */
+int pilot_ot_csr_pca(pilot_ot_csr *csr, const int *cols, int n_sel, int scale, double max_value, int n_comps, double *scores,
+                     double *pcs, double *variance, double *variance_ratio, int *info);
+/* of a dense row-major matrix (Y, Y_is_device, dtype, n, n_cols_total, ld: pilot_ot_group_moments's) */
+int pilot_ot_pca(const void *Y, int Y_is_device, int dtype, long long n, int n_cols_total, long long ld, const int *cols, int n_sel,
+                 int scale, double max_value, int n_comps, double *scores, double *pcs, double *variance, double *variance_ratio,
+                 int *info);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

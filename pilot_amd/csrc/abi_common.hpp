@@ -34,6 +34,8 @@ enum WsSlot {
     WS_GM_Y, WS_GM_AUX, WS_GM_PART, WS_GM_COUNT, WS_GM_OUT,                      // pilot_ot_moments.hip
     WS_CSR_COUNTS, WS_CSR_TOTAL, WS_CSR_CODES, WS_CSR_COLS, WS_CSR_OUT,          // pilot_ot_csr.hip
     WS_GS_Y, WS_GS_AUX, WS_GS_PART, WS_GS_OUT,                                   // pilot_ot_group_sums.hip
+    WS_PCA_V, WS_PCA_VEC, WS_PCA_Z, WS_PCA_PCS, WS_PCA_SCORES, WS_PCA_STATS, WS_PCA_COLS, WS_PCA_POS,   // pilot_ot_pca.hip
+    WS_PCA_SIDX, WS_PCA_SVAL, WS_PCA_CSVAL, WS_PCA_Y, WS_PCA_S, WS_PCA_PARTW,
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

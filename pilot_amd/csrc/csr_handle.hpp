@@ -1,5 +1,6 @@
 // The sparse matrix handle of the C ABI (include/pilot_ot.h, "sparse matrices"), shared by the translation units that read it:
-// pilot_ot_csr.hip owns its life cycle and the column form, pilot_ot_group_sums.hip reads the row form.  Host-side only.
+// pilot_ot_csr.hip owns its life cycle and the column form, pilot_ot_group_sums.hip reads the row form, pilot_ot_pca.hip both.
+// Host-side only.
 #pragma once
 
 struct pilot_ot_csr {

@@ -1024,6 +1024,15 @@ class DeviceCSR(_Closing):
         _lib.check(_lib.load().pilot_ot_csr_densify(h, None if cols is None else _lib.iptr(cols), n_sel, buf.ptr))
         return DeviceMatrix(buf.ptr, n, owner=buf, shape=(n, n_sel), dtype=self.dtype)
 
+    def pca(self, n_comps=50, scale=True, max_value=10.0, cols=None, return_info=False):
+        """:func:`pca` of the matrix: the forward product reads the row form, the transposed one the column form."""
+        n, n_total = self.shape
+        k, scale, max_value, cols, n_sel = _pca_args(n, n_total, n_comps, scale, max_value, cols)
+        out = _pca_outputs(n, n_sel, k)
+        _lib.check(_lib.load().pilot_ot_csr_pca(self._handle(), None if cols is None else _lib.iptr(cols), n_sel, scale, max_value, k,
+                                                *(_lib.dptr(a) for a in out[:4]), _lib.iptr(out[4])))
+        return _pca_result(out, return_info)
+
     def close(self):
         if self.h:
             _lib.load().pilot_ot_csr_destroy(self.h)
@@ -1091,6 +1100,78 @@ def group_sums(Y, codes, n_groups, cols=None):
         Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_total, Y.ld, _lib.iptr(codes), n_groups,
         None if cols is None else _lib.iptr(cols), n_sel, _lib.lptr(count), _lib.dptr(sums)))
     return count, sums
+
+
+# ---- principal components (K15; scanpy's scale + tl.pca(svd_solver='arpack') of pilotpy's extract_annot_expression) ----------
+PCA_MAX_COMPS = 64
+
+
+def _pca_args(n, n_total, n_comps, scale, max_value, cols):
+    """pca's arguments checked on the host: (n_comps, scale 0 / 1, max_value with None -> inf, cols int32 or None, columns)"""
+    if cols is not None:
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or (cols.size and cols.dtype.kind not in "iu"):
+            raise ValueError("cols: a 1-D array of column indices, got %s %s" % (cols.shape, cols.dtype))
+        if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= n_total):
+            raise ValueError("cols outside [0, %d)" % n_total)
+        if np.unique(cols).size != cols.size:
+            raise ValueError("cols names a column twice")
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+    n_sel = n_total if cols is None else cols.size
+    if n < 2:
+        raise ValueError("principal components need at least 2 rows, got %d" % n)
+    cap = min(n - 1, n_sel - 1, PCA_MAX_COMPS)
+    if isinstance(n_comps, bool) or int(n_comps) != n_comps or not 1 <= n_comps <= cap:
+        raise ValueError("n_comps=%r outside [1, min(rows - 1, columns - 1, %d)] = [1, %d]" % (n_comps, PCA_MAX_COMPS, cap))
+    if max_value is None:
+        max_value = np.inf
+    if isinstance(max_value, (str, bytes, bool)) or not np.isscalar(max_value) or not float(max_value) > 0.0:
+        raise ValueError("max_value=%r must be positive (None: no clip)" % (max_value,))
+    return int(n_comps), int(bool(scale)), float(max_value), cols, n_sel
+
+
+def _pca_outputs(n, n_sel, k):
+    return np.empty((n, k)), np.empty((n_sel, k)), np.empty(k), np.empty(k), np.zeros(2, dtype=np.int32)
+
+
+def _pca_result(out, return_info):
+    scores, pcs, variance, ratio, info = out
+    steps, flags = int(info[0]), int(info[1])
+    if return_info:
+        return scores, pcs, variance, ratio, dict(steps=steps, flags=flags, converged=not flags & _lib.PCA_NOT_CONVERGED,
+                                                  rank_deficient=bool(flags & _lib.PCA_RANK_DEFICIENT))
+    if flags & _lib.PCA_RANK_DEFICIENT:
+        raise ValueError("pca: the matrix has fewer than n_comps=%d principal directions (rank-deficient)" % scores.shape[1])
+    if flags & _lib.PCA_NOT_CONVERGED:
+        raise ValueError("pca: Lanczos did not converge in %d steps" % steps)
+    return scores, pcs, variance, ratio
+
+
+def pca(Y, n_comps=50, scale=True, max_value=10.0, cols=None, return_info=False):
+    """K15: the principal components of the rows x columns matrix ``Y`` (include/pilot_ot.h, "principal components") -- scanpy's
+    ``pp.scale(max_value)`` followed by ``tl.pca`` restated, without ever forming the standardised matrix.  ``Y``: a
+    :class:`DeviceCSR` (forwarded to its own method), a C-contiguous float32 / float64 numpy array, a :class:`DeviceMatrix` or
+    :func:`device_columns` of one.  ``scale``: every selected column is centred, divided by its ddof-1 standard deviation (0 -> 1)
+    and clipped from above at ``max_value`` (None: no clip) first; False: the values as they are.  ``cols``: the selected columns,
+    distinct, in any order (default: all).  Returns ``(scores, pcs, variance, variance_ratio)``, all float64: rows x n_comps,
+    columns x n_comps, and two vectors of n_comps, largest variance first; in every component the score of largest magnitude is
+    positive.  All arithmetic is float64 in a fixed order: a repeated call, and float32 / float64 uploads of the same values,
+    return the same bits.  Every argument is checked before any device work (ValueError: fewer than 2 rows, ``n_comps`` outside
+    ``[1, min(rows - 1, columns - 1, 64)]``, a column out of range or repeated, ``max_value`` not positive, a non-finite value
+    of a host array).  A matrix with fewer than ``n_comps`` directions, or no convergence within the basis of min(columns, 1024)
+    vectors, raises ValueError; with ``return_info`` nothing is raised and a fifth item, ``dict(steps, flags, converged,
+    rank_deficient)``, tells."""
+    if isinstance(Y, DeviceCSR):
+        return Y.pca(n_comps=n_comps, scale=scale, max_value=max_value, cols=cols, return_info=return_info)
+    Y = _dense_arg(Y, "Y", mode="strict")
+    k, scale, max_value, cols, n_sel = _pca_args(Y.rows, Y.cols, n_comps, scale, max_value, cols)
+    if not Y.on_dev and not np.isfinite(Y.keep if cols is None else Y.keep[:, cols]).all():
+        raise ValueError("Y holds a non-finite value")
+    out = _pca_outputs(Y.rows, n_sel, k)
+    _lib.check(_lib.load().pilot_ot_pca(Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld,
+                                        None if cols is None else _lib.iptr(cols), n_sel, scale, max_value, k,
+                                        *(_lib.dptr(a) for a in out[:4]), _lib.iptr(out[4])))
+    return _pca_result(out, return_info)
 
 
 def fitted_curves(params, model, times, noise=None, device=False):

@@ -31,6 +31,8 @@ highly_variable_genes,                         scanpy's pp.highly_variable_genes
 cell_type_diff_two_sub_patient_groups          plot/ploting.py:460-556 (the table, without the plot or the file)
 pseudobulk_counts, pseudobulk_inputs,          plot/pseudobulk_DE_analysis.py:590-610 (get_pseudobulk_DE's aggregation and the
 deseq2_size_factors                            inputs of its R calls) and DESeq2's median-of-ratios size factors restated
+pca, extract_annot_expression                  Trajectory.py:171-228 (scanpy's normalize_total / log1p / scale / tl.pca restated;
+                                               no reclustering)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -778,6 +780,91 @@ def _lib_check_normalize(X, cols, out):
     from . import _lib
     _lib.check(_lib.load().pilot_ot_normalize_log1p(X.ctypes.data, 0 if X.dtype == np.float32 else 1, X.shape[0], X.shape[1],
                                                     1e4, _lib.iptr(cols), int(cols.size), out.ctypes.data))
+
+
+# ---- principal components (Trajectory.py:199-208: normalize_total -> log1p -> scale(max_value) -> sc.tl.pca) ------------------
+def _gene_columns(adata, genes, n_vars):
+    """``genes`` (names of ``adata.var_names`` or a boolean mask over them) as column indices; None: every column"""
+    if genes is None:
+        return None
+    genes = np.asarray(genes)
+    if genes.ndim != 1:
+        raise ValueError("genes: a 1-D list of names or a boolean mask, got shape %s" % (genes.shape,))
+    if genes.dtype == bool:
+        if genes.size != n_vars:
+            raise ValueError("genes: a mask of %d entries for %d genes" % (genes.size, n_vars))
+        return np.flatnonzero(genes).astype(np.int32)
+    where = pd.Index(adata.var_names).get_indexer(genes)
+    if (where < 0).any():
+        raise ValueError("genes not in adata.var_names: %s" % list(genes[where < 0][:5]))
+    return where.astype(np.int32)
+
+
+def pca(adata, n_comps=50, normalize=False, target_sum=1e4, scale=True, max_value=10, genes=None, key_added="X_pca"):
+    """The embedding the other entry points read from ``adata.obsm['X_pca']``, made on the device from ``adata.X``: optionally
+    scanpy's ``normalize_total(target_sum)`` + ``log1p`` (``normalize``; on the device copy only, ``adata.X`` is untouched), then
+    ``pp.scale(max_value)`` and ``tl.pca`` restated (``engine.pca``; scanpy is not installed where this library is built and
+    tested, so the rule is UNPINNED here: scanpy 1.9's ddof-1 scale with the clip on the upper side only, scikit-learn 1.3's
+    u-based sign).  ``genes``: the genes to use, names or a boolean mask (default: all).  A scipy sparse ``adata.X`` goes up once as
+    an ``engine.DeviceCSR`` and is never made dense; the standardised matrix is not formed either way.  Like scanpy, ``n_comps``
+    is lowered to ``min(cells, genes) - 1`` when it is not below ``min(cells, genes)``.  Writes ``adata.obsm[key_added]`` (cells x
+    n_comps, float32 as scanpy gives for float32 data), ``adata.varm['PCs']`` (all genes x n_comps, zero rows for genes not used)
+    and ``adata.uns['pca'] = {'variance', 'variance_ratio'}``; returns the scores.  Differences from scanpy: all arithmetic is
+    float64 (scanpy scales in float32), the Lanczos start vector is fixed (ARPACK's is random), and Z is never dense."""
+    X = adata.X
+    n, n_vars = X.shape
+    cols = _gene_columns(adata, genes, n_vars)
+    n_sel = n_vars if cols is None else cols.size
+    if not 0 < float(target_sum) < np.inf:
+        raise ValueError("target_sum=%r must be positive" % (target_sum,))
+    if min(n, n_sel) >= 2 and n_comps is not None and n_comps >= min(n, n_sel):
+        n_comps = min(n, n_sel) - 1
+    engine._pca_args(n, n_vars, n_comps, scale, max_value, cols)       # every argument judged before anything goes up
+    if _is_sparse(X):
+        if not np.isfinite(X.data).all():
+            raise ValueError("adata.X holds a non-finite value")
+        Y = _sparse_rows(X, None)
+        if normalize and Y.nnz:
+            Y.normalize_log1p(target_sum)
+    else:
+        Y = _dense_rows(X, slice(None))
+        if not np.isfinite(Y).all():
+            raise ValueError("adata.X holds a non-finite value")
+        if normalize and Y.size:
+            from . import _lib
+            out = np.empty_like(Y)
+            every = np.arange(n_vars, dtype=np.int32)
+            _lib.check(_lib.load().pilot_ot_normalize_log1p(Y.ctypes.data, _lib.dtype_code(Y.dtype), n, n_vars, float(target_sum),
+                                                            _lib.iptr(every), n_vars, out.ctypes.data))
+            Y = out
+    scores, pcs, variance, ratio = engine.pca(Y, n_comps=n_comps, scale=scale, max_value=max_value, cols=cols)
+    del Y
+    PCs = np.zeros((n_vars, pcs.shape[1]))
+    PCs[slice(None) if cols is None else cols] = pcs
+    scores = scores.astype(np.float32)
+    adata.obsm[key_added] = scores
+    adata.varm["PCs"] = PCs
+    adata.uns["pca"] = {"variance": variance, "variance_ratio": ratio}
+    return scores
+
+
+def extract_annot_expression(adata, columns=["cell_type_original", "patient_region", "region", "X_pca"], reclustering=False,
+                             reduction=False, resu=0.1, max_value=10, target_sum=1e4):
+    """(data, annot) of a scRNA data set (Trajectory.py:171-228).  ``data``: the embedding as a frame with columns ``PCA_1..``
+    -- ``adata.obsm[columns[3]]``, or with ``reduction`` the one :func:`pca` makes from ``adata.X`` (normalize_total(target_sum),
+    log1p, scale(max_value), 50 components) and writes to ``adata.obsm['X_pca']``; unlike the reference, ``adata.X`` itself is
+    left as it is.  ``annot``: ``adata.obs[columns[:3]]`` renamed ``cell_types, sampleID, status``.  ``reclustering`` (Louvain
+    communities of scanpy's neighbour graph) is not implemented and raises before any device work."""
+    if reclustering:
+        raise NotImplementedError("extract_annot_expression: reclustering (Louvain on the neighbour graph) is not implemented")
+    if reduction:
+        data = pca(adata, normalize=True, target_sum=target_sum, scale=True, max_value=max_value)
+    else:
+        data = adata.obsm[columns[3]]
+    data = pd.DataFrame(data, columns=["PCA_" + str(i) for i in range(1, data.shape[1] + 1)])
+    annot = adata.obs[list(columns[0:3])].copy(deep=False)
+    annot.columns = ["cell_types", "sampleID", "status"]
+    return data, annot
 
 
 # ---- gene-cluster differentiation (Gene_cluster_specific.py:8-201, Trajectory.py:1129-1172) --------------------------------

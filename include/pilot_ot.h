@@ -560,6 +560,28 @@ int pilot_ot_pca(const void *Y, int Y_is_device, int dtype, long long n, int n_c
                  int scale, double max_value, int n_comps, double *scores, double *pcs, double *variance, double *variance_ratio,
                  int *info);
 
+/* ---- cell neighbours (K16): the exact k-nearest-neighbour graph of the rows of X (the cells of an embedding, n x D row-major,
+ * X_is_device / dtype / ld as in pilot_ot_group_moments) and the per-row part of UMAP's fuzzy simplicial set -- what pilotpy takes
+ * from scanpy's pp.neighbors (tools/Trajectory.py:217-220, 1045-1060).  The n x n distance matrix is never formed.
+ * A squared distance is the direct sum over d of (x_d - y_d)^2 in the element type, d ascending; metric 0 (euclidean) returns its
+ * IEEE square root, metric 1 (cosine) divides every row by its f64 norm first (quotient rounded to the element type) and returns
+ * half the sum, 1 - cos for unit rows.  Row i itself is left out by index.  The neighbours of a row are ordered by (distance,
+ * index) ascending; no atomics, the same call returns the same bits.  Every returned distance is within (D + 6) u relative of the
+ * exact distance between the stored (for cosine: the normalised and rounded) values, u = 2^-24 / 2^-53.
+ * Query rows row_begin .. row_end - 1; the corpus is always all n rows.  indices / distances: (row_end - row_begin) x k, host.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, D < 1, ld < D, dtype, metric, k < 1, n < k + 1, a row range that is empty
+ * or not inside [0, n); after the flag pass: a non-finite value, or under cosine an all-zero row (the message names the first such
+ * row).  PILOT_OT_ENOTSUP: k > PILOT_OT_KNN_ROWS_MAX_K, n > INT_MAX. */
+#define PILOT_OT_KNN_ROWS_MAX_K 64
+int pilot_ot_knn_rows(const void *X, int X_is_device, int dtype, long long n, int D, long long ld, int metric, int k,
+                      long long row_begin, long long row_end, int *indices, double *distances);
+/* distances: n x k (host, finite, >= 0), the distances of every cell to its k = n_neighbors - 1 neighbours.  Per row, in f64:
+ * rho = the smallest non-zero distance (0: none); sigma = the value a bisection of at most 64 steps (start 1, doubling while no
+ * upper end is known) reaches for sum_j exp(-max(0, d_j - rho) / sigma) = log2(k + 1) within 1e-5, then floored at 1e-3 x the row's
+ * mean distance (rho > 0) or x the mean of all distances (rho = 0); weights[j] = 1 where d_j - rho <= 0 or sigma = 0, else
+ * exp(-(d_j - rho) / sigma).  weights: n x k, sigma, rho: n (host).  Refusals as above (k, n, NULL; a distance not finite or < 0). */
+int pilot_ot_knn_smooth(const double *distances, long long n, int k, double *weights, double *sigma, double *rho);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

@@ -25,6 +25,7 @@ FLAG_CONVERGED, FLAG_NAN, FLAG_ABSORB_LAST, FLAG_ABSORBED, FLAG_F64 = 1, 2, 4, 8
 DIFFMAP_NOT_CONVERGED, DIFFMAP_DEGENERATE = 1, 2
 TRAJFIT_OLS, TRAJFIT_HUBER, TRAJFIT_NOT_CONVERGED = 0, 1, 1
 PCA_NOT_CONVERGED, PCA_RANK_DEFICIENT = 1, 2
+KNN_ROWS_MAX_K = 64
 
 # every symbol include/pilot_ot.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -48,7 +49,7 @@ SYMBOLS = [
     "pilot_ot_csr_upload", "pilot_ot_csr_destroy", "pilot_ot_csr_normalize_log1p", "pilot_ot_csr_build_columns", "pilot_ot_csr_slice_rows",
     "pilot_ot_csr_column_nnz", "pilot_ot_csr_group_moments", "pilot_ot_csr_densify",
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
-    "pilot_ot_csr_pca", "pilot_ot_pca",
+    "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -179,6 +180,9 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_group_sums_col_block.argtypes = []
     L.pilot_ot_csr_pca.argtypes = [c_vp, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_pca.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
+    L.pilot_ot_knn_rows.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, ctypes.c_longlong,
+                                    ctypes.c_longlong, ip, dp]
+    L.pilot_ot_knn_smooth.argtypes = [dp, ctypes.c_longlong, c_int, dp, dp, dp]
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

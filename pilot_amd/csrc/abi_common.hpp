@@ -36,6 +36,7 @@ enum WsSlot {
     WS_GS_Y, WS_GS_AUX, WS_GS_PART, WS_GS_OUT,                                   // pilot_ot_group_sums.hip
     WS_PCA_V, WS_PCA_VEC, WS_PCA_Z, WS_PCA_PCS, WS_PCA_SCORES, WS_PCA_STATS, WS_PCA_COLS, WS_PCA_POS,   // pilot_ot_pca.hip
     WS_PCA_SIDX, WS_PCA_SVAL, WS_PCA_CSVAL, WS_PCA_Y, WS_PCA_S, WS_PCA_PARTW,
+    WS_KNN_X, WS_KNN_UNIT, WS_KNN_FLAGS, WS_KNN_BEST_D, WS_KNN_BEST_I, WS_KNN_OUT_D, WS_KNN_OUT_I, WS_KNN_SM_IN, WS_KNN_SM_OUT,   // pilot_ot_knn.hip
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

@@ -1174,6 +1174,95 @@ def pca(Y, n_comps=50, scale=True, max_value=10.0, cols=None, return_info=False)
     return _pca_result(out, return_info)
 
 
+# ---- cell neighbours (K16; scanpy's pp.neighbors of pilotpy's extract_annot_expression / reclustering_data) -------------------
+KNN_MAX_K = _lib.KNN_ROWS_MAX_K
+
+
+def _knn_k(k, what="k"):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError("%s=%r outside [1, %d]" % (what, k, KNN_MAX_K))
+    return int(k)
+
+
+def knn(X, k, metric="euclidean", rows=None):
+    """K16: the exact ``k`` nearest neighbours of rows of the n x D matrix ``X`` among all its rows (include/pilot_ot.h, "cell
+    neighbours"), by brute force on the device: the n x n distance matrix is never formed.  ``X``: a numpy array (a view with a
+    unit column stride goes up as it is) or a :class:`DeviceMatrix`, float32 or float64; other dtypes convert to float64.
+    ``metric``: ``"euclidean"`` or ``"cosine"`` (1 - cos, from unit rows).  ``rows=(begin, end)``: the query rows (default: all);
+    the corpus is always all n rows.  Returns ``(indices int32 (m, k), distances float64 (m, k))``; a row is never its own
+    neighbour (left out by index, so duplicates of it are neighbours at distance 0), and its neighbours are ordered by (distance,
+    index) ascending.  Distances are direct sums of squared differences in X's dtype: every one is within (D + 6) u relative of the
+    exact distance between the stored values (u = 2^-24 / 2^-53), far from the origin too, and a repeated call returns the same
+    bits.  ValueError before any device work: ``k`` outside [1, 64], n < k + 1, an unknown metric, a bad row range; from the
+    device's first pass: a non-finite value, or under cosine an all-zero row (the message names the row)."""
+    Y = _dense_arg(X, "X", mode="strided", axes=" (rows x dims)")
+    k = _knn_k(k)
+    if metric not in _lib.ROW_METRICS:
+        raise ValueError("metric=%r: %s" % (metric, " or ".join(_lib.ROW_METRICS)))
+    n, D = Y.rows, Y.cols
+    if D < 1:
+        raise ValueError("X has no columns")
+    if n < k + 1:
+        raise ValueError("k=%d neighbours need at least k + 1 rows, got %d" % (k, n))
+    if n > np.iinfo(np.int32).max:
+        raise NotImplementedError("%d rows need more than 32-bit row indices" % n)
+    begin, end = (0, n) if rows is None else rows
+    if isinstance(begin, bool) or isinstance(end, bool) or int(begin) != begin or int(end) != end or not 0 <= begin < end <= n:
+        raise ValueError("rows=%r: (begin, end) with 0 <= begin < end <= %d" % (rows, n))
+    m = int(end) - int(begin)
+    indices, distances = np.empty((m, k), dtype=np.int32), np.empty((m, k))
+    _lib.check(_lib.load().pilot_ot_knn_rows(Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), n, D, Y.ld, _lib.ROW_METRICS[metric], k,
+                                             int(begin), int(end), _lib.iptr(indices), _lib.dptr(distances)))
+    return indices, distances
+
+
+def _knn_graph_args(indices, distances, n_neighbors):
+    distances = np.ascontiguousarray(distances, dtype=np.float64)
+    if distances.ndim != 2 or isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)) \
+            or distances.shape[1] != n_neighbors - 1:
+        raise ValueError("distances %s: n x (n_neighbors - 1) with n_neighbors=%r" % (distances.shape, n_neighbors))
+    _knn_k(distances.shape[1], "n_neighbors - 1")
+    if distances.shape[0] < 1:
+        raise ValueError("distances has no rows")
+    if not (np.isfinite(distances).all() and (distances >= 0).all()):
+        raise ValueError("distances must be finite and not negative")
+    if indices is not None:
+        indices = np.asarray(indices)
+        if indices.shape != distances.shape or indices.dtype.kind not in "iu":
+            raise ValueError("indices: integers of shape %s, got %s %s" % (distances.shape, indices.shape, indices.dtype))
+        if indices.size and (indices.min() < 0 or indices.max() >= distances.shape[0]):
+            raise ValueError("indices outside [0, %d): the graph needs every row's neighbours" % distances.shape[0])
+    return indices, distances
+
+
+def knn_smooth(distances, n_neighbors):
+    """The per-row part of UMAP's fuzzy simplicial set on the device, in float64: ``distances`` n x (n_neighbors - 1) as
+    :func:`knn` returns them (``n_neighbors`` counts the cell itself, as scanpy's does).  Returns ``(weights (n, n_neighbors - 1),
+    sigma (n,), rho (n,))``: rho the smallest non-zero distance of the row (0: none), sigma from at most 64 bisection steps of
+    ``sum_j exp(-max(0, d_j - rho) / sigma) = log2(n_neighbors)`` to 1e-5, floored at 1e-3 x the row's mean distance (rho = 0: x the
+    mean of all distances), weights 1 where ``d_j <= rho`` or sigma = 0 and ``exp(-(d_j - rho) / sigma)`` otherwise."""
+    _, distances = _knn_graph_args(None, distances, n_neighbors)
+    n, k = distances.shape
+    weights, sigma, rho = np.empty((n, k)), np.empty(n), np.empty(n)
+    _lib.check(_lib.load().pilot_ot_knn_smooth(_lib.dptr(distances), n, k, _lib.dptr(weights), _lib.dptr(sigma), _lib.dptr(rho)))
+    return weights, sigma, rho
+
+
+def knn_connectivities(indices, distances, n_neighbors):
+    """UMAP's symmetric connectivities of the whole graph ``(indices, distances)`` of :func:`knn`: the weights W of
+    :func:`knn_smooth` placed at (i, indices[i, c]) give A, and the result is the fuzzy union A + A^T - A o A^T, an n x n scipy CSR
+    matrix in float64, exactly symmetric (the union is formed on the host: it is O(n k))."""
+    import scipy.sparse as sp
+    indices, distances = _knn_graph_args(indices, distances, n_neighbors)
+    weights = knn_smooth(distances, n_neighbors)[0]
+    n, k = distances.shape
+    A = sp.csr_matrix((weights.ravel(), indices.ravel().astype(np.int32), np.arange(0, n * k + 1, k)), shape=(n, n))
+    At = A.T.tocsr()
+    C = (A + At - A.multiply(At)).tocsr()
+    C.eliminate_zeros()
+    return C
+
+
 def fitted_curves(params, model, times, noise=None, device=False):
     """One standardised curve per gene over ``times``: ``design(model[g], t) @ params[g]`` (``params``: G x 3 = Intercept, Treat,
     Treat2; ``model``: indices into :data:`TRAJFIT_MODELS`, or their names), plus, with ``noise`` (T x G per-time-point spreads,

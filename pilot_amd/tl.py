@@ -33,6 +33,8 @@ pseudobulk_counts, pseudobulk_inputs,          plot/pseudobulk_DE_analysis.py:59
 deseq2_size_factors                            inputs of its R calls) and DESeq2's median-of-ratios size factors restated
 pca, extract_annot_expression                  Trajectory.py:171-228 (scanpy's normalize_total / log1p / scale / tl.pca restated;
                                                no reclustering)
+neighbors                                      Trajectory.py:217-220, 1045-1060 (scanpy's pp.neighbors: the exact kNN graph of the
+                                               cells and UMAP's connectivities restated; no Louvain)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -854,9 +856,11 @@ def extract_annot_expression(adata, columns=["cell_type_original", "patient_regi
     -- ``adata.obsm[columns[3]]``, or with ``reduction`` the one :func:`pca` makes from ``adata.X`` (normalize_total(target_sum),
     log1p, scale(max_value), 50 components) and writes to ``adata.obsm['X_pca']``; unlike the reference, ``adata.X`` itself is
     left as it is.  ``annot``: ``adata.obs[columns[:3]]`` renamed ``cell_types, sampleID, status``.  ``reclustering`` (Louvain
-    communities of scanpy's neighbour graph) is not implemented and raises before any device work."""
+    communities of scanpy's neighbour graph) is not implemented and raises before any device work: :func:`neighbors` makes the
+    graph, the Louvain step is the missing part."""
     if reclustering:
-        raise NotImplementedError("extract_annot_expression: reclustering (Louvain on the neighbour graph) is not implemented")
+        raise NotImplementedError("extract_annot_expression: reclustering is not implemented: tl.neighbors builds the neighbour graph "
+                                  "(obsp['distances'] / ['connectivities']), the Louvain communities of it are the missing part")
     if reduction:
         data = pca(adata, normalize=True, target_sum=target_sum, scale=True, max_value=max_value)
     else:
@@ -865,6 +869,55 @@ def extract_annot_expression(adata, columns=["cell_type_original", "patient_regi
     annot = adata.obs[list(columns[0:3])].copy(deep=False)
     annot.columns = ["cell_types", "sampleID", "status"]
     return data, annot
+
+
+def neighbors(adata, n_neighbors=15, n_pcs=None, use_rep="X_pca", metric="euclidean", key_added=None):
+    """The cell neighbour graph scanpy's ``pp.neighbors`` gives (Trajectory.py:217-220, 1045-1060), made on the device from
+    ``adata.obsm[use_rep]`` (its first ``n_pcs`` columns, read as a strided view without a copy): the exact ``n_neighbors - 1``
+    nearest other cells of every cell (``engine.knn``; ``n_neighbors`` counts the cell itself, as scanpy's does) under
+    ``metric`` ``"euclidean"`` or ``"cosine"``, and UMAP's fuzzy-simplicial-set connectivities of them
+    (``engine.knn_connectivities``).  Writes ``adata.obsp['distances']`` (cells x cells CSR, float64, ``n_neighbors - 1`` stored
+    entries per row before ``eliminate_zeros()``, which scanpy also applies), ``adata.obsp['connectivities']`` (symmetric CSR,
+    float64) and ``adata.uns['neighbors'] = {'connectivities_key', 'distances_key', 'params': {n_neighbors, method: 'umap', metric,
+    use_rep, n_pcs}}``; with ``key_added`` the names are ``uns[key_added]``, ``obsp[key_added + '_distances']`` and
+    ``obsp[key_added + '_connectivities']``, as scanpy names them.  An ``adata`` without ``obsp`` gets a dict.  Returns None.
+    ValueError before any device work: a missing representation, ``n_neighbors < 2`` or ``n_neighbors - 1 > 64``, ``n_pcs``
+    outside the representation.  Differences from scanpy: the graph is exact at every size (scanpy switches to approximate
+    NN-descent above 4 096 cells); ties are ordered by index; sigma, rho and the weights are float64 (umap-learn: float32);
+    ``method='gauss'``, ``knn=False`` and custom metrics are not offered.  scanpy and umap-learn are not installed where this
+    library is built and tested, so the rule is UNPINNED here: it is held to tests/neighbors_restatement.py."""
+    import scipy.sparse as sp
+    if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)) or n_neighbors < 2:
+        raise ValueError("n_neighbors=%r: an integer of at least 2 (it counts the cell itself)" % (n_neighbors,))
+    if n_neighbors - 1 > engine.KNN_MAX_K:
+        raise ValueError("n_neighbors=%d: at most %d" % (n_neighbors, engine.KNN_MAX_K + 1))
+    if metric not in ("euclidean", "cosine"):
+        raise ValueError("metric=%r: euclidean or cosine" % (metric,))
+    if use_rep not in adata.obsm:
+        raise ValueError("adata.obsm has no %r (tl.pca makes 'X_pca')" % (use_rep,))
+    X = adata.obsm[use_rep]
+    if len(X.shape) != 2:
+        raise ValueError("adata.obsm[%r] must be 2-D, got %s" % (use_rep, X.shape))
+    if n_pcs is not None:
+        if isinstance(n_pcs, bool) or not isinstance(n_pcs, (int, np.integer)) or not 1 <= n_pcs <= X.shape[1]:
+            raise ValueError("n_pcs=%r outside [1, %d], the columns of adata.obsm[%r]" % (n_pcs, X.shape[1], use_rep))
+        X = np.asarray(X)[:, :int(n_pcs)]
+    n = X.shape[0]
+    if n < n_neighbors:
+        raise ValueError("n_neighbors=%d needs at least as many cells, got %d" % (n_neighbors, n))
+    k = int(n_neighbors) - 1
+    indices, distances = engine.knn(X, k, metric=metric)
+    connectivities = engine.knn_connectivities(indices, distances, int(n_neighbors))
+    graph = sp.csr_matrix((distances.ravel(), indices.ravel(), np.arange(0, n * k + 1, k)), shape=(n, n))
+    graph.eliminate_zeros()
+    prefix = "" if key_added is None else key_added + "_"
+    if getattr(adata, "obsp", None) is None:
+        adata.obsp = {}
+    adata.obsp[prefix + "distances"] = graph
+    adata.obsp[prefix + "connectivities"] = connectivities
+    adata.uns["neighbors" if key_added is None else key_added] = {
+        "connectivities_key": prefix + "connectivities", "distances_key": prefix + "distances",
+        "params": {"n_neighbors": int(n_neighbors), "method": "umap", "metric": metric, "use_rep": use_rep, "n_pcs": n_pcs}}
 
 
 # ---- gene-cluster differentiation (Gene_cluster_specific.py:8-201, Trajectory.py:1129-1172) --------------------------------

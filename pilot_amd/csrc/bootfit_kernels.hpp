@@ -85,7 +85,8 @@ __global__ void __launch_bounds__(TF_BLOCK) bootfit_kernel(const T *__restrict__
         cs = fmax(sse > 1e-8 * syy ? sqrt(fmax(sse, 0.0) / n) : sqrt(syy / n), a.sigma_min);
     }
 
-    // Newton steps with a bracketing line search: trajfit_kernel's Huber loop, the basis at the lane's resampled time
+    // Newton steps with a bracketing line search: trajfit_kernel's Huber loop, the basis at the lane's resampled time (a copy, kept
+    // identical to it: as one shared function the loop compiles to other FMA fusions and the fits' last bits move)
     double cF = 0.0, d[4] = {0.0, 0.0, 0.0, 0.0}, s0 = 0.0, t = 0.0, tmax = 0.0, lo = 0.0, flo = 0.0, hi = -1.0, fhi = 0.0;
     double bt = 0.0, bF = 0.0, bg[4] = {}, bH[4][4] = {};
     bool start = true, have_best = false;

@@ -1,64 +1,20 @@
 // C ABI of the batched bootstrap Huber fits (include/pilot_ot.h, section "bootstrap Huber fits"; kernel: bootfit_kernels.hpp).
-// The host maps the base times once (K9's scaled basis, back-transform and penalty; no Gram: each resample forms its own in the
-// kernel), copies Y once and streams the index vectors through the device in bounded chunks of problems.
+// The host maps the base times once (trajfit_host.hpp: K9's scaled basis, back-transform and penalty; no Gram: each resample forms
+// its own in the kernel), copies Y once and streams the index vectors through the device in bounded chunks of problems.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "abi_common.hpp"
 #include "bootfit_kernels.hpp"
+#include "trajfit_host.hpp"
 
 namespace {
 
 constexpr size_t CHUNK_BYTES = size_t(256) << 20;      // index vectors on the device: at most this many bytes at a time
-constexpr int MAX_ITER = 100;                          // Newton steps per fit before PILOT_OT_TRAJFIT_NOT_CONVERGED (as K9)
-constexpr double HUBER_ALPHA = 1e-4;                   // scikit-learn's HuberRegressor default penalty
-
-// u = (x - m) / s of the base times and, per model, K9's basis (C, quad_k, quad_scale), coefficients on [1, f(x)] (R) and the
-// penalty alpha ||w||^2 written on gamma (pen) -- the parts of pilot_ot_trajfit.hip's prepare() that do not depend on the Gram.
-// s = max |x - m|, 1 when every time is the same.
-void prepare_map(const double *x, int n, std::vector<double> &u, pilot::TrajfitArgs &a) {
-    double sum = 0.0;
-    for (int i = 0; i < n; ++i) sum += x[i];
-    const double m = sum / n;
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s = std::max(s, std::fabs(x[i] - m));
-    if (!(s > 0.0)) s = 1.0;
-    u.resize(n);
-    for (int i = 0; i < n; ++i) u[i] = (x[i] - m) / s;
-    const double kappa = 2.0 * m / s, qs = 1.0 / (1.0 + std::fabs(kappa));
-    const double E[3][3] = {{1.0, -m / s, m * m / (s * s)}, {0.0, 1.0 / s, -2.0 * m / (s * s)}, {0.0, 0.0, 1.0 / (s * s)}};
-    std::memset(&a, 0, sizeof(a));
-    for (int md = 0; md < 3; ++md) {
-        pilot::TrajfitModel &M = a.mod[md];
-        const int p = md == 1 ? 3 : 2;
-        double C[3][3] = {};
-        C[0][0] = 1.0;
-        if (md == 0) C[1][1] = 1.0;
-        else if (md == 1) { C[1][1] = 1.0; C[2][2] = 1.0; }
-        else { C[1][1] = kappa * qs; C[2][1] = qs; }
-        std::memcpy(M.C, C, sizeof(C));
-        double EC[3][3] = {};
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < p; ++j)
-                for (int k = 0; k < 3; ++k) EC[i][j] += E[i][k] * C[k][j];
-        const int rows[3] = {0, md == 2 ? 2 : 1, 2};                                   // quadratic: [1, x^2]
-        for (int i = 0; i < p; ++i)
-            for (int j = 0; j < p; ++j) M.R[i][j] = EC[rows[i]][j];
-        for (int i = 0; i < p; ++i)
-            for (int j = 0; j < p; ++j)
-                for (int r = 1; r < p; ++r) M.pen[i][j] += HUBER_ALPHA * M.R[r][i] * M.R[r][j];
-    }
-    a.quad_k = kappa;
-    a.quad_scale = qs;
-    a.sigma_min = 10.0 * DBL_EPSILON;
-    a.n = n;
-}
 
 int check_args(const void *Y, int dtype, int n, int n_cols, long long ld, const double *x, int n_problems, const int *cols,
                const int *models, int B, const int *idx, double epsilon, const double *params) {
@@ -95,14 +51,10 @@ PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int 
     if (n_problems == 0) return PILOT_OT_OK;
     pilot::TrajfitArgs a;
     std::vector<double> u;
-    prepare_map(x, n, u, a);
+    pilot::trajfit_time_map(x, n, u, a);
     a.huber = 1;
     a.epsilon = epsilon;
-    a.max_iter = MAX_ITER;
-    if (const char *sw = pilot::test_switch("PILOT_OT_TRAJFIT_MAX_ITER")) {      // (tests: the NOT_CONVERGED path)
-        const int v = atoi(sw);
-        if (v >= 0 && v < a.max_iter) a.max_iter = v;
-    }
+    a.max_iter = pilot::trajfit_max_iter();
     const size_t per_problem = (size_t)n * B * sizeof(int);
     long long pc = (long long)std::max<size_t>(1, CHUNK_BYTES / per_problem);
     if (const char *sw = pilot::test_switch("PILOT_OT_BOOTFIT_CHUNK_PROBLEMS")) {  // (tests: many chunks)
@@ -111,16 +63,15 @@ PILOT_API int pilot_ot_bootstrap_huber_fits(const void *Y, int Y_is_device, int 
     }
     pc = std::min<long long>(pc, n_problems);
 
-    double *d_u, *d_out;
+    const double *d_u;
+    const pilot::TrajfitArgs *d_args;
+    double *d_out;
     int *d_idx, *d_pm;
-    const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
-    HIP_TRY(pilot::ws(pilot::WS_BOOT_U, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
-    const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
+    rc = pilot::trajfit_stage(pilot::WS_BOOT_U, u, a, &d_u, &d_args);
+    if (rc != PILOT_OT_OK) return rc;
     HIP_TRY(pilot::ws(pilot::WS_BOOT_OUT, (size_t)pc * B * pilot::BF_NOUT, &d_out));
     HIP_TRY(pilot::ws(pilot::WS_BOOT_IDX, (size_t)pc * n * B + 2 * (size_t)n_problems, &d_idx));    // the chunk's indices, then cols and models
     d_pm = d_idx + (size_t)pc * n * B;
-    HIP_TRY(hipMemcpy(d_u, u.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_pm, cols, sizeof(int) * n_problems, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_pm + n_problems, models, sizeof(int) * n_problems, hipMemcpyHostToDevice));
     const void *yd;                                              // a host Y is copied whole (its n x n_cols part)

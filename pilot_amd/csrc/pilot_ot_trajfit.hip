@@ -5,20 +5,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "abi_common.hpp"
-#include "trajfit_kernels.hpp"
+#include "trajfit_host.hpp"
 
 namespace {
 
 constexpr size_t CHUNK_BYTES = size_t(256) << 20;      // device copy of a host Y: at most this many bytes of columns at a time
-constexpr int MAX_ITER = 100;                          // Newton steps per (target, model) before PILOT_OT_TRAJFIT_NOT_CONVERGED
-constexpr double HUBER_ALPHA = 1e-4;                   // scikit-learn's HuberRegressor default penalty
 
 // inverse of a small symmetric positive definite matrix (Gauss-Jordan with partial pivoting; k <= 3)
 bool invert(int k, const double A[3][3], double X[3][3]) {
@@ -45,22 +41,16 @@ bool invert(int k, const double A[3][3], double X[3][3]) {
     return true;
 }
 
-// The shared part of a call: u = (x - m) / s and every per-model matrix of pilot::TrajfitArgs
+// The shared part of a call: the time map (trajfit_host.hpp) and what depends on the Gram of [1, u, u^2]: per model G and vd,
+// and the Pearson sum sxx; the range of x
 int prepare(const double *x, int n, std::vector<double> &u, pilot::TrajfitArgs &a) {
-    double sum = 0.0, xmin = x[0], xmax = x[0];
-    for (int i = 0; i < n; ++i) {
-        sum += x[i];
-        xmin = std::min(xmin, x[i]);
-        xmax = std::max(xmax, x[i]);
-    }
-    const double m = sum / n;
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s = std::max(s, std::fabs(x[i] - m));
-    u.resize(n);
+    pilot::trajfit_time_map(x, n, u, a);
+    double xmin = x[0], xmax = x[0];
     double mu[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = 0; i < n; ++i) {
-        const double v = (x[i] - m) / s;
-        u[i] = v;
+        xmin = std::min(xmin, x[i]);
+        xmax = std::max(xmax, x[i]);
+        const double v = u[i];
         double p = 1.0;
         for (int k = 0; k < 5; ++k) { mu[k] += p; p *= v; }
     }
@@ -70,53 +60,29 @@ int prepare(const double *x, int n, std::vector<double> &u, pilot::TrajfitArgs &
     double G3[3][3];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) G3[i][j] = mu[i + j];
-
-    const double kappa = 2.0 * m / s, qs = 1.0 / (1.0 + std::fabs(kappa));
-    // delta (prediction polynomial in u) -> coefficients of 1, x, x^2
-    const double E[3][3] = {{1.0, -m / s, m * m / (s * s)}, {0.0, 1.0 / s, -2.0 * m / (s * s)}, {0.0, 0.0, 1.0 / (s * s)}};
-    std::memset(&a, 0, sizeof(a));
     for (int md = 0; md < 3; ++md) {
         pilot::TrajfitModel &M = a.mod[md];
         const int p = md == 1 ? 3 : 2;
-        double C[3][3] = {};
-        C[0][0] = 1.0;
-        if (md == 0) C[1][1] = 1.0;
-        else if (md == 1) { C[1][1] = 1.0; C[2][2] = 1.0; }
-        else { C[1][1] = kappa * qs; C[2][1] = qs; }
+        const double (&C)[3][3] = M.C;
         double BB[3][3] = {}, H[3][3] = {};
         for (int i = 0; i < p; ++i)
             for (int j = 0; j < p; ++j)
                 for (int k = 0; k < 3; ++k)
                     for (int l = 0; l < 3; ++l) BB[i][j] += C[k][i] * G3[k][l] * C[l][j];
         if (!invert(p, BB, H)) return fail(PILOT_OT_EINVAL, "x: the Gram matrix of the model features is singular");
-        std::memcpy(M.C, C, sizeof(C));
         for (int i = 0; i < p; ++i)
             for (int j = 0; j < 3; ++j)
                 for (int k = 0; k < p; ++k) M.G[i][j] += H[i][k] * C[j][k];          // G = H C^T
-        double EC[3][3] = {};
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < p; ++j)
-                for (int k = 0; k < 3; ++k) EC[i][j] += E[i][k] * C[k][j];
-        const int rows[3] = {0, md == 2 ? 2 : 1, 2};                                   // quadratic: [1, x^2]
-        for (int i = 0; i < p; ++i)
-            for (int j = 0; j < p; ++j) M.R[i][j] = EC[rows[i]][j];
         for (int j = 0; j < p; ++j) {
             double v = 0.0;
             for (int k = 0; k < p; ++k)
                 for (int l = 0; l < p; ++l) v += M.R[j][k] * H[k][l] * M.R[j][l];
             M.vd[j] = v;                                                               // diag(R H R^T) = diag((Z^T Z)^-1)
         }
-        for (int i = 0; i < p; ++i)
-            for (int j = 0; j < p; ++j)
-                for (int r = 1; r < p; ++r) M.pen[i][j] += HUBER_ALPHA * M.R[r][i] * M.R[r][j];
     }
-    a.quad_k = kappa;
-    a.quad_scale = qs;
     a.sxx = sxx;
     a.x_min = xmin;
     a.x_max = xmax;
-    a.sigma_min = 10.0 * DBL_EPSILON;
-    a.n = n;
     return PILOT_OT_OK;
 }
 
@@ -160,11 +126,7 @@ PILOT_API int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype
     a.epsilon = epsilon;
     a.pval_thr = pval_thr;
     a.modify_r2 = modify_r2 != 0;
-    a.max_iter = MAX_ITER;
-    if (const char *sw = pilot::test_switch("PILOT_OT_TRAJFIT_MAX_ITER")) {      // (tests: the NOT_CONVERGED path)
-        const int v = atoi(sw);
-        if (v >= 0 && v < a.max_iter) a.max_iter = v;
-    }
+    a.max_iter = pilot::trajfit_max_iter();
     const size_t es = pilot::elem_size(dtype);
     long long tc = (long long)(CHUNK_BYTES / ((size_t)n * es)) / 64 * 64;
     if (const char *sw = pilot::test_switch("PILOT_OT_TRAJFIT_CHUNK_TARGETS")) {   // (tests: many chunks)
@@ -174,13 +136,12 @@ PILOT_API int pilot_ot_trajectory_fits(const void *Y, int Y_is_device, int dtype
     tc = std::max(tc, 64LL);
     tc = std::min(tc, ((long long)n_targets + 63) / 64 * 64);
 
-    double *d_u, *d_out;
-    const size_t n_args = (sizeof(pilot::TrajfitArgs) + sizeof(double) - 1) / sizeof(double);
-    HIP_TRY(pilot::ws(pilot::WS_TF_U, (size_t)n + n_args, &d_u));                   // u, then the arguments struct
-    const pilot::TrajfitArgs *d_args = reinterpret_cast<const pilot::TrajfitArgs *>(d_u + n);
+    const double *d_u;
+    const pilot::TrajfitArgs *d_args;
+    double *d_out;
+    rc = pilot::trajfit_stage(pilot::WS_TF_U, u, a, &d_u, &d_args);
+    if (rc != PILOT_OT_OK) return rc;
     HIP_TRY(pilot::ws(pilot::WS_TF_OUT, (size_t)tc * pilot::TF_NOUT, &d_out));
-    HIP_TRY(hipMemcpy(d_u, u.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_u + n, &a, sizeof(a), hipMemcpyHostToDevice));
     std::vector<double> rec((size_t)tc * pilot::TF_NOUT);
     int not_conv = 0;
     for (long long t0 = 0; t0 < n_targets; t0 += tc) {

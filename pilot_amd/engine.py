@@ -757,6 +757,17 @@ def diffusion_map_from_kernel(Kmat, n_evecs=2, epsilon=1.0, alpha=0.5, return_in
 TRAJFIT_MODELS = ("linear", "linear_quadratic", "quadratic")
 
 
+def _fit_inputs(Y, x):
+    """``Y`` (observations x targets) and the time ``x`` of the model fits as ``(Y, x, n, T)``: the dense argument, float64
+    times, and the two sizes."""
+    x = _as_f64(np.ravel(x), "x")
+    Y = _dense_arg(Y, "Y", mode="strided", axes=" (observations x targets)")
+    n, T = Y.rows, Y.cols
+    if x.size != n:
+        raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
+    return Y, x, n, T
+
+
 def trajectory_fits(Y, x, model="ols", epsilon=1.35, pval_thr=0.05, modify_r2=False, return_info=False):
     """The three trajectory models of every target column of ``Y`` (n observations x targets, float32 / float64, a numpy
     array or a :class:`DeviceMatrix`) against the time ``x`` (n values), on the device: ``linear`` [x], ``linear_quadratic``
@@ -770,11 +781,7 @@ def trajectory_fits(Y, x, model="ols", epsilon=1.35, pval_thr=0.05, modify_r2=Fa
     ``_lib.TRAJFIT_NOT_CONVERGED`` bits) and ``not_converged`` (the flagged count)."""
     if model not in ("ols", "huber"):
         raise ValueError("model=%r must be 'ols' or 'huber'" % (model,))
-    x = _as_f64(np.ravel(x), "x")
-    Y = _dense_arg(Y, "Y", mode="strided", axes=" (observations x targets)")
-    n, T = Y.rows, Y.cols
-    if x.size != n:
-        raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
+    Y, x, n, T = _fit_inputs(Y, x)
     fits = dict(params=np.empty((T, 3, 3)), pvalues=np.empty((T, 3, 3)), rsquared_adj=np.empty((T, 3)),
                 mod_rsquared_adj=np.empty((T, 3)), chosen=np.empty(T, dtype=np.int32), slope=np.empty(T),
                 pattern=np.empty(T, dtype=np.int32), pearson_r=np.empty(T), pearson_p=np.empty(T), zero_fraction=np.empty(T),
@@ -804,11 +811,7 @@ def bootstrap_huber_fits(Y, x, cols, models, idx, epsilon=1.35, return_info=Fals
     (``epsilon``, alpha 1e-4) by K9's method.  Returns ``params`` (problems x B x 3, on [1, f(x)]; the third slot NaN for the
     two-coefficient models); with ``return_info`` also a dict of ``sigma``, ``steps``, ``flags`` (problems x B) and
     ``not_converged`` (the count flagged ``_lib.TRAJFIT_NOT_CONVERGED``)."""
-    x = _as_f64(np.ravel(x), "x")
-    Y = _dense_arg(Y, "Y", mode="strided", axes=" (observations x targets)")
-    n, T = Y.rows, Y.cols
-    if x.size != n:
-        raise ValueError("x has %d values, Y has %d observations" % (x.size, n))
+    Y, x, n, T = _fit_inputs(Y, x)
     cols = np.ascontiguousarray(np.ravel(cols), dtype=np.int32)
     models = np.ascontiguousarray(np.ravel(models), dtype=np.int32)
     idx = np.asarray(idx)

@@ -114,6 +114,37 @@ def test_bootfit_not_converged_flag():
     assert info["not_converged"] == int((info["flags"] != 0).sum()) > 0
 
 
+@pytest.mark.parametrize("n", [5, 20, 67])
+def test_identity_bootstrap_is_the_trajectory_fit(n):
+    """A bootstrap whose index vector is the identity is K9's Huber fit of that column and model: the two kernels carry the same
+    Newton loop and run it from two starts (K9: the OLS fit, K10: the penalised least-squares fit).  Both reach the optimum by
+    the objective criterion; their coefficients are held to 2e-6 of the largest, the sum of the 1e-6 each entry is held to
+    against its own restatement."""
+    Y, x, cols, models, _ = _problem(np.random.default_rng(n), n, 2, np.float64)
+    idx = np.ascontiguousarray(np.broadcast_to(np.arange(n, dtype=np.int32)[None, :, None], (3, n, 2)))
+    params, info = engine.bootstrap_huber_fits(Y, x, cols, models, idx, return_info=True)
+    fits, finfo = engine.trajectory_fits(Y, x, model="huber", return_info=True)
+    assert np.array_equal(params[:, 0].view(np.uint64), params[:, 1].view(np.uint64))
+    assert np.array_equal(np.ascontiguousarray(info["sigma"][:, 0]).view(np.uint64),
+                          np.ascontiguousarray(info["sigma"][:, 1]).view(np.uint64))
+    assert np.array_equal(info["steps"][:, 0], info["steps"][:, 1])
+    assert not info["flags"].any() and info["not_converged"] == 0
+    assert not finfo["flags"].any() and finfo["not_converged"] == 0
+    for q in range(cols.size):
+        f, c, m = BR.MODELS[models[q]], cols[q], models[q]
+        y = Y[:, c]
+        p_ref, _, F_ref = BR.huber_opt(x, x, y, f)
+        p = p_ref.size
+        boot, traj = params[q, 0], fits["params"][c, m]
+        F_boot = BR.objective(x, y, f, boot, info["sigma"][q, 0])
+        F_traj = BR.objective(x, y, f, traj, finfo["sigma"][c, m])
+        diff = np.abs(boot[:p] - traj[:p]).max() / np.abs(p_ref).max()
+        print("n=%d %s: objective / optimum - 1: bootstrap %.1e, trajectory %.1e; params differ by %.1e of the largest"
+              % (n, f, F_boot / F_ref - 1, F_traj / F_ref - 1, diff))
+        assert F_boot <= F_ref * (1 + 1e-10) and F_traj <= F_ref * (1 + 1e-10), (f, q, F_boot, F_traj, F_ref)
+        assert diff <= 2e-6, (f, q, boot, traj)
+
+
 # ---- end to end -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def cohort():

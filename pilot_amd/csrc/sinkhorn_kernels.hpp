@@ -1349,6 +1349,8 @@ sinkhorn_stream_kernel(GridParams p) {
         // 56 %: c3 kernel 0.609 -> 0.626 / 0.651 ms, the idle column-updates cost more than the skipped blocks; at one row-tile, where the
         // update itself is a few dozen instructions, the gate changes nothing either (the 634 x 14 cohort 0.350 / 0.351 / 0.347 ms at gates
         // 1 / 2 / 4, K = 20 .. 32 +2 .. +7 %): profiles/r06/ab_experiments.md sections 3 and 8)
+        // (the same feed as PairBatch, split_tile.hpp, kept inline here: through that struct 74 of these kernels' instantiations change
+        // registers or scratch and two lose a wave per SIMD -- profiles/split_tile/stream_feed_resources.diff)
         const unsigned long long wmask = ballot_b(want) & colmask;
         if (wmask) {
             if (res_next >= res_end && !exhausted) {

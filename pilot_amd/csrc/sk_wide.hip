@@ -16,7 +16,7 @@ hipError_t launch_wide_value(dim3 grid, hipStream_t s, const GridParams &p, cons
 }
 size_t wide_rec_elems() { return (size_t)WIDE_REC; }
 hipError_t launch_quad(dim3 grid, hipStream_t s, const GridParams &p) {
-    hipLaunchKernelGGL(sinkhorn_quad_kernel<8>, grid, dim3(WAVE * QUAD_WAVES), 0, s, p);
+    hipLaunchKernelGGL(sinkhorn_quad_kernel, grid, dim3(WAVE * QUAD_WAVES), 0, s, p);
     return hipGetLastError();
 }
 

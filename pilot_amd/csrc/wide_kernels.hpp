@@ -1,24 +1,19 @@
-// Sinkhorn pair-grid kernel for 128 < K <= 256 cell types (symmetric cost, max(M)/reg <= 16): the fp16-split formulation of
-// sinkhorn_stream_kernel<CfgH32x16, ...> with the cell types of a 16-pair tile spread over the EIGHT waves of a workgroup.
+// Sinkhorn pair-grid kernel for 128 < K <= 256 cell types (symmetric cost, max(M)/reg <= 16): EIGHT waves per 16-pair tile.
+// The formulation -- wave w owns the output row-tiles 2 w and 2 w + 1 -- is told in split_tile.hpp; this kernel's own:
 //
 // Why a kernel of its own: one wave per tile needs 5 panels x RT x 4 registers per lane and the stationary operand image
 // (2 fp16 pieces x K^2 x 2 B = 256 KB at K = 256) in LDS -- neither fits beyond 8 row-tiles, and round 3 sent every K > 128
 // to the POT-literal kernel (one workgroup per pair, K' streamed from L2 twice per update): 151 ms for 200 patients at K = 130
-// against 0.7 ms at K = 128.  Here wave w owns the OUTPUT row-tiles 2w and 2w + 1:
-//   * its rows of the operand image live in REGISTERS (2 pieces x 8 k-blocks x 2 tiles x 16 B = 128 VGPRs per lane, loaded
-//     once per wave; G^T = G serves both products), so no image is ever read in the update loop;
-//   * the accumulator registers of tiles 2w, 2w + 1 are exactly k-block w of the next product's B operand (the layout rule
-//     of the stream kernel), so after the element-wise step a wave publishes ONE k-block of packed pieces (2 KB) in LDS
-//     and every wave reads all eight: two workgroup barriers per update, 16 KB of panel per product;
-//   * per-column decisions (tau test, marginal error, stop) are taken from LDS reductions that every wave reads in the same
-//     order, so the replicated control state never diverges and a pair's bits do not depend on its slot or workgroup;
+// against 0.7 ms at K = 128.  Here
+//   * a wave's rows of the operand image are 2 pieces x 8 k-blocks x 2 tiles x 16 B = 128 VGPRs per lane, 16 KB of panel per product;
+//   * the layout is always the 16-row-tile one; how much of it holds cell types is known at run time only: the products skip the
+//     k-blocks beyond K (KBL) and a wave whose tiles are all padding (live_wave);
 //   * a finished pair leaves its (u, v) pieces in a global record (the ring-slot format of the stream kernel); the costs
 //     <Gamma, M> are formed afterwards by sinkhorn_wide_value_kernel, 16 records per wave with ring_flush_body;
 //   * a pair in which POT would tau-absorb, or that ends as NaN, is marked in its record and forwarded by the value kernel to
 //     the POT-literal kernel (nan_list) -- at max(M)/reg <= 16 and K > 128 those are a handful.
-// Same scaled domain, same stopping rule (f32 floor of the threshold) and the same tolerance as the fp16-split stream kernel.
 #pragma once
-#include "sinkhorn_kernels.hpp"
+#include "split_tile.hpp"
 
 namespace pilot {
 
@@ -76,17 +71,8 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
                 }
         }
     };
-    // X (my two tiles) -> the packed pieces of my k-block
-    auto pieces_of = [&](const acc_t (&X)[2], u32x4_t &hi, u32x4_t &lo) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            unsigned int a, b;
-            quot_pieces(X[h / 2][2 * (h & 1)], X[h / 2][2 * (h & 1) + 1], a, b);
-            hi[h] = a; lo[h] = b;
-        }
-    };
 
-    bool active = false, want = true, exhausted = false;
+    bool active = false, want = true;
     int q = 0, ii = 0, chk = 1, flags = 0;
     float errv = 1.f, thr = 0.f;
     acc_t A[2], B[2], V[2], U[2], ACC[2];
@@ -95,7 +81,8 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
 #pragma unroll
         for (int r = 0; r < NREG; ++r) { A[tl][r] = B[tl][r] = V[tl][r] = U[tl][r] = 0.f; ACC[tl][r] = 1.f; }
     u32x4_t pu_hi = {0u, 0u, 0u, 0u}, pu_lo = pu_hi, pv_hi = pu_hi, pv_lo = pu_hi;
-    int res_next = 0, res_end = 0, res_base = 0, qbatch = 0, ibatch = 0, jbatch = 0, draws = 0;
+    PairBatch<TILE> batch;
+    int draws = 0;
     const bool all_over = p.unequal && *p.unequal != 0;                  // histograms of unequal mass: see the stream kernel
     if (threadIdx.x < 2 * TILE) (&ovc[0][0])[threadIdx.x] = 0;
     __syncthreads();
@@ -105,38 +92,9 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
         // ---- (re)fill columns: every wave runs the same logic on the same replicated state; the queue atomic is wave 0's ----
         const unsigned long long wmask = __ballot(want) & colmask;
         if (wmask) {
-            if (res_next >= res_end && !exhausted) {
-                int base;
-                if (draws == 0) {                   // the first batch is the workgroup's own number: no atomic, no barrier
-                    base = (int)blockIdx.x * TILE;
-                } else {
-                    if (threadIdx.x == 0)
-                        sh_base[draws & 1] = (int)gridDim.x * TILE + __hip_atomic_fetch_add(p.queue_head, TILE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __syncthreads();
-                    base = __builtin_amdgcn_readfirstlane(sh_base[draws & 1]);
-                }
-                ++draws;
-                exhausted = base >= n_items;
-                res_next = exhausted ? n_items : base;
-                res_end = (base + TILE < n_items) ? base + TILE : n_items;
-                if (exhausted) res_end = n_items;
-                res_base = base;
-                const int bi = base + col;
-                qbatch = (p.list && bi < n_items) ? p.list[bi] : bi;
-                const int qv = bi < n_items ? qbatch : 0;
-                ibatch = p.row_begin + (qv / N) * p.row_step;
-                jbatch = qv % N;
-            }
-            const int avail = res_end - res_next;
-            const int n_want = (int)__popcll(wmask);
-            const int rank = (int)__popcll(wmask & ((1ull << col) - 1ull));
-            const int item = res_next + rank;
-            const bool take = want && rank < avail;
-            const int bsel = 4 * ((item - res_base) & (TILE - 1));
-            const int qsel = __builtin_amdgcn_ds_bpermute(bsel, qbatch);
-            const int isel = __builtin_amdgcn_ds_bpermute(bsel, ibatch), jsel = __builtin_amdgcn_ds_bpermute(bsel, jbatch);
-            res_next = __builtin_amdgcn_readfirstlane(res_next + (n_want < avail ? n_want : avail));
-            if (want && !take && exhausted) {       // no work left: the slot goes dark
+            if (batch.empty()) batch.open(split_draw<TILE>(draws, sh_base, p, [] { __syncthreads(); }), n_items, p, col);
+            const auto [take, qsel, isel, jsel] = batch.deal(want, wmask, col);
+            if (want && !take && batch.exhausted) { // no work left: the slot goes dark
                 want = false;
 #pragma unroll
                 for (int tl = 0; tl < 2; ++tl)
@@ -159,7 +117,7 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
                         U[tl][r] = uinit - uinit * PADC[tl][r];             // u0 = 1/K, 0 in padded slots
                     }
                 }
-                pieces_of(U, pu_hi, pu_lo);
+                split_pieces_of<C>(U, pu_hi, pu_lo);
                 thr = Pt[(size_t)N * KP + jsel] * H_IN_SCALE;
                 chk = 1; ii = 0; flags = 0; errv = 1.f;
                 if (all_over) {                     // not a problem for the scaled fp16 domain: straight to the POT-literal kernel
@@ -179,7 +137,7 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
         for (int tl = 0; tl < 2; ++tl)
 #pragma unroll
             for (int r = 0; r < NREG; ++r) { V[tl][r] = B[tl][r] * C::rcp(ACC[tl][r]); mx = fmaxf(mx, V[tl][r]); }
-        pieces_of(V, pv_hi, pv_lo);
+        split_pieces_of<C>(V, pv_hi, pv_lo);
         PB[0][wave][0][lane] = pv_hi; PB[0][wave][1][lane] = pv_lo;
         if (active && !(mx <= tau)) ovc[par][col] = 1;                   // (NaN counts as over: caught below as a hand-over)
         __syncthreads();
@@ -190,7 +148,7 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
         for (int tl = 0; tl < 2; ++tl)
 #pragma unroll
             for (int r = 0; r < NREG; ++r) { U[tl][r] = A[tl][r] * C::rcp(ACC[tl][r]); mx = fmaxf(mx, U[tl][r]); }
-        pieces_of(U, pu_hi, pu_lo);
+        split_pieces_of<C>(U, pu_hi, pu_lo);
         PB[1][wave][0][lane] = pu_hi; PB[1][wave][1][lane] = pu_lo;
         if (active && !(mx <= tau)) ovc[par][col] = 1;
         if (threadIdx.x < TILE) ovc[par ^ 1][threadIdx.x] = 0;           // next iteration's flags (nobody reads them before barrier 2 of it)
@@ -211,27 +169,8 @@ __global__ void __launch_bounds__(WAVE * WIDE_WAVES, 2) sinkhorn_wide_kernel(Gri
         if (pending) chk += p.period;
         const bool capped = active && ii >= p.max_iter;
         if (__ballot(pending || capped)) {                               // (the same in every wave)
-            float e2 = 0.f;
-#pragma unroll
-            for (int tl = 0; tl < 2; ++tl) {
-                float et = 0.f;
-#pragma unroll
-                for (int r = 0; r < NREG; ++r) { const float d = V[tl][r] * ACC[tl][r] - B[tl][r]; et += d * d; }
-                e2 += et;
-            }
-            e2 = group_sum<C>(e2);
-            if (grp == 0) red_e2[par][wave][col] = e2;
-            __syncthreads();
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < WIDE_WAVES; ++w) tot += red_e2[par][w][col];     // wave order: the same sum in every wave
-            const float e = sqrtf(tot);
-            bool fin = capped;
-            if (pending) {
-                errv = e;
-                if (e <= thr) { fin = true; flags |= FLAG_CONVERGED; }
-                else if (e != e) { fin = true; flags |= FLAG_NAN; }
-            }
+            const float e = split_marginal_error<C, WIDE_WAVES>(V, ACC, B, red_e2[par], wave, col, grp, [] { __syncthreads(); });
+            const bool fin = split_stop(e, pending, capped, thr, errv, flags);
             if (fin) {
                 // the pair's record: my k-block of the u and v pieces; wave 0 adds the scale, the output index and the flags
                 float *rec = rec_base + (size_t)q * WIDE_REC;

@@ -197,6 +197,34 @@ def test_k_129_to_256_runs_eight_waves_per_tile(K, switches):
     assert absorbed.sum() > 0                                            # (at tau = 1.2 some pair does absorb)
 
 
+@pytest.mark.parametrize("K,N", [(113, 101), (129, 81), (113, 1), (128, 3), (129, 4), (256, 8)])
+def test_four_and_eight_wave_kernels_draw_batches_from_the_queue(K, N):
+    """The pair feed of sinkhorn_quad_kernel and sinkhorn_wide_kernel (split_tile.hpp): a workgroup's first batch of 16 pairs is
+    the one of its own number, the later ones come from the device-wide counter through LDS.  Premise: 256 CUs, so quad launches
+    at most 512 workgroups and wide at most 256, one tile each per draw.  (113, 101): 10 201 pairs, 638 tiles, a last batch of 9
+    (drawn up to 318 CUs); (129, 81): 6 561 pairs, 411 tiles, a last batch of 1 (drawn up to 410 CUs).  Their row subsets are
+    served by static batches only, so subset / full identity ties the two feed paths together.  The small grids are the other
+    end: fewer pairs than one tile (1, 9) and exact multiples of 16 (16, 64).  In the oracle every pair of these grids converges
+    (at most 61 updates) and none absorbs, so no pair is excluded from the tolerance."""
+    P, M = make_problem(N, K, 6, seed=K, cells_per_patient=3000)
+    if N > 7:
+        P[7] = P[3]                                                      # duplicate patients: the slowest pairs
+    Eo, io = O.sinkhorn_grid(P, M, 0.1, n_threads=16, return_info=True)
+    Eg, ig = engine.sinkhorn_grid(P, M, 0.1, return_info=True)
+    f64 = (ig["flags"] & _lib.FLAG_F64) > 0
+    print("K %d N %d: max|E - Eo| %.3e, iters max %d (oracle %d), f64 share %.4f"
+          % (K, N, np.abs(Eg - Eo).max(), ig["iters"].max(), io["iters"].max(), f64.mean()))
+    assert Eg.shape == (N, N) and np.abs(Eg - Eo).max() <= TOL32
+    assert np.all(ig["iters"] % 20 == 1) and np.all(ig["iters"] <= io["iters"])
+    assert f64.sum() == 0 if K <= 128 else f64.mean() < 0.2
+    Er, ir = engine.sinkhorn_grid(P, M, 0.1, return_info=True)
+    np.testing.assert_array_equal(Er, Eg)                                # deterministic
+    np.testing.assert_array_equal(ir["iters"], ig["iters"])
+    for rb, rs in ((0, 7), (3, 11)):
+        if rb < N:
+            np.testing.assert_array_equal(engine.sinkhorn_grid(P, M, 0.1, row_begin=rb, row_end=N, row_step=rs), Eg[rb:N:rs])
+
+
 def test_generic_kernel_is_pot_literal_including_absorption_and_tiny_reg():
     """precision='generic' forces the reference-semantics kernel on any shape: same update counts, absorption flags and
     errors as the oracle at reg 0.01 (every pair absorbs, some on their last update); and a reg whose exp(-M/reg) leaves the

@@ -582,6 +582,29 @@ int pilot_ot_knn_rows(const void *X, int X_is_device, int dtype, long long n, in
  * exp(-(d_j - rho) / sigma).  weights: n x k, sigma, rho: n (host).  Refusals as above (k, n, NULL; a distance not finite or < 0). */
 int pilot_ot_knn_smooth(const double *distances, long long n, int k, double *weights, double *sigma, double *rho);
 
+/* ---- Louvain communities (K17): the communities of the cell graph that pilotpy takes from sknetwork.clustering.Louvain(resolution)
+ * on obsp['distances'] / ['connectivities'] (tools/Trajectory.py:217-220, 1050-1060), by a SYNCHRONOUS rule: deterministic, no seed,
+ * parallel over nodes (restated in tests/louvain_restatement.py).  It is not sknetwork's sequential sweep.
+ * A: n x n CSR on the host (indptr: n + 1 entries from 0), weights finite and >= 0, maybe unsymmetric; the columns of a row may be
+ * unsorted or repeated (repeats add), stored zeros are dropped, diagonal entries are allowed.  out_i = sum_j A_ij, in_i = sum_j A_ji,
+ * w = sum_i out_i, S = A + A^T.  Q = Qs / w^2 with Qs = (w / 2) sum_{c_i = c_j} S_ij - resolution sum_c Out_c In_c (Dugue-Perez
+ * modularity; Newman's when A is symmetric).  A level starts from singletons; a sweep moves every node against one snapshot: node i
+ * in X takes the community C != X among those of its stored neighbours j != i with the largest
+ *     g(C) = w (k_C - k_X) - resolution (out_i (In_C - (In_X - in_i)) + in_i (Out_C - (Out_X - out_i))),  k_C = sum_{j in C, j != i} S_ij
+ * (f64, every product and sum rounded on its own; ties to the lowest C) iff g > 0, except that a singleton never moves to a
+ * singleton of higher id.  A sweep that moved nothing ends the level; otherwise it is kept iff Qs_new - Qs_kept > tol w^2, else
+ * discarded and the level ends; at most 128 sweeps a level.  Then the surviving communities, ranked by id, become the nodes of the
+ * next level (S' = P^T S P, out' / in' the member sums); the run ends when a level merges nothing or after max_levels levels.
+ * Every sum has one fixed order and no floating-point atomic is used: the same call returns the same bits.
+ * Out (host): labels n ints in 0 .. k-1, numbered by decreasing community size, ties to the smallest member; *modularity = Q of
+ * them; info[0] = levels run, info[1] = sweeps run, info[2] = k.  n = 0 writes nothing but info and Q = 0; w = 0: every node its own
+ * community, Q = 0, no level.  S goes up once; a level uploads nothing and brings back only its counters.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n < 0, indptr not non-decreasing from 0, a column outside [0, n), a weight
+ * negative or not finite (the message names the entry), resolution not finite or < 0, tol < 0, max_levels < 1, w^2 not finite.
+ * PILOT_OT_ENOTSUP (before any HIP call): n > INT_MAX, or more than INT_MAX entries in S. */
+int pilot_ot_louvain(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
+                     int max_levels, int *labels, double *modularity, int *info /* 3 */);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

@@ -37,6 +37,8 @@ enum WsSlot {
     WS_PCA_V, WS_PCA_VEC, WS_PCA_Z, WS_PCA_PCS, WS_PCA_SCORES, WS_PCA_STATS, WS_PCA_COLS, WS_PCA_POS,   // pilot_ot_pca.hip
     WS_PCA_SIDX, WS_PCA_SVAL, WS_PCA_CSVAL, WS_PCA_Y, WS_PCA_S, WS_PCA_PARTW,
     WS_KNN_X, WS_KNN_UNIT, WS_KNN_FLAGS, WS_KNN_BEST_D, WS_KNN_BEST_I, WS_KNN_OUT_D, WS_KNN_OUT_I, WS_KNN_SM_IN, WS_KNN_SM_OUT,   // pilot_ot_knn.hip
+    WS_LV_VAL0, WS_LV_VAL1, WS_LV_DEG0, WS_LV_DEG1, WS_LV_IDX0, WS_LV_IDX1, WS_LV_TOT, WS_LV_SUMS, WS_LV_INT, WS_LV_FLAG, WS_LV_ECOMM,   // pilot_ot_louvain.hip
+    WS_LV_NKEYS, WS_LV_EKEYS, WS_LV_CNT,
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

@@ -1266,6 +1266,56 @@ def knn_connectivities(indices, distances, n_neighbors):
     return C
 
 
+# ---- Louvain communities (K17; sknetwork's Louvain of pilotpy's extract_annot_expression / reclustering_data, by a synchronous rule) --
+def _louvain_args(graph, resolution, tol, max_levels):
+    """(indptr int64, indices int32, data float64, n) of the square graph, every argument judged: nothing touches the library"""
+    import scipy.sparse as sp
+    if isinstance(resolution, bool) or not isinstance(resolution, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(resolution) or resolution < 0:
+        raise ValueError("resolution=%r: a finite number, not negative" % (resolution,))
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0:
+        raise ValueError("tol=%r: a number, not negative" % (tol,))
+    if isinstance(max_levels, bool) or not isinstance(max_levels, (int, np.integer)) or max_levels < 1:
+        raise ValueError("max_levels=%r: an integer of at least 1" % (max_levels,))
+    if sp.issparse(graph):
+        A = graph.tocsr()
+    else:
+        A = np.asarray(graph) if graph is not None else np.empty(0)
+        if A.ndim != 2 or A.dtype.kind not in "fiub":
+            raise ValueError("graph: a scipy sparse matrix or a square 2-D array of numbers, got %s %s" % (A.shape, A.dtype))
+        A = sp.csr_matrix(A)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("graph must be square, got %s" % (A.shape,))
+    if A.dtype.kind not in "fiub":
+        raise ValueError("graph: weights of dtype %s" % A.dtype)
+    n = A.shape[0]
+    if n > np.iinfo(np.int32).max:
+        raise NotImplementedError("%d nodes need more than 32-bit node indices" % n)
+    data = np.ascontiguousarray(A.data, dtype=np.float64)
+    if data.size and not (np.isfinite(data).all() and data.min() >= 0):
+        raise ValueError("graph: every weight must be finite and not negative")
+    return np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32), data, n
+
+
+def louvain(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
+    """K17: the Louvain communities of a weighted graph on the device (include/pilot_ot.h, "Louvain communities"), by a
+    SYNCHRONOUS rule: every node of a sweep chooses its move against the same snapshot, and a sweep is kept only if the modularity
+    rose by more than ``tol``; deterministic, no seed, the same bits from every call.  It is not sknetwork's sequential sweep, so
+    where the node order decides, the labels differ from sknetwork's; on clustered data the partitions agree.
+    ``graph``: a scipy sparse matrix of any format or a square ndarray, weights finite and >= 0; it may be unsymmetric (the
+    modularity is then Dugue and Perez's directed one at ``resolution``, as sknetwork's is; Newman's for a symmetric graph).
+    Returns ``labels`` (int32, 0 .. k-1 by decreasing community size, ties to the smallest member); with ``return_info``
+    ``(labels, dict(modularity, levels, sweeps, communities))``.  ValueError before any device work: a graph that is not square, a
+    weight negative or not finite, ``resolution`` negative or not finite, ``tol < 0``, ``max_levels < 1``."""
+    indptr, indices, data, n = _louvain_args(graph, resolution, tol, max_levels)
+    labels, q, info = np.empty(n, dtype=np.int32), ctypes.c_double(0.0), np.zeros(3, dtype=np.int32)
+    _lib.check(_lib.load().pilot_ot_louvain(n, _lib.lptr(indptr), _lib.iptr(indices), _lib.dptr(data), float(resolution), float(tol),
+                                            int(max_levels), _lib.iptr(labels), ctypes.byref(q), _lib.iptr(info)))
+    if return_info:
+        return labels, {"modularity": q.value, "levels": int(info[0]), "sweeps": int(info[1]), "communities": int(info[2])}
+    return labels
+
+
 def fitted_curves(params, model, times, noise=None, device=False):
     """One standardised curve per gene over ``times``: ``design(model[g], t) @ params[g]`` (``params``: G x 3 = Intercept, Treat,
     Treat2; ``model``: indices into :data:`TRAJFIT_MODELS`, or their names), plus, with ``noise`` (T x G per-time-point spreads,

@@ -34,7 +34,10 @@ deseq2_size_factors                            inputs of its R calls) and DESeq2
 pca, extract_annot_expression                  Trajectory.py:171-228 (scanpy's normalize_total / log1p / scale / tl.pca restated;
                                                no reclustering)
 neighbors                                      Trajectory.py:217-220, 1045-1060 (scanpy's pp.neighbors: the exact kNN graph of the
-                                               cells and UMAP's connectivities restated; no Louvain)
+                                               cells and UMAP's connectivities restated)
+louvain, reclustering_data                     Trajectory.py:217-220, 1000-1062 (sknetwork's Louvain(resolution) of the neighbour
+                                               graph by a synchronous, deterministic rule; no Leiden, so no tl.Clustering and
+                                               no return_sil_ari)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -856,11 +859,12 @@ def extract_annot_expression(adata, columns=["cell_type_original", "patient_regi
     -- ``adata.obsm[columns[3]]``, or with ``reduction`` the one :func:`pca` makes from ``adata.X`` (normalize_total(target_sum),
     log1p, scale(max_value), 50 components) and writes to ``adata.obsm['X_pca']``; unlike the reference, ``adata.X`` itself is
     left as it is.  ``annot``: ``adata.obs[columns[:3]]`` renamed ``cell_types, sampleID, status``.  ``reclustering`` (Louvain
-    communities of scanpy's neighbour graph) is not implemented and raises before any device work: :func:`neighbors` makes the
-    graph, the Louvain step is the missing part."""
+    communities of scanpy's neighbour graph) is not implemented here and raises before any device work: :func:`neighbors` makes
+    the graph, the Louvain step is the missing part of THIS function -- :func:`louvain` and :func:`reclustering_data` take it."""
     if reclustering:
         raise NotImplementedError("extract_annot_expression: reclustering is not implemented: tl.neighbors builds the neighbour graph "
-                                  "(obsp['distances'] / ['connectivities']), the Louvain communities of it are the missing part")
+                                  "(obsp['distances'] / ['connectivities']), the Louvain communities of it are the missing part here; "
+                                  "tl.louvain writes them to obs, tl.reclustering_data returns them")
     if reduction:
         data = pca(adata, normalize=True, target_sum=target_sum, scale=True, max_value=max_value)
     else:
@@ -918,6 +922,89 @@ def neighbors(adata, n_neighbors=15, n_pcs=None, use_rep="X_pca", metric="euclid
     adata.uns["neighbors" if key_added is None else key_added] = {
         "connectivities_key": prefix + "connectivities", "distances_key": prefix + "distances",
         "params": {"n_neighbors": int(n_neighbors), "method": "umap", "metric": metric, "use_rep": use_rep, "n_pcs": n_pcs}}
+
+
+# ---- Louvain communities of the neighbour graph (Trajectory.py:217-220, 1000-1062: sknetwork's Louvain(resolution)) -------------
+def _neighbor_graph(adata, mode, neighbors_key):
+    if mode not in ("connectivities", "distances"):
+        raise ValueError("mode=%r: connectivities or distances" % (mode,))
+    key = "neighbors" if neighbors_key is None else neighbors_key
+    entry = adata.uns.get(key) if hasattr(adata.uns, "get") else None
+    name = entry.get(mode + "_key") if isinstance(entry, dict) else None
+    obsp = getattr(adata, "obsp", None)
+    if name is None or obsp is None or name not in obsp:
+        raise ValueError("adata has no neighbour graph under uns[%r] / obsp: run tl.neighbors first" % (key,))
+    return obsp[name]
+
+
+def louvain(adata, resolution=1.0, mode="connectivities", neighbors_key=None, key_added="louvain"):
+    """The Louvain communities of the cells' neighbour graph, on the device (``engine.louvain``): reads the ``obsp`` matrix that
+    ``adata.uns[neighbors_key or 'neighbors']`` names for ``mode`` (``"connectivities"`` or ``"distances"``, what :func:`neighbors`
+    wrote), writes ``adata.obs[key_added]`` as a pandas Categorical of the strings ``"0" .. "k-1"`` (scanpy's convention; 0 is the
+    largest community) and ``adata.uns[key_added] = {'params': {'resolution', 'mode'}, 'modularity': Q}``.  Returns None.  A
+    missing graph raises ValueError naming ``tl.neighbors``.  The rule is synchronous and deterministic, not
+    sknetwork's or scanpy's sequential, seeded sweep: where the node order decides, the labels differ from theirs.  Leiden is not
+    offered."""
+    graph = _neighbor_graph(adata, mode, neighbors_key)
+    labels, info = engine.louvain(graph, resolution=resolution, return_info=True)
+    k = info["communities"]
+    adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=[str(c) for c in range(k)])
+    adata.uns[key_added] = {"params": {"resolution": resolution, "mode": mode}, "modularity": info["modularity"]}
+
+
+class _Cells:
+    """what reclustering_data's array branch hands to :func:`neighbors`: the reference wraps the array in an AnnData"""
+
+    def __init__(self, rep):
+        self.obsm, self.uns, self.obsp = {"X": rep}, {}, {}
+
+
+def reclustering_data(adata, resu=0.01, normalization=False, target_sum=1e6, n_neighbor=15, method_="umap", metric_t="cosine",
+                      mode="distances", origine_scr_rna=False, dimension_rect=False, n_component=25):
+    """The reference's re-clustering (Trajectory.py:1000-1062): the integer Louvain labels of the cells' neighbour graph.
+    ``origine_scr_rna=True``: ``adata`` is an AnnData; :func:`pca` (50 components; ``normalize_total(target_sum)``, ``log1p`` and
+    ``scale(max_value=10)`` iff ``normalization``) then :func:`neighbors` (``n_neighbors=n_neighbor``, ``metric=metric_t``,
+    ``n_pcs=n_component`` iff ``dimension_rect``); a matrix of at most 50 genes without ``dimension_rect`` gives its neighbours from
+    X itself, as scanpy does (with ``normalization`` that case raises NotImplementedError: the scaled matrix is never formed).  ``origine_scr_rna=False``: ``adata`` is a cells x features array and the neighbours are scanpy's
+    defaults (15, euclidean), found on the array itself when it has at most 50 columns, else on its 50-component ``engine.pca``
+    (no scaling).  Then ``engine.louvain`` of the ``mode`` matrix (``"distances"`` or ``"connectivities"``) at resolution ``resu``;
+    returns the int32 label array.  ``method_`` other than ``"umap"`` raises ValueError.  Deviations from pilotpy: the Louvain rule
+    is the synchronous one of DESIGN.md K17, not sknetwork's sequential sweep, so labels differ from pilotpy's where sknetwork's
+    node order matters; ``adata.X`` and ``adata.raw`` are left alone (the reference normalises and scales ``adata`` in place); with
+    ``origine_scr_rna`` the graph is left in ``adata.obsp`` / ``adata.uns['neighbors']`` and the scores in ``adata.obsm['X_pca']``,
+    as scanpy leaves them."""
+    if method_ != "umap":
+        raise ValueError("method_=%r: only 'umap' (scanpy's default connectivities) is offered" % (method_,))
+    if mode not in ("connectivities", "distances"):
+        raise ValueError("mode=%r: connectivities or distances" % (mode,))
+    engine._louvain_args(np.zeros((1, 1)), resu, 0.0, 1)
+    if origine_scr_rna:
+        n_vars = adata.X.shape[1]
+        if dimension_rect or n_vars > 50:
+            pca(adata, n_comps=50, normalize=bool(normalization), target_sum=target_sum, scale=bool(normalization), max_value=10)
+            neighbors(adata, n_neighbors=n_neighbor, metric=metric_t, n_pcs=n_component if dimension_rect else None)
+        else:
+            if normalization:
+                raise NotImplementedError("reclustering_data: normalization=True with at most 50 genes and dimension_rect=False would take the "
+                                          "neighbours from the normalised and scaled matrix itself, which is not formed here")
+            cells = _Cells(_dense_rows(adata.X.toarray() if _is_sparse(adata.X) else adata.X, slice(None)))
+            neighbors(cells, n_neighbors=n_neighbor, metric=metric_t, use_rep="X")
+            if getattr(adata, "obsp", None) is None:
+                adata.obsp = {}
+            adata.obsp.update(cells.obsp)
+            adata.uns["neighbors"] = cells.uns["neighbors"]
+        graph = adata.obsp[mode]
+    else:
+        X = np.asarray(adata)
+        if X.ndim != 2:
+            raise ValueError("adata: a cells x features array, got shape %s" % (X.shape,))
+        rep = _dense_rows(X, slice(None))
+        if rep.shape[1] > 50:
+            rep = engine.pca(rep, n_comps=50, scale=False)[0]
+        cells = _Cells(rep)
+        neighbors(cells, use_rep="X")
+        graph = cells.obsp[mode]
+    return engine.louvain(graph, resolution=resu)
 
 
 # ---- gene-cluster differentiation (Gene_cluster_specific.py:8-201, Trajectory.py:1129-1172) --------------------------------

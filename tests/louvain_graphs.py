@@ -46,6 +46,27 @@ def hub(n=200, hub_degree=150, seed=8):
     return W.tocsr()
 
 
+# the degrees of nodes 0 .. 10 of tile_crossing(): one either side of every limit of the move kernels' degree bins and of the
+# workgroup kernel's staging, sort and LDS sizes (DESIGN.md K17 lists which degree reaches which path)
+LADDER = (63, 64, 65, 256, 257, 512, 513, 4096, 4097, 8192, 8193)
+
+
+def tile_crossing(n=9000, seed=21):
+    """random_symmetric(n, 6, seed) with nodes 0 .. 31 cut out of it; node t < 11 is then joined to LADDER[t] distinct nodes of
+    32 .. n-1 with weights 1 .. 3, both directions; nodes 11 .. 31 stay isolated.  Symmetric, exact, largest other degree 19"""
+    W = random_symmetric(n, 6, seed).tocoo()
+    keep = (W.row >= 32) & (W.col >= 32)
+    rows, cols, vals = [W.row[keep]], [W.col[keep]], [W.data[keep]]
+    rng = np.random.default_rng(seed)
+    for t, d in enumerate(LADDER):
+        others = rng.choice(np.arange(32, n), d, replace=False)
+        weights = rng.integers(1, 4, d).astype(np.float64)
+        rows += [np.full(d, t), others]
+        cols += [others, np.full(d, t)]
+        vals += [weights, weights]
+    return sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n)).tocsr()
+
+
 def odd_ends():
     """(raw CSR, n): isolated nodes (2, 9), a node whose only entry is a self-loop (5), a self-loop beside edges (0), repeated and
     unsorted columns (rows 0, 3, 7), a stored zero (row 4), two triangles and a tail; unsymmetric"""

@@ -2,7 +2,16 @@
 
 Exact cases: integer weights, resolution in {1, 0.5, 0.25}, tol = 0.  Every quantity of the rule is then an integer (or a multiple of
 1/4) below 2^53 in float64, so no sum order or rounding can excuse a difference: the labels must equal the restatement's element
-for element, under every setting of the degree bins.  Float weights: a planted partition, where the partition must be the
+for element, under every setting of the degree bins.  The small graphs (12 .. 300 nodes) run the one-tile form of everything;
+three larger exact ones cross the limits of the host's dispatch (the table is in DESIGN.md K17):
+  directed_knn_ranks(n=2049)  the node sort past one LDS tile of 2048: P = 4096, one real key and 2047 pads in the second tile;
+  directed_knn_ranks(n=4096)  the same with P = m and no pad; both unsymmetric, nnz(S) > 8192: the edge sort over 8 / 16 tiles and
+                              the scan's carry on the edge heads;
+  tile_crossing()             9000 nodes (the rank scan past 8192, node sort P = 16 384, edge sort P = 131 072) with degrees 63, 64,
+                              65, 256, 257, 512, 513, 4096, 4097, 8192, 8193: both sides of the wave / workgroup / long bins, the
+                              workgroup kernel with many elements per thread at 64 and 128 KiB of LDS, the long kernel at its
+                              default limit; level 1 (3068 nodes at resolution 1) sorts past one tile again.
+Integer weights make the rule indifferent to a sum's order, so these show a lost, doubled or misplaced element.  Float weights: a planted partition, where the partition must be the
 restatement's, and graphs without structure, where the modularity is held to the sequential reference's."""
 import numpy as np
 import pandas as pd
@@ -81,6 +90,105 @@ def test_every_degree_bin_gives_the_same_labels(name):
                 _check_exact(A, gamma, expect[gamma])
     finally:
         _lib.test_switch("PILOT_OT_LOUVAIN_BINS", None)
+
+
+# ---- past one sort tile, one scan round and 64 KiB of LDS ---------------------------------------------------------------------------
+# The graphs above have at most 300 nodes: one LDS tile of the global sort, one round of the scan, a workgroup kernel with one
+# element per thread.  The ones below cross each of those limits (DESIGN.md K17 has the table of which size reaches which path)
+# and are still exact, so the labels are still held element for element.  A restatement run takes seconds here: every expectation
+# is computed once per (graph, resolution) and shared.
+_GRAPHS, _EXPECT = {}, {}
+
+
+def _big_graph(name, **kw):
+    key = (name,) + tuple(sorted(kw.items()))
+    if key not in _GRAPHS:
+        _GRAPHS[key] = getattr(LG, name)(**kw)
+    return key, _GRAPHS[key]
+
+
+def _expected(key, gamma):
+    if (key, gamma) not in _EXPECT:
+        _EXPECT[key, gamma] = LR.louvain(_GRAPHS[key], gamma, 0.0)
+        print("restatement %s resolution %g: (levels, sweeps, communities) = %s, Q = %.6f" % (key, gamma, _EXPECT[key, gamma][2], _EXPECT[key, gamma][1]))
+    return _EXPECT[key, gamma]
+
+
+def _second_level(A, gamma):
+    """(m, nnz, largest degree) of the graph the restatement's first level aggregates to, by its own run_level and aggregate"""
+    A = LR.as_csr(A)
+    out, inn, w = LR.degrees(A)
+    S = (A + A.T).tocsr()
+    S.sum_duplicates()
+    S.sort_indices()
+    L = LR._Level(S.indptr.astype(np.int64), S.indices.astype(np.int64), S.data.copy(), out, inn)
+    comm, Out, In, size, _, _ = LR.run_level(L, w, gamma, 0.0)
+    coarse = LR.aggregate(L, comm, Out, In, size)[0]
+    return coarse.m, len(coarse.indices), int(np.diff(coarse.indptr).max())
+
+
+# what the restatement returns on LG.tile_crossing() at tol = 0 (resolution: (levels, sweeps, communities)), computed on the CPU
+TILE_CROSSING_RUNS = {1.0: (6, 18, 71), 0.5: (4, 24, 24), 0.25: (4, 20, 22)}
+
+
+@pytest.mark.parametrize("gamma", GAMMAS)
+def test_tile_crossing(gamma):
+    """9 000 nodes, nnz(S) = 106 198, degrees either side of every bin and LDS limit: at level 0 the node sort runs 8 tiles
+    (P = 16 384) and the edge sort 64 (P = 131 072), both scans carry past 8 192, the workgroup kernel runs with up to 32 elements
+    per thread and 128 KiB of LDS, the long kernel at its default limit (degree 8 193).  At resolution 1 level 1 has 3 068 nodes
+    (the node sort past one tile again) and hubs of degree ~3 000 in the workgroup bin (P = 4 096, 64 KiB).  The facts are asserted
+    on the graph and the restatement before the device is touched"""
+    key, A = _big_graph("tile_crossing")
+    S = (A + A.T).tocsr()
+    deg = np.diff(S.indptr)
+    assert (A != A.T).nnz == 0 and deg[:11].tolist() == list(LG.LADDER) and deg[11:].max() == 19 and (deg == 0).sum() == 21
+    assert A.shape[0] == 9000 > 8192 and S.nnz == 106198 and A.data.sum() == 347014.0 and LG.exact_enough(A)
+    expect = _expected(key, gamma)
+    assert expect[2] == TILE_CROSSING_RUNS[gamma]
+    if gamma == 1.0:
+        assert abs(expect[1] - 0.350633) <= 5e-7
+        m1, nnz1, deg1 = _second_level(A, gamma)
+        print("level 1: m %d nnz %d largest degree %d" % (m1, nnz1, deg1))
+        assert (m1, nnz1) == (3068, 69189) and m1 > 2048 and 2048 < deg1 <= 4096
+    _check_exact(A, gamma, expect)
+
+
+@pytest.mark.parametrize("bins", ["64,512", "8,8192"])
+def test_tile_crossing_under_other_bins(bins):
+    """"64,512": the degrees 513 .. 8 193 (and level 1's hubs) go to the long kernel; "8,8192": thousands of nodes of degree 9 .. 19
+    go to the workgroup kernel, P = 16 or 32 beside P = 8 192 in one launch.  The labels never change"""
+    key, A = _big_graph("tile_crossing")
+    expect = {gamma: _expected(key, gamma) for gamma in GAMMAS}
+    try:
+        _lib.test_switch("PILOT_OT_LOUVAIN_BINS", bins)
+        for gamma in GAMMAS:
+            _check_exact(A, gamma, expect[gamma])
+    finally:
+        _lib.test_switch("PILOT_OT_LOUVAIN_BINS", None)
+
+
+@pytest.mark.parametrize("bins", [None, "8,8192"])
+def test_tile_crossing_twice(bins):
+    """the bin lists are filled by integer atomics in no fixed order (8 workgroup-bin nodes and a long-bin one; thousands under
+    "8,8192"): two calls give the same labels and the same info, bit for bit"""
+    A = _big_graph("tile_crossing")[1]
+    try:
+        _lib.test_switch("PILOT_OT_LOUVAIN_BINS", bins)
+        labels, info = engine.louvain(A, tol=0.0, return_info=True)
+        again, info2 = engine.louvain(A, tol=0.0, return_info=True)
+    finally:
+        _lib.test_switch("PILOT_OT_LOUVAIN_BINS", None)
+    assert np.array_equal(again, labels) and info2 == info, (info, info2)
+
+
+@pytest.mark.parametrize("gamma", [1.0, 0.25])
+@pytest.mark.parametrize("n", [2049, 4096])
+def test_directed_knn_ranks_past_a_tile(n, gamma):
+    """unsymmetric and exact; 2 049 nodes: the node sort has P = 4 096, one real key and 2 047 pads in its second tile; 4 096: P = m,
+    no pad at all"""
+    key, A = _big_graph("directed_knn_ranks", n=n)
+    assert A.shape[0] == n > 2048 and (A != A.T).nnz > 0
+    _check_exact(A, gamma, _expected(key, gamma))
 
 
 class _Adata:

@@ -209,3 +209,21 @@ def test_restatement_keeps_its_promises():
     odd, n = LG.odd_ends()
     assert odd.nnz > LR.as_csr(odd).nnz                             # repeats and a stored zero
     assert LR.ordered_sum(np.arange(1000.0)) == 499500.0
+
+
+def test_tile_crossing_graph_is_what_the_device_tests_need():
+    """the structure tests/test_gpu_louvain.py relies on to reach the tiled sort, the scan's carry and every degree bin's limits
+    (no restatement run here)"""
+    A = LG.tile_crossing()
+    assert A.shape == (9000, 9000) and (A != A.T).nnz == 0 and LG.exact_enough(A) and A.data.min() >= 1.0
+    S = LR.as_csr(A) + LR.as_csr(A).T
+    deg = np.diff(S.tocsr().indptr)
+    assert deg[:11].tolist() == list(LG.LADDER) == [63, 64, 65, 256, 257, 512, 513, 4096, 4097, 8192, 8193]
+    assert deg[11:32].tolist() == [0] * 21 and (deg == 0).sum() == 21 and deg[32:].max() == 19
+    assert A.shape[0] > 8192 and S.nnz == 106198 > 8192 and A.data.sum() == 347014.0
+    assert S.diagonal().sum() == 0.0
+    B = LG.tile_crossing()                                          # deterministic
+    assert (A != B).nnz == 0 and np.array_equal(A.indices, B.indices)
+    for n in (2049, 4096):                                          # the two sizes of the unsymmetric graph past one sort tile
+        K = LG.directed_knn_ranks(n=n)
+        assert K.shape == (n, n) and (K != K.T).nnz > 0 and LG.exact_enough(K)

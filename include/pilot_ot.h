@@ -362,7 +362,8 @@ int pilot_ot_diffusion_kernel_of_rows(const double *E, int E_is_device, int N, i
  * _dev: device pointers, synchronises `stream` (the tridiagonal problem is solved on the host); info on the host.
  * _of_rows: the whole chain from E (on the host, or in HBM when E_is_device): E / max(E) -> Euclidean row distances -> k-nn
  * Gaussian kernel -> the above; dmap / evecs / evals / info on the host. */
-#define PILOT_OT_DIFFMAP_NOT_CONVERGED 1  /* the basis cap (min(N, 1024) vectors) was reached before every wanted Ritz pair converged */
+#define PILOT_OT_DIFFMAP_NOT_CONVERGED 1  /* the basis cap (min(N, 1024) vectors) was reached before every wanted Ritz pair converged
+                                           * and a verification block showed that no copy of a wanted eigenvalue is hidden */
 #define PILOT_OT_DIFFMAP_DEGENERATE 2     /* more than one eigenvalue mu of P with mu >= 1 - 1e-10: a (nearly) disconnected graph */
 int pilot_ot_diffusion_map_dev(const double *d_K, int N, double epsilon, double alpha, int n_evecs, double *d_dmap, double *d_evecs,
                                double *d_evals, int *info, void *stream);
@@ -550,7 +551,8 @@ int pilot_ot_group_sums_col_block(void);
  * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, scale not 0 / 1, max_value not positive, a column out of range or named
  * twice, n < 2, n_comps out of range, for the dense call dtype / ld / n_cols_total as in pilot_ot_group_moments; after the moments
  * pass: a non-finite value in a selected column.  PILOT_OT_ENOTSUP: n > INT_MAX. */
-#define PILOT_OT_PCA_NOT_CONVERGED 1   /* the basis cap was reached before every wanted Ritz pair converged */
+#define PILOT_OT_PCA_NOT_CONVERGED 1   /* the basis cap was reached before every wanted Ritz pair converged and a verification
+                                        * block showed that no copy of a wanted eigenvalue is hidden */
 #define PILOT_OT_PCA_RANK_DEFICIENT 2  /* the Krylov space ended before n_comps pairs, or a wanted lambda <= n_sel * DBL_EPSILON * lambda_0 */
 /* of a sparse matrix: the forward product reads the row form, the transposed one the column form (built if need be) */
 int pilot_ot_csr_pca(pilot_ot_csr *csr, const int *cols, int n_sel, int scale, double max_value, int n_comps, double *scores,

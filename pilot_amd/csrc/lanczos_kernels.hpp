@@ -79,29 +79,11 @@ __device__ inline double lz_restart_entry(int n, int c) {
     return 2.0 * ((double)(z >> 11) * 0x1.0p-53) - 1.0;
 }
 
-// End of Lanczos step j (basis V[0..j] holds j + 1 vectors, w = S v_j after the two Gram-Schmidt passes with coefficients h1, h2):
-//   alpha[j] = h1[j] + h2[j];  beta[j] = |w|;  V[j + 1] = w / beta[j]  (when j + 1 < B).
-// Breakdown (beta[j] <= tol: the Krylov space is invariant -- at step 0 always, since V[0] is an eigenvector): beta[j] = 0 and
-// V[j + 1] is the next restart vector, orthogonalised against V[0..j] by two classical Gram-Schmidt passes and normalised; the
-// restart count lives in *n_restart.  One workgroup of DM_FIN threads; w is overwritten.
-static __global__ void __launch_bounds__(DM_FIN) lz_finish_kernel(double *__restrict__ V, int N, int j, int B, double *__restrict__ w,
-                                                                  const double *__restrict__ h1, const double *__restrict__ h2,
-                                                                  double tol, double *__restrict__ alpha, double *__restrict__ beta,
-                                                                  int *__restrict__ n_restart) {
-    __shared__ double red[DM_FIN];
-    __shared__ double hs[1024];                               // (B <= 1024)
-    double s = 0.0;
-    for (int n = threadIdx.x; n < N; n += DM_FIN) s += w[n] * w[n];
-    const double b = sqrt(dm_block_sum<DM_FIN>(s, red));
-    if (threadIdx.x == 0) alpha[j] = h1[j] + h2[j];
-    if (b > tol) {
-        if (threadIdx.x == 0) beta[j] = b;
-        if (j + 1 < B)
-            for (int n = threadIdx.x; n < N; n += DM_FIN) V[(size_t)(j + 1) * N + n] = w[n] / b;
-        return;
-    }
-    if (threadIdx.x == 0) beta[j] = 0.0;
-    if (j + 1 >= B) return;                                   // (basis complete: nothing to continue with)
+// V[j + 1] = the next restart vector (number *n_restart, which is counted up), orthogonalised against V[0..j] by two classical
+// Gram-Schmidt passes and normalised.  For every thread of a workgroup of DM_FIN threads; w (N) is overwritten, red (DM_FIN) and
+// hs (1024 >= j + 1) are LDS.
+__device__ inline void lz_restart_into(double *__restrict__ V, int N, int j, double *__restrict__ w, int *__restrict__ n_restart,
+                                       double *red, double *hs) {
     const int c = *n_restart;
     __syncthreads();
     if (threadIdx.x == 0) *n_restart = c + 1;
@@ -124,10 +106,46 @@ static __global__ void __launch_bounds__(DM_FIN) lz_finish_kernel(double *__rest
         }
         __syncthreads();
     }
-    s = 0.0;
+    double s = 0.0;
     for (int n = threadIdx.x; n < N; n += DM_FIN) s += w[n] * w[n];
     const double r = sqrt(dm_block_sum<DM_FIN>(s, red));
     for (int n = threadIdx.x; n < N; n += DM_FIN) V[(size_t)(j + 1) * N + n] = w[n] / r;
+}
+
+// End of Lanczos step j (basis V[0..j] holds j + 1 vectors, w = S v_j after the two Gram-Schmidt passes with coefficients h1, h2):
+//   alpha[j] = h1[j] + h2[j];  beta[j] = |w|;  V[j + 1] = w / beta[j]  (when j + 1 < B).
+// Breakdown (beta[j] <= tol: the Krylov space is invariant -- at step 0 always, since V[0] is an eigenvector): beta[j] = 0 and
+// V[j + 1] is the next restart vector (lz_restart_into); the restart count lives in *n_restart.  One workgroup of DM_FIN threads;
+// w is overwritten.
+static __global__ void __launch_bounds__(DM_FIN) lz_finish_kernel(double *__restrict__ V, int N, int j, int B, double *__restrict__ w,
+                                                                  const double *__restrict__ h1, const double *__restrict__ h2,
+                                                                  double tol, double *__restrict__ alpha, double *__restrict__ beta,
+                                                                  int *__restrict__ n_restart) {
+    __shared__ double red[DM_FIN];
+    __shared__ double hs[1024];                               // (B <= 1024)
+    double s = 0.0;
+    for (int n = threadIdx.x; n < N; n += DM_FIN) s += w[n] * w[n];
+    const double b = sqrt(dm_block_sum<DM_FIN>(s, red));
+    if (threadIdx.x == 0) alpha[j] = h1[j] + h2[j];
+    if (b > tol) {
+        if (threadIdx.x == 0) beta[j] = b;
+        if (j + 1 < B)
+            for (int n = threadIdx.x; n < N; n += DM_FIN) V[(size_t)(j + 1) * N + n] = w[n] / b;
+        return;
+    }
+    if (threadIdx.x == 0) beta[j] = 0.0;
+    if (j + 1 >= B) return;                                   // (basis complete: nothing to continue with)
+    lz_restart_into(V, N, j, w, n_restart, red, hs);
+}
+
+// The start of a verification block after step j (j + 1 < B <= 1024), without a breakdown: beta[j] = 0 and V[j + 1] is the next
+// restart vector in place of the Krylov vector that step j wrote there.  One workgroup of DM_FIN threads; w is overwritten.
+static __global__ void __launch_bounds__(DM_FIN) lz_restart_kernel(double *__restrict__ V, int N, int j, double *__restrict__ w,
+                                                                   double *__restrict__ beta, int *__restrict__ n_restart) {
+    __shared__ double red[DM_FIN];
+    __shared__ double hs[1024];
+    if (threadIdx.x == 0) beta[j] = 0.0;
+    lz_restart_into(V, N, j, w, n_restart, red, hs);
 }
 
 // Ritz vectors and the back-transform: psi[n][c] = dis[n] * sum_k Z[k][c] V[k][n] (k < nk, in order), c < m.  Z: nk x m row-major.

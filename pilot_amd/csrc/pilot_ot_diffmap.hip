@@ -17,8 +17,8 @@
 
 namespace {
 
-constexpr int MAX_BASIS = pilot::LZ_MAX_BASIS, MAX_EVECS = pilot::LZ_MAX_EVECS, CHECK_EVERY = pilot::LZ_CHECK_EVERY;
-constexpr double RESID_TOL = pilot::LZ_RESID_TOL, BREAKDOWN_TOL = pilot::LZ_BREAKDOWN_TOL;
+constexpr int MAX_BASIS = pilot::LZ_MAX_BASIS, MAX_EVECS = pilot::LZ_MAX_EVECS;
+constexpr double BREAKDOWN_TOL = pilot::LZ_BREAKDOWN_TOL;
 constexpr double DEGENERATE_MU = 1.0 - 1e-10;
 using pilot::order_desc;
 using pilot::tridiag_ql;
@@ -72,41 +72,28 @@ PILOT_API int pilot_ot_diffusion_map_dev(const double *d_K, int N, double epsilo
     HIP_TRY(hipMemsetAsync(n_restart, 0, sizeof(int), s));
     HIP_TRY(hipGetLastError());
 
-    // Lanczos: step j extends the basis V[0..j] by V[j + 1]; every CHECK_EVERY steps T is read back and its Ritz pairs tested
-    std::vector<double> ha(B), hb(B), d, e, z;
-    int steps = 0, next_check = m;
-    bool converged = false;
-    while (steps < B) {
-        const int j = steps, nk = j + 1;
-        const double *vj = V + (size_t)j * N;
-        hipLaunchKernelGGL(pilot::lz_gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, s, S, N, vj, w);
-        pilot::lanczos_step(V, N, j, B, w, h1, h2, BREAKDOWN_TOL, al, be, n_restart, s);
-        HIP_TRY(hipGetLastError());
-        steps = nk;
-        if (steps < next_check && steps < B) continue;
-        next_check = steps + CHECK_EVERY;
-        HIP_TRY(hipMemcpyAsync(ha.data(), al, sizeof(double) * steps, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(hb.data(), be, sizeof(double) * steps, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (steps == N) { converged = true; break; }           // a complete basis: T is similar to S
-        // a breakdown after step 0 (step 0 always breaks down: V[0] is an eigenvector) means the Krylov space of a restart
-        // vector was exhausted; what lies outside it is unexplored, so only a complete basis is accepted from then on
-        bool late_breakdown = false;
-        for (int k = 1; k < steps; ++k) late_breakdown |= hb[k] == 0.0;
-        if (late_breakdown) continue;
-        d.assign(ha.begin(), ha.begin() + steps);
-        e.assign(hb.begin(), hb.begin() + steps);
-        z.assign(steps, 0.0);
-        z[steps - 1] = 1.0;
-        if (!tridiag_ql(steps, d.data(), e.data(), z.data(), 1)) continue;
-        const std::vector<int> ix = order_desc(d);
-        bool ok = true;
-        for (int c = 0; c < m; ++c) ok &= std::fabs(hb[steps - 1] * z[ix[c]]) <= RESID_TOL;
-        if (ok) { converged = true; break; }
-    }
+    // Lanczos (lanczos_run: the steps, the look at T every LZ_CHECK_EVERY steps from step m on, and the acceptance rule).  Step 0
+    // always breaks down (V[0] is an eigenvector); converged wanted pairs only begin the verification block, whose steps are not
+    // part of the result unless it found something and the basis went on to become complete.
+    pilot::LanczosSpec spec;
+    spec.N = N;
+    spec.B = B;
+    spec.want = m;
+    spec.breakdown = BREAKDOWN_TOL;
+    spec.norm = 1.0;                                           // |S| = 1
+    spec.floor_rel = 0.0;
+    spec.start_is_eigenvector = true;
+    pilot::LanczosRun run;
+    HIP_TRY(pilot::lanczos_run(spec, V, w, h1, h2, al, be, n_restart, s, [&](const double *vj, double *wj) {
+        hipLaunchKernelGGL(pilot::lz_gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, s, S, N, vj, wj);
+    }, &run));
+    const std::vector<double> &ha = run.ha, &hb = run.hb;
+    const int steps = run.steps;
+    const bool converged = run.converged;
+    std::vector<double> d, e, z;
 
     // the Ritz pairs of the final basis: eigenvectors of T as columns
-    const int nk = steps;
+    const int nk = run.nk;
     d.assign(ha.begin(), ha.begin() + nk);
     e.assign(hb.begin(), hb.begin() + nk);
     z.assign((size_t)nk * nk, 0.0);

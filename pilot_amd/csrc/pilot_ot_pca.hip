@@ -93,47 +93,32 @@ int solve(const Operator &op, const std::vector<double> &ssq, int k, double *sco
     HIP_TRY(hipMemsetAsync(n_restart, 0, sizeof(int), s));
     HIP_TRY(hipGetLastError());
 
-    // Lanczos: step j extends the basis V[0..j] by V[j + 1]; every LZ_CHECK_EVERY steps T is read back and its Ritz pairs tested
-    const double breakdown = pilot::LZ_BREAKDOWN_TOL * trace;
-    std::vector<double> ha(B), hb(B), d, e, z;
-    int steps = 0, next_check = k;
-    bool converged = false;
-    while (steps < B) {
-        const int j = steps;
-        const double *vj = V + (size_t)j * D;
+    // Lanczos (lanczos_run: the steps, the look at T every LZ_CHECK_EVERY steps from step k on, and the acceptance rule).  A
+    // breakdown means that the Krylov space of the start vector is invariant: its Ritz pairs are eigenpairs, but it holds only one
+    // direction per distinct eigenvalue, so a breakdown, like k converged pairs, only begins the verification block; the steps of
+    // that block are not part of the result unless it found something and the basis went on to become complete.
+    pilot::LanczosSpec spec;
+    spec.N = D;
+    spec.B = B;
+    spec.want = k;
+    spec.breakdown = pilot::LZ_BREAKDOWN_TOL * trace;
+    spec.norm = 0.0;                                           // tolerances relative to the leading Ritz value
+    spec.floor_rel = (double)D * std::numeric_limits<double>::epsilon();
+    spec.start_is_eigenvector = false;
+    pilot::LanczosRun run;
+    HIP_TRY(pilot::lanczos_run(spec, V, w, h1, h2, al, be, n_restart, s, [&](const double *vj, double *wj) {
         hipLaunchKernelGGL(pilot::pca_dot_kernel, dim3(1), dim3(pilot::DM_FIN), 0, s, op.sbar, vj, D, dot);
         op.forward(vj, dot, t);
         hipLaunchKernelGGL(pilot::pca_sum_kernel, dim3(pilot::PCA_SUM_BLOCKS), dim3(256), 0, s, t, n, part);
-        op.transposed(t, part, w);
-        pilot::lanczos_step(V, D, j, B, w, h1, h2, breakdown, al, be, n_restart, s);
-        HIP_TRY(hipGetLastError());
-        steps = j + 1;
-        if (steps < next_check && steps < B) continue;
-        next_check = steps + pilot::LZ_CHECK_EVERY;
-        HIP_TRY(hipMemcpyAsync(ha.data(), al, sizeof(double) * steps, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(hb.data(), be, sizeof(double) * steps, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        // a breakdown: the Krylov space of the start vector is invariant, its Ritz pairs are eigenpairs and it holds every
-        // eigen-direction of A (one per distinct eigenvalue); the steps after it explored a restart vector and are dropped
-        int first = -1;
-        for (int q = 0; q < steps && first < 0; ++q)
-            if (hb[q] == 0.0) first = q;
-        if (first >= 0) { steps = first + 1; converged = true; break; }
-        if (steps == D) { converged = true; break; }           // a complete basis: T is similar to A
-        d.assign(ha.begin(), ha.begin() + steps);
-        e.assign(hb.begin(), hb.begin() + steps);
-        z.assign(steps, 0.0);
-        z[steps - 1] = 1.0;
-        if (!pilot::tridiag_ql(steps, d.data(), e.data(), z.data(), 1)) continue;
-        const std::vector<int> ix = pilot::order_desc(d);
-        const double tol = pilot::LZ_RESID_TOL * d[ix[0]];
-        bool ok = true;
-        for (int c = 0; c < k; ++c) ok &= std::fabs(hb[steps - 1] * z[ix[c]]) <= tol;
-        if (ok) { converged = true; break; }
-    }
+        op.transposed(t, part, wj);
+    }, &run));
+    const std::vector<double> &ha = run.ha, &hb = run.hb;
+    const int steps = run.steps;
+    const bool converged = run.converged;
+    std::vector<double> d, e, z;
 
     // the Ritz pairs of the final basis: eigenvectors of T as columns
-    const int nk = steps, have = std::min(k, nk);
+    const int nk = run.nk, have = std::min(k, nk);
     d.assign(ha.begin(), ha.begin() + nk);
     e.assign(hb.begin(), hb.begin() + nk);
     z.assign((size_t)nk * nk, 0.0);

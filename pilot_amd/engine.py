@@ -1161,9 +1161,9 @@ def pca(Y, n_comps=50, scale=True, max_value=10.0, cols=None, return_info=False)
     positive.  All arithmetic is float64 in a fixed order: a repeated call, and float32 / float64 uploads of the same values,
     return the same bits.  Every argument is checked before any device work (ValueError: fewer than 2 rows, ``n_comps`` outside
     ``[1, min(rows - 1, columns - 1, 64)]``, a column out of range or repeated, ``max_value`` not positive, a non-finite value
-    of a host array).  A matrix with fewer than ``n_comps`` directions, or no convergence within the basis of min(columns, 1024)
-    vectors, raises ValueError; with ``return_info`` nothing is raised and a fifth item, ``dict(steps, flags, converged,
-    rank_deficient)``, tells."""
+    of a host array).  A matrix with fewer than ``n_comps`` directions, or no verified convergence within the basis of
+    min(columns, 1024) vectors (a repeated eigenvalue is found or the call says so), raises ValueError; with
+    ``return_info`` nothing is raised and a fifth item, ``dict(steps, flags, converged, rank_deficient)``, tells."""
     if isinstance(Y, DeviceCSR):
         return Y.pca(n_comps=n_comps, scale=scale, max_value=max_value, cols=cols, return_info=return_info)
     Y = _dense_arg(Y, "Y", mode="strict")

@@ -1,5 +1,8 @@
 """Diffusion map on the device (K8: pilot_ot_diffusion_map_dev / _of_rows, engine.diffusion_map_*, tl.diffusion_map) against the
-numpy / scipy restatement of pydiffmap (tests/diffmap_restatement.py) and a dense eigensolver."""
+numpy / scipy restatement of pydiffmap (tests/diffmap_restatement.py) and a dense eigensolver; symmetric clouds (lattices, rings, a
+three-fold cohort), whose leading eigenvalues repeat, against the dense eigensolver by eigenvalue lists, residuals and projectors."""
+import functools
+
 import numpy as np
 import pytest
 from scipy.spatial.distance import cdist
@@ -147,6 +150,112 @@ def test_full_gaussian_kernel_against_a_dense_eigensolver(N):
     check_sign_rule(evecs)
 
 
+# ---- repeated eigenvalues: symmetric clouds ------------------------------------------------------------------------------------------
+# A point cloud with a symmetry (a square lattice, a ring, a three-fold cohort) gives the Markov operator repeated eigenvalues among
+# the leading ones, and a Krylov space grown from one vector holds one direction per distinct eigenvalue: a single-vector Lanczos
+# run that accepts as soon as the wanted Ritz pairs have converged can return the next distinct eigenvalue in place of the copy.
+def _lattice(a):
+    i, j = np.meshgrid(np.arange(a, dtype=np.float64), np.arange(a, dtype=np.float64), indexing="ij")
+    return np.stack([i.ravel(), j.ravel()], axis=1)
+
+
+def _ring(N):
+    t = 2.0 * np.pi * np.arange(N) / N
+    return np.stack([np.cos(t), np.sin(t)], axis=1)
+
+
+def _threefold():
+    rng = np.random.default_rng(11)
+    X = rng.standard_normal((15, 2)) + np.array([3.0, 0.0])        # 15 points drawn once, placed at radius 3
+    out = []
+    for turn in (0.0, 2.0 * np.pi / 3.0, 4.0 * np.pi / 3.0):
+        c, s_ = np.cos(turn), np.sin(turn)
+        out.append(X @ np.array([[c, s_], [-s_, c]]))
+    return np.concatenate(out)
+
+
+CLOUDS = {"lattice5": (lambda: _lattice(5), 2.0), "lattice6": (lambda: _lattice(6), 0.5), "lattice8": (lambda: _lattice(8), 1.0),
+          "lattice10": (lambda: _lattice(10), 0.5), "ring12": (lambda: _ring(12), 0.05), "ring64": (lambda: _ring(64), 0.05),
+          "ring200": (lambda: _ring(200), 0.05), "threefold": (_threefold, 1.0)}
+SYMMETRIC_CASES = ([(c, al, ne) for c in ("lattice5", "lattice6", "lattice8", "lattice10") for al in (0.0, 0.5, 1.0) for ne in (1, 2, 3, 4, 5)]
+                   + [(c, 0.5, ne) for c in ("ring12", "ring64", "ring200") for ne in (1, 2, 4)]
+                   + [("threefold", 0.5, ne) for ne in (1, 2, 3, 4)])
+
+
+@functools.lru_cache(maxsize=None)
+def _symmetric_reference(cloud, alpha):
+    """(K, d, P, mu descending, phi to match) of the full Gaussian kernel of the cloud: numpy's eigh of S, as in
+    test_full_gaussian_kernel_against_a_dense_eigensolver"""
+    make, eps = CLOUDS[cloud]
+    X = make()
+    K = np.exp(-((X[:, None, :] - X[None, :, :]) ** 2).sum(-1) / (4 * eps))
+    qa = K.sum(1) ** -alpha
+    A = qa[:, None] * K * qa[None, :]
+    d = A.sum(1)
+    S = A / np.sqrt(d)[:, None] / np.sqrt(d)[None, :]
+    mu, phi = np.linalg.eigh(0.5 * (S + S.T))
+    mu, phi = mu[::-1].copy(), phi[:, ::-1].copy()
+    P = A / d[:, None]
+    assert mu[0] - mu[1] >= GAP                                    # a connected graph: mu = 1 is simple
+    if cloud != "threefold":                                       # an exactly repeated pair among the first five after mu = 1
+        assert (np.abs(np.diff(mu[1:6])) <= 1e-13).any(), (cloud, alpha, mu[:6])
+    for a in (K, d, P, mu, phi):
+        a.setflags(write=False)
+    return K, d, P, mu, phi
+
+
+def _wanted_clusters(mu, n_evecs):
+    """index ranges [a, b) of the descending spectrum mu: maximal runs closer than GAP, wholly inside the wanted 1 .. n_evecs and
+    GAP away from the rest"""
+    out, a = [], 1
+    while a <= n_evecs:
+        b = a + 1
+        while b < mu.size and mu[b - 1] - mu[b] < GAP:
+            b += 1
+        if b <= n_evecs + 1 and mu[a - 1] - mu[a] >= GAP and mu[a] - mu[b - 1] < GAP:
+            out.append((a, b))
+        a = b
+    return out
+
+
+@pytest.mark.parametrize("cloud,alpha,n_evecs", SYMMETRIC_CASES)
+def test_repeated_eigenvalues_of_symmetric_clouds(cloud, alpha, n_evecs):
+    """The eigenvalues as a sorted list with their multiplicity, eigenvectors by their residual (a column is defined only up to a
+    rotation inside its eigenspace), and the projector of every cluster of eigenvalues that lies inside the wanted set.  The sign
+    rule: the device takes the entry of largest magnitude before it normalises the column, and a symmetric cloud has entries that
+    differ in the last bit only, which the division can make equal; so an entry within 8 ulp of the largest must be positive."""
+    eps = CLOUDS[cloud][1]
+    K, d, P, mu, phi = _symmetric_reference(cloud, alpha)
+    N = K.shape[0]
+    dmap, evecs, evals, info = engine.diffusion_map_from_kernel(np.array(K), n_evecs=n_evecs, epsilon=eps, alpha=alpha, return_info=True)
+    what = "%s alpha=%g n_evecs=%d" % (cloud, alpha, n_evecs)
+    want = (mu[1:n_evecs + 1] - 1.0) / eps
+    print("%s: %d steps, flags %d, mu %s, reference %s" % (what, info["steps"], info["flags"], 1.0 + eps * evals, mu[1:n_evecs + 1]))
+    assert info["converged"] and not info["degenerate"] and info["flags"] == 0, (what, info)
+    assert info["steps"] <= N
+    assert dmap.shape == evecs.shape == (N, n_evecs) and evals.shape == (n_evecs,)
+    e_val = np.abs(evals - want).max()
+    res = np.abs(P @ evecs - evecs * (1.0 + eps * evals)[None, :]).max()
+    print("%s: evals %.2e (tol %.0e), residual %.2e (1e-10)" % (what, e_val, 1e-10 / eps, res))
+    assert e_val <= 1e-10 / eps, (what, evals, want)
+    assert res <= 1e-10, what
+    np.testing.assert_allclose(np.linalg.norm(evecs, axis=0), 1.0, rtol=0, atol=1e-12)
+    for c in range(n_evecs):
+        big = np.abs(evecs[:, c]) >= np.abs(evecs[:, c]).max() * (1.0 - 8 * np.finfo(np.float64).eps)
+        assert (evecs[big, c] > 0.0).any(), "%s column %d: the largest entries are negative" % (what, c)
+    np.testing.assert_allclose(dmap, evecs * np.sqrt(-1.0 / evals), rtol=1e-14, atol=0)
+    for a, b in _wanted_clusters(mu, n_evecs):
+        q, _ = np.linalg.qr(np.sqrt(d)[:, None] * evecs[:, a - 1:b - 1])
+        e_proj = np.abs(q @ q.T - phi[:, a:b] @ phi[:, a:b].T).max()
+        print("%s: cluster [%d, %d): projector %.2e (tol 1e-6)" % (what, a, b, e_proj))
+        assert e_proj <= 1e-6, what
+
+
+def test_cluster_rule_of_the_symmetric_cases():
+    mu = np.array([1.0, 0.8, 0.8, 0.7, 0.5, 0.5, 0.5, 0.1])
+    assert [_wanted_clusters(mu, k) for k in (1, 2, 3, 4, 6)] == [[], [(1, 3)], [(1, 3), (3, 4)], [(1, 3), (3, 4)], [(1, 3), (3, 4), (4, 7)]]
+
+
 def test_repeated_calls_and_both_routes_give_identical_bits():
     """Fixed-order sums, no float atomics: the same call twice, and the host-array route against the DeviceMatrix route (the
     matrix where the pair grid left it)."""
@@ -203,6 +312,18 @@ def test_disconnected_kernel_is_degenerate():
     with pytest.raises(ValueError, match="knn"):
         tl.diffusion_map(ad, knn=5)
     assert set(ad.uns) == {"EMD"}
+    # three components: mu = 1 three times, and the copy a single restart vector does not show needs a second restart
+    rng = np.random.default_rng(7)
+    X = np.r_[rng.random((30, 2)), rng.random((25, 2)) + 50.0, rng.random((20, 2)) + 100.0]
+    D = np.sqrt(((X[:, None, :] - X[None, :, :]) ** 2).sum(-1))
+    K = np.exp(-D ** 2 / 4.0)
+    K[D > 10.0] = 0.0
+    dmap, evecs, evals, info = engine.diffusion_map_from_kernel(K, n_evecs=2, epsilon=1.0, return_info=True)
+    print("three components: evals %s, %d steps, flags %d" % (evals, info["steps"], info["flags"]))
+    assert info["degenerate"] and info["flags"] & _lib.DIFFMAP_DEGENERATE
+    assert abs(evals[0]) <= 1e-10 and abs(evals[1]) <= 1e-10
+    with pytest.raises(ValueError):
+        engine.diffusion_map_from_kernel(K, n_evecs=2, epsilon=1.0)
 
 
 def test_small_basis_is_not_converged(matrices, switches):

@@ -14,7 +14,11 @@ Bounds.  A Ritz pair is accepted at a residual of 1e-12 lambda_0, so an eigenvec
 1e-12 / 1e-3 = 1e-9 in angle, and a score column by that times the largest singular direction it can leak into; f64 rounding of
 the sums (a few hundred terms, 1e-13 relative) is far inside.  Scores and PCs: per column <= 1e-8 max|reference column|.
 Eigenvalues converge with the square of the vector error: variance and variance_ratio <= 1e-10 of the leading one.  The sparse
-and the dense route are held to each other by the same bounds."""
+and the dense route are held to each other by the same bounds.
+
+The gap condition keeps repeated eigenvalues out of those inputs.  The orthogonal designs further down are the inputs where wanted
+eigenvalues repeat exactly or nearly (test_repeated_eigenvalues_are_found), held to contracts that do not need a gap: the variances
+with their multiplicity, residuals, orthonormality and the projector of every eigenvalue cluster inside the first k."""
 import functools
 
 import numpy as np
@@ -234,6 +238,135 @@ def test_small_basis_is_not_converged(switches):
         _run("wide", np.float32, "sparse")
     switches.delenv("PILOT_OT_PCA_BASIS")
     assert _run("wide", np.float32, "sparse", return_info=True)[4]["converged"]
+
+
+# ---- repeated eigenvalues: orthogonal designs ------------------------------------------------------------------------------------
+# Columns 1 .. D of the Sylvester matrix of order 64 are orthogonal, have zero sum and entries +-1, so Y = (H[:, 1:D+1] + 1) * s has
+# entries 0 or 2 s_j (exact in float32 for integer s, true zeros in the CSR), centres to H * s and has Zc^T Zc = 64 diag(s^2) exactly:
+# the variances are 64 s_j^2 / 63 with every multiplicity known.  A Krylov space grown from one vector holds one direction per
+# distinct eigenvalue, so these are the inputs a single-vector Lanczos run gets wrong unless it looks for hidden copies.
+def _sylvester64():
+    H = np.array([[1.0]])
+    for _ in range(6):
+        H = np.kron(H, np.array([[1.0, 1.0], [1.0, -1.0]]))
+    return H
+
+
+DESIGNS = {
+    "pairs": (3, 3, 2, 2, 1, 1, 1, 1, 1, 1),
+    "null": (4, 3, 0, 3, 2, 1, 1, 1, 0, 1, 1, 1, 1, 1, 0),                    # three all-zero columns among the others
+    "near-6": (3, 3 * (1 - 1e-6), 2, 1, 1, 1, 1, 1),
+    "near-9": (3, 3 * (1 - 1e-9), 2, 1, 1, 1, 1, 1),
+}
+DESIGN_CASES = ([("pairs", k, False, dt) for k in (1, 2, 3, 4) for dt in (np.float32, np.float64)]
+                + [("null", k, False, dt) for k in (2, 3) for dt in (np.float32, np.float64)]
+                + [(d, k, False, np.float64) for d in ("near-6", "near-9") for k in (2, 3)]
+                + [("pairs", k, True, dt) for k in (2, 5) for dt in (np.float32, np.float64)])
+
+
+@functools.lru_cache(maxsize=None)
+def _design(name, scale):
+    """(Y, A = Zc^T Zc of the restatement's float64 Z, Zc, every reference variance sorted, eigenvectors of A to match)"""
+    s = np.array(DESIGNS[name], dtype=np.float64)
+    D = s.size
+    H = _sylvester64()
+    Y = (H[:, 1:D + 1] + 1.0) * s[None, :]
+    if scale:
+        want = np.ones(D)                                          # every column has unit variance: A = 63 I
+    else:
+        want = np.sort(64.0 * s ** 2 / 63.0)[::-1]
+    all_var = PR.pca(Y, 1, scale, 10.0 if scale else None)[4]
+    assert all_var.shape == (D,)
+    assert (np.abs(all_var - want) <= 1e-13 * np.where(want > 0, want, want[0])).all(), (all_var, want)
+    Z = PR.standardise(Y, scale, 10.0)
+    Zc = Z - Z.mean(axis=0)
+    A = Zc.T @ Zc
+    if not scale:
+        assert np.array_equal(A, np.diag(64.0 * s ** 2)) or name.startswith("near")
+    lam, vec = np.linalg.eigh(A)
+    for a in (Y, A, Zc, want, vec):
+        a.setflags(write=False)
+    return Y, A, Zc, want, vec[:, ::-1]
+
+
+def _clusters_within(lam, k, gap):
+    """index ranges [a, b) of the descending spectrum lam: maximal runs whose members are mutually closer than gap, that lie
+    wholly inside the first k, and that are at least gap away from everything else"""
+    out, a = [], 0
+    while a < k:
+        b = a + 1
+        while b < lam.size and lam[b - 1] - lam[b] < gap:
+            b += 1
+        if b <= k and lam[a] - lam[b - 1] < gap:
+            out.append((a, b))
+        a = b
+    return out
+
+
+def _design_arg(Y, route, dtype):
+    if route == "sparse":
+        X = sp.csr_matrix(Y.astype(dtype))
+        assert X.nnz == int((Y != 0).sum())
+        return engine.DeviceCSR.upload(X)
+    return np.ascontiguousarray(Y.astype(dtype))
+
+
+@pytest.mark.parametrize("route", ["sparse", "dense"])
+@pytest.mark.parametrize("name,k,scale,dtype", DESIGN_CASES)
+def test_repeated_eigenvalues_are_found(name, k, scale, dtype, route):
+    """Every contract of test_parity on inputs whose wanted eigenvalues repeat (or nearly do), where a column of the answer is
+    defined only up to a rotation inside its eigenspace: the variances with their multiplicity, orthonormal directions that are
+    eigenvectors (residual <= 1e-10 lambda_0: the solver's 1e-12 with the factor 100 the diffusion-map tests allow for the
+    reference product), scores = Zc pcs, the sign rule, and for every cluster of eigenvalues inside the first k the projector."""
+    Y, A, Zc, want, vec = _design(name, scale)
+    n, D = Y.shape
+    if dtype == np.float32:
+        assert np.array_equal(Y.astype(np.float32).astype(np.float64), Y)
+    kw = dict(scale=True, max_value=10.0) if scale else dict(scale=False)
+    scores, pcs, variance, ratio, info = engine.pca(_design_arg(Y, route, dtype), n_comps=k, return_info=True, **kw)
+    what = "%s k=%d scale=%s %s %s" % (name, k, scale, np.dtype(dtype).name, route)
+    print("%s: %d Lanczos steps, flags %d, variance %s" % (what, info["steps"], info["flags"], variance))
+    assert info["converged"] and not info["rank_deficient"] and info["flags"] == 0, (what, info)
+    e_var = np.abs(variance - want[:k]).max() / want[0]
+    e_ratio = np.abs(ratio - want[:k] / want.sum()).max() / (want[0] / want.sum())
+    lam = variance * (n - 1)
+    resid = np.abs(A @ pcs - pcs * lam[None, :]).max() / lam[0]
+    ortho = np.abs(pcs.T @ pcs - np.eye(k)).max()
+    proj = Zc @ pcs
+    e_scores = (np.abs(scores - proj).max(axis=0) / np.abs(proj).max(axis=0)).max()
+    print("%s: variance %.2e, ratio %.2e (tol %.0e); residual %.2e (1e-10); orthonormal %.2e (1e-12); scores %.2e (tol %.0e)"
+          % (what, e_var, e_ratio, TOL_VAR, resid, ortho, e_scores, TOL_VEC))
+    assert e_var <= TOL_VAR and e_ratio <= TOL_VAR, what
+    assert ortho <= 1e-12 and resid <= 1e-10, what
+    assert e_scores <= TOL_VEC, what
+    at = np.abs(scores).argmax(axis=0)
+    assert (scores[at, np.arange(k)] > 0).all(), what              # the sign rule
+    for a, b in _clusters_within(want * (n - 1), k, MIN_GAP * want[0] * (n - 1)):
+        e_proj = np.abs(pcs[:, a:b] @ pcs[:, a:b].T - vec[:, a:b] @ vec[:, a:b].T).max()
+        print("%s: cluster [%d, %d): projector %.2e (tol %.0e)" % (what, a, b, e_proj, TOL_VEC))
+        assert e_proj <= TOL_VEC, what
+
+
+def test_cluster_rule_of_the_design_cases():
+    """the clusters the projector check sees, on the reference alone: a cut cluster is left to the residual check"""
+    gap = MIN_GAP * 9.0
+    lam = np.array([9.0, 9.0, 4.0, 4.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0])
+    assert [_clusters_within(lam, k, gap) for k in (1, 2, 3, 4)] == [[], [(0, 2)], [(0, 2)], [(0, 2), (2, 4)]]
+    assert _clusters_within(np.array([16.0, 9.0, 9.0, 4.0, 1.0]), 2, gap) == [(0, 1)]
+    assert _clusters_within(np.ones(10), 5, gap) == []
+
+
+@pytest.mark.parametrize("route", ["sparse", "dense"])
+def test_a_breakdown_without_room_to_verify_is_not_converged(route, switches):
+    """Three basis vectors hold the three distinct eigenvalues of the pairs design and nothing can look behind them: the call must
+    say so instead of returning (9, 4) for the variances (9, 9)."""
+    Y = _design("pairs", False)[0]
+    switches.setenv("PILOT_OT_PCA_BASIS", "3")
+    out = engine.pca(_design_arg(Y, route, np.float64), n_comps=2, scale=False, return_info=True)
+    print("basis 3, %s: %d steps, flags %d, variance %s" % (route, out[4]["steps"], out[4]["flags"], out[2]))
+    assert not out[4]["converged"] and out[4]["flags"] & _lib.PCA_NOT_CONVERGED
+    with pytest.raises(ValueError):
+        engine.pca(_design_arg(Y, route, np.float64), n_comps=2, scale=False)
 
 
 def test_non_finite_values_on_the_device_are_refused():

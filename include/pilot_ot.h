@@ -607,6 +607,25 @@ int pilot_ot_knn_smooth(const double *distances, long long n, int k, double *wei
 int pilot_ot_louvain(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
                      int max_levels, int *labels, double *modularity, int *info /* 3 */);
 
+/* ---- silhouette of labelled rows (K18): sklearn.metrics.silhouette_samples of the n rows of X (n x D row-major, X_is_device /
+ * dtype / ld as in pilot_ot_knn_rows) under the labels codes[i] in 0 .. n_clusters - 1 -- the score pilotpy's select_best_sil
+ * (plot/ploting.py:384-458) takes per resolution, at the cell level.  Neither the n x n distance matrix nor an n x n_clusters table
+ * is formed.  The distances are pilot_ot_knn_rows's (metric 0 / 1 as there: direct sums of squared differences in the element
+ * type; cosine from the rows normalised and rounded to the element type).  a_i = the mean distance from i to the other members of
+ * its cluster (i left out by index, so copies of it count at distance 0), b_i = the smallest mean distance from i to the members
+ * of another cluster, samples[i] = (b_i - a_i) / max(a_i, b_i); 0 when i's cluster has one member or max(a_i, b_i) = 0.  The rows
+ * are ordered by (code, row) once; every per-cluster sum is float64, one add per member in ascending row order, no atomics: the
+ * result does not depend on the launch geometry and the same call returns the same bits.  Every sample is within
+ * 4 ((D + 6) u + n 2^-53) of the value the exact distances between the stored values give, u = 2^-24 / 2^-53.
+ * samples: n doubles (host); *score: their mean, summed in ascending row order on the host.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, D < 1, ld < D, dtype, metric, n_clusters outside [2, n - 1], a code
+ * outside [0, n_clusters), a code without rows; after the flag pass: a non-finite value, or under cosine an all-zero row (the
+ * message names the first such row).  PILOT_OT_ENOTSUP: n > INT_MAX. */
+int pilot_ot_silhouette_points(const void *X, int X_is_device, int dtype, long long n, int D, long long ld, int metric, const int *codes,
+                             int n_clusters, double *samples, double *score);
+/* the geometry of that kernel for D columns of `dtype`: query rows per block (one per lane) and corpus rows per staged LDS tile */
+int pilot_ot_silhouette_points_geometry(int D, int dtype, int *queries_per_block, int *tile_rows);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

@@ -50,6 +50,7 @@ SYMBOLS = [
     "pilot_ot_csr_column_nnz", "pilot_ot_csr_group_moments", "pilot_ot_csr_densify",
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
     "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain",
+    "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -184,6 +185,8 @@ def load() -> ctypes.CDLL:
                                     ctypes.c_longlong, ip, dp]
     L.pilot_ot_knn_smooth.argtypes = [dp, ctypes.c_longlong, c_int, dp, dp, dp]
     L.pilot_ot_louvain.argtypes = [ctypes.c_longlong, llp, ip, dp, c_dbl, c_dbl, c_int, ip, dp, ip]
+    L.pilot_ot_silhouette_points.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, ip, c_int, dp, dp]
+    L.pilot_ot_silhouette_points_geometry.argtypes = [c_int, c_int, ip, ip]
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

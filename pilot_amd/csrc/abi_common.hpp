@@ -39,6 +39,7 @@ enum WsSlot {
     WS_KNN_X, WS_KNN_UNIT, WS_KNN_FLAGS, WS_KNN_BEST_D, WS_KNN_BEST_I, WS_KNN_OUT_D, WS_KNN_OUT_I, WS_KNN_SM_IN, WS_KNN_SM_OUT,   // pilot_ot_knn.hip
     WS_LV_VAL0, WS_LV_VAL1, WS_LV_DEG0, WS_LV_DEG1, WS_LV_IDX0, WS_LV_IDX1, WS_LV_TOT, WS_LV_SUMS, WS_LV_INT, WS_LV_FLAG, WS_LV_ECOMM,   // pilot_ot_louvain.hip
     WS_LV_NKEYS, WS_LV_EKEYS, WS_LV_CNT,
+    WS_SIL_X, WS_SIL_UNIT, WS_SIL_FLAGS, WS_SIL_SORTED, WS_SIL_ORDER, WS_SIL_OFFSETS, WS_SIL_OUT,   // pilot_ot_silhouette_points.hip
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

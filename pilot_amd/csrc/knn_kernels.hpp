@@ -1,10 +1,11 @@
-// K16: the exact k-nearest-neighbour graph of the rows of an n x D matrix (the cells of an embedding) and the per-row part of UMAP's
-// fuzzy simplicial set.  The n x n distance matrix is never formed.
+// K16: the exact k-nearest-neighbour graph of the rows of an n x D matrix (the cells of an embedding); the per-row part of UMAP's
+// fuzzy simplicial set is in knn_smooth_kernel.hpp.  The n x n distance matrix is never formed.
 //
 // knn_rows_kernel: one query row per lane, corpus rows staged through LDS in tiles and read back as wave-wide broadcasts.  A squared
 // distance is the direct sum over d of (x_d - y_d)^2 in the element type T, d ascending, one fused multiply-add per term; the corpus is
 // scanned in ascending row order and a candidate enters a query's list only if it is strictly closer than the list's k-th, behind
 // every entry at the same distance, so a list is ordered by (distance, index).  No atomics: the same call gives the same bits.
+// knn_sweep is that walk over the corpus with the per-sub-tile step left to the caller; K18 (silhouette_kernels.hpp) runs on it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,33 +64,21 @@ template <typename T> __device__ __forceinline__ void knn_insert(T *bd, int *bi,
     if (cnt == k) kth = bd[(size_t)(k - 1) * m];
 }
 
-// Queries q0 + blockIdx.x * KNN_THREADS + lane of the m query rows row_begin .. row_begin + m against all n rows of X (leading
-// dimension ld).  best_d / best_i: k x m scratch lists (lane-contiguous).  out_i / out_d: m x k row-major; out_d = sqrt(sum)
-// (metric 0) or sum / 2 (metric 1: X holds unit rows), formed in f64.  REGQ: D <= KNN_REGQ_D and the query stays in registers;
-// otherwise any D, and a query chunk is read again from X for every sub-tile.
-template <typename T, bool REGQ>
-__global__ __launch_bounds__(KNN_THREADS, KNN_WAVES) void knn_rows_kernel(const T *__restrict__ X, long long ld, int n, int D, int k, int metric,
-                                                               long long row_begin, int m, int q0, T *__restrict__ best_d,
-                                                               int *__restrict__ best_i, int *__restrict__ out_i,
-                                                               double *__restrict__ out_d) {
-    __shared__ __attribute__((aligned(16))) T ys[KnnTile<T>::CAP];
+// One query (the row xq of D dims) against all n rows of X (leading dimension ld), by every lane of the block at once: the corpus
+// goes through the LDS tile ys (KnnTile<T>::CAP elements) in ascending row order and each(j0, acc) is called for every sub-tile
+// with acc[p] = the squared distance to corpus row j0 + p (rows past n: to a row of zeros).  Every lane is at the same corpus row
+// at the same time.  REGQ: D <= KNN_REGQ_D and the query stays in registers; otherwise any D, and a query chunk is read again
+// from xq for every sub-tile.
+template <typename T, bool REGQ, typename F>
+__device__ __forceinline__ void knn_sweep(const T *__restrict__ X, long long ld, int n, int D, const T *xq, T *ys, F &&each) {
     const KnnTile<T> tile(D);
     const int dl_max = tile.dl, ns = tile.ns, tp = ns * KNN_PB;
-    const long long qi = (long long)q0 + (long long)blockIdx.x * KNN_THREADS + threadIdx.x;
-    const bool active = qi < m;
-    const long long row = row_begin + (active ? qi : 0);       // an idle lane works on a valid row and keeps nothing
-    const T *xq = X + row * ld;
-    T *bd = best_d + (active ? qi : 0);
-    int *bi = best_i + (active ? qi : 0);
-
     T q[REGQ ? KNN_REGQ_D : KNN_DC];
     if constexpr (REGQ) {
 #pragma unroll
         for (int d = 0; d < KNN_REGQ_D; ++d) q[d] = d < D ? xq[d] : T(0);
     }
     T acc[KNN_PB];
-    T kth = T(0);
-    int cnt = 0;
 
     for (long long t0 = 0; t0 < n; t0 += tp) {
         for (int dg = 0; dg < tile.Dpad; dg += dl_max) {
@@ -126,21 +115,47 @@ __global__ __launch_bounds__(KNN_THREADS, KNN_WAVES) void knn_rows_kernel(const 
                         knn_chunk(q, yt + ch * KNN_DC * KNN_PB, acc);
                     }
                 }
-                if (!last) continue;
-#pragma unroll
-                for (int p = 0; p < KNN_PB; ++p) {
-                    const long long j = j0 + p;
-                    const T d = acc[p];
-                    if (active && j < n && j != row && (cnt < k || d < kth)) knn_insert(bd, bi, (size_t)m, k, cnt, kth, d, (int)j);
-                }
+                if (last) each(j0, acc);
             }
         }
     }
+}
+
+// the distance of a finished sum of squares, formed in f64: its square root (metric 0) or half of it (metric 1: between unit rows)
+template <typename T> __device__ __forceinline__ double knn_distance(T sum, int metric) {
+    const double s = (double)sum;
+    return metric == 0 ? sqrt(s) : 0.5 * s;
+}
+
+// Queries q0 + blockIdx.x * KNN_THREADS + lane of the m query rows row_begin .. row_begin + m against all n rows of X (leading
+// dimension ld).  best_d / best_i: k x m scratch lists (lane-contiguous).  out_i / out_d: m x k row-major; out_d = knn_distance of
+// the sum.  REGQ: as in knn_sweep.
+template <typename T, bool REGQ>
+__global__ __launch_bounds__(KNN_THREADS, KNN_WAVES) void knn_rows_kernel(const T *__restrict__ X, long long ld, int n, int D, int k, int metric,
+                                                               long long row_begin, int m, int q0, T *__restrict__ best_d,
+                                                               int *__restrict__ best_i, int *__restrict__ out_i,
+                                                               double *__restrict__ out_d) {
+    __shared__ __attribute__((aligned(16))) T ys[KnnTile<T>::CAP];
+    const long long qi = (long long)q0 + (long long)blockIdx.x * KNN_THREADS + threadIdx.x;
+    const bool active = qi < m;
+    const long long row = row_begin + (active ? qi : 0);       // an idle lane works on a valid row and keeps nothing
+    T *bd = best_d + (active ? qi : 0);
+    int *bi = best_i + (active ? qi : 0);
+    T kth = T(0);
+    int cnt = 0;
+
+    knn_sweep<T, REGQ>(X, ld, n, D, X + row * ld, ys, [&](long long j0, const T *acc) {
+#pragma unroll
+        for (int p = 0; p < KNN_PB; ++p) {
+            const long long j = j0 + p;
+            const T d = acc[p];
+            if (active && j < n && j != row && (cnt < k || d < kth)) knn_insert(bd, bi, (size_t)m, k, cnt, kth, d, (int)j);
+        }
+    });
     if (!active) return;
     for (int c = 0; c < k; ++c) {
-        const double s = (double)bd[(size_t)c * m];
         out_i[(size_t)qi * k + c] = bi[(size_t)c * m];
-        out_d[(size_t)qi * k + c] = metric == 0 ? sqrt(s) : 0.5 * s;
+        out_d[(size_t)qi * k + c] = knn_distance(bd[(size_t)c * m], metric);
     }
 }
 
@@ -179,52 +194,6 @@ template <typename T> __global__ void knn_normalize_kernel(const T *__restrict__
     const T *x = X + i * ld;
     const double norm = sqrt(knn_row_ssq(x, D, &finite));
     for (int d = 0; d < D; ++d) U[i * D + d] = (T)((double)x[d] / norm);
-}
-
-// ---- the per-row part of UMAP's fuzzy simplicial set (tests/neighbors_restatement.py states the same rule) ---------------------
-constexpr int KNN_SMOOTH_STEPS = 64;
-constexpr double KNN_SMOOTH_TOL = 1e-5;
-constexpr double KNN_SMOOTH_FLOOR = 1e-3;
-
-// dist: n x k distances to the k = n_neighbors - 1 other cells, ascending.  rho = the smallest non-zero one (0: none).  sigma: the
-// bisection of sum_j exp(-max(0, d_j - rho) / sigma) = log2(k + 1), floored at KNN_SMOOTH_FLOOR x the row's mean distance (rho > 0)
-// or x global_mean (rho = 0).  weights = 1 where d_j - rho <= 0 or sigma = 0, else exp(-(d_j - rho) / sigma).  One row per thread.
-__global__ void knn_smooth_kernel(const double *__restrict__ dist, long long n, int k, double global_mean, double *__restrict__ weights,
-                                  double *__restrict__ sigma, double *__restrict__ rho) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double *d = dist + i * k;
-    const double target = log2((double)(k + 1));
-    double r = 0.0, mean = 0.0;
-    for (int c = 0; c < k; ++c) {
-        mean += d[c];
-        if (d[c] > 0.0 && (r == 0.0 || d[c] < r)) r = d[c];
-    }
-    mean /= (double)k;
-    double lo = 0.0, hi = INFINITY, mid = 1.0;
-    for (int it = 0; it < KNN_SMOOTH_STEPS; ++it) {
-        double psum = 0.0;
-        for (int c = 0; c < k; ++c) {
-            const double g = d[c] - r;
-            psum += g > 0.0 ? exp(-(g / mid)) : 1.0;
-        }
-        if (fabs(psum - target) < KNN_SMOOTH_TOL) break;
-        if (psum > target) {
-            hi = mid;
-            mid = (lo + hi) / 2.0;
-        } else {
-            lo = mid;
-            mid = isinf(hi) ? mid * 2.0 : (lo + hi) / 2.0;
-        }
-    }
-    const double floor = KNN_SMOOTH_FLOOR * (r > 0.0 ? mean : global_mean);
-    if (mid < floor) mid = floor;
-    for (int c = 0; c < k; ++c) {
-        const double g = d[c] - r;
-        weights[i * k + c] = (g <= 0.0 || mid == 0.0) ? 1.0 : exp(-(g / mid));
-    }
-    sigma[i] = mid;
-    rho[i] = r;
 }
 
 }  // namespace pilot

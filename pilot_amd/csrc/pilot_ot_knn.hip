@@ -1,5 +1,5 @@
-// C ABI of the cell neighbour graph (include/pilot_ot.h, section "cell neighbours"; kernels: knn_kernels.hpp).  The matrix is a dense
-// row-major one on the host or in HBM; the results are host arrays, so the calls synchronise.
+// C ABI of the cell neighbour graph (include/pilot_ot.h, section "cell neighbours"; kernels: knn_kernels.hpp, knn_smooth_kernel.hpp).
+// The matrix is a dense row-major one on the host or in HBM; the results are host arrays, so the calls synchronise.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -7,7 +7,8 @@
 #include <cmath>
 
 #include "abi_common.hpp"
-#include "knn_kernels.hpp"
+#include "knn_host.hpp"
+#include "knn_smooth_kernel.hpp"
 
 namespace {
 
@@ -15,28 +16,7 @@ template <typename T>
 int knn_rows(const void *x, long long ld, int n, int D, int metric, int k, long long row_begin, int m, int *indices, double *distances) {
     const T *X = static_cast<const T *>(x);
     hipStream_t s = nullptr;
-    const unsigned row_grid = (unsigned)((n + 255) / 256);
-
-    // finiteness and, under cosine, zero rows: a flag and the first offending row
-    int *flags;
-    const int none[2] = {INT_MAX, INT_MAX};
-    int found[2];
-    HIP_TRY(pilot::ws(pilot::WS_KNN_FLAGS, 2, &flags));
-    HIP_TRY(hipMemcpy(flags, none, sizeof(none), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pilot::knn_check_kernel<T>, dim3(row_grid), dim3(256), 0, s, X, ld, n, D, metric, flags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(found, flags, sizeof(found), hipMemcpyDeviceToHost));
-    if (found[0] != INT_MAX)
-        return fail(PILOT_OT_EINVAL, "row %d holds a non-finite value%s", found[0], metric == 1 ? " (or its sum of squares overflows)" : "");
-    if (found[1] != INT_MAX) return fail(PILOT_OT_EINVAL, "row %d is all zero: its cosine distances are undefined", found[1]);
-
-    if (metric == 1) {                                         // unit rows, packed
-        T *U;
-        HIP_TRY(pilot::ws(pilot::WS_KNN_UNIT, (size_t)n * D, &U));
-        hipLaunchKernelGGL(pilot::knn_normalize_kernel<T>, dim3(row_grid), dim3(256), 0, s, X, ld, n, D, U);
-        X = U;
-        ld = D;
-    }
+    if (int rc = pilot::knn_checked_rows(&X, &ld, n, D, metric, pilot::WS_KNN_FLAGS, pilot::WS_KNN_UNIT)) return rc;
     T *best_d;
     int *best_i, *out_i;
     double *out_d;

@@ -1267,12 +1267,17 @@ def knn_connectivities(indices, distances, n_neighbors):
 
 
 # ---- Louvain communities (K17; sknetwork's Louvain of pilotpy's extract_annot_expression / reclustering_data, by a synchronous rule) --
-def _louvain_args(graph, resolution, tol, max_levels):
-    """(indptr int64, indices int32, data float64, n) of the square graph, every argument judged: nothing touches the library"""
-    import scipy.sparse as sp
+def check_resolution(resolution):
+    """ValueError unless ``resolution`` is what :func:`louvain` takes: a finite number, not negative"""
     if isinstance(resolution, bool) or not isinstance(resolution, (int, float, np.integer, np.floating)) \
             or not np.isfinite(resolution) or resolution < 0:
         raise ValueError("resolution=%r: a finite number, not negative" % (resolution,))
+
+
+def _louvain_args(graph, resolution, tol, max_levels):
+    """(indptr int64, indices int32, data float64, n) of the square graph, every argument judged: nothing touches the library"""
+    import scipy.sparse as sp
+    check_resolution(resolution)
     if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0:
         raise ValueError("tol=%r: a number, not negative" % (tol,))
     if isinstance(max_levels, bool) or not isinstance(max_levels, (int, np.integer)) or max_levels < 1:
@@ -1314,6 +1319,46 @@ def louvain(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
     if return_info:
         return labels, {"modularity": q.value, "levels": int(info[0]), "sweeps": int(info[1]), "communities": int(info[2])}
     return labels
+
+
+# ---- silhouette of labelled points (K18; the score pilotpy's select_best_sil takes per resolution, at the cell level) -------------
+def silhouette_geometry(D, dtype=np.float32):
+    """``(queries per block, corpus rows per staged tile)`` of :func:`silhouette_samples` for ``D`` columns of ``dtype``."""
+    if np.dtype(dtype) not in (np.float32, np.float64):
+        raise ValueError("dtype=%s: float32 or float64" % np.dtype(dtype).name)
+    block, tile = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.load().pilot_ot_silhouette_points_geometry(int(D), _lib.dtype_code(np.dtype(dtype)), ctypes.byref(block),
+                                                               ctypes.byref(tile)))
+    return block.value, tile.value
+
+
+def silhouette_samples(X, labels, metric="euclidean", return_score=False):
+    """K18: ``sklearn.metrics.silhouette_samples(X, labels, metric=metric)`` of the C rows of the C x D matrix ``X`` on the device
+    (include/pilot_ot.h, "silhouette of labelled rows"), without the C x C distance matrix and without a C x k table, so it works
+    at the cell level where :func:`silhouette_of_rows` cannot.  ``X`` and ``metric`` are :func:`knn`'s, and so are the distances:
+    direct sums of squared differences in X's dtype, never |x|^2 + |y|^2 - 2 x.y.  ``labels``: one per row, of any hashable type.
+    With a_i the mean distance from i to the other members of its cluster (i is left out by index, so copies of it count at
+    distance 0) and b_i the smallest mean distance to the members of another cluster, s_i = (b_i - a_i) / max(a_i, b_i), and
+    0 where i's cluster has one member or max(a_i, b_i) = 0.  Returns the float64 array s, or ``(s, mean of s)`` with
+    ``return_score``.  Every s_i is within 4 ((D + 6) u + C 2^-53) of the value the exact distances give (u = 2^-24 / 2^-53);
+    sums are float64 in a fixed order, so a repeated call and the host and device routes return the same bits.  ValueError
+    before any device work: a wrong label length, an unknown metric, no columns, a number of labels outside 2 .. C - 1; from the
+    device's first pass: a non-finite value, or under cosine an all-zero row (the message names the row)."""
+    Y = _dense_arg(X, "X", mode="strided", axes=" (rows x dims)")
+    if metric not in _lib.ROW_METRICS:
+        raise ValueError("metric=%r: %s" % (metric, " or ".join(_lib.ROW_METRICS)))
+    n, D = Y.rows, Y.cols
+    if D < 1:
+        raise ValueError("X has no columns")
+    codes, n_clusters = _label_codes(labels, n)
+    if not 2 <= n_clusters <= n - 1:
+        raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % n_clusters)
+    if n > np.iinfo(np.int32).max:
+        raise NotImplementedError("%d rows need more than 32-bit row indices" % n)
+    samples, score = np.empty(n, dtype=np.float64), ctypes.c_double(0.0)
+    _lib.check(_lib.load().pilot_ot_silhouette_points(Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), n, D, Y.ld, _lib.ROW_METRICS[metric],
+                                                      _lib.iptr(codes), n_clusters, _lib.dptr(samples), ctypes.byref(score)))
+    return (samples, score.value) if return_score else samples
 
 
 def fitted_curves(params, model, times, noise=None, device=False):

@@ -38,6 +38,9 @@ neighbors                                      Trajectory.py:217-220, 1045-1060 
 louvain, reclustering_data                     Trajectory.py:217-220, 1000-1062 (sknetwork's Louvain(resolution) of the neighbour
                                                graph by a synchronous, deterministic rule; no Leiden, so no tl.Clustering and
                                                no return_sil_ari)
+select_best_sil, clustering_emd                plot/ploting.py:384-458, 287-354 (the silhouette sweep over resolutions and the
+                                               samples' Predicted_Labels, without plots or files; Louvain instead of Leiden)
+select_best_resolution, silhouette             the same sweep over cells, on the matrix-free silhouette (not in the reference)
 =============================================  ==========================================
 """
 from __future__ import annotations
@@ -875,6 +878,26 @@ def extract_annot_expression(adata, columns=["cell_type_original", "patient_regi
     return data, annot
 
 
+def _metric_checked(metric):
+    if metric not in ("euclidean", "cosine"):
+        raise ValueError("metric=%r: euclidean or cosine" % (metric,))
+    return metric
+
+
+def _representation(adata, use_rep, n_pcs):
+    """``adata.obsm[use_rep]``, or the strided view of its first ``n_pcs`` columns"""
+    if use_rep not in adata.obsm:
+        raise ValueError("adata.obsm has no %r (tl.pca makes 'X_pca')" % (use_rep,))
+    X = adata.obsm[use_rep]
+    if len(X.shape) != 2:
+        raise ValueError("adata.obsm[%r] must be 2-D, got %s" % (use_rep, X.shape))
+    if n_pcs is not None:
+        if isinstance(n_pcs, bool) or not isinstance(n_pcs, (int, np.integer)) or not 1 <= n_pcs <= X.shape[1]:
+            raise ValueError("n_pcs=%r outside [1, %d], the columns of adata.obsm[%r]" % (n_pcs, X.shape[1], use_rep))
+        X = np.asarray(X)[:, :int(n_pcs)]
+    return X
+
+
 def neighbors(adata, n_neighbors=15, n_pcs=None, use_rep="X_pca", metric="euclidean", key_added=None):
     """The cell neighbour graph scanpy's ``pp.neighbors`` gives (Trajectory.py:217-220, 1045-1060), made on the device from
     ``adata.obsm[use_rep]`` (its first ``n_pcs`` columns, read as a strided view without a copy): the exact ``n_neighbors - 1``
@@ -895,17 +918,8 @@ def neighbors(adata, n_neighbors=15, n_pcs=None, use_rep="X_pca", metric="euclid
         raise ValueError("n_neighbors=%r: an integer of at least 2 (it counts the cell itself)" % (n_neighbors,))
     if n_neighbors - 1 > engine.KNN_MAX_K:
         raise ValueError("n_neighbors=%d: at most %d" % (n_neighbors, engine.KNN_MAX_K + 1))
-    if metric not in ("euclidean", "cosine"):
-        raise ValueError("metric=%r: euclidean or cosine" % (metric,))
-    if use_rep not in adata.obsm:
-        raise ValueError("adata.obsm has no %r (tl.pca makes 'X_pca')" % (use_rep,))
-    X = adata.obsm[use_rep]
-    if len(X.shape) != 2:
-        raise ValueError("adata.obsm[%r] must be 2-D, got %s" % (use_rep, X.shape))
-    if n_pcs is not None:
-        if isinstance(n_pcs, bool) or not isinstance(n_pcs, (int, np.integer)) or not 1 <= n_pcs <= X.shape[1]:
-            raise ValueError("n_pcs=%r outside [1, %d], the columns of adata.obsm[%r]" % (n_pcs, X.shape[1], use_rep))
-        X = np.asarray(X)[:, :int(n_pcs)]
+    _metric_checked(metric)
+    X = _representation(adata, use_rep, n_pcs)
     n = X.shape[0]
     if n < n_neighbors:
         raise ValueError("n_neighbors=%d needs at least as many cells, got %d" % (n_neighbors, n))
@@ -977,7 +991,7 @@ def reclustering_data(adata, resu=0.01, normalization=False, target_sum=1e6, n_n
         raise ValueError("method_=%r: only 'umap' (scanpy's default connectivities) is offered" % (method_,))
     if mode not in ("connectivities", "distances"):
         raise ValueError("mode=%r: connectivities or distances" % (mode,))
-    engine._louvain_args(np.zeros((1, 1)), resu, 0.0, 1)
+    engine.check_resolution(resu)
     if origine_scr_rna:
         n_vars = adata.X.shape[1]
         if dimension_rect or n_vars > 50:
@@ -1005,6 +1019,160 @@ def reclustering_data(adata, resu=0.01, normalization=False, target_sum=1e6, n_n
         neighbors(cells, use_rep="X")
         graph = cells.obsp[mode]
     return engine.louvain(graph, resolution=resu)
+
+
+# ---- choosing the resolution: silhouette sweeps (plot/ploting.py:287-458: select_best_sil, clustering_emd) ----------------------
+_SWEEP_COLUMNS = ["resolution", "silhouette", "n_clusters", "modularity"]
+
+
+def _resolution_list(resolutions, start, step, end):
+    """a non-empty ``resolutions`` as floats, else the reference's list (ploting.py:408): 0.2, 0.3 .. 2.0 by default"""
+    out = list(resolutions) if resolutions is not None and len(resolutions) else \
+        [start + step * i for i in range(int((end - start) / step) + 1)]
+    for res in out:
+        engine.check_resolution(res)
+    return [float(res) for res in out]
+
+
+def _best_resolution(resolutions, scores, start):
+    """the reference's rule (ploting.py:410-434): ``start`` unless a silhouette is > 0, then the first resolution, in list order,
+    whose silhouette is strictly greater than every earlier one's; NaN never wins"""
+    best_res, best_sil = start, 0
+    for res, sil in zip(resolutions, scores):
+        if float(sil) > best_sil:
+            best_sil, best_res = sil, res
+    return best_res
+
+
+def _sweep(adata, resolutions, start, graph, score):
+    """one Louvain run and one ``score(labels)`` per resolution; a labelling with one cluster, or one cluster per point, scores NaN"""
+    n, rows = graph.shape[0], []
+    for res in resolutions:
+        labels, info = engine.louvain(graph, resolution=res, return_info=True)
+        k = info["communities"]
+        rows.append((res, score(labels) if 2 <= k <= n - 1 else np.nan, k, info["modularity"]))
+    frame = pd.DataFrame(rows, columns=_SWEEP_COLUMNS)
+    adata.uns["best_res"] = _best_resolution(frame["resolution"], frame["silhouette"], start)
+    return frame
+
+
+def silhouette(adata, labels_key="louvain", use_rep="X_pca", n_pcs=None, metric="euclidean", key_added=None):
+    """The silhouette of every cell under the labels ``adata.obs[labels_key]`` (what :func:`louvain` wrote), from the cells' rows of
+    ``adata.obsm[use_rep]`` (its first ``n_pcs`` columns) on the device: ``engine.silhouette_samples`` (K18), which forms neither
+    the cells x cells distance matrix nor a cells x clusters table.  Writes ``adata.obs[key_added or labels_key + '_silhouette']``
+    (float64) and returns the mean, ``sklearn.metrics.silhouette_score``'s value.  ValueError before any device work: a missing
+    representation or label column, an unknown metric, ``n_pcs`` outside the representation, fewer than 2 labels or one per cell."""
+    _metric_checked(metric)
+    X = _representation(adata, use_rep, n_pcs)
+    if labels_key not in adata.obs:
+        raise ValueError("adata.obs has no %r (tl.louvain writes 'louvain')" % (labels_key,))
+    samples, score = engine.silhouette_samples(X, np.asarray(adata.obs[labels_key]), metric=metric, return_score=True)
+    adata.obs[labels_key + "_silhouette" if key_added is None else key_added] = samples
+    return score
+
+
+def select_best_resolution(adata, resolutions=None, start=0.2, step=0.1, end=2, mode="connectivities", neighbors_key=None,
+                           use_rep="X_pca", n_pcs=None, metric="euclidean"):
+    """:func:`select_best_sil` at the cell level: for every resolution, ``engine.louvain`` of the graph :func:`neighbors` left in
+    ``adata.obsp`` (``mode``, ``neighbors_key`` as in :func:`louvain`) and the mean of ``engine.silhouette_samples`` (K18) of
+    the cells' rows of ``adata.obsm[use_rep]`` (its first ``n_pcs`` columns) under those labels.  The resolution list and the
+    best-resolution rule are :func:`select_best_sil`'s.  Returns a frame with the columns ``resolution, silhouette, n_clusters,
+    modularity`` and writes ``adata.uns['best_res']``; it writes no labels: call ``tl.louvain(adata, resolution=best_res)`` next.
+    Every resolution costs one Louvain run plus one all-pairs pass over the cells (19 of each by default): the distances are
+    recomputed, not kept, since cells x cells of them do not fit.  A labelling with one cluster, or one cluster per cell, gets NaN
+    and is never best.  ValueError before any device work: a missing graph or representation, an unknown metric."""
+    _metric_checked(metric)
+    resolutions = _resolution_list(resolutions, start, step, end)
+    graph = _neighbor_graph(adata, mode, neighbors_key)
+    X = _representation(adata, use_rep, n_pcs)
+    if X.shape[0] != graph.shape[0]:
+        raise ValueError("the graph has %d cells, adata.obsm[%r] %d" % (graph.shape[0], use_rep, X.shape[0]))
+    return _sweep(adata, resolutions, start, graph,
+                  lambda labels: engine.silhouette_samples(X, labels, metric=metric, return_score=True)[1])
+
+
+_EMD_NEIGHBORS = 15          # scanpy's pp.neighbors default, which the reference takes for the samples
+
+
+def _emd_points(adata, metric):
+    """``uns['EMD']`` as the reference's ``sc.AnnData(EMD)`` has it: the samples are the points, the rows their coordinates"""
+    _metric_checked(metric)
+    if "EMD" not in adata.uns:
+        raise ValueError("adata.uns has no 'EMD': run tl.wasserstein_distance first")
+    E = np.ascontiguousarray(adata.uns["EMD"], dtype=np.float64)
+    if E.ndim != 2 or E.shape[0] != E.shape[1]:
+        raise ValueError("uns['EMD'] must be samples x samples, got %s" % (E.shape,))
+    if E.shape[0] < _EMD_NEIGHBORS:
+        raise ValueError("%d samples: the neighbour graph of scanpy's defaults needs n_neighbors = %d of them" % (E.shape[0], _EMD_NEIGHBORS))
+    return E
+
+
+def _emd_graph(E, metric):
+    indices, distances = engine.knn(E, _EMD_NEIGHBORS - 1, metric=metric)
+    return engine.knn_connectivities(indices, distances, _EMD_NEIGHBORS)
+
+
+def select_best_sil(adata, resolutions=None, metric="cosine", start=0.2, step=0.1, end=2):
+    """The numerical core of the reference's ``pl.select_best_sil`` (plot/ploting.py:384-458; no plots, no files): the silhouette
+    of the samples' clustering at every resolution, and the best resolution in ``adata.uns['best_res']``.  Returns a frame with
+    the columns ``resolution, silhouette, n_clusters, modularity``.
+
+    The rule, shared with :func:`clustering_emd`.  Points: the rows of ``uns['EMD']``, unnormalised, as ``sc.AnnData(EMD)`` has
+    them.  Graph: ``engine.knn(E, 14, metric)`` then ``engine.knn_connectivities(.., 15)``, scanpy's defaults ``n_neighbors=15``,
+    ``method='umap'``; fewer than 15 samples raise ValueError.  Clustering: ``engine.louvain(graph, resolution)``.  Silhouette:
+    ``engine.silhouette_of_rows(E, labels, metric)`` -- on ``EMD`` here, on ``EMD / EMD.max()`` in :func:`clustering_emd`, as
+    the reference does; the samples x samples matrix path is the right one at this size.  Resolution list: the reference's
+    ``[start + step * i for i in range(int((end - start) / step) + 1)]``, 19 values 0.2 .. 2.0 by default.  Best resolution: the
+    reference's rule, ``best_sil = 0``, ``best_res = start``, replaced only by a strictly greater silhouette, in list order.
+
+    Deviations from pilotpy: Louvain by the synchronous rule of DESIGN.md K17 where the reference runs Leiden (the labels are
+    unpinned, as everywhere in K17); the rows themselves are used (scanpy silently reduces them to 50 principal components when
+    there are more than 50 samples); a non-empty ``resolutions`` is honoured (the reference overwrites its argument); a labelling
+    with one cluster, or one cluster per sample, gets silhouette NaN and can never be best (the reference crashes inside
+    scikit-learn).  ValueError before any device work: no ``uns['EMD']``, an unknown metric, fewer than 15 samples."""
+    E = _emd_points(adata, metric)
+    resolutions = _resolution_list(resolutions, start, step, end)
+    return _sweep(adata, resolutions, start, _emd_graph(E, metric),
+                  lambda labels: engine.silhouette_of_rows(E, labels, metric=metric))
+
+
+def clustering_emd(adata, res=0.3, metric="cosine"):
+    """The numerical core of the reference's ``pl.clustering_emd`` (plot/ploting.py:287-354; no heat map): the sub-groups of the
+    samples at resolution ``res``.  Returns the reference's ``proportion_df``: one row per sample (``uns['proportions']`` order),
+    the columns ``uns['annot'].cell_type.unique()``, then ``Predicted_Labels`` (the strings "0" .. "k-1", 0 the largest group, as
+    :func:`louvain` names them) and ``sampleID`` -- what :func:`compute_diff_expressions`,
+    :func:`cell_type_diff_two_sub_patient_groups` and :func:`pseudobulk_inputs` take.  Writes ``adata.uns['clustering_emd'] =
+    {'params': {res, metric}, 'silhouette', 'modularity'}``, the silhouette being the one the reference computes here and drops.
+
+    The rule, shared with :func:`select_best_sil`.  Points: the rows of ``uns['EMD']``, unnormalised, as ``sc.AnnData(EMD)`` has
+    them.  Graph: ``engine.knn(E, 14, metric)`` then ``engine.knn_connectivities(.., 15)``, scanpy's defaults ``n_neighbors=15``,
+    ``method='umap'``; fewer than 15 samples raise ValueError.  Clustering: ``engine.louvain(graph, res)``.  Silhouette:
+    ``engine.silhouette_of_rows`` with ``metric`` on ``EMD / EMD.max()`` here (on ``EMD`` in :func:`select_best_sil`), as the
+    reference does.  Resolution list and best resolution: see :func:`select_best_sil`; pass ``res=adata.uns['best_res']``.
+
+    Deviations from pilotpy: those of :func:`select_best_sil` (Louvain by K17's synchronous rule instead of Leiden, labels
+    unpinned; the rows themselves instead of 50 principal components; NaN for a labelling of one cluster or of one per sample).
+    ValueError before any device work: no ``uns['EMD']`` / ``['proportions']`` / ``['annot']``, an unknown metric, fewer than 15
+    samples, proportions that do not match EMD or the cell types."""
+    E = _emd_points(adata, metric)
+    for key in ("proportions", "annot"):
+        if key not in adata.uns:
+            raise ValueError("adata.uns has no %r: run tl.wasserstein_distance first" % key)
+    engine.check_resolution(res)
+    proportions = adata.uns["proportions"]
+    cell_types = adata.uns["annot"]["cell_type"].unique()
+    proportion_df = pd.DataFrame(proportions).T
+    if proportion_df.shape != (E.shape[0], len(cell_types)):
+        raise ValueError("uns['proportions'] is %d samples x %d cell types, uns['EMD'] has %d samples and uns['annot'] %d cell types"
+                         % (proportion_df.shape + (E.shape[0], len(cell_types))))
+    labels, info = engine.louvain(_emd_graph(E, metric), resolution=res, return_info=True)
+    k = info["communities"]
+    sil = engine.silhouette_of_rows(E, labels, metric=metric, normalize_by_max=True) if 2 <= k <= E.shape[0] - 1 else np.nan
+    adata.uns["clustering_emd"] = {"params": {"res": res, "metric": metric}, "silhouette": sil, "modularity": info["modularity"]}
+    proportion_df.columns = cell_types
+    proportion_df["Predicted_Labels"] = np.array([str(c) for c in labels], dtype=object)
+    proportion_df["sampleID"] = list(proportions.keys())
+    return proportion_df
 
 
 # ---- gene-cluster differentiation (Gene_cluster_specific.py:8-201, Trajectory.py:1129-1172) --------------------------------

@@ -626,6 +626,39 @@ int pilot_ot_silhouette_points(const void *X, int X_is_device, int dtype, long l
 /* the geometry of that kernel for D columns of `dtype`: query rows per block (one per lane) and corpus rows per staged LDS tile */
 int pilot_ot_silhouette_points_geometry(int D, int dtype, int *queries_per_block, int *tile_rows);
 
+/* ---- elastic principal tree (K19): what pilotpy's fit_pricipla_graph (plot/ploting.py:229-282) asks of ElPiGraph -- a tree of
+ * nodes fitted to the n rows of X (n x D row-major, X_is_device / dtype / ld as in pilot_ot_knn_rows; D <= 64) and the pseudotime
+ * of every row along it.  The growth of the tree is the caller's; these calls fit candidate trees, give the start its moments and
+ * project the points.  Every sum has one fixed order that depends on n alone and no floating-point atomic is used: the same call
+ * returns the same bits, and a candidate's results are the same bits alone and in any batch, from a host matrix and from HBM.
+ *
+ * pilot_ot_elastic_fit_batch fits B candidates of m nodes each.  Candidate b: start positions Y0[b] (m x D) and spring matrix
+ * S[b] (m x m, symmetric).  At most max_iter times: every point goes to its nearest node (pilot_ot_knn_rows's distances -- direct
+ * sums of squared differences in the element type, the nodes rounded to it -- ties to the lowest node); cnt_j / sum_j = the count
+ * and the f64 sum of node j's points in ascending row order; (diag(cnt) / n + S) Y' = sum / n is solved by Cholesky;
+ * change = max_j |Y'_j - Y_j| / |Y'_j - centre|; Y <- Y'; stop once change < eps.  One more partition of the final Y gives
+ * counts (B x m), sums (B x m x D) and energy[b] = (the f64 mean squared distance of the points to their nodes, trace(Y^T S Y)).
+ * iters[b]: the solves done.  flags[b]: PILOT_OT_ELASTIC_CONVERGED, or PILOT_OT_ELASTIC_SINGULAR when a pivot was not positive
+ * (then Y[b] is the last iterate and energy[b] is NaN).
+ * pilot_ot_point_moments: mean (D) = the column means, cross (D x D) = sum_i (x_i - mean)(x_i - mean)^T, f64.
+ * pilot_ot_tree_projection: nodes (m x D), n_edges pairs edges[2 e] / edges[2 e + 1] = (a, b) with a the end nearer the source,
+ * base[j] = the tree distance from the source to node j.  Row i: p = y_a + t (y_b - y_a), t clipped to [0, 1], on the edge with the
+ * smallest f64 |x_i - p|^2 (ties to the lowest edge); pseudotime[i] = base[a] + t |y_b - y_a|, d2[i] = |x_i - p|^2, edge[i], t[i].
+ * All outputs are host arrays.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, D outside [1, 64], ld < D, dtype, n < 1, m outside [2, 65], B < 1, a
+ * non-finite Y0 / S / centre / nodes / base, max_iter < 1, eps < 0, n_edges outside [1, m - 1], an edge end outside [0, m); after
+ * the flag pass: a non-finite value in X (the message names the first such row).  PILOT_OT_ENOTSUP: n > INT_MAX. */
+#define PILOT_OT_ELASTIC_CONVERGED 1
+#define PILOT_OT_ELASTIC_SINGULAR 2
+#define PILOT_OT_ELASTIC_MAX_NODES 65
+#define PILOT_OT_ELASTIC_MAX_D 64
+int pilot_ot_elastic_fit_batch(const void *X, int X_is_device, int dtype, long long n, int D, long long ld, int B, int m,
+                               const double *Y0, const double *S, const double *centre, int max_iter, double eps, double *Y,
+                               double *energy, int *iters, int *flags, int *counts, double *sums);
+int pilot_ot_point_moments(const void *X, int X_is_device, int dtype, long long n, int D, long long ld, double *mean, double *cross);
+int pilot_ot_tree_projection(const void *X, int X_is_device, int dtype, long long n, int D, long long ld, int m, const double *nodes,
+                             int n_edges, const int *edges, const double *base, double *pseudotime, double *d2, int *edge, double *t);
+
 /* ---- cell-level W2 pair grid (EXTENSION: not in the reference; BASELINE config 5) ------ */
 /* Compares patients by their raw cell clouds instead of cell-type proportions.  X: n_cells x D float32 embedding
  * with the cells of patient i stored contiguously at rows offsets[i] .. offsets[i+1] (offsets: N + 1 entries).

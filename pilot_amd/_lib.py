@@ -26,6 +26,7 @@ DIFFMAP_NOT_CONVERGED, DIFFMAP_DEGENERATE = 1, 2
 TRAJFIT_OLS, TRAJFIT_HUBER, TRAJFIT_NOT_CONVERGED = 0, 1, 1
 PCA_NOT_CONVERGED, PCA_RANK_DEFICIENT = 1, 2
 KNN_ROWS_MAX_K = 64
+ELASTIC_CONVERGED, ELASTIC_SINGULAR, ELASTIC_MAX_NODES, ELASTIC_MAX_D = 1, 2, 65, 64
 
 # every symbol include/pilot_ot.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -51,6 +52,7 @@ SYMBOLS = [
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
     "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain",
     "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
+    "pilot_ot_elastic_fit_batch", "pilot_ot_point_moments", "pilot_ot_tree_projection",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
     "pilot_ot_multi_emd", "pilot_ot_multi_sync", "pilot_ot_multi_fetch", "pilot_ot_multi_device_matrix",
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
@@ -187,6 +189,11 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_louvain.argtypes = [ctypes.c_longlong, llp, ip, dp, c_dbl, c_dbl, c_int, ip, dp, ip]
     L.pilot_ot_silhouette_points.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, ip, c_int, dp, dp]
     L.pilot_ot_silhouette_points_geometry.argtypes = [c_int, c_int, ip, ip]
+    L.pilot_ot_elastic_fit_batch.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, dp, dp, dp,
+                                             c_int, c_dbl, dp, dp, ip, ip, ip, dp]
+    L.pilot_ot_point_moments.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, dp, dp]
+    L.pilot_ot_tree_projection.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, dp, c_int, ip, dp,
+                                           dp, dp, ip, dp]
     L.pilot_ot_multi_create.argtypes = [c_int, c_int, ip, c_int, c_int, ctypes.POINTER(c_vp)]
     L.pilot_ot_multi_destroy.argtypes = [c_vp]
     L.pilot_ot_multi_set_inputs.argtypes = [c_vp, dp, dp]

@@ -1482,3 +1482,273 @@ def curve_activities(curves, times):
     out = np.empty((G, 4), dtype=np.float64)
     _lib.check(_lib.load().pilot_ot_curve_activities(curves.ptr, curves.on_dev, G, T, _lib.dptr(times), _lib.dptr(out)))
     return out
+
+
+# ---- elastic principal tree and pseudotime (K19; the two ElPiGraph calls of pilotpy's fit_pricipla_graph) ------------------------
+TREE_MAX_NODES = _lib.ELASTIC_MAX_NODES - 1       # a tree of M nodes peaks at M + 1 while it grows
+TREE_BAND = 1e-10                                 # candidates within this relative distance of the lowest energy are tied
+
+
+def _points_arg(X):
+    Y = _dense_arg(X, "X", mode="strided", axes=" (points x dims)")
+    if not 1 <= Y.cols <= _lib.ELASTIC_MAX_D:
+        raise ValueError("X has %d columns: the principal tree takes 1 to %d" % (Y.cols, _lib.ELASTIC_MAX_D))
+    if Y.rows < 1:
+        raise ValueError("X has no rows")
+    if Y.rows > np.iinfo(np.int32).max:
+        raise NotImplementedError("%d rows need more than 32-bit row indices" % Y.rows)
+    return Y
+
+
+def _points_call(fn, Y, *args):
+    _lib.check(fn(Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, *args))
+
+
+def _fit_controls(max_iter, eps):
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError("max_iter=%r must be an integer >= 1" % (max_iter,))
+    if not eps >= 0:
+        raise ValueError("eps=%r must be >= 0" % (eps,))
+    return int(max_iter), float(eps)
+
+
+def point_moments(X):
+    """``(mean (D,), cross (D, D))`` of the rows of ``X``: the column means and ``sum_i (x_i - mean)(x_i - mean)^T``, float64 sums
+    in a fixed order on the device (include/pilot_ot.h, "elastic principal tree").  ``X`` as in :func:`principal_tree`."""
+    Y = _points_arg(X)
+    mean, cross = np.empty(Y.cols), np.empty((Y.cols, Y.cols))
+    _points_call(_lib.load().pilot_ot_point_moments, Y, _lib.dptr(mean), _lib.dptr(cross))
+    return mean, cross
+
+
+def tree_springs(n_nodes, edges, lam=0.01, mu=0.1):
+    """The m x m spring matrix of a tree: ``lam * v v^T`` per edge (a, b), v = e_a - e_b, plus ``mu * s s^T`` per node c of degree
+    k >= 2, s = e_c - (1 / k) sum of e_l over c's neighbours l (in edge-list order)."""
+    S = np.zeros((n_nodes, n_nodes))
+    nb = [[] for _ in range(n_nodes)]
+    for a, b in edges:
+        v = np.zeros(n_nodes)
+        v[a], v[b] = 1.0, -1.0
+        S += lam * np.outer(v, v)
+        nb[a].append(b)
+        nb[b].append(a)
+    for c, ls in enumerate(nb):
+        if len(ls) >= 2:
+            s = np.zeros(n_nodes)
+            s[c] = 1.0
+            s[ls] = -1.0 / len(ls)
+            S += mu * np.outer(s, s)
+    return S
+
+
+ElasticFit = collections.namedtuple("ElasticFit", "nodes energy iters flags counts sums")
+
+
+def _elastic_fit(Y, nodes, springs, centre, max_iter, eps):
+    """:func:`elastic_fit` of a batch (B, m, D) / (B, m, m) with the singular flag left to the caller"""
+    nodes, springs, centre = _as_f64(nodes, "nodes"), _as_f64(springs, "springs"), _as_f64(centre, "centre")
+    if nodes.ndim != 3 or nodes.shape[0] < 1 or nodes.shape[2] != Y.cols:
+        raise ValueError("nodes: (candidates, m, %d) expected, got %s" % (Y.cols, nodes.shape))
+    B, m, D = nodes.shape
+    if not 2 <= m <= _lib.ELASTIC_MAX_NODES:
+        raise ValueError("m=%d nodes outside [2, %d]" % (m, _lib.ELASTIC_MAX_NODES))
+    if springs.shape != (B, m, m):
+        raise ValueError("springs: %s expected, got %s" % ((B, m, m), springs.shape))
+    if centre.shape != (D,):
+        raise ValueError("centre: %d values expected, got %s" % (D, centre.shape))
+    max_iter, eps = _fit_controls(max_iter, eps)
+    out = ElasticFit(np.empty((B, m, D)), np.empty((B, 2)), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32),
+                     np.empty((B, m), dtype=np.int32), np.empty((B, m, D)))
+    _points_call(_lib.load().pilot_ot_elastic_fit_batch, Y, B, m, _lib.dptr(nodes), _lib.dptr(springs), _lib.dptr(centre), max_iter, eps,
+                 _lib.dptr(out.nodes), _lib.dptr(out.energy), _lib.iptr(out.iters), _lib.iptr(out.flags), _lib.iptr(out.counts),
+                 _lib.dptr(out.sums))
+    return out
+
+
+def elastic_fit(X, nodes, springs, centre, max_iter=10, eps=0.01):
+    """K19: fit elastic graphs to the rows of ``X`` on the device (include/pilot_ot.h, "elastic principal tree").  ``nodes``
+    (m, D) start positions and ``springs`` (m, m) the spring matrix (:func:`tree_springs`), or batches (B, m, D) / (B, m, m) fitted
+    in one call; ``centre`` (D,): the point the change of a node is measured against (the data mean).  At most ``max_iter`` times:
+    partition the points by nearest node (:func:`knn`'s distances in X's dtype, ties to the lowest node), solve
+    ``(diag(cnt) / n + S) Y' = sum / n``, stop once ``max_j |Y'_j - Y_j| / |Y'_j - centre| < eps``.  Returns ``ElasticFit(nodes,
+    energy, iters, flags, counts, sums)``: the fitted positions, ``energy[..., 0]`` the mean squared distance of the points to
+    their nodes and ``energy[..., 1] = trace(Y^T S Y)``, the solves done, ``flags & 1`` converged, and the counts and sums of the
+    final partition.  A candidate gives the same bits alone and in any batch.  ValueError: a bad shape, m outside [2, 65], D
+    outside [1, 64], non-finite arguments, ``max_iter < 1``, ``eps < 0`` (all before any device work); a candidate whose system
+    is singular (a pivot of the Cholesky factor was not positive; the message names the candidate)."""
+    Y = _points_arg(X)
+    nodes, springs = np.asarray(nodes, dtype=np.float64), np.asarray(springs, dtype=np.float64)
+    single = nodes.ndim == 2
+    fit = _elastic_fit(Y, nodes[None] if single else nodes, springs[None] if single and springs.ndim == 2 else springs, centre,
+                       max_iter, eps)
+    bad = np.flatnonzero(fit.flags & _lib.ELASTIC_SINGULAR)
+    if bad.size:
+        raise ValueError("elastic fit: the system of candidate %d is singular (a node without points and without springs?)" % bad[0])
+    return ElasticFit(*(a[0] for a in fit)) if single else fit
+
+
+def _tree_neighbours(m, edges):
+    nb = [[] for _ in range(m)]
+    for a, b in edges:
+        nb[a].append(b)
+        nb[b].append(a)
+    return nb
+
+
+def _drop_index(edges, gone, into=None):
+    """the edge list with node ``gone`` replaced by ``into`` and every index above it shifted down"""
+    def f(v):
+        v = into if v == gone and into is not None else v
+        return v - 1 if v > gone else v
+    return [(f(a), f(b)) for a, b in edges]
+
+
+def _grow_candidates(nodes, edges, counts, sums):
+    """every tree one node larger, in the listed order: an edge bisected, then a node attached to every node"""
+    m = len(nodes)
+    nb = _tree_neighbours(m, edges)
+    out = []
+    for i, (a, b) in enumerate(edges):
+        e = list(edges)
+        e[i] = (a, m)
+        e.append((m, b))
+        out.append((np.vstack([nodes, 0.5 * (nodes[a] + nodes[b])]), e, "bisect edge %d" % i))
+    for v in range(m):
+        if len(nb[v]) == 1:
+            y = 2.0 * nodes[v] - nodes[nb[v][0]]
+        elif counts[v] > 0:
+            y = sums[v] / counts[v]
+        else:
+            y = nodes[nb[v]].mean(axis=0)
+        out.append((np.vstack([nodes, y]), list(edges) + [(v, m)], "attach to node %d" % v))
+    return out
+
+
+def _shrink_candidates(nodes, edges):
+    """every tree one node smaller, in the listed order: an edge contracted, then a leaf deleted"""
+    m = len(nodes)
+    nb = _tree_neighbours(m, edges)
+    out = []
+    for i, (a, b) in enumerate(edges):
+        keep, gone = min(a, b), max(a, b)
+        y = nodes.copy()
+        y[keep] = 0.5 * (nodes[a] + nodes[b])
+        out.append((np.delete(y, gone, axis=0), _drop_index(edges[:i] + edges[i + 1:], gone, keep), "contract edge %d" % i))
+    for v in range(m):
+        if len(nb[v]) == 1:
+            rest = [e for e in edges if v not in e]
+            out.append((np.delete(nodes, v, axis=0), _drop_index(rest, v), "delete leaf %d" % v))
+    return out
+
+
+def principal_tree(X, n_nodes=20, lam=0.01, mu=0.1, max_iter=10, eps=0.01, return_info=False):
+    """K19: the elastic principal tree of the rows of ``X`` (Albergante et al., Entropy 2020; what ElPiGraph's
+    ``computeElasticPrincipalTree(X, n_nodes)`` fits), grown on the host and fitted on the device.  ``X``: n x D, D <= 64, a numpy
+    array or a :class:`DeviceMatrix`, float32 or float64 (other dtypes convert to float64); it goes up once.  The tree starts as
+    two nodes at ``mean -/+ sqrt(w) v`` for the leading eigenpair (w, v) of the covariance (v's largest entry positive) and grows
+    by the grammar *grow, grow, shrink* until it has ``n_nodes`` nodes (3 to 64).  A grow step tries every edge bisected and a node
+    attached to every node; a shrink step every edge contracted and every leaf deleted; all candidates of a step are fitted in one
+    :func:`elastic_fit` batch and the lowest-listed one whose energy (mean squared distance + ``trace(Y^T S Y)``) is within
+    1e-10 relative of the lowest wins -- candidates of the same topology reach the same optimum and tie to rounding.  Returns
+    ``(nodes float64 (n_nodes, D), edges int32 (n_nodes - 1, 2))``; with ``return_info`` also a dict: ``steps``, ``candidates``
+    (fitted per step), ``winners`` (index per step), ``energy`` (of the winner per step, the last one the tree's) and ``labels``.
+    The same call returns the same bits.  ValueError: bad arguments (before any device work), all points coincide, a non-finite
+    value in X (names the row), a candidate with a singular system (names the step and the candidate)."""
+    Y = _points_arg(X)
+    if isinstance(n_nodes, bool) or not isinstance(n_nodes, (int, np.integer)) or not 3 <= n_nodes <= TREE_MAX_NODES:
+        raise ValueError("n_nodes=%r outside [3, %d]" % (n_nodes, TREE_MAX_NODES))
+    if not (np.isfinite(lam) and np.isfinite(mu) and lam >= 0 and mu >= 0):
+        raise ValueError("lam=%r, mu=%r must be finite and >= 0" % (lam, mu))
+    max_iter, eps = _fit_controls(max_iter, eps)
+    n = Y.rows
+    if n < 2:
+        raise ValueError("a principal tree needs at least 2 points, got %d" % n)
+    if not Y.on_dev:
+        Y = _dense_arg(DeviceMatrix.upload(Y.keep), "X")
+    centre, cross = point_moments(Y.keep)
+    w, V = np.linalg.eigh(cross / (n - 1))
+    w, v = w[-1], V[:, -1]
+    if not w > 0:
+        raise ValueError("all points coincide: there is no direction to start the tree along")
+    v = v if v[np.argmax(np.abs(v))] > 0 else -v
+    half = np.sqrt(w) * v
+
+    def fit(cands, step):
+        B = len(cands)
+        springs = np.stack([tree_springs(len(c[0]), c[1], lam, mu) for c in cands])
+        res = _elastic_fit(Y, np.stack([c[0] for c in cands]), springs, centre, max_iter, eps)
+        bad = np.flatnonzero(res.flags & _lib.ELASTIC_SINGULAR)
+        if bad.size:
+            raise ValueError("principal tree: step %d, candidate %d (%s): its system is singular" % (step, bad[0], cands[bad[0]][2]))
+        E = res.energy.sum(axis=1)
+        win = int(np.flatnonzero(E <= E.min() * (1.0 + TREE_BAND))[0])
+        info["candidates"].append(B)
+        info["winners"].append(win)
+        info["energy"].append(float(E[win]))
+        info["labels"].append(cands[win][2])
+        return res.nodes[win], cands[win][1], res.counts[win], res.sums[win]
+
+    info = {"candidates": [], "winners": [], "energy": [], "labels": []}
+    nodes, edges, counts, sums = fit([(np.stack([centre - half, centre + half]), [(0, 1)], "start")], 0)
+    step = 0
+    while len(nodes) < n_nodes:
+        for grow in (True, True, False):
+            step += 1
+            cands = _grow_candidates(nodes, edges, counts, sums) if grow else _shrink_candidates(nodes, edges)
+            nodes, edges, counts, sums = fit(cands, step)
+    edges = np.asarray(edges, dtype=np.int32).reshape(-1, 2)
+    info["steps"] = step
+    return (nodes, edges, info) if return_info else (nodes, edges)
+
+
+def tree_orientation(nodes, edges, source=0):
+    """``(oriented edges int32 (E, 2), base float64 (m,))`` of a tree: every edge as (a, b) with a the end nearer ``source``, in
+    the order given, and the tree distance from ``source`` to every node (a host walk).  ValueError unless the edges form a tree
+    on the m nodes and ``source`` is one of them."""
+    nodes = _as_f64(nodes, "nodes")
+    if nodes.ndim != 2 or not 2 <= nodes.shape[0] <= _lib.ELASTIC_MAX_NODES:
+        raise ValueError("nodes: (m, D) with 2 <= m <= %d expected, got %s" % (_lib.ELASTIC_MAX_NODES, nodes.shape))
+    m = nodes.shape[0]
+    edges = np.asarray(edges)
+    if edges.shape != (m - 1, 2) or not np.issubdtype(edges.dtype, np.integer) or edges.min() < 0 or edges.max() >= m:
+        raise ValueError("edges: %d pairs of node indices in [0, %d) expected" % (m - 1, m))
+    if isinstance(source, bool) or not isinstance(source, (int, np.integer)) or not 0 <= source < m:
+        raise ValueError("source=%r is not a node index in [0, %d)" % (source, m))
+    nb = [[] for _ in range(m)]
+    for e, (a, b) in enumerate(edges):
+        nb[a].append((int(b), e))
+        nb[b].append((int(a), e))
+    base = np.full(m, np.nan)
+    base[source] = 0.0
+    oriented = np.array(edges, dtype=np.int32)
+    stack = [int(source)]
+    while stack:
+        a = stack.pop()
+        for b, e in nb[a]:
+            if np.isnan(base[b]):
+                base[b] = base[a] + np.sqrt(((nodes[b] - nodes[a]) ** 2).sum())
+                oriented[e] = (a, b)
+                stack.append(b)
+    if np.isnan(base).any():
+        raise ValueError("edges: not a tree (node %d is not connected to the source)" % int(np.flatnonzero(np.isnan(base))[0]))
+    return oriented, base
+
+
+def tree_pseudotime(X, nodes, edges, source=0):
+    """K19: every row of ``X`` onto its nearest edge of the tree ``(nodes, edges)`` and its pseudotime from node ``source`` (what
+    ElPiGraph's ``getPseudotime`` gives), on the device in float64.  Returns ``(pseudotime, d2, edge, t)``, one entry per row: with
+    (a, b) = ``tree_orientation(nodes, edges, source)[0][edge]`` the projection is ``y_a + t (y_b - y_a)``, t clipped to [0, 1],
+    ``d2`` its squared distance from the row (the smallest over the edges, ties to the lowest edge) and
+    ``pseudotime = dist(source, a) + t |y_b - y_a|``.  ValueError before any device work: bad shapes, edges that are no tree, a bad
+    ``source``; from the device's first pass: a non-finite value in X (names the row)."""
+    Y = _points_arg(X)
+    oriented, base = tree_orientation(nodes, edges, source)
+    nodes = _as_f64(nodes, "nodes")
+    if nodes.shape[1] != Y.cols:
+        raise ValueError("nodes have %d columns, X has %d" % (nodes.shape[1], Y.cols))
+    n = Y.rows
+    oriented = np.ascontiguousarray(oriented, dtype=np.int32)
+    pt, d2, edge, t = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32), np.empty(n)
+    _points_call(_lib.load().pilot_ot_tree_projection, Y, nodes.shape[0], _lib.dptr(nodes), len(oriented), _lib.iptr(oriented),
+                 _lib.dptr(base), _lib.dptr(pt), _lib.dptr(d2), _lib.iptr(edge), _lib.dptr(t))
+    return pt, d2, edge, t

@@ -396,7 +396,7 @@ def diffusion_map(adata, n_evecs=2, epsilon=1, alpha=0.5, knn=64):
     (float64, N x n_evecs, sample order), computed on the device from ``adata.uns['EMD']`` (a numpy array or an
     ``engine.DeviceMatrix``).  Returns the embedding.  A disconnected neighbour graph (eigenvalue 1 repeated: the coordinates
     sqrt(-1 / lambda) are meaningless) or an eigensolver that did not converge raises ValueError and leaves ``adata.uns``
-    alone.  Pseudotime (ElPiGraph) and the plot itself are not part of this."""
+    alone.  The plot itself is not part of this; the pseudotime along the embedding is :func:`fit_principal_graph`'s."""
     E = adata.uns["EMD"]
     dmap, _, _, info = engine.diffusion_map_of_rows(E, n_evecs=n_evecs, epsilon=epsilon, alpha=alpha, k=knn, return_info=True)
     if info["degenerate"]:
@@ -406,6 +406,32 @@ def diffusion_map(adata, n_evecs=2, epsilon=1, alpha=0.5, knn=64):
         raise ValueError("diffusion map: the eigensolver did not converge in %d Lanczos steps" % info["steps"])
     adata.uns["embedding"] = dmap
     return dmap
+
+
+def fit_principal_graph(adata, NumNodes=20, source_node=0, Lambda=0.01, Mu=0.1, X=None):
+    """fit_pricipla_graph (plot/ploting.py:229-282) without ElPiGraph, plots or files: the elastic principal tree of the
+    embedding (``engine.principal_tree``, ``NumNodes`` nodes, elasticity ``Lambda`` / ``Mu``) and every sample's pseudotime along
+    it from node ``source_node`` (``engine.tree_pseudotime``), both on the device.  The points are ``X`` when given, else
+    ``adata.uns['embedding']`` (:func:`diffusion_map`).  Writes ``adata.uns['pseudotime']`` (n float64, row order) and
+    ``adata.uns['principal_graph']``: ``nodes``, ``edges`` (each as (a, b) with a the end nearer the source), ``energy`` of the
+    tree, per point the ``edge`` it projects onto and the parameter ``t`` along it, and ``params``.  Returns the pseudotime.
+    Nothing is written when a step raises.  The rule is this library's statement of the published algorithm (README, "Principal
+    tree"), not a pin to an elpigraph release."""
+    if X is None:
+        if "embedding" not in adata.uns:
+            raise KeyError("fit_principal_graph needs points: run tl.diffusion_map (adata.uns['embedding']) or pass X=")
+        X = adata.uns["embedding"]
+    nodes, edges, info = engine.principal_tree(X, n_nodes=NumNodes, lam=Lambda, mu=Mu, return_info=True)
+    pseudotime, _, edge, t = engine.tree_pseudotime(X, nodes, edges, source=source_node)
+    oriented, _ = engine.tree_orientation(nodes, edges, source_node)
+    adata.uns["pseudotime"] = pseudotime
+    adata.uns["principal_graph"] = {"nodes": nodes, "edges": oriented, "energy": info["energy"][-1], "edge": edge, "t": t,
+                                    "params": {"NumNodes": int(NumNodes), "source_node": int(source_node), "Lambda": float(Lambda),
+                                               "Mu": float(Mu), "steps": info["steps"]}}
+    return pseudotime
+
+
+fit_pricipla_graph = fit_principal_graph      # the reference's spelling
 
 
 def wasserstein_distance(adata, emb_matrix="X_PCA", clusters_col="cell_types", sample_col="sampleID",
@@ -689,7 +715,7 @@ def cell_importance(adata, pseudotime=None, p_val=1):
     (``engine.trajectory_fits``, every p-value <= ``p_val`` to be eligible), and the report table (numeric columns).  Writes
     ``adata.uns['cellnames']`` (the selected cell types, best R^2 first) and ``adata.uns['orders']`` (sampleID, Time_score
     1..N in pseudotime order).  ``pseudotime``: one value per sample in ``uns['proportions']`` order; default
-    ``adata.uns['pseudotime']`` (pilotpy's fit_pricipla_graph)."""
+    ``adata.uns['pseudotime']`` (pilotpy's fit_pricipla_graph; here :func:`fit_principal_graph` writes it)."""
     if pseudotime is None:
         if "pseudotime" not in adata.uns:
             raise KeyError("cell_importance needs a pseudotime: pass pseudotime= (one value per sample, e.g. a diffusion "

@@ -27,6 +27,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 constexpr float CELL_NEG_BIG = -1.0e30f;
@@ -519,9 +521,7 @@ __global__ void __launch_bounds__(CELL_WG) cell_w2_kernel(CellParams p) {
                 hv_new[row] = logb2 - lse2;
             });
             if (check) {   // wave-uniform
-                float s = e2;
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+                const float s = lanes_sum(e2);
                 if (lane == 0) red[wave] = s;
             }
             __syncthreads();
@@ -541,8 +541,7 @@ __global__ void __launch_bounds__(CELL_WG) cell_w2_kernel(CellParams p) {
         }
         // ---- value <Gamma, C> ---------------------------------------------------------------------------------------
         float part = value_pass<KB, NP, (AUG && NP == 2)>(Xb, o_p, nxp, np, o_q, nyq, nq, hu, hv_cur, p.dot_unscale, p.inv_scale, wave, n_waves, lane);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
+        part = lanes_sum(part);
         if (lane == 0) red[16 + wave] = part;
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -14,6 +14,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 // max of a buffer of non-negative doubles -> out[0] (preset to 0): the bit patterns of non-negative doubles order like
@@ -25,10 +27,7 @@ static __global__ void max_reduce_kernel(const double *__restrict__ X, long n, d
     for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) m = X[t] > m ? X[t] : m;
     part[threadIdx.x] = m;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) part[threadIdx.x] = part[threadIdx.x] > part[threadIdx.x + s] ? part[threadIdx.x] : part[threadIdx.x + s];
-        __syncthreads();
-    }
+    tree_fold<256>(part, [](double a, double b) { return a > b ? a : b; });      // (a NaN in X loses wherever it stands)
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned long long *>(out), (unsigned long long)__double_as_longlong(part[0]));
 }
 

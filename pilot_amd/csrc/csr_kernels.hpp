@@ -4,8 +4,8 @@
 // fixed order and nothing uses a floating-point atomic (integer atomics count), so every result has the same bits on every run.
 //
 // Row kernels (normalise, densify): one wave per row, CSR_ROW_WAVES rows per workgroup; the lanes stride over the row's stored
-// values.  A row's total is 64 per-lane partial sums (lane l adds entries l, l + 64, ... in that order) joined by a butterfly of
-// six __shfl_xor steps, which leaves the same bits in every lane.
+// values.  A row's total is 64 per-lane partial sums (lane l adds entries l, l + 64, ... in that order) joined by the wave
+// butterfly (lanes_sum, reduce.hpp), which leaves the same bits in every lane.
 //
 // Column form: the rows are cut into slices of CSR_SLICE_ROWS.  (1) every slice counts its entries per column (integer atomics
 // into counts[slice][column]); (2) one thread per column turns its counts into an exclusive prefix over the slices and the
@@ -25,6 +25,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 constexpr int CSR_SLICE_ROWS = 512;     // rows per slice of the column-form build (pilot_ot_csr_slice_rows)
@@ -32,17 +34,6 @@ constexpr int CSR_ROW_WAVES = 4;        // rows (waves) per workgroup of the row
 constexpr int CSR_COL_THREADS = 256;    // threads per column of the moments kernel
 constexpr int CSR_SCAN_THREADS = 1024;
 constexpr int CSR_MAX_GROUPS = 8;
-
-__device__ inline double csr_wave_sum(double s) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
-    return s;
-}
-__device__ inline int csr_wave_sum(int s) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
-    return s;
-}
 
 // normalize_total(target_sum) then log1p on the stored values of every row: the expressions of trajfit_normalize_kernel
 template <typename T>
@@ -54,7 +45,7 @@ __global__ void __launch_bounds__(64 * CSR_ROW_WAVES) csr_normalize_kernel(const
     const long long p0 = indptr[r], p1 = indptr[r + 1];
     double s = 0.0;
     for (long long p = p0 + lane; p < p1; p += 64) s += (double)data[p];
-    const double total = csr_wave_sum(s);
+    const double total = lanes_sum(s);
     const double scale = total > 0.0 ? target_sum / total : 0.0;
     for (long long p = p0 + lane; p < p1; p += 64) data[p] = (T)log1p((double)data[p] * scale);
 }
@@ -197,8 +188,8 @@ __global__ void __launch_bounds__(CSR_COL_THREADS) csr_group_moments_kernel(cons
     }
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        const double ws = csr_wave_sum(s[g]);
-        const int wk = csr_wave_sum(k[g]);
+        const double ws = lanes_sum(s[g]);
+        const int wk = lanes_sum(k[g]);
         if (lane == 0) {
             red.d[g][wave] = ws;
             red.k[g][wave] = wk;
@@ -210,13 +201,8 @@ __global__ void __launch_bounds__(CSR_COL_THREADS) csr_group_moments_kernel(cons
     int stored[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        double a = red.d[g][0];
-        int b = red.k[g][0];
-#pragma unroll
-        for (int w = 1; w < CSR_COL_THREADS / 64; ++w) {
-            a += red.d[g][w];
-            b += red.k[g][w];
-        }
+        const double a = fold_in_order<CSR_COL_THREADS / 64>(red.d[g], Sum{});
+        const int b = fold_in_order<CSR_COL_THREADS / 64>(red.k[g], Sum{});
         mu[g] = rows.n[g] > 0 ? a / (double)rows.n[g] : nan;
         stored[g] = b;
     }
@@ -235,13 +221,12 @@ __global__ void __launch_bounds__(CSR_COL_THREADS) csr_group_moments_kernel(cons
     }
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        const double wq = csr_wave_sum(q[g]);
+        const double wq = lanes_sum(q[g]);
         if (lane == 0) red.d[g][wave] = wq;
     }
     __syncthreads();
     if (t < NG && t < n_groups) {
-        double a = red.d[t][0];
-        for (int w = 1; w < CSR_COL_THREADS / 64; ++w) a += red.d[t][w];
+        const double a = fold_in_order<CSR_COL_THREADS / 64>(red.d[t], Sum{});
         double m = nan, v = nan;
 #pragma unroll
         for (int g = 0; g < NG; ++g)                       // (mu, stored, rows.n by a constant index: they stay in registers)

@@ -6,14 +6,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace pilot {
+#include "reduce.hpp"
 
-// ---- fixed-order reductions over a wave of 64 -----------------------------------------------------------------------------------
-__device__ inline double cv_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);     // every lane ends with the same tree sum
-    return v;
-}
+namespace pilot {
 
 // ---- K11a: sample standard deviation (ddof 1) of every selected column over each contiguous row segment --------------------------
 // Grid (column tiles of 64, segments); one lane per column (64 consecutive elements of a row per wave: coalesced along the genes),
@@ -84,13 +79,13 @@ __global__ void __launch_bounds__(64) fitted_curves_kernel(const double *__restr
         o[t] = v;
         s += v;
     }
-    const double mean = cv_wave_sum(s) / T;
+    const double mean = lanes_sum(s) / T;
     double q = 0.0;
     for (int t = lane; t < T; t += 64) {             // (a lane re-reads only what it wrote)
         const double d = o[t] - mean;
         q += d * d;
     }
-    double scale = sqrt(cv_wave_sum(q) / T);
+    double scale = sqrt(lanes_sum(q) / T);
     if (scale < 10.0 * 2.220446049250313e-16) scale = 1.0;
     for (int t = lane; t < T; t += 64) o[t] = (o[t] - mean) / scale;
 }
@@ -146,11 +141,9 @@ __global__ void __launch_bounds__(256) curve_distance_kernel(const double *__res
             D[(long long)j * G + i] = d;
             mx = fmax(mx, d);
         }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
-    if ((tid & 63) == 0) wmax[tid >> 6] = mx;
-    __syncthreads();
-    if (tid == 0) bmax[bi * gridDim.x + bj] = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+    const auto larger = [](double a, double b) { return fmax(a, b); };      // (fmax: a NaN distance is passed over)
+    mx = waves_in_order<4>(lanes_reduce(mx, larger), wmax, larger);
+    if (tid == 0) bmax[bi * gridDim.x + bj] = mx;
 }
 
 // ---- K11b, merging: the nearest-neighbour chain over the full G x G matrix in HBM, one persistent workgroup --------------------------
@@ -199,12 +192,7 @@ __global__ void __launch_bounds__(CV_NN_BLOCK) nn_chain_kernel(double *__restric
                 const double d = row[i];
                 if (i != x && d < bv) { bv = d; bi = i; }
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ov = __shfl_xor(bv, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
+            lanes_best(bv, bi, LowestMin{});
             if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
             __syncthreads();
             if (tid == 0) {
@@ -266,8 +254,8 @@ __global__ void __launch_bounds__(64) curve_activities_kernel(const double *__re
         tr += ((c[j + 1] - m1) + (c[j] - m0)) / 2.0 * dt;
         sw += ((m1 - cT) + (m0 - cT)) / 2.0 * dt;
     }
-    tr = cv_wave_sum(tr);
-    sw = cv_wave_sum(sw);
+    tr = lanes_sum(tr);
+    sw = lanes_sum(sw);
     if (lane != 0) return;
     double *o = out + (long long)g * 4;
     o[0] = (cT - c0) / span;

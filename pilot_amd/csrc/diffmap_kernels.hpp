@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lanczos_kernels.hpp"
+#include "reduce.hpp"
 
 namespace pilot {
 
@@ -52,7 +53,7 @@ static __global__ void __launch_bounds__(DM_RED) dm_row_kernel(const double *__r
     double s = 0.0;
     if (mode == 0) for (int j = threadIdx.x; j < N; j += DM_RED) s += row[j];
     else           for (int j = threadIdx.x; j < N; j += DM_RED) s += row[j] * qa[j];
-    s = dm_block_sum<DM_RED>(s, red);
+    s = block_tree_sum<DM_RED>(s, red);
     if (threadIdx.x == 0) {
         if (mode == 0) qa[i] = pow(s, -alpha);
         else {
@@ -78,7 +79,7 @@ static __global__ void __launch_bounds__(DM_FIN) lz_start_kernel(const double *_
     __shared__ double red[DM_FIN];
     double s = 0.0;
     for (int n = threadIdx.x; n < N; n += DM_FIN) s += phi[n] * phi[n];
-    const double nrm = sqrt(dm_block_sum<DM_FIN>(s, red));
+    const double nrm = sqrt(block_tree_sum<DM_FIN>(s, red));
     for (int n = threadIdx.x; n < N; n += DM_FIN) V[n] = phi[n] / nrm;
 }
 
@@ -91,7 +92,7 @@ static __global__ void __launch_bounds__(256) lz_gemv_kernel(const double *__res
     const double *row = S + (size_t)i * N;
     double s = 0.0;
     for (int j = lane; j < N; j += 64) s += row[j] * v[j];
-    s = dm_wave_sum(s);
+    s = lanes_sum(s);
     if (lane == 0) w[i] = s;
 }
 
@@ -112,17 +113,10 @@ static __global__ void __launch_bounds__(DM_RED) dm_finalize_kernel(const double
         const double a = fabs(x);
         if (a > best) { best = a; at = n; }                    // (n ascending: the first of equal magnitudes stays)
     }
-    const double nrm = sqrt(dm_block_sum<DM_RED>(s, red));
+    const double nrm = sqrt(block_tree_sum<DM_RED>(s, red));
     bv[threadIdx.x] = best; bi[threadIdx.x] = at;
     __syncthreads();
-    for (int st = DM_RED / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            const double a = bv[threadIdx.x], b = bv[threadIdx.x + st];
-            const int ia = bi[threadIdx.x], ib = bi[threadIdx.x + st];
-            if (b > a || (b == a && ib < ia)) { bv[threadIdx.x] = b; bi[threadIdx.x] = ib; }
-        }
-        __syncthreads();
-    }
+    tree_best<DM_RED>(bv, bi, LowestMax{});
     const double sgn = (bi[0] < N && psi[(size_t)bi[0] * m + c] < 0.0) ? -1.0 : 1.0;     // (an all-NaN column: no index)
     const double scale = sqrt(-1.0 / lambda[c]);
     for (int n = threadIdx.x; n < N; n += DM_RED) {

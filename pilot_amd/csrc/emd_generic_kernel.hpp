@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "emd_kernels.hpp"
+#include "reduce.hpp"
 
 namespace pilot {
 
@@ -23,38 +24,6 @@ __host__ __device__ constexpr size_t emdg_lds_bytes(int K) {
 }
 // global slab per resident workgroup: F (K*K), A (K) doubles, then Apar (K ints, padded to 8 bytes)
 __host__ __device__ constexpr size_t emdg_slab_doubles(int K) { return (size_t)K * K + K + (K + 1) / 2; }
-
-struct BlockMin { double v; int i; };
-// workgroup-wide (value, index) minimum, smallest index among equal values; every thread gets the result
-__device__ inline BlockMin block_argmin(double v, int i, double *red_v, int *red_i) {
-    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(i, off);
-        if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-    if (lane == 0) { red_v[wave] = v; red_i[wave] = i; }
-    __syncthreads();
-    BlockMin r{red_v[0], red_i[0]};
-#pragma unroll
-    for (int w = 1; w < EMDG_WG / 64; ++w)
-        if (red_v[w] < r.v || (red_v[w] == r.v && red_i[w] < r.i)) { r.v = red_v[w]; r.i = red_i[w]; }
-    __syncthreads();
-    return r;
-}
-__device__ inline double block_sum(double v, double *red_v) {
-    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if (lane == 0) red_v[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < EMDG_WG / 64; ++w) s += red_v[w];
-    __syncthreads();
-    return s;
-}
 
 // PILOT_PLAN_TU (pilot_ot_plans.hip): emd_generic_plan_kernel, the same source with pairs from the list in `pa`, results at the
 // item's index, and the final pass over F also writing every entry of the pair's K x K block of pa.plans (see emd_grid_kernel)
@@ -110,7 +79,7 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_plan_kernel(EmdParams p, 
             ra[k] = p.P[(size_t)i_s * K + k]; rb[k] = p.P[(size_t)j_s * K + k];
             sa += ra[k]; sb += rb[k];
         }
-        sa = block_sum(sa, red_v); sb = block_sum(sb, red_v);
+        sa = block_sum<EMDG_WG / 64>(sa, red_v); sb = block_sum<EMDG_WG / 64>(sb, red_v);
         const double scale = sa / sb, tol = 1e-15 * (sa > 0.0 ? sa : 1.0);
         for (size_t e = tid; e < (size_t)K * K; e += EMDG_WG) F[e] = 0.0;
         for (int k = tid; k < K; k += EMDG_WG) {
@@ -174,10 +143,10 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_plan_kernel(EmdParams p, 
                 double bv = INF; int bi = 0x7fffffff;
                 for (int j = tid; j < K; j += EMDG_WG)
                     if (openC[j] && (dC[j] < bv || (dC[j] == bv && j < bi))) { bv = dC[j]; bi = j; }
-                const BlockMin m = block_argmin(bv, bi, red_v, red_i);
-                if (!(m.v < INF)) break;                              // nothing (more) reachable: only rounding dust is left
-                const int best = m.i;
-                const double bd = m.v;
+                block_best<EMDG_WG / 64>(bv, bi, red_v, red_i, LowestMin{});      // every thread gets the workgroup's pair
+                if (!(bv < INF)) break;                               // nothing (more) reachable: only rounding dust is left
+                const int best = bi;
+                const double bd = bv;
                 if (tid == 0) { openC[best] = 0; fC[best] = bd; sh_i[0] = 0; }
                 __syncthreads();
                 if (rb[best] > 0.0) { target = best; dstar = bd; break; }     // (uniform: LDS value)
@@ -252,7 +221,7 @@ __global__ void __launch_bounds__(EMDG_WG) emd_generic_plan_kernel(EmdParams p, 
         } else {
             for (size_t e = tid; e < (size_t)K * K; e += EMDG_WG) { const double f = F[e]; if (f != 0.0) cost += f * M[e]; }
         }
-        cost = block_sum(cost, red_v);
+        cost = block_sum<EMDG_WG / 64>(cost, red_v);
         if (tid == 0) {
             p.emd[q] = trip ? __builtin_nan("") : cost;
             if (p.n_aug) p.n_aug[q] = trip ? -(n_aug * 8 + trip) : n_aug;

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "plan_args.hpp"
+#include "reduce.hpp"
 
 namespace pilot {
 
@@ -39,31 +40,6 @@ struct GenericParams {
 #define PILOT_GENERIC_WG 1024
 #endif
 constexpr int GENERIC_WG = PILOT_GENERIC_WG, GENERIC_WAVES = GENERIC_WG / 64;     // (sixteen waves: a sixteenth of the contraction range each)
-
-__device__ inline double block_reduce_sum(double x, double *red) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    __syncthreads();
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < GENERIC_WG / 64; ++w) s += red[w];       // fixed order
-    return s;
-}
-__device__ inline double wave_tree_sum(double x) {      // every lane gets the sum of the 64, always added in the same order
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ inline double block_reduce_max(double x, double *red) {
-    for (int off = 32; off >= 1; off >>= 1) { const double y = __shfl_xor(x, off); x = y > x ? y : x; }
-    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    __syncthreads();
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    double s = red[0];
-    for (int w = 1; w < GENERIC_WG / 64; ++w) s = red[w] > s ? red[w] : s;
-    return s;
-}
 
 // PILOT_PLAN_TU (pilot_ot_plans.hip): sinkhorn_generic_plan_kernel, the same source with pairs from the list in `pa` (p.list is
 // not read), results at the item's index, and the final pass also storing POT's get_Gamma entry by entry into the pair's K x K
@@ -155,9 +131,12 @@ static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_plan_kerne
                 mu = fabs(u[k]) > mu ? fabs(u[k]) : mu;
                 mv = fabs(v[k]) > mv ? fabs(v[k]) : mv;
             }
-            const bool has_nan = block_reduce_max(nanf, red) > 0.0;
-            mu = block_reduce_max(mu, red);
-            mv = block_reduce_max(mv, red);
+            // (block_max / block_sum end in a barrier, so `red` is free for the next call at once; nothing else rides on their
+            // barriers: u, v, alpha, beta are last written behind the barrier that ends product() or build_kernel(), and the
+            // write-back of u, v after a NaN comes after the two barriers of the block_sum or block_max in front of it)
+            const bool has_nan = block_max<GENERIC_WAVES>(nanf, red) > 0.0;
+            mu = block_max<GENERIC_WAVES>(mu, red);
+            mv = block_max<GENERIC_WAVES>(mv, red);
             if (!has_nan && (mu > p.tau || mv > p.tau)) {      // POT: absorb the scalings into the potentials
                 for (int k = threadIdx.x; k < K; k += GENERIC_WG) {
                     alpha[k] += reg * log(u[k]); u[k] = 1.0 / K;
@@ -173,10 +152,10 @@ static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_plan_kerne
                     const double lv = log(v[j]);
                     double s = 0.0;
                     for (int i = lane; i < K; i += 64) s += exp(-(p.M[(size_t)i * K + j] - alpha[i] - beta[j]) / reg + log(u[i]) + lv);
-                    s = wave_tree_sum(s);
+                    s = lanes_sum(s);
                     if (lane == 0) e2 += (s - b[j]) * (s - b[j]);
                 }
-                err = sqrt(block_reduce_sum(e2, red));
+                err = sqrt(block_sum<GENERIC_WAVES>(e2, red));
             }
             if (err <= p.stop_thr) { flags |= 1; break; }
             if (has_nan) {                                      // POT: "Numerical errors": back to the last good iterate
@@ -200,7 +179,7 @@ static __global__ void __launch_bounds__(GENERIC_WG) sinkhorn_generic_plan_kerne
                 val += p.M[t] * exp(-(p.M[t] - alpha[i] - beta[j]) / reg + log(u[i]) + log(v[j]));
             }
         }
-        val = block_reduce_sum(val, red);
+        val = block_sum<GENERIC_WAVES>(val, red);
         if (threadIdx.x == 0) {
             p.emd[q] = val;
             if (p.iters) p.iters[q] = iters;

@@ -9,32 +9,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 constexpr int DM_RED = 256;            // threads of the row-reduction / dot-product workgroups
 constexpr int DM_FIN = 1024;           // threads of the single-workgroup step finish
-
-// fixed-order sum over the workgroup (blockDim.x == NT, a power of two): every thread passes its partial, all get the total
-template <int NT>
-__device__ inline double dm_block_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// fixed-order sum over one wave (64 lanes, butterfly): every lane gets the total
-__device__ inline double dm_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // h[k] = V[k] . w for k < nk: one workgroup (DM_RED threads) per basis vector
 static __global__ void __launch_bounds__(DM_RED) lz_dots_kernel(const double *__restrict__ V, int N, const double *__restrict__ w,
@@ -43,7 +23,7 @@ static __global__ void __launch_bounds__(DM_RED) lz_dots_kernel(const double *__
     const double *vk = V + (size_t)blockIdx.x * N;
     double s = 0.0;
     for (int n = threadIdx.x; n < N; n += DM_RED) s += vk[n] * w[n];
-    s = dm_block_sum<DM_RED>(s, red);
+    s = block_tree_sum<DM_RED>(s, red);
     if (threadIdx.x == 0) h[blockIdx.x] = s;
 }
 
@@ -95,7 +75,7 @@ __device__ inline void lz_restart_into(double *__restrict__ V, int N, int j, dou
             const double *vk = V + (size_t)k * N;
             double t = 0.0;
             for (int n = lane; n < N; n += 64) t += vk[n] * w[n];
-            t = dm_wave_sum(t);
+            t = lanes_sum(t);
             if (lane == 0) hs[k] = t;
         }
         __syncthreads();
@@ -108,7 +88,7 @@ __device__ inline void lz_restart_into(double *__restrict__ V, int N, int j, dou
     }
     double s = 0.0;
     for (int n = threadIdx.x; n < N; n += DM_FIN) s += w[n] * w[n];
-    const double r = sqrt(dm_block_sum<DM_FIN>(s, red));
+    const double r = sqrt(block_tree_sum<DM_FIN>(s, red));
     for (int n = threadIdx.x; n < N; n += DM_FIN) V[(size_t)(j + 1) * N + n] = w[n] / r;
 }
 
@@ -125,7 +105,7 @@ static __global__ void __launch_bounds__(DM_FIN) lz_finish_kernel(double *__rest
     __shared__ double hs[1024];                               // (B <= 1024)
     double s = 0.0;
     for (int n = threadIdx.x; n < N; n += DM_FIN) s += w[n] * w[n];
-    const double b = sqrt(dm_block_sum<DM_FIN>(s, red));
+    const double b = sqrt(block_tree_sum<DM_FIN>(s, red));
     if (threadIdx.x == 0) alpha[j] = h1[j] + h2[j];
     if (b > tol) {
         if (threadIdx.x == 0) beta[j] = b;

@@ -23,6 +23,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 constexpr int LV_WAVE_MAX = 64;        // neighbours a wave stages, one per lane
@@ -71,6 +73,11 @@ __device__ inline double lv_gain(double w, double gamma, double kC, double kX, d
 }
 // is candidate (g1, c1) ahead of (g2, c2)?  c < 0: no candidate
 __device__ inline bool lv_better(double g1, int c1, double g2, int c2) { return c1 >= 0 && (c2 < 0 || g1 > g2 || (g1 == g2 && c1 < c2)); }
+struct LvTake {       // the (value, index) order of reduce.hpp's pair reductions
+    __device__ void operator()(double g2, int c2, double &g, int &C) const {
+        if (lv_better(g2, c2, g, C)) { g = g2; C = c2; }
+    }
+};
 
 __device__ inline void lv_decide(int i, int X, double g, int C, const int *size, int *next, LvCounters *cnt) {
     const bool move = C >= 0 && g > 0.0 && !(size[X] == 1 && size[C] == 1 && C > X);
@@ -130,11 +137,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_wave_kernel(LvGraph G, LvS
     }
     int C = (c >= 0 && c != X) ? c : -1;
     double g = C >= 0 ? lv_gain(w, gamma, kC, kX, G.out[i], G.in[i], S.Out[C], S.In[C], S.Out[X], S.In[X]) : 0.0;
-    for (int off = 32; off > 0; off >>= 1) {
-        const double g2 = __shfl_xor(g, off);
-        const int c2 = __shfl_xor(C, off);
-        if (lv_better(g2, c2, g, C)) { g = g2; C = c2; }
-    }
+    lanes_best(g, C, LvTake{});
     if (lane == 0) lv_decide(i, X, g, C, S.size, next, cnt);
 }
 
@@ -146,13 +149,7 @@ __device__ inline void lv_reduce_decide(int i, int X, double g, int C, const int
     r_g[tid] = g;
     r_c[tid] = C;
     __syncthreads();
-    for (int s = LV_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s && lv_better(r_g[tid + s], r_c[tid + s], r_g[tid], r_c[tid])) {
-            r_g[tid] = r_g[tid + s];
-            r_c[tid] = r_c[tid + s];
-        }
-        __syncthreads();
-    }
+    tree_best<LV_THREADS>(r_g, r_c, LvTake{});
     if (tid == 0) lv_decide(i, X, r_g[0], r_c[0], size, next, cnt);
 }
 

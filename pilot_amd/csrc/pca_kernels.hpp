@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lanczos_kernels.hpp"
+#include "reduce.hpp"
 
 namespace pilot {
 
@@ -40,19 +41,9 @@ constexpr int PCA_START_STREAM = -1;    // the start vector: entry j = lz_restar
 
 __device__ inline double pca_z(double y, double mu, double sg, double maxv) { return fmin((y - mu) / sg, maxv); }
 
-// fixed-order sum over a workgroup of 256: the wave butterfly, then the four wave sums in wave order; every thread gets it
-__device__ inline double pca_block_sum(double v, double *red4) {
-    const double ws = dm_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    const double r = ((red4[0] + red4[1]) + red4[2]) + red4[3];
-    __syncthreads();
-    return r;
-}
-
 // 1 . t from the block sums of pca_sum_kernel (blockDim.x == 256 >= PCA_SUM_BLOCKS)
 __device__ inline double pca_total(const double *__restrict__ part, double *red4) {
-    return pca_block_sum((int)threadIdx.x < PCA_SUM_BLOCKS ? part[threadIdx.x] : 0.0, red4);
+    return block_sum<4>((int)threadIdx.x < PCA_SUM_BLOCKS ? part[threadIdx.x] : 0.0, red4);
 }
 
 // mean / m2 (one group's column moments over n rows) -> mu, sigma, c.  scale == 0: 0, 1, 0.  implicit == 0 (dense): c = 0.
@@ -106,13 +97,13 @@ __global__ void __launch_bounds__(PCA_COL_THREADS) pca_column_pass_kernel(const 
         csval[p] = v;
         s += v;
     }
-    const double sb = pca_block_sum(s, red) / (double)n;
+    const double sb = block_sum<4>(s, red) / (double)n;
     double q = 0.0;
     for (long long p = p0 + threadIdx.x; p < p1; p += PCA_COL_THREADS) {      // (a thread reads back what it wrote itself)
         const double e = csval[p] - sb;
         q = fma(e, e, q);
     }
-    q = pca_block_sum(q, red);
+    q = block_sum<4>(q, red);
     if (threadIdx.x == 0) {
         const long long absent = n - (p1 - p0);
         sbar[j] = sb;
@@ -126,7 +117,7 @@ static __global__ void __launch_bounds__(DM_FIN) pca_dot_kernel(const double *__
     __shared__ double red[DM_FIN];
     double s = 0.0;
     for (int j = threadIdx.x; j < N; j += DM_FIN) s += a[j] * b[j];
-    s = dm_block_sum<DM_FIN>(s, red);
+    s = block_tree_sum<DM_FIN>(s, red);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -138,7 +129,7 @@ static __global__ void __launch_bounds__(DM_FIN) pca_start_kernel(int N, double 
         const double r = lz_restart_entry(j, PCA_START_STREAM);
         s += r * r;
     }
-    const double nrm = sqrt(dm_block_sum<DM_FIN>(s, red));
+    const double nrm = sqrt(block_tree_sum<DM_FIN>(s, red));
     for (int j = threadIdx.x; j < N; j += DM_FIN) V[j] = lz_restart_entry(j, PCA_START_STREAM) / nrm;
 }
 
@@ -154,7 +145,7 @@ static __global__ void __launch_bounds__(64 * PCA_ROW_WAVES) pca_csr_forward_ker
     const long long p1 = indptr[r + 1];
     double s = 0.0;
     for (long long p = indptr[r] + lane; p < p1; p += 64) s += sval[p] * v[sidx[p]];
-    s = dm_wave_sum(s);
+    s = lanes_sum(s);
     if (lane == 0) t[r] = s - dot[0];
 }
 
@@ -165,7 +156,7 @@ static __global__ void __launch_bounds__(256) pca_sum_kernel(const double *__res
     const long long b = (long long)blockIdx.x * chunk, e = min(n, b + chunk);
     double s = 0.0;
     for (long long i = b + threadIdx.x; i < e; i += 256) s += t[i];
-    s = pca_block_sum(s, red);
+    s = block_sum<4>(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -181,7 +172,7 @@ static __global__ void __launch_bounds__(PCA_COL_THREADS) pca_csr_transposed_ker
     const long long p1 = colptr[c + 1];
     double s = 0.0;
     for (long long p = colptr[c] + threadIdx.x; p < p1; p += PCA_COL_THREADS) s += csval[p] * t[rowidx[p]];
-    s = pca_block_sum(s, red);
+    s = block_sum<4>(s, red);
     const double tot = pca_total(part, red);
     if (threadIdx.x == 0) w[j] = s - sbar[j] * tot;
 }
@@ -238,14 +229,7 @@ static __global__ void __launch_bounds__(DM_RED) pca_sign_kernel(double *__restr
     }
     bv[threadIdx.x] = best; bi[threadIdx.x] = at;
     __syncthreads();
-    for (int st = DM_RED / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            const double a = bv[threadIdx.x], b = bv[threadIdx.x + st];
-            const long long ia = bi[threadIdx.x], ib = bi[threadIdx.x + st];
-            if (b > a || (b == a && ib < ia)) { bv[threadIdx.x] = b; bi[threadIdx.x] = ib; }
-        }
-        __syncthreads();
-    }
+    tree_best<DM_RED>(bv, bi, LowestMax{});
     if (bi[0] >= n || !(scores[bi[0] * k + c] < 0.0)) return;  // (uniform over the workgroup; an all-NaN column: no index)
     __syncthreads();                                           // (every thread has read the deciding score before it may flip)
     for (long long i = threadIdx.x; i < n; i += DM_RED) scores[i * k + c] = -scores[i * k + c];
@@ -273,13 +257,13 @@ static __global__ void __launch_bounds__(PCA_COL_THREADS) pca_dense_column_pass_
     const int j = blockIdx.x;
     double s = 0.0;
     for (long long i = threadIdx.x; i < n; i += PCA_COL_THREADS) s += S[i * D + j];
-    const double sb = pca_block_sum(s, red) / (double)n;
+    const double sb = block_sum<4>(s, red) / (double)n;
     double q = 0.0;
     for (long long i = threadIdx.x; i < n; i += PCA_COL_THREADS) {
         const double e = S[i * D + j] - sb;
         q = fma(e, e, q);
     }
-    q = pca_block_sum(q, red);
+    q = block_sum<4>(q, red);
     if (threadIdx.x == 0) {
         sbar[j] = sb;
         ssq[j] = q;
@@ -295,7 +279,7 @@ static __global__ void __launch_bounds__(64 * PCA_ROW_WAVES) pca_dense_forward_k
     const double *row = S + r * D;
     double s = 0.0;
     for (int j = lane; j < D; j += 64) s += row[j] * v[j];
-    s = dm_wave_sum(s);
+    s = lanes_sum(s);
     if (lane == 0) t[r] = s - dot[0];
 }
 

@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 // ---- proportions --------------------------------------------------------------------------------------------
@@ -46,11 +48,7 @@ __global__ void __launch_bounds__(256) count_kernel(const int *__restrict__ cell
             if (ss[i] >= N) ss[i] = -1;
             if (ss[i] >= 0) { smin = ss[i] < smin ? ss[i] : smin; smax = ss[i] > smax ? ss[i] : smax; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int a = __shfl_xor(smin, o, 64), b = __shfl_xor(smax, o, 64);
-            smin = a < smin ? a : smin; smax = b > smax ? b : smax;
-        }
+        lanes_best(smin, smax, [](int a, int b, int &lo, int &hi) { lo = a < lo ? a : lo; hi = b > hi ? b : hi; });     // one butterfly for both
         __syncthreads();                                     // (the previous chunk's flush has read bins / first / red)
         if (lane == 0) { red[wave] = smin; red[4 + wave] = smax; }
         __syncthreads();
@@ -95,8 +93,7 @@ __global__ void __launch_bounds__(256) prior_kernel(const unsigned int *__restri
     if (k >= K) return;
     unsigned long long nk = 0;
     for (int n = lane; n < N; n += 64) nk += counts[(size_t)n * K + k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nk += __shfl_xor(nk, o, 64);
+    nk = lanes_sum(nk);
     if (lane == 0) {
         const double pr = double(nk) / double(n_total - 1);          // :407   n_k / (C - 1)
         prior[k] = pr * regulizer;                                    // :409
@@ -117,8 +114,7 @@ __global__ void __launch_bounds__(256) proportions_kernel(const unsigned int *__
     const double sum_prior = sum_prior_sh;
     unsigned long long r = 0;                               // sum(counts[n]): integers, exact in any order
     for (int k = lane; k < K; k += 64) r += counts[(size_t)n * K + k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+    r = lanes_sum(r);
     const double rs = double(r);
     for (int k = lane; k < K; k += 64) {
         const double c = double(counts[(size_t)n * K + k]);

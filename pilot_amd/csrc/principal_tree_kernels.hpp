@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "knn_kernels.hpp"
+#include "reduce.hpp"
 
 namespace pilot {
 
@@ -133,10 +134,7 @@ __global__ __launch_bounds__(KNN_THREADS, KNN_WAVES) void pt_partition_kernel(co
             }
         }
         if (tid < m) pc[tid] = (c == 0 ? 0 : pc[tid]) + cnt[tid];
-        for (int s = KNN_THREADS / 2; s > 0; s >>= 1) {                          // a fixed tree: the same bits every time
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
+        tree_fold<KNN_THREADS>(red, Sum{});                                      // a fixed tree: the same bits every time
         if (tid == 0) mse += red[0];
         __syncthreads();
     }
@@ -145,17 +143,6 @@ __global__ __launch_bounds__(KNN_THREADS, KNN_WAVES) void pt_partition_kernel(co
 
 // element (i, j <= i) of a packed lower triangle
 __device__ __forceinline__ int pt_tri(int i, int j) { return i * (i + 1) / 2 + j; }
-
-// buf[0] = the sum of buf[0 .. len), added as a fixed tree; every thread of the block calls it
-__device__ inline void pt_tree_sum(double *buf, int len) {
-    int s = 1;
-    while (s < len) s <<= 1;
-    for (s >>= 1; s > 0; s >>= 1) {
-        for (int i = threadIdx.x; i < s; i += blockDim.x)
-            if (i + s < len) buf[i] += buf[i + s];
-        __syncthreads();
-    }
-}
 
 // Candidate blockIdx.x.  S: m x m, centre: D, partials as pt_partition_kernel wrote them over Q blocks.  A fit pass (final_pass = 0)
 // replaces Y / YT by the solution, counts the iteration and sets PT_CONVERGED when max_j |Y'_j - Y_j| / |Y'_j - centre| < eps, or
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(PT_FIN_THREADS) void pt_finish_kernel(int n, int D,
             R[e] = Y[e] * v;
         }
         __syncthreads();
-        pt_tree_sum(R, md);
+        tree_fold(R, md, Sum{});
         if (tid == 0) energy[2 * (size_t)b + 1] = R[0];
         return;
     }

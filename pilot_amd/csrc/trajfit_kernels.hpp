@@ -18,6 +18,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "reduce.hpp"
+
 namespace pilot {
 
 constexpr int TF_WAVES = 8;                       // waves of a workgroup: observation slices
@@ -473,10 +475,7 @@ __global__ void __launch_bounds__(TF_NORM_THREADS) trajfit_normalize_kernel(cons
     for (int j = threadIdx.x; j < n_genes; j += TF_NORM_THREADS) s += (double)row[j];
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = TF_NORM_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    tree_fold<TF_NORM_THREADS>(red, Sum{});
     const double total = red[0];
     const double scale = total > 0.0 ? target_sum / total : 0.0;
     T *o = out + (long long)blockIdx.x * n_cols;

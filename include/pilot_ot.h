@@ -607,6 +607,28 @@ int pilot_ot_knn_smooth(const double *distances, long long n, int k, double *wei
 int pilot_ot_louvain(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
                      int max_levels, int *labels, double *modularity, int *info /* 3 */);
 
+/* ---- Leiden communities (K20): the clustering pilotpy runs on the samples (tools/Trajectory.py:527-588, plot/ploting.py:320-323,
+ * 426-427), as Louvain above with Leiden's refinement under the same SYNCHRONOUS rule (restated in
+ * tests/leiden_restatement.py), so that every returned community is connected in S.  It is not leidenalg: greedy instead of a random
+ * choice, synchronous, and every level restarts from singletons.  Arguments, A, S, Q, the sum orders and the refusals are
+ * pilot_ot_louvain's.  A level: (1) the move phase is a level of pilot_ot_louvain as it is, giving P with the totals OutP, InP; if
+ * every community of P is one node the run ends, the level's nodes are the communities and Q = Qs(level start) / w^2.
+ * (2) Refinement of P.  "Neighbour": a stored neighbour j != i with P_j = P_i.  Fixed for the level, i in X = P_i: e_i = sum S_ij
+ * over its neighbours in stored order, node_ok_i = [w e_i - resolution (out_i (InP_X - in_i) + in_i (OutP_X - out_i)) >= 0].  R starts
+ * as singletons and is swept like the move phase (at most 128 sweeps, kept iff Qs(R_new) - Qs(R_kept) > tol w^2, ended by a sweep
+ * that moves nothing or is discarded).  Per snapshot (R, OutR, InR, sizeR): c_i = sum S_ij over the neighbours with R_j != R_i in
+ * stored order, cut_T = sum of c_i over T's members ascending, sub_ok_T = [w cut_T - resolution (OutR_T (InP_X - InR_T) + InR_T
+ * (OutP_X - OutR_T)) >= 0].  Node i decides only if sizeR[R_i] = 1 and node_ok_i; its candidates are the T != R_i that hold a
+ * neighbour and have sub_ok_T, k_T summed over those neighbours in stored order, g(T) the g above with X = R_i (k_X = 0); largest g,
+ * ties to the lowest T; it moves iff g > 0 and not (sizeR_T = 1 and T > R_i).  Settle: a move into a T of one member stands only
+ * if that member did not itself decide to leave (read from the unsettled decisions, written to a separate array).  Every product
+ * and sum is rounded on its own, in the order written.  (3) If R merged nothing the run ends as in (1); else R's sub-communities
+ * become the next level's nodes by pilot_ot_louvain's aggregation; after level max_levels the run ends there with Q = Qs(R kept) /
+ * w^2.  Only singletons move and a joiner has an edge to a member that stays, so every community is connected whatever the rounding.
+ * Out: labels, *modularity as above; info[0] = levels, info[1] = move sweeps, info[2] = refinement sweeps, info[3] = k. */
+int pilot_ot_leiden(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
+                    int max_levels, int *labels, double *modularity, int *info /* 4 */);
+
 /* ---- silhouette of labelled rows (K18): sklearn.metrics.silhouette_samples of the n rows of X (n x D row-major, X_is_device /
  * dtype / ld as in pilot_ot_knn_rows) under the labels codes[i] in 0 .. n_clusters - 1 -- the score pilotpy's select_best_sil
  * (plot/ploting.py:384-458) takes per resolution, at the cell level.  Neither the n x n distance matrix nor an n x n_clusters table

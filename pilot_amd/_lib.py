@@ -50,7 +50,7 @@ SYMBOLS = [
     "pilot_ot_csr_upload", "pilot_ot_csr_destroy", "pilot_ot_csr_normalize_log1p", "pilot_ot_csr_build_columns", "pilot_ot_csr_slice_rows",
     "pilot_ot_csr_column_nnz", "pilot_ot_csr_group_moments", "pilot_ot_csr_densify",
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
-    "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain",
+    "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain", "pilot_ot_leiden",
     "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
     "pilot_ot_elastic_fit_batch", "pilot_ot_point_moments", "pilot_ot_tree_projection",
     "pilot_ot_multi_create", "pilot_ot_multi_destroy", "pilot_ot_multi_set_inputs", "pilot_ot_multi_sinkhorn",
@@ -187,6 +187,7 @@ def load() -> ctypes.CDLL:
                                     ctypes.c_longlong, ip, dp]
     L.pilot_ot_knn_smooth.argtypes = [dp, ctypes.c_longlong, c_int, dp, dp, dp]
     L.pilot_ot_louvain.argtypes = [ctypes.c_longlong, llp, ip, dp, c_dbl, c_dbl, c_int, ip, dp, ip]
+    L.pilot_ot_leiden.argtypes = [ctypes.c_longlong, llp, ip, dp, c_dbl, c_dbl, c_int, ip, dp, ip]
     L.pilot_ot_silhouette_points.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, ip, c_int, dp, dp]
     L.pilot_ot_silhouette_points_geometry.argtypes = [c_int, c_int, ip, ip]
     L.pilot_ot_elastic_fit_batch.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, dp, dp, dp,

@@ -38,7 +38,7 @@ enum WsSlot {
     WS_PCA_SIDX, WS_PCA_SVAL, WS_PCA_CSVAL, WS_PCA_Y, WS_PCA_S, WS_PCA_PARTW,
     WS_KNN_X, WS_KNN_UNIT, WS_KNN_FLAGS, WS_KNN_BEST_D, WS_KNN_BEST_I, WS_KNN_OUT_D, WS_KNN_OUT_I, WS_KNN_SM_IN, WS_KNN_SM_OUT,   // pilot_ot_knn.hip
     WS_LV_VAL0, WS_LV_VAL1, WS_LV_DEG0, WS_LV_DEG1, WS_LV_IDX0, WS_LV_IDX1, WS_LV_TOT, WS_LV_SUMS, WS_LV_INT, WS_LV_FLAG, WS_LV_ECOMM,   // pilot_ot_louvain.hip
-    WS_LV_NKEYS, WS_LV_EKEYS, WS_LV_CNT,
+    WS_LV_NKEYS, WS_LV_EKEYS, WS_LV_CNT, WS_LD_INT, WS_LD_DBL,                   // (WS_LD_*: the refinement of pilot_ot_leiden)
     WS_SIL_X, WS_SIL_UNIT, WS_SIL_FLAGS, WS_SIL_SORTED, WS_SIL_ORDER, WS_SIL_OFFSETS, WS_SIL_OUT,   // pilot_ot_silhouette_points.hip
     WS_PT_X, WS_PT_FLAGS, WS_PT_Y, WS_PT_YT, WS_PT_S, WS_PT_CENTRE, WS_PT_STATE, WS_PT_ITERS, WS_PT_ENERGY, WS_PT_COUNTS, WS_PT_SUMS,   // pilot_ot_principal_tree.hip
     WS_PT_PCOUNTS, WS_PT_PSUMS, WS_PT_PMSE, WS_PT_PART, WS_PT_OUT,

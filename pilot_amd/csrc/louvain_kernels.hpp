@@ -20,6 +20,13 @@
 // counters.  Every other sum also has one fixed order: community totals over the members ascending (lv_runs_kernel), the two sums
 // of Qs in chunks of LV_CHUNK consecutive entries and then over the chunks (lv_chunk_sums_kernel, lv_qs_kernel), a coarse weight
 // over its fine edges in (row, column) order (lv_coarse_edges_kernel).
+//
+// K20 (Leiden's refinement under the same synchronous rule; DESIGN.md K20, restated in tests/leiden_restatement.py) runs the three
+// move kernels in their CONSTRAINED form, `template <bool CON>` with an LvRefine beside the snapshot: the snapshot is then the
+// refinement R of the move phase's partition `parent`; a node decides only while it is a singleton of R with node_ok, any other
+// writes next[i] = X; a neighbour in another parent community is staged as no neighbour; a candidate without sub_ok is skipped;
+// moves are counted by ld_settle_kernel, not here.  CON = false is K17 as it was: every constrained branch is `if constexpr`.
+// The small kernels of the refinement are at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,6 +63,10 @@ struct LvState {                       // the snapshot of a sweep
     const double *Out, *In;
     const int *size;
 };
+struct LvRefine {                      // K20: what constrains a sweep of the refinement (unread when CON = false)
+    const int *parent;                 // the move phase's community of every node
+    const int *node_ok, *sub_ok;       // per node, fixed for the level; per sub-community id, of this snapshot
+};
 struct LvEdge {                        // an edge of the aggregation's sort: (coarse row << 32 | coarse column, fine edge index)
     lv_u64 key, e;
 };
@@ -79,11 +90,14 @@ struct LvTake {       // the (value, index) order of reduce.hpp's pair reduction
     }
 };
 
-__device__ inline void lv_decide(int i, int X, double g, int C, const int *size, int *next, LvCounters *cnt) {
+template <bool CON> __device__ inline void lv_decide(int i, int X, double g, int C, const int *size, int *next, LvCounters *cnt) {
     const bool move = C >= 0 && g > 0.0 && !(size[X] == 1 && size[C] == 1 && C > X);
     next[i] = move ? C : X;
-    if (move) atomicAdd(&cnt->moved, 1);
+    if constexpr (!CON)
+        if (move) atomicAdd(&cnt->moved, 1);
 }
+// K20: may node i of sub-community X decide in this sweep?
+__device__ inline bool lv_decides(const LvRefine &R, int i, int X, const int *size) { return size[X] == 1 && R.node_ok[i] != 0; }
 
 __global__ void lv_iota_kernel(int *x, int n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -104,8 +118,9 @@ __global__ void lv_bin_kernel(const int *indptr, int m, int wave_max, int wg_max
 
 // ---- the move kernels ---------------------------------------------------------------------------------------------------------
 // four nodes per workgroup, a wave each; a node of another bin is left to that bin's kernel
-__global__ __launch_bounds__(LV_THREADS) void lv_move_wave_kernel(LvGraph G, LvState S, double w, double gamma, int wave_max, int *next,
-                                                                  LvCounters *cnt) {
+template <bool CON>
+__global__ __launch_bounds__(LV_THREADS) void lv_move_wave_kernel(LvGraph G, LvState S, LvRefine R, double w, double gamma, int wave_max,
+                                                                  int *next, LvCounters *cnt) {
     __shared__ int s_c[LV_THREADS / 64][64];
     __shared__ double s_v[LV_THREADS / 64][64];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -122,12 +137,19 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_wave_kernel(LvGraph G, LvS
         const int j = G.col[e0 + lane];
         v = G.val[e0 + lane];
         c = j == node ? -1 : S.comm[j];
+        if constexpr (CON)
+            if (R.parent[j] != R.parent[node]) c = -1;
     }
     s_c[wv][lane] = c;
     s_v[wv][lane] = v;
     __syncthreads();
     if (!mine) return;
     const int i = (int)node, X = S.comm[i];
+    if constexpr (CON)
+        if (!lv_decides(R, i, X, S.size)) {                                    // (the whole wave leaves: one node per wave)
+            if (lane == 0) next[i] = X;
+            return;
+        }
     double kC = 0.0, kX = 0.0;
     for (int q = 0; q < d; ++q) {
         const int cq = s_c[wv][q];
@@ -136,13 +158,15 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_wave_kernel(LvGraph G, LvS
         if (cq == X) kX = __dadd_rn(kX, vq);
     }
     int C = (c >= 0 && c != X) ? c : -1;
+    if constexpr (CON)
+        if (C >= 0 && !R.sub_ok[C]) C = -1;
     double g = C >= 0 ? lv_gain(w, gamma, kC, kX, G.out[i], G.in[i], S.Out[C], S.In[C], S.Out[X], S.In[X]) : 0.0;
     lanes_best(g, C, LvTake{});
-    if (lane == 0) lv_decide(i, X, g, C, S.size, next, cnt);
+    if (lane == 0) lv_decide<CON>(i, X, g, C, S.size, next, cnt);
 }
 
 // the workgroup's best candidate, then the decision
-__device__ inline void lv_reduce_decide(int i, int X, double g, int C, const int *size, int *next, LvCounters *cnt) {
+template <bool CON> __device__ inline void lv_reduce_decide(int i, int X, double g, int C, const int *size, int *next, LvCounters *cnt) {
     __shared__ double r_g[LV_THREADS];
     __shared__ int r_c[LV_THREADS];
     const int tid = threadIdx.x;
@@ -150,15 +174,21 @@ __device__ inline void lv_reduce_decide(int i, int X, double g, int C, const int
     r_c[tid] = C;
     __syncthreads();
     tree_best<LV_THREADS>(r_g, r_c, LvTake{});
-    if (tid == 0) lv_decide(i, X, r_g[0], r_c[0], size, next, cnt);
+    if (tid == 0) lv_decide<CON>(i, X, r_g[0], r_c[0], size, next, cnt);
 }
 
 // a workgroup per listed node; dynamic LDS: 16 B x (the list's largest degree padded to a power of two)
-__global__ __launch_bounds__(LV_THREADS) void lv_move_wg_kernel(LvGraph G, LvState S, double w, double gamma, const int *list, int *next,
-                                                                LvCounters *cnt) {
+template <bool CON>
+__global__ __launch_bounds__(LV_THREADS) void lv_move_wg_kernel(LvGraph G, LvState S, LvRefine R, double w, double gamma, const int *list,
+                                                                int *next, LvCounters *cnt) {
     __shared__ double s_kX;
     const int tid = threadIdx.x;
     const int i = list[blockIdx.x], e0 = G.indptr[i], d = G.indptr[i + 1] - e0, X = S.comm[i];
+    if constexpr (CON)
+        if (!lv_decides(R, i, X, S.size)) {                                    // (the whole workgroup leaves, before any barrier)
+            if (tid == 0) next[i] = X;
+            return;
+        }
     int P = 2;
     while (P < d) P <<= 1;
     lv_u64 *keys = static_cast<lv_u64 *>(lv_dyn_lds());
@@ -168,7 +198,9 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_wg_kernel(LvGraph G, LvSta
         if (p < d) {
             const int j = G.col[e0 + p];
             vals[p] = G.val[e0 + p];
-            if (j != i) key = ((lv_u64)S.comm[j] << 32) | (lv_u64)p;
+            bool neighbour = j != i;
+            if constexpr (CON) neighbour = neighbour && R.parent[j] == R.parent[i];
+            if (neighbour) key = ((lv_u64)S.comm[j] << 32) | (lv_u64)p;
         }
         keys[p] = key;
     }
@@ -193,6 +225,8 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_wg_kernel(LvGraph G, LvSta
             const lv_u64 ck = key >> 32;
             if (((int)ck == X) != (phase == 0)) continue;
             if (p > 0 && (keys[p - 1] >> 32) == ck) continue;
+            if constexpr (CON)
+                if (!R.sub_ok[(int)ck]) continue;
             double k = 0.0;
             for (int q = p; q < d && (keys[q] >> 32) == ck; ++q) k = __dadd_rn(k, vals[(int)(keys[q] & 0xffffffffu)]);
             if (phase == 0) s_kX = k;
@@ -204,21 +238,30 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_wg_kernel(LvGraph G, LvSta
         }
         __syncthreads();
     }
-    lv_reduce_decide(i, X, g, C, S.size, next, cnt);
+    lv_reduce_decide<CON>(i, X, g, C, S.size, next, cnt);
 }
 
 // a workgroup per listed node, the neighbours' communities staged in HBM (ecomm, the node's own stretch of an nnz-long array); the
 // first entry of a community in the row walks the rest of the row for it: O(d^2 / 256) per lane
-__global__ __launch_bounds__(LV_THREADS) void lv_move_long_kernel(LvGraph G, LvState S, double w, double gamma, const int *list, int *ecomm,
-                                                                  int *next, LvCounters *cnt) {
+template <bool CON>
+__global__ __launch_bounds__(LV_THREADS) void lv_move_long_kernel(LvGraph G, LvState S, LvRefine R, double w, double gamma, const int *list,
+                                                                  int *ecomm, int *next, LvCounters *cnt) {
     __shared__ double s_kX;
     const int tid = threadIdx.x;
     const int i = list[blockIdx.x], e0 = G.indptr[i], d = G.indptr[i + 1] - e0, X = S.comm[i];
+    if constexpr (CON)
+        if (!lv_decides(R, i, X, S.size)) {
+            if (tid == 0) next[i] = X;
+            return;
+        }
     int *ec = ecomm + e0;
     const double *val = G.val + e0;
     for (int p = tid; p < d; p += LV_THREADS) {
         const int j = G.col[e0 + p];
-        ec[p] = j == i ? -1 : S.comm[j];
+        int c = j == i ? -1 : S.comm[j];
+        if constexpr (CON)
+            if (R.parent[j] != R.parent[i]) c = -1;
+        ec[p] = c;
     }
     if (tid == 0) s_kX = 0.0;
     __syncthreads();
@@ -228,6 +271,8 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_long_kernel(LvGraph G, LvS
         for (int p = tid; p < d; p += LV_THREADS) {
             const int c = ec[p];
             if (c < 0 || (c == X) != (phase == 0)) continue;
+            if constexpr (CON)
+                if (!R.sub_ok[c]) continue;
             bool head = true;
             for (int q = 0; q < p; ++q)
                 if (ec[q] == c) { head = false; break; }
@@ -243,7 +288,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_move_long_kernel(LvGraph G, LvS
         }
         __syncthreads();
     }
-    lv_reduce_decide(i, X, g, C, S.size, next, cnt);
+    lv_reduce_decide<CON>(i, X, g, C, S.size, next, cnt);
 }
 
 // ---- a bitonic sort in HBM of P = 2^x elements with distinct keys (pads excepted), ascending -------------------------------------------
@@ -416,6 +461,65 @@ __global__ void lv_coarse_edges_kernel(const LvEdge *keys, int nnz, const int *f
     }
     if (p == nnz - 1)
         for (int r = cu + 1; r <= m2; ++r) indptr2[r] = *total;
+}
+
+// ---- K20: the small kernels of the refinement (the sweep itself: the move kernels above with CON = true) -----------------------------
+// is w x - gamma (o (InP - i) + n (OutP - o_)) >= 0, every product and sum rounded on its own, in the order written
+__device__ inline bool ld_well_connected(double w, double gamma, double x, double o, double n, double OutP, double InP) {
+    const double a = __dmul_rn(o, __dadd_rn(InP, -n));
+    const double b = __dmul_rn(n, __dadd_rn(OutP, -o));
+    return __dadd_rn(__dmul_rn(w, x), -__dmul_rn(gamma, __dadd_rn(a, b))) >= 0.0;
+}
+// fixed for the level: e_i = the stored S_ij, j != i, inside i's parent community in stored order, and node_ok_i from it
+__global__ void ld_node_ok_kernel(LvGraph G, const int *parent, const double *OutP, const double *InP, double w, double gamma, int *node_ok) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G.m) return;
+    const int X = parent[i];
+    double e_i = 0.0;
+    for (int e = G.indptr[i]; e < G.indptr[i + 1]; ++e) {
+        const int j = G.col[e];
+        if (j != i && parent[j] == X) e_i = __dadd_rn(e_i, G.val[e]);
+    }
+    node_ok[i] = ld_well_connected(w, gamma, e_i, G.out[i], G.in[i], OutP[X], InP[X]) ? 1 : 0;
+}
+// per snapshot: c_i = the stored S_ij, j != i, inside i's parent community and outside i's sub-community, in stored order
+__global__ void ld_cut_kernel(LvGraph G, const int *parent, const int *sub, double *c) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G.m) return;
+    const int X = parent[i], T = sub[i];
+    double s = 0.0;
+    for (int e = G.indptr[i]; e < G.indptr[i + 1]; ++e) {
+        const int j = G.col[e];
+        if (j != i && parent[j] == X && sub[j] != T) s = __dadd_rn(s, G.val[e]);
+    }
+    c[i] = s;
+}
+// keys: the snapshot's node keys sorted (sub-community << 32 | node), as lv_runs_kernel reads them; cut[T]: lv_runs_kernel's sum of c
+// over T's members.  The thread at a run's head writes sub_ok[T] and, for a T of one member, owner[T]: one writer per entry.  An id
+// without members keeps what the arrays held; nothing reads those.
+__global__ void ld_sub_ok_kernel(const lv_u64 *keys, int m, const int *parent, const double *OutP, const double *InP, LvState S,
+                                 const double *cut, double w, double gamma, int *sub_ok, int *owner) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const lv_u64 ck = keys[p] >> 32;
+    if (p > 0 && (keys[p - 1] >> 32) == ck) return;
+    const int T = (int)ck, member = (int)(keys[p] & 0xffffffffu), X = parent[member];
+    sub_ok[T] = ld_well_connected(w, gamma, cut[T], S.Out[T], S.In[T], OutP[X], InP[X]) ? 1 : 0;
+    if (S.size[T] == 1) owner[T] = member;
+}
+// raw: the sweep's unsettled decisions.  A move into a sub-community of one member stands only if that member did not itself
+// decide to leave; next is a separate array (settling in place would race with the reads of raw); counts the moves that stand
+__global__ void ld_settle_kernel(int m, const int *sub, const int *size, const int *owner, const int *raw, int *next, LvCounters *cnt) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int X = sub[i];
+    int T = raw[i];
+    if (T != X && size[T] == 1) {
+        const int j = owner[T];
+        if (raw[j] != sub[j]) T = X;
+    }
+    next[i] = T;
+    if (T != X) atomicAdd(&cnt->moved, 1);
 }
 
 }  // namespace pilot

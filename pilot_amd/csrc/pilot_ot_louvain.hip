@@ -1,6 +1,7 @@
 // C ABI of the Louvain communities (include/pilot_ot.h, section "Louvain communities"; kernels and the rule: louvain_kernels.hpp).
 // The host forms S = A + A^T once (transpose by counting sort, then a merge) and renumbers the labels at the end; everything
-// between the two runs on the device: a level uploads nothing and brings back only its counters.
+// between the two runs on the device: a level uploads nothing and brings back only its counters.  pilot_ot_leiden (K20) is the same
+// run with a refinement between a level's move phase and its aggregation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +20,7 @@ namespace {
 using pilot::LvCounters;
 using pilot::LvEdge;
 using pilot::LvGraph;
+using pilot::LvRefine;
 using pilot::LvState;
 using pilot::lv_u64;
 
@@ -131,8 +133,9 @@ struct Totals {                        // community totals of one assignment
     int *size;
 };
 
-int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int wave_max, int wg_max, int *labels, double *modularity,
-        int *info) {
+// info: levels, sweeps, communities; with `leiden` levels, move sweeps, refinement sweeps, communities
+int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int wave_max, int wg_max, bool leiden, int *labels,
+        double *modularity, int *info) {
     const int nnz0 = h.indptr[n];
     const long big = std::max<long>(n, nnz0) + 1;
     const int chunks0 = (n + pilot::LV_CHUNK - 1) / pilot::LV_CHUNK;
@@ -159,6 +162,16 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
     HIP_TRY(pilot::ws(pilot::WS_LV_NKEYS, (size_t)pow2_at_least(n), &nkeys));
     HIP_TRY(pilot::ws(pilot::WS_LV_EKEYS, (size_t)pow2_at_least(nnz0), &ekeys));
     HIP_TRY(pilot::ws(pilot::WS_LV_CNT, 1, &cnt));
+    // K20: the move phase's partition and its totals, kept while its refinement runs through comm / next / kept / fresh
+    int *parent = nullptr, *node_ok = nullptr, *sub_ok = nullptr, *owner = nullptr, *raw = nullptr, *spare_size = nullptr;
+    double *OutP = nullptr, *InP = nullptr, *cut_node = nullptr, *cut = nullptr, *spare_sum = nullptr;
+    if (leiden) {
+        HIP_TRY(pilot::ws(pilot::WS_LD_INT, 6 * (size_t)n, &parent));
+        HIP_TRY(pilot::ws(pilot::WS_LD_DBL, 5 * (size_t)n, &OutP));
+        node_ok = parent + n, sub_ok = parent + 2 * (size_t)n, owner = parent + 3 * (size_t)n, raw = parent + 4 * (size_t)n;
+        spare_size = parent + 5 * (size_t)n;
+        InP = OutP + n, cut_node = OutP + 2 * (size_t)n, cut = OutP + 3 * (size_t)n, spare_sum = OutP + 4 * (size_t)n;
+    }
     int *comm = ints, *next = ints + n, *label = ints + 4 * (size_t)n, *wg_list = ints + 5 * (size_t)n, *long_list = ints + 6 * (size_t)n;
     Totals kept{tot, tot + n, ints + 2 * (size_t)n}, fresh{tot + 2 * (size_t)n, tot + 3 * (size_t)n, ints + 3 * (size_t)n};
     double *internal = sums, *prod = sums + n, *part_x = sums + 2 * (size_t)n, *part_y = part_x + chunks0;
@@ -173,12 +186,17 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
 
     const double w = h.w, w2 = w * w;
     const size_t wg_lds_max = 16 * (size_t)pow2_at_least(wg_max);
-    if (wg_lds_max > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::lv_move_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)wg_lds_max));
-    int m = n, nnz = nnz0, cur = 0, levels = 0, sweeps = 0;
+    if (wg_lds_max > 64 * 1024) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::lv_move_wg_kernel<false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_max));
+        if (leiden)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::lv_move_wg_kernel<true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_max));
+    }
+    int m = n, nnz = nnz0, cur = 0, levels = 0, sweeps = 0, refine_sweeps = 0;
     double qs_kept = 0.0;
     LvCounters hc;
+    const LvRefine no_refine{nullptr, nullptr, nullptr};
 
     // community totals of the assignment c into t, and its Qs into cnt->qs
     auto judge = [&](const LvGraph &G, const int *c, const Totals &t) -> int {
@@ -208,17 +226,18 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
         const int n_wg = hc.n_wg, n_long = hc.n_long;
         const size_t wg_lds = 16 * (size_t)pow2_at_least(hc.max_wg_degree);
         ++levels;
+        const double qs_start = qs_kept;
         for (int s = 0; s < pilot::LV_MAX_SWEEPS; ++s) {
             const LvState S{comm, kept.Out, kept.In, kept.size};
             HIP_TRY(hipMemsetAsync(&cnt->moved, 0, sizeof(int), nullptr));
-            hipLaunchKernelGGL(pilot::lv_move_wave_kernel, dim3(blocks_for(m, pilot::LV_THREADS / 64)), dim3(pilot::LV_THREADS), 0, nullptr, G, S, w,
-                               gamma, wave_max, next, cnt);
+            hipLaunchKernelGGL(pilot::lv_move_wave_kernel<false>, dim3(blocks_for(m, pilot::LV_THREADS / 64)), dim3(pilot::LV_THREADS), 0, nullptr,
+                               G, S, no_refine, w, gamma, wave_max, next, cnt);
             if (n_wg > 0)
-                hipLaunchKernelGGL(pilot::lv_move_wg_kernel, dim3((unsigned)n_wg), dim3(pilot::LV_THREADS), wg_lds, nullptr, G, S, w, gamma, wg_list,
-                                   next, cnt);
+                hipLaunchKernelGGL(pilot::lv_move_wg_kernel<false>, dim3((unsigned)n_wg), dim3(pilot::LV_THREADS), wg_lds, nullptr, G, S, no_refine,
+                                   w, gamma, wg_list, next, cnt);
             if (n_long > 0)
-                hipLaunchKernelGGL(pilot::lv_move_long_kernel, dim3((unsigned)n_long), dim3(pilot::LV_THREADS), 0, nullptr, G, S, w, gamma, long_list,
-                                   ecomm, next, cnt);
+                hipLaunchKernelGGL(pilot::lv_move_long_kernel<false>, dim3((unsigned)n_long), dim3(pilot::LV_THREADS), 0, nullptr, G, S, no_refine,
+                                   w, gamma, long_list, ecomm, next, cnt);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
             ++sweeps;
@@ -231,6 +250,52 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
             std::swap(kept, fresh);
         }
 
+        if (leiden) {
+            // every community of the move phase one node: the run ends, the level's nodes are the communities
+            hipLaunchKernelGGL(pilot::lv_alive_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, kept.size, m, flag);
+            hipLaunchKernelGGL(pilot::lv_scan_kernel, dim3(1), dim3(1024), 0, nullptr, flag, pos, (long)m, &cnt->coarse_m);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+            qs_kept = qs_start;
+            if (hc.coarse_m == m) break;
+            // the refinement: the move phase's partition becomes the constraint, and the same loop runs from singletons again
+            HIP_TRY(hipMemcpyAsync(parent, comm, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(OutP, kept.Out, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(InP, kept.In, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
+            hipLaunchKernelGGL(pilot::ld_node_ok_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G, parent, OutP, InP, w, gamma, node_ok);
+            hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, comm, m);
+            if (int rc = judge(G, comm, kept)) return rc;                       // (leaves the sorted node keys of comm in nkeys)
+            const LvRefine R{parent, node_ok, sub_ok};
+            for (int s = 0; s < pilot::LV_MAX_SWEEPS; ++s) {
+                const LvState S{comm, kept.Out, kept.In, kept.size};
+                HIP_TRY(hipMemsetAsync(&cnt->moved, 0, sizeof(int), nullptr));
+                hipLaunchKernelGGL(pilot::ld_cut_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G, parent, comm, cut_node);
+                hipLaunchKernelGGL(pilot::lv_runs_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, nkeys, m, cut_node, cut_node, cut, spare_sum,
+                                   spare_size);
+                hipLaunchKernelGGL(pilot::ld_sub_ok_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, nkeys, m, parent, OutP, InP, S, cut, w, gamma,
+                                   sub_ok, owner);
+                hipLaunchKernelGGL(pilot::lv_move_wave_kernel<true>, dim3(blocks_for(m, pilot::LV_THREADS / 64)), dim3(pilot::LV_THREADS), 0,
+                                   nullptr, G, S, R, w, gamma, wave_max, raw, cnt);
+                if (n_wg > 0)
+                    hipLaunchKernelGGL(pilot::lv_move_wg_kernel<true>, dim3((unsigned)n_wg), dim3(pilot::LV_THREADS), wg_lds, nullptr, G, S, R, w,
+                                       gamma, wg_list, raw, cnt);
+                if (n_long > 0)
+                    hipLaunchKernelGGL(pilot::lv_move_long_kernel<true>, dim3((unsigned)n_long), dim3(pilot::LV_THREADS), 0, nullptr, G, S, R, w,
+                                       gamma, long_list, ecomm, raw, cnt);
+                hipLaunchKernelGGL(pilot::ld_settle_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, m, comm, kept.size, owner, raw, next, cnt);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+                ++refine_sweeps;
+                if (hc.moved == 0) break;
+                if (int rc = judge(G, next, fresh)) return rc;
+                HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+                if (!(hc.qs - qs_kept > tol * w2)) break;
+                qs_kept = hc.qs;
+                std::swap(comm, next);
+                std::swap(kept, fresh);
+            }
+        }
+
         // aggregation: surviving ids ranked ascending
         int *rank = pos;
         hipLaunchKernelGGL(pilot::lv_alive_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, kept.size, m, flag);
@@ -239,6 +304,7 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
         const int m2 = hc.coarse_m;
+        if (leiden && m2 == m) qs_kept = qs_start;                              // the refinement merged nothing: the run ends as above
         if (m2 == m || levels == max_levels) break;
         const DeviceLevel &nx = lev[cur ^ 1];
         const long P = pow2_at_least(nnz);
@@ -261,15 +327,16 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
     HIP_TRY(hipMemcpy(labels, label, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     info[0] = levels;
     info[1] = sweeps;
-    info[2] = renumber(n, labels);
+    if (leiden) info[2] = refine_sweeps;
+    info[leiden ? 3 : 2] = renumber(n, labels);
     *modularity = qs_kept / w2;
     return PILOT_OT_OK;
 }
 
-}  // namespace
-
-PILOT_API int pilot_ot_louvain(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
-                               int max_levels, int *labels, double *modularity, int *info) {
+// both entry points: the argument checks, the n = 0 and w = 0 cases and the refusals, all before any HIP call; then the run
+int communities(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol, int max_levels,
+                bool leiden, int *labels, double *modularity, int *info) {
+    const int k_slot = leiden ? 3 : 2;
     if (!indptr || !indices || !weights || !labels || !modularity || !info) return fail(PILOT_OT_EINVAL, "NULL pointer");
     if (n < 0) return fail(PILOT_OT_EINVAL, "n=%lld nodes", n);
     if (!std::isfinite(resolution) || resolution < 0.0) return fail(PILOT_OT_EINVAL, "resolution=%g must be finite and not negative", resolution);
@@ -285,7 +352,7 @@ PILOT_API int pilot_ot_louvain(long long n, const long long *indptr, const int *
             if (!(weights[e] >= 0.0) || std::isinf(weights[e]))
                 return fail(PILOT_OT_EINVAL, "weights[%lld]=%g (row %lld, column %d) must be finite and not negative", e, weights[e], i, indices[e]);
         }
-    info[0] = info[1] = info[2] = 0;
+    for (int s = 0; s <= k_slot; ++s) info[s] = 0;
     *modularity = 0.0;
     if (n == 0) return PILOT_OT_OK;
 
@@ -300,7 +367,7 @@ PILOT_API int pilot_ot_louvain(long long n, const long long *indptr, const int *
     if (!std::isfinite(h.w * h.w)) return fail(PILOT_OT_EINVAL, "the squared total weight %g^2 overflows", h.w);
     if (h.w == 0.0) {                                                           // no weight: every node its own community, Q = 0
         for (long long i = 0; i < n; ++i) labels[i] = (int)i;
-        info[2] = (int)n;
+        info[k_slot] = (int)n;
         return PILOT_OT_OK;
     }
     int wave_max = pilot::LV_WAVE_MAX, wg_max = pilot::LV_WG_MAX;
@@ -311,5 +378,17 @@ PILOT_API int pilot_ot_louvain(long long n, const long long *indptr, const int *
             wg_max = std::min(std::max(b, wave_max), pilot::LV_WG_MAX);
         }
     }
-    return run((int)n, h, resolution, tol, max_levels, wave_max, wg_max, labels, modularity, info);
+    return run((int)n, h, resolution, tol, max_levels, wave_max, wg_max, leiden, labels, modularity, info);
+}
+
+}  // namespace
+
+PILOT_API int pilot_ot_louvain(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
+                               int max_levels, int *labels, double *modularity, int *info) {
+    return communities(n, indptr, indices, weights, resolution, tol, max_levels, false, labels, modularity, info);
+}
+
+PILOT_API int pilot_ot_leiden(long long n, const long long *indptr, const int *indices, const double *weights, double resolution, double tol,
+                              int max_levels, int *labels, double *modularity, int *info) {
+    return communities(n, indptr, indices, weights, resolution, tol, max_levels, true, labels, modularity, info);
 }

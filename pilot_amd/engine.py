@@ -1321,6 +1321,35 @@ def louvain(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
     return labels
 
 
+# ---- Leiden communities (K20; sc.tl.leiden of pilotpy's Clustering, clustering_emd and select_best_sil, by K17's synchronous rule) ---
+def leiden(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
+    """K20: Leiden communities of a weighted graph on the device (include/pilot_ot.h, "Leiden communities"): every level is a
+    level of :func:`louvain` followed by Leiden's refinement of its partition under the same synchronous rule, and the refined
+    sub-communities become the next level's nodes.  EVERY RETURNED COMMUNITY IS CONNECTED in A + A^T, which :func:`louvain` does
+    not promise; the modularity is about the same.  Deterministic, no seed, the same bits from every call.  It is
+    not leidenalg: greedy where leidenalg draws at random, synchronous, and every level restarts from singletons, so the labels
+    are not leidenalg's.  ``graph``, ``resolution``, ``tol``, ``max_levels``, the labels and the ValueErrors before any device
+    work are :func:`louvain`'s; with ``return_info`` ``(labels, dict(modularity, levels, move_sweeps, refine_sweeps,
+    communities))``."""
+    indptr, indices, data, n = _louvain_args(graph, resolution, tol, max_levels)
+    labels, q, info = np.empty(n, dtype=np.int32), ctypes.c_double(0.0), np.zeros(4, dtype=np.int32)
+    _lib.check(_lib.load().pilot_ot_leiden(n, _lib.lptr(indptr), _lib.iptr(indices), _lib.dptr(data), float(resolution), float(tol),
+                                           int(max_levels), _lib.iptr(labels), ctypes.byref(q), _lib.iptr(info)))
+    if return_info:
+        return labels, {"modularity": q.value, "levels": int(info[0]), "move_sweeps": int(info[1]), "refine_sweeps": int(info[2]),
+                        "communities": int(info[3])}
+    return labels
+
+
+def check_clustering_method(method):
+    """the engine call ``method`` names (``"louvain"`` or ``"leiden"``); ValueError for anything else"""
+    if method == "louvain":
+        return louvain
+    if method == "leiden":
+        return leiden
+    raise ValueError("method=%r: 'louvain' or 'leiden'" % (method,))
+
+
 # ---- silhouette of labelled points (K18; the score pilotpy's select_best_sil takes per resolution, at the cell level) -------------
 def silhouette_geometry(D, dtype=np.float32):
     """``(queries per block, corpus rows per staged tile)`` of :func:`silhouette_samples` for ``D`` columns of ``dtype``."""

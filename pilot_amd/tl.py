@@ -36,10 +36,13 @@ pca, extract_annot_expression                  Trajectory.py:171-228 (scanpy's n
 neighbors                                      Trajectory.py:217-220, 1045-1060 (scanpy's pp.neighbors: the exact kNN graph of the
                                                cells and UMAP's connectivities restated)
 louvain, reclustering_data                     Trajectory.py:217-220, 1000-1062 (sknetwork's Louvain(resolution) of the neighbour
-                                               graph by a synchronous, deterministic rule; no Leiden, so no tl.Clustering and
-                                               no return_sil_ari)
+                                               graph by a synchronous, deterministic rule)
+leiden, leiden_clustering, sil_ari                  Trajectory.py:527-588, 107-113 (sc.tl.leiden by the synchronous rule of DESIGN.md
+                                               K20: connected communities, labels unpinned; the resolution loop and the Rand index
+                                               of Clustering; the tail of return_sil_ari=True, which itself stays as it was)
 select_best_sil, clustering_emd                plot/ploting.py:384-458, 287-354 (the silhouette sweep over resolutions and the
-                                               samples' Predicted_Labels, without plots or files; Louvain instead of Leiden)
+                                               samples' Predicted_Labels, without plots or files; Louvain by default,
+                                               method="leiden" for the reference's choice)
 select_best_resolution, silhouette             the same sweep over cells, on the matrix-free silhouette (not in the reference)
 =============================================  ==========================================
 """
@@ -983,10 +986,22 @@ def louvain(adata, resolution=1.0, mode="connectivities", neighbors_key=None, ke
     wrote), writes ``adata.obs[key_added]`` as a pandas Categorical of the strings ``"0" .. "k-1"`` (scanpy's convention; 0 is the
     largest community) and ``adata.uns[key_added] = {'params': {'resolution', 'mode'}, 'modularity': Q}``.  Returns None.  A
     missing graph raises ValueError naming ``tl.neighbors``.  The rule is synchronous and deterministic, not
-    sknetwork's or scanpy's sequential, seeded sweep: where the node order decides, the labels differ from theirs.  Leiden is not
-    offered."""
+    sknetwork's or scanpy's sequential, seeded sweep: where the node order decides, the labels differ from theirs.  Leiden is
+    :func:`leiden`."""
     graph = _neighbor_graph(adata, mode, neighbors_key)
     labels, info = engine.louvain(graph, resolution=resolution, return_info=True)
+    k = info["communities"]
+    adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=[str(c) for c in range(k)])
+    adata.uns[key_added] = {"params": {"resolution": resolution, "mode": mode}, "modularity": info["modularity"]}
+
+
+def leiden(adata, resolution=1.0, mode="connectivities", neighbors_key=None, key_added="leiden"):
+    """:func:`louvain` with ``engine.leiden`` in place of ``engine.louvain``: the same graph, the same
+    ``adata.obs[key_added]`` Categorical and ``adata.uns[key_added] = {'params': {'resolution', 'mode'}, 'modularity': Q}``, but
+    every community is connected in the graph.  Synchronous and deterministic, not leidenalg's seeded random refinement: the labels
+    are not scanpy's ``tl.leiden`` labels.  Returns None."""
+    graph = _neighbor_graph(adata, mode, neighbors_key)
+    labels, info = engine.leiden(graph, resolution=resolution, return_info=True)
     k = info["communities"]
     adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=[str(c) for c in range(k)])
     adata.uns[key_added] = {"params": {"resolution": resolution, "mode": mode}, "modularity": info["modularity"]}
@@ -1070,11 +1085,12 @@ def _best_resolution(resolutions, scores, start):
     return best_res
 
 
-def _sweep(adata, resolutions, start, graph, score):
-    """one Louvain run and one ``score(labels)`` per resolution; a labelling with one cluster, or one cluster per point, scores NaN"""
+def _sweep(adata, resolutions, start, graph, score, cluster=engine.louvain):
+    """one ``cluster`` run (engine.louvain or engine.leiden) and one ``score(labels)`` per resolution; a labelling with one
+    cluster, or one cluster per point, scores NaN"""
     n, rows = graph.shape[0], []
     for res in resolutions:
-        labels, info = engine.louvain(graph, resolution=res, return_info=True)
+        labels, info = cluster(graph, resolution=res, return_info=True)
         k = info["communities"]
         rows.append((res, score(labels) if 2 <= k <= n - 1 else np.nan, k, info["modularity"]))
     frame = pd.DataFrame(rows, columns=_SWEEP_COLUMNS)
@@ -1098,7 +1114,7 @@ def silhouette(adata, labels_key="louvain", use_rep="X_pca", n_pcs=None, metric=
 
 
 def select_best_resolution(adata, resolutions=None, start=0.2, step=0.1, end=2, mode="connectivities", neighbors_key=None,
-                           use_rep="X_pca", n_pcs=None, metric="euclidean"):
+                           use_rep="X_pca", n_pcs=None, metric="euclidean", method="louvain"):
     """:func:`select_best_sil` at the cell level: for every resolution, ``engine.louvain`` of the graph :func:`neighbors` left in
     ``adata.obsp`` (``mode``, ``neighbors_key`` as in :func:`louvain`) and the mean of ``engine.silhouette_samples`` (K18) of
     the cells' rows of ``adata.obsm[use_rep]`` (its first ``n_pcs`` columns) under those labels.  The resolution list and the
@@ -1106,15 +1122,17 @@ def select_best_resolution(adata, resolutions=None, start=0.2, step=0.1, end=2, 
     modularity`` and writes ``adata.uns['best_res']``; it writes no labels: call ``tl.louvain(adata, resolution=best_res)`` next.
     Every resolution costs one Louvain run plus one all-pairs pass over the cells (19 of each by default): the distances are
     recomputed, not kept, since cells x cells of them do not fit.  A labelling with one cluster, or one cluster per cell, gets NaN
-    and is never best.  ValueError before any device work: a missing graph or representation, an unknown metric."""
+    and is never best.  ``method="leiden"`` clusters with ``engine.leiden`` (K20) instead.  ValueError before any device work: a
+    missing graph or representation, an unknown metric or method."""
     _metric_checked(metric)
+    cluster = engine.check_clustering_method(method)
     resolutions = _resolution_list(resolutions, start, step, end)
     graph = _neighbor_graph(adata, mode, neighbors_key)
     X = _representation(adata, use_rep, n_pcs)
     if X.shape[0] != graph.shape[0]:
         raise ValueError("the graph has %d cells, adata.obsm[%r] %d" % (graph.shape[0], use_rep, X.shape[0]))
     return _sweep(adata, resolutions, start, graph,
-                  lambda labels: engine.silhouette_samples(X, labels, metric=metric, return_score=True)[1])
+                  lambda labels: engine.silhouette_samples(X, labels, metric=metric, return_score=True)[1], cluster)
 
 
 _EMD_NEIGHBORS = 15          # scanpy's pp.neighbors default, which the reference takes for the samples
@@ -1138,7 +1156,7 @@ def _emd_graph(E, metric):
     return engine.knn_connectivities(indices, distances, _EMD_NEIGHBORS)
 
 
-def select_best_sil(adata, resolutions=None, metric="cosine", start=0.2, step=0.1, end=2):
+def select_best_sil(adata, resolutions=None, metric="cosine", start=0.2, step=0.1, end=2, method="louvain"):
     """The numerical core of the reference's ``pl.select_best_sil`` (plot/ploting.py:384-458; no plots, no files): the silhouette
     of the samples' clustering at every resolution, and the best resolution in ``adata.uns['best_res']``.  Returns a frame with
     the columns ``resolution, silhouette, n_clusters, modularity``.
@@ -1155,14 +1173,17 @@ def select_best_sil(adata, resolutions=None, metric="cosine", start=0.2, step=0.
     unpinned, as everywhere in K17); the rows themselves are used (scanpy silently reduces them to 50 principal components when
     there are more than 50 samples); a non-empty ``resolutions`` is honoured (the reference overwrites its argument); a labelling
     with one cluster, or one cluster per sample, gets silhouette NaN and can never be best (the reference crashes inside
-    scikit-learn).  ValueError before any device work: no ``uns['EMD']``, an unknown metric, fewer than 15 samples."""
+    scikit-learn).  ``method="leiden"`` clusters with ``engine.leiden`` (K20: Leiden by the synchronous rule, every group connected
+    in the graph; still not leidenalg's labels).  ValueError before any device work: no ``uns['EMD']``, an unknown metric or
+    method, fewer than 15 samples."""
+    cluster = engine.check_clustering_method(method)
     E = _emd_points(adata, metric)
     resolutions = _resolution_list(resolutions, start, step, end)
     return _sweep(adata, resolutions, start, _emd_graph(E, metric),
-                  lambda labels: engine.silhouette_of_rows(E, labels, metric=metric))
+                  lambda labels: engine.silhouette_of_rows(E, labels, metric=metric), cluster)
 
 
-def clustering_emd(adata, res=0.3, metric="cosine"):
+def clustering_emd(adata, res=0.3, metric="cosine", method="louvain"):
     """The numerical core of the reference's ``pl.clustering_emd`` (plot/ploting.py:287-354; no heat map): the sub-groups of the
     samples at resolution ``res``.  Returns the reference's ``proportion_df``: one row per sample (``uns['proportions']`` order),
     the columns ``uns['annot'].cell_type.unique()``, then ``Predicted_Labels`` (the strings "0" .. "k-1", 0 the largest group, as
@@ -1178,8 +1199,10 @@ def clustering_emd(adata, res=0.3, metric="cosine"):
 
     Deviations from pilotpy: those of :func:`select_best_sil` (Louvain by K17's synchronous rule instead of Leiden, labels
     unpinned; the rows themselves instead of 50 principal components; NaN for a labelling of one cluster or of one per sample).
-    ValueError before any device work: no ``uns['EMD']`` / ``['proportions']`` / ``['annot']``, an unknown metric, fewer than 15
-    samples, proportions that do not match EMD or the cell types."""
+    ``method="leiden"`` clusters with ``engine.leiden`` (K20) and is recorded as ``params['method']``; the default leaves ``params``
+    as it was.  ValueError before any device work: no ``uns['EMD']`` / ``['proportions']`` / ``['annot']``, an unknown metric or
+    method, fewer than 15 samples, proportions that do not match EMD or the cell types."""
+    cluster = engine.check_clustering_method(method)
     E = _emd_points(adata, metric)
     for key in ("proportions", "annot"):
         if key not in adata.uns:
@@ -1191,14 +1214,104 @@ def clustering_emd(adata, res=0.3, metric="cosine"):
     if proportion_df.shape != (E.shape[0], len(cell_types)):
         raise ValueError("uns['proportions'] is %d samples x %d cell types, uns['EMD'] has %d samples and uns['annot'] %d cell types"
                          % (proportion_df.shape + (E.shape[0], len(cell_types))))
-    labels, info = engine.louvain(_emd_graph(E, metric), resolution=res, return_info=True)
+    labels, info = cluster(_emd_graph(E, metric), resolution=res, return_info=True)
     k = info["communities"]
     sil = engine.silhouette_of_rows(E, labels, metric=metric, normalize_by_max=True) if 2 <= k <= E.shape[0] - 1 else np.nan
     adata.uns["clustering_emd"] = {"params": {"res": res, "metric": metric}, "silhouette": sil, "modularity": info["modularity"]}
+    if method != "louvain":
+        adata.uns["clustering_emd"]["params"]["method"] = method
     proportion_df.columns = cell_types
     proportion_df["Predicted_Labels"] = np.array([str(c) for c in labels], dtype=object)
     proportion_df["sampleID"] = list(proportions.keys())
     return proportion_df
+
+
+# ---- the samples' Leiden clusters against their statuses (Trajectory.py:527-588: Clustering; :107-113: return_sil_ari's tail) ---
+def rand_index(labels_true, labels_pred):
+    """``sklearn.metrics.rand_score``: the share of the pairs of points on which two labellings agree (together in both or apart in
+    both), from the contingency table; 1.0 for fewer than two points.  It is the plain Rand index, not the adjusted one."""
+    a, b = np.asarray(labels_true).ravel(), np.asarray(labels_pred).ravel()
+    if a.shape != b.shape:
+        raise ValueError("labels_true has %d entries, labels_pred %d" % (a.size, b.size))
+    n = a.size
+    if n < 2:
+        return 1.0
+    ia, ib = np.unique(a, return_inverse=True)[1], np.unique(b, return_inverse=True)[1]
+    table = np.zeros((int(ia.max()) + 1, int(ib.max()) + 1), dtype=np.int64)
+    np.add.at(table, (ia, ib), 1)
+
+    def together(counts):                          # the pairs inside the cells / rows / columns of the table
+        return int((counts * (counts - 1) // 2).sum())
+    pairs = n * (n - 1) // 2
+    return float(pairs + 2 * together(table) - together(table.sum(axis=1)) - together(table.sum(axis=0))) / float(pairs)
+
+
+def leiden_clustering(EMD, df, category="status", sample_col=1, res=0.01, metric="cosine", steper=0.01, max_steps=1000):
+    """The reference's ``Clustering`` (Trajectory.py:527-588) under a name of its own -- ``wasserstein_distance(return_sil_ari=True)``
+    is pinned to the REFERENCE's function of that name, and ``tl`` keeps the name free for it: Leiden clusters of the samples, as many as there are statuses, and
+    their Rand index against the statuses.  Points: the rows of ``EMD`` (callers pass ``EMD / EMD.max()``).  Graph: the one of
+    :func:`select_best_sil` (``engine.knn(EMD, 14, metric)``, ``engine.knn_connectivities(.., 15)``; fewer than 15 samples raise
+    ValueError), formed once.  The reference's loop on it with ``engine.leiden`` (K20): ``res += steper`` while there are fewer
+    clusters than ``df[category].unique()``, ``res -= 0.001`` while there are more, stop at equality.  Returns ``(labels,
+    rand_index, true_labels)``: the integer labels, :func:`rand_index` of them against ``true_labels`` (what the reference calls
+    ARI is ``rand_score``, the plain Rand index), and the first ``category`` value of every sample in first-appearance order
+    (:func:`return_real_labels`).  Deviations from pilotpy: Leiden by the synchronous rule (labels unpinned); ``category`` where
+    the reference reads ``df.status``; the reference's loop can oscillate for ever, here ``max_steps`` steps without equality
+    raise ValueError naming the last two resolutions and cluster counts, and so does a resolution that falls below 0.
+    ValueError before any device work: ``EMD`` not square or not matching the samples, a missing column, an unknown metric,
+    ``res`` negative or not finite, ``steper`` not positive, ``max_steps < 1``, fewer than 15 samples."""
+    _metric_checked(metric)
+    E = np.ascontiguousarray(EMD, dtype=np.float64)
+    if E.ndim != 2 or E.shape[0] != E.shape[1]:
+        raise ValueError("EMD must be samples x samples, got %s" % (E.shape,))
+    if category not in df.columns:
+        raise ValueError("df has no column %r" % (category,))
+    if isinstance(sample_col, bool) or not isinstance(sample_col, (int, np.integer)) or not -len(df.columns) <= sample_col < len(df.columns):
+        raise ValueError("sample_col=%r: the position of the sample column among %d" % (sample_col, len(df.columns)))
+    engine.check_resolution(res)
+    if isinstance(steper, bool) or not isinstance(steper, (int, float, np.integer, np.floating)) or not np.isfinite(steper) or steper <= 0:
+        raise ValueError("steper=%r: a positive number" % (steper,))
+    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 1:
+        raise ValueError("max_steps=%r: an integer of at least 1" % (max_steps,))
+    first_rows = ~df[df.columns[sample_col]].duplicated().to_numpy()           # (what return_real_labels returns, without the library)
+    true_labels = list(df[category].to_numpy()[first_rows])
+    if len(true_labels) != E.shape[0]:
+        raise ValueError("EMD has %d samples, df[%r] %d" % (E.shape[0], df.columns[sample_col], len(true_labels)))
+    if E.shape[0] < _EMD_NEIGHBORS:
+        raise ValueError("%d samples: the neighbour graph of scanpy's defaults needs n_neighbors = %d of them" % (E.shape[0], _EMD_NEIGHBORS))
+    n_clust = len(df[category].unique())
+    graph = _emd_graph(E, metric)
+    res, seen = float(res), []
+    for _ in range(int(max_steps)):
+        if res < 0:
+            raise ValueError("the resolution fell to %g with %d clusters for %d statuses (before it: resolution %g)"
+                             % (res, seen[-1][1], n_clust, seen[-1][0]))
+        labels, info = engine.leiden(graph, resolution=res, return_info=True)
+        k = info["communities"]
+        seen = seen[-1:] + [(res, k)]
+        if k < n_clust:
+            res = res + steper
+        elif k > n_clust:
+            res = res - 0.001
+        else:
+            return labels.astype(int), rand_index(true_labels, labels), true_labels
+    raise ValueError("no resolution gave %d clusters in %d steps: the last two were resolution %g with %d clusters and %g with %d"
+                     % ((n_clust, max_steps) + seen[0] + seen[-1]))
+
+
+def sil_ari(adata, res=0.01, steper=0.01, metric="cosine"):
+    """What the reference's ``wasserstein_distance(return_sil_ari=True)`` does after the distances (Trajectory.py:107-113), from
+    ``uns['EMD']`` and ``uns['annot']``: :func:`leiden_clustering` of ``EMD / EMD.max()`` against the statuses, then ``uns['real_labels']``
+    (the statuses), ``uns['Sil']`` (:func:`Sil_computing` of the statuses on ``EMD / EMD.max()``) and ``uns['ARI']`` (the Rand
+    index).  Returns None.  ``wasserstein_distance(return_sil_ari=True)`` itself is unchanged."""
+    E = _emd_points(adata, metric)
+    if "annot" not in adata.uns:
+        raise ValueError("adata.uns has no 'annot': run tl.wasserstein_distance first")
+    E = E / E.max()
+    _predicted, ari, real_labels = leiden_clustering(E, adata.uns["annot"], metric=metric, res=res, steper=steper)
+    adata.uns["real_labels"] = real_labels
+    adata.uns["Sil"] = Sil_computing(E, real_labels, metric=metric)
+    adata.uns["ARI"] = ari
 
 
 # ---- gene-cluster differentiation (Gene_cluster_specific.py:8-201, Trajectory.py:1129-1172) --------------------------------

@@ -9,7 +9,10 @@ on the host, uploads it once and ends in the copy of the labels, after one warm-
 with the levels, the sweeps and the time per sweep (the whole call over its sweeps: aggregation and the host steps included).
 Host (--cpu, the smallest case, connectivities): ``networkx.community.louvain_communities`` (sequential, seed 0) if networkx is
 importable, else the sequential reference of tests/louvain_restatement.py, with the modularity either reaches at the same
-resolution.  No threshold is set.  Writes OUT/louvain_rate.txt (--out, default profiles/louvain/)."""
+resolution.  --leiden: ``engine.leiden`` (K20) is timed beside ``engine.louvain`` on the same graphs in the same way, with its
+levels, move and refinement sweeps, its ratio to the Louvain time, and the number of communities of either that are not connected
+in A + A^T (tests/leiden_restatement.py's ``disconnected``).  No threshold is set.  Writes OUT/louvain_rate.txt, with --leiden
+OUT/leiden_rate.txt (--out, default profiles/louvain/)."""
 import argparse
 import os
 import sys
@@ -42,7 +45,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--resolution", type=float, default=1.0)
     ap.add_argument("--cpu", action="store_true", help="also run a sequential Louvain on the host (smallest case, connectivities)")
+    ap.add_argument("--leiden", action="store_true", help="also time engine.leiden on the same graphs")
     a = ap.parse_args()
+    import leiden_restatement as LD
     import louvain_restatement as LR
     from pilot_amd import _lib, engine, tl
 
@@ -74,6 +79,18 @@ def main():
                 % (n, mode, 1e3 * best, 1e3 * med, a.repeats, info["levels"], info["sweeps"], 1e3 * best / max(info["sweeps"], 1),
                    info["communities"], info["modularity"]))
             kept[(n, mode)] = (A, labels, info)
+            if a.leiden:
+                engine.leiden(A, resolution=a.resolution)
+                times = []
+                for _ in range(a.repeats):
+                    t0 = time.perf_counter()
+                    refined, rinfo = engine.leiden(A, resolution=a.resolution, return_info=True)
+                    times.append(time.perf_counter() - t0)
+                rbest, rmed = min(times), float(np.median(times))
+                say("%7d %-14s: leiden best %8.1f ms, median %8.1f ms of %d calls (%.2f x louvain); %d levels, %d move + %d refinement sweeps; "
+                    "%d communities, Q = %.4f; communities not connected: louvain %d, leiden %d"
+                    % (n, mode, 1e3 * rbest, 1e3 * rmed, a.repeats, rbest / best, rinfo["levels"], rinfo["move_sweeps"], rinfo["refine_sweeps"],
+                       rinfo["communities"], rinfo["modularity"], LD.disconnected(A, labels), LD.disconnected(A, refined)))
     if a.cpu:
         n = min(a.cells)
         A, labels, info = kept[(n, "connectivities")]
@@ -95,7 +112,7 @@ def main():
         say("host: %s, %d connectivities: %.1f s, %d communities, Q = %.4f (device: %d communities, Q = %.4f)"
             % (name, n, t, int(host.max()) + 1, LR.modularity(A, host, a.resolution), info["communities"], info["modularity"]))
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "louvain_rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "leiden_rate.txt" if a.leiden else "louvain_rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

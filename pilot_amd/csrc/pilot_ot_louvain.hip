@@ -1,7 +1,8 @@
 // C ABI of the Louvain communities (include/pilot_ot.h, section "Louvain communities"; kernels and the rule: louvain_kernels.hpp).
 // The host forms S = A + A^T once (transpose by counting sort, then a merge) and renumbers the labels at the end; everything
 // between the two runs on the device: a level uploads nothing and brings back only its counters.  pilot_ot_leiden (K20) is the same
-// run with a refinement between a level's move phase and its aggregation.
+// run with a refinement between a level's move phase and its aggregation.  Run holds a call's device state and the steps of a level
+// (layout, judge, sweep_phase<CON> for the move phase and the refinement, survivors, aggregate); run() is the level loop over them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -133,73 +134,52 @@ struct Totals {                        // community totals of one assignment
     int *size;
 };
 
-// info: levels, sweeps, communities; with `leiden` levels, move sweeps, refinement sweeps, communities
-int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int wave_max, int wg_max, bool leiden, int *labels,
-        double *modularity, int *info) {
-    const int nnz0 = h.indptr[n];
-    const long big = std::max<long>(n, nnz0) + 1;
-    const int chunks0 = (n + pilot::LV_CHUNK - 1) / pilot::LV_CHUNK;
+struct Run {                           // the device state of one run and the steps of a level: a step returns a count or 0, or a PILOT_OT_E* (< 0)
     DeviceLevel lev[2];
-    double *tot, *sums;
-    int *ints, *flags, *ecomm;
+    int *comm, *next, *label, *wg_list, *long_list, *flag, *pos, *ecomm;      // comm: the level's kept assignment, next: a sweep's proposal
+    Totals kept, fresh;                                                        // of comm and of next
+    double *internal, *prod, *part_x, *part_y;
     lv_u64 *nkeys;
     LvEdge *ekeys;
-    LvCounters *cnt;
-    const pilot::WsSlot val_slot[2] = {pilot::WS_LV_VAL0, pilot::WS_LV_VAL1}, deg_slot[2] = {pilot::WS_LV_DEG0, pilot::WS_LV_DEG1},
-                        idx_slot[2] = {pilot::WS_LV_IDX0, pilot::WS_LV_IDX1};
-    for (int b = 0; b < 2; ++b) {
-        HIP_TRY(pilot::ws(val_slot[b], (size_t)nnz0, &lev[b].val));
-        HIP_TRY(pilot::ws(deg_slot[b], 2 * (size_t)n, &lev[b].out));
-        HIP_TRY(pilot::ws(idx_slot[b], (size_t)n + 1 + (size_t)nnz0, &lev[b].indptr));
-        lev[b].in = lev[b].out + n;
-        lev[b].col = lev[b].indptr + n + 1;
-    }
-    HIP_TRY(pilot::ws(pilot::WS_LV_TOT, 4 * (size_t)n, &tot));
-    HIP_TRY(pilot::ws(pilot::WS_LV_SUMS, 2 * (size_t)n + 2 * (size_t)chunks0, &sums));
-    HIP_TRY(pilot::ws(pilot::WS_LV_INT, 7 * (size_t)n, &ints));
-    HIP_TRY(pilot::ws(pilot::WS_LV_FLAG, 2 * (size_t)big, &flags));
-    HIP_TRY(pilot::ws(pilot::WS_LV_ECOMM, (size_t)nnz0, &ecomm));
-    HIP_TRY(pilot::ws(pilot::WS_LV_NKEYS, (size_t)pow2_at_least(n), &nkeys));
-    HIP_TRY(pilot::ws(pilot::WS_LV_EKEYS, (size_t)pow2_at_least(nnz0), &ekeys));
-    HIP_TRY(pilot::ws(pilot::WS_LV_CNT, 1, &cnt));
-    // K20: the move phase's partition and its totals, kept while its refinement runs through comm / next / kept / fresh
-    int *parent = nullptr, *node_ok = nullptr, *sub_ok = nullptr, *owner = nullptr, *raw = nullptr, *spare_size = nullptr;
-    double *OutP = nullptr, *InP = nullptr, *cut_node = nullptr, *cut = nullptr, *spare_sum = nullptr;
-    if (leiden) {
-        HIP_TRY(pilot::ws(pilot::WS_LD_INT, 6 * (size_t)n, &parent));
-        HIP_TRY(pilot::ws(pilot::WS_LD_DBL, 5 * (size_t)n, &OutP));
-        node_ok = parent + n, sub_ok = parent + 2 * (size_t)n, owner = parent + 3 * (size_t)n, raw = parent + 4 * (size_t)n;
-        spare_size = parent + 5 * (size_t)n;
-        InP = OutP + n, cut_node = OutP + 2 * (size_t)n, cut = OutP + 3 * (size_t)n, spare_sum = OutP + 4 * (size_t)n;
-    }
-    int *comm = ints, *next = ints + n, *label = ints + 4 * (size_t)n, *wg_list = ints + 5 * (size_t)n, *long_list = ints + 6 * (size_t)n;
-    Totals kept{tot, tot + n, ints + 2 * (size_t)n}, fresh{tot + 2 * (size_t)n, tot + 3 * (size_t)n, ints + 3 * (size_t)n};
-    double *internal = sums, *prod = sums + n, *part_x = sums + 2 * (size_t)n, *part_y = part_x + chunks0;
-    int *flag = flags, *pos = flags + big;
+    LvCounters *cnt, hc;                                                       // hc: the counters as last read back
+    int *parent, *node_ok, *sub_ok, *owner, *raw, *spare_size;                 // K20: the move phase's partition and its totals, kept
+    double *OutP, *InP, *cut_node, *cut, *spare_sum;                           // while the refinement runs through comm / next / kept / fresh
+    double w, gamma, tol, qs_kept;                                             // qs_kept: Qs of comm
+    int wave_max, wg_max, n_wg, n_long, wg_lds;                                // n_wg, n_long, wg_lds (bytes): what lv_bin_kernel found on the level
 
-    HIP_TRY(hipMemcpy(lev[0].indptr, h.indptr.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(lev[0].col, h.col.data(), sizeof(int) * (size_t)nnz0, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(lev[0].val, h.val.data(), sizeof(double) * (size_t)nnz0, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(lev[0].out, h.out.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(lev[0].in, h.in.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, label, n);
-
-    const double w = h.w, w2 = w * w;
-    const size_t wg_lds_max = 16 * (size_t)pow2_at_least(wg_max);
-    if (wg_lds_max > 64 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::lv_move_wg_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_max));
-        if (leiden)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pilot::lv_move_wg_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_max));
+    // the workspace, slot by slot: its elements and first array, then the arrays that follow in it.  Slots, sizes and order are fixed
+    int layout(int n, int nnz0, bool leiden) {
+        const size_t N = (size_t)n, E = (size_t)nnz0, big = (size_t)std::max<long>(n, nnz0) + 1, chunks = (n + pilot::LV_CHUNK - 1) / pilot::LV_CHUNK;
+        const pilot::WsSlot val_slot[2] = {pilot::WS_LV_VAL0, pilot::WS_LV_VAL1}, deg_slot[2] = {pilot::WS_LV_DEG0, pilot::WS_LV_DEG1},
+                            idx_slot[2] = {pilot::WS_LV_IDX0, pilot::WS_LV_IDX1};
+        for (int b = 0; b < 2; ++b) {
+            HIP_TRY(pilot::ws(val_slot[b], E, &lev[b].val));
+            HIP_TRY(pilot::ws(deg_slot[b], 2 * N, &lev[b].out));
+            HIP_TRY(pilot::ws(idx_slot[b], N + 1 + E, &lev[b].indptr));
+            lev[b].in = lev[b].out + N, lev[b].col = lev[b].indptr + N + 1;
+        }
+        HIP_TRY(pilot::ws(pilot::WS_LV_TOT, 4 * N, &kept.Out));
+        kept.In = kept.Out + N, fresh.Out = kept.In + N, fresh.In = fresh.Out + N;
+        HIP_TRY(pilot::ws(pilot::WS_LV_SUMS, 2 * N + 2 * chunks, &internal));
+        prod = internal + N, part_x = prod + N, part_y = part_x + chunks;
+        HIP_TRY(pilot::ws(pilot::WS_LV_INT, 7 * N, &comm));
+        next = comm + N, kept.size = next + N, fresh.size = kept.size + N, label = fresh.size + N, wg_list = label + N, long_list = wg_list + N;
+        HIP_TRY(pilot::ws(pilot::WS_LV_FLAG, 2 * big, &flag));
+        pos = flag + big;
+        HIP_TRY(pilot::ws(pilot::WS_LV_ECOMM, E, &ecomm));
+        HIP_TRY(pilot::ws(pilot::WS_LV_NKEYS, (size_t)pow2_at_least(n), &nkeys));
+        HIP_TRY(pilot::ws(pilot::WS_LV_EKEYS, (size_t)pow2_at_least(nnz0), &ekeys));
+        HIP_TRY(pilot::ws(pilot::WS_LV_CNT, 1, &cnt));
+        if (!leiden) return PILOT_OT_OK;
+        HIP_TRY(pilot::ws(pilot::WS_LD_INT, 6 * N, &parent));
+        node_ok = parent + N, sub_ok = node_ok + N, owner = sub_ok + N, raw = owner + N, spare_size = raw + N;
+        HIP_TRY(pilot::ws(pilot::WS_LD_DBL, 5 * N, &OutP));
+        InP = OutP + N, cut_node = InP + N, cut = cut_node + N, spare_sum = cut + N;
+        return PILOT_OT_OK;
     }
-    int m = n, nnz = nnz0, cur = 0, levels = 0, sweeps = 0, refine_sweeps = 0;
-    double qs_kept = 0.0;
-    LvCounters hc;
-    const LvRefine no_refine{nullptr, nullptr, nullptr};
 
     // community totals of the assignment c into t, and its Qs into cnt->qs
-    auto judge = [&](const LvGraph &G, const int *c, const Totals &t) -> int {
+    int judge(const LvGraph &G, const int *c, const Totals &t) {
         const long P = pow2_at_least(G.m);
         const int chunks = (G.m + pilot::LV_CHUNK - 1) / pilot::LV_CHUNK;
         hipLaunchKernelGGL(pilot::lv_node_keys_kernel, dim3(blocks_for(P)), dim3(256), 0, nullptr, c, G.m, P, nkeys);
@@ -213,123 +193,138 @@ int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int
         hipLaunchKernelGGL(pilot::lv_qs_kernel, dim3(1), dim3(64), 0, nullptr, part_x, part_y, chunks, w, gamma, cnt);
         HIP_TRY(hipGetLastError());
         return PILOT_OT_OK;
-    };
+    }
 
-    while (levels < max_levels) {
-        const LvGraph G = lev[cur].graph(m);
-        HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(LvCounters), nullptr));
-        hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, comm, m);
-        hipLaunchKernelGGL(pilot::lv_bin_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G.indptr, m, wave_max, wg_max, wg_list, long_list, cnt);
-        if (int rc = judge(G, comm, kept)) return rc;
-        HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-        qs_kept = hc.qs;
-        const int n_wg = hc.n_wg, n_long = hc.n_long;
-        const size_t wg_lds = 16 * (size_t)pow2_at_least(hc.max_wg_degree);
-        ++levels;
-        const double qs_start = qs_kept;
-        for (int s = 0; s < pilot::LV_MAX_SWEEPS; ++s) {
+    // Sweeps until nothing moves, a sweep is discarded or LV_MAX_SWEEPS; leaves the kept assignment in comm / kept, its Qs in qs_kept, and
+    // returns the sweeps run.  CON, the refinement: sub_ok first (the sorted node keys of comm are those judge left), raw decisions settled
+    template <bool CON> int sweep_phase(const LvGraph &G) {
+        const int m = G.m;
+        const LvRefine R = CON ? LvRefine{parent, node_ok, sub_ok} : LvRefine{nullptr, nullptr, nullptr};
+        const dim3 nodes(blocks_for(m)), waves(blocks_for(m, pilot::LV_THREADS / 64)), block(pilot::LV_THREADS);
+        int sweeps = 0;
+        while (sweeps < pilot::LV_MAX_SWEEPS) {
             const LvState S{comm, kept.Out, kept.In, kept.size};
+            int *dest = CON ? raw : next;
             HIP_TRY(hipMemsetAsync(&cnt->moved, 0, sizeof(int), nullptr));
-            hipLaunchKernelGGL(pilot::lv_move_wave_kernel<false>, dim3(blocks_for(m, pilot::LV_THREADS / 64)), dim3(pilot::LV_THREADS), 0, nullptr,
-                               G, S, no_refine, w, gamma, wave_max, next, cnt);
+            if (CON) {
+                hipLaunchKernelGGL(pilot::ld_cut_kernel, nodes, dim3(256), 0, nullptr, G, parent, comm, cut_node);
+                hipLaunchKernelGGL(pilot::lv_runs_kernel, nodes, dim3(256), 0, nullptr, nkeys, m, cut_node, cut_node, cut, spare_sum, spare_size);
+                hipLaunchKernelGGL(pilot::ld_sub_ok_kernel, nodes, dim3(256), 0, nullptr, nkeys, m, parent, OutP, InP, S, cut, w, gamma, sub_ok, owner);
+            }
+            hipLaunchKernelGGL(pilot::lv_move_wave_kernel<CON>, waves, block, 0, nullptr, G, S, R, w, gamma, wave_max, dest, cnt);
             if (n_wg > 0)
-                hipLaunchKernelGGL(pilot::lv_move_wg_kernel<false>, dim3((unsigned)n_wg), dim3(pilot::LV_THREADS), wg_lds, nullptr, G, S, no_refine,
-                                   w, gamma, wg_list, next, cnt);
+                hipLaunchKernelGGL(pilot::lv_move_wg_kernel<CON>, dim3((unsigned)n_wg), block, wg_lds, nullptr, G, S, R, w, gamma, wg_list, dest, cnt);
             if (n_long > 0)
-                hipLaunchKernelGGL(pilot::lv_move_long_kernel<false>, dim3((unsigned)n_long), dim3(pilot::LV_THREADS), 0, nullptr, G, S, no_refine,
-                                   w, gamma, long_list, ecomm, next, cnt);
+                hipLaunchKernelGGL(pilot::lv_move_long_kernel<CON>, dim3((unsigned)n_long), block, 0, nullptr, G, S, R, w, gamma, long_list, ecomm,
+                                   dest, cnt);
+            if (CON) hipLaunchKernelGGL(pilot::ld_settle_kernel, nodes, dim3(256), 0, nullptr, m, comm, kept.size, owner, raw, next, cnt);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
             ++sweeps;
             if (hc.moved == 0) break;
             if (int rc = judge(G, next, fresh)) return rc;
             HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-            if (!(hc.qs - qs_kept > tol * w2)) break;                          // discarded: the kept assignment stands
+            if (!(hc.qs - qs_kept > tol * (w * w))) break;                     // discarded: the kept assignment stands
             qs_kept = hc.qs;
             std::swap(comm, next);
             std::swap(kept, fresh);
         }
+        return sweeps;
+    }
 
-        if (leiden) {
-            // every community of the move phase one node: the run ends, the level's nodes are the communities
-            hipLaunchKernelGGL(pilot::lv_alive_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, kept.size, m, flag);
-            hipLaunchKernelGGL(pilot::lv_scan_kernel, dim3(1), dim3(1024), 0, nullptr, flag, pos, (long)m, &cnt->coarse_m);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-            qs_kept = qs_start;
-            if (hc.coarse_m == m) break;
-            // the refinement: the move phase's partition becomes the constraint, and the same loop runs from singletons again
-            HIP_TRY(hipMemcpyAsync(parent, comm, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(OutP, kept.Out, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(InP, kept.In, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
-            hipLaunchKernelGGL(pilot::ld_node_ok_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G, parent, OutP, InP, w, gamma, node_ok);
-            hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, comm, m);
-            if (int rc = judge(G, comm, kept)) return rc;                       // (leaves the sorted node keys of comm in nkeys)
-            const LvRefine R{parent, node_ok, sub_ok};
-            for (int s = 0; s < pilot::LV_MAX_SWEEPS; ++s) {
-                const LvState S{comm, kept.Out, kept.In, kept.size};
-                HIP_TRY(hipMemsetAsync(&cnt->moved, 0, sizeof(int), nullptr));
-                hipLaunchKernelGGL(pilot::ld_cut_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G, parent, comm, cut_node);
-                hipLaunchKernelGGL(pilot::lv_runs_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, nkeys, m, cut_node, cut_node, cut, spare_sum,
-                                   spare_size);
-                hipLaunchKernelGGL(pilot::ld_sub_ok_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, nkeys, m, parent, OutP, InP, S, cut, w, gamma,
-                                   sub_ok, owner);
-                hipLaunchKernelGGL(pilot::lv_move_wave_kernel<true>, dim3(blocks_for(m, pilot::LV_THREADS / 64)), dim3(pilot::LV_THREADS), 0,
-                                   nullptr, G, S, R, w, gamma, wave_max, raw, cnt);
-                if (n_wg > 0)
-                    hipLaunchKernelGGL(pilot::lv_move_wg_kernel<true>, dim3((unsigned)n_wg), dim3(pilot::LV_THREADS), wg_lds, nullptr, G, S, R, w,
-                                       gamma, wg_list, raw, cnt);
-                if (n_long > 0)
-                    hipLaunchKernelGGL(pilot::lv_move_long_kernel<true>, dim3((unsigned)n_long), dim3(pilot::LV_THREADS), 0, nullptr, G, S, R, w,
-                                       gamma, long_list, ecomm, raw, cnt);
-                hipLaunchKernelGGL(pilot::ld_settle_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, m, comm, kept.size, owner, raw, next, cnt);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-                ++refine_sweeps;
-                if (hc.moved == 0) break;
-                if (int rc = judge(G, next, fresh)) return rc;
-                HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-                if (!(hc.qs - qs_kept > tol * w2)) break;
-                qs_kept = hc.qs;
-                std::swap(comm, next);
-                std::swap(kept, fresh);
-            }
-        }
-
-        // aggregation: surviving ids ranked ascending
-        int *rank = pos;
+    // flags the ids that still have members, ranks them ascending into pos (and renames the labels of n_relabel nodes); returns their number
+    int survivors(int m, int n_relabel = 0) {
         hipLaunchKernelGGL(pilot::lv_alive_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, kept.size, m, flag);
-        hipLaunchKernelGGL(pilot::lv_scan_kernel, dim3(1), dim3(1024), 0, nullptr, flag, rank, (long)m, &cnt->coarse_m);
-        hipLaunchKernelGGL(pilot::lv_relabel_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, label, n, comm, rank);
+        hipLaunchKernelGGL(pilot::lv_scan_kernel, dim3(1), dim3(1024), 0, nullptr, flag, pos, (long)m, &cnt->coarse_m);
+        if (n_relabel) hipLaunchKernelGGL(pilot::lv_relabel_kernel, dim3(blocks_for(n_relabel)), dim3(256), 0, nullptr, label, n_relabel, comm, pos);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-        const int m2 = hc.coarse_m;
-        if (leiden && m2 == m) qs_kept = qs_start;                              // the refinement merged nothing: the run ends as above
-        if (m2 == m || levels == max_levels) break;
-        const DeviceLevel &nx = lev[cur ^ 1];
-        const long P = pow2_at_least(nnz);
-        hipLaunchKernelGGL(pilot::lv_coarse_nodes_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, m, kept.size, rank, kept.Out, kept.In, nx.out,
+        return hc.coarse_m;
+    }
+
+    // aggregation; returns the coarse nodes.  Unless nothing merged or the level is the `last`, builds the coarse graph in nx, its entries in *nnz
+    int aggregate(const LvGraph &G, int n, bool last, const DeviceLevel &nx, int *nnz) {
+        const int m = G.m, m2 = survivors(m, n), nnz1 = *nnz;               // (n: the original nodes' labels are renamed with the ranks)
+        if (m2 < 0 || m2 == m || last) return m2;
+        const long P = pow2_at_least(nnz1), keys = std::max<long>(m, P - nnz1);
+        hipLaunchKernelGGL(pilot::lv_coarse_nodes_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, m, kept.size, pos, kept.Out, kept.In, nx.out,
                            nx.in);
-        hipLaunchKernelGGL(pilot::lv_edge_keys_kernel, dim3(blocks_for(std::max<long>(m, P - nnz))), dim3(256), 0, nullptr, G, comm, rank, nnz, P,
-                           ekeys);
+        hipLaunchKernelGGL(pilot::lv_edge_keys_kernel, dim3(blocks_for(keys)), dim3(256), 0, nullptr, G, comm, pos, nnz1, P, ekeys);
         HIP_TRY(device_sort(ekeys, P));
-        int *epos = ecomm;                                                      // (rank lives in pos; ecomm is free between sweeps)
-        hipLaunchKernelGGL(pilot::lv_edge_heads_kernel, dim3(blocks_for(nnz)), dim3(256), 0, nullptr, ekeys, nnz, flag);
-        hipLaunchKernelGGL(pilot::lv_scan_kernel, dim3(1), dim3(1024), 0, nullptr, flag, epos, (long)nnz, &cnt->coarse_nnz);
-        hipLaunchKernelGGL(pilot::lv_coarse_edges_kernel, dim3(blocks_for(nnz)), dim3(256), 0, nullptr, ekeys, nnz, flag, epos, G.val, m2,
+        hipLaunchKernelGGL(pilot::lv_edge_heads_kernel, dim3(blocks_for(nnz1)), dim3(256), 0, nullptr, ekeys, nnz1, flag);
+        hipLaunchKernelGGL(pilot::lv_scan_kernel, dim3(1), dim3(1024), 0, nullptr, flag, ecomm, (long)nnz1, &cnt->coarse_nnz);   // (ecomm is free here)
+        hipLaunchKernelGGL(pilot::lv_coarse_edges_kernel, dim3(blocks_for(nnz1)), dim3(256), 0, nullptr, ekeys, nnz1, flag, ecomm, G.val, m2,
                            &cnt->coarse_nnz, nx.indptr, nx.col, nx.val);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+        *nnz = hc.coarse_nnz;
+        return m2;
+    }
+};
+
+// the level loop.  info: levels, sweeps, communities; with `leiden` levels, move sweeps, refinement sweeps, communities
+int run(int n, const HostGraph &h, double gamma, double tol, int max_levels, int wave_max, int wg_max, bool leiden, int *labels,
+        double *modularity, int *info) {
+    const int nnz0 = h.indptr[n];
+    Run r{};
+    r.w = h.w, r.gamma = gamma, r.tol = tol, r.wave_max = wave_max, r.wg_max = wg_max;
+    if (int rc = r.layout(n, nnz0, leiden)) return rc;
+    HIP_TRY(hipMemcpy(r.lev[0].indptr, h.indptr.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.lev[0].col, h.col.data(), sizeof(int) * (size_t)nnz0, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.lev[0].val, h.val.data(), sizeof(double) * (size_t)nnz0, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.lev[0].out, h.out.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.lev[0].in, h.in.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, r.label, n);
+
+    const size_t wg_lds_max = 16 * (size_t)pow2_at_least(wg_max);
+    const void *wg_kernel[2] = {(const void *)pilot::lv_move_wg_kernel<false>, (const void *)pilot::lv_move_wg_kernel<true>};
+    if (wg_lds_max > 64 * 1024)
+        for (int con = 0; con <= (int)leiden; ++con)
+            HIP_TRY(hipFuncSetAttribute(wg_kernel[con], hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds_max));
+    int m = n, nnz = nnz0, cur = 0, levels = 0, sweeps = 0, refine_sweeps = 0, count;
+
+    while (levels < max_levels) {
+        const LvGraph G = r.lev[cur].graph(m);
+        HIP_TRY(hipMemsetAsync(r.cnt, 0, sizeof(LvCounters), nullptr));
+        hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, r.comm, m);
+        hipLaunchKernelGGL(pilot::lv_bin_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G.indptr, m, wave_max, wg_max, r.wg_list, r.long_list,
+                           r.cnt);
+        if (int rc = r.judge(G, r.comm, r.kept)) return rc;
+        HIP_TRY(hipMemcpy(&r.hc, r.cnt, sizeof(r.hc), hipMemcpyDeviceToHost));
+        const double qs_start = r.qs_kept = r.hc.qs;                            // Qs of the level's nodes as singletons
+        r.n_wg = r.hc.n_wg, r.n_long = r.hc.n_long, r.wg_lds = 16 * (int)pow2_at_least(r.hc.max_wg_degree);
+        ++levels;
+        if ((count = r.sweep_phase<false>(G)) < 0) return count;
+        sweeps += count;
+
+        if (leiden) {
+            if ((count = r.survivors(m)) < 0) return count;
+            r.qs_kept = qs_start;                                               // the singletons' Qs again, whichever way it goes on
+            if (count == m) break;                   // Leiden's end 1 of 2: every community of the move phase is one node, and the run ends
+            // the refinement: the move phase's partition becomes the constraint, and the same loop runs from singletons again
+            HIP_TRY(hipMemcpyAsync(r.parent, r.comm, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(r.OutP, r.kept.Out, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(r.InP, r.kept.In, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, nullptr));
+            hipLaunchKernelGGL(pilot::ld_node_ok_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, G, r.parent, r.OutP, r.InP, r.w, gamma, r.node_ok);
+            hipLaunchKernelGGL(pilot::lv_iota_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, r.comm, m);
+            if (int rc = r.judge(G, r.comm, r.kept)) return rc;                 // (leaves the sorted node keys of comm in nkeys)
+            if ((count = r.sweep_phase<true>(G)) < 0) return count;
+            refine_sweeps += count;
+        }
+
+        const int m2 = r.aggregate(G, n, levels == max_levels, r.lev[cur ^ 1], &nnz);
+        if (m2 < 0) return m2;
+        if (leiden && m2 == m) r.qs_kept = qs_start;                            // Leiden's end 2 of 2: the refinement merged nothing; as end 1
+        if (m2 == m || levels == max_levels) break;
         m = m2;
-        nnz = hc.coarse_nnz;
         cur ^= 1;
     }
-    HIP_TRY(hipMemcpy(labels, label, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(labels, r.label, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     info[0] = levels;
     info[1] = sweeps;
     if (leiden) info[2] = refine_sweeps;
     info[leiden ? 3 : 2] = renumber(n, labels);
-    *modularity = qs_kept / w2;
+    *modularity = r.qs_kept / (r.w * r.w);
     return PILOT_OT_OK;
 }
 

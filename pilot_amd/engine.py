@@ -1302,6 +1302,15 @@ def _louvain_args(graph, resolution, tol, max_levels):
     return np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32), data, n
 
 
+def _communities(symbol, keys, graph, resolution, tol, max_levels, return_info):
+    """the call behind :func:`louvain` and :func:`leiden`: the library's ``symbol``, whose info counters are named by ``keys``"""
+    indptr, indices, data, n = _louvain_args(graph, resolution, tol, max_levels)
+    labels, q, info = np.empty(n, dtype=np.int32), ctypes.c_double(0.0), np.zeros(len(keys), dtype=np.int32)
+    _lib.check(getattr(_lib.load(), symbol)(n, _lib.lptr(indptr), _lib.iptr(indices), _lib.dptr(data), float(resolution), float(tol),
+                                            int(max_levels), _lib.iptr(labels), ctypes.byref(q), _lib.iptr(info)))
+    return (labels, dict(zip(("modularity",) + keys, [q.value] + info.tolist()))) if return_info else labels
+
+
 def louvain(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
     """K17: the Louvain communities of a weighted graph on the device (include/pilot_ot.h, "Louvain communities"), by a
     SYNCHRONOUS rule: every node of a sweep chooses its move against the same snapshot, and a sweep is kept only if the modularity
@@ -1312,13 +1321,7 @@ def louvain(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
     Returns ``labels`` (int32, 0 .. k-1 by decreasing community size, ties to the smallest member); with ``return_info``
     ``(labels, dict(modularity, levels, sweeps, communities))``.  ValueError before any device work: a graph that is not square, a
     weight negative or not finite, ``resolution`` negative or not finite, ``tol < 0``, ``max_levels < 1``."""
-    indptr, indices, data, n = _louvain_args(graph, resolution, tol, max_levels)
-    labels, q, info = np.empty(n, dtype=np.int32), ctypes.c_double(0.0), np.zeros(3, dtype=np.int32)
-    _lib.check(_lib.load().pilot_ot_louvain(n, _lib.lptr(indptr), _lib.iptr(indices), _lib.dptr(data), float(resolution), float(tol),
-                                            int(max_levels), _lib.iptr(labels), ctypes.byref(q), _lib.iptr(info)))
-    if return_info:
-        return labels, {"modularity": q.value, "levels": int(info[0]), "sweeps": int(info[1]), "communities": int(info[2])}
-    return labels
+    return _communities("pilot_ot_louvain", ("levels", "sweeps", "communities"), graph, resolution, tol, max_levels, return_info)
 
 
 # ---- Leiden communities (K20; sc.tl.leiden of pilotpy's Clustering, clustering_emd and select_best_sil, by K17's synchronous rule) ---
@@ -1331,14 +1334,8 @@ def leiden(graph, resolution=1.0, tol=1e-3, max_levels=32, return_info=False):
     are not leidenalg's.  ``graph``, ``resolution``, ``tol``, ``max_levels``, the labels and the ValueErrors before any device
     work are :func:`louvain`'s; with ``return_info`` ``(labels, dict(modularity, levels, move_sweeps, refine_sweeps,
     communities))``."""
-    indptr, indices, data, n = _louvain_args(graph, resolution, tol, max_levels)
-    labels, q, info = np.empty(n, dtype=np.int32), ctypes.c_double(0.0), np.zeros(4, dtype=np.int32)
-    _lib.check(_lib.load().pilot_ot_leiden(n, _lib.lptr(indptr), _lib.iptr(indices), _lib.dptr(data), float(resolution), float(tol),
-                                           int(max_levels), _lib.iptr(labels), ctypes.byref(q), _lib.iptr(info)))
-    if return_info:
-        return labels, {"modularity": q.value, "levels": int(info[0]), "move_sweeps": int(info[1]), "refine_sweeps": int(info[2]),
-                        "communities": int(info[3])}
-    return labels
+    return _communities("pilot_ot_leiden", ("levels", "move_sweeps", "refine_sweeps", "communities"), graph, resolution, tol, max_levels,
+                        return_info)
 
 
 def check_clustering_method(method):

@@ -968,9 +968,13 @@ def neighbors(adata, n_neighbors=15, n_pcs=None, use_rep="X_pca", metric="euclid
 
 
 # ---- Louvain communities of the neighbour graph (Trajectory.py:217-220, 1000-1062: sknetwork's Louvain(resolution)) -------------
-def _neighbor_graph(adata, mode, neighbors_key):
+def _check_mode(mode):
     if mode not in ("connectivities", "distances"):
         raise ValueError("mode=%r: connectivities or distances" % (mode,))
+
+
+def _neighbor_graph(adata, mode, neighbors_key):
+    _check_mode(mode)
     key = "neighbors" if neighbors_key is None else neighbors_key
     entry = adata.uns.get(key) if hasattr(adata.uns, "get") else None
     name = entry.get(mode + "_key") if isinstance(entry, dict) else None
@@ -978,6 +982,12 @@ def _neighbor_graph(adata, mode, neighbors_key):
     if name is None or obsp is None or name not in obsp:
         raise ValueError("adata has no neighbour graph under uns[%r] / obsp: run tl.neighbors first" % (key,))
     return obsp[name]
+
+
+def _write_communities(adata, cluster, resolution, mode, neighbors_key, key_added):
+    labels, info = cluster(_neighbor_graph(adata, mode, neighbors_key), resolution=resolution, return_info=True)
+    adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=[str(c) for c in range(info["communities"])])
+    adata.uns[key_added] = {"params": {"resolution": resolution, "mode": mode}, "modularity": info["modularity"]}
 
 
 def louvain(adata, resolution=1.0, mode="connectivities", neighbors_key=None, key_added="louvain"):
@@ -988,11 +998,7 @@ def louvain(adata, resolution=1.0, mode="connectivities", neighbors_key=None, ke
     missing graph raises ValueError naming ``tl.neighbors``.  The rule is synchronous and deterministic, not
     sknetwork's or scanpy's sequential, seeded sweep: where the node order decides, the labels differ from theirs.  Leiden is
     :func:`leiden`."""
-    graph = _neighbor_graph(adata, mode, neighbors_key)
-    labels, info = engine.louvain(graph, resolution=resolution, return_info=True)
-    k = info["communities"]
-    adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=[str(c) for c in range(k)])
-    adata.uns[key_added] = {"params": {"resolution": resolution, "mode": mode}, "modularity": info["modularity"]}
+    _write_communities(adata, engine.louvain, resolution, mode, neighbors_key, key_added)
 
 
 def leiden(adata, resolution=1.0, mode="connectivities", neighbors_key=None, key_added="leiden"):
@@ -1000,11 +1006,7 @@ def leiden(adata, resolution=1.0, mode="connectivities", neighbors_key=None, key
     ``adata.obs[key_added]`` Categorical and ``adata.uns[key_added] = {'params': {'resolution', 'mode'}, 'modularity': Q}``, but
     every community is connected in the graph.  Synchronous and deterministic, not leidenalg's seeded random refinement: the labels
     are not scanpy's ``tl.leiden`` labels.  Returns None."""
-    graph = _neighbor_graph(adata, mode, neighbors_key)
-    labels, info = engine.leiden(graph, resolution=resolution, return_info=True)
-    k = info["communities"]
-    adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=[str(c) for c in range(k)])
-    adata.uns[key_added] = {"params": {"resolution": resolution, "mode": mode}, "modularity": info["modularity"]}
+    _write_communities(adata, engine.leiden, resolution, mode, neighbors_key, key_added)
 
 
 class _Cells:
@@ -1030,8 +1032,7 @@ def reclustering_data(adata, resu=0.01, normalization=False, target_sum=1e6, n_n
     as scanpy leaves them."""
     if method_ != "umap":
         raise ValueError("method_=%r: only 'umap' (scanpy's default connectivities) is offered" % (method_,))
-    if mode not in ("connectivities", "distances"):
-        raise ValueError("mode=%r: connectivities or distances" % (mode,))
+    _check_mode(mode)
     engine.check_resolution(resu)
     if origine_scr_rna:
         n_vars = adata.X.shape[1]
@@ -1085,7 +1086,7 @@ def _best_resolution(resolutions, scores, start):
     return best_res
 
 
-def _sweep(adata, resolutions, start, graph, score, cluster=engine.louvain):
+def _sweep(adata, resolutions, start, graph, score, cluster):
     """one ``cluster`` run (engine.louvain or engine.leiden) and one ``score(labels)`` per resolution; a labelling with one
     cluster, or one cluster per point, scores NaN"""
     n, rows = graph.shape[0], []
@@ -1138,16 +1139,25 @@ def select_best_resolution(adata, resolutions=None, start=0.2, step=0.1, end=2, 
 _EMD_NEIGHBORS = 15          # scanpy's pp.neighbors default, which the reference takes for the samples
 
 
+def _emd_square(EMD, name):
+    E = np.ascontiguousarray(EMD, dtype=np.float64)
+    if E.ndim != 2 or E.shape[0] != E.shape[1]:
+        raise ValueError("%s must be samples x samples, got %s" % (name, E.shape))
+    return E
+
+
+def _emd_enough(E):
+    if E.shape[0] < _EMD_NEIGHBORS:
+        raise ValueError("%d samples: the neighbour graph of scanpy's defaults needs n_neighbors = %d of them" % (E.shape[0], _EMD_NEIGHBORS))
+
+
 def _emd_points(adata, metric):
     """``uns['EMD']`` as the reference's ``sc.AnnData(EMD)`` has it: the samples are the points, the rows their coordinates"""
     _metric_checked(metric)
     if "EMD" not in adata.uns:
         raise ValueError("adata.uns has no 'EMD': run tl.wasserstein_distance first")
-    E = np.ascontiguousarray(adata.uns["EMD"], dtype=np.float64)
-    if E.ndim != 2 or E.shape[0] != E.shape[1]:
-        raise ValueError("uns['EMD'] must be samples x samples, got %s" % (E.shape,))
-    if E.shape[0] < _EMD_NEIGHBORS:
-        raise ValueError("%d samples: the neighbour graph of scanpy's defaults needs n_neighbors = %d of them" % (E.shape[0], _EMD_NEIGHBORS))
+    E = _emd_square(adata.uns["EMD"], "uns['EMD']")
+    _emd_enough(E)
     return E
 
 
@@ -1261,9 +1271,7 @@ def leiden_clustering(EMD, df, category="status", sample_col=1, res=0.01, metric
     ValueError before any device work: ``EMD`` not square or not matching the samples, a missing column, an unknown metric,
     ``res`` negative or not finite, ``steper`` not positive, ``max_steps < 1``, fewer than 15 samples."""
     _metric_checked(metric)
-    E = np.ascontiguousarray(EMD, dtype=np.float64)
-    if E.ndim != 2 or E.shape[0] != E.shape[1]:
-        raise ValueError("EMD must be samples x samples, got %s" % (E.shape,))
+    E = _emd_square(EMD, "EMD")
     if category not in df.columns:
         raise ValueError("df has no column %r" % (category,))
     if isinstance(sample_col, bool) or not isinstance(sample_col, (int, np.integer)) or not -len(df.columns) <= sample_col < len(df.columns):
@@ -1277,8 +1285,7 @@ def leiden_clustering(EMD, df, category="status", sample_col=1, res=0.01, metric
     true_labels = list(df[category].to_numpy()[first_rows])
     if len(true_labels) != E.shape[0]:
         raise ValueError("EMD has %d samples, df[%r] %d" % (E.shape[0], df.columns[sample_col], len(true_labels)))
-    if E.shape[0] < _EMD_NEIGHBORS:
-        raise ValueError("%d samples: the neighbour graph of scanpy's defaults needs n_neighbors = %d of them" % (E.shape[0], _EMD_NEIGHBORS))
+    _emd_enough(E)
     n_clust = len(df[category].unique())
     graph = _emd_graph(E, metric)
     res, seen = float(res), []

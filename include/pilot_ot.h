@@ -536,6 +536,35 @@ int pilot_ot_csr_group_sums(pilot_ot_csr *csr, const int *codes, int n_groups, c
 int pilot_ot_group_sums_slice_rows(void);
 int pilot_ot_group_sums_col_block(void);
 
+/* ---- rank sums (K21): per selected column, the tie-averaged ranks of the used rows summed per group -- what the Wilcoxon /
+ * Mann-Whitney rank-sum test of a group against the rest (scanpy's rank_genes_groups(method="wilcoxon")) and the Kruskal-Wallis
+ * test over all groups are made of.  Y, dtype, n, n_cols_total, ld, codes, cols and n_cols are pilot_ot_group_moments's; n_groups
+ * in [1, 1024].  N = the used rows (code >= 0); an unused row is never read.  Per selected column j, over the used rows:
+ * rank_i = the 1-based rank of y_ij, equal values sharing the mean of their positions (scipy.stats.rankdata(method="average"));
+ * equality is numeric, -0.0 == 0.0, and in a sparse matrix a stored 0 ties with the implicit ones.
+ * Out (host): count[g] = rows with codes == g; rank2[g][j] = 2 * sum_{i in g} rank_i (n_groups x n_cols, an exact integer);
+ * ties[j] = sum over the runs of equal values of t^3 - t, t the run's length.  No used rows: all 0.
+ * Only a column's non-zero used values are sorted (the zeros are one run whose place follows from the number of negatives), by
+ * one wave for up to pilot_ot_rank_sums_wave_max() of them, one workgroup in LDS up to pilot_ot_rank_sums_wg_max(), and one
+ * workgroup in HBM with tiles of pilot_ot_rank_sums_sort_tile() in LDS beyond.  Everything on the device is an integer and only
+ * integer atomics are used: the dense and sparse routes and a repeated call return the same values.
+ * A NaN or infinity in a used row of a selected column: PILOT_OT_EINVAL with *bad_row / *bad_col (nullable; -1 otherwise) the row
+ * and the column of Y of the first one -- the lowest position in cols, then the lowest row.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n < 0, n_cols_total < 1, ld < n_cols_total, dtype not 0 / 1, n_groups
+ * outside [1, 1024], n_cols < 0 (or != n_cols_total without cols), a column outside [0, n_cols_total), a code >= n_groups.
+ * PILOT_OT_ENOTSUP (before any HIP call): n > INT_MAX, or N > 2^21 - 1 (t^3 must fit 63 bits). */
+int pilot_ot_rank_sums(const void *Y, int Y_is_device, int dtype, long long n, int n_cols_total, long long ld, const int *codes,
+                       int n_groups, const int *cols, int n_cols, long long *count, long long *rank2, long long *ties,
+                       long long *bad_row, int *bad_col);
+/* The same of a sparse matrix, from its column form (built by the first call that needs it): the work per column is
+ * O(stored log stored), never O(n).  cols NULL: every column (n_cols = the matrix's).  Same error cases (n_groups and n_cols < 0
+ * are judged before the handle). */
+int pilot_ot_csr_rank_sums(pilot_ot_csr *csr, const int *codes, int n_groups, const int *cols, int n_cols, long long *count,
+                           long long *rank2, long long *ties, long long *bad_row, int *bad_col);
+int pilot_ot_rank_sums_wave_max(void);
+int pilot_ot_rank_sums_wg_max(void);
+int pilot_ot_rank_sums_sort_tile(void);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

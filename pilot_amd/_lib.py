@@ -50,6 +50,8 @@ SYMBOLS = [
     "pilot_ot_csr_upload", "pilot_ot_csr_destroy", "pilot_ot_csr_normalize_log1p", "pilot_ot_csr_build_columns", "pilot_ot_csr_slice_rows",
     "pilot_ot_csr_column_nnz", "pilot_ot_csr_group_moments", "pilot_ot_csr_densify",
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
+    "pilot_ot_rank_sums", "pilot_ot_csr_rank_sums", "pilot_ot_rank_sums_wave_max", "pilot_ot_rank_sums_wg_max",
+    "pilot_ot_rank_sums_sort_tile",
     "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain", "pilot_ot_leiden",
     "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
     "pilot_ot_elastic_fit_batch", "pilot_ot_point_moments", "pilot_ot_tree_projection",
@@ -181,6 +183,12 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_csr_group_sums.argtypes = [c_vp, ip, c_int, ip, c_int, llp, dp]
     L.pilot_ot_group_sums_slice_rows.argtypes = []
     L.pilot_ot_group_sums_col_block.argtypes = []
+    L.pilot_ot_rank_sums.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, ip, c_int, llp, llp, llp,
+                                     llp, ip]
+    L.pilot_ot_csr_rank_sums.argtypes = [c_vp, ip, c_int, ip, c_int, llp, llp, llp, llp, ip]
+    L.pilot_ot_rank_sums_wave_max.argtypes = []
+    L.pilot_ot_rank_sums_wg_max.argtypes = []
+    L.pilot_ot_rank_sums_sort_tile.argtypes = []
     L.pilot_ot_csr_pca.argtypes = [c_vp, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_pca.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_knn_rows.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, ctypes.c_longlong,

@@ -42,6 +42,7 @@ enum WsSlot {
     WS_SIL_X, WS_SIL_UNIT, WS_SIL_FLAGS, WS_SIL_SORTED, WS_SIL_ORDER, WS_SIL_OFFSETS, WS_SIL_OUT,   // pilot_ot_silhouette_points.hip
     WS_PT_X, WS_PT_FLAGS, WS_PT_Y, WS_PT_YT, WS_PT_S, WS_PT_CENTRE, WS_PT_STATE, WS_PT_ITERS, WS_PT_ENERGY, WS_PT_COUNTS, WS_PT_SUMS,   // pilot_ot_principal_tree.hip
     WS_PT_PCOUNTS, WS_PT_PSUMS, WS_PT_PMSE, WS_PT_PART, WS_PT_OUT,
+    WS_RS_Y, WS_RS_INT, WS_RS_LL, WS_RS_REC, WS_RS_OUT,                          // pilot_ot_rank_sums.hip
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

@@ -1009,6 +1009,12 @@ class DeviceCSR(_Closing):
             self._handle(), _lib.iptr(codes), n_groups, None if cols is None else _lib.iptr(cols), n_sel, _lib.lptr(count), _lib.dptr(sums)))
         return count, sums
 
+    def rank_sums(self, codes, n_groups, cols=None):
+        """:func:`rank_sums` of the matrix, read from the column form: only a column's stored non-zero entries are sorted, the
+        zeros (implicit or stored) are one run.  ``(count, rank_sums, ties)``."""
+        codes, n_groups, cols, n_sel = _rank_sums_args(self.shape[0], self.shape[1], codes, n_groups, cols)
+        return _rank_sums_call("pilot_ot_csr_rank_sums", (self._handle(),), codes, n_groups, cols, n_sel)
+
     def densify(self, cols=None):
         """A rows x len(cols) :class:`DeviceMatrix` of the matrix's dtype holding the columns ``cols`` (distinct, any order;
         default: all), dense in HBM."""
@@ -1103,6 +1109,97 @@ def group_sums(Y, codes, n_groups, cols=None):
         Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_total, Y.ld, _lib.iptr(codes), n_groups,
         None if cols is None else _lib.iptr(cols), n_sel, _lib.lptr(count), _lib.dptr(sums)))
     return count, sums
+
+
+# ---- rank sums (K21; the Wilcoxon rank-sum test of scanpy's rank_genes_groups and the Kruskal-Wallis test) ---------------------
+RANK_SUMS_MAX_GROUPS = 1024
+RANK_SUMS_MAX_ROWS = 2 ** 21 - 1
+
+
+def rank_sums_limits():
+    """``(wave_max, wg_max, sort_tile)`` of :func:`rank_sums`: a column with at most ``wave_max`` non-zero used entries is ranked
+    by one wave, up to ``wg_max`` by one workgroup in LDS, a longer one in HBM through LDS tiles of ``sort_tile`` records."""
+    L = _lib.load()
+    return int(L.pilot_ot_rank_sums_wave_max()), int(L.pilot_ot_rank_sums_wg_max()), int(L.pilot_ot_rank_sums_sort_tile())
+
+
+def _rank_sums_args(n, n_total, codes, n_groups, cols):
+    """rank_sums' arguments checked on the host: (codes int32, n_groups, cols int32 or None, selected columns)"""
+    codes, n_groups, cols = _moment_args(n, n_total, codes, n_groups, None, cols, RANK_SUMS_MAX_GROUPS)
+    used = int(np.count_nonzero(codes >= 0))
+    if used > RANK_SUMS_MAX_ROWS:
+        raise NotImplementedError("rank_sums: %d used rows; the tie term t^3 - t is exact up to %d" % (used, RANK_SUMS_MAX_ROWS))
+    return codes, n_groups, cols, n_total if cols is None else cols.size
+
+
+def _rank_sums_call(symbol, head, codes, n_groups, cols, n_sel):
+    count, ties = np.empty(n_groups, dtype=np.int64), np.empty(n_sel, dtype=np.int64)
+    rank2 = np.empty((n_groups, n_sel), dtype=np.int64)
+    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_int(-1)
+    _lib.check(getattr(_lib.load(), symbol)(
+        *head, _lib.iptr(codes), n_groups, None if cols is None else _lib.iptr(cols), n_sel, _lib.lptr(count), _lib.lptr(rank2),
+        _lib.lptr(ties), ctypes.byref(bad_row), ctypes.byref(bad_col)))
+    return count, rank2 * 0.5, ties
+
+
+def rank_sums(Y, codes, n_groups, cols=None):
+    """K21: per selected column of ``Y``, the ranks of the used rows (``codes >= 0``; N of them) summed per group
+    (include/pilot_ot.h, "rank sums").  ``Y``, ``codes`` and ``cols`` are :func:`group_moments`'s; ``n_groups`` in 1..1024.  Within
+    a column equal values share the mean of their positions (``scipy.stats.rankdata(method="average")``); ``-0.0 == 0.0``, and in
+    a :class:`DeviceCSR` a stored zero ties with the implicit ones.  Returns ``(count, rank_sums, ties)``: ``n_groups`` int64, an
+    ``n_groups x columns`` float64 array of exact multiples of 1/2, and per column the int64 ``sum(t^3 - t)`` over its runs of
+    equal values.  The device works in integers alone, so the dense route, the sparse route and a repeated call return the same
+    arrays.  More than 2^21 - 1 used rows: NotImplementedError; a NaN or infinity in a used row of a selected column: ValueError
+    naming the first one; every other argument is checked before any device work (ValueError).  :func:`rank_sum_z` and
+    :func:`kruskal_h` turn the result into test statistics."""
+    if isinstance(Y, DeviceCSR):
+        return Y.rank_sums(codes, n_groups, cols=cols)
+    Y = _dense_arg(Y, "Y", mode="strict")
+    codes, n_groups, cols, n_sel = _rank_sums_args(Y.rows, Y.cols, codes, n_groups, cols)
+    return _rank_sums_call("pilot_ot_rank_sums", (Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld), codes, n_groups, cols,
+                           n_sel)
+
+
+def _rank_results(count, rank_sums, ties):
+    count = np.asarray(count, dtype=np.float64)
+    R, ties = np.asarray(rank_sums, dtype=np.float64), np.asarray(ties, dtype=np.float64)
+    if count.ndim != 1 or R.ndim != 2 or R.shape[0] != count.size or ties.shape != R.shape[1:]:
+        raise ValueError("count %s, rank_sums %s and ties %s are not one rank_sums result" % (count.shape, R.shape, ties.shape))
+    return count, R, ties, float(count.sum())
+
+
+def rank_sum_z(count, rank_sums, ties, tie_correct=False):
+    """The Wilcoxon rank-sum (Mann-Whitney) statistics of every group against the other used rows, from :func:`rank_sums`'s
+    result; pure numpy.  ``z = (R_g - n_g (N + 1) / 2) / sqrt(n_g (N - n_g) / 12 * ((N + 1) - c ties / (N (N - 1))))`` with
+    c = 1 for ``tie_correct`` and 0 without, and ``U = R_g - n_g (n_g + 1) / 2``; the two-sided p-value is
+    ``2 * scipy.stats.norm.sf(abs(z))``.  With the correction these are the values of
+    ``scipy.stats.mannwhitneyu(use_continuity=False, method="asymptotic")``.  Where the variance is zero (an all-equal column, an
+    empty group, a group holding every row) z = 0.  Returns ``(z, U)``, both ``n_groups x columns``."""
+    count, R, ties, N = _rank_results(count, rank_sums, ties)
+    n = count[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        spread = (N + 1) - (ties / (N * (N - 1)) if tie_correct else 0.0)
+        z = (R - n * (N + 1) / 2) / np.sqrt(n * (N - n) / 12 * spread)
+    z[~np.isfinite(z)] = 0.0
+    return z, R - n * (n + 1) / 2
+
+
+def kruskal_h(count, rank_sums, ties):
+    """The Kruskal-Wallis test over the groups that have rows, from :func:`rank_sums`'s result; numpy and scipy.
+    ``H = (12 / (N (N + 1)) * sum_g R_g^2 / n_g - 3 (N + 1)) / (1 - ties / (N^3 - N))``, ``p = chi2.sf(H, df)``, ``df`` = those
+    groups - 1: the values of ``scipy.stats.kruskal``.  An all-equal column gives H = p = NaN, as scipy does.  Returns
+    ``(H, p, df)``."""
+    from scipy import stats
+    count, R, ties, N = _rank_results(count, rank_sums, ties)
+    ssbn = np.zeros(R.shape[1])
+    for g in np.flatnonzero(count > 0):
+        ssbn += R[g] ** 2 / count[g]
+    df = int(np.count_nonzero(count > 0)) - 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        correction = 1.0 - ties / (N ** 3 - N)
+        H = (12.0 / (N * (N + 1)) * ssbn - 3 * (N + 1)) / correction
+    H[correction == 0] = np.nan
+    return H, stats.chi2.sf(H, df), df
 
 
 # ---- principal components (K15; scanpy's scale + tl.pca(svd_solver='arpack') of pilotpy's extract_annot_expression) ----------

@@ -1928,6 +1928,50 @@ def _two_group_fit(count, mean, m2, design, first):
     return mean[0] - mean[1], ave, m2[0] + m2[1], n - 2.0, np.sqrt(1.0 / n1 + 1.0 / n2)
 
 
+def _subgroup_selection(who, adata, cell_type, proportions, selected_genes, groups, label_name, sample_col, col_cell, normalization,
+                        n_top_genes, highly_variable_genes_):
+    """The cell, label and gene selection of the sub-group comparisons (``who`` names the caller in the errors): the cells of
+    ``cell_type`` take the ``label_name`` of their sample in ``proportions`` and the code of that label's position in ``groups``
+    (-1: another label, left out; ``groups=None``: every label that occurs, sorted); the matrix goes up once
+    (:func:`_cell_type_matrix`), the highly variable genes are taken over ALL the cell type's cells and ``selected_genes``
+    restricts and orders them.  Every check that needs no device comes before the upload.  Returns
+    ``(matrix, codes int32, cols, gene names, group names)``."""
+    genes = np.asarray(list(adata.var_names), dtype=object)
+    if selected_genes is not None:
+        pos = {g: i for i, g in enumerate(genes)}
+        unknown = [g for g in selected_genes if g not in pos]
+        if unknown:
+            raise KeyError("%s: selected_genes not in adata.var_names: %s" % (who, unknown))
+    label_of = _sample_labels(proportions, label_name)
+    rows = _cell_type_rows(adata, col_cell, cell_type)
+    samples = np.asarray(adata.obs[sample_col])[rows]
+    missing = [s for s in pd.unique(samples) if s not in label_of]
+    if missing:
+        raise KeyError("%s: samples of %r missing from proportions: %s" % (who, cell_type, missing))
+    labels = np.asarray([label_of[s] for s in samples], dtype=object)
+    if groups is None:
+        groups = sorted(pd.unique(labels), key=str)
+        if len(groups) < 2:
+            raise ValueError("%s: the cells of %r carry one label, %s" % (who, cell_type, groups))
+    codes = np.full(labels.size, -1, dtype=np.int32)
+    for g, name in enumerate(groups):                      # (the callers refuse a name given twice)
+        codes[labels == name] = g
+        if not (codes == g).any():
+            raise ValueError("%s: group %r has no cells of %r" % (who, name, cell_type))
+
+    D = _cell_type_matrix(adata, rows, normalization)
+    cols = np.arange(genes.size)
+    if highly_variable_genes_:
+        cols = np.flatnonzero(highly_variable_genes(D, n_top_genes)["highly_variable"].values)
+    if selected_genes is not None:
+        among = set(cols.tolist())
+        outside = [g for g in selected_genes if pos[g] not in among]
+        if outside:
+            raise KeyError("%s: selected_genes outside the highly variable genes: %s" % (who, outside))
+        cols = np.asarray([pos[g] for g in selected_genes], dtype=np.int64)
+    return D, codes, cols, genes, list(groups)
+
+
 def compute_diff_expressions(adata, cell_type, proportions, selected_genes=None, group1="Tumor 1", group2="Tumor 2",
                              label_name="Predicted_Labels", sample_col="sampleID", col_cell="cell_types", normalization=False,
                              n_top_genes=2000, highly_variable_genes_=True, design="reference"):
@@ -1966,36 +2010,9 @@ def compute_diff_expressions(adata, cell_type, proportions, selected_genes=None,
         raise ValueError("design=%r must be one of %s" % (design, ", ".join(map(repr, _DE_DESIGNS))))
     if group1 == group2:
         raise ValueError("group1 and group2 are both %r" % (group1,))
-    genes = np.asarray(list(adata.var_names), dtype=object)
-    if selected_genes is not None:
-        pos = {g: i for i, g in enumerate(genes)}
-        unknown = [g for g in selected_genes if g not in pos]
-        if unknown:
-            raise KeyError("compute_diff_expressions: selected_genes not in adata.var_names: %s" % unknown)
-    label_of = _sample_labels(proportions, label_name)
-    rows = _cell_type_rows(adata, col_cell, cell_type)
-    samples = np.asarray(adata.obs[sample_col])[rows]
-    missing = [s for s in pd.unique(samples) if s not in label_of]
-    if missing:
-        raise KeyError("compute_diff_expressions: samples of %r missing from proportions: %s" % (cell_type, missing))
-    labels = np.asarray([label_of[s] for s in samples], dtype=object)
-    codes = np.where(labels == group1, 0, np.where(labels == group2, 1, -1)).astype(np.int32)
-    for g, name in enumerate((group1, group2)):
-        if not (codes == g).any():
-            raise ValueError("compute_diff_expressions: group %r has no cells of %r" % (name, cell_type))
-
-    D = _cell_type_matrix(adata, rows, normalization)
-    cols = np.arange(genes.size)
-    if highly_variable_genes_:
-        cols = np.flatnonzero(highly_variable_genes(D, n_top_genes)["highly_variable"].values)
-    if selected_genes is not None:
-        among = set(cols.tolist())
-        outside = [g for g in selected_genes if pos[g] not in among]
-        if outside:
-            raise KeyError("compute_diff_expressions: selected_genes outside the highly variable genes: %s" % outside)
-        cols = np.asarray([pos[g] for g in selected_genes], dtype=np.int64)
-    every = cols.size == genes.size and np.array_equal(cols, np.arange(genes.size))      # (every column in order: the 16-byte reads)
-    count, mean, m2 = engine.group_moments(D, codes, 2, cols=None if every else cols.astype(np.int32))
+    D, codes, cols, genes, _ = _subgroup_selection("compute_diff_expressions", adata, cell_type, proportions, selected_genes, (group1, group2),
+                                                   label_name, sample_col, col_cell, normalization, n_top_genes, highly_variable_genes_)
+    count, mean, m2 = engine.group_moments(D, codes, 2, cols=_selected_or_every(cols, genes.size))
     del D
 
     G = cols.size
@@ -2012,6 +2029,184 @@ def compute_diff_expressions(adata, cell_type, proportions, selected_genes=None,
                        index=pd.Index(genes[cols], name="gene"))
     res.attrs["df_prior"], res.attrs["s2_prior"] = float(df_prior), float(s2_prior)
     return res
+
+
+def _selected_or_every(cols, n_vars):
+    """None when ``cols`` is every column in order (the calls then take their contiguous reads), else ``cols`` as int32"""
+    every = cols.size == n_vars and np.array_equal(cols, np.arange(n_vars))
+    return None if every else cols.astype(np.int32)
+
+
+def wilcoxon_diff_expressions(adata, cell_type, proportions, selected_genes=None, group1="Tumor 1", group2="Tumor 2",
+                              label_name="Predicted_Labels", sample_col="sampleID", col_cell="cell_types", normalization=False,
+                              n_top_genes=2000, highly_variable_genes_=True, tie_correct=True):
+    """The non-parametric companion of :func:`compute_diff_expressions`: per gene, the Wilcoxon rank-sum (Mann-Whitney) test of
+    the cells of ``cell_type`` in sub-group ``group1`` against those in ``group2``, with the same cell, label and gene selection.
+    The ranks are taken on the device among the cells of the two groups (``engine.rank_sums``), the means come from
+    ``engine.group_sums``, and the tail is ``engine.rank_sum_z``: with ``tie_correct`` (the default here) U, z and the p-value
+    are those of ``scipy.stats.mannwhitneyu(x1, x2, use_continuity=False, method="asymptotic")``.  A gene whose values are all
+    equal has z = 0, p = 1.  Returns a frame indexed by gene, in gene order: ``logFC`` (mean of group1 - mean of group2),
+    ``AveExpr``, ``U`` (of group1), ``z`` (positive: higher in group1), ``P.Value``, ``adj.P.Val`` (Benjamini-Hochberg).  Raised
+    before any device work: ValueError for equal group names or a group without cells, KeyError as
+    :func:`compute_diff_expressions`."""
+    from scipy import stats
+    if group1 == group2:
+        raise ValueError("group1 and group2 are both %r" % (group1,))
+    D, codes, cols, genes, _ = _subgroup_selection("wilcoxon_diff_expressions", adata, cell_type, proportions, selected_genes, (group1, group2),
+                                                   label_name, sample_col, col_cell, normalization, n_top_genes, highly_variable_genes_)
+    sel = _selected_or_every(cols, genes.size)
+    count, R, ties = engine.rank_sums(D, codes, 2, cols=sel)
+    sums = engine.group_sums(D, codes, 2, cols=sel)[1]
+    del D
+    n = count.astype(np.float64)[:, None]
+    mean = sums / n
+    z, U = engine.rank_sum_z(count, R, ties, tie_correct=tie_correct)
+    p = 2.0 * stats.norm.sf(np.abs(z[0]))
+    return pd.DataFrame({"logFC": mean[0] - mean[1], "AveExpr": (n[0] * mean[0] + n[1] * mean[1]) / n.sum(), "U": U[0], "z": z[0],
+                         "P.Value": p, "adj.P.Val": _bh_adjust(p)}, index=pd.Index(genes[cols], name="gene"))
+
+
+def kruskal_diff_expressions(adata, cell_type, proportions, groups=None, selected_genes=None, label_name="Predicted_Labels",
+                             sample_col="sampleID", col_cell="cell_types", normalization=False, n_top_genes=2000,
+                             highly_variable_genes_=True):
+    """The Kruskal-Wallis test, per gene, of the cells of ``cell_type`` over the patient sub-groups ``groups`` (default: every
+    label of ``label_name`` that a sample of the cell type carries, sorted) -- what :func:`clustering_emd` returns is often three
+    or more sub-groups, which the two-group tests cannot take at once.  Selection as :func:`compute_diff_expressions`; the ranks
+    among the cells of those groups come from ``engine.rank_sums``, H and its chi-square p-value from ``engine.kruskal_h``: the
+    values of ``scipy.stats.kruskal``.  A gene whose values are all equal has H = p = NaN, as in scipy, and is left out of the
+    Benjamini-Hochberg adjustment.  Returns a frame indexed by gene, in gene order: ``H``, ``df``, ``P.Value``, ``adj.P.Val`` and
+    one column ``mean(<group>)`` per group.  Raised before any device work: ValueError for fewer than two groups, a group named
+    twice or a group without cells, KeyError as :func:`compute_diff_expressions`."""
+    if groups is not None:
+        groups = list(groups)
+        if len(set(groups)) != len(groups):
+            raise ValueError("kruskal_diff_expressions: a group is named twice in %s" % (groups,))
+        if len(groups) < 2:
+            raise ValueError("kruskal_diff_expressions: %d group(s); the test compares at least two" % len(groups))
+    D, codes, cols, genes, groups = _subgroup_selection("kruskal_diff_expressions", adata, cell_type, proportions, selected_genes, groups,
+                                                        label_name, sample_col, col_cell, normalization, n_top_genes, highly_variable_genes_)
+    sel =_selected_or_every(cols, genes.size)
+    count, R, ties = engine.rank_sums(D, codes, len(groups), cols=sel)
+    sums = engine.group_sums(D, codes, len(groups), cols=sel)[1]
+    del D
+    H, p, df = engine.kruskal_h(count, R, ties)
+    adj = np.full(p.size, np.nan)
+    adj[np.isfinite(p)] = _bh_adjust(p[np.isfinite(p)])
+    out = {"H": H, "df": np.full(p.size, df, dtype=np.int64), "P.Value": p, "adj.P.Val": adj}
+    for g, name in enumerate(groups):
+        out["mean(%s)" % (name,)] = sums[g] / float(count[g])
+    return pd.DataFrame(out, index=pd.Index(genes[cols], name="gene"))
+
+
+_RGG_CORRECTIONS = ("benjamini-hochberg", "bonferroni")
+
+
+def rank_genes_groups(adata, groupby, groups="all", reference="rest", n_genes=None, method="wilcoxon", tie_correct=False,
+                      corr_method="benjamini-hochberg", genes=None, key_added=None):
+    """scanpy's ``tl.rank_genes_groups(method="wilcoxon")`` on the device: the marker genes of every group of
+    ``adata.obs[groupby]`` -- what names the clusters ``"0" .. "k-1"`` of :func:`louvain`, :func:`leiden` and
+    :func:`reclustering_data`.  Reads ``adata.X`` (dense, or scipy sparse: uploaded once as an ``engine.DeviceCSR`` and never made
+    dense); ``.raw`` is left alone.  scanpy is not installed where this library is built and tested, so the layout of the result
+    is UNPINNED; the statistic is pinned to scipy.
+
+    ``reference="rest"``: one ``engine.rank_sums`` call over all cells gives the rank-sum z of every group against all other
+    cells.  ``reference=<group>``: one call per tested group, the ranks taken among the cells of the two groups only.  The score
+    is z (``engine.rank_sum_z``; ``tie_correct`` as scanpy's, off by default), ``pvals = 2 norm.sf(|z|)``, ``pvals_adj`` is
+    Benjamini-Hochberg over the genes tested or ``min(p * genes tested, 1)`` for ``corr_method="bonferroni"``, and
+    ``logfoldchanges = log2((expm1(mean_group) + 1e-9) / (expm1(mean_other) + 1e-9))`` with the means from
+    ``engine.group_sums`` (log1p data, as scanpy assumes).  ``groups``: ``"all"`` (every group that has cells) or a list of
+    names; ``genes``: names or a boolean mask (default: all); per group the genes come in descending score, equal scores in
+    gene order, and the first ``n_genes`` are kept (default: all).
+
+    Writes ``adata.uns[key_added or "rank_genes_groups"]``: ``params`` and the record arrays ``names`` (object), ``scores``
+    (float32), ``pvals``, ``pvals_adj`` (float64), ``logfoldchanges`` (float32), one field per tested group.  Returns the tidy
+    frame ``group, names, scores, pvals, pvals_adj, logfoldchanges``.  ValueError before any device work: another ``method`` or
+    ``corr_method``, a missing ``groupby``, an unknown group or reference, a group without cells, nothing left to test."""
+    from scipy import stats
+    if method != "wilcoxon":
+        raise ValueError("rank_genes_groups: method=%r is not implemented, only 'wilcoxon'" % (method,))
+    if corr_method not in _RGG_CORRECTIONS:
+        raise ValueError("rank_genes_groups: corr_method=%r must be one of %s" % (corr_method, ", ".join(map(repr, _RGG_CORRECTIONS))))
+    if groupby not in adata.obs:
+        raise ValueError("rank_genes_groups: adata.obs has no column %r" % (groupby,))
+    if n_genes is not None and int(n_genes) < 1:
+        raise ValueError("rank_genes_groups: n_genes=%r must be positive" % (n_genes,))
+    labels = pd.Series(np.asarray(adata.obs[groupby])).astype("category") if not isinstance(adata.obs[groupby].dtype, pd.CategoricalDtype) \
+        else adata.obs[groupby]
+    names = [str(c) for c in labels.cat.categories]
+    cat = np.asarray(labels.cat.codes, dtype=np.int32)
+    sizes = np.bincount(cat[cat >= 0], minlength=len(names))
+    if len(names) > engine.RANK_SUMS_MAX_GROUPS:
+        raise ValueError("rank_genes_groups: %d groups in %r, at most %d" % (len(names), groupby, engine.RANK_SUMS_MAX_GROUPS))
+    index = {name: g for g, name in enumerate(names)}
+    if isinstance(groups, str) and groups == "all":
+        tested = [g for g in range(len(names)) if sizes[g] > 0]
+    else:
+        if isinstance(groups, (str, int)):
+            raise ValueError("rank_genes_groups: groups=%r must be 'all' or a list of group names" % (groups,))
+        unknown = [str(g) for g in groups if str(g) not in index]
+        if unknown:
+            raise ValueError("rank_genes_groups: groups not in adata.obs[%r]: %s" % (groupby, unknown))
+        tested = list(dict.fromkeys(index[str(g)] for g in groups))
+    ref = None
+    if reference != "rest":
+        if str(reference) not in index:
+            raise ValueError("rank_genes_groups: reference=%r is not a group of adata.obs[%r]" % (reference, groupby))
+        ref = index[str(reference)]
+        tested = [g for g in tested if g != ref]
+    empty = [names[g] for g in tested + ([] if ref is None else [ref]) if sizes[g] == 0]
+    if empty:
+        raise ValueError("rank_genes_groups: groups without cells: %s" % empty)
+    if not tested:
+        raise ValueError("rank_genes_groups: nothing to test (groups=%r, reference=%r)" % (groups, reference))
+    if ref is None and any(sizes[g] == sizes.sum() for g in tested):
+        raise ValueError("rank_genes_groups: one group holds every cell, there is no rest to test it against")
+    X = adata.X
+    n_vars = X.shape[1]
+    cols = _gene_columns(adata, genes, n_vars)
+    var_names = np.asarray(list(adata.var_names), dtype=object)
+    tested_genes = var_names if cols is None else var_names[cols]
+    G = tested_genes.size
+    keep = G if n_genes is None else min(int(n_genes), G)
+
+    Y = _sparse_rows(X, None) if _is_sparse(X) else engine.DeviceMatrix.upload(_dense_rows(X, slice(None)))
+    K = len(names)
+    sums = engine.group_sums(Y, cat, K, cols=cols)[1]
+    n = sizes.astype(np.float64)
+    if ref is None:
+        count, R, ties = engine.rank_sums(Y, cat, K, cols=cols)
+        z_all = engine.rank_sum_z(count, R, ties, tie_correct=tie_correct)[0]
+        total = sums.sum(axis=0)
+    out = {k: [] for k in ("names", "scores", "pvals", "pvals_adj", "logfoldchanges")}
+    for g in tested:
+        if ref is None:
+            z = z_all[g]
+            mean_other = (total - sums[g]) / (n.sum() - n[g])
+        else:
+            two = np.where(cat == g, 0, np.where(cat == ref, 1, -1)).astype(np.int32)
+            z = engine.rank_sum_z(*engine.rank_sums(Y, two, 2, cols=cols), tie_correct=tie_correct)[0][0]
+            mean_other = sums[ref] / n[ref]
+        p = 2.0 * stats.norm.sf(np.abs(z))
+        adj = _bh_adjust(p) if corr_method == "benjamini-hochberg" else np.minimum(p * G, 1.0)
+        lfc = np.log2((np.expm1(sums[g] / n[g]) + 1e-9) / (np.expm1(mean_other) + 1e-9))
+        order = np.argsort(-z, kind="stable")[:keep]
+        out["names"].append(tested_genes[order])
+        out["scores"].append(z[order].astype(np.float32))
+        out["pvals"].append(p[order])
+        out["pvals_adj"].append(adj[order])
+        out["logfoldchanges"].append(lfc[order].astype(np.float32))
+    del Y
+    fields = [names[g] for g in tested]
+    kinds = {"names": "O", "scores": "float32", "pvals": "float64", "pvals_adj": "float64", "logfoldchanges": "float32"}
+    result = {"params": {"groupby": groupby, "reference": reference, "method": method, "use_raw": False, "layer": None,
+                         "corr_method": corr_method, "tie_correct": bool(tie_correct)}}
+    for k, arrays in out.items():
+        result[k] = np.rec.fromarrays(arrays, dtype=[(f, kinds[k]) for f in fields])
+    adata.uns[key_added or "rank_genes_groups"] = result
+    frame = {"group": np.repeat(np.asarray(fields, dtype=object), keep)}
+    for k, arrays in out.items():
+        frame[k] = np.concatenate(arrays)
+    return pd.DataFrame(frame)
 
 
 def cell_type_diff_two_sub_patient_groups(proportions, cell_types, labels="Predicted_Labels", group1="Tumor 1", group2="Tumor 2"):

@@ -565,6 +565,43 @@ int pilot_ot_rank_sums_wave_max(void);
 int pilot_ot_rank_sums_wg_max(void);
 int pilot_ot_rank_sums_sort_tile(void);
 
+/* ---- negative-binomial GLM (K22): DESeq2's model (Love, Huber, Anders 2014) for the one design pilotpy's compute_pseudobulk_DE
+ * uses, `~ stage` (plot/pseudobulk_DE_analysis.py:96-159): an intercept plus a group indicator, for which every piece decouples by
+ * group.  DESeq2 is not installed where this library is built, so the rule is THIS LIBRARY'S STATEMENT, unpinned (DESIGN.md K22;
+ * restated in tests/nb_glm_restatement.py).  Y: m samples x n_genes, row-major (Y_is_device / dtype / ld as in
+ * pilot_ot_group_moments), c = rint(Y); codes[j] in 0 .. n_groups - 1 (host); size_factors[j] > 0 (host).  minDisp = 1e-8,
+ * maxDisp = max(10, m), minmu = 0.5.  All arithmetic is f64; every sum has one fixed order (the samples by group, then by index)
+ * and no atomic adds a floating-point value: the same call returns the same bits, from float32 and float64 storage of the same
+ * counts, from a host matrix and from HBM.
+ *
+ * pilot_ot_nb_dispersions: per gene, mu_j = max(s_j * mean_{i in g(j)} c_i / s_i, minmu) and x = log(alpha) maximising
+ *     L(x) = sum_j [lgamma(c_j + r) - lgamma(r) - (c_j + r) log1p(alpha mu_j) + c_j log(alpha mu_j)] - 1/2 sum_g log(sum_{j in g} w_j)
+ *            [- (x - log_prior_mean)^2 / (2 prior_var)],   r = 1 / alpha,  w_j = mu_j / (1 + alpha mu_j)
+ * (the Cox-Reid adjusted profile likelihood; the last term only with log_prior_mean != NULL) BY THIS SEARCH: six rounds of the
+ * 64-point grid x_i = lo + (hi - lo) i / 63, from [log minDisp, log maxDisp]; b = the first largest value (lowest index on ties);
+ * the next bracket is [x_max(b-1,0), x_min(b+1,63)].  A global search, not DESeq2's line search from a moments start.
+ * Out (host): log_disp, objective (n_genes; the last round's x_b and L(x_b)), fitted_mean (nullable; n_genes x n_groups, the
+ * normalised group means).  A gene of zeros, or one whose log_prior_mean is not finite, gets NaN in log_disp and objective.
+ * pilot_ot_nb_group_fits: with the gene's dispersion alpha (host; NaN leaves the gene out: q = w = NaN), per (gene, group) q = the
+ * root of sum_{j in g} (c_j - s_j q) / (1 + alpha s_j q) = 0 by safeguarded Newton / bisection steps in log q (stopped at
+ * |step| <= 1e-12, or after 100 steps with PILOT_OT_NB_NOT_CONVERGED), raised to minmu / max_{j in g} s_j if below
+ * (PILOT_OT_NB_FLOORED; a group of zeros ends there), and w = sum_{j in g} mu_j / (1 + alpha mu_j) with mu_j = max(s_j q, minmu).
+ * Out (host): q, w, steps, flags: n_genes x n_groups; *n_not_converged (nullable).
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n_genes < 1, dtype, ld < n_genes, m < 2, n_groups outside [2, m - 1], a code
+ * out of range, a group without samples, a size factor not positive and finite, with a prior a prior_var not positive and finite, a
+ * dispersion outside [minDisp, maxDisp]; after the check pass: a negative or non-finite count (the message names it; of
+ * pilot_ot_nb_dispersions also *bad_row / *bad_col, nullable, else -1: the lowest column, then the lowest row).
+ * PILOT_OT_ENOTSUP: m > INT_MAX; of pilot_ot_nb_dispersions m > pilot_ot_nb_glm_max_samples() (a gene is staged in LDS). */
+#define PILOT_OT_NB_NOT_CONVERGED 1
+#define PILOT_OT_NB_FLOORED 2
+int pilot_ot_nb_dispersions(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
+                            int n_groups, const double *size_factors, const double *log_prior_mean, double prior_var, double *log_disp,
+                            double *objective, double *fitted_mean, long long *bad_row, int *bad_col);
+int pilot_ot_nb_group_fits(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
+                           int n_groups, const double *size_factors, const double *dispersion, double *q, double *w, int *steps,
+                           int *flags, int *n_not_converged);
+int pilot_ot_nb_glm_max_samples(void);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

@@ -43,6 +43,7 @@ enum WsSlot {
     WS_PT_X, WS_PT_FLAGS, WS_PT_Y, WS_PT_YT, WS_PT_S, WS_PT_CENTRE, WS_PT_STATE, WS_PT_ITERS, WS_PT_ENERGY, WS_PT_COUNTS, WS_PT_SUMS,   // pilot_ot_principal_tree.hip
     WS_PT_PCOUNTS, WS_PT_PSUMS, WS_PT_PMSE, WS_PT_PART, WS_PT_OUT,
     WS_RS_Y, WS_RS_INT, WS_RS_LL, WS_RS_REC, WS_RS_OUT,                          // pilot_ot_rank_sums.hip
+    WS_NB_Y, WS_NB_INT, WS_NB_SF, WS_NB_BAD, WS_NB_PRIOR, WS_NB_OUT, WS_NB_FIT_INT,   // pilot_ot_nb_glm.hip
     WS_SLOTS
 };
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);

@@ -1202,6 +1202,209 @@ def kruskal_h(count, rank_sums, ties):
     return H, stats.chi2.sf(H, df), df
 
 
+# ---- negative-binomial GLM (K22; DESeq2's model for the one-factor design of pilotpy's compute_pseudobulk_DE) ------------------
+NB_MIN_DISP = 1e-8
+NB_MIN_MU = 0.5
+
+
+def nb_max_disp(m):
+    """``maxDisp = max(10, m)`` of m samples"""
+    return float(max(10, int(m)))
+
+
+def nb_clip(disp, m):
+    """``disp`` clipped to [minDisp, maxDisp]: the end points of :func:`nb_dispersions`' grid are the logs of the bounds, which
+    ``exp`` returns to within an ulp.  NaN stays."""
+    return np.clip(disp, NB_MIN_DISP, nb_max_disp(m))
+
+
+def nb_glm_limits():
+    """The most samples :func:`nb_dispersions` takes: a gene's counts and fitted means are staged in LDS."""
+    return int(_lib.load().pilot_ot_nb_glm_max_samples())
+
+
+def _nb_args(m, n_genes, codes, n_groups, size_factors):
+    """the design arguments of the two NB calls checked on the host: (codes int32, n_groups, size factors float64)"""
+    if isinstance(n_groups, bool) or int(n_groups) != n_groups:
+        raise ValueError("n_groups=%r must be an integer" % (n_groups,))
+    n_groups = int(n_groups)
+    if n_genes < 1:
+        raise ValueError("counts has no columns")
+    if m < 2:
+        raise ValueError("counts has %d rows: at least 2 samples" % m)
+    if not 2 <= n_groups <= m - 1:
+        raise ValueError("n_groups=%d must be in [2, m - 1 = %d]: a residual degree of freedom is needed" % (n_groups, m - 1))
+    codes = np.asarray(codes)
+    if codes.ndim != 1 or codes.size != m:
+        raise ValueError("codes has shape %s for %d samples" % (codes.shape, m))
+    if codes.dtype.kind not in "iu":
+        raise ValueError("codes must be integers, got %s" % codes.dtype)
+    if int(codes.min()) < 0 or int(codes.max()) >= n_groups:
+        raise ValueError("codes outside [0, %d)" % n_groups)
+    count = np.bincount(codes, minlength=n_groups)
+    if (count == 0).any():
+        raise ValueError("group %d has no sample" % int(np.flatnonzero(count == 0)[0]))
+    sf = np.ascontiguousarray(size_factors, dtype=np.float64)
+    if sf.shape != (m,):
+        raise ValueError("size_factors has shape %s for %d samples" % (sf.shape, m))
+    if not (np.isfinite(sf).all() and (sf > 0).all()):
+        raise ValueError("size_factors must be positive and finite")
+    return np.ascontiguousarray(codes, dtype=np.int32), n_groups, sf
+
+
+def _nb_bad_count(err, bad_row, bad_col):
+    """the ValueError of a bad count with its position as attributes"""
+    err.row, err.col = int(bad_row.value), int(bad_col.value)
+    return err
+
+
+def nb_dispersions(counts, codes, n_groups, size_factors, log_prior_mean=None, prior_var=None, return_info=False):
+    """K22: per gene (column) of ``counts`` (samples x genes, float32 / float64 numpy array, :class:`DeviceMatrix` or
+    :func:`device_columns` window; c = rint(counts)) the log dispersion of the negative-binomial model with one mean per group
+    (include/pilot_ot.h, "negative-binomial GLM"): the maximiser, by six rounds of a 64-point grid over
+    [log 1e-8, log max(10, m)], of the Cox-Reid adjusted profile likelihood at the fitted means
+    ``mu_j = max(s_j * mean_{i in g(j)} c_i / s_i, 0.5)`` -- with ``log_prior_mean`` (one per gene) and ``prior_var`` minus
+    ``(x - log_prior_mean)^2 / (2 prior_var)``, the MAP estimate.  A global search, not DESeq2's line search.  ``codes``: the group
+    of every sample, each of 0 .. n_groups - 1 used, ``2 <= n_groups <= m - 1``; ``size_factors`` positive.  Returns the float64
+    log dispersions; with ``return_info`` also a dict: ``objective`` (the likelihood there) and ``fitted_mean`` (genes x groups,
+    the normalised group means).  A gene of zeros gives NaN.  The same bits from a repeated call, from float32 and float64 storage
+    and from host and device matrices.  More than :func:`nb_glm_limits` samples: NotImplementedError; a negative or non-finite
+    count: ValueError naming its row and column; every other argument is checked before any device work (ValueError)."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    codes, n_groups, sf = _nb_args(Y.rows, Y.cols, codes, n_groups, size_factors)
+    if (log_prior_mean is None) != (prior_var is None):
+        raise ValueError("log_prior_mean and prior_var come together")
+    if log_prior_mean is not None:
+        log_prior_mean = np.ascontiguousarray(log_prior_mean, dtype=np.float64)
+        if log_prior_mean.shape != (Y.cols,):
+            raise ValueError("log_prior_mean has shape %s for %d genes" % (log_prior_mean.shape, Y.cols))
+        prior_var = float(prior_var)
+        if not (np.isfinite(prior_var) and prior_var > 0):
+            raise ValueError("prior_var=%r must be positive and finite" % (prior_var,))
+    limit = nb_glm_limits()
+    if Y.rows > limit:
+        raise NotImplementedError("nb_dispersions: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    x, objective = np.empty(Y.cols), np.empty(Y.cols)
+    fitted = np.empty((Y.cols, n_groups)) if return_info else None
+    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_int(-1)
+    try:
+        _lib.check(_lib.load().pilot_ot_nb_dispersions(
+            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), n_groups, _lib.dptr(sf),
+            None if log_prior_mean is None else _lib.dptr(log_prior_mean), 0.0 if prior_var is None else prior_var, _lib.dptr(x),
+            _lib.dptr(objective), None if fitted is None else _lib.dptr(fitted), ctypes.byref(bad_row), ctypes.byref(bad_col)))
+    except ValueError as err:
+        raise _nb_bad_count(err, bad_row, bad_col)
+    return (x, {"objective": objective, "fitted_mean": fitted}) if return_info else x
+
+
+def nb_group_fits(counts, codes, n_groups, size_factors, dispersion, return_info=False):
+    """K22: per (gene, group) the maximum-likelihood normalised mean ``q`` of the negative-binomial model at the gene's
+    ``dispersion`` -- the root of ``sum_{j in g} (c_j - s_j q) / (1 + alpha s_j q) = 0``, raised to ``0.5 / max_{j in g} s_j`` if
+    below -- and ``w = sum_{j in g} mu_j / (1 + alpha mu_j)`` with ``mu_j = max(s_j q, 0.5)``, the diagonal of ``X^T W X`` by
+    group (include/pilot_ot.h).  ``counts``, ``codes``, ``n_groups`` and ``size_factors`` are :func:`nb_dispersions`'s;
+    ``dispersion``: one per gene in [1e-8, max(10, m)], NaN leaves the gene out (NaN results).  Returns ``(q, w)``, both genes x
+    groups; with ``return_info`` also a dict: ``steps``, ``flags`` (``_lib.NB_NOT_CONVERGED``, ``_lib.NB_FLOORED``) and
+    ``n_not_converged``.  Errors as :func:`nb_dispersions` (no limit on the samples)."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    codes, n_groups, sf = _nb_args(Y.rows, Y.cols, codes, n_groups, size_factors)
+    alpha = np.ascontiguousarray(dispersion, dtype=np.float64)
+    if alpha.shape != (Y.cols,):
+        raise ValueError("dispersion has shape %s for %d genes" % (alpha.shape, Y.cols))
+    given = alpha[~np.isnan(alpha)]
+    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(Y.rows)):
+        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(Y.rows)))
+    q, w = np.empty((Y.cols, n_groups)), np.empty((Y.cols, n_groups))
+    steps, flags = np.empty((Y.cols, n_groups), dtype=np.int32), np.empty((Y.cols, n_groups), dtype=np.int32)
+    bad = ctypes.c_int(0)
+    _lib.check(_lib.load().pilot_ot_nb_group_fits(
+        Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), n_groups, _lib.dptr(sf), _lib.dptr(alpha),
+        _lib.dptr(q), _lib.dptr(w), _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad)))
+    return (q, w, {"steps": steps, "flags": flags, "n_not_converged": bad.value}) if return_info else (q, w)
+
+
+def _nb_used(disp):
+    """the genes the trend and the prior variance are fitted on: a gene-wise estimate of at least 100 minDisp"""
+    disp = np.asarray(disp, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(disp) & (disp >= 100 * NB_MIN_DISP)
+
+
+def nb_trend(base_mean, disp, fit_type="parametric"):
+    """The dispersion trend over the genes with ``disp >= 1e-6`` (step 4 of DESIGN.md K22); pure numpy.  ``"parametric"``:
+    DESeq2's ``a0 + a1 / base_mean`` from (0.1, 1): every pass keeps the genes with ``1e-4 < disp / fitted < 15`` and fits a
+    Gamma-family identity-link GLM on them by IRLS (weights 1 / fitted^2, run until the coefficients move by less than 1e-14
+    relative), until ``sum(log(new / old)^2) < 1e-6``.  A non-positive coefficient or more than 10 passes: ValueError (DESeq2
+    falls back to a local regression there; here ask for ``fit_type="mean"``).  ``"mean"``: one constant, the mean of the used
+    estimates.  Returns ``(fitted, info)``: the trend at every gene's ``base_mean`` and a dict with ``fit_type``,
+    ``coefficients`` (a0, a1), ``used`` (the mask of the last fit) and ``passes``."""
+    mean, disp = np.asarray(base_mean, dtype=np.float64), np.asarray(disp, dtype=np.float64)
+    if mean.ndim != 1 or mean.shape != disp.shape:
+        raise ValueError("base_mean %s and disp %s: one of each per gene" % (mean.shape, disp.shape))
+    if fit_type not in ("parametric", "mean"):
+        raise ValueError("fit_type=%r must be 'parametric' or 'mean'" % (fit_type,))
+    use = _nb_used(disp)
+    if not use.any():
+        raise ValueError("fit_type=%r: no gene has a dispersion estimate of at least %g" % (fit_type, 100 * NB_MIN_DISP))
+    if fit_type == "mean":
+        a0 = float(disp[use].mean())
+        return np.where(np.isfinite(mean), a0, np.nan), {"fit_type": "mean", "coefficients": (a0, 0.0), "used": use, "passes": 0}
+    failed = "fit_type='parametric': the dispersion trend a0 + a1 / mean did not fit (%s); use fit_type='mean'"
+    inv = np.zeros_like(mean)
+    inv[use] = 1.0 / mean[use]
+    coefs = np.array([0.1, 1.0])
+    for passes in range(1, 11):
+        ratio = np.where(use, disp, np.nan) / (coefs[0] + coefs[1] * inv)
+        with np.errstate(invalid="ignore"):
+            good = use & (ratio > 1e-4) & (ratio < 15)
+        if np.count_nonzero(good) < 2:
+            raise ValueError(failed % "fewer than two genes within 1e-4 < disp / fitted < 15")
+        y, z = disp[good], inv[good]
+        new = coefs.copy()
+        for _ in range(200):
+            f = new[0] + new[1] * z
+            if not (f > 0).all():
+                raise ValueError(failed % "a fitted value is not positive")
+            wt = 1.0 / (f * f)
+            s0, s1, s2, t0, t1 = wt.sum(), (wt * z).sum(), (wt * z * z).sum(), (wt * y).sum(), (wt * z * y).sum()
+            det = s0 * s2 - s1 * s1
+            nxt = np.array([(t0 * s2 - t1 * s1) / det, (s0 * t1 - s1 * t0) / det])
+            moved = np.abs(nxt - new).max() <= 1e-14 * np.abs(nxt).max()
+            new = nxt
+            if moved:
+                break
+        if not (np.isfinite(new).all() and (new > 0).all()):
+            raise ValueError(failed % ("a coefficient is not positive: %r" % (tuple(new),)))
+        change = float((np.log(new / coefs) ** 2).sum())
+        coefs = new
+        if change < 1e-6:
+            break
+    else:
+        raise ValueError(failed % "more than 10 passes")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fitted = coefs[0] + coefs[1] / mean
+    return fitted, {"fit_type": "parametric", "coefficients": (float(coefs[0]), float(coefs[1])), "used": good, "passes": passes}
+
+
+def nb_prior_var(log_disp, log_trend, m, k):
+    """The width of the log-normal dispersion prior (step 5 of DESIGN.md K22); numpy and scipy.  Over the genes with
+    ``exp(log_disp) >= 1e-6``: ``rho = log_disp - log_trend``, ``var_log_disp = (1.4826 median|rho - median rho|)^2`` and
+    ``prior_var = max(var_log_disp - trigamma((m - k) / 2), 0.25)`` -- the same formula for ``m - k <= 3``, where DESeq2
+    simulates.  Returns ``(prior_var, var_log_disp)``."""
+    from scipy import special
+    x, t = np.asarray(log_disp, dtype=np.float64), np.asarray(log_trend, dtype=np.float64)
+    if x.ndim != 1 or x.shape != t.shape:
+        raise ValueError("log_disp %s and log_trend %s: one of each per gene" % (x.shape, t.shape))
+    if m - k < 1:
+        raise ValueError("m=%d samples in k=%d groups leave no residual degree of freedom" % (m, k))
+    with np.errstate(over="ignore", invalid="ignore"):
+        use = _nb_used(np.exp(x)) & np.isfinite(t)
+    if not use.any():
+        raise ValueError("no gene has a dispersion estimate of at least %g" % (100 * NB_MIN_DISP))
+    rho = x[use] - t[use]
+    var_log_disp = float((1.4826 * np.median(np.abs(rho - np.median(rho)))) ** 2)
+    return max(var_log_disp - float(special.polygamma(1, (m - k) / 2.0)), 0.25), var_log_disp
+
+
 # ---- principal components (K15; scanpy's scale + tl.pca(svd_solver='arpack') of pilotpy's extract_annot_expression) ----------
 PCA_MAX_COMPS = 64
 

@@ -31,6 +31,8 @@ highly_variable_genes,                         scanpy's pp.highly_variable_genes
 cell_type_diff_two_sub_patient_groups          plot/ploting.py:460-556 (the table, without the plot or the file)
 pseudobulk_counts, pseudobulk_inputs,          plot/pseudobulk_DE_analysis.py:590-610 (get_pseudobulk_DE's aggregation and the
 deseq2_size_factors                            inputs of its R calls) and DESeq2's median-of-ratios size factors restated
+deseq2_dispersions, compute_pseudobulk_DE,     plot/pseudobulk_DE_analysis.py:96-159, 628-646 (DESeq2's NB GLM for `~ stage` restated:
+get_pseudobulk_DE                              dispersions, Wald test, BH; no apeglm shrinkage, rlog, plots, files or R)
 pca, extract_annot_expression                  Trajectory.py:171-228 (scanpy's normalize_total / log1p / scale / tl.pca restated;
                                                no reclustering)
 neighbors                                      Trajectory.py:217-220, 1045-1060 (scanpy's pp.neighbors: the exact kNN graph of the
@@ -2284,8 +2286,8 @@ def pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col="cell_types"
     """``(cluster_counts, cluster_metadata)`` as ``get_pseudobulk_DE`` hands them to DESeq2 (plot/pseudobulk_DE_analysis.py:
     597-610): the samples x genes sums of ``cell_type`` (:func:`pseudobulk_counts`), the rows of ``proportion_df`` for those
     samples with the ``stage`` column (a copy of ``cluster_col``), ``remove_samples`` dropped from both, the metadata in the
-    counts' order, and the genes that are zero in every remaining sample dropped.  No plots, CSV files or R: ``rlog``, ``DESeq()``
-    and ``lfcShrink`` stay in R, and this pair is what the reference's ``compute_pseudobulk_DE`` takes, unchanged.  A sample of the
+    counts' order, and the genes that are zero in every remaining sample dropped.  No plots, CSV files or R: this pair is what the
+    reference's ``compute_pseudobulk_DE`` takes, unchanged, and :func:`compute_pseudobulk_DE` here takes it too.  A sample of the
     cell type that ``proportion_df`` lacks raises KeyError, as in the reference."""
     cluster_counts = pseudobulk_counts(adata, cell_type, celltype_col, sample_col)
     n_cells = cluster_counts.attrs["n_cells"]
@@ -2321,3 +2323,143 @@ def deseq2_size_factors(cluster_counts):
         raise ValueError("deseq2_size_factors: every gene contains at least one zero, cannot compute log geometric means")
     sf = np.exp(np.median(logc[:, use] - lg[use], axis=1))
     return pd.Series(sf, index=getattr(cluster_counts, "index", None))
+
+
+# ---- pseudobulk differential expression: DESeq2's NB GLM for `~ stage` (plot/pseudobulk_DE_analysis.py:96-159, 628-646) ----------
+def _nb_counts(cluster_counts, who):
+    """the samples x genes table as a C-contiguous float32 / float64 array (the device rounds it) and its gene names"""
+    c = np.asarray(cluster_counts)
+    if c.ndim != 2:
+        raise ValueError("%s: a samples x genes frame, got shape %s" % (who, c.shape))
+    if c.dtype not in (np.float32, np.float64):
+        c = c.astype(np.float64)
+    names = getattr(cluster_counts, "columns", None)
+    return np.ascontiguousarray(c), pd.Index(names if names is not None else np.arange(c.shape[1]))
+
+
+def _nb_dispersion_table(c, genes, codes, k, sf, fit_type):
+    """steps 1-5 of DESIGN.md K22 for the samples x genes array c: the frame of :func:`deseq2_dispersions`"""
+    m = c.shape[0]
+    x_gene = engine.nb_dispersions(c, codes, k, sf)
+    q = np.rint(c.astype(np.float64)) / sf[:, None]
+    base_mean, base_var = q.mean(axis=0), q.var(axis=0, ddof=1)
+    base_mean[np.isnan(x_gene)] = np.nan
+    base_var[np.isnan(x_gene)] = np.nan
+    disp_gene = engine.nb_clip(np.exp(x_gene), m)               # (the grid's end points are the bounds up to an ulp)
+    fit, trend = engine.nb_trend(base_mean, disp_gene, fit_type)
+    log_fit = np.log(fit)
+    prior_var, var_log_disp = engine.nb_prior_var(x_gene, log_fit, m, k)
+    x_map = engine.nb_dispersions(c, codes, k, sf, log_prior_mean=log_fit, prior_var=prior_var)
+    with np.errstate(invalid="ignore"):
+        outlier = x_gene > log_fit + 2.0 * np.sqrt(var_log_disp)
+    disp_map = engine.nb_clip(np.exp(x_map), m)
+    out = pd.DataFrame({"baseMean": base_mean, "baseVar": base_var, "dispGeneEst": disp_gene, "dispFit": fit, "dispMAP": disp_map,
+                        "dispersion": np.where(outlier, disp_gene, disp_map), "dispOutlier": outlier}, index=genes)
+    out.attrs.update(trend=trend, prior_var=prior_var, var_log_disp=var_log_disp)
+    return out
+
+
+def _nb_size_factors(cluster_counts, size_factors, m):
+    sf = deseq2_size_factors(cluster_counts) if size_factors is None else size_factors
+    sf = np.ascontiguousarray(sf, dtype=np.float64)
+    if sf.shape != (m,):
+        raise ValueError("size_factors has shape %s for %d samples" % (sf.shape, m))
+    return sf
+
+
+def deseq2_dispersions(cluster_counts, groups, size_factors=None, fit_type="parametric"):
+    """DESeq2's dispersion estimates (``estimateDispersions``; Love, Huber, Anders 2014) of a samples x genes count frame under
+    the one-factor design ``~ groups`` (one label per sample; at least two groups and one residual degree of freedom), on the
+    device (``engine.nb_dispersions``).  DESeq2 is not installed where this library is built and tested: the rule
+    is this library's statement, UNPINNED, like limma's.  With c = rint(counts), ``size_factors`` (default
+    :func:`deseq2_size_factors` of the table) and ``q = c / s``: ``baseMean`` / ``baseVar`` the mean and ddof-1 variance of q;
+    ``dispGeneEst`` the maximiser of the Cox-Reid adjusted profile likelihood at the group-mean fitted values, clipped to
+    [1e-8, max(10, m)]; ``dispFit`` the trend (``engine.nb_trend``: ``"parametric"`` a0 + a1 / baseMean by Gamma-GLM passes, which
+    raises ValueError where DESeq2 would fall back to a local regression, or ``"mean"``); ``dispMAP`` the maximiser with the
+    log-normal prior around the trend (``engine.nb_prior_var``); ``dispOutlier``: dispGeneEst more than two residual standard
+    deviations above the trend, where ``dispersion`` keeps dispGeneEst, else dispMAP.  A gene of zeros has NaN everywhere (and
+    dispOutlier False).  ``attrs``: ``trend`` (fit_type, coefficients, the genes of the last fit, passes), ``prior_var``,
+    ``var_log_disp``.
+
+    Deviations from DESeq2: the dispersion search is global (six rounds of a 64-point grid) where DESeq2 runs a line search from a
+    moments start, so on a multimodal gene the two can differ; no Cook's-distance handling; for ``m - k <= 3`` the same
+    prior-variance formula is used, where DESeq2 simulates."""
+    c, genes = _nb_counts(cluster_counts, "deseq2_dispersions")
+    uniq, codes = np.unique(np.asarray(groups), return_inverse=True)
+    codes = np.ravel(codes)
+    if codes.shape != (c.shape[0],):
+        raise ValueError("deseq2_dispersions: %d group labels for %d samples" % (codes.size, c.shape[0]))
+    sf = _nb_size_factors(cluster_counts, size_factors, c.shape[0])
+    return _nb_dispersion_table(c, genes, codes.astype(np.int32), len(uniq), sf, fit_type)
+
+
+def _nb_wald_table(genes, table, q, w):
+    """the host tail of the Wald test: group 1 over group 0 of the fits (q, w), rows ordered by padj (NaN last, stable)"""
+    from scipy import stats
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lfc = np.log2(q[:, 1]) - np.log2(q[:, 0])                   # (as a difference: swapping the groups negates it exactly)
+        se = np.log2(np.e) * np.sqrt(1.0 / w[:, 0] + 1.0 / w[:, 1])
+        stat = lfc / se
+    p = 2.0 * stats.norm.sf(np.abs(stat))
+    padj = np.full(p.shape, np.nan)
+    ok = ~np.isnan(p)
+    padj[ok] = _bh_adjust(p[ok])
+    out = pd.DataFrame({"gene": np.asarray(genes), "baseMean": table["baseMean"].to_numpy(), "log2FoldChange": lfc, "lfcSE": se,
+                        "stat": stat, "pvalue": p, "padj": padj, "dispersion": table["dispersion"].to_numpy()})
+    return out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
+
+
+def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=None, group2=None, cluster_col=None, fit_type="parametric"):
+    """The reference's ``compute_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:96-159) without R: the negative-binomial Wald
+    test of DESeq2 for the design ``~ stage`` between two patient sub-groups, on the device.  Takes :func:`pseudobulk_inputs`'
+    pair unchanged; the samples of ``group1`` and ``group2`` (by ``cluster_metadata[cluster_col]``) are selected first, as the
+    reference does, so the size factors (:func:`deseq2_size_factors`) and the dispersions (:func:`deseq2_dispersions`) come from
+    those samples only.  Then per gene and group the maximum-likelihood normalised mean at the final dispersion
+    (``engine.nb_group_fits``) and, on the host, ``log2FoldChange = log2(mean_group2) - log2(mean_group1)``,
+    ``lfcSE = log2(e) sqrt(1 / W_1 + 1 / W_2)``, ``stat``, ``pvalue = 2 norm.sf(|stat|)`` and the Benjamini-Hochberg ``padj`` over
+    the genes with a p-value.  Returns ONE frame -- ``gene, baseMean, log2FoldChange, lfcSE, stat, pvalue, padj, dispersion`` --
+    ordered by ``padj`` (NaN last, ties in gene order: the reference's ``arrange(padj)``); a gene that is zero in every selected
+    sample has NaN in every numeric column.  ``attrs``: ``dispersions`` (the frame of :func:`deseq2_dispersions`),
+    ``size_factors``, ``n_not_converged``.
+
+    Deviations from the reference's call, which is unpinned here (no DESeq2 where this library is tested): no apeglm shrinkage --
+    ``log2FoldChange`` is the maximum-likelihood estimate where ``lfcShrink`` returns a shrunken one, and ``lfcSE`` its Wald
+    standard error; no ``rlog``; no Cook's-distance outlier handling; no independent filtering, ``padj`` is plain BH; no beta
+    ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the formula where DESeq2 simulates; the
+    reference returns R's list (the frame at index 1), this returns the frame.  Fewer than three selected samples, or a group
+    without samples: ValueError before any device work."""
+    if cluster_col is None or cluster_col not in cluster_metadata.columns:
+        raise ValueError("compute_pseudobulk_DE: cluster_col=%r is not a column of cluster_metadata" % (cluster_col,))
+    stage = cluster_metadata[cluster_col]
+    if group1 == group2:
+        raise ValueError("compute_pseudobulk_DE: group1 and group2 are both %r" % (group1,))
+    meta = cluster_metadata[(stage == group1) | (stage == group2)]
+    counts = cluster_counts.loc[meta.index]
+    codes = (meta[cluster_col] == group2).to_numpy().astype(np.int32)
+    n2 = int(codes.sum())
+    if n2 == 0 or n2 == codes.size:
+        raise ValueError("compute_pseudobulk_DE: no sample of %r" % ((group2 if n2 == 0 else group1),))
+    if codes.size < 3:
+        raise ValueError("compute_pseudobulk_DE: %d samples in two groups leave no residual degree of freedom" % codes.size)
+    c, genes = _nb_counts(counts, "compute_pseudobulk_DE")
+    sf = _nb_size_factors(counts, None, c.shape[0])
+    table = _nb_dispersion_table(c, genes, codes, 2, sf, fit_type)
+    q, w, info = engine.nb_group_fits(c, codes, 2, sf, table["dispersion"].to_numpy(), return_info=True)
+    out = _nb_wald_table(genes, table, q, w)
+    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=info["n_not_converged"])
+    return out
+
+
+def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
+                      remove_samples=()):
+    """The numbers of the reference's ``get_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:506-666) in one process with no R:
+    :func:`pseudobulk_inputs` of ``cell_type``, then :func:`compute_pseudobulk_DE` for every pair of
+    ``itertools.combinations(np.unique(proportion_df[cluster_col]), 2)``.  Returns ``{"<g2>vs<g1>": frame}`` (the names of the
+    reference's ``_DE.csv`` files; the fold change is g2 over g1).  No plots, no files, no rlog PCA, no enrichment; the deviations
+    of :func:`compute_pseudobulk_DE` apply."""
+    import itertools
+    cluster_counts, cluster_metadata = pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col, sample_col, cluster_col, remove_samples)
+    out = {}
+    for g1, g2 in itertools.combinations(np.unique(proportion_df[cluster_col]), 2):
+        out["%svs%s" % (g2, g1)] = compute_pseudobulk_DE(cluster_counts, cluster_metadata, group1=g1, group2=g2, cluster_col=cluster_col)
+    return out

@@ -15,10 +15,13 @@ struct pilot_ot_plan {
     void *img;         // 3 operand images, sized for f64 at this K
     void *p_slot;      // N x KP proportions in accumulator-slot order (f32 or f64; sized for f64)
     int *track_list;   // N x N
-    int *ctrl;         // control block of a call: CTRL_BLOCK_INTS ints, slots named next to CTRL_INTS in sinkhorn_layout.hpp
+    int *ctrl;         // TWO control blocks of CTRL_BLOCK_INTS ints each (slots named next to CTRL_INTS in sinkhorn_layout.hpp), zeroed at creation.
+                       // An ordinary grid call works on block ctrl_par and its prep kernel zeroes the other one for the call after it;
+                       // the calls that keep a memset of their own (the wide kernel, a captured graph) work on block 0
+    int ctrl_par;      // block of the next ordinary grid call; flips when that call's prep launch has been issued
     int *order_list;   // N x N: longest-first work order of the fast launch
     unsigned char *order_bucket;  // N x N
-    int *order_hist;   // ctrl + CTRL_ORDER_HIST
+    int *order_tiles;  // ORDER_NB bucket counts per order tile of the prep kernel (order_tile_count(N, N) tiles), read by the scatter
     int *flags_ws;     // N x N per-pair flags when the caller passes none
     int *emd_counter;  // 1: dynamic pair queue of the exact-EMD kernel
     double *f_slab;    // exact-EMD flow values: one K*K block per resident wave (per 16-lane group of a wave for K <= 16); allocated by the

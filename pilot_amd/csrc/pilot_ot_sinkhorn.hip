@@ -83,7 +83,7 @@ PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
     pl->img = nullptr; pl->p_slot = nullptr; pl->track_list = nullptr; pl->ctrl = nullptr;
     pl->emd_counter = nullptr; pl->f_slab = nullptr; pl->f_slab_bytes = 0; pl->emdg_slab = nullptr; pl->emdg_wgs = 0; pl->n_cu = 256; pl->kws = nullptr; pl->generic_wgs = 0; pl->nan_list = nullptr;
     pl->wide_rec = nullptr; pl->wide_rec_n = 0;
-    pl->order_list = nullptr; pl->order_bucket = nullptr; pl->order_hist = nullptr;
+    pl->order_list = nullptr; pl->order_bucket = nullptr; pl->order_tiles = nullptr; pl->ctrl_par = 0;
     pl->flags_ws = nullptr;
     pl->timing = 0; pl->n_timed = 0; pl->n_calls = 0;
     pl->graph_mode = 0; pl->gkey_seen = 0; pl->gstream = nullptr; pl->gexec = nullptr;
@@ -112,7 +112,11 @@ PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
         if (e == hipSuccess) e = hipMalloc(&pl->p_slot, p_bytes);
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->track_list), sizeof(int) * (size_t)N * N);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->ctrl), pilot::CTRL_BLOCK_INTS * sizeof(int));
+    // (two control blocks, both zero from here on whenever a call finds them: see run_grid)
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->ctrl), 2 * pilot::CTRL_BLOCK_INTS * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(pl->ctrl, 0, 2 * pilot::CTRL_BLOCK_INTS * sizeof(int));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // (the first call may come on a stream that does not wait for the null stream)
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_tiles), sizeof(int) * pilot::ORDER_NB * (size_t)pilot::order_tile_count(N, N));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_list), sizeof(int) * (size_t)N * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->order_bucket), (size_t)N * N);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl->emd_counter), pilot::emd_counter_bytes());
@@ -126,7 +130,6 @@ PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
         pilot_ot_plan_destroy(pl);
         return fail(PILOT_OT_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
     }
-    pl->order_hist = pl->ctrl + pilot::CTRL_ORDER_HIST;
     *plan = pl;
     return PILOT_OT_OK;
 }
@@ -146,6 +149,7 @@ PILOT_API int pilot_ot_plan_destroy(pilot_ot_plan *pl) {
     if (pl->ctrl) (void)hipFree(pl->ctrl);
     if (pl->order_list) (void)hipFree(pl->order_list);
     if (pl->order_bucket) (void)hipFree(pl->order_bucket);
+    if (pl->order_tiles) (void)hipFree(pl->order_tiles);
     if (pl->flags_ws) (void)hipFree(pl->flags_ws);
     if (pl->emd_counter) (void)hipFree(pl->emd_counter);
     if (pl->f_slab) (void)hipFree(pl->f_slab);
@@ -184,10 +188,19 @@ int check_grid_args(int N, int K, double reg, int num_iter_max, double stop_thr,
 // go to the reference-semantics kernel (generic_kernels.hpp), which rebuilds the absorbed kernel like POT.
 constexpr double MAX_COST_OVER_REG = PILOT_OT_MAX_COST_OVER_REG;
 
-// list / list_len (device, nullable): only the listed pairs (NaN hand-over of the fast kernels); queue: zeroed counter
+// The two control blocks of a plan.  Both are zero when the plan is made.  An ordinary grid call (run_grid outside graph capture)
+// works on block ctrl_par and has its prep kernel zero the other one, which nothing reads meanwhile; the parity flips once
+// that prep launch is issued, so the next call finds its block zero without a memset.  A call that returns before that launch
+// (argument error, empty row range, a shape handed to the POT-literal kernel) leaves the parity alone.
+int *ctrl_block(const pilot_ot_plan *pl, int which) { return pl->ctrl + (size_t)which * pilot::CTRL_BLOCK_INTS; }
+// The block that the next ordinary call does not read and zeroes itself: where a POT-literal call of its own keeps its queue head.
+int *ctrl_spare(const pilot_ot_plan *pl) { return ctrl_block(pl, pl->ctrl_par ^ 1); }
+
+// list / list_len (device, nullable): only the listed pairs (NaN hand-over of the fast kernels) with `queue`, their zeroed counter.
+// Without a list: a call of its own, which zeroes and uses the slot CTRL_GENERIC_HEAD of the control block `own`.
 int run_generic(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double *d_P, const double *d_M, double reg, int num_iter_max, double stop_thr, double tau,
                 int check_period, int row_begin, int n_rows, int row_step, double *d_emd, int *d_iters, double *d_err, int *d_flags,
-                hipStream_t s, const int *list = nullptr, const int *list_len = nullptr, int *queue = nullptr) {
+                hipStream_t s, int *own, const int *list = nullptr, const int *list_len = nullptr, int *queue = nullptr) {
     const int N = pl->N, K = pl->K;
     const int n_pairs = n_rows * N;
     if (n_pairs == 0) return PILOT_OT_OK;
@@ -205,7 +218,7 @@ int run_generic(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const doub
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pl->kws), per * wgs));
         pl->generic_wgs = wgs;
     }
-    if (!queue) { queue = pl->ctrl + pilot::CTRL_GENERIC_HEAD; HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), s)); }
+    if (!queue) { queue = own + pilot::CTRL_GENERIC_HEAD; HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), s)); }
     pilot::GenericParams g;
     g.P = d_P; g.M = d_M; g.N = N; g.K = K; g.n_pairs = n_pairs; g.row_begin = row_begin; g.row_step = row_step;
     g.reg = reg; g.tau = tau; g.stop_thr = stop_thr; g.max_iter = num_iter_max; g.period = check_period;
@@ -221,9 +234,9 @@ int run_generic(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const doub
 }
 
 // The launch parameters run_grid and run_wide share: the whole call on the plan's buffers, in the longest-first order, drawn from
-// the fast launch's queue head.  Pairs that end in NaN ("Numerical errors" in POT) are collected and re-solved by the POT-literal
+// the fast launch's queue head, with the control block `ctrl`.  Pairs that end in NaN ("Numerical errors" in POT) are collected and re-solved by the POT-literal
 // kernel, which returns the last good iterate like POT does.
-pilot::GridParams call_params(const pilot_ot_plan *pl, int n_pairs, int row_begin, int row_step, int num_iter_max, int check_period,
+pilot::GridParams call_params(const pilot_ot_plan *pl, int *ctrl, int n_pairs, int row_begin, int row_step, int num_iter_max, int check_period,
                               double stop_thr, double tau, double floor_ulps, double *d_emd, int *d_iters, double *d_err, int *d_flags) {
     pilot::GridParams p;
     p.P = pl->p_slot; p.img = pl->img; p.N = pl->N; p.K = pl->K;
@@ -234,31 +247,35 @@ pilot::GridParams call_params(const pilot_ot_plan *pl, int n_pairs, int row_begi
     p.max_iter = num_iter_max; p.period = check_period;
     p.stop_thr = stop_thr; p.tau = tau; p.floor_ulps = floor_ulps;
     p.emd = d_emd; p.iters = d_iters; p.err = d_err; p.flags = d_flags;
-    p.track_list = pl->track_list; p.track_count = pl->ctrl + pilot::CTRL_TRACK_LEN;
-    p.queue_head = pl->ctrl + pilot::CTRL_HEAD_FAST; p.queue_shards = nullptr;
+    p.track_list = pl->track_list; p.track_count = ctrl + pilot::CTRL_TRACK_LEN;
+    p.queue_head = ctrl + pilot::CTRL_HEAD_FAST; p.queue_shards = nullptr;
     p.ring = 0; p.bands = 1;
     p.fb_list = nullptr; p.fb_count = nullptr;
-    p.nan_list = pl->nan_list; p.nan_count = pl->ctrl + pilot::CTRL_NAN_LEN;
-    p.unequal = pl->ctrl + pilot::CTRL_UNEQUAL;
+    p.nan_list = pl->nan_list; p.nan_count = ctrl + pilot::CTRL_NAN_LEN;
+    p.unequal = ctrl + pilot::CTRL_UNEQUAL;
     p.debug = 0;
     return p;
 }
 
 // The passes that plan_grid (sinkhorn_layout.hpp) lays out for this call, launched in order: every decision is taken there, the
 // pointers are bound here.
+// captured: the call is being recorded into a graph, whose replays have their pointers baked in: it works on block 0 behind its
+// caller's memset node over BOTH control blocks, zeroes nothing in its prep kernel, and leaves the parity to its caller, which
+// sets it to 1 after every such call and replay -- block 1 is then the zero one, and the next ordinary call zeroes block 0.
 int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double *d_P, const double *d_M, double reg, int num_iter_max,
              double stop_thr, double tau, int check_period, double floor_ulps, bool sym, int row_begin, int n_rows, int row_step,
-             double *d_emd, int *d_iters, double *d_err, int *d_flags, hipStream_t s, bool mixed = false) {
+             double *d_emd, int *d_iters, double *d_err, int *d_flags, hipStream_t s, bool mixed, bool captured) {
     const int N = pl->N, K = pl->K, RT = (K + 15) / 16;
     const pilot::GridPasses g = pilot::plan_grid(cfg, N, K, n_rows, sym, mixed, pl->max_cost / reg, pl->n_cu, sw);
     if (g.rc != PILOT_OT_OK) return fail(g.rc, "%s", g.msg);
-    HIP_TRY(hipMemsetAsync(pl->ctrl, 0, pilot::CTRL_BLOCK_INTS * sizeof(int), s));     // one control block, one memset per call
     if (n_rows == 0) return PILOT_OT_OK;
-    pilot::GridParams p = call_params(pl, n_rows * N, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd, d_iters,
+    int *const ctrl = captured ? pl->ctrl : ctrl_block(pl, pl->ctrl_par);
+    int *const zero_ctrl = captured ? nullptr : ctrl_spare(pl);
+    pilot::GridParams p = call_params(pl, ctrl, n_rows * N, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd, d_iters,
                                       d_err, d_flags);
     p.debug = sw.debug;
     int *const lists[] = {pl->order_list, pl->track_list, pl->nan_list + (size_t)N * N};       // (PairList)
-    auto slot = [&](int at) { return at == pilot::CTRL_NONE ? nullptr : pl->ctrl + at; };
+    auto slot = [&](int at) { return at == pilot::CTRL_NONE ? nullptr : ctrl + at; };
     if (g.f64.run) { p.fb_list = lists[g.f64.list]; p.fb_count = slot(pilot::CTRL_FB_LEN); }
     if (g.fast.solo_blocks) { p.solo_len = slot(pilot::CTRL_SOLO_LEN); p.solo_head = slot(pilot::CTRL_HEAD_SOLO); }
     auto launch = [&](const pilot::PassPlan &v) -> hipError_t {
@@ -274,7 +291,9 @@ int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, cons
                                        : pilot::launch_stream_f32(RT, sym, v.track, wgs, v.lds.bytes, s, p);
     };
     HIP_TRY(pilot::launch_prep(cfg, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, g.write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step,
-                               pl->order_bucket, pl->order_hist, pl->order_list, slot(pilot::CTRL_SPLIT), slot(pilot::CTRL_HEAD_FAST), g.mode, g.ob, s));
+                               pl->order_bucket, slot(pilot::CTRL_ORDER_HIST), pl->order_tiles, pl->order_list, slot(pilot::CTRL_SPLIT),
+                               slot(pilot::CTRL_HEAD_FAST), g.mode, g.ob, zero_ctrl, s));
+    if (!captured) pl->ctrl_par ^= 1;       // (the prep launch is issued: the other block is zero when the next call starts)
     hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     if (g.fast.run) HIP_TRY(launch(g.fast));
@@ -284,14 +303,15 @@ int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, cons
     HIP_TRY(launch(g.track));
     if (g.f64.run) {
         HIP_TRY(pilot::launch_prep(pilot::CFG_F64, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, 2, stop_thr, floor_ulps, 0, row_begin, row_step,
-                                   pl->order_bucket, pl->order_hist, pl->order_list, slot(pilot::CTRL_SPLIT), slot(pilot::CTRL_HEAD_FAST), 0, 1, s));
+                                   pl->order_bucket, slot(pilot::CTRL_ORDER_HIST), pl->order_tiles, pl->order_list, slot(pilot::CTRL_SPLIT),
+                                   slot(pilot::CTRL_HEAD_FAST), 0, 1, nullptr, s));
         p.img = pl->img; p.fb_list = nullptr; p.fb_count = nullptr;
         HIP_TRY(launch(g.f64));
     }
     if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
     if (sw.debug & pilot::DBG_NO_NAN_PASS) return PILOT_OT_OK;
     return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags,
-                       s, pl->nan_list, slot(pilot::CTRL_NAN_LEN), slot(pilot::CTRL_NAN_HEAD));
+                       s, ctrl, pl->nan_list, slot(pilot::CTRL_NAN_LEN), slot(pilot::CTRL_NAN_HEAD));
 }
 
 // 128 < K <= 256 with a symmetric cost inside the fp16-split range: sinkhorn_wide_kernel (wide_kernels.hpp) on the operand
@@ -316,6 +336,7 @@ int run_wide(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double 
         }
         return PILOT_OT_OK;
     }
+    // (this path keeps its memset and block 0: no plan runs both it and run_grid, which is for K <= 128)
     HIP_TRY(hipMemsetAsync(pl->ctrl, 0, (pilot::CTRL_ORDER_HIST + 2 * pilot::ORDER_NB) * sizeof(int), s));
     if (n_rows == 0) return PILOT_OT_OK;
     const int n_pairs = n_rows * N;
@@ -328,8 +349,9 @@ int run_wide(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double 
     int ob = (n_pairs + 1023) / 1024;
     if (ob > pl->n_cu) ob = pl->n_cu;
     HIP_TRY(pilot::launch_prep(pilot::CFG_H32, d_M, K, RT, reg, pl->img, d_P, pl->p_slot, N, 0, stop_thr, floor_ulps, n_rows, row_begin, row_step,
-                               pl->order_bucket, pl->order_hist, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT, pl->ctrl + pilot::CTRL_HEAD_FAST, 0, ob, s));
-    const pilot::GridParams p = call_params(pl, n_pairs, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd,
+                               pl->order_bucket, pl->ctrl + pilot::CTRL_ORDER_HIST, pl->order_tiles, pl->order_list, pl->ctrl + pilot::CTRL_SPLIT,
+                               pl->ctrl + pilot::CTRL_HEAD_FAST, 0, ob, nullptr, s));
+    const pilot::GridParams p = call_params(pl, pl->ctrl, n_pairs, row_begin, row_step, num_iter_max, check_period, stop_thr, tau, floor_ulps, d_emd,
                                             d_iters, d_err, d_flags);
     hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
@@ -340,7 +362,7 @@ int run_wide(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double 
     HIP_TRY(pilot::launch_wide_value(dim3(pilot::clamp_wgs(pl->n_cu, 2, tiles)), s, p, pl->wide_rec));
     if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
     return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
-                       d_flags, s, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);
+                       d_flags, s, pl->ctrl, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);
 }
 
 pilot::SinkhornSwitches read_switches() {
@@ -379,7 +401,7 @@ PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, c
         }
         if (precision == PILOT_OT_PREC_GENERIC || pl->K > MAX_K || pl->max_cost / reg > MAX_COST_OVER_REG)
             return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows_g, row_step, d_emd,
-                               d_iters, d_err, d_flags, static_cast<hipStream_t>(stream));
+                               d_iters, d_err, d_flags, static_cast<hipStream_t>(stream), ctrl_spare(pl));
     }
     // (the range is judged by the plan's max_cost / reg: 1 / reg for Trajectory.py:101's normalised cost unless the caller said
     // otherwise with pilot_ot_plan_set_max_cost; the host and multi-device entry points set it from the M they copy in)
@@ -397,33 +419,35 @@ PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, c
     const int cfg = mixed ? pilot::CFG_S32
                           : (precision == PILOT_OT_PREC_F32 ? pilot::CFG_F32
                              : (precision == PILOT_OT_PREC_BF16X3 ? pilot::CFG_S32 : (precision == PILOT_OT_PREC_F16X2 ? pilot::CFG_H32 : pilot::CFG_F64)));
-    auto run = [&](hipStream_t on) {
+    auto run = [&](hipStream_t on, bool captured) -> int {
+        if (captured) HIP_TRY(hipMemsetAsync(pl->ctrl, 0, 2 * pilot::CTRL_BLOCK_INTS * sizeof(int), on));      // (the graph's memset node)
         int r = run_grid(cfg, pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, f32_floor_ulps, cost_is_symmetric != 0,
-                         row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags, on, mixed);
+                         row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags, on, mixed, captured);
         // a shape whose operand images do not fit LDS in this precision (non-symmetric cost at large K): the POT-literal
         // kernel takes the whole grid -- the reference has no such limit
         if (r == PILOT_OT_ENOTSUP)
             r = run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters,
-                            d_err, d_flags, on);
+                            d_err, d_flags, on, captured ? pl->ctrl : ctrl_spare(pl));
         return r;
     };
-    if (!pl->graph_mode || pl->timing || n_rows == 0) return run(s);
+    if (!pl->graph_mode || pl->timing || n_rows == 0) return run(s, false);
     // graph replay: the first call with a new argument set runs as usual (and grows the work buffers), the second one is
     // captured, later ones replay the instantiated graph
     const pilot_ot_plan::GraphKey key = {d_P, d_M, d_emd, d_iters, d_err, d_flags, reg, stop_thr, tau, f32_floor_ulps, pl->max_cost, num_iter_max,
                                          check_period, cfg, mixed ? 1 : 0, cost_is_symmetric != 0 ? 1 : 0, row_begin, n_rows, row_step, sw};
     if (pl->gexec && key == pl->gkey) {
         HIP_TRY(hipGraphLaunch(pl->gexec, s));
+        pl->ctrl_par = 1;
         return PILOT_OT_OK;
     }
     if (pl->gexec) { (void)hipGraphExecDestroy(pl->gexec); pl->gexec = nullptr; }
     if (!(pl->gkey_seen && key == pl->gkey)) {
         pl->gkey = key; pl->gkey_seen = 1;
-        return run(s);
+        return run(s, false);
     }
     if (!pl->gstream) HIP_TRY(hipStreamCreateWithFlags(&pl->gstream, hipStreamNonBlocking));
     HIP_TRY(hipStreamBeginCapture(pl->gstream, hipStreamCaptureModeThreadLocal));
-    rc = run(pl->gstream);
+    rc = run(pl->gstream, true);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(pl->gstream, &graph);
     if (rc != PILOT_OT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -432,6 +456,7 @@ PILOT_API int pilot_ot_sinkhorn_grid_dev(pilot_ot_plan *pl, const double *d_P, c
     (void)hipGraphDestroy(graph);
     if (ie != hipSuccess) { (void)hipGetLastError(); pl->gexec = nullptr; return fail(PILOT_OT_EHIP, "graph instantiation failed: %s", hipGetErrorString(ie)); }
     HIP_TRY(hipGraphLaunch(pl->gexec, s));
+    pl->ctrl_par = 1;       // (a graph works on block 0 behind a memset of both: see run_grid)
     return PILOT_OT_OK;
 }
 

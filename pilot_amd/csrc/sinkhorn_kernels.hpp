@@ -1849,46 +1849,78 @@ __device__ inline void write_split_forms(const double *__restrict__ Msrc, int K,
     }
 }
 // first product of every pair: (G^T u0)[j] = (1/K) * sum_k G[k][j] (times `scale`), in accumulator-slot order
-// (four adjacent lanes share a slot, each sums every fourth k: the K serial fp64 exponentials of a slot were the longest
-// chain of the whole preparation)
+// Workgroup `rank` of the `nwg` that share the table takes a contiguous run of slots.  The K fp64 exponentials of a slot -- a
+// load and an exp each, in series the longest chain of the whole preparation -- are evaluated one per thread into `e` (LDS,
+// slots x K doubles); four adjacent lanes then share a slot, each adds every fourth k in increasing k, and two shuffles add
+// the four partial sums: the order of the additions is fixed, so the table does not depend on nwg.
+// Every thread of the workgroup calls this (one barrier inside).
 template <class C>
 __device__ inline void write_first_product(const double *__restrict__ Msrc, int K, int RT, double reg, typename C::T *__restrict__ tab,
-                                           double scale, int tid, int nthr) {
+                                           double scale, int rank, int nwg, double *__restrict__ e) {
     using M = C;
     using T = typename C::T;
     const int KP = RT * M::TILE;
-    for (int idx = tid; idx < 4 * KP; idx += nthr) {              // (4 KP and nthr are multiples of the wave size)
-        const int part = idx & 3, slot = idx >> 2;
-        const int r = slot % M::NREG;                             // slot order [tile][group][reg]
-        const int g = (slot / M::NREG) % M::NGRP;
-        const int t = slot / (M::NGRP * M::NREG);
-        const int j = M::lidx(t, r, g);
+    const int per = (KP + nwg - 1) / nwg, s0 = rank * per;
+    const int ns = KP - s0 < per ? KP - s0 : per;                 // slots of this workgroup (<= 0: none)
+    auto type_of = [](int slot) {                                 // slot order [tile][group][reg]
+        return M::lidx(slot / (M::NGRP * M::NREG), slot % M::NREG, (slot / M::NREG) % M::NGRP);
+    };
+    for (int i = threadIdx.x; i < ns * K; i += blockDim.x) {
+        const int j = type_of(s0 + i / K), k = i % K;
+        e[i] = j < K ? exp(-Msrc[(size_t)k * K + j] / reg) : 0.0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * ns; i += blockDim.x) {      // (the four lanes of a slot are active together)
+        const int part = i & 3, sl = i >> 2;
+        const int j = type_of(s0 + sl);
         double s = 0.0;
         if (j < K)
-            for (int k = part; k < K; k += 4) s += exp(-Msrc[(size_t)k * K + j] / reg);
+            for (int k = part; k < K; k += 4) s += e[sl * K + k];
         s += __shfl_xor(s, 1);
         s += __shfl_xor(s, 2);
-        if (part == 0) tab[slot] = T(j < K ? s / K * scale : 1.0);   // padded slots: 1 keeps b/acc = 0/1 finite
+        if (part == 0) tab[s0 + sl] = T(j < K ? s / K * scale : 1.0);   // padded slots: 1 keeps b/acc = 0/1 finite
     }
 }
 
+// The setup workgroups of the prep kernel (PREP_SETUP_BLOCKS of 256 threads; `wg` of them is this one).  The pieces that hang on
+// exp(-M/reg) -- operand forms, first-product tables, plain tables, tail weights -- are ROLES: the workgroups are dealt round over
+// the roles the call has, so the pieces run side by side and a thread evaluates a few exponentials, not every piece's share in
+// turn.  The proportions, the thresholds and the zeroing of the next call's control block are spread over all of them.  Which
+// thread writes a value never enters the value.  `lds`: the launch's dynamic LDS (the order tiles' size: >= 548 B per cell type).
+constexpr int PREP_SETUP_BLOCKS = 64, PREP_MAX_ROLES = 6;
+static_assert(PREP_SETUP_BLOCKS / PREP_MAX_ROLES >= 4, "a first-product role needs four workgroups: <= 64 of 256 slots x K doubles each in LDS");
 template <class C>
 __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT, double reg,
                                   typename C::T *__restrict__ img, const double *__restrict__ Psrc,
                                   typename C::T *__restrict__ Pdst, long n_p, int write_tail, double stop_thr,
-                                  double floor_ulps, int tid, int nthr, int *unequal = nullptr) {
+                                  double floor_ulps, int wg, int *unequal, int *__restrict__ zero_ctrl, double *lds) {
     using M = C;
     using T = typename C::T;
     const int KP = RT * M::TILE;
     const int nimg = form_elems<C>(RT);
+    const int tid = wg * (int)blockDim.x + (int)threadIdx.x, nthr = PREP_SETUP_BLOCKS * (int)blockDim.x;
+    if (zero_ctrl)
+        for (int i = tid; i < CTRL_BLOCK_INTS; i += nthr) zero_ctrl[i] = 0;
+    // the mass of the first histogram, which the thresholds below compare every row's with: once per workgroup that has rows
+    // (lds[0]; the barrier before the thresholds publishes it)
+    const bool has_rows = (long)wg * blockDim.x < n_p / KP;
+    if (has_rows && threadIdx.x == 0) {
+        double mass0 = 0.0;
+        for (int k = 0; k < K; ++k) mass0 += Psrc[k];
+        lds[0] = mass0;
+    }
+    // roles, in this order: [first product][forms or plain image][HALF: tracking forms][HALF: tracking first product][plain tables][tail weights]
+    const int n_roles = (C::HALF ? 4 : 2) + ((write_tail & 2) ? 1 : 0) + ((write_tail & 1) ? 1 : 0);
+    const int role = wg % n_roles, rank = wg / n_roles, nwg = (PREP_SETUP_BLOCKS - role + n_roles - 1) / n_roles;
+    const int rtid = rank * (int)blockDim.x + (int)threadIdx.x, rnthr = nwg * (int)blockDim.x;
+    const int r_plain = C::HALF ? 4 : 2, r_tail = r_plain + ((write_tail & 2) ? 1 : 0);
+    if (role == 0) {
+        write_first_product<C>(Msrc, K, RT, reg, img + acc0_offset<C>(RT), C::HALF ? double(H_GIBBS_SCALE) * double(H_PANEL_SCALE) : 1.0, rank, nwg, lds + 1);
+    } else if (role == 1) {
     if constexpr (C::SPLIT) {
-        write_split_forms<C>(Msrc, K, RT, reg, img, (write_tail & 4) != 0, tid, nthr);
-        if constexpr (C::HALF) {     // the bf16-split block of the tracking kernel
-            write_split_forms<CfgS32x16>(Msrc, K, RT, reg, img + track_img_offset<C>(RT), false, tid, nthr);
-            write_first_product<CfgS32x16>(Msrc, K, RT, reg, img + track_img_offset<C>(RT) + acc0_offset<CfgS32x16>(RT), 1.0, tid, nthr);
-        }
+        write_split_forms<C>(Msrc, K, RT, reg, img, (write_tail & 4) != 0, rtid, rnthr);
     } else {
-    for (int idx = tid; idx < nimg; idx += nthr) {
+    for (int idx = rtid; idx < nimg; idx += rnthr) {
         const int lane = idx % WAVE;
         int rest = idx / WAVE;
         const int t = rest % RT; rest /= RT;
@@ -1908,11 +1940,14 @@ __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT
         img[2 * nimg + idx] = T(gm);
     }
     }
-    write_first_product<C>(Msrc, K, RT, reg, img + acc0_offset<C>(RT), C::HALF ? double(H_GIBBS_SCALE) * double(H_PANEL_SCALE) : 1.0, tid, nthr);
-    // tail-row weights for the VALU variant (see tail_rows): [form][chain][k-step][lane] pairs behind the table
-    if (write_tail & 2) {     // plain tables of solo_pairs: G[lane][k], G[k][lane], (G o M)[lane][k]
+    } else if (C::HALF && role == 2) {     // the bf16-split block of the tracking kernel
+        if constexpr (C::HALF) write_split_forms<CfgS32x16>(Msrc, K, RT, reg, img + track_img_offset<C>(RT), false, rtid, rnthr);
+    } else if (C::HALF && role == 3) {
+        if constexpr (C::HALF)
+            write_first_product<CfgS32x16>(Msrc, K, RT, reg, img + track_img_offset<C>(RT) + acc0_offset<CfgS32x16>(RT), 1.0, rank, nwg, lds + 1);
+    } else if ((write_tail & 2) && role == r_plain) {     // plain tables of solo_pairs: G[lane][k], G[k][lane], (G o M)[lane][k]
         T *plain = img + plain_offset<C>(RT);
-        for (int idx = tid; idx < 3 * 64 * WAVE; idx += nthr) {
+        for (int idx = rtid; idx < 3 * 64 * WAVE; idx += rnthr) {
             const int lane = idx % WAVE, k = (idx / WAVE) % 64, tbl = idx / (64 * WAVE);
             double v = 0.0;
             if (k < K && lane < K) {
@@ -1922,11 +1957,11 @@ __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT
             }
             plain[idx] = T(v);
         }
-    }
-    if (write_tail & 1) {
+    } else if ((write_tail & 1) && role == r_tail) {
+        // tail-row weights for the VALU variant (see tail_rows): [form][chain][k-step][lane] pairs behind the table
         const int nst = (RT - 1) * 4 + 1;
         T *tail = img + tail_offset<C>(RT);
-        for (int idx = tid; idx < 2 * 2 * nst * WAVE * 2; idx += nthr) {
+        for (int idx = rtid; idx < 2 * 2 * nst * WAVE * 2; idx += rnthr) {
             const int h = idx & 1;
             int rest = idx >> 1;
             const int lane = rest % WAVE; rest /= WAVE;
@@ -1941,8 +1976,8 @@ __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT
     }
     // stop threshold per (column) patient behind the proportions: POT's stopThr, floored in f32 at floor_ulps * eps * ||b||_2
     // (the marginal error cannot get below the rounding of b itself)
-    double mass0 = 0.0;
-    for (int k = 0; k < K; ++k) mass0 += Psrc[k];
+    __syncthreads();
+    const double mass0 = has_rows ? lds[0] : 0.0;
     for (long row = tid; row < n_p / KP; row += nthr) {
         double n2 = 0.0, mass = 0.0;
         for (int k = 0; k < K; ++k) { n2 += Psrc[row * K + k] * Psrc[row * K + k]; mass += Psrc[row * K + k]; }
@@ -1972,34 +2007,15 @@ __device__ inline void setup_body(const double *__restrict__ Msrc, int K, int RT
 // Sinkhorn needs more updates the closer the two histograms are (the diagonal pairs a == b are the slowest
 // by far), and a pair's updates are a serial chain, so the long pairs must START first or they become the
 // tail of the launch.  Pairs are bucketed by -log2 of their L1 distance (NB buckets, 4 per octave, exact
-// duplicates in the last one) and the work list is emitted from the highest bucket down.  Three tiny
-// launches: bucket ids + histogram, (prefix is folded into) scatter.
-
-// wave-aggregated LDS counter: lanes with equal `b` share one atomic; returns the lane's slot (base + rank among equals)
-__device__ inline int lds_count_aggregated(int *counters, int b, bool valid) {
-    int slot = 0;
-    unsigned long long todo = ballot_b(valid);
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const int b0 = __builtin_amdgcn_readlane(b, leader);
-        const unsigned long long same = ballot_b(valid && b == b0);
-        const int lane = threadIdx.x % WAVE;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&counters[b0], (int)__popcll(same));
-        base = __builtin_amdgcn_readlane(base, leader);
-        if (valid && b == b0) slot = base + (int)__popcll(same & ((1ull << lane) - 1ull));
-        todo &= ~same;
-    }
-    return slot;
-}
+// duplicates in the last one) and the work list is emitted from the highest bucket down.  Two
+// launches: bucket ids + histograms (of the grid and of every tile; in the prep kernel), then the scatter, which folds the prefix in.
 
 // Tile of ORDER_RI selected rows x ORDER_JW columns per workgroup: the column histograms are staged transposed in LDS
 // (coalesced global reads, conflict-free LDS reads), the row histograms are LDS broadcasts; 2 VALU per |a_k - b_k|.
-constexpr int ORDER_JW = 128, ORDER_RI = 8;
-
+// (ORDER_JW, ORDER_RI: sinkhorn_layout.hpp.)  A thread's items: column jl, the R rows of its half of the tile.
 __device__ inline void bucket_body(int tile, const double *__restrict__ Psrc, int N, int K, int n_rows, int row_begin,
-                                   int row_step, unsigned char *__restrict__ bucket, int *__restrict__ hist, int collapse,
-                                   unsigned char *order_smem) {
+                                   int row_step, unsigned char *__restrict__ bucket, int *__restrict__ hist,
+                                   int *__restrict__ tile_counts, int collapse, unsigned char *order_smem) {
     // rows of the caller's N x K proportions (float is plenty for a sort key; L1 does not care about slot order)
     const int K4 = (K + 3) & ~3;
     float *Bt = reinterpret_cast<float *>(order_smem);           // [K4][ORDER_JW + 1]
@@ -2010,9 +2026,21 @@ __device__ inline void bucket_body(int tile, const double *__restrict__ Psrc, in
     const int nj = N - jb < ORDER_JW ? N - jb : ORDER_JW;
     const int nr = n_rows - rb < ORDER_RI ? n_rows - rb : ORDER_RI;
     for (int e = threadIdx.x; e < ORDER_NB; e += blockDim.x) lh[e] = 0;
-    for (int e = threadIdx.x; e < nj * K; e += blockDim.x) {
-        const int row = e / K, k = e % K;
-        Bt[k * (ORDER_JW + 1) + row] = float(Psrc[(size_t)jb * K + e]);
+    // (a thread stages nj K / 256 values, 25 at c3's shape: ORDER_STAGE loads are in flight at a time, not one after the other --
+    // unconditional loads of a clamped index, since a guarded load is waited for inside its branch)
+    constexpr int ORDER_STAGE = 8;
+    for (int e0 = threadIdx.x; e0 < nj * K; e0 += ORDER_STAGE * blockDim.x) {
+        double v[ORDER_STAGE];
+#pragma unroll
+        for (int u = 0; u < ORDER_STAGE; ++u) {
+            const int e = e0 + u * (int)blockDim.x;
+            v[u] = Psrc[(size_t)jb * K + (e < nj * K ? e : nj * K - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < ORDER_STAGE; ++u) {
+            const int e = e0 + u * (int)blockDim.x;
+            if (e < nj * K) Bt[(e % K) * (ORDER_JW + 1) + e / K] = float(v[u]);
+        }
     }
     for (int e = threadIdx.x; e < (K4 - K) * ORDER_JW; e += blockDim.x) Bt[(K + e / ORDER_JW) * (ORDER_JW + 1) + e % ORDER_JW] = 0.f;
     for (int e = threadIdx.x; e < ORDER_RI * K4; e += blockDim.x) {
@@ -2055,50 +2083,71 @@ __device__ inline void bucket_body(int tile, const double *__restrict__ Psrc, in
             // full grid still send the same pair down the same path.
             b = ORDER_NB - 2;
         }
-        if (valid) bucket[(size_t)rr * N + jb + jl] = (unsigned char)b;
-        (void)lds_count_aggregated(lh, b, valid);
+        if (valid) { bucket[(size_t)rr * N + jb + jl] = (unsigned char)b; atomicAdd(&lh[b], 1); }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < ORDER_NB; i += blockDim.x) if (lh[i]) atomicAdd(&hist[i], lh[i]);
+    // the tile's own counts stay: the scatter reserves its list ranges from them and needs no counting pass of its own
+    for (int i = threadIdx.x; i < ORDER_NB; i += blockDim.x) {
+        tile_counts[(size_t)tile * ORDER_NB + i] = lh[i];
+        if (lh[i]) atomicAdd(&hist[i], lh[i]);
+    }
 }
 
 // One launch prepares a call: workgroups [0, n_tiles) compute the order keys (bucket_body), the rest build the operand
 // images, tables and the slot-ordered proportions (setup_body).  The two halves are independent.
-constexpr int PREP_SETUP_BLOCKS = 64;
+// zero_ctrl (nullable): the control block of the NEXT call, which nothing reads during this one; the setup workgroups zero it.
 template <class C>
 __global__ void __launch_bounds__(256) sinkhorn_prep_kernel(const double *__restrict__ Msrc, int K, int RT, double reg,
                                                             typename C::T *__restrict__ img, const double *__restrict__ Psrc,
                                                             typename C::T *__restrict__ Pdst, int N, int write_tail, double stop_thr,
                                                             double floor_ulps, int n_tiles,
                                                             int n_rows, int row_begin, int row_step,
-                                                            unsigned char *__restrict__ bucket, int *__restrict__ hist, int collapse) {
+                                                            unsigned char *__restrict__ bucket, int *__restrict__ hist,
+                                                            int *__restrict__ tile_counts, int collapse, int *__restrict__ zero_ctrl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char order_smem[];
     if ((int)blockIdx.x < n_tiles) {
-        bucket_body(blockIdx.x, Psrc, N, K, n_rows, row_begin, row_step, bucket, hist, collapse, order_smem);
+        bucket_body(blockIdx.x, Psrc, N, K, n_rows, row_begin, row_step, bucket, hist, tile_counts, collapse, order_smem);
     } else {
         setup_body<C>(Msrc, K, RT, reg, img, Psrc, Pdst, (long)N * RT * C::TILE, write_tail, stop_thr, floor_ulps,
-                      ((int)blockIdx.x - n_tiles) * (int)blockDim.x + (int)threadIdx.x, PREP_SETUP_BLOCKS * (int)blockDim.x,
-                      hist - (CTRL_ORDER_HIST - CTRL_UNEQUAL));
+                      (int)blockIdx.x - n_tiles, hist - (CTRL_ORDER_HIST - CTRL_UNEQUAL), zero_ctrl, reinterpret_cast<double *>(order_smem));
     }
 }
 
 // list position of bucket b = (number of items in higher buckets) + a range reserved per workgroup.
-// Every workgroup owns a contiguous chunk of items: LDS histogram of the chunk, ONE global atomic per
-// (workgroup, bucket) to reserve the range, then LDS cursors -- a handful of hot global addresses would
-// otherwise serialise all N^2 atomics.
+// Every workgroup owns a contiguous run of the prep kernel's order tiles and knows their bucket counts (tile_counts): ONE
+// global atomic per (workgroup, bucket) reserves the range, then LDS cursors place the items in one pass over their keys -- a
+// handful of hot global addresses would otherwise serialise all N^2 atomics.  (Which range a workgroup gets, and the order
+// inside a bucket, vary from run to run; the list holds every item once, bucket-major from the highest bucket down.)
 // `split` (control slots CTRL_SPLIT.., written by workgroup 0): n_dup, the number of leading list items that the solo waves take
 // (the exact duplicates a == b: top bucket, first in the list); the tile queue (`main_queue_head`) starts behind them.
 // solo_mode bit 1: the launch carries solo waves.
-static __global__ void order_scatter_kernel(const unsigned char *__restrict__ bucket, int n_items, const int *__restrict__ hist,
+static __global__ void __launch_bounds__(2 * ORDER_JW) order_scatter_kernel(const unsigned char *__restrict__ bucket, int N, int n_rows, int n_tiles,
+                                     const int *__restrict__ tile_counts, const int *__restrict__ hist,
                                      int *__restrict__ cursor, int *__restrict__ list, int *__restrict__ split,
                                      int *__restrict__ main_queue_head, int solo_mode) {
-    __shared__ int offs[ORDER_NB], lh[ORDER_NB], lbase[ORDER_NB], gh[ORDER_NB];
+    __shared__ int lh[ORDER_NB], lbase[ORDER_NB], gh[ORDER_NB];
+    const int chunk = (n_tiles + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int t0 = (int)blockIdx.x * chunk, t1 = t0 + chunk < n_tiles ? t0 + chunk : n_tiles;
+    constexpr int R = ORDER_RI / 2;        // a thread's items in a tile, as in bucket_body: pair index (-1: none) and key
+    const int n_jb = (N + ORDER_JW - 1) / ORDER_JW;
+    const int jl = threadIdx.x % ORDER_JW, half = threadIdx.x / ORDER_JW;
+    int q[R], b[R];
+    auto load_keys = [&](int t) {
+        const int j = (t % n_jb) * ORDER_JW + jl, rr0 = (t / n_jb) * ORDER_RI + half * R;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            q[r] = (t < t1 && j < N && rr0 + r < n_rows) ? (rr0 + r) * N + j : -1;
+            b[r] = q[r] >= 0 ? bucket[q[r]] : 0;
+        }
+    };
+    load_keys(t0);                         // (in flight while the ranges are reserved)
     if (threadIdx.x < ORDER_NB) { lh[threadIdx.x] = 0; gh[threadIdx.x] = hist[threadIdx.x]; }
     __syncthreads();
-    if (threadIdx.x < ORDER_NB) {          // items in higher buckets come first
-        int run = 0;
-        for (int b = ORDER_NB - 1; b > (int)threadIdx.x; --b) run += gh[b];
-        offs[threadIdx.x] = run;
+    if (threadIdx.x < ORDER_NB) {
+        int run = 0, c = 0;
+        for (int b = ORDER_NB - 1; b > (int)threadIdx.x; --b) run += gh[b];       // items in higher buckets come first
+        for (int t = t0; t < t1; ++t) c += tile_counts[(size_t)t * ORDER_NB + threadIdx.x];
+        lbase[threadIdx.x] = run + (c ? atomicAdd(&cursor[threadIdx.x], c) : 0);
     }
     if (blockIdx.x == 0 && threadIdx.x == 64) {
         const int n_dup = (solo_mode & 2) ? gh[ORDER_NB - 1] : 0;
@@ -2106,27 +2155,11 @@ static __global__ void order_scatter_kernel(const unsigned char *__restrict__ bu
         *main_queue_head = n_dup;          // the tile queue starts behind the duplicates
     }
     __syncthreads();
-    const int chunk = (n_items + gridDim.x - 1) / gridDim.x;
-    const int q0 = blockIdx.x * chunk, q1 = (q0 + chunk < n_items) ? q0 + chunk : n_items;
-    const int n_it = (q1 - q0 + (int)blockDim.x - 1) / (int)blockDim.x;      // whole waves stay in the loop: ballots inside
-    for (int it = 0; it < n_it; ++it) {
-        const int q = q0 + it * blockDim.x + threadIdx.x;
-        const bool valid = q < q1;
-        (void)lds_count_aggregated(lh, valid ? bucket[q] : 0, valid);
-    }
-    __syncthreads();
-    if (threadIdx.x < ORDER_NB) {
-        const int c = lh[threadIdx.x];
-        lbase[threadIdx.x] = offs[threadIdx.x] + (c ? atomicAdd(&cursor[threadIdx.x], c) : 0);
-        lh[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    for (int it = 0; it < n_it; ++it) {
-        const int q = q0 + it * blockDim.x + threadIdx.x;
-        const bool valid = q < q1;
-        const int b = valid ? bucket[q] : 0;
-        const int slot = lds_count_aggregated(lh, b, valid);
-        if (valid) list[lbase[b] + slot] = q;
+    for (int t = t0; t < t1; ++t) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (q[r] >= 0) list[lbase[b[r]] + atomicAdd(&lh[b[r]], 1)] = q[r];
+        load_keys(t + 1);
     }
 }
 

@@ -29,10 +29,12 @@ hipError_t launch_stream_h32(int RT, bool sym, int live1, dim3 grid, size_t lds,
 // variants with the last row-tile on the VALU (tv = 1: <= 2 live rows, 2: <= 4; see tail_rows); RT >= 2
 hipError_t launch_stream_tv(int cfg, int tv, int RT, bool sym, bool track, dim3 grid, size_t lds, hipStream_t s, const GridParams &p);
 // one call's preparation: operand images + tables + slot-ordered proportions and the longest-first order keys in one
-// launch (sinkhorn_prep_kernel), then the scatter.  mode: bit 1 solo duplicates, bit 2 natural order.
+// launch (sinkhorn_prep_kernel), then the scatter.  mode: bit 1 solo duplicates, bit 2 natural order.  hist: ORDER_HIST slot of
+// the call's control block; tile_counts: the plan's order_tiles; zero_ctrl (nullable): the control block the kernel zeroes for
+// the next call.
 hipError_t launch_prep(int cfg, const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                       double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                       int *main_queue_head, int mode, int n_blocks, hipStream_t s);
+                       double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                       int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s);
 // 128 < K <= 256, symmetric cost, fp16-split range (wide_kernels.hpp): the pair-grid kernel (8 waves per 16-pair tile; one
 // record of wide_rec_elems() 4-byte words per pair in `rec`) and the kernel that turns the records into costs
 hipError_t launch_wide(dim3 grid, hipStream_t s, const GridParams &p, float *rec);

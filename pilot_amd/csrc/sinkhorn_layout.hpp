@@ -119,10 +119,15 @@ constexpr StreamLds stream_lds(CfgShape c, int RT, bool sym, bool track, int tv,
         if (ring >= min_ring || want == 1) return {fixed + slots * (size_t)(ring < 1 ? 1 : ring), ring, want};
     }
 }
-// ---- control block of a call (pilot_ot_plan::ctrl; ints, zeroed per call by the host): CTRL_INTS counters and queue heads, then the
+// ---- control block of a call (ints, all zero when the call starts): CTRL_INTS counters and queue heads, then the
 // order histograms and, from a 128-byte boundary, the ticket counters of the two sharded work queues (see QUEUE_SHARD_MAX_RT and
-// order_bucket_kernel in sinkhorn_kernels.hpp)
+// order_bucket_kernel in sinkhorn_kernels.hpp).  A plan holds two (pilot_ot_plan::ctrl): an ordinary grid call works on one
+// while the setup workgroups of its prep kernel zero the other for the call after it, so no call waits for a memset; the wide
+// kernel's call and a call captured into a graph keep a memset and block 0 (see run_grid in pilot_ot_sinkhorn.hip).
 constexpr int ORDER_NB = 48;
+// the prep kernel computes the order keys in tiles of ORDER_RI selected rows x ORDER_JW columns, one workgroup each
+constexpr int ORDER_JW = 128, ORDER_RI = 8;
+constexpr long order_tile_count(int N, int n_rows) { return n_rows > 0 ? (long)((N + ORDER_JW - 1) / ORDER_JW) * ((n_rows + ORDER_RI - 1) / ORDER_RI) : 0; }
 constexpr int QUEUE_SHARDS = 32, QUEUE_SHARD_STRIDE = 32;
 enum : int {
     CTRL_TRACK_LEN = 0,          // length of track_list: the fast launch's hand-overs to the tracking launch

@@ -42,11 +42,11 @@ hipError_t stream_any(int RT, bool sym, bool track, dim3 grid, size_t lds, hipSt
 // prepare a call: operand images / tables / slot-ordered proportions + the longest-first order keys, then the scatter
 template <class C>
 hipError_t prep_any(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                    double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                    int *main_queue_head, int mode, int n_blocks, hipStream_t s) {
+                    double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                    int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s) {
     using T = typename C::T;
     const int collapse = (mode >> 2) & 1;    // bit 2: no longest-first order (experiment switch)
-    const int tiles = n_rows > 0 ? ((N + ORDER_JW - 1) / ORDER_JW) * ((n_rows + ORDER_RI - 1) / ORDER_RI) : 0;
+    const int tiles = (int)order_tile_count(N, n_rows);
     const int K4 = (K + 3) & ~3;
     const size_t lds = sizeof(float) * ((size_t)K4 * (ORDER_JW + 1) + (size_t)ORDER_RI * K4) + sizeof(int) * ORDER_NB;
     static bool attr_set[64] = {};    // more than 64 KB of dynamic LDS (K > 112) needs the opt-in; once per device
@@ -59,10 +59,12 @@ hipError_t prep_any(const double *M, int K, int RT, double reg, void *img, const
         attr_set[dev] = true;
     }
     hipLaunchKernelGGL(sinkhorn_prep_kernel<C>, dim3(tiles + PREP_SETUP_BLOCKS), dim3(256), lds, s, M, K, RT, reg, static_cast<T *>(img), P,
-                       static_cast<T *>(Pslot), N, write_tail, stop_thr, floor_ulps, tiles, n_rows, row_begin, row_step, bucket, hist, collapse);
+                       static_cast<T *>(Pslot), N, write_tail, stop_thr, floor_ulps, tiles, n_rows, row_begin, row_step, bucket, hist, tile_counts, collapse,
+                       zero_ctrl);
+    // the scatter: a workgroup per order tile while that is no more than two for each of the n_blocks the caller sized for
     if (n_rows > 0)
-        hipLaunchKernelGGL(order_scatter_kernel, dim3(n_blocks), dim3(256), 0, s, bucket, n_rows * N, hist, hist + ORDER_NB, list, split,
-                           main_queue_head, mode & 3);
+        hipLaunchKernelGGL(order_scatter_kernel, dim3(tiles < 2 * n_blocks ? tiles : 2 * n_blocks), dim3(2 * ORDER_JW), 0, s, bucket, N, n_rows,
+                           tiles, tile_counts, hist, hist + ORDER_NB, list, split, main_queue_head, mode & 3);
     return hipGetLastError();
 }
 }  // namespace
@@ -72,28 +74,28 @@ hipError_t launch_stream_f32(int RT, bool sym, bool track, dim3 grid, size_t lds
     return stream_any<CfgF32x16>(RT, sym, track, grid, lds, s, p);
 }
 hipError_t launch_prep_f64(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                           int *main_queue_head, int mode, int n_blocks, hipStream_t s);
+                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                           int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s);
 hipError_t launch_prep_s32(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                           int *main_queue_head, int mode, int n_blocks, hipStream_t s);
+                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                           int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s);
 hipError_t launch_prep_h32(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                           int *main_queue_head, int mode, int n_blocks, hipStream_t s);
+                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                           int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s);
 hipError_t launch_prep(int cfg, const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                       double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                       int *main_queue_head, int mode, int n_blocks, hipStream_t s) {
+                       double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                       int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s) {
     if (cfg == CFG_F64)
-        return launch_prep_f64(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
+        return launch_prep_f64(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
     if (cfg == CFG_H32)
-        return launch_prep_h32(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
+        return launch_prep_h32(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
     if (cfg == CFG_S32)
-        return launch_prep_s32(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
-    return prep_any<CfgF32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
+        return launch_prep_s32(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
+    return prep_any<CfgF32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
 }
 size_t track_img_elems(int cfg, int RT) { return cfg == CFG_H32 ? (size_t)track_img_offset<CfgH32x16>(RT) : 0; }
 size_t img_elems(int cfg, int RT) {
@@ -117,10 +119,10 @@ hipError_t launch_solo_track_f64(dim3 grid, hipStream_t s, const GridParams &p) 
     return hipGetLastError();
 }
 hipError_t launch_prep_f64(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                           int *main_queue_head, int mode, int n_blocks, hipStream_t s) {
-    return prep_any<CfgF64x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
+                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                           int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s) {
+    return prep_any<CfgF64x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
 }
 #elif SK_PART == 7
 // split configuration with only register 0 of the last row-tile live (K mod 16 in 1..4): TV = 1 skips the dead registers
@@ -139,10 +141,10 @@ hipError_t launch_stream_h32(int RT, bool sym, int live1, dim3 grid, size_t lds,
     return stream_any<CfgH32x16>(RT, sym, false, grid, lds, s, p);
 }
 hipError_t launch_prep_h32(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                           int *main_queue_head, int mode, int n_blocks, hipStream_t s) {
-    return prep_any<CfgH32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
+                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                           int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s) {
+    return prep_any<CfgH32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
 }
 #elif SK_PART == 6
 hipError_t launch_stream_s32_l1(int RT, bool sym, bool track, dim3 grid, size_t lds, hipStream_t s, const GridParams &p);
@@ -151,10 +153,10 @@ hipError_t launch_stream_s32(int RT, bool sym, bool track, int live1, dim3 grid,
     return stream_any<CfgS32x16>(RT, sym, track, grid, lds, s, p);
 }
 hipError_t launch_prep_s32(const double *M, int K, int RT, double reg, void *img, const double *P, void *Pslot, int N, int write_tail,
-                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *list, int *split,
-                           int *main_queue_head, int mode, int n_blocks, hipStream_t s) {
-    return prep_any<CfgS32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, list, split,
-                               main_queue_head, mode, n_blocks, s);
+                           double stop_thr, double floor_ulps, int n_rows, int row_begin, int row_step, unsigned char *bucket, int *hist, int *tile_counts, int *list, int *split,
+                           int *main_queue_head, int mode, int n_blocks, int *zero_ctrl, hipStream_t s) {
+    return prep_any<CfgS32x16>(M, K, RT, reg, img, P, Pslot, N, write_tail, stop_thr, floor_ulps, n_rows, row_begin, row_step, bucket, hist, tile_counts, list, split,
+                               main_queue_head, mode, n_blocks, zero_ctrl, s);
 }
 #else
 #if SK_PART == 2

@@ -602,6 +602,37 @@ int pilot_ot_nb_group_fits(const void *Y, int Y_is_device, int dtype, long long 
                            int *flags, int *n_not_converged);
 int pilot_ot_nb_glm_max_samples(void);
 
+/* pilot_ot_nb_shrink (K23): the shrunken fold change that pilotpy's compute_pseudobulk_DE reads after
+ * `lfcShrink(dds, coef, res, type = "apeglm")` (plot/pseudobulk_DE_analysis.py:140-151; Zhu, Ibrahim, Love 2019), for two groups:
+ * code 0 the denominator, code 1 the numerator.  apeglm is not installed where this library is built, so the rule is THIS
+ * LIBRARY'S STATEMENT, unpinned (restated in tests/nb_shrink_restatement.py).  Y, codes, size_factors as above
+ * with n_groups = 2; dispersion: the gene's final dispersion alpha (host; NaN leaves the gene out: NaN everywhere, flags 0).
+ * Natural-log scale.  Per gene, eta_j = b0 + b1 [codes[j] = 1] + log s_j, mu_j = exp(eta_j), and the log posterior up to constants
+ *     P(b0, b1) = sum_j [c_j log(alpha mu_j) - (c_j + 1/alpha) log1p(alpha mu_j)] - b0^2 / (2 sigma0^2) - log1p(b1^2 / S^2)
+ * with sigma0 = intercept_scale (apeglm's prior.no.shrink.scale, 15) and S = prior_scale of the Cauchy prior on b1 (prior.df = 1).
+ * P is strictly concave in b0; the profile p(b1) = max_b0 P(b0, b1) has its largest value between 0 and the maximum-likelihood
+ * b1 and can have TWO local maxima there, so the estimate is defined BY THIS SEARCH: far_end[gene] = sg E (host, finite; sg the
+ * sign of the maximum-likelihood b1, E = |it| + 1, or 30 where a group's fit is PILOT_OT_NB_FLOORED); t in [0, asinh(E / S)] with
+ * b1 = sg S sinh(t); six rounds of the 64-point grid t_i = lo + (hi - lo) i / 63; b = the first largest p (lowest index on ties);
+ * the next bracket is [t_max(b-1,0), t_min(b+1,63)].  b = 63 in a bracket that still ends at asinh(E / S) sets
+ * PILOT_OT_NB_AT_BOUND.  For every grid point b0 is the root of sum_j (c_j - mu_j) / (1 + alpha mu_j) - b0 / sigma0^2 by safeguarded
+ * Newton / bisection steps as pilot_ot_nb_group_fits' (|step| <= 1e-12; 100 steps in any of them set PILOT_OT_NB_NOT_CONVERGED),
+ * each grid point started from its own b0 of the round before.  Same bits as stated above for the K22 calls.
+ * Out (host, n_genes): beta0, beta1, objective = b0, b1 and p at the last round's winner; info (n_genes x 2): the groups' observed
+ * information W_g = sum_{j in g} mu_j (1 + alpha c_j) / (1 + alpha mu_j)^2 there; flags: PILOT_OT_NB_* in the low
+ * PILOT_OT_NB_SHRINK_STEPS_SHIFT bits, above them the gene's inner steps summed over the grid points and rounds; *n_at_bound
+ * (nullable): the genes flagged PILOT_OT_NB_AT_BOUND.
+ * PILOT_OT_EINVAL (before any HIP call): the cases of pilot_ot_nb_group_fits with n_groups = 2 (so m >= 3 and both groups have a
+ * sample), a prior_scale or intercept_scale not positive and finite, a far_end not finite; after the check pass a negative or
+ * non-finite count (*bad_row / *bad_col as pilot_ot_nb_dispersions).  PILOT_OT_ENOTSUP: m > pilot_ot_nb_glm_max_samples() (a gene's
+ * counts and size factors are staged in LDS, 16 m bytes). */
+#define PILOT_OT_NB_AT_BOUND 4
+#define PILOT_OT_NB_SHRINK_STEPS_SHIFT 8
+int pilot_ot_nb_shrink(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
+                       const double *size_factors, const double *dispersion, const double *far_end, double prior_scale,
+                       double intercept_scale, double *beta0, double *beta1, double *objective, double *info, int *flags, int *n_at_bound,
+                       long long *bad_row, int *bad_col);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

@@ -27,6 +27,7 @@ TRAJFIT_OLS, TRAJFIT_HUBER, TRAJFIT_NOT_CONVERGED = 0, 1, 1
 PCA_NOT_CONVERGED, PCA_RANK_DEFICIENT = 1, 2
 KNN_ROWS_MAX_K = 64
 NB_NOT_CONVERGED, NB_FLOORED = 1, 2
+NB_AT_BOUND, NB_SHRINK_STEPS_SHIFT = 4, 8
 ELASTIC_CONVERGED, ELASTIC_SINGULAR, ELASTIC_MAX_NODES, ELASTIC_MAX_D = 1, 2, 65, 64
 
 # every symbol include/pilot_ot.h declares (tests check the library exports all of them)
@@ -53,7 +54,7 @@ SYMBOLS = [
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
     "pilot_ot_rank_sums", "pilot_ot_csr_rank_sums", "pilot_ot_rank_sums_wave_max", "pilot_ot_rank_sums_wg_max",
     "pilot_ot_rank_sums_sort_tile",
-    "pilot_ot_nb_dispersions", "pilot_ot_nb_group_fits", "pilot_ot_nb_glm_max_samples",
+    "pilot_ot_nb_dispersions", "pilot_ot_nb_group_fits", "pilot_ot_nb_glm_max_samples", "pilot_ot_nb_shrink",
     "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain", "pilot_ot_leiden",
     "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
     "pilot_ot_elastic_fit_batch", "pilot_ot_point_moments", "pilot_ot_tree_projection",
@@ -195,6 +196,8 @@ def load() -> ctypes.CDLL:
                                           dp, llp, ip]
     L.pilot_ot_nb_group_fits.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, dp, dp, dp, dp, ip, ip, ip]
     L.pilot_ot_nb_glm_max_samples.argtypes = []
+    L.pilot_ot_nb_shrink.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, dp, dp, dp, c_dbl, c_dbl, dp, dp, dp,
+                                     dp, ip, ip, llp, ip]
     L.pilot_ot_csr_pca.argtypes = [c_vp, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_pca.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_knn_rows.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, ctypes.c_longlong,

@@ -1,5 +1,5 @@
 // C ABI of the negative-binomial GLM for a one-factor design (include/pilot_ot.h, section "negative-binomial GLM"; kernels:
-// nb_glm_kernels.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
+// nb_glm_kernels.hpp, nb_shrink_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
 // codes, size factors, dispersions and the results are host arrays.  The host orders the samples by group once per call.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 
 #include "abi_common.hpp"
 #include "nb_glm_kernels.hpp"
+#include "nb_shrink_kernel.hpp"
 
 namespace {
 
@@ -130,6 +131,42 @@ int group_fits(const void *y, long long ld, long long m, int n_genes, int k, con
     return PILOT_OT_OK;
 }
 
+template <typename T>
+int shrink(const void *y, long long ld, int m, int n_genes, const DevDesign &dd, int n0, const double *dispersion, const double *far_end,
+           double prior_scale, double intercept_scale, double *beta0, double *beta1, double *objective, double *info, int *flags,
+           long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    const size_t G = (size_t)n_genes;
+    double *d_dbl;                                           // dispersion, far_end | beta0, beta1, objective, info (2 a gene)
+    int *d_flags;
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, 7 * G, &d_dbl));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, G, &d_flags));
+    HIP_TRY(hipMemcpy(d_dbl, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dbl + G, far_end, sizeof(double) * G, hipMemcpyHostToDevice));
+    const size_t lds = sizeof(double) * 2 * (size_t)m;
+    auto kern = pilot::nb_shrink_kernel<T>;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_genes), dim3(64), lds, nullptr, static_cast<const T *>(y), ld, m, n0, dd.order, dd.ss, d_dbl,
+                       d_dbl + G, prior_scale, intercept_scale, d_dbl + 2 * G, d_dbl + 3 * G, d_dbl + 4 * G, d_dbl + 5 * G, d_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(beta0, d_dbl + 2 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(beta1, d_dbl + 3 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(objective, d_dbl + 4 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(info, d_dbl + 5 * G, sizeof(double) * 2 * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags, d_flags, sizeof(int) * G, hipMemcpyDeviceToHost));
+    return PILOT_OT_OK;
+}
+
+// a dispersion is NaN (the gene is left out) or within [minDisp, maxDisp]
+int check_dispersions(const double *dispersion, int n_genes, long long m) {
+    const double max_disp = pilot::nb_max_disp(m);
+    for (int j = 0; j < n_genes; ++j)
+        if (!std::isnan(dispersion[j]) && !(dispersion[j] >= pilot::NB_MIN_DISP && dispersion[j] <= max_disp))
+            return fail(PILOT_OT_EINVAL, "dispersion[%d]=%g outside [%g, %g] (NaN: the gene is left out)", j, dispersion[j], pilot::NB_MIN_DISP,
+                        max_disp);
+    return PILOT_OT_OK;
+}
+
 int check_matrix(int dtype, int n_genes, long long ld) {
     if (n_genes < 1) return fail(PILOT_OT_EINVAL, "n_genes=%d", n_genes);
     if (int rc = pilot::check_ld(ld, n_genes)) return rc;
@@ -172,11 +209,7 @@ PILOT_API int pilot_ot_nb_group_fits(const void *Y, int Y_is_device, int dtype, 
     if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
     Design d;
     if (int rc = make_design(m, codes, n_groups, size_factors, d)) return rc;
-    const double max_disp = pilot::nb_max_disp(m);
-    for (int j = 0; j < n_genes; ++j)
-        if (!std::isnan(dispersion[j]) && !(dispersion[j] >= pilot::NB_MIN_DISP && dispersion[j] <= max_disp))
-            return fail(PILOT_OT_EINVAL, "dispersion[%d]=%g outside [%g, %g] (NaN: the gene is left out)", j, dispersion[j], pilot::NB_MIN_DISP,
-                        max_disp);
+    if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
     if ((long long)n_genes * n_groups > INT_MAX)
         return fail(PILOT_OT_ENOTSUP, "n_genes * n_groups = %lld results need more than 32-bit indices", (long long)n_genes * n_groups);
     const void *y;
@@ -190,5 +223,41 @@ PILOT_API int pilot_ot_nb_group_fits(const void *Y, int Y_is_device, int dtype, 
     int bad = 0;
     for (long long t = 0; t < (long long)n_genes * n_groups; ++t) bad += (flags[t] & pilot::NB_FLAG_NOT_CONVERGED) != 0;
     if (n_not_converged) *n_not_converged = bad;
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_nb_shrink(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
+                                 const double *size_factors, const double *dispersion, const double *far_end, double prior_scale,
+                                 double intercept_scale, double *beta0, double *beta1, double *objective, double *info, int *flags,
+                                 int *n_at_bound, long long *bad_row, int *bad_col) {
+    if (bad_row) *bad_row = -1;
+    if (bad_col) *bad_col = -1;
+    if (n_at_bound) *n_at_bound = 0;
+    if (!Y || !codes || !size_factors || !dispersion || !far_end || !beta0 || !beta1 || !objective || !info || !flags)
+        return fail(PILOT_OT_EINVAL, "NULL pointer");
+    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
+    if (!(std::isfinite(prior_scale) && prior_scale > 0.0)) return fail(PILOT_OT_EINVAL, "prior_scale=%g must be positive and finite", prior_scale);
+    if (!(std::isfinite(intercept_scale) && intercept_scale > 0.0))
+        return fail(PILOT_OT_EINVAL, "intercept_scale=%g must be positive and finite", intercept_scale);
+    Design d;
+    if (int rc = make_design(m, codes, 2, size_factors, d)) return rc;
+    if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
+    for (int j = 0; j < n_genes; ++j)
+        if (!std::isfinite(far_end[j])) return fail(PILOT_OT_EINVAL, "far_end[%d]=%g must be finite", j, far_end[j]);
+    if (m > pilot::NB_MAX_SAMPLES)
+        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts and size factors are staged in LDS, at most %d", m, pilot::NB_MAX_SAMPLES);
+    const void *y;
+    long long y_ld;
+    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
+    DevDesign dd;
+    if (int rc = upload_design(d, dd)) return rc;
+    if (int rc = dtype == 0 ? shrink<float>(y, y_ld, (int)m, n_genes, dd, d.gstart[1], dispersion, far_end, prior_scale, intercept_scale, beta0,
+                                            beta1, objective, info, flags, bad_row, bad_col)
+                            : shrink<double>(y, y_ld, (int)m, n_genes, dd, d.gstart[1], dispersion, far_end, prior_scale, intercept_scale, beta0,
+                                             beta1, objective, info, flags, bad_row, bad_col))
+        return rc;
+    int at_bound = 0;
+    for (int j = 0; j < n_genes; ++j) at_bound += (flags[j] & pilot::NB_FLAG_AT_BOUND) != 0;
+    if (n_at_bound) *n_at_bound = at_bound;
     return PILOT_OT_OK;
 }

@@ -1405,6 +1405,118 @@ def nb_prior_var(log_disp, log_trend, m, k):
     return max(var_log_disp - float(special.polygamma(1, (m - k) / 2.0)), 0.25), var_log_disp
 
 
+# ---- shrunken fold changes (K23; apeglm's posterior mode for the two groups of pilotpy's compute_pseudobulk_DE) ----------------
+NB_INTERCEPT_SCALE = 15.0
+NB_FAR_END_FLOORED = 30.0
+
+
+def nb_far_end(lfc, floored):
+    """``sg * E`` of :func:`nb_shrink`'s search from the maximum-likelihood fold change ``lfc`` (natural log): sg its sign (+ for
+    0), ``E = |lfc| + 1``, or 30 where ``floored`` (a group's fit carries ``_lib.NB_FLOORED``: the likelihood is monotone there
+    and only the prior bounds the mode).  A NaN ``lfc`` (a gene left out) gives 1."""
+    lfc, floored = np.asarray(lfc, dtype=np.float64), np.asarray(floored, dtype=bool)
+    with np.errstate(invalid="ignore"):
+        E = np.where(floored, NB_FAR_END_FLOORED, np.abs(lfc) + 1.0)
+        return np.where(np.isnan(lfc), 1.0, np.where(lfc >= 0, E, -E))
+
+
+def nb_shrink(counts, codes, size_factors, dispersion, far_end, prior_scale, intercept_scale=NB_INTERCEPT_SCALE, return_info=False):
+    """K23: per gene (column) of ``counts`` the posterior mode ``(beta0, beta1)``, on the natural-log scale, of the two-group
+    negative-binomial model ``log mu_j = beta0 + beta1 [codes[j] = 1] + log s_j`` at the gene's ``dispersion`` under apeglm's
+    priors: a normal of scale ``intercept_scale`` on beta0 and a Cauchy of scale ``prior_scale`` on beta1 (include/pilot_ot.h,
+    pilot_ot_nb_shrink; the rule is this library's statement, unpinned).  The profile over beta0 can have two
+    local maxima in beta1, so the mode is found by six rounds of a 64-point grid over ``t in [0, asinh(E / S)]``,
+    ``beta1 = sg S sinh(t)``, with ``far_end = sg E`` per gene (:func:`nb_far_end`).  ``counts``, ``codes`` (0 / 1, both used)
+    and ``size_factors`` as :func:`nb_dispersions`; ``dispersion``: one per gene in [1e-8, max(10, m)], NaN leaves the gene out
+    (NaN results, no flags).  Returns ``(beta0, beta1)``; with ``return_info`` also a dict: ``objective`` (the log posterior up
+    to constants there), ``w0`` / ``w1`` (the groups' observed information, for :func:`nb_posterior_sd`), ``flags``
+    (``_lib.NB_NOT_CONVERGED``, ``_lib.NB_AT_BOUND``), ``steps`` (the gene's inner Newton steps over all grid points and rounds),
+    ``n_at_bound``, ``n_not_converged``.  The same bits from a repeated call, from float32 and float64 storage and from host and
+    device matrices.  Errors as :func:`nb_dispersions`."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    codes, _, sf = _nb_args(Y.rows, Y.cols, codes, 2, size_factors)
+    alpha, far = np.ascontiguousarray(dispersion, dtype=np.float64), np.ascontiguousarray(far_end, dtype=np.float64)
+    if alpha.shape != (Y.cols,) or far.shape != (Y.cols,):
+        raise ValueError("dispersion %s and far_end %s: one of each for %d genes" % (alpha.shape, far.shape, Y.cols))
+    given = alpha[~np.isnan(alpha)]
+    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(Y.rows)):
+        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(Y.rows)))
+    if not np.isfinite(far).all():
+        raise ValueError("far_end must be finite")
+    prior_scale, intercept_scale = float(prior_scale), float(intercept_scale)
+    if not (np.isfinite(prior_scale) and prior_scale > 0):
+        raise ValueError("prior_scale=%r must be positive and finite" % (prior_scale,))
+    if not (np.isfinite(intercept_scale) and intercept_scale > 0):
+        raise ValueError("intercept_scale=%r must be positive and finite" % (intercept_scale,))
+    limit = nb_glm_limits()
+    if Y.rows > limit:
+        raise NotImplementedError("nb_shrink: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    b0, b1, objective, w = np.empty(Y.cols), np.empty(Y.cols), np.empty(Y.cols), np.empty((Y.cols, 2))
+    raw = np.empty(Y.cols, dtype=np.int32)
+    at_bound, bad_row, bad_col = ctypes.c_int(0), ctypes.c_longlong(-1), ctypes.c_int(-1)
+    try:
+        _lib.check(_lib.load().pilot_ot_nb_shrink(
+            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), _lib.dptr(sf), _lib.dptr(alpha),
+            _lib.dptr(far), prior_scale, intercept_scale, _lib.dptr(b0), _lib.dptr(b1), _lib.dptr(objective), _lib.dptr(w),
+            _lib.iptr(raw), ctypes.byref(at_bound), ctypes.byref(bad_row), ctypes.byref(bad_col)))
+    except ValueError as err:
+        raise _nb_bad_count(err, bad_row, bad_col)
+    if not return_info:
+        return b0, b1
+    flags = raw & ((1 << _lib.NB_SHRINK_STEPS_SHIFT) - 1)
+    return b0, b1, {"objective": objective, "w0": w[:, 0].copy(), "w1": w[:, 1].copy(), "flags": flags,
+                    "steps": raw >> _lib.NB_SHRINK_STEPS_SHIFT, "n_at_bound": at_bound.value,
+                    "n_not_converged": int(np.count_nonzero(flags & _lib.NB_NOT_CONVERGED))}
+
+
+def nb_prior_scale(lfc, se, use=None):
+    """The scale of :func:`nb_shrink`'s Cauchy prior from the maximum-likelihood fold changes ``lfc`` and their standard errors
+    ``se`` (natural log), as apeglm's ``priorVar``; numpy and scipy.  Over the genes where both are finite (and ``use``, a mask:
+    the genes without a floored group fit), with ``D = lfc`` and ``V = se^2``: ``A`` is the root on [1e-6, 400] of the score of the
+    marginal likelihood ``D ~ N(0, V + A)``, ``f(A) = sum (D^2 - V - A) / (V + A)^2`` (``scipy.optimize.brentq``); 1e-6 if
+    ``f(1e-6) <= 0`` and 400 if ``f(400) >= 0``.  Returns ``(S, A)`` with ``S = min(sqrt(A), 1)``.  Fewer than two usable genes:
+    ValueError."""
+    from scipy import optimize
+    D, se = np.asarray(lfc, dtype=np.float64), np.asarray(se, dtype=np.float64)
+    if D.ndim != 1 or D.shape != se.shape:
+        raise ValueError("lfc %s and se %s: one of each per gene" % (D.shape, se.shape))
+    ok = np.isfinite(D) & np.isfinite(se)
+    if use is not None:
+        use = np.asarray(use, dtype=bool)
+        if use.shape != D.shape:
+            raise ValueError("use has shape %s for %d genes" % (use.shape, D.size))
+        ok &= use
+    if np.count_nonzero(ok) < 2:
+        raise ValueError("nb_prior_scale: %d usable genes (finite, no floored group fit), at least 2" % np.count_nonzero(ok))
+    D, V = D[ok], se[ok] ** 2
+
+    def f(A):
+        return float(((D * D - V - A) / (V + A) ** 2).sum())
+
+    lo, hi = 1e-6, 400.0
+    if f(lo) <= 0:
+        A = lo
+    elif f(hi) >= 0:
+        A = hi
+    else:
+        A = float(optimize.brentq(f, lo, hi, xtol=1e-14, rtol=1e-14, maxiter=500))
+    return min(float(np.sqrt(A)), 1.0), A
+
+
+def nb_posterior_sd(beta1, w0, w1, prior_scale, intercept_scale=NB_INTERCEPT_SCALE):
+    """The Laplace approximation of the posterior standard deviation of beta1 at :func:`nb_shrink`'s mode: with the Hessian of
+    minus the log posterior, ``H00 = w0 + w1 + 1 / sigma0^2``, ``H01 = w1``, ``H11 = w1 + 2 (S^2 - b1^2) / (S^2 + b1^2)^2``,
+    ``sd = sqrt(H00 / (H00 H11 - H01^2))``; NaN where the determinant is not positive (the Cauchy prior is not log-concave
+    beyond ``|b1| = S``) and where an input is NaN."""
+    b1, w0, w1 = (np.asarray(a, dtype=np.float64) for a in (beta1, w0, w1))
+    S2 = float(prior_scale) ** 2
+    h00 = w0 + w1 + 1.0 / float(intercept_scale) ** 2
+    h11 = w1 + 2.0 * (S2 - b1 * b1) / (S2 + b1 * b1) ** 2
+    det = h00 * h11 - w1 * w1
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(det > 0, np.sqrt(h00 / det), np.nan)
+
+
 # ---- principal components (K15; scanpy's scale + tl.pca(svd_solver='arpack') of pilotpy's extract_annot_expression) ----------
 PCA_MAX_COMPS = 64
 

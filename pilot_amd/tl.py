@@ -2409,7 +2409,72 @@ def _nb_wald_table(genes, table, q, w):
     return out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
 
 
-def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=None, group2=None, cluster_col=None, fit_type="parametric"):
+def _check_shrink(shrink, who):
+    if shrink not in (None, "apeglm"):
+        raise ValueError("%s: shrink=%r must be None or 'apeglm'" % (who, shrink))
+
+
+def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
+    """The reference's ``lfcShrink(dds, coef, res, type = "apeglm")`` step (plot/pseudobulk_DE_analysis.py:146-151; Zhu, Ibrahim,
+    Love 2019) without R, on the device (``engine.nb_shrink``; apeglm is not installed where this library is built
+    and tested, so the rule is this library's statement, UNPINNED).  ``cluster_counts``: the samples x genes counts of the
+    selected samples; ``groups``: 0 / 1 or a boolean per sample, 1 for the numerator group; ``de``: the frame
+    :func:`compute_pseudobulk_DE` returned for those samples, which supplies the dispersions, the size factors
+    (``attrs['size_factors']``), the maximum-likelihood columns and which genes have a floored group fit (``attrs['floored']``).
+    Per gene the posterior mode of the fold change under a Cauchy prior of scale ``prior_scale`` (default: estimated from the
+    maximum-likelihood fold changes and their standard errors, ``engine.nb_prior_scale``, at most 1) and a wide normal on the
+    intercept, and its Laplace standard deviation (``engine.nb_posterior_sd``).  Returns a copy of ``de`` with
+    ``log2FoldChange = beta1 / ln 2`` and ``lfcSE = sd / ln 2`` (NaN where the posterior is not log-concave at its mode); the
+    new columns ``lfcMLE`` and ``lfcMLESE`` keep the old values; ``stat``, ``pvalue``, ``padj`` and the row order are unchanged,
+    as ``lfcShrink`` keeps the unshrunken Wald test.  ``attrs`` gains ``shrink='apeglm'``, ``prior_scale``, ``prior_var``,
+    ``n_at_bound`` (genes whose mode sits at the end of the searched interval; none is expected).
+
+    Not covered: s-values, other coefficients or more than two groups, apeglm's other likelihoods.  The intercept prior sits
+    on group 0, as in apeglm, so swapping the groups moves the estimate slightly instead of negating it."""
+    c, genes = _nb_counts(cluster_counts, "lfc_shrink")
+    codes = np.asarray(groups)
+    if codes.shape != (c.shape[0],):
+        raise ValueError("lfc_shrink: groups has shape %s for %d samples" % (codes.shape, c.shape[0]))
+    if codes.dtype.kind not in "biu" or not np.isin(codes, (0, 1)).all():
+        raise ValueError("lfc_shrink: groups must be 0 / 1 or boolean, 1 for the numerator group")
+    codes = codes.astype(np.int32)
+    if codes.min() == codes.max():
+        raise ValueError("lfc_shrink: every sample is in group %d" % codes[0])
+    needed = ["gene", "log2FoldChange", "lfcSE", "dispersion"]
+    if not hasattr(de, "columns") or any(col not in de.columns for col in needed):
+        raise ValueError("lfc_shrink: de must be a frame of compute_pseudobulk_DE (columns %s)" % ", ".join(needed))
+    if "lfcMLE" in de.columns:
+        raise ValueError("lfc_shrink: de is already shrunken (it has a column lfcMLE)")
+    if "size_factors" not in de.attrs or "floored" not in de.attrs:
+        raise ValueError("lfc_shrink: de.attrs lacks 'size_factors' / 'floored': pass the frame compute_pseudobulk_DE returned")
+    if prior_scale is not None and not (isinstance(prior_scale, (int, float, np.integer, np.floating)) and not isinstance(prior_scale, bool)
+                                        and np.isfinite(prior_scale) and prior_scale > 0):
+        raise ValueError("lfc_shrink: prior_scale=%r must be positive and finite (None: estimated)" % (prior_scale,))
+    named = pd.Index(de["gene"])
+    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)      # the frame's row of every gene of the table
+    if len(de) != len(genes) or (at < 0).any():
+        raise ValueError("lfc_shrink: the genes of de are not the columns of cluster_counts")
+    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
+    ln2 = np.log(2.0)
+    disp = de["dispersion"].to_numpy(dtype=np.float64)[at]
+    lfc, se = de["log2FoldChange"].to_numpy(dtype=np.float64)[at] * ln2, de["lfcSE"].to_numpy(dtype=np.float64)[at] * ln2
+    floored = np.asarray(de.attrs["floored"].reindex(genes), dtype=bool)
+    if prior_scale is None:
+        S, A = engine.nb_prior_scale(lfc, se, use=~floored)
+    else:
+        S, A = float(prior_scale), float(prior_scale) ** 2
+    b0, b1, info = engine.nb_shrink(c, codes, sf, disp, engine.nb_far_end(lfc, floored), S, return_info=True)
+    sd = engine.nb_posterior_sd(b1, info["w0"], info["w1"], S)
+    row = genes.get_indexer(de["gene"])                          # the table's column of every row of the frame
+    out = de.copy()
+    out["lfcMLE"], out["lfcMLESE"] = de["log2FoldChange"], de["lfcSE"]
+    out["log2FoldChange"], out["lfcSE"] = (b1 / ln2)[row], (sd / ln2)[row]
+    out.attrs.update(shrink="apeglm", prior_scale=S, prior_var=A, n_at_bound=info["n_at_bound"])
+    return out
+
+
+def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=None, group2=None, cluster_col=None, fit_type="parametric",
+                          shrink=None, prior_scale=None):
     """The reference's ``compute_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:96-159) without R: the negative-binomial Wald
     test of DESeq2 for the design ``~ stage`` between two patient sub-groups, on the device.  Takes :func:`pseudobulk_inputs`'
     pair unchanged; the samples of ``group1`` and ``group2`` (by ``cluster_metadata[cluster_col]``) are selected first, as the
@@ -2420,14 +2485,20 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     the genes with a p-value.  Returns ONE frame -- ``gene, baseMean, log2FoldChange, lfcSE, stat, pvalue, padj, dispersion`` --
     ordered by ``padj`` (NaN last, ties in gene order: the reference's ``arrange(padj)``); a gene that is zero in every selected
     sample has NaN in every numeric column.  ``attrs``: ``dispersions`` (the frame of :func:`deseq2_dispersions`),
-    ``size_factors``, ``n_not_converged``.
+    ``size_factors``, ``n_not_converged``, ``floored`` (per gene whether a group's fit was raised to its floor, a group of zeros).
 
-    Deviations from the reference's call, which is unpinned here (no DESeq2 where this library is tested): no apeglm shrinkage --
-    ``log2FoldChange`` is the maximum-likelihood estimate where ``lfcShrink`` returns a shrunken one, and ``lfcSE`` its Wald
-    standard error; no ``rlog``; no Cook's-distance outlier handling; no independent filtering, ``padj`` is plain BH; no beta
+    ``shrink``: ``None`` (the default) returns the maximum-likelihood ``log2FoldChange`` and its Wald ``lfcSE``; ``"apeglm"``
+    applies :func:`lfc_shrink` (with ``prior_scale``), which is what the reference's call returns: the posterior mode and
+    standard deviation under apeglm's prior, beside the unchanged Wald columns, with ``lfcMLE`` / ``lfcMLESE`` keeping the
+    maximum-likelihood values.  Anything else: ValueError before any device work.
+
+    Deviations from the reference's call, which is unpinned here (no DESeq2 or apeglm where this library is tested): the
+    shrinkage is opt-in (``shrink="apeglm"``) and its mode comes from a global grid search, not apeglm's local optimiser; no
+    s-values; no ``rlog``; no Cook's-distance outlier handling; no independent filtering, ``padj`` is plain BH; no beta
     ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the formula where DESeq2 simulates; the
     reference returns R's list (the frame at index 1), this returns the frame.  Fewer than three selected samples, or a group
     without samples: ValueError before any device work."""
+    _check_shrink(shrink, "compute_pseudobulk_DE")
     if cluster_col is None or cluster_col not in cluster_metadata.columns:
         raise ValueError("compute_pseudobulk_DE: cluster_col=%r is not a column of cluster_metadata" % (cluster_col,))
     stage = cluster_metadata[cluster_col]
@@ -2446,20 +2517,25 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     table = _nb_dispersion_table(c, genes, codes, 2, sf, fit_type)
     q, w, info = engine.nb_group_fits(c, codes, 2, sf, table["dispersion"].to_numpy(), return_info=True)
     out = _nb_wald_table(genes, table, q, w)
-    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=info["n_not_converged"])
-    return out
+    floored = pd.Series(((info["flags"] & engine._lib.NB_FLOORED) != 0).any(axis=1), index=genes)
+    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=info["n_not_converged"],
+                     floored=floored)
+    return lfc_shrink(counts, codes, out, prior_scale) if shrink else out
 
 
 def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
-                      remove_samples=()):
+                      remove_samples=(), shrink=None):
     """The numbers of the reference's ``get_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:506-666) in one process with no R:
     :func:`pseudobulk_inputs` of ``cell_type``, then :func:`compute_pseudobulk_DE` for every pair of
     ``itertools.combinations(np.unique(proportion_df[cluster_col]), 2)``.  Returns ``{"<g2>vs<g1>": frame}`` (the names of the
-    reference's ``_DE.csv`` files; the fold change is g2 over g1).  No plots, no files, no rlog PCA, no enrichment; the deviations
-    of :func:`compute_pseudobulk_DE` apply."""
+    reference's ``_DE.csv`` files; the fold change is g2 over g1).  ``shrink`` is :func:`compute_pseudobulk_DE`'s (``"apeglm"``:
+    the shrunken fold changes the reference writes).  No plots, no files, no rlog PCA, no enrichment; the deviations of
+    :func:`compute_pseudobulk_DE` apply."""
     import itertools
+    _check_shrink(shrink, "get_pseudobulk_DE")
     cluster_counts, cluster_metadata = pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col, sample_col, cluster_col, remove_samples)
     out = {}
     for g1, g2 in itertools.combinations(np.unique(proportion_df[cluster_col]), 2):
-        out["%svs%s" % (g2, g1)] = compute_pseudobulk_DE(cluster_counts, cluster_metadata, group1=g1, group2=g2, cluster_col=cluster_col)
+        out["%svs%s" % (g2, g1)] = compute_pseudobulk_DE(cluster_counts, cluster_metadata, group1=g1, group2=g2, cluster_col=cluster_col,
+                                                         shrink=shrink)
     return out

@@ -10,7 +10,14 @@ prior: the MAP pass) and around ``nb_group_fits`` -- each call ends in device-to
 its c = 0 path for all but one sample (log1p, one division and the running sums: everything it does except the two lgamma and the
 log of a positive count), which prices the arithmetic around lgamma.  Host: the restatement on --host-genes of the genes (default
 200), scaled by genes / host-genes and reported as such.  No DESeq2 timing exists where this library is built.
-Writes OUT/rate.txt (--out, default profiles/pseudobulk_de/)."""
+Writes OUT/rate.txt (--out, default profiles/pseudobulk_de/).
+
+--shrink: instead, the shrunken fold change (K23: engine.nb_shrink) beside the dispersion pass on the same tables: both are one
+wave per gene and six 64-point rounds over LDS-staged samples; nb_shrink replaces two lgamma a sample by an inner Newton loop of
+divides.  The dispersions come from one MAP-less pass, the far ends from nb_group_fits, the prior scale from
+engine.nb_prior_scale.  ``nb_dispersions`` and ``nb_shrink`` alternate in one loop, best of --reps each; the mean inner steps a
+lane and round (from the call's ``steps``) go beside the times so that the ratio can be read.  Host: the vectorised restatement
+(tests/nb_shrink_restatement.py) on --host-genes genes, scaled.  Writes OUT/shrink_rate.txt."""
 import argparse
 import os
 import sys
@@ -30,6 +37,7 @@ def main():
     ap.add_argument("--genes", type=int, default=20000)
     ap.add_argument("--host-genes", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--shrink", action="store_true")
     a = ap.parse_args()
     import nb_glm_restatement as RR
     from pilot_amd import _lib, engine
@@ -50,7 +58,47 @@ def main():
         return best, out
 
     say("%s; %s; at most %d samples a gene" % (_lib.device_name(), time.strftime("%Y-%m-%d"), engine.nb_glm_limits()))
-    for m in a.samples:
+    for m in (a.samples if a.shrink else ()):
+        import nb_shrink_restatement as SR
+        rng = np.random.default_rng(m)
+        s = RR.size_factors(rng, m)
+        codes = (np.arange(m) % 2).astype(np.int32)
+        c = RR.nb_class(rng, s, codes, 2, a.genes)
+        D = engine.DeviceMatrix.upload(c.astype(np.float32))
+        alpha = engine.nb_clip(np.exp(engine.nb_dispersions(D, codes, 2, s)), m)
+        q, w, fit = engine.nb_group_fits(D, codes, 2, s, alpha, return_info=True)
+        floored = ((fit["flags"] & _lib.NB_FLOORED) != 0).any(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lfc, se = np.log(q[:, 1]) - np.log(q[:, 0]), np.sqrt(1.0 / w[:, 0] + 1.0 / w[:, 1])
+        S, A = engine.nb_prior_scale(lfc, se, use=~floored)
+        far = engine.nb_far_end(lfc, floored)
+        engine.nb_dispersions(D, codes, 2, s)
+        engine.nb_shrink(D, codes, s, alpha, far, S)
+        t_disp = t_shrink = np.inf
+        for _ in range(a.reps):                                         # the two calls alternate
+            t0 = time.perf_counter()
+            engine.nb_dispersions(D, codes, 2, s)
+            t1 = time.perf_counter()
+            b0, b1, info = engine.nb_shrink(D, codes, s, alpha, far, S, return_info=True)
+            t2 = time.perf_counter()
+            t_disp, t_shrink = min(t_disp, t1 - t0), min(t_shrink, t2 - t1)
+        live = ~np.isnan(alpha)
+        say("case %d genes x %d samples, float32 in HBM, 2 groups; prior scale %.4g (prior variance %.4g), %d floored genes"
+            % (a.genes, m, S, A, floored.sum()))
+        say("  nb_shrink %.2f ms, nb_dispersions (gene-wise) %.2f ms beside it: ratio %.2f; best of %d, alternating"
+            % (1e3 * t_shrink, 1e3 * t_disp, t_shrink / t_disp, a.reps))
+        say("  inner steps a lane and round: mean %.2f, largest gene mean %.2f; %d at bound, %d not converged"
+            % (info["steps"][live].mean() / 384.0, info["steps"][live].max() / 384.0, info["n_at_bound"], info["n_not_converged"]))
+        h = min(a.host_genes, a.genes)
+        t0 = time.perf_counter()
+        found = SR.search(c[:, :h], codes, s, alpha[:h], far[:h], S)
+        t_host = time.perf_counter() - t0
+        res = SR.resolved(c[:, :h], codes, s, alpha[:h], far[:h], S, found)
+        say("  host restatement on %d genes: %.2f s; scaled by %d / %d: %.0f s; device against it on the resolved genes (%d): t off by "
+            "at most %.2g" % (h, t_host, a.genes, h, t_host * a.genes / h, res.sum(),
+                              np.abs(SR.t_of(b1[:h][res], S) - found["t"][res]).max(initial=0)))
+        del D
+    for m in (() if a.shrink else a.samples):
         rng = np.random.default_rng(m)
         s = RR.size_factors(rng, m)
         codes = (np.arange(m) % 2).astype(np.int32)
@@ -85,7 +133,7 @@ def main():
                np.abs(np.expm1(x[:h][res] - xh[res])).max(initial=0)))
         del D, Z
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

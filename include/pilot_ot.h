@@ -117,6 +117,19 @@ int pilot_ot_shutdown(void);                      /* free the calling thread's c
  * The library reads no environment variable that changes what it computes. */
 int pilot_ot_test_switch(const char *name, const char *value);
 
+/* TEST HOOK: the workspace guard.  Every device temporary of the feature entry points comes from the calling thread's pool, one
+ * buffer per slot.  With the test switch "PILOT_OT_WS_GUARD" set to "1" every hand-out synchronises the device, fills the bytes
+ * requested with 0xFF (float and double NaN, int -1), keeps at least 256 bytes of slack behind them filled with the canary 0xA5,
+ * and first verifies the canary of the slot's previous hand-out; a result that changes under the guard read scratch nobody wrote,
+ * a damaged canary is an access past the request.  The value "selftest" also damages the canary byte at offset 7 of the first
+ * slot handed out (the control of the check itself).  Unset, the pool makes no extra HIP call. */
+int pilot_ot_ws_slot_count(void);              /* number of slots; no HIP call */
+const char *pilot_ot_ws_slot_name(int slot);   /* "WS_GS_PART", ...; NULL out of range; no HIP call */
+/* checks every slot's canary now; seen (nullable, slot_count bytes): 1 where the slot was handed out under guard since the last
+ * reset; bad_slot = -1 when intact, else the damaged slot, the first damaged offset past the request and the request's size;
+ * reset != 0 clears seen and the damage record afterwards */
+int pilot_ot_ws_guard_report(unsigned char *seen, int *bad_slot, long long *bad_offset, long long *bad_request, int reset);
+
 /* thin device-memory helpers so a host language without a HIP binding can keep data resident */
 int pilot_ot_dev_alloc(void **dptr, unsigned long long bytes);
 int pilot_ot_dev_free(void *dptr);

@@ -63,6 +63,7 @@ SYMBOLS = [
     "pilot_ot_multi_times", "pilot_ot_multi_rccl_info", "pilot_ot_sinkhorn_grid_multi", "pilot_ot_emd_grid_multi",
     "pilot_ot_comm_unique_id", "pilot_ot_comm_init_rank", "pilot_ot_comm_destroy", "pilot_ot_comm_info",
     "pilot_ot_comm_all_gather_rows", "pilot_ot_comm_all_reduce_max",
+    "pilot_ot_ws_slot_count", "pilot_ot_ws_slot_name", "pilot_ot_ws_guard_report",
 ]
 GATHER = {"auto": 0, "rccl": 1, "copy": 2}
 ROW_METRICS = {"euclidean": 0, "cosine": 1}
@@ -231,10 +232,14 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_comm_destroy.argtypes = [c_vp]
     L.pilot_ot_comm_all_gather_rows.argtypes = [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]
     L.pilot_ot_comm_all_reduce_max.argtypes = [c_vp, c_vp, c_int, c_vp]
+    L.pilot_ot_ws_slot_count.argtypes = []
+    L.pilot_ot_ws_slot_name.argtypes = [c_int]
+    L.pilot_ot_ws_guard_report.argtypes = [ctypes.POINTER(ctypes.c_ubyte), ip, llp, llp, c_int]
     for name in SYMBOLS:
         fn = getattr(L, name)
-        if name != "pilot_ot_last_error":
+        if name not in ("pilot_ot_last_error", "pilot_ot_ws_slot_name"):
             fn.restype = c_int
+    L.pilot_ot_ws_slot_name.restype = ctypes.c_char_p
     _lib = L
     return L
 

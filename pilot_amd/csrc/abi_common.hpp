@@ -21,31 +21,43 @@ void abi_multi_release();
 // The calling thread's pool of device temporaries: one buffer per slot, grown on demand, released by pilot_ot_shutdown.  Every
 // buffer of every translation unit has a slot of its own here, so two buffers that are live together (diffmap chains into the
 // consumer entry points) never share one.
+// The list of slots: the enum below and the name table (pilot_ot_ws_slot_name) both expand these lines, so they cannot disagree.
+#define PILOT_WS_SLOT_LIST(X) \
+    X(WS_PREPASS_X) X(WS_PREPASS) \
+    X(WS_COST_X) X(WS_COST_C) X(WS_COST_AUX) \
+    X(WS_CONS_E) X(WS_CONS_D) X(WS_CONS_MAX) X(WS_CONS_LABELS) X(WS_CONS_SIZES) X(WS_CONS_SCORES) X(WS_CONS_K) \
+    X(WS_PLAN_P) X(WS_PLAN_M) X(WS_PLAN_PI) X(WS_PLAN_PJ) X(WS_PLAN_VAL) X(WS_PLAN_IT) X(WS_PLAN_FL) X(WS_PLAN_Q) \
+    X(WS_PLAN_PLANS) X(WS_PLAN_SLAB) X(WS_PLAN_ROWMIN) X(WS_PLAN_KWS) X(WS_PLAN_ACC) X(WS_PLAN_GOFF) X(WS_PLAN_GIDX) \
+    X(WS_DM_S) X(WS_DM_V) X(WS_DM_VEC) X(WS_DM_Z) X(WS_DM_PSI) X(WS_DM_E) X(WS_DM_D) X(WS_DM_K) X(WS_DM_MAX) X(WS_DM_OUT) \
+    X(WS_TF_U) X(WS_TF_Y) X(WS_TF_OUT) X(WS_TF_COLS) \
+    X(WS_BOOT_U) X(WS_BOOT_OUT) X(WS_BOOT_IDX) X(WS_BOOT_Y) \
+    X(WS_CV_Y) X(WS_CV_IN) X(WS_CV_AUX) X(WS_CV_OUT) X(WS_CV_BMAX) X(WS_CV_CHAIN) X(WS_CV_Z) \
+    X(WS_GM_Y) X(WS_GM_AUX) X(WS_GM_PART) X(WS_GM_COUNT) X(WS_GM_OUT) \
+    X(WS_CSR_COUNTS) X(WS_CSR_TOTAL) X(WS_CSR_CODES) X(WS_CSR_COLS) X(WS_CSR_OUT) \
+    X(WS_GS_Y) X(WS_GS_AUX) X(WS_GS_PART) X(WS_GS_OUT) \
+    X(WS_PCA_V) X(WS_PCA_VEC) X(WS_PCA_Z) X(WS_PCA_PCS) X(WS_PCA_SCORES) X(WS_PCA_STATS) X(WS_PCA_COLS) X(WS_PCA_POS) \
+    X(WS_PCA_SIDX) X(WS_PCA_SVAL) X(WS_PCA_CSVAL) X(WS_PCA_Y) X(WS_PCA_S) X(WS_PCA_PARTW) \
+    X(WS_KNN_X) X(WS_KNN_UNIT) X(WS_KNN_FLAGS) X(WS_KNN_BEST_D) X(WS_KNN_BEST_I) X(WS_KNN_OUT_D) X(WS_KNN_OUT_I) X(WS_KNN_SM_IN) X(WS_KNN_SM_OUT) \
+    X(WS_LV_VAL0) X(WS_LV_VAL1) X(WS_LV_DEG0) X(WS_LV_DEG1) X(WS_LV_IDX0) X(WS_LV_IDX1) X(WS_LV_TOT) X(WS_LV_SUMS) X(WS_LV_INT) X(WS_LV_FLAG) X(WS_LV_ECOMM) \
+    X(WS_LV_NKEYS) X(WS_LV_EKEYS) X(WS_LV_CNT) X(WS_LD_INT) X(WS_LD_DBL) \
+    X(WS_SIL_X) X(WS_SIL_UNIT) X(WS_SIL_FLAGS) X(WS_SIL_SORTED) X(WS_SIL_ORDER) X(WS_SIL_OFFSETS) X(WS_SIL_OUT) \
+    X(WS_PT_X) X(WS_PT_FLAGS) X(WS_PT_Y) X(WS_PT_YT) X(WS_PT_S) X(WS_PT_CENTRE) X(WS_PT_STATE) X(WS_PT_ITERS) X(WS_PT_ENERGY) X(WS_PT_COUNTS) X(WS_PT_SUMS) \
+    X(WS_PT_PCOUNTS) X(WS_PT_PSUMS) X(WS_PT_PMSE) X(WS_PT_PART) X(WS_PT_OUT) \
+    X(WS_RS_Y) X(WS_RS_INT) X(WS_RS_LL) X(WS_RS_REC) X(WS_RS_OUT) \
+    X(WS_NB_Y) X(WS_NB_INT) X(WS_NB_SF) X(WS_NB_BAD) X(WS_NB_PRIOR) X(WS_NB_OUT) X(WS_NB_FIT_INT)
+// (by prefix: PREPASS pilot_ot_prepass.hip, COST _cost, CONS _consumers, PLAN _plans, DM _diffmap, TF _trajfit, BOOT _bootfit, CV _curves,
+//  GM _moments, CSR _csr, GS _group_sums, PCA _pca, KNN _knn, LV _louvain and LD the refinement of pilot_ot_leiden, SIL _silhouette_points,
+//  PT _principal_tree, RS _rank_sums, NB _nb_glm)
 enum WsSlot {
-    WS_PREPASS_X, WS_PREPASS,                                                   // pilot_ot_prepass.hip
-    WS_COST_X, WS_COST_C, WS_COST_AUX,                                          // pilot_ot_cost.hip
-    WS_CONS_E, WS_CONS_D, WS_CONS_MAX, WS_CONS_LABELS, WS_CONS_SIZES, WS_CONS_SCORES, WS_CONS_K,   // pilot_ot_consumers.hip
-    WS_PLAN_P, WS_PLAN_M, WS_PLAN_PI, WS_PLAN_PJ, WS_PLAN_VAL, WS_PLAN_IT, WS_PLAN_FL, WS_PLAN_Q,    // pilot_ot_plans.hip
-    WS_PLAN_PLANS, WS_PLAN_SLAB, WS_PLAN_ROWMIN, WS_PLAN_KWS, WS_PLAN_ACC, WS_PLAN_GOFF, WS_PLAN_GIDX,
-    WS_DM_S, WS_DM_V, WS_DM_VEC, WS_DM_Z, WS_DM_PSI, WS_DM_E, WS_DM_D, WS_DM_K, WS_DM_MAX, WS_DM_OUT,  // pilot_ot_diffmap.hip
-    WS_TF_U, WS_TF_Y, WS_TF_OUT, WS_TF_COLS,                                    // pilot_ot_trajfit.hip
-    WS_BOOT_U, WS_BOOT_OUT, WS_BOOT_IDX, WS_BOOT_Y,                             // pilot_ot_bootfit.hip
-    WS_CV_Y, WS_CV_IN, WS_CV_AUX, WS_CV_OUT, WS_CV_BMAX, WS_CV_CHAIN, WS_CV_Z,   // pilot_ot_curves.hip
-    WS_GM_Y, WS_GM_AUX, WS_GM_PART, WS_GM_COUNT, WS_GM_OUT,                      // pilot_ot_moments.hip
-    WS_CSR_COUNTS, WS_CSR_TOTAL, WS_CSR_CODES, WS_CSR_COLS, WS_CSR_OUT,          // pilot_ot_csr.hip
-    WS_GS_Y, WS_GS_AUX, WS_GS_PART, WS_GS_OUT,                                   // pilot_ot_group_sums.hip
-    WS_PCA_V, WS_PCA_VEC, WS_PCA_Z, WS_PCA_PCS, WS_PCA_SCORES, WS_PCA_STATS, WS_PCA_COLS, WS_PCA_POS,   // pilot_ot_pca.hip
-    WS_PCA_SIDX, WS_PCA_SVAL, WS_PCA_CSVAL, WS_PCA_Y, WS_PCA_S, WS_PCA_PARTW,
-    WS_KNN_X, WS_KNN_UNIT, WS_KNN_FLAGS, WS_KNN_BEST_D, WS_KNN_BEST_I, WS_KNN_OUT_D, WS_KNN_OUT_I, WS_KNN_SM_IN, WS_KNN_SM_OUT,   // pilot_ot_knn.hip
-    WS_LV_VAL0, WS_LV_VAL1, WS_LV_DEG0, WS_LV_DEG1, WS_LV_IDX0, WS_LV_IDX1, WS_LV_TOT, WS_LV_SUMS, WS_LV_INT, WS_LV_FLAG, WS_LV_ECOMM,   // pilot_ot_louvain.hip
-    WS_LV_NKEYS, WS_LV_EKEYS, WS_LV_CNT, WS_LD_INT, WS_LD_DBL,                   // (WS_LD_*: the refinement of pilot_ot_leiden)
-    WS_SIL_X, WS_SIL_UNIT, WS_SIL_FLAGS, WS_SIL_SORTED, WS_SIL_ORDER, WS_SIL_OFFSETS, WS_SIL_OUT,   // pilot_ot_silhouette_points.hip
-    WS_PT_X, WS_PT_FLAGS, WS_PT_Y, WS_PT_YT, WS_PT_S, WS_PT_CENTRE, WS_PT_STATE, WS_PT_ITERS, WS_PT_ENERGY, WS_PT_COUNTS, WS_PT_SUMS,   // pilot_ot_principal_tree.hip
-    WS_PT_PCOUNTS, WS_PT_PSUMS, WS_PT_PMSE, WS_PT_PART, WS_PT_OUT,
-    WS_RS_Y, WS_RS_INT, WS_RS_LL, WS_RS_REC, WS_RS_OUT,                          // pilot_ot_rank_sums.hip
-    WS_NB_Y, WS_NB_INT, WS_NB_SF, WS_NB_BAD, WS_NB_PRIOR, WS_NB_OUT, WS_NB_FIT_INT,   // pilot_ot_nb_glm.hip
+#define PILOT_WS_SLOT_ENUM(name) name,
+    PILOT_WS_SLOT_LIST(PILOT_WS_SLOT_ENUM)
+#undef PILOT_WS_SLOT_ENUM
     WS_SLOTS
 };
+// CONTRACT: a hand-out is an UNDEFINED buffer of `bytes` bytes.  Whatever an earlier hand-out of the slot held is gone (the pool may
+// have regrown it, and under the test switch PILOT_OT_WS_GUARD every hand-out is filled with 0xFF and followed by a canary), so a
+// caller writes every byte a kernel or a copy will read, addresses nothing past `bytes`, and keeps the pointer instead of asking
+// for the same slot again while it still needs the contents.  pilot_ot_ws_guard_report tells what the guard saw.
 hipError_t ws_buffer(WsSlot slot, size_t bytes, void **out);
 // n elements of T (at least one) from `slot`
 template <typename T> hipError_t ws(WsSlot slot, size_t n, T **out) {

@@ -122,31 +122,97 @@ PILOT_API int pilot_ot_stream_sync(void *stream) {
 namespace {
 // Temporaries of the host entry points come from a per-thread pool that only grows (hipMalloc / hipFree cost about a
 // millisecond a pair and hipFree synchronises the device: nine of them were most of a 22 ms medians call); released by
-// pilot_ot_shutdown().  One buffer per pilot::WsSlot.
+// pilot_ot_shutdown().  One buffer per pilot::WsSlot.  A hand-out is an undefined buffer (abi_common.hpp, ws_buffer): under the test
+// switch PILOT_OT_WS_GUARD it is poisoned and followed by a canary, so a kernel that reads what nobody wrote or touches the slack
+// shows (tests/test_gpu_ws_guard.py); with the switch unset get() makes the HIP calls it always made.
 struct WsPool {
     static constexpr int SLOTS = pilot::WS_SLOTS;
+    static constexpr size_t GUARD_SLACK = 256;            // least canary bytes behind a guarded request
+    static constexpr int POISON = 0xFF, CANARY = 0xA5;
     void *p[SLOTS] = {};
     size_t cap[SLOTS] = {};
     int device = -1;
+    // guard mode (test switch PILOT_OT_WS_GUARD): request of each slot's last guarded hand-out, the slots handed out under guard since
+    // the last reset, and the earliest canary damage found since then
+    size_t req[SLOTS] = {};
+    bool guarded[SLOTS] = {};
+    unsigned char seen[SLOTS] = {};
+    int bad_slot = -1;
+    long long bad_offset = 0, bad_request = 0;
+    bool selftest_done = false;
     void release() {
-        for (int i = 0; i < SLOTS; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr; cap[i] = 0; }
+        for (int i = 0; i < SLOTS; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr; cap[i] = 0; guarded[i] = false; }
         device = -1;
+    }
+    hipError_t grow(int slot, size_t bytes) {
+        if (p[slot]) (void)hipFree(p[slot]);
+        p[slot] = nullptr; cap[slot] = 0; guarded[slot] = false;
+        const size_t want = bytes + bytes / 4 + 256;
+        const hipError_t e = hipMalloc(&p[slot], want);
+        if (e == hipSuccess) cap[slot] = want;
+        return e;
+    }
+    // the canary [req, cap) of a guarded slot, read back; the device must be idle
+    hipError_t check_canary(int slot) {
+        if (!guarded[slot] || !p[slot]) return hipSuccess;
+        const size_t n = cap[slot] - req[slot];
+        std::vector<unsigned char> h(n);
+        const hipError_t e = hipMemcpy(h.data(), static_cast<unsigned char *>(p[slot]) + req[slot], n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        for (size_t i = 0; i < n && bad_slot < 0; ++i)
+            if (h[i] != (unsigned char)CANARY) { bad_slot = slot; bad_offset = (long long)i; bad_request = (long long)req[slot]; }
+        return hipSuccess;
+    }
+    hipError_t get_guarded(int slot, size_t bytes, void **out, bool selftest) {
+        hipError_t e = hipDeviceSynchronize();       // (entry points launch on streams that do not order against the null stream)
+        if (e == hipSuccess) e = check_canary(slot);
+        if (e == hipSuccess && bytes + GUARD_SLACK > cap[slot]) e = grow(slot, bytes);
+        unsigned char *b = static_cast<unsigned char *>(p[slot]);
+        if (e == hipSuccess) e = hipMemset(b, POISON, bytes);
+        if (e == hipSuccess) e = hipMemset(b + bytes, CANARY, cap[slot] - bytes);
+        if (e == hipSuccess && selftest && !selftest_done) {       // the control: one damaged byte inside the slot's own slack
+            selftest_done = true;
+            e = hipMemset(b + bytes + 7, 0, 1);
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) return e;
+        req[slot] = bytes; guarded[slot] = true; seen[slot] = 1;
+        *out = b;
+        return hipSuccess;
     }
     hipError_t get(int slot, size_t bytes, void **out) {
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
         if (dev != device) { release(); device = dev; }
+        if (const char *g = pilot::test_switch("PILOT_OT_WS_GUARD")) {
+            const bool selftest = !strcmp(g, "selftest");
+            if (selftest || !strcmp(g, "1")) return get_guarded(slot, bytes, out, selftest);
+        }
+        guarded[slot] = false;                       // (a plain hand-out may use the bytes a canary stood in)
         if (bytes > cap[slot]) {
-            if (p[slot]) (void)hipFree(p[slot]);
-            p[slot] = nullptr; cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            e = hipMalloc(&p[slot], want);
+            e = grow(slot, bytes);
             if (e != hipSuccess) return e;
-            cap[slot] = want;
         }
         *out = p[slot];
         return hipSuccess;
+    }
+    int report(unsigned char *seen_out, int *slot, long long *offset, long long *request, int reset) {
+        bool any = false;
+        for (int i = 0; i < SLOTS; ++i) any = any || (guarded[i] && p[i]);
+        if (any) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (int i = 0; i < SLOTS; ++i) HIP_TRY(check_canary(i));
+        }
+        if (seen_out) memcpy(seen_out, seen, SLOTS);
+        if (slot) *slot = bad_slot;
+        if (offset) *offset = bad_slot < 0 ? 0 : bad_offset;
+        if (request) *request = bad_slot < 0 ? 0 : bad_request;
+        if (reset) {                                 // (every canary was just judged: a reported damage is not found again at the next hand-out)
+            for (int i = 0; i < SLOTS; ++i) { seen[i] = 0; guarded[i] = false; }
+            bad_slot = -1; bad_offset = bad_request = 0; selftest_done = false;
+        }
+        return PILOT_OT_OK;
     }
 };
 // Per-thread caches (host-entry workspace + pre-pass pool) live in a process-wide registry, not in thread_local objects:
@@ -407,6 +473,21 @@ int host_fetch(const Fetch *f, int n) {
     return PILOT_OT_OK;
 }
 }  // namespace pilot
+
+namespace {
+const char *const g_ws_slot_names[] = {
+#define PILOT_WS_SLOT_NAME(name) #name,
+    PILOT_WS_SLOT_LIST(PILOT_WS_SLOT_NAME)
+#undef PILOT_WS_SLOT_NAME
+};
+static_assert(sizeof(g_ws_slot_names) / sizeof(g_ws_slot_names[0]) == pilot::WS_SLOTS, "one name per slot");
+}  // namespace
+
+PILOT_API int pilot_ot_ws_slot_count(void) { return pilot::WS_SLOTS; }
+PILOT_API const char *pilot_ot_ws_slot_name(int slot) { return slot >= 0 && slot < pilot::WS_SLOTS ? g_ws_slot_names[slot] : nullptr; }
+PILOT_API int pilot_ot_ws_guard_report(unsigned char *seen, int *bad_slot, long long *bad_offset, long long *bad_request, int reset) {
+    return tctx().ws.report(seen, bad_slot, bad_offset, bad_request, reset);
+}
 
 PILOT_API int pilot_ot_shutdown(void) {
     {

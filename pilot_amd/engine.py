@@ -37,6 +37,46 @@ class _Closing:
             pass
 
 
+def ws_slot_names():
+    """names of the workspace pool's slots, in slot order (no device needed)"""
+    L = _lib.load()
+    return [L.pilot_ot_ws_slot_name(i).decode() for i in range(L.pilot_ot_ws_slot_count())]
+
+
+def ws_guard_report(reset=False):
+    """``(seen names, damage)`` of the calling thread's workspace guard: the slots handed out under guard since the last reset and
+    ``None`` or ``(slot name, first damaged offset past the request, request bytes)``"""
+    L = _lib.load()
+    names = ws_slot_names()
+    seen = (ctypes.c_ubyte * len(names))()
+    slot, off, req = ctypes.c_int(-1), ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.check(L.pilot_ot_ws_guard_report(seen, ctypes.byref(slot), ctypes.byref(off), ctypes.byref(req), int(bool(reset))))
+    damage = None if slot.value < 0 else (names[slot.value], off.value, req.value)
+    return {n for n, s in zip(names, seen) if s}, damage
+
+
+class ws_guard:
+    """TEST HOOK: run the body with the workspace guard on (``PILOT_OT_WS_GUARD``, include/pilot_ot.h).  Entering resets the calling
+    thread's report and sets the switch; leaving checks every canary, stores ``(seen names, damage or None)`` in ``result`` (also
+    ``seen`` and ``damage``), resets the report and clears the switch.  ``mode="selftest"`` damages one canary byte on purpose."""
+
+    def __init__(self, mode="1"):
+        self.mode, self.result, self.seen, self.damage = mode, None, None, None
+
+    def __enter__(self):
+        ws_guard_report(reset=True)
+        _lib.test_switch("PILOT_OT_WS_GUARD", self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        try:
+            self.result = ws_guard_report(reset=True)
+            self.seen, self.damage = self.result
+        finally:
+            _lib.test_switch("PILOT_OT_WS_GUARD", None)
+        return False
+
+
 def _square(A, name):
     if A.ndim != 2 or A.shape[0] != A.shape[1]:
         raise ValueError("%s must be square, got %s" % (name, A.shape))

@@ -646,6 +646,39 @@ int pilot_ot_nb_shrink(const void *Y, int Y_is_device, int dtype, long long m, i
                        double intercept_scale, double *beta0, double *beta1, double *objective, double *info, int *flags, int *n_at_bound,
                        long long *bad_row, int *bad_col);
 
+/* pilot_ot_nb_dispersions_blind, pilot_ot_nb_rlog (K24): the two device steps of `rlog(dds, blind = TRUE)`, which pilotpy's
+ * compute_pseudobulk_PCA returns (plot/pseudobulk_DE_analysis.py:161-207; Love, Huber, Anders 2014, "regularized logarithm").
+ * THIS LIBRARY'S STATEMENT, unpinned (restated in tests/nb_rlog_restatement.py).  Y, size_factors, dtype, ld and
+ * the same-bits statement as above; there are no groups: blind means the design `~ 1`.
+ *
+ * pilot_ot_nb_dispersions_blind: pilot_ot_nb_dispersions with the ONE group of all m >= 2 samples (which that call refuses) and no
+ * prior: mu_j = max(s_j mean_i(c_i / s_i), minmu), the same search.  base_mean (nullable, n_genes): mean_j(c_j / s_j).
+ *
+ * pilot_ot_nb_rlog: per gene, with alpha = dispersion[gene] (host; the trend value; NaN leaves the gene out: NaN in its column and
+ * intercept), lambda = ln2^2 / prior_var, lambda0 = 1e-6 ln2^2 and eta_j = b0 + b_j + log s_j, the maximiser over (b0, b_1 .. b_m) of
+ *     P = sum_j [c_j eta_j - (c_j + 1/alpha) log1p(alpha e^{eta_j})] - lambda/2 sum_j b_j^2 - lambda0/2 b0^2
+ * P is strictly concave, so the result does not depend on the path (DESeq2's IRLS stops at a deviance change of 1e-4 and clamps mu
+ * at 0.5 inside its loop; this returns the optimum).  The path: from b0 = log mean_j(c_j / s_j), b = 0, Newton steps on the
+ * arrowhead system -- mu = e^eta, r = (c - mu) / (1 + alpha mu), w = mu (1 + alpha c) / (1 + alpha mu)^2, g = r - lambda b,
+ * h = w + lambda, d0 = (sum r - lambda0 b0 - sum w g / h) / (sum w + lambda0 - sum w^2 / h), d_j = (g_j - w_j d0) / h_j -- of
+ * length t, halved from 1 at most 20 times until P does not fall (a non-finite value counts as a fall; the change of P is summed
+ * term by term, not taken as a difference of two sums; a step within 1e-10 at t = 1 is taken whole); stopped once max(|t d0|, max_j |t d_j|) <= 1e-10, or after 100 iterations
+ * with PILOT_OT_NB_NOT_CONVERGED.  Every sum is a per-lane partial in sample order (lane l: samples l, l + 64, ...) closed by one
+ * fixed butterfly: a gene gives the same bits alone and in any batch.
+ * Out: out, m x n_genes float64 with leading dimension ld_out >= n_genes, on the host or in HBM (out_is_device):
+ * (b0 + b_j) / ln2; a gene of zeros gives 0 in every sample and a NaN intercept.  Host: intercept (n_genes) = b0 / ln2, steps
+ * (iterations), flags (PILOT_OT_NB_NOT_CONVERGED); *n_not_converged (nullable).
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n_genes < 1, dtype, ld < n_genes, ld_out < n_genes, m < 2, a size factor
+ * not positive and finite, a prior_var not positive and finite, a dispersion outside [minDisp, maxDisp]; after the check pass a
+ * negative or non-finite count (*bad_row / *bad_col as pilot_ot_nb_dispersions).  PILOT_OT_ENOTSUP: m > INT_MAX;
+ * m > pilot_ot_nb_glm_max_samples() (a gene's counts, log size factors and coefficients are staged in LDS, 24 m bytes). */
+int pilot_ot_nb_dispersions_blind(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld,
+                                  const double *size_factors, double *log_disp, double *objective, double *base_mean, long long *bad_row,
+                                  int *bad_col);
+int pilot_ot_nb_rlog(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *size_factors,
+                     const double *dispersion, double prior_var, void *out, int out_is_device, long long ld_out, double *intercept,
+                     int *steps, int *flags, int *n_not_converged, long long *bad_row, int *bad_col);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

@@ -1,5 +1,5 @@
 // C ABI of the negative-binomial GLM for a one-factor design (include/pilot_ot.h, section "negative-binomial GLM"; kernels:
-// nb_glm_kernels.hpp, nb_shrink_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
+// nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
 // codes, size factors, dispersions and the results are host arrays.  The host orders the samples by group once per call.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 
 #include "abi_common.hpp"
 #include "nb_glm_kernels.hpp"
+#include "nb_rlog_kernel.hpp"
 #include "nb_shrink_kernel.hpp"
 
 namespace {
@@ -157,6 +158,58 @@ int shrink(const void *y, long long ld, int m, int n_genes, const DevDesign &dd,
     return PILOT_OT_OK;
 }
 
+// every check of (m, size_factors) of the calls without groups.  No HIP call.
+int check_samples(long long m, const double *sf) {
+    if (m < 2) return fail(PILOT_OT_EINVAL, "m=%lld samples: at least 2", m);
+    if (m > INT_MAX) return fail(PILOT_OT_ENOTSUP, "m=%lld samples need more than 32-bit indices", m);
+    for (long long i = 0; i < m; ++i)
+        if (!(std::isfinite(sf[i]) && sf[i] > 0.0)) return fail(PILOT_OT_EINVAL, "size_factors[%lld]=%g must be positive and finite", i, sf[i]);
+    return PILOT_OT_OK;
+}
+
+// the design `~ 1` of m samples (blind): one group, the samples in their own order
+int make_blind_design(long long m, const double *sf, Design &d) {
+    if (int rc = check_samples(m, sf)) return rc;
+    d.order.resize((size_t)m);
+    for (long long i = 0; i < m; ++i) d.order[(size_t)i] = (int)i;
+    d.gof.assign((size_t)m, 0);
+    d.gstart = {0, (int)m};
+    d.ss.assign(sf, sf + m);
+    return PILOT_OT_OK;
+}
+
+template <typename T>
+int rlog(const void *y, long long ld, int m, int n_genes, const double *sf, const double *dispersion, double prior_var, void *out,
+         int out_is_device, long long ld_out, double *intercept, int *steps, int *flags, long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    const size_t G = (size_t)n_genes, M = (size_t)m;
+    std::vector<double> s(2 * M);                            // the size factors, then their logarithms
+    for (size_t j = 0; j < M; ++j) { s[j] = sf[j]; s[M + j] = std::log(sf[j]); }
+    double *d_sf, *d_disp, *d_dbl;                           // d_dbl: intercept | the packed m x G result when `out` is on the host
+    int *d_int;                                              // steps, flags
+    HIP_TRY(pilot::ws(pilot::WS_NB_SF, 2 * M, &d_sf));
+    HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G, &d_disp));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, G + (out_is_device ? 0 : M * G), &d_dbl));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 2 * G, &d_int));
+    HIP_TRY(hipMemcpy(d_sf, s.data(), sizeof(double) * 2 * M, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_disp, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
+    double *d_res = out_is_device ? static_cast<double *>(out) : d_dbl + G;
+    const long long ld_res = out_is_device ? ld_out : (long long)n_genes;
+    const double ln2 = pilot::NB_RLOG_LN2, lambda = ln2 * ln2 / prior_var, lambda0 = pilot::NB_RLOG_INTERCEPT_RIDGE * ln2 * ln2;
+    const size_t lds = sizeof(double) * 3 * M;
+    auto kern = pilot::nb_rlog_kernel<T>;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_genes), dim3(64), lds, nullptr, static_cast<const T *>(y), ld, m, d_sf, d_disp, lambda, lambda0,
+                       d_res, ld_res, d_dbl, d_int, d_int + G);
+    HIP_TRY(hipGetLastError());
+    if (!out_is_device)
+        HIP_TRY(hipMemcpy2D(out, sizeof(double) * (size_t)ld_out, d_res, sizeof(double) * G, sizeof(double) * G, M, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(intercept, d_dbl, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(steps, d_int, sizeof(int) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags, d_int + G, sizeof(int) * G, hipMemcpyDeviceToHost));
+    return PILOT_OT_OK;
+}
+
 // a dispersion is NaN (the gene is left out) or within [minDisp, maxDisp]
 int check_dispersions(const double *dispersion, int n_genes, long long m) {
     const double max_disp = pilot::nb_max_disp(m);
@@ -199,6 +252,26 @@ PILOT_API int pilot_ot_nb_dispersions(const void *Y, int Y_is_device, int dtype,
                                            bad_row, bad_col)
                       : dispersions<double>(y, y_ld, (int)m, n_genes, n_groups, dd, log_prior_mean, prior_var, log_disp, objective, fitted_mean,
                                             bad_row, bad_col);
+}
+
+PILOT_API int pilot_ot_nb_dispersions_blind(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld,
+                                            const double *size_factors, double *log_disp, double *objective, double *base_mean,
+                                            long long *bad_row, int *bad_col) {
+    if (bad_row) *bad_row = -1;
+    if (bad_col) *bad_col = -1;
+    if (!Y || !size_factors || !log_disp || !objective) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
+    Design d;
+    if (int rc = make_blind_design(m, size_factors, d)) return rc;
+    if (m > pilot::NB_MAX_SAMPLES)
+        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts and fitted means are staged in LDS, at most %d", m, pilot::NB_MAX_SAMPLES);
+    const void *y;
+    long long y_ld;
+    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
+    DevDesign dd;
+    if (int rc = upload_design(d, dd)) return rc;
+    return dtype == 0 ? dispersions<float>(y, y_ld, (int)m, n_genes, 1, dd, nullptr, 0.0, log_disp, objective, base_mean, bad_row, bad_col)
+                      : dispersions<double>(y, y_ld, (int)m, n_genes, 1, dd, nullptr, 0.0, log_disp, objective, base_mean, bad_row, bad_col);
 }
 
 PILOT_API int pilot_ot_nb_group_fits(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
@@ -259,5 +332,34 @@ PILOT_API int pilot_ot_nb_shrink(const void *Y, int Y_is_device, int dtype, long
     int at_bound = 0;
     for (int j = 0; j < n_genes; ++j) at_bound += (flags[j] & pilot::NB_FLAG_AT_BOUND) != 0;
     if (n_at_bound) *n_at_bound = at_bound;
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_nb_rlog(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *size_factors,
+                               const double *dispersion, double prior_var, void *out, int out_is_device, long long ld_out,
+                               double *intercept, int *steps, int *flags, int *n_not_converged, long long *bad_row, int *bad_col) {
+    if (bad_row) *bad_row = -1;
+    if (bad_col) *bad_col = -1;
+    if (n_not_converged) *n_not_converged = 0;
+    if (!Y || !size_factors || !dispersion || !out || !intercept || !steps || !flags) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
+    if (ld_out < n_genes) return fail(PILOT_OT_EINVAL, "ld_out=%lld is smaller than n_genes=%d", ld_out, n_genes);
+    if (int rc = check_samples(m, size_factors)) return rc;
+    if (!(std::isfinite(prior_var) && prior_var > 0.0)) return fail(PILOT_OT_EINVAL, "prior_var=%g must be positive and finite", prior_var);
+    if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
+    if (m > pilot::NB_MAX_SAMPLES)
+        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts, log size factors and coefficients are staged in LDS, at most %d", m,
+                    pilot::NB_MAX_SAMPLES);
+    const void *y;
+    long long y_ld;
+    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
+    if (int rc = dtype == 0 ? rlog<float>(y, y_ld, (int)m, n_genes, size_factors, dispersion, prior_var, out, out_is_device, ld_out, intercept,
+                                          steps, flags, bad_row, bad_col)
+                            : rlog<double>(y, y_ld, (int)m, n_genes, size_factors, dispersion, prior_var, out, out_is_device, ld_out, intercept,
+                                           steps, flags, bad_row, bad_col))
+        return rc;
+    int bad = 0;
+    for (int j = 0; j < n_genes; ++j) bad += (flags[j] & pilot::NB_FLAG_NOT_CONVERGED) != 0;
+    if (n_not_converged) *n_not_converged = bad;
     return PILOT_OT_OK;
 }

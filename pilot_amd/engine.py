@@ -1557,6 +1557,120 @@ def nb_posterior_sd(beta1, w0, w1, prior_scale, intercept_scale=NB_INTERCEPT_SCA
         return np.where(det > 0, np.sqrt(h00 / det), np.nan)
 
 
+# ---- regularised log transform (K24; DESeq2's rlog(blind = TRUE) of pilotpy's compute_pseudobulk_PCA) ---------------------------
+def _nb_blind_args(m, n_genes, size_factors):
+    """the samples of the two calls without groups checked on the host: the size factors as float64"""
+    if n_genes < 1:
+        raise ValueError("counts has no columns")
+    if m < 2:
+        raise ValueError("counts has %d rows: at least 2 samples" % m)
+    sf = np.ascontiguousarray(size_factors, dtype=np.float64)
+    if sf.shape != (m,):
+        raise ValueError("size_factors has shape %s for %d samples" % (sf.shape, m))
+    if not (np.isfinite(sf).all() and (sf > 0).all()):
+        raise ValueError("size_factors must be positive and finite")
+    return sf
+
+
+def nb_dispersions_blind(counts, size_factors, return_info=False):
+    """K24: :func:`nb_dispersions` for the design ``~ 1`` (DESeq2's ``blind = TRUE``): ONE group of all the samples, which that call
+    refuses, and no prior -- ``mu_j = max(s_j * mean_i(c_i / s_i), 0.5)`` and the same six rounds of the 64-point grid on the
+    Cox-Reid adjusted profile likelihood.  ``counts`` and ``size_factors`` as there, at least 2 samples.  Returns the float64 log
+    dispersions (NaN for a gene of zeros); with ``return_info`` also a dict: ``objective`` and ``base_mean`` (the mean of
+    ``c / s`` over the samples, as the device summed it).  Errors as :func:`nb_dispersions`."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
+    limit = nb_glm_limits()
+    if Y.rows > limit:
+        raise NotImplementedError("nb_dispersions_blind: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    x, objective, base_mean = np.empty(Y.cols), np.empty(Y.cols), np.empty(Y.cols)
+    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_int(-1)
+    try:
+        _lib.check(_lib.load().pilot_ot_nb_dispersions_blind(
+            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(x), _lib.dptr(objective),
+            _lib.dptr(base_mean), ctypes.byref(bad_row), ctypes.byref(bad_col)))
+    except ValueError as err:
+        raise _nb_bad_count(err, bad_row, bad_col)
+    return (x, {"objective": objective, "base_mean": base_mean}) if return_info else x
+
+
+NB_RLOG_UPPER_QUANTILE = 0.05
+
+
+def nb_rlog_prior_var(counts, size_factors, base_mean, disp_fit):
+    """The prior variance of :func:`nb_rlog`'s sample coefficients on the log2 scale (step 2 of DESIGN.md K24: DESeq2's
+    ``matchWeightedUpperQuantileForVariance`` restated); numpy and scipy, one sort of samples x genes values on the host.
+    ``counts``: a host samples x genes array (c = rint); ``base_mean`` and ``disp_fit`` one per gene.  Over the genes with
+    ``base_mean > 0`` and all samples: ``x = |log2(c / s + 0.5) - log2(base_mean + 0.5)|`` with weight
+    ``1 / (1 / base_mean + disp_fit)``; the weights of equal x are summed, ``cum`` is their running sum in ascending x and W its
+    total; ``o = 1 + (W - 1) 0.95``, ``low = max(floor(o), 1)``, ``high = min(low + 1, W)``, ``f = o mod 1``; q(t) is the x at the
+    first position with ``cum >= t`` (the last x beyond the end); ``Q = (1 - f) q(low) + f q(high)`` (Hmisc's ``wtd.quantile`` with
+    ``normwt = FALSE``); returns ``(Q / norm.ppf(0.975))^2``.  No gene with a positive mean and a finite trend: ValueError."""
+    from scipy import special
+    c = np.rint(np.asarray(counts, dtype=np.float64))
+    if c.ndim != 2:
+        raise ValueError("counts: a samples x genes host array, got shape %s" % (c.shape,))
+    sf = _nb_blind_args(c.shape[0], c.shape[1], size_factors)
+    mean, fit = np.asarray(base_mean, dtype=np.float64), np.asarray(disp_fit, dtype=np.float64)
+    if mean.shape != (c.shape[1],) or fit.shape != mean.shape:
+        raise ValueError("base_mean %s and disp_fit %s: one of each for %d genes" % (mean.shape, fit.shape, c.shape[1]))
+    with np.errstate(invalid="ignore"):
+        use = (mean > 0) & np.isfinite(fit)
+    if not use.any():
+        raise ValueError("nb_rlog_prior_var: no gene has a positive mean and a finite dispersion trend")
+    x = np.abs(np.log2(c[:, use] / sf[:, None] + 0.5) - np.log2(mean[use] + 0.5)[None])
+    weight = np.broadcast_to((1.0 / (1.0 / mean[use] + fit[use]))[None], x.shape)
+    values, inverse = np.unique(x.ravel(), return_inverse=True)
+    cum = np.cumsum(np.bincount(np.ravel(inverse), weights=weight.ravel(), minlength=values.size))
+    W = cum[-1]
+    o = 1.0 + (W - 1.0) * (1.0 - NB_RLOG_UPPER_QUANTILE)
+    low = max(np.floor(o), 1.0)
+    high = min(low + 1.0, W)
+    f = o % 1.0
+    q = lambda t: values[min(int(np.searchsorted(cum, t, side="left")), values.size - 1)]
+    Q = (1.0 - f) * q(low) + f * q(high)
+    return float((Q / special.ndtri(1.0 - NB_RLOG_UPPER_QUANTILE / 2.0)) ** 2)
+
+
+def nb_rlog(counts, size_factors, dispersion, prior_var, on_device=False, return_info=False):
+    """K24: the regularised log transform of ``counts`` (samples x genes, as :func:`nb_dispersions` takes them) on the log2 scale
+    (include/pilot_ot.h, pilot_ot_nb_rlog; the rule is this library's statement, unpinned).  Per gene the
+    negative-binomial GLM ``log mu_j = beta0 + beta_j + log s_j`` with one coefficient a sample at the gene's ``dispersion`` (the
+    trend value, in [1e-8, max(10, m)]; NaN leaves the gene out), a normal prior of variance ``prior_var`` (log2 scale,
+    :func:`nb_rlog_prior_var`) on the sample coefficients and an all but flat one on the intercept; the posterior mode is the one
+    maximiser of a strictly concave function, found by damped Newton steps (one wave per gene, the samples along the lanes) to
+    1e-10.  Returns ``(beta0 + beta_j) / ln 2`` as a samples x genes float64 array, or with ``on_device`` as a
+    :class:`DeviceMatrix` that :func:`pca` takes without a trip through the host.  A gene of zeros gives 0 in every sample.  With
+    ``return_info`` also a dict: ``intercept`` (``beta0 / ln 2``; NaN for a gene of zeros), ``steps`` (Newton iterations),
+    ``flags`` (``_lib.NB_NOT_CONVERGED`` after 100) and ``n_not_converged``.  The same bits from a repeated call, from float32 and
+    float64 storage, from host and device matrices, and for a gene alone or in any batch.  Errors as :func:`nb_dispersions`."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
+    alpha = np.ascontiguousarray(dispersion, dtype=np.float64)
+    if alpha.shape != (Y.cols,):
+        raise ValueError("dispersion has shape %s for %d genes" % (alpha.shape, Y.cols))
+    given = alpha[~np.isnan(alpha)]
+    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(Y.rows)):
+        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(Y.rows)))
+    if isinstance(prior_var, (str, bytes, bool)) or not np.isscalar(prior_var) or not (np.isfinite(prior_var) and prior_var > 0):
+        raise ValueError("prior_var=%r must be positive and finite" % (prior_var,))
+    limit = nb_glm_limits()
+    if Y.rows > limit:
+        raise NotImplementedError("nb_rlog: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    out = _device_result(Y.rows, Y.cols) if on_device else np.empty((Y.rows, Y.cols), dtype=np.float64)
+    intercept = np.empty(Y.cols)
+    steps, flags = np.empty(Y.cols, dtype=np.int32), np.empty(Y.cols, dtype=np.int32)
+    bad, bad_row, bad_col = ctypes.c_int(0), ctypes.c_longlong(-1), ctypes.c_int(-1)
+    try:
+        _lib.check(_lib.load().pilot_ot_nb_rlog(
+            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(alpha), float(prior_var),
+            ctypes.c_void_p(out.ptr if on_device else out.ctypes.data), int(bool(on_device)), Y.cols, _lib.dptr(intercept),
+            _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad), ctypes.byref(bad_row), ctypes.byref(bad_col)))
+    except ValueError as err:
+        raise _nb_bad_count(err, bad_row, bad_col)
+    return (out, {"intercept": intercept, "steps": steps, "flags": flags, "n_not_converged": bad.value}) if return_info else out
+
+
 # ---- principal components (K15; scanpy's scale + tl.pca(svd_solver='arpack') of pilotpy's extract_annot_expression) ----------
 PCA_MAX_COMPS = 64
 

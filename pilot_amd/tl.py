@@ -2494,7 +2494,7 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
 
     Deviations from the reference's call, which is unpinned here (no DESeq2 or apeglm where this library is tested): the
     shrinkage is opt-in (``shrink="apeglm"``) and its mode comes from a global grid search, not apeglm's local optimiser; no
-    s-values; no ``rlog``; no Cook's-distance outlier handling; no independent filtering, ``padj`` is plain BH; no beta
+    s-values; ``rlog`` is :func:`compute_pseudobulk_PCA`'s; no Cook's-distance outlier handling; no independent filtering, ``padj`` is plain BH; no beta
     ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the formula where DESeq2 simulates; the
     reference returns R's list (the frame at index 1), this returns the frame.  Fewer than three selected samples, or a group
     without samples: ValueError before any device work."""
@@ -2523,13 +2523,99 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     return lfc_shrink(counts, codes, out, prior_scale) if shrink else out
 
 
+# ---- regularised log transform and its PCA: rlog(dds, blind = TRUE), plotPCA_subgroups (plot/pseudobulk_DE_analysis.py:161-233) ---
+def rlog(cluster_counts, size_factors=None, fit_type="parametric", prior_var=None):
+    """DESeq2's ``rlog(dds, blind = TRUE)`` of a samples x genes count frame without R, on the device (DESeq2 is not
+    installed where this library is built and tested, so the rule is this library's statement, UNPINNED).  With c = rint(counts)
+    and ``size_factors`` (default :func:`deseq2_size_factors`): the gene-wise dispersions of the design ``~ 1``
+    (``engine.nb_dispersions_blind``), their trend over ``baseMean = mean_j(c_j / s_j)`` (``engine.nb_trend`` with ``fit_type``),
+    clipped to [1e-8, max(10, m)] -- rlog reads the TREND value for every gene, there is no MAP step --, the prior variance of the
+    sample coefficients (``engine.nb_rlog_prior_var``; ``prior_var`` skips it) and per gene the ridge-penalised negative-binomial
+    GLM with one coefficient a sample (``engine.nb_rlog``).  Returns a float64 frame shaped and labelled like ``cluster_counts``:
+    ``log2`` of the fitted normalised count of every sample; a gene of zeros is 0 everywhere.  ``attrs``: ``size_factors``,
+    ``dispFit`` (what the fit used), ``prior_var``, ``intercept`` (log2; NaN for a gene of zeros), ``n_not_converged``.
+
+    Deviations from DESeq2: the fit is the optimum of the penalised likelihood (to 1e-10 in the coefficients), where DESeq2's IRLS
+    stops at a deviance change of 1e-4 and clamps mu at 0.5 inside its loop; the dispersions come from the global grid search of
+    :func:`deseq2_dispersions`; a parametric trend that does not fit raises ValueError where DESeq2 falls back to a local
+    regression (``fit_type="mean"``); the weighted-quantile rule of the prior variance is restated from memory of Hmisc."""
+    c, genes = _nb_counts(cluster_counts, "rlog")
+    m = c.shape[0]
+    if m < 2:
+        raise ValueError("rlog: %d samples, at least 2" % m)
+    if c.shape[1] < 1:
+        raise ValueError("rlog: the table has no genes")
+    if fit_type not in ("parametric", "mean"):
+        raise ValueError("rlog: fit_type=%r must be 'parametric' or 'mean'" % (fit_type,))
+    if prior_var is not None and not (isinstance(prior_var, (int, float, np.integer, np.floating)) and not isinstance(prior_var, bool)
+                                      and np.isfinite(prior_var) and prior_var > 0):
+        raise ValueError("rlog: prior_var=%r must be positive and finite (None: estimated)" % (prior_var,))
+    sf = _nb_size_factors(cluster_counts, size_factors, m)
+    if not (np.isfinite(sf).all() and (sf > 0).all()):
+        raise ValueError("rlog: size_factors must be positive and finite")
+    x = engine.nb_dispersions_blind(c, sf)
+    base_mean = (np.rint(c.astype(np.float64)) / sf[:, None]).mean(axis=0)
+    fit, _ = engine.nb_trend(base_mean, engine.nb_clip(np.exp(x), m), fit_type)
+    fit = engine.nb_clip(fit, m)
+    pv = engine.nb_rlog_prior_var(c, sf, base_mean, fit) if prior_var is None else float(prior_var)
+    values, info = engine.nb_rlog(c, sf, fit, pv, return_info=True)
+    out = pd.DataFrame(values, index=getattr(cluster_counts, "index", None), columns=genes)
+    out.attrs.update(size_factors=pd.Series(sf, index=out.index), dispFit=pd.Series(fit, index=genes), prior_var=pv,
+                     intercept=pd.Series(info["intercept"], index=genes), n_not_converged=info["n_not_converged"])
+    return out
+
+
+def compute_pseudobulk_PCA(cluster_counts=None, cluster_metadata=None):
+    """The reference's ``compute_pseudobulk_PCA`` (plot/pseudobulk_DE_analysis.py:161-207) without R: ``as.data.frame(assay(rlog(dds,
+    blind = TRUE)))`` of :func:`pseudobulk_inputs`' pair, a genes x samples frame (:func:`rlog`, transposed; its ``attrs`` are
+    kept).  ``cluster_metadata`` is only aligned -- its index must be the samples of ``cluster_counts``, as
+    ``DESeqDataSetFromMatrix`` demands -- because ``blind`` ignores the design.  The deviations of :func:`rlog` apply."""
+    if cluster_metadata is not None and not pd.Index(cluster_metadata.index).equals(pd.Index(cluster_counts.index)):
+        raise ValueError("compute_pseudobulk_PCA: the rows of cluster_metadata are not the samples of cluster_counts, in their order")
+    rld = rlog(cluster_counts)
+    out = rld.T
+    out.attrs.update(rld.attrs)
+    return out
+
+
+def pseudobulk_pca(rld, variance_threshold=0.2, n_components=2):
+    """The numbers of the reference's ``plotPCA_subgroups`` (plot/pseudobulk_DE_analysis.py:209-218): of a samples x genes table
+    ``rld`` (:func:`rlog`'s frame, or ``compute_pseudobulk_PCA(...).T`` as the reference passes it; any other samples x genes table
+    is taken as it is, nothing is transformed) keep the genes whose variance over the samples (ddof 0, scikit-learn's
+    ``VarianceThreshold``) exceeds ``variance_threshold``, then the first ``n_components`` principal components of the centred
+    samples x kept-genes matrix on the device (``engine.pca(scale=False)``), with scikit-learn 1.7's signs: in every component
+    the loading of largest magnitude is positive.  Returns ``(scores, variance_ratio)``: a frame samples x ``PC1 ..`` and the
+    explained variance ratios.  Fewer than ``n_components + 1`` genes pass, or a bad argument: ValueError before any device work.
+    No plot."""
+    X = np.asarray(rld, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("pseudobulk_pca: a samples x genes table, got shape %s" % (X.shape,))
+    if isinstance(n_components, bool) or int(n_components) != n_components or n_components < 1:
+        raise ValueError("pseudobulk_pca: n_components=%r must be a positive integer" % (n_components,))
+    if not isinstance(variance_threshold, (int, float, np.integer, np.floating)) or isinstance(variance_threshold, bool) \
+            or not variance_threshold >= 0:
+        raise ValueError("pseudobulk_pca: variance_threshold=%r must be a number >= 0" % (variance_threshold,))
+    if not np.isfinite(X).all():
+        raise ValueError("pseudobulk_pca: the table holds a non-finite value")
+    kept = np.flatnonzero(X.var(axis=0) > variance_threshold)
+    if kept.size < n_components + 1:
+        raise ValueError("pseudobulk_pca: %d genes have a variance above %g, at least n_components + 1 = %d are needed"
+                         % (kept.size, variance_threshold, n_components + 1))
+    scores, pcs, _, ratio = engine.pca(np.ascontiguousarray(X), n_comps=int(n_components), scale=False, cols=kept.astype(np.int32))
+    sign = np.sign(pcs[np.abs(pcs).argmax(axis=0), np.arange(pcs.shape[1])])
+    sign[sign == 0] = 1.0
+    names = ["PC%d" % (i + 1) for i in range(scores.shape[1])]
+    return pd.DataFrame(scores * sign[None], index=getattr(rld, "index", None), columns=names), ratio
+
+
 def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
                       remove_samples=(), shrink=None):
     """The numbers of the reference's ``get_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:506-666) in one process with no R:
     :func:`pseudobulk_inputs` of ``cell_type``, then :func:`compute_pseudobulk_DE` for every pair of
     ``itertools.combinations(np.unique(proportion_df[cluster_col]), 2)``.  Returns ``{"<g2>vs<g1>": frame}`` (the names of the
     reference's ``_DE.csv`` files; the fold change is g2 over g1).  ``shrink`` is :func:`compute_pseudobulk_DE`'s (``"apeglm"``:
-    the shrunken fold changes the reference writes).  No plots, no files, no rlog PCA, no enrichment; the deviations of
+    the shrunken fold changes the reference writes).  No plots, no files, no enrichment; the rlog PCA the reference draws first is
+    :func:`compute_pseudobulk_PCA` / :func:`pseudobulk_pca` on :func:`pseudobulk_inputs`' pair; the deviations of
     :func:`compute_pseudobulk_DE` apply."""
     import itertools
     _check_shrink(shrink, "get_pseudobulk_DE")

@@ -17,7 +17,14 @@ wave per gene and six 64-point rounds over LDS-staged samples; nb_shrink replace
 divides.  The dispersions come from one MAP-less pass, the far ends from nb_group_fits, the prior scale from
 engine.nb_prior_scale.  ``nb_dispersions`` and ``nb_shrink`` alternate in one loop, best of --reps each; the mean inner steps a
 lane and round (from the call's ``steps``) go beside the times so that the ratio can be read.  Host: the vectorised restatement
-(tests/nb_shrink_restatement.py) on --host-genes genes, scaled.  Writes OUT/shrink_rate.txt."""
+(tests/nb_shrink_restatement.py) on --host-genes genes, scaled.  Writes OUT/shrink_rate.txt.
+
+--rlog: instead, the regularised log transform (K24: engine.nb_rlog, on_device=True) beside the dispersion pass on the same tables:
+both are one wave per gene over LDS-staged samples; the dispersion pass evaluates 6 x 64 x m likelihood terms with lgamma a gene,
+nb_rlog about (iterations + halvings) x m terms in three passes, spread over the lanes.  The dispersions are the trend of one
+blind pass (engine.nb_dispersions_blind, engine.nb_trend), the prior variance engine.nb_rlog_prior_var's.  ``nb_dispersions`` and
+``nb_rlog`` alternate in one loop, best of --reps each; the mean iterations a gene go beside the times.  Host: the vectorised
+restatement of the same iteration (tests/nb_rlog_restatement.py) on --host-genes genes, scaled.  Writes OUT/rlog_rate.txt."""
 import argparse
 import os
 import sys
@@ -38,7 +45,10 @@ def main():
     ap.add_argument("--host-genes", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shrink", action="store_true")
+    ap.add_argument("--rlog", action="store_true")
     a = ap.parse_args()
+    if a.shrink and a.rlog:
+        ap.error("--shrink and --rlog are separate runs")
     import nb_glm_restatement as RR
     from pilot_amd import _lib, engine
 
@@ -98,7 +108,41 @@ def main():
             "at most %.2g" % (h, t_host, a.genes, h, t_host * a.genes / h, res.sum(),
                               np.abs(SR.t_of(b1[:h][res], S) - found["t"][res]).max(initial=0)))
         del D
-    for m in (() if a.shrink else a.samples):
+    for m in (a.samples if a.rlog else ()):
+        import nb_rlog_restatement as LR
+        rng = np.random.default_rng(m)
+        s = RR.size_factors(rng, m)
+        codes = (np.arange(m) % 2).astype(np.int32)
+        c = RR.nb_class(rng, s, codes, 2, a.genes)
+        D = engine.DeviceMatrix.upload(c.astype(np.float32))
+        x = engine.nb_dispersions_blind(D, s)
+        mean = (c / s[:, None]).mean(axis=0)
+        fit = engine.nb_clip(engine.nb_trend(mean, engine.nb_clip(np.exp(x), m))[0], m)
+        pv = engine.nb_rlog_prior_var(c, s, mean, fit)
+        engine.nb_dispersions(D, codes, 2, s)
+        engine.nb_rlog(D, s, fit, pv, on_device=True)
+        t_disp = t_rlog = np.inf
+        for _ in range(a.reps):                                         # the two calls alternate
+            t0 = time.perf_counter()
+            engine.nb_dispersions(D, codes, 2, s)
+            t1 = time.perf_counter()
+            R, info = engine.nb_rlog(D, s, fit, pv, on_device=True, return_info=True)
+            t2 = time.perf_counter()
+            t_disp, t_rlog = min(t_disp, t1 - t0), min(t_rlog, t2 - t1)
+        live = np.isfinite(info["intercept"])
+        say("case %d genes x %d samples, float32 in HBM, result kept in HBM; prior variance %.4g" % (a.genes, m, pv))
+        say("  nb_rlog %.2f ms, nb_dispersions (gene-wise, 2 groups) %.2f ms beside it: ratio %.2f; best of %d, alternating"
+            % (1e3 * t_rlog, 1e3 * t_disp, t_rlog / t_disp, a.reps))
+        say("  iterations a gene: mean %.2f, largest %d; %d not converged" % (info["steps"][live].mean(), info["steps"].max(), info["n_not_converged"]))
+        h = min(a.host_genes, a.genes)
+        t0 = time.perf_counter()
+        ref = LR.arrowhead_rlog(c[:, :h], s, fit[:h], pv)
+        t_host = time.perf_counter() - t0
+        got = engine.download(R)[:, :h]
+        say("  host restatement (vectorised numpy) on %d genes: %.1f ms; scaled by %d / %d: %.2f s; device against it: rlog off by at most "
+            "%.2g" % (h, 1e3 * t_host, a.genes, h, t_host * a.genes / h, np.abs(got - ref["rlog"]).max()))
+        del D, R
+    for m in (() if a.shrink or a.rlog else a.samples):
         rng = np.random.default_rng(m)
         s = RR.size_factors(rng, m)
         codes = (np.arange(m) % 2).astype(np.int32)
@@ -133,7 +177,7 @@ def main():
                np.abs(np.expm1(x[:h][res] - xh[res])).max(initial=0)))
         del D, Z
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

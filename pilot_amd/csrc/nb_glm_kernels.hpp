@@ -15,13 +15,17 @@
 //                       exactly and c log is 0) is a uniform branch, and so is a group boundary: one running sum of w per lane closes
 //                       each group's log term, and L adds the groups' closed parts in group order (so with two groups the result
 //                       does not depend on which of them is code 0).  No sum crosses lanes; the only cross-lane step is the first-maximum argmax
-//                       (reduce.hpp's lanes_best with LowestMax).  NB_ROUNDS rounds of the NB_GRID-point grid
-//                       x_i = lo + (hi - lo) * i / 63 run inside the launch, the next bracket being [x_{max(b-1,0)}, x_{min(b+1,63)}].
-//                       LDS: 8 (2 m + k) bytes.
+//                       of nb_grid_rounds.  LDS: 8 (2 m + k) bytes.
 // nb_group_fit_kernel   one lane per (gene, group), genes along the lanes so that a sample's row is read coalesced.  The root of
 //                         f(q) = sum_{p in g} (c_p - s_p q) / (1 + a s_p q)
-//                       in u = log q by Newton steps kept inside a shrinking bracket (bisection when a step leaves it or gains too
-//                       little), from the Poisson estimate sum c / sum s.
+//                       in u = log q by nb_bracketed_root, from the Poisson estimate sum c / sum s.
+//
+// The two pieces K23 (nb_shrink_kernel.hpp) shares:
+// nb_grid_rounds        the search of a wave whose lanes are grid points: NB_ROUNDS rounds of the NB_GRID-point grid
+//                       x_i = lo + (hi - lo) * i / 63 inside one launch, the first largest value winning (reduce.hpp's lanes_best with
+//                       LowestMax) and the next bracket being [x_{max(b-1,0)}, x_{min(b+1,63)}].
+// nb_bracketed_root     the root of a decreasing score by Newton steps kept inside a shrinking bracket, bisection when a step leaves
+//                       it or gains too little; to NB_FIT_TOL in at most NB_FIT_MAX_STEPS steps.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +47,54 @@ constexpr int NB_FLAG_FLOORED = 2;          // PILOT_OT_NB_FLOORED
 constexpr nb_u64 NB_NO_BAD = ~0ull;
 
 __host__ __device__ inline double nb_max_disp(long long m) { return m > 10 ? (double)m : 10.0; }
+
+// One wave, lane = grid point.  eval(round, x): the value at this lane's point x;  won(round, b): lane b holds the round's first largest
+// value (b is wave-uniform; the caller keeps what its eval computed and writes its results from lane b of round NB_ROUNDS - 1).
+template <typename Eval, typename Won>
+__device__ inline void nb_grid_rounds(double lo, double hi, int lane, Eval eval, Won won) {
+    for (int round = 0; round < NB_ROUNDS; ++round) {
+        double best = eval(round, lo + (hi - lo) * (double)lane / 63.0);
+        int b = lane;
+        lanes_best(best, b, LowestMax{});
+        const int bl = b > 0 ? b - 1 : 0, bh = b < 63 ? b + 1 : 63;
+        const double nlo = lo + (hi - lo) * (double)bl / 63.0, nhi = lo + (hi - lo) * (double)bh / 63.0;
+        won(round, b);
+        lo = nlo;
+        hi = nhi;
+    }
+}
+
+// The root in [ulo, uhi] of score(u, f, df) (f >= 0 at ulo, f <= 0 at uhi, df < 0) from u inside the bracket.  Returns the steps taken,
+// NB_FIT_MAX_STEPS with converged = false when the last step is still longer than NB_FIT_TOL.
+// ENDS_INSIDE: whether a Newton step that lands ON an end of the bracket is taken (true) or replaced by a bisection (false).
+//   false  nb_group_fit_kernel (K22), on purpose: the rule decides the last bits of q and the step counts of a fit that ends on a
+//          step of 0, and K22's were recorded with it (one solve per
+//          (gene, group): the bisection a rejected step restarts costs a few steps, not the convergence).
+//   true   nb_shrink_solve (K23).  One end of the bracket is always u itself, so a Newton step below the last bit of u, un == u, lands
+//          on an end: it is a step of 0 and ends the loop -- rejected, it would restart a bisection of whatever bracket the
+//          one-sided iterates have left, which K23 pays 384 times a gene.
+template <bool ENDS_INSIDE, typename Score>
+__host__ __device__ inline int nb_bracketed_root(double ulo, double uhi, double &u, bool &converged, Score score) {
+    double dxold = uhi - ulo, dx = dxold, f, df;
+    score(u, f, df);
+    converged = false;
+    int steps;
+    for (steps = 1; steps <= NB_FIT_MAX_STEPS; ++steps) {
+        if (f > 0.0) ulo = u; else uhi = u;
+        const double un = u - f / df;
+        dxold = dx;
+        if (!(ENDS_INSIDE ? un >= ulo && un <= uhi : un > ulo && un < uhi) || fabs(2.0 * f) > fabs(dxold * df)) {
+            dx = 0.5 * (uhi - ulo);
+            u = ulo + dx;
+        } else {
+            dx = un - u;
+            u = un;
+        }
+        if (fabs(dx) <= NB_FIT_TOL) { converged = true; break; }
+        score(u, f, df);
+    }
+    return converged ? steps : NB_FIT_MAX_STEPS;
+}
 
 template <typename T>
 __global__ void __launch_bounds__(256) nb_check_kernel(const T *__restrict__ Y, long long ld, long long m, int n_genes, nb_u64 *bad) {
@@ -97,10 +149,9 @@ __global__ void __launch_bounds__(64) nb_dispersion_kernel(const T *__restrict__
         return;
     }
     const double half_inv_var = log_prior_mean ? 0.5 / prior_var : 0.0;
-    double lo = log(NB_MIN_DISP), hi = log(nb_max_disp(m));
     double x = 0.0, L = 0.0;
-    for (int round = 0; round < NB_ROUNDS; ++round) {
-        x = lo + (hi - lo) * (double)lane / 63.0;
+    nb_grid_rounds(log(NB_MIN_DISP), log(nb_max_disp(m)), lane, [&](int, double at) {
+        x = at;
         const double alpha = exp(x), r = 1.0 / alpha, lg_r = lgamma(r);
         L = 0.0;
         int p = 0;
@@ -116,15 +167,10 @@ __global__ void __launch_bounds__(64) nb_dispersion_kernel(const T *__restrict__
             L += Lg - 0.5 * log(sw);                 // a group's part is closed on its own: two groups may swap codes, bit for bit
         }
         if (log_prior_mean) L -= (x - lpm) * (x - lpm) * half_inv_var;
-        double best = L;
-        int b = lane;
-        lanes_best(best, b, LowestMax{});
-        const int bl = b > 0 ? b - 1 : 0, bh = b < 63 ? b + 1 : 63;
-        const double nlo = lo + (hi - lo) * (double)bl / 63.0, nhi = lo + (hi - lo) * (double)bh / 63.0;
+        return L;
+    }, [&](int round, int b) {
         if (round == NB_ROUNDS - 1 && lane == b) { log_disp[gene] = x; objective[gene] = L; }
-        lo = nlo;
-        hi = nhi;
-    }
+    });
 }
 
 // f(q) and q f'(q) of one group: its samples are the sorted positions a .. b - 1
@@ -177,24 +223,11 @@ __global__ void __launch_bounds__(256) nb_group_fit_kernel(const T *__restrict__
         double ulo = log(qmin > lower ? qmin : lower), uhi = log(qmax);
         double u = log(sum_c / sum_s);
         u = u < ulo ? ulo : (u > uhi ? uhi : u);
-        double dxold = uhi - ulo, dx = dxold, f, qdf;
-        nb_score(Y, ld, gene, order, ss, a, b, alpha, exp(u), f, qdf);
-        bool done = false;
-        for (steps = 1; steps <= NB_FIT_MAX_STEPS; ++steps) {
-            if (f > 0.0) ulo = u; else uhi = u;
-            const double un = u - f / qdf;
-            dxold = dx;
-            if (!(un > ulo && un < uhi) || fabs(2.0 * f) > fabs(dxold * qdf)) {
-                dx = 0.5 * (uhi - ulo);
-                u = ulo + dx;
-            } else {
-                dx = un - u;
-                u = un;
-            }
-            if (fabs(dx) <= NB_FIT_TOL) { done = true; break; }
-            nb_score(Y, ld, gene, order, ss, a, b, alpha, exp(u), f, qdf);
-        }
-        if (!done) { flags |= NB_FLAG_NOT_CONVERGED; steps = NB_FIT_MAX_STEPS; }
+        bool done;
+        steps = nb_bracketed_root<false>(ulo, uhi, u, done, [&](double at, double &f, double &qdf) {
+            nb_score(Y, ld, gene, order, ss, a, b, alpha, exp(at), f, qdf);
+        });
+        if (!done) flags |= NB_FLAG_NOT_CONVERGED;
         q = exp(u);
     }
     const double floor_q = NB_MIN_MU / smax;

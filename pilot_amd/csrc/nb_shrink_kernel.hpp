@@ -6,13 +6,13 @@
 // p can have two local maxima between 0 and the maximum-likelihood b1, so the estimate is DEFINED by a search:
 //
 // nb_shrink_kernel   one wave per gene, A LANE IS A GRID POINT of t in [0, asinh(E / S)], b1 = sg S sinh(t).  The gene's c_p and s_p
-//                    are staged once in LDS and read as broadcasts.  NB_ROUNDS rounds of the NB_GRID-point grid, as
-//                    nb_dispersion_kernel: every lane solves its own b0 (nb_shrink_solve: Newton steps kept inside a shrinking
-//                    bracket, warm-started from the lane's last b0: one exp per group and one divide per sample a step), then
-//                    evaluates p once (nb_shrink_value: the only log / log1p); the first largest p wins (lanes_best, LowestMax).
+//                    are staged once in LDS and read as broadcasts.  The search is K22's nb_grid_rounds: every lane solves its own
+//                    b0 (nb_shrink_solve: K22's nb_bracketed_root, warm-started from the lane's last b0: one exp per group and one
+//                    divide per sample a step), then evaluates p once (nb_shrink_value: the only log / log1p).
 //                    No floating-point sum crosses lanes, and a group's part of every sum is closed on its own.
 //                    LDS: 16 m bytes.
-// The per-lane arithmetic is __host__ __device__, so that a host program can walk the same search.
+// The per-lane arithmetic is __host__ __device__: a stand-alone host program that includes this header runs nb_shrink_solve on fixed
+// inputs, which is how a change to the shared root finder is compared bit for bit before it reaches a GPU.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -85,33 +85,13 @@ __host__ __device__ inline void nb_shrink_bracket(const NbShrinkGene &g, double 
 // where a lane without a previous b0 starts: the Poisson estimate at b1
 __host__ __device__ inline double nb_shrink_start(const NbShrinkGene &g, double b1) { return log(g.c_sum / (g.s_sum[0] + exp(b1) * g.s_sum[1])); }
 
-// the root in b0 at b1 from u (moved into the bracket), as nb_group_fit_kernel steps.  Returns the steps taken; converged = false
-// after NB_FIT_MAX_STEPS.
+// the root in b0 at b1 from u (moved into the bracket) by nb_bracketed_root, the ends counting as inside.  Returns the steps taken;
+// converged = false after NB_FIT_MAX_STEPS.
 __host__ __device__ inline int nb_shrink_solve(const double *c, const double *s, const NbShrinkGene &g, double b1, double &u, bool &converged) {
-    double ulo, uhi, f, df;
+    double ulo, uhi;
     nb_shrink_bracket(g, b1, ulo, uhi);
     u = u > ulo ? (u < uhi ? u : uhi) : ulo;                 // (a NaN start goes to ulo)
-    double dxold = uhi - ulo, dx = dxold;
-    nb_shrink_score(c, s, g, u, b1, f, df);
-    converged = false;
-    int steps;
-    for (steps = 1; steps <= NB_FIT_MAX_STEPS; ++steps) {
-        if (f > 0.0) ulo = u; else uhi = u;
-        const double un = u - f / df;
-        dxold = dx;
-        // (the ends count as inside: a Newton step below the last bit of u, un == u, is a step of 0 and ends the loop -- rejected, it
-        // would restart a bisection of whatever bracket the one-sided iterates have left)
-        if (!(un >= ulo && un <= uhi) || fabs(2.0 * f) > fabs(dxold * df)) {
-            dx = 0.5 * (uhi - ulo);
-            u = ulo + dx;
-        } else {
-            dx = un - u;
-            u = un;
-        }
-        if (fabs(dx) <= NB_FIT_TOL) { converged = true; break; }
-        nb_shrink_score(c, s, g, u, b1, f, df);
-    }
-    return converged ? steps : NB_FIT_MAX_STEPS;
+    return nb_bracketed_root<true>(ulo, uhi, u, converged, [&](double at, double &f, double &df) { nb_shrink_score(c, s, g, at, b1, f, df); });
 }
 
 // P(u, b1) and the two groups' observed information there
@@ -171,24 +151,20 @@ __global__ void __launch_bounds__(64) nb_shrink_kernel(const T *__restrict__ Y, 
     NbShrinkGene g;
     nb_shrink_gene(sc, sS, m, n0, alpha, sigma0, g);
     const double fe = far_end[gene], t_end = asinh(fabs(fe) / S);
-    double lo = 0.0, hi = t_end, u = 0.0;
+    double u = 0.0, b1 = 0.0, P = 0.0, w0 = 0.0, w1 = 0.0;
     bool at_end = true;
     int flags = 0, steps = 0;
-    for (int round = 0; round < NB_ROUNDS; ++round) {
-        const double t = lo + (hi - lo) * (double)lane / 63.0, b1 = nb_shrink_beta1(fe, S, t);
-        if (round == 0) u = nb_shrink_start(g, b1);
+    nb_grid_rounds(0.0, t_end, lane, [&](int round, double t) {
+        b1 = nb_shrink_beta1(fe, S, t);
+        if (round == 0) u = nb_shrink_start(g, b1);          // (later rounds start from the lane's last b0)
         bool converged;
         steps += nb_shrink_solve(sc, sS, g, b1, u, converged);
         if (!converged) flags |= NB_FLAG_NOT_CONVERGED;
-        double w0, w1;
-        const double P = nb_shrink_value(sc, sS, g, u, b1, S, w0, w1);
-        double best = P;
-        int b = lane;
-        lanes_best(best, b, LowestMax{});
+        P = nb_shrink_value(sc, sS, g, u, b1, S, w0, w1);
+        return P;
+    }, [&](int round, int b) {
         if (b == 63 && at_end) flags |= NB_FLAG_AT_BOUND;
         at_end = at_end && b == 63;
-        const int bl = b > 0 ? b - 1 : 0, bh = b < 63 ? b + 1 : 63;
-        const double nlo = lo + (hi - lo) * (double)bl / 63.0, nhi = lo + (hi - lo) * (double)bh / 63.0;
         if (round == NB_ROUNDS - 1) {
             flags = lanes_reduce(flags, Max{});              // (AT_BOUND is uniform, so the largest value is the OR)
             steps = lanes_reduce(steps, Sum{});
@@ -201,9 +177,7 @@ __global__ void __launch_bounds__(64) nb_shrink_kernel(const T *__restrict__ Y, 
                 flags_out[gene] = flags | (steps << NB_SHRINK_STEPS_SHIFT);
             }
         }
-        lo = nlo;
-        hi = nhi;
-    }
+    });
 }
 
 }  // namespace pilot

@@ -23,18 +23,27 @@ struct Design {
     std::vector<double> ss;
 };
 
-// every check of (m, codes, n_groups, size_factors), then the sorted design.  No HIP call.
-int make_design(long long m, const int *codes, int n_groups, const double *sf, Design &d) {
+// every check of (m, size_factors) and, with codes (a grouped call), of (n_groups, codes), in the order the calls have always
+// refused them.  No HIP call.
+int check_samples(long long m, const double *sf, const int *codes = nullptr, int n_groups = 1) {
     if (m < 2) return fail(PILOT_OT_EINVAL, "m=%lld samples: at least 2", m);
     if (m > INT_MAX) return fail(PILOT_OT_ENOTSUP, "m=%lld samples need more than 32-bit indices", m);
-    if (n_groups < 2 || n_groups > m - 1)
+    if (codes && (n_groups < 2 || n_groups > m - 1))
         return fail(PILOT_OT_EINVAL, "n_groups=%d must be in [2, m - 1 = %lld] (a residual degree of freedom is needed)", n_groups, m - 1);
-    d.gstart.assign((size_t)n_groups + 1, 0);
     for (long long i = 0; i < m; ++i) {
-        if (codes[i] < 0 || codes[i] >= n_groups) return fail(PILOT_OT_EINVAL, "codes[%lld]=%d outside [0, %d)", i, codes[i], n_groups);
+        if (codes && (codes[i] < 0 || codes[i] >= n_groups)) return fail(PILOT_OT_EINVAL, "codes[%lld]=%d outside [0, %d)", i, codes[i], n_groups);
         if (!(std::isfinite(sf[i]) && sf[i] > 0.0)) return fail(PILOT_OT_EINVAL, "size_factors[%lld]=%g must be positive and finite", i, sf[i]);
-        ++d.gstart[(size_t)codes[i] + 1];
     }
+    return PILOT_OT_OK;
+}
+
+// check_samples, then the sorted design.  Without codes: the design `~ 1` of m samples (blind), one group (n_groups = 1), the
+// samples in their own order.
+int make_design(long long m, const int *codes, int n_groups, const double *sf, Design &d) {
+    if (int rc = check_samples(m, sf, codes, n_groups)) return rc;
+    const auto code = [codes](long long i) { return codes ? codes[i] : 0; };
+    d.gstart.assign((size_t)n_groups + 1, 0);
+    for (long long i = 0; i < m; ++i) ++d.gstart[(size_t)code(i) + 1];
     for (int g = 0; g < n_groups; ++g) {
         if (d.gstart[(size_t)g + 1] == 0) return fail(PILOT_OT_EINVAL, "group %d has no sample", g);
         d.gstart[(size_t)g + 1] += d.gstart[g];
@@ -44,9 +53,9 @@ int make_design(long long m, const int *codes, int n_groups, const double *sf, D
     d.gof.resize((size_t)m);
     d.ss.resize((size_t)m);
     for (long long i = 0; i < m; ++i) {
-        const int p = at[codes[i]]++;
+        const int p = at[code(i)]++;
         d.order[p] = (int)i;
-        d.gof[p] = codes[i];
+        d.gof[p] = code(i);
         d.ss[p] = sf[i];
     }
     return PILOT_OT_OK;
@@ -69,6 +78,15 @@ int upload_design(const Design &d, DevDesign &dev) {
     HIP_TRY(hipMemcpy(dev.gof, d.gof.data(), sizeof(int) * m, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dev.gstart, d.gstart.data(), sizeof(int) * k1, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dev.ss, d.ss.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+    return PILOT_OT_OK;
+}
+
+// one workgroup of one wave per gene with `lds_doubles` doubles of dynamic LDS, which the kernel is allowed first
+template <typename... P, typename... A> int launch_wave_per_gene(void (*kern)(P...), int n_genes, size_t lds_doubles, A... args) {
+    const size_t lds = sizeof(double) * lds_doubles;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_genes), dim3(64), lds, nullptr, args...);
+    HIP_TRY(hipGetLastError());
     return PILOT_OT_OK;
 }
 
@@ -100,12 +118,10 @@ int dispersions(const void *y, long long ld, int m, int n_genes, int k, const De
         HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G, &d_prior));
         HIP_TRY(hipMemcpy(d_prior, log_prior_mean, sizeof(double) * G, hipMemcpyHostToDevice));
     }
-    const size_t lds = sizeof(double) * (2 * (size_t)m + (size_t)k);
-    auto kern = pilot::nb_dispersion_kernel<T>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_genes), dim3(64), lds, nullptr, static_cast<const T *>(y), ld, m, k, dd.order, dd.gof, dd.ss,
-                       dd.gstart, d_prior, prior_var, d_out, d_out + G, fitted_mean ? d_out + 2 * G : nullptr);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_wave_per_gene(pilot::nb_dispersion_kernel<T>, n_genes, 2 * (size_t)m + (size_t)k, static_cast<const T *>(y), ld, m, k,
+                                      dd.order, dd.gof, dd.ss, dd.gstart, d_prior, prior_var, d_out, d_out + G,
+                                      fitted_mean ? d_out + 2 * G : nullptr))
+        return rc;
     HIP_TRY(hipMemcpy(log_disp, d_out, sizeof(double) * G, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(objective, d_out + G, sizeof(double) * G, hipMemcpyDeviceToHost));
     if (fitted_mean) HIP_TRY(hipMemcpy(fitted_mean, d_out + 2 * G, sizeof(double) * G * k, hipMemcpyDeviceToHost));
@@ -144,37 +160,15 @@ int shrink(const void *y, long long ld, int m, int n_genes, const DevDesign &dd,
     HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, G, &d_flags));
     HIP_TRY(hipMemcpy(d_dbl, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_dbl + G, far_end, sizeof(double) * G, hipMemcpyHostToDevice));
-    const size_t lds = sizeof(double) * 2 * (size_t)m;
-    auto kern = pilot::nb_shrink_kernel<T>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_genes), dim3(64), lds, nullptr, static_cast<const T *>(y), ld, m, n0, dd.order, dd.ss, d_dbl,
-                       d_dbl + G, prior_scale, intercept_scale, d_dbl + 2 * G, d_dbl + 3 * G, d_dbl + 4 * G, d_dbl + 5 * G, d_flags);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_wave_per_gene(pilot::nb_shrink_kernel<T>, n_genes, 2 * (size_t)m, static_cast<const T *>(y), ld, m, n0, dd.order, dd.ss,
+                                      d_dbl, d_dbl + G, prior_scale, intercept_scale, d_dbl + 2 * G, d_dbl + 3 * G, d_dbl + 4 * G, d_dbl + 5 * G,
+                                      d_flags))
+        return rc;
     HIP_TRY(hipMemcpy(beta0, d_dbl + 2 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(beta1, d_dbl + 3 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(objective, d_dbl + 4 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(info, d_dbl + 5 * G, sizeof(double) * 2 * G, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags, d_flags, sizeof(int) * G, hipMemcpyDeviceToHost));
-    return PILOT_OT_OK;
-}
-
-// every check of (m, size_factors) of the calls without groups.  No HIP call.
-int check_samples(long long m, const double *sf) {
-    if (m < 2) return fail(PILOT_OT_EINVAL, "m=%lld samples: at least 2", m);
-    if (m > INT_MAX) return fail(PILOT_OT_ENOTSUP, "m=%lld samples need more than 32-bit indices", m);
-    for (long long i = 0; i < m; ++i)
-        if (!(std::isfinite(sf[i]) && sf[i] > 0.0)) return fail(PILOT_OT_EINVAL, "size_factors[%lld]=%g must be positive and finite", i, sf[i]);
-    return PILOT_OT_OK;
-}
-
-// the design `~ 1` of m samples (blind): one group, the samples in their own order
-int make_blind_design(long long m, const double *sf, Design &d) {
-    if (int rc = check_samples(m, sf)) return rc;
-    d.order.resize((size_t)m);
-    for (long long i = 0; i < m; ++i) d.order[(size_t)i] = (int)i;
-    d.gof.assign((size_t)m, 0);
-    d.gstart = {0, (int)m};
-    d.ss.assign(sf, sf + m);
     return PILOT_OT_OK;
 }
 
@@ -196,12 +190,9 @@ int rlog(const void *y, long long ld, int m, int n_genes, const double *sf, cons
     double *d_res = out_is_device ? static_cast<double *>(out) : d_dbl + G;
     const long long ld_res = out_is_device ? ld_out : (long long)n_genes;
     const double ln2 = pilot::NB_RLOG_LN2, lambda = ln2 * ln2 / prior_var, lambda0 = pilot::NB_RLOG_INTERCEPT_RIDGE * ln2 * ln2;
-    const size_t lds = sizeof(double) * 3 * M;
-    auto kern = pilot::nb_rlog_kernel<T>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_genes), dim3(64), lds, nullptr, static_cast<const T *>(y), ld, m, d_sf, d_disp, lambda, lambda0,
-                       d_res, ld_res, d_dbl, d_int, d_int + G);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_wave_per_gene(pilot::nb_rlog_kernel<T>, n_genes, 3 * M, static_cast<const T *>(y), ld, m, d_sf, d_disp, lambda, lambda0,
+                                      d_res, ld_res, d_dbl, d_int, d_int + G))
+        return rc;
     if (!out_is_device)
         HIP_TRY(hipMemcpy2D(out, sizeof(double) * (size_t)ld_out, d_res, sizeof(double) * G, sizeof(double) * G, M, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(intercept, d_dbl, sizeof(double) * G, hipMemcpyDeviceToHost));
@@ -226,6 +217,75 @@ int check_matrix(int dtype, int n_genes, long long ld) {
     return pilot::check_dtype(dtype);
 }
 
+int positive_finite(const char *name, double v, const char *when = "") {
+    return std::isfinite(v) && v > 0.0 ? PILOT_OT_OK : fail(PILOT_OT_EINVAL, "%s=%g must be positive and finite%s", name, v, when);
+}
+
+int no_check() { return PILOT_OT_OK; }
+
+// what an entry point hands the prologue, and what it gets back
+struct Call {
+    const void *Y;
+    int Y_is_device, dtype;
+    long long m;
+    int n_genes;
+    long long ld;
+    const double *sf;
+    bool design;                  // false (rlog): the samples are checked, nothing is sorted or uploaded
+    const int *codes;             // of a design: NULL for `~ 1` (blind), one group
+    int n_groups;
+    const double *dispersion;     // nullable: checked right after the design
+    const char *staged;           // nullable: what of a gene the kernel stages in LDS, so that m is limited
+    const void *y;                // out: Y on the device and its leading dimension, the design on the host and the device
+    long long y_ld;
+    Design d;
+    DevDesign dd;
+};
+
+// The one way into the five entry points: -1 into bad_row / bad_col, then every refusal in the order the calls have always made
+// them -- a NULL argument, the matrix, the call's own checks `before` the design, the design (or the samples alone), the
+// dispersions, the call's own checks `after` them, the LDS limit on m -- then Y staged and the design uploaded.
+template <typename Before, typename After>
+int prologue(Call &c, bool null_arg, long long *bad_row, int *bad_col, Before before, After after) {
+    if (bad_row) *bad_row = -1;
+    if (bad_col) *bad_col = -1;
+    if (null_arg) return fail(PILOT_OT_EINVAL, "NULL pointer");
+    if (int rc = check_matrix(c.dtype, c.n_genes, c.ld)) return rc;
+    if (int rc = before()) return rc;
+    if (int rc = c.design ? make_design(c.m, c.codes, c.n_groups, c.sf, c.d) : check_samples(c.m, c.sf)) return rc;
+    if (c.dispersion)
+        if (int rc = check_dispersions(c.dispersion, c.n_genes, c.m)) return rc;
+    if (int rc = after()) return rc;
+    if (c.staged && c.m > pilot::NB_MAX_SAMPLES)
+        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's %s are staged in LDS, at most %d", c.m, c.staged, pilot::NB_MAX_SAMPLES);
+    if (int rc = pilot::stage_dense(c.Y, c.Y_is_device, pilot::elem_size(c.dtype), c.m, c.n_genes, c.ld, pilot::WS_NB_Y, &c.y, &c.y_ld)) return rc;
+    return c.design ? upload_design(c.d, c.dd) : PILOT_OT_OK;
+}
+
+// body(T()) with T the element type of dtype code `dtype` (checked)
+template <typename Body> int by_dtype(int dtype, Body body) { return dtype == 0 ? body(float()) : body(double()); }
+
+// how many of n flag words carry `flag`, into the nullable *out
+void count_flag(const int *flags, long long n, int flag, int *out) {
+    int count = 0;
+    for (long long t = 0; t < n; ++t) count += (flags[t] & flag) != 0;
+    if (out) *out = count;
+}
+
+// pilot_ot_nb_dispersions and, without codes, pilot_ot_nb_dispersions_blind
+int nb_dispersions(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes, int n_groups,
+                   const double *size_factors, const double *log_prior_mean, double prior_var, double *log_disp, double *objective,
+                   double *fitted_mean, long long *bad_row, int *bad_col, bool blind) {
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, true, codes, n_groups, nullptr, "counts and fitted means"};
+    if (int rc = prologue(c, !Y || (!blind && !codes) || !size_factors || !log_disp || !objective, bad_row, bad_col,
+                          [&] { return log_prior_mean ? positive_finite("prior_var", prior_var, " when a prior is given") : PILOT_OT_OK; }, no_check))
+        return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return dispersions<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, n_groups, c.dd, log_prior_mean, prior_var, log_disp, objective, fitted_mean,
+                                        bad_row, bad_col);
+    });
+}
+
 }  // namespace
 
 PILOT_API int pilot_ot_nb_glm_max_samples(void) { return pilot::NB_MAX_SAMPLES; }
@@ -233,69 +293,32 @@ PILOT_API int pilot_ot_nb_glm_max_samples(void) { return pilot::NB_MAX_SAMPLES; 
 PILOT_API int pilot_ot_nb_dispersions(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
                                       int n_groups, const double *size_factors, const double *log_prior_mean, double prior_var,
                                       double *log_disp, double *objective, double *fitted_mean, long long *bad_row, int *bad_col) {
-    if (bad_row) *bad_row = -1;
-    if (bad_col) *bad_col = -1;
-    if (!Y || !codes || !size_factors || !log_disp || !objective) return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
-    if (log_prior_mean && !(std::isfinite(prior_var) && prior_var > 0.0))
-        return fail(PILOT_OT_EINVAL, "prior_var=%g must be positive and finite when a prior is given", prior_var);
-    Design d;
-    if (int rc = make_design(m, codes, n_groups, size_factors, d)) return rc;
-    if (m > pilot::NB_MAX_SAMPLES)
-        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts and fitted means are staged in LDS, at most %d", m, pilot::NB_MAX_SAMPLES);
-    const void *y;
-    long long y_ld;
-    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
-    DevDesign dd;
-    if (int rc = upload_design(d, dd)) return rc;
-    return dtype == 0 ? dispersions<float>(y, y_ld, (int)m, n_genes, n_groups, dd, log_prior_mean, prior_var, log_disp, objective, fitted_mean,
-                                           bad_row, bad_col)
-                      : dispersions<double>(y, y_ld, (int)m, n_genes, n_groups, dd, log_prior_mean, prior_var, log_disp, objective, fitted_mean,
-                                            bad_row, bad_col);
+    return nb_dispersions(Y, Y_is_device, dtype, m, n_genes, ld, codes, n_groups, size_factors, log_prior_mean, prior_var, log_disp, objective,
+                          fitted_mean, bad_row, bad_col, false);
 }
 
 PILOT_API int pilot_ot_nb_dispersions_blind(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld,
                                             const double *size_factors, double *log_disp, double *objective, double *base_mean,
                                             long long *bad_row, int *bad_col) {
-    if (bad_row) *bad_row = -1;
-    if (bad_col) *bad_col = -1;
-    if (!Y || !size_factors || !log_disp || !objective) return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
-    Design d;
-    if (int rc = make_blind_design(m, size_factors, d)) return rc;
-    if (m > pilot::NB_MAX_SAMPLES)
-        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts and fitted means are staged in LDS, at most %d", m, pilot::NB_MAX_SAMPLES);
-    const void *y;
-    long long y_ld;
-    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
-    DevDesign dd;
-    if (int rc = upload_design(d, dd)) return rc;
-    return dtype == 0 ? dispersions<float>(y, y_ld, (int)m, n_genes, 1, dd, nullptr, 0.0, log_disp, objective, base_mean, bad_row, bad_col)
-                      : dispersions<double>(y, y_ld, (int)m, n_genes, 1, dd, nullptr, 0.0, log_disp, objective, base_mean, bad_row, bad_col);
+    return nb_dispersions(Y, Y_is_device, dtype, m, n_genes, ld, nullptr, 1, size_factors, nullptr, 0.0, log_disp, objective, base_mean, bad_row,
+                          bad_col, true);
 }
 
 PILOT_API int pilot_ot_nb_group_fits(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes,
                                      int n_groups, const double *size_factors, const double *dispersion, double *q, double *w, int *steps,
                                      int *flags, int *n_not_converged) {
     if (n_not_converged) *n_not_converged = 0;
-    if (!Y || !codes || !size_factors || !dispersion || !q || !w || !steps || !flags) return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
-    Design d;
-    if (int rc = make_design(m, codes, n_groups, size_factors, d)) return rc;
-    if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
-    if ((long long)n_genes * n_groups > INT_MAX)
-        return fail(PILOT_OT_ENOTSUP, "n_genes * n_groups = %lld results need more than 32-bit indices", (long long)n_genes * n_groups);
-    const void *y;
-    long long y_ld;
-    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
-    DevDesign dd;
-    if (int rc = upload_design(d, dd)) return rc;
-    if (int rc = dtype == 0 ? group_fits<float>(y, y_ld, m, n_genes, n_groups, dd, dispersion, q, w, steps, flags)
-                            : group_fits<double>(y, y_ld, m, n_genes, n_groups, dd, dispersion, q, w, steps, flags))
+    const long long n_out = (long long)n_genes * n_groups;
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, true, codes, n_groups, dispersion, nullptr};
+    if (int rc = prologue(c, !Y || !codes || !size_factors || !dispersion || !q || !w || !steps || !flags, nullptr, nullptr, no_check, [&] {
+            return n_out > INT_MAX ? fail(PILOT_OT_ENOTSUP, "n_genes * n_groups = %lld results need more than 32-bit indices", n_out) : PILOT_OT_OK;
+        }))
         return rc;
-    int bad = 0;
-    for (long long t = 0; t < (long long)n_genes * n_groups; ++t) bad += (flags[t] & pilot::NB_FLAG_NOT_CONVERGED) != 0;
-    if (n_not_converged) *n_not_converged = bad;
+    if (int rc = by_dtype(dtype, [&](auto t) {
+            return group_fits<decltype(t)>(c.y, c.y_ld, m, n_genes, n_groups, c.dd, dispersion, q, w, steps, flags);
+        }))
+        return rc;
+    count_flag(flags, n_out, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
     return PILOT_OT_OK;
 }
 
@@ -303,63 +326,48 @@ PILOT_API int pilot_ot_nb_shrink(const void *Y, int Y_is_device, int dtype, long
                                  const double *size_factors, const double *dispersion, const double *far_end, double prior_scale,
                                  double intercept_scale, double *beta0, double *beta1, double *objective, double *info, int *flags,
                                  int *n_at_bound, long long *bad_row, int *bad_col) {
-    if (bad_row) *bad_row = -1;
-    if (bad_col) *bad_col = -1;
     if (n_at_bound) *n_at_bound = 0;
-    if (!Y || !codes || !size_factors || !dispersion || !far_end || !beta0 || !beta1 || !objective || !info || !flags)
-        return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
-    if (!(std::isfinite(prior_scale) && prior_scale > 0.0)) return fail(PILOT_OT_EINVAL, "prior_scale=%g must be positive and finite", prior_scale);
-    if (!(std::isfinite(intercept_scale) && intercept_scale > 0.0))
-        return fail(PILOT_OT_EINVAL, "intercept_scale=%g must be positive and finite", intercept_scale);
-    Design d;
-    if (int rc = make_design(m, codes, 2, size_factors, d)) return rc;
-    if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
-    for (int j = 0; j < n_genes; ++j)
-        if (!std::isfinite(far_end[j])) return fail(PILOT_OT_EINVAL, "far_end[%d]=%g must be finite", j, far_end[j]);
-    if (m > pilot::NB_MAX_SAMPLES)
-        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts and size factors are staged in LDS, at most %d", m, pilot::NB_MAX_SAMPLES);
-    const void *y;
-    long long y_ld;
-    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
-    DevDesign dd;
-    if (int rc = upload_design(d, dd)) return rc;
-    if (int rc = dtype == 0 ? shrink<float>(y, y_ld, (int)m, n_genes, dd, d.gstart[1], dispersion, far_end, prior_scale, intercept_scale, beta0,
-                                            beta1, objective, info, flags, bad_row, bad_col)
-                            : shrink<double>(y, y_ld, (int)m, n_genes, dd, d.gstart[1], dispersion, far_end, prior_scale, intercept_scale, beta0,
-                                             beta1, objective, info, flags, bad_row, bad_col))
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, true, codes, 2, dispersion, "counts and size factors"};
+    if (int rc = prologue(
+            c, !Y || !codes || !size_factors || !dispersion || !far_end || !beta0 || !beta1 || !objective || !info || !flags, bad_row, bad_col,
+            [&] {
+                if (int rc = positive_finite("prior_scale", prior_scale)) return rc;
+                return positive_finite("intercept_scale", intercept_scale);
+            },
+            [&] {
+                for (int j = 0; j < n_genes; ++j)
+                    if (!std::isfinite(far_end[j])) return fail(PILOT_OT_EINVAL, "far_end[%d]=%g must be finite", j, far_end[j]);
+                return PILOT_OT_OK;
+            }))
         return rc;
-    int at_bound = 0;
-    for (int j = 0; j < n_genes; ++j) at_bound += (flags[j] & pilot::NB_FLAG_AT_BOUND) != 0;
-    if (n_at_bound) *n_at_bound = at_bound;
+    if (int rc = by_dtype(dtype, [&](auto t) {
+            return shrink<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, c.dd, c.d.gstart[1], dispersion, far_end, prior_scale, intercept_scale, beta0,
+                                       beta1, objective, info, flags, bad_row, bad_col);
+        }))
+        return rc;
+    count_flag(flags, n_genes, pilot::NB_FLAG_AT_BOUND, n_at_bound);
     return PILOT_OT_OK;
 }
 
 PILOT_API int pilot_ot_nb_rlog(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *size_factors,
                                const double *dispersion, double prior_var, void *out, int out_is_device, long long ld_out,
                                double *intercept, int *steps, int *flags, int *n_not_converged, long long *bad_row, int *bad_col) {
-    if (bad_row) *bad_row = -1;
-    if (bad_col) *bad_col = -1;
     if (n_not_converged) *n_not_converged = 0;
-    if (!Y || !size_factors || !dispersion || !out || !intercept || !steps || !flags) return fail(PILOT_OT_EINVAL, "NULL pointer");
-    if (int rc = check_matrix(dtype, n_genes, ld)) return rc;
-    if (ld_out < n_genes) return fail(PILOT_OT_EINVAL, "ld_out=%lld is smaller than n_genes=%d", ld_out, n_genes);
-    if (int rc = check_samples(m, size_factors)) return rc;
-    if (!(std::isfinite(prior_var) && prior_var > 0.0)) return fail(PILOT_OT_EINVAL, "prior_var=%g must be positive and finite", prior_var);
-    if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
-    if (m > pilot::NB_MAX_SAMPLES)
-        return fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts, log size factors and coefficients are staged in LDS, at most %d", m,
-                    pilot::NB_MAX_SAMPLES);
-    const void *y;
-    long long y_ld;
-    if (int rc = pilot::stage_dense(Y, Y_is_device, pilot::elem_size(dtype), m, n_genes, ld, pilot::WS_NB_Y, &y, &y_ld)) return rc;
-    if (int rc = dtype == 0 ? rlog<float>(y, y_ld, (int)m, n_genes, size_factors, dispersion, prior_var, out, out_is_device, ld_out, intercept,
-                                          steps, flags, bad_row, bad_col)
-                            : rlog<double>(y, y_ld, (int)m, n_genes, size_factors, dispersion, prior_var, out, out_is_device, ld_out, intercept,
-                                           steps, flags, bad_row, bad_col))
+    // (the prologue gets no dispersions: this call has always refused a bad prior_var after the samples and before the dispersions)
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, false, nullptr, 1, nullptr, "counts, log size factors and coefficients"};
+    if (int rc = prologue(
+            c, !Y || !size_factors || !dispersion || !out || !intercept || !steps || !flags, bad_row, bad_col,
+            [&] { return ld_out < n_genes ? fail(PILOT_OT_EINVAL, "ld_out=%lld is smaller than n_genes=%d", ld_out, n_genes) : PILOT_OT_OK; },
+            [&] {
+                if (int rc = positive_finite("prior_var", prior_var)) return rc;
+                return check_dispersions(dispersion, n_genes, m);
+            }))
         return rc;
-    int bad = 0;
-    for (int j = 0; j < n_genes; ++j) bad += (flags[j] & pilot::NB_FLAG_NOT_CONVERGED) != 0;
-    if (n_not_converged) *n_not_converged = bad;
+    if (int rc = by_dtype(dtype, [&](auto t) {
+            return rlog<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, size_factors, dispersion, prior_var, out, out_is_device, ld_out, intercept, steps,
+                                     flags, bad_row, bad_col);
+        }))
+        return rc;
+    count_flag(flags, n_genes, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
     return PILOT_OT_OK;
 }

@@ -1263,39 +1263,74 @@ def nb_glm_limits():
     return int(_lib.load().pilot_ot_nb_glm_max_samples())
 
 
-def _nb_args(m, n_genes, codes, n_groups, size_factors):
-    """the design arguments of the two NB calls checked on the host: (codes int32, n_groups, size factors float64)"""
-    if isinstance(n_groups, bool) or int(n_groups) != n_groups:
-        raise ValueError("n_groups=%r must be an integer" % (n_groups,))
-    n_groups = int(n_groups)
+def _nb_blind_args(m, n_genes, size_factors, groups=None):
+    """the samples of an NB call checked on the host: the size factors as float64.  ``groups``: what a grouped call checks of its
+    own, between the shape and the size factors (which refusal comes first is behaviour)"""
     if n_genes < 1:
         raise ValueError("counts has no columns")
     if m < 2:
         raise ValueError("counts has %d rows: at least 2 samples" % m)
-    if not 2 <= n_groups <= m - 1:
-        raise ValueError("n_groups=%d must be in [2, m - 1 = %d]: a residual degree of freedom is needed" % (n_groups, m - 1))
-    codes = np.asarray(codes)
-    if codes.ndim != 1 or codes.size != m:
-        raise ValueError("codes has shape %s for %d samples" % (codes.shape, m))
-    if codes.dtype.kind not in "iu":
-        raise ValueError("codes must be integers, got %s" % codes.dtype)
-    if int(codes.min()) < 0 or int(codes.max()) >= n_groups:
-        raise ValueError("codes outside [0, %d)" % n_groups)
-    count = np.bincount(codes, minlength=n_groups)
-    if (count == 0).any():
-        raise ValueError("group %d has no sample" % int(np.flatnonzero(count == 0)[0]))
+    if groups is not None:
+        groups()
     sf = np.ascontiguousarray(size_factors, dtype=np.float64)
     if sf.shape != (m,):
         raise ValueError("size_factors has shape %s for %d samples" % (sf.shape, m))
     if not (np.isfinite(sf).all() and (sf > 0).all()):
         raise ValueError("size_factors must be positive and finite")
+    return sf
+
+
+def _nb_args(m, n_genes, codes, n_groups, size_factors):
+    """the design arguments of the grouped NB calls checked on the host: (codes int32, n_groups, size factors float64)"""
+    if isinstance(n_groups, bool) or int(n_groups) != n_groups:
+        raise ValueError("n_groups=%r must be an integer" % (n_groups,))
+    n_groups = int(n_groups)
+
+    def groups():
+        if not 2 <= n_groups <= m - 1:
+            raise ValueError("n_groups=%d must be in [2, m - 1 = %d]: a residual degree of freedom is needed" % (n_groups, m - 1))
+        c = np.asarray(codes)
+        if c.ndim != 1 or c.size != m:
+            raise ValueError("codes has shape %s for %d samples" % (c.shape, m))
+        if c.dtype.kind not in "iu":
+            raise ValueError("codes must be integers, got %s" % c.dtype)
+        if int(c.min()) < 0 or int(c.max()) >= n_groups:
+            raise ValueError("codes outside [0, %d)" % n_groups)
+        count = np.bincount(c, minlength=n_groups)
+        if (count == 0).any():
+            raise ValueError("group %d has no sample" % int(np.flatnonzero(count == 0)[0]))
+
+    sf = _nb_blind_args(m, n_genes, size_factors, groups)
     return np.ascontiguousarray(codes, dtype=np.int32), n_groups, sf
 
 
-def _nb_bad_count(err, bad_row, bad_col):
-    """the ValueError of a bad count with its position as attributes"""
-    err.row, err.col = int(bad_row.value), int(bad_col.value)
-    return err
+def _nb_dispersion_arg(dispersion, n_genes, m, shape_checked=False):
+    """one dispersion per gene as float64, each NaN (the gene is left out) or in [NB_MIN_DISP, nb_max_disp(m)].  ``shape_checked``:
+    the caller has refused a wrong shape in words of its own"""
+    alpha = np.ascontiguousarray(dispersion, dtype=np.float64)
+    if not shape_checked and alpha.shape != (n_genes,):
+        raise ValueError("dispersion has shape %s for %d genes" % (alpha.shape, n_genes))
+    given = alpha[~np.isnan(alpha)]
+    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(m)):
+        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(m)))
+    return alpha
+
+
+def _nb_sample_limit(name, m):
+    """``name``'s refusal of more samples than a gene can stage in LDS (the first call that loads the library)"""
+    limit = nb_glm_limits()
+    if m > limit:
+        raise NotImplementedError("%s: %d samples; a gene is staged in LDS, at most %d" % (name, m, limit))
+
+
+def _nb_call(fn, *args):
+    """``fn(*args, &bad_row, &bad_col)`` checked; the ValueError of a bad count carries its position as ``row`` and ``col``"""
+    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_int(-1)
+    try:
+        _lib.check(fn(*args, ctypes.byref(bad_row), ctypes.byref(bad_col)))
+    except ValueError as err:
+        err.row, err.col = int(bad_row.value), int(bad_col.value)
+        raise
 
 
 def nb_dispersions(counts, codes, n_groups, size_factors, log_prior_mean=None, prior_var=None, return_info=False):
@@ -1321,19 +1356,13 @@ def nb_dispersions(counts, codes, n_groups, size_factors, log_prior_mean=None, p
         prior_var = float(prior_var)
         if not (np.isfinite(prior_var) and prior_var > 0):
             raise ValueError("prior_var=%r must be positive and finite" % (prior_var,))
-    limit = nb_glm_limits()
-    if Y.rows > limit:
-        raise NotImplementedError("nb_dispersions: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    _nb_sample_limit("nb_dispersions", Y.rows)
     x, objective = np.empty(Y.cols), np.empty(Y.cols)
     fitted = np.empty((Y.cols, n_groups)) if return_info else None
-    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_int(-1)
-    try:
-        _lib.check(_lib.load().pilot_ot_nb_dispersions(
-            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), n_groups, _lib.dptr(sf),
-            None if log_prior_mean is None else _lib.dptr(log_prior_mean), 0.0 if prior_var is None else prior_var, _lib.dptr(x),
-            _lib.dptr(objective), None if fitted is None else _lib.dptr(fitted), ctypes.byref(bad_row), ctypes.byref(bad_col)))
-    except ValueError as err:
-        raise _nb_bad_count(err, bad_row, bad_col)
+    _nb_call(_lib.load().pilot_ot_nb_dispersions,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), n_groups, _lib.dptr(sf),
+             None if log_prior_mean is None else _lib.dptr(log_prior_mean), 0.0 if prior_var is None else prior_var, _lib.dptr(x),
+             _lib.dptr(objective), None if fitted is None else _lib.dptr(fitted))
     return (x, {"objective": objective, "fitted_mean": fitted}) if return_info else x
 
 
@@ -1347,12 +1376,7 @@ def nb_group_fits(counts, codes, n_groups, size_factors, dispersion, return_info
     ``n_not_converged``.  Errors as :func:`nb_dispersions` (no limit on the samples)."""
     Y = _dense_arg(counts, "counts", mode="strict")
     codes, n_groups, sf = _nb_args(Y.rows, Y.cols, codes, n_groups, size_factors)
-    alpha = np.ascontiguousarray(dispersion, dtype=np.float64)
-    if alpha.shape != (Y.cols,):
-        raise ValueError("dispersion has shape %s for %d genes" % (alpha.shape, Y.cols))
-    given = alpha[~np.isnan(alpha)]
-    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(Y.rows)):
-        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(Y.rows)))
+    alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
     q, w = np.empty((Y.cols, n_groups)), np.empty((Y.cols, n_groups))
     steps, flags = np.empty((Y.cols, n_groups), dtype=np.int32), np.empty((Y.cols, n_groups), dtype=np.int32)
     bad = ctypes.c_int(0)
@@ -1478,9 +1502,7 @@ def nb_shrink(counts, codes, size_factors, dispersion, far_end, prior_scale, int
     alpha, far = np.ascontiguousarray(dispersion, dtype=np.float64), np.ascontiguousarray(far_end, dtype=np.float64)
     if alpha.shape != (Y.cols,) or far.shape != (Y.cols,):
         raise ValueError("dispersion %s and far_end %s: one of each for %d genes" % (alpha.shape, far.shape, Y.cols))
-    given = alpha[~np.isnan(alpha)]
-    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(Y.rows)):
-        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(Y.rows)))
+    alpha = _nb_dispersion_arg(alpha, Y.cols, Y.rows, shape_checked=True)
     if not np.isfinite(far).all():
         raise ValueError("far_end must be finite")
     prior_scale, intercept_scale = float(prior_scale), float(intercept_scale)
@@ -1488,19 +1510,14 @@ def nb_shrink(counts, codes, size_factors, dispersion, far_end, prior_scale, int
         raise ValueError("prior_scale=%r must be positive and finite" % (prior_scale,))
     if not (np.isfinite(intercept_scale) and intercept_scale > 0):
         raise ValueError("intercept_scale=%r must be positive and finite" % (intercept_scale,))
-    limit = nb_glm_limits()
-    if Y.rows > limit:
-        raise NotImplementedError("nb_shrink: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    _nb_sample_limit("nb_shrink", Y.rows)
     b0, b1, objective, w = np.empty(Y.cols), np.empty(Y.cols), np.empty(Y.cols), np.empty((Y.cols, 2))
     raw = np.empty(Y.cols, dtype=np.int32)
-    at_bound, bad_row, bad_col = ctypes.c_int(0), ctypes.c_longlong(-1), ctypes.c_int(-1)
-    try:
-        _lib.check(_lib.load().pilot_ot_nb_shrink(
-            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), _lib.dptr(sf), _lib.dptr(alpha),
-            _lib.dptr(far), prior_scale, intercept_scale, _lib.dptr(b0), _lib.dptr(b1), _lib.dptr(objective), _lib.dptr(w),
-            _lib.iptr(raw), ctypes.byref(at_bound), ctypes.byref(bad_row), ctypes.byref(bad_col)))
-    except ValueError as err:
-        raise _nb_bad_count(err, bad_row, bad_col)
+    at_bound = ctypes.c_int(0)
+    _nb_call(_lib.load().pilot_ot_nb_shrink,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), _lib.dptr(sf), _lib.dptr(alpha),
+             _lib.dptr(far), prior_scale, intercept_scale, _lib.dptr(b0), _lib.dptr(b1), _lib.dptr(objective), _lib.dptr(w),
+             _lib.iptr(raw), ctypes.byref(at_bound))
     if not return_info:
         return b0, b1
     flags = raw & ((1 << _lib.NB_SHRINK_STEPS_SHIFT) - 1)
@@ -1558,20 +1575,6 @@ def nb_posterior_sd(beta1, w0, w1, prior_scale, intercept_scale=NB_INTERCEPT_SCA
 
 
 # ---- regularised log transform (K24; DESeq2's rlog(blind = TRUE) of pilotpy's compute_pseudobulk_PCA) ---------------------------
-def _nb_blind_args(m, n_genes, size_factors):
-    """the samples of the two calls without groups checked on the host: the size factors as float64"""
-    if n_genes < 1:
-        raise ValueError("counts has no columns")
-    if m < 2:
-        raise ValueError("counts has %d rows: at least 2 samples" % m)
-    sf = np.ascontiguousarray(size_factors, dtype=np.float64)
-    if sf.shape != (m,):
-        raise ValueError("size_factors has shape %s for %d samples" % (sf.shape, m))
-    if not (np.isfinite(sf).all() and (sf > 0).all()):
-        raise ValueError("size_factors must be positive and finite")
-    return sf
-
-
 def nb_dispersions_blind(counts, size_factors, return_info=False):
     """K24: :func:`nb_dispersions` for the design ``~ 1`` (DESeq2's ``blind = TRUE``): ONE group of all the samples, which that call
     refuses, and no prior -- ``mu_j = max(s_j * mean_i(c_i / s_i), 0.5)`` and the same six rounds of the 64-point grid on the
@@ -1580,17 +1583,11 @@ def nb_dispersions_blind(counts, size_factors, return_info=False):
     ``c / s`` over the samples, as the device summed it).  Errors as :func:`nb_dispersions`."""
     Y = _dense_arg(counts, "counts", mode="strict")
     sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
-    limit = nb_glm_limits()
-    if Y.rows > limit:
-        raise NotImplementedError("nb_dispersions_blind: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    _nb_sample_limit("nb_dispersions_blind", Y.rows)
     x, objective, base_mean = np.empty(Y.cols), np.empty(Y.cols), np.empty(Y.cols)
-    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_int(-1)
-    try:
-        _lib.check(_lib.load().pilot_ot_nb_dispersions_blind(
-            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(x), _lib.dptr(objective),
-            _lib.dptr(base_mean), ctypes.byref(bad_row), ctypes.byref(bad_col)))
-    except ValueError as err:
-        raise _nb_bad_count(err, bad_row, bad_col)
+    _nb_call(_lib.load().pilot_ot_nb_dispersions_blind,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(x), _lib.dptr(objective),
+             _lib.dptr(base_mean))
     return (x, {"objective": objective, "base_mean": base_mean}) if return_info else x
 
 
@@ -1646,28 +1643,18 @@ def nb_rlog(counts, size_factors, dispersion, prior_var, on_device=False, return
     float64 storage, from host and device matrices, and for a gene alone or in any batch.  Errors as :func:`nb_dispersions`."""
     Y = _dense_arg(counts, "counts", mode="strict")
     sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
-    alpha = np.ascontiguousarray(dispersion, dtype=np.float64)
-    if alpha.shape != (Y.cols,):
-        raise ValueError("dispersion has shape %s for %d genes" % (alpha.shape, Y.cols))
-    given = alpha[~np.isnan(alpha)]
-    if given.size and not (given.min() >= NB_MIN_DISP and given.max() <= nb_max_disp(Y.rows)):
-        raise ValueError("dispersion outside [%g, %g]" % (NB_MIN_DISP, nb_max_disp(Y.rows)))
+    alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
     if isinstance(prior_var, (str, bytes, bool)) or not np.isscalar(prior_var) or not (np.isfinite(prior_var) and prior_var > 0):
         raise ValueError("prior_var=%r must be positive and finite" % (prior_var,))
-    limit = nb_glm_limits()
-    if Y.rows > limit:
-        raise NotImplementedError("nb_rlog: %d samples; a gene is staged in LDS, at most %d" % (Y.rows, limit))
+    _nb_sample_limit("nb_rlog", Y.rows)
     out = _device_result(Y.rows, Y.cols) if on_device else np.empty((Y.rows, Y.cols), dtype=np.float64)
     intercept = np.empty(Y.cols)
     steps, flags = np.empty(Y.cols, dtype=np.int32), np.empty(Y.cols, dtype=np.int32)
-    bad, bad_row, bad_col = ctypes.c_int(0), ctypes.c_longlong(-1), ctypes.c_int(-1)
-    try:
-        _lib.check(_lib.load().pilot_ot_nb_rlog(
-            Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(alpha), float(prior_var),
-            ctypes.c_void_p(out.ptr if on_device else out.ctypes.data), int(bool(on_device)), Y.cols, _lib.dptr(intercept),
-            _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad), ctypes.byref(bad_row), ctypes.byref(bad_col)))
-    except ValueError as err:
-        raise _nb_bad_count(err, bad_row, bad_col)
+    bad = ctypes.c_int(0)
+    _nb_call(_lib.load().pilot_ot_nb_rlog,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(alpha), float(prior_var),
+             ctypes.c_void_p(out.ptr if on_device else out.ctypes.data), int(bool(on_device)), Y.cols, _lib.dptr(intercept),
+             _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad))
     return (out, {"intercept": intercept, "steps": steps, "flags": flags, "n_not_converged": bad.value}) if return_info else out
 
 

@@ -38,7 +38,7 @@ struct pilot_ot_plan {
     int timing;                       // 0 off
     long n_timed;                     // calls recorded so far
     long n_calls;                     // calls seen while timing is on (every `timing`-th one is recorded)
-    hipEvent_t ev[TIMING_RING][4];    // [slot]{main begin, main end, track begin, track end}
+    hipEvent_t ev[TIMING_RING][3];    // [slot]{main begin, main end = track begin, track end}
     // hipGraph replay of a repeated Sinkhorn call (pilot_ot_plan_enable_graph): the launch sequence of one call captured
     // on `gstream` and replayed on the caller's stream while the arguments stay the same
     int graph_mode;                   // 0 off

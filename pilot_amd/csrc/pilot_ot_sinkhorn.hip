@@ -87,7 +87,7 @@ PILOT_API int pilot_ot_plan_create(int N, int K, pilot_ot_plan **plan) {
     pl->flags_ws = nullptr;
     pl->timing = 0; pl->n_timed = 0; pl->n_calls = 0;
     pl->graph_mode = 0; pl->gkey_seen = 0; pl->gstream = nullptr; pl->gexec = nullptr;
-    for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 4; ++j) pl->ev[i][j] = nullptr;
+    for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 3; ++j) pl->ev[i][j] = nullptr;
     hipError_t e = hipGetDevice(&pl->device);
     if (e == hipSuccess) pl->n_cu = pilot::cu_count();
     const int kp = ((K + 31) / 32) * 32;
@@ -159,7 +159,7 @@ PILOT_API int pilot_ot_plan_destroy(pilot_ot_plan *pl) {
     if (pl->wide_rec) (void)hipFree(pl->wide_rec);
     if (pl->gexec) (void)hipGraphExecDestroy(pl->gexec);
     if (pl->gstream) (void)hipStreamDestroy(pl->gstream);
-    for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 4; ++j) if (pl->ev[i][j]) (void)hipEventDestroy(pl->ev[i][j]);
+    for (int i = 0; i < TIMING_RING; ++i) for (int j = 0; j < 3; ++j) if (pl->ev[i][j]) (void)hipEventDestroy(pl->ev[i][j]);
     delete pl;
     return PILOT_OT_OK;
 }
@@ -297,7 +297,7 @@ int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, cons
     hipEvent_t *ev = (pl->timing > 0 && (pl->n_calls++ % pl->timing) == 0) ? pl->ev[pl->n_timed % TIMING_RING] : nullptr;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     if (g.fast.run) HIP_TRY(launch(g.fast));
-    if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
+    if (ev) HIP_TRY(hipEventRecord(ev[1], s));     // (end of the main pass = begin of the tracking pass: one record)
     // (the fp16-split configuration tracks on the bf16-split operand block behind its own)
     p.img = static_cast<float *>(pl->img) + pilot::track_img_elems(cfg, RT);
     HIP_TRY(launch(g.track));
@@ -308,7 +308,7 @@ int run_grid(int cfg, pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, cons
         p.img = pl->img; p.fb_list = nullptr; p.fb_count = nullptr;
         HIP_TRY(launch(g.f64));
     }
-    if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
+    if (ev) { HIP_TRY(hipEventRecord(ev[2], s)); ++pl->n_timed; }
     if (sw.debug & pilot::DBG_NO_NAN_PASS) return PILOT_OT_OK;
     return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err, d_flags,
                        s, ctrl, pl->nan_list, slot(pilot::CTRL_NAN_LEN), slot(pilot::CTRL_NAN_HEAD));
@@ -358,9 +358,9 @@ int run_wide(pilot_ot_plan *pl, const pilot::SinkhornSwitches &sw, const double 
     const int tiles = (n_pairs + 15) / 16;
     int wgs = pl->n_cu < tiles ? pl->n_cu : tiles;            // one 512-thread workgroup per CU (230 VGPRs: two waves per SIMD)
     HIP_TRY(pilot::launch_wide(dim3(wgs), s, p, pl->wide_rec));
-    if (ev) { HIP_TRY(hipEventRecord(ev[1], s)); HIP_TRY(hipEventRecord(ev[2], s)); }
+    if (ev) HIP_TRY(hipEventRecord(ev[1], s));     // (end of the main pass = begin of the tracking pass: one record)
     HIP_TRY(pilot::launch_wide_value(dim3(pilot::clamp_wgs(pl->n_cu, 2, tiles)), s, p, pl->wide_rec));
-    if (ev) { HIP_TRY(hipEventRecord(ev[3], s)); ++pl->n_timed; }
+    if (ev) { HIP_TRY(hipEventRecord(ev[2], s)); ++pl->n_timed; }
     return run_generic(pl, sw, d_P, d_M, reg, num_iter_max, stop_thr, tau, check_period, row_begin, n_rows, row_step, d_emd, d_iters, d_err,
                        d_flags, s, pl->ctrl, pl->nan_list, pl->ctrl + pilot::CTRL_NAN_LEN, pl->ctrl + pilot::CTRL_NAN_HEAD);
 }
@@ -516,9 +516,9 @@ PILOT_API int pilot_ot_plan_enable_timing(pilot_ot_plan *pl, int enable) {
     if (!pl) return fail(PILOT_OT_EINVAL, "plan is NULL");
     if (enable)
         for (int i = 0; i < TIMING_RING; ++i)
-            for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 3; ++j)
                 if (!pl->ev[i][j]) HIP_TRY(hipEventCreate(&pl->ev[i][j]));
-    pl->timing = enable > 0 ? enable : 0;       // n > 1: every n-th call is timed (four event records cost a 0.7 ms call 2 %)
+    pl->timing = enable > 0 ? enable : 0;       // n > 1: every n-th call is timed (the event records cost a 0.7 ms call 2 %)
     pl->n_timed = 0; pl->n_calls = 0;
     return PILOT_OT_OK;
 }
@@ -531,7 +531,7 @@ PILOT_API int pilot_ot_plan_kernel_times(pilot_ot_plan *pl, int max_n, float *ma
         const long call = pl->n_timed - n + t;
         hipEvent_t *ev = pl->ev[call % TIMING_RING];
         HIP_TRY(hipEventElapsedTime(&main_ms[t], ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&track_ms[t], ev[2], ev[3]));
+        HIP_TRY(hipEventElapsedTime(&track_ms[t], ev[1], ev[2]));
     }
     *n_out = (int)n;
     return PILOT_OT_OK;

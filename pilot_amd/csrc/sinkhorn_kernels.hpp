@@ -645,6 +645,9 @@ template <int RT, int NP> struct SplitImage { u32x4_t a[NP][split_kblocks(RT)][R
 #ifndef PILOT_DEFER_HANDOVER
 #define PILOT_DEFER_HANDOVER 1
 #endif
+#ifndef PILOT_BOUNDARY_DRAW
+#define PILOT_BOUNDARY_DRAW 3   // a refill that outruns the wave's batch draws the next one in the same iteration from this many row-tiles on (profiles/r08/loop_waits.md)
+#endif
 #ifndef PILOT_E2_PACKED
 #define PILOT_E2_PACKED 1     // (round 6: the lane's squared error two slots per v_pk_fma_f32; instructions -12 per error test, time unchanged)
 #endif
@@ -1342,6 +1345,13 @@ sinkhorn_stream_kernel(GridParams p) {
     int qc = wave_id % QUEUE_SHARDS, q_tries = 0;                       // (sharded queue: the counter this wave draws from)
     const int q_max_tries = n_tile_waves >= QUEUE_SHARDS ? 4 : QUEUE_SHARDS;
     const bool hand_all_over = C::HALF && p.unequal && *p.unequal != 0;
+    // row-tile t of a pair's a or b (16-byte loads: a lane's slots are contiguous).  fp16-split configuration: where only slot 0 of the last
+    // row-tile is live (dead() above) only that slot is loaded: the compiler keeps other values in the three registers nobody reads, and a 16-byte load into
+    // them made the wave wait for ALL its loads before the next write to one of those values -- inside the refill block.
+    auto load_row = [&](const T *row, int t, acc_t &x) {
+        if (C::HALF && TV > 0 && t == RT - 1) x[0] = row[t * NGRP * NREG];
+        else load_regs<C>(row + t * NGRP * NREG, x);
+    };
     for (;;) {
         // ---- (re)fill columns: a new pair starts with u = v = 1/K and ACC = G^T u0 (table) ----------
         // (round 6, tried and dropped: refills -- and with them the error checks, which follow a refill by 1 + 20 n updates -- only on
@@ -1353,7 +1363,32 @@ sinkhorn_stream_kernel(GridParams p) {
         // registers or scratch and two lose a wave per SIMD -- profiles/split_tile/stream_feed_resources.diff)
         const unsigned long long wmask = ballot_b(want) & colmask;
         if (wmask) {
-            if (res_next >= res_end && !exhausted) {
+            // SPAN (fp16-split configuration from PILOT_BOUNDARY_DRAW row-tiles on): items go to the wanting columns from the wave's
+            // current batch first; where that batch has fewer left than columns that want one (none at all, usually) and the queue has
+            // not ended, the next batch is drawn HERE, once, and serves the remaining columns in the same iteration.  Otherwise the draw
+            // waits for the iteration after the one that emptied the batch: the columns that met the end of a batch idle one update and
+            // the wave runs the refill block twice.  Never earlier than that: a wave that holds an undrawn batch when the queue ends
+            // runs on alone.  (Not below three row-tiles: c2's kernel measured 3 % slower with it although none of its waves ever holds
+            // a second batch and its ISA differs by two instructions in front of the loop -- the cause is NOT understood, the
+            // threshold is that measurement and nothing more; c3 -1.2 %.  The other configurations keep the feed they had, copied
+            // below under !SPAN rather than shared through a helper: their register counts and scratch are at their limits, and the
+            // shared form cost 30 of them 16 bytes of scratch each, profiles/r08/stream_resources.diff.)
+            constexpr bool SPAN = C::HALF && RT >= PILOT_BOUNDARY_DRAW;
+            int n_want = 0, rank = 0, avail = 0, qsel = 0, isel = 0, jsel = 0;
+            bool take = false;
+            if constexpr (SPAN) {
+                n_want = (int)__popcll(wmask);
+                rank = (int)__popcll(wmask & ((1ull << col) - 1ull));
+                avail = res_end - res_next;
+                take = want && rank < avail;
+                if (avail > 0) {                                                     // (wave-uniform)
+                    const int bsel = 4 * ((res_next + rank - res_base) & (TILE - 1));
+                    qsel = __builtin_amdgcn_ds_bpermute(bsel, qbatch);               // (every lane takes part)
+                    isel = __builtin_amdgcn_ds_bpermute(bsel, ibatch), jsel = __builtin_amdgcn_ds_bpermute(bsel, jbatch);
+                    res_next = __builtin_amdgcn_readfirstlane(res_next + (n_want < avail ? n_want : avail));
+                }
+            }
+            if ((SPAN ? n_want > avail : res_next >= res_end) && !exhausted) {     // (wave-uniform)
                 // A wave's FIRST batch is the one of its own number (behind the exact duplicates the solo waves take), the later
                 // ones come from the device-wide counter, which therefore hands out positions behind the statically dealt
                 // part: the 2048 waves of a launch no longer start with 2048 atomics on one address (11.4 ns each, serial:
@@ -1394,16 +1429,28 @@ sinkhorn_stream_kernel(GridParams p) {
                 const int qv = bi < n_items ? qbatch : 0;
                 ibatch = p.row_begin + (qv / N) * p.row_step;
                 jbatch = qv % N;
+                if constexpr (SPAN) {
+                    // the columns the old batch did not reach: ranks avail .. of the wanting ones, items 0 .. of the new batch
+                    const int rank2 = rank - avail, avail2 = res_end - res_next, left = n_want - avail;
+                    const bool take2 = want && !take && rank2 < avail2;
+                    const int bsel = 4 * ((res_next + (rank2 > 0 ? rank2 : 0) - res_base) & (TILE - 1));
+                    const int q2 = __builtin_amdgcn_ds_bpermute(bsel, qbatch);       // (every lane takes part)
+                    const int i2 = __builtin_amdgcn_ds_bpermute(bsel, ibatch), j2 = __builtin_amdgcn_ds_bpermute(bsel, jbatch);
+                    if (take2) { qsel = q2; isel = i2; jsel = j2; take = true; }
+                    res_next = __builtin_amdgcn_readfirstlane(res_next + (left < avail2 ? left : avail2));
+                }
             }
-            const int avail = res_end - res_next;
-            const int n_want = (int)__popcll(wmask);
-            const int rank = (int)__popcll(wmask & ((1ull << col) - 1ull));
-            const int item = res_next + rank;
-            const bool take = want && rank < avail;
-            const int bsel = 4 * ((item - res_base) & (TILE - 1));
-            const int qsel = __builtin_amdgcn_ds_bpermute(bsel, qbatch);     // (every lane takes part)
-            const int isel = __builtin_amdgcn_ds_bpermute(bsel, ibatch), jsel = __builtin_amdgcn_ds_bpermute(bsel, jbatch);
-            res_next = __builtin_amdgcn_readfirstlane(res_next + (n_want < avail ? n_want : avail));
+            if constexpr (!SPAN) {
+                avail = res_end - res_next;
+                n_want = (int)__popcll(wmask);
+                rank = (int)__popcll(wmask & ((1ull << col) - 1ull));
+                const int item = res_next + rank;
+                take = want && rank < avail;
+                const int bsel = 4 * ((item - res_base) & (TILE - 1));
+                qsel = __builtin_amdgcn_ds_bpermute(bsel, qbatch);     // (every lane takes part)
+                isel = __builtin_amdgcn_ds_bpermute(bsel, ibatch), jsel = __builtin_amdgcn_ds_bpermute(bsel, jbatch);
+                res_next = __builtin_amdgcn_readfirstlane(res_next + (n_want < avail ? n_want : avail));
+            }
             if (want && !take && exhausted) {   // no work left: the slot goes dark
                 want = false;
 #pragma unroll
@@ -1425,10 +1472,14 @@ sinkhorn_stream_kernel(GridParams p) {
                 q = qsel;
                 const int i = isel, j = jsel;
                 const T *pa = Pt + (size_t)i * KP + grp * NREG, *pb = Pt + (size_t)j * KP + grp * NREG;
+                // Memory operations return in issue order and a wait counts the ones still out, so each of these loads can be waited for
+                // where it is first used (v = b / acc needs b's row-tile t and, in this order, a's: a wait for 2 t + 2 of the 9) -- as long
+                // as nothing forces a wait for all of them: see load_row and the reload behind the parked flush.  (All of b, then a -- the
+                // order of first use -- measured slower: c3 kernel 0.5845 vs 0.5785 ms, profiles/r08/loop_waits.md.)
 #pragma unroll
                 for (int t = 0; t < RT; ++t) {
-                    load_regs<C>(pa + t * NGRP * NREG, A[t]);          // 16-byte loads: a lane's slots are contiguous
-                    load_regs<C>(pb + t * NGRP * NREG, B[t]);
+                    load_row(pa, t, A[t]);
+                    load_row(pb, t, B[t]);
                 }
                 thr = Pt[(size_t)N * KP + j];                 // stop threshold of column patient j (prep: f32 floor folded in; HALF: scaled copy)
 #pragma unroll
@@ -1723,9 +1774,23 @@ sinkhorn_stream_kernel(GridParams p) {
                                 if constexpr (!C::HALF) load_regs<C>(park + t * NREG * WAVE, U[t]);
 #pragma unroll
                                 for (int r = 0; r < NREG; ++r) { A[t][r] = T(0); B[t][r] = T(0); }
+                                if constexpr (!C::HALF) {
+                                    if (active) {
+                                        load_regs<C>(pa + t * NGRP * NREG, A[t]);
+                                        load_regs<C>(pb + t * NGRP * NREG, B[t]);
+                                    }
+                                }
+                            }
+                            // (fp16-split configuration: one block, b first.  These loads are still out when the next update starts, and the
+                            // wait the compiler puts in front of v = b / acc is the strictest one over every way into it -- with a and b
+                            // interleaved under a condition per row-tile, one way had b's first row-tile as the last load issued: a wait
+                            // for everything)
+                            if constexpr (C::HALF) {
                                 if (active) {
-                                    load_regs<C>(pa + t * NGRP * NREG, A[t]);
-                                    load_regs<C>(pb + t * NGRP * NREG, B[t]);
+#pragma unroll
+                                    for (int t = 0; t < RT; ++t) load_row(pb, t, B[t]);
+#pragma unroll
+                                    for (int t = 0; t < RT; ++t) load_row(pa, t, A[t]);
                                 }
                             }
                             if constexpr (C::HALF) product_h(a_gt.img, PU, ACC);

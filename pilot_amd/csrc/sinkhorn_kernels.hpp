@@ -651,6 +651,18 @@ template <int RT, int NP> struct SplitImage { u32x4_t a[NP][split_kblocks(RT)][R
 #ifndef PILOT_E2_PACKED
 #define PILOT_E2_PACKED 1     // (round 6: the lane's squared error two slots per v_pk_fma_f32; instructions -12 per error test, time unchanged)
 #endif
+#ifndef PILOT_SCALAR_QUOT
+#define PILOT_SCALAR_QUOT 1   // (round 9: the quotient multiplies of the fp16-split update as single v_mul_f32; c3 kernel 0.5694 -> 0.5563 ms, c2 unchanged)
+#endif
+// a * b as ONE v_mul_f32.  The SLP vectoriser pairs the quotient multiplies of adjacent slots (v = b rcp(acc), u = a rcp(acc)) into
+// v_pk_mul_f32 -- 9 of them per update at four row-tiles -- and a packed f32 instruction beside MFMAs holds the SIMD's vector issue for
+// longer than the two plain ones it replaces: 9 instructions more per update and 2 % less time (profiles/r09/loop_stalls.md).  The
+// empty asm hides the product from the vectoriser and orders nothing; an IEEE multiply is the same either way, so are the bits.
+template <bool UNPACK> __device__ inline float mul_unpacked(float a, float b) {
+    float x = a * b;
+    if constexpr (UNPACK) asm("" : "+v"(x));
+    return x;
+}
 template <class C, int RT>
 __device__ inline void panel_product_pieces_regs(const SplitImage<RT, C::NP> &A, const SplitPanel<RT, C::NP> &B,
                                                  typename C::acc_t (&OUT)[RT], const typename C::acc_t &last_init) {
@@ -1525,6 +1537,9 @@ sinkhorn_stream_kernel(GridParams p) {
 
         T mx = T(0);
         if constexpr (C::HALF) {
+            // (one v_mul_f32 per quotient up to four row-tiles, see mul_unpacked; from five on the kernels spill, and the extra live values
+            // cost the seven-row-tile ones 16 bytes of scratch more: they keep the packed form, profiles/r09/stream_resources.diff)
+            constexpr bool QUOT1 = PILOT_SCALAR_QUOT && RT <= 4;
             // ---- v = b / (G^T u), u = a / (G v): quotients straight into the pieces the products read ----
             // (the f32 quotients are temporaries; V is read again only by the marginal error of an update that ends with a
             // test -- small scaled values keep ABSOLUTE precision as pieces, which is all a product needs, but
@@ -1532,7 +1547,7 @@ sinkhorn_stream_kernel(GridParams p) {
 #pragma unroll
             for (int t = 0; t < RT; ++t)
 #pragma unroll
-                for (int r = 0; r < NREG; ++r) V[t][r] = dead(t, r) ? T(0) : B[t][r] * M::rcp(ACC[t][r]);
+                for (int r = 0; r < NREG; ++r) V[t][r] = dead(t, r) ? T(0) : T(mul_unpacked<QUOT1>(float(B[t][r]), float(M::rcp(ACC[t][r]))));
             quot_panel(V, PV);
             // max(v) over the leading pieces, two elements per instruction; PV is dead once the product below is issued
             unsigned int m2 = 0u;
@@ -1555,7 +1570,7 @@ sinkhorn_stream_kernel(GridParams p) {
 #pragma unroll
                 for (int t = 0; t < RT; ++t)
 #pragma unroll
-                    for (int r = 0; r < NREG; ++r) X[t][r] = dead(t, r) ? T(0) : A[t][r] * M::rcp(ACC[t][r]);
+                    for (int r = 0; r < NREG; ++r) X[t][r] = dead(t, r) ? T(0) : T(mul_unpacked<QUOT1>(float(A[t][r]), float(M::rcp(ACC[t][r]))));
                 quot_panel(X, PU);
             }
             // ... joined by max(u) (a NaN piece makes the maximum NaN and the comparison below false: the pair is caught by the

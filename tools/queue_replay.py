@@ -10,6 +10,7 @@ any pair -- "tile-updates" -- against the ideal sum(iters) / 16.  The replay nee
             duplicates 47, higher buckets first, natural order inside a bucket (the device's order inside a bucket varies from
             run to run)
   natural   row-major
+  dupfirst  exact duplicates first, then row-major: what is left of the key without the order pass
   perfect   longest pair first (not available before the pairs have run: the bound, not a proposal)
   a function key(P, M) -> (N, N) array, larger first (--key-func FILE.py:NAME, or replay(..., order=order_of(values)))
 
@@ -17,6 +18,10 @@ Queue model, as in the kernel: wave w takes batch w as its first (static) batch,
 counter in the order the waves ask (waves step in lockstep here, lower wave first within a step); a column that wants a pair
 takes the next item of the wave's batch; when the batch has fewer items left than columns that want one, the next batch is
 drawn in the same step (--late-draw: in the next step, the kernel before profiles/r08) and never earlier.
+
+--merge-within N models a consolidated drain (not built: profiles/r09/loop_stalls.md): after the refills of a step, a wave that has
+seen the queue's end hands ALL its live columns to another such wave among the N consecutive waves of its workgroup (N = 4) whenever
+they fit into that wave's empty columns, the wave with the fewest live columns giving first, to the fullest wave that can take them.
 
 Prints: tile-updates executed, the ideal, the excess, the makespan (steps until the last wave is done), the mean finish
 step of a wave, and how many refills took items of two batches in one step (`spans`; 0 with --late-draw) out of how many
@@ -56,7 +61,7 @@ def order_of(values):
     return np.argsort(-v.astype(np.float64), kind="stable")
 
 
-def replay(iters, order, n_waves=2048, late_draw=False):
+def replay(iters, order, n_waves=2048, late_draw=False, merge_within=0):
     """-> dict(executed, ideal, excess, makespan, mean_finish).  iters: update count per pair; order: pair numbers in queue order."""
     it = np.asarray(iters).reshape(-1).astype(np.int64)[np.asarray(order)]
     n = it.size
@@ -68,7 +73,7 @@ def replay(iters, order, n_waves=2048, late_draw=False):
     dry = np.zeros(n_waves, dtype=bool)                     # the wave has seen the queue's end
     head = min(n_waves, n_batches)                          # next batch of the counter (behind the statically dealt ones)
     finish = np.zeros(n_waves, dtype=np.int64)
-    executed, step, spans, later_draws = 0, 0, 0, 0
+    executed, step, spans, later_draws, merges = 0, 0, 0, 0, 0
 
     def draw(w):
         nonlocal head, later_draws
@@ -105,6 +110,21 @@ def replay(iters, order, n_waves=2048, late_draw=False):
                 cols = cols[k:]
                 if late_draw and not drawn:       # the old kernel: the batch ran out under this refill, the draw waits a step
                     break
+        if merge_within > 1 and dry.any():
+            live = (left > 0).sum(1)
+            for g in np.unique(np.nonzero(dry & (live > 0) & (live < TILE))[0] // merge_within):
+                ws = [w for w in range(g * merge_within, min((g + 1) * merge_within, n_waves)) if dry[w] and 0 < live[w] < TILE]
+                for d in sorted(ws, key=lambda w: live[w]):                     # the giver: fewest live columns first
+                    takers = [w for w in ws if w != d and live[w] > 0 and live[w] + live[d] <= TILE]
+                    if not live[d] or not takers:
+                        continue
+                    t = max(takers, key=lambda w: live[w])
+                    free = np.nonzero(left[t] == 0)[0][:live[d]]
+                    left[t, free] = left[d][left[d] > 0]
+                    left[d] = 0
+                    live[t] += live[d]
+                    live[d] = 0
+                    merges += 1
         busy = (left > 0).any(1)
         if not busy.any():
             break
@@ -114,29 +134,32 @@ def replay(iters, order, n_waves=2048, late_draw=False):
         np.subtract(left, 1, out=left, where=left > 0)
     ideal = it.sum() / TILE
     return dict(executed=executed, ideal=float(ideal), excess=executed / ideal - 1.0, makespan=step, mean_finish=float(finish.mean()),
-                spans=spans, later_draws=later_draws)
+                spans=spans, later_draws=later_draws, merges=merges)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("iters", help="iters.npy of bench.py --dump-outputs (any shape, row-major pair numbers)")
     ap.add_argument("--config", default="c3", help="synthetic config the dump came from (for the key order)")
-    ap.add_argument("--order", nargs="+", default=["key", "natural", "perfect"], choices=["key", "natural", "perfect"])
+    ap.add_argument("--order", nargs="+", default=["key", "natural", "perfect"], choices=["key", "natural", "dupfirst", "perfect"])
     ap.add_argument("--key-func", default=None, metavar="FILE.py:NAME", help="a further order: key(P, M) -> (N, N), larger first")
     ap.add_argument("--waves", type=int, default=2048, help="waves of the launch (256 CUs x 4 SIMDs x 2)")
     ap.add_argument("--late-draw", action="store_true", help="draw a batch in the step after the one that ran out")
+    ap.add_argument("--merge-within", type=int, default=0, metavar="N",
+                    help="dry waves hand their live columns to another dry wave among the N waves of their workgroup (0: off)")
     args = ap.parse_args()
     iters = np.load(args.iters)
     orders = {}
     P = M = None
-    if "key" in args.order or args.key_func:
+    if "key" in args.order or "dupfirst" in args.order or args.key_func:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
         from pilot_amd.synthetic import CONFIGS, make_problem
         P, M = make_problem(**CONFIGS[args.config])
         if P.shape[0] ** 2 != iters.size:
             sys.exit("iters holds %d pairs, config %s has %d" % (iters.size, args.config, P.shape[0] ** 2))
     for o in args.order:
-        orders[o] = (order_of(l1_bucket_key(P)) if o == "key" else np.arange(iters.size) if o == "natural" else order_of(iters))
+        orders[o] = (order_of(l1_bucket_key(P)) if o == "key" else order_of(l1_bucket_key(P) == ORDER_NB - 1) if o == "dupfirst"
+                     else np.arange(iters.size) if o == "natural" else order_of(iters))
     if args.key_func:
         path, name = args.key_func.rsplit(":", 1)
         spec = importlib.util.spec_from_file_location("queue_replay_key", path)
@@ -145,10 +168,13 @@ def main():
         orders[name] = order_of(getattr(mod, name)(P, M))
     it = iters.reshape(-1)
     print("%d pairs, mean %.2f updates, max %d; %d waves, draw in the %s step" % (it.size, it.mean(), it.max(), args.waves, "next" if args.late_draw else "same"))
-    print("%-10s %12s %12s %8s %9s %12s %8s %12s" % ("order", "executed", "ideal", "excess", "makespan", "mean finish", "spans", "later draws"))
+    if args.merge_within > 1:
+        print("dry waves merge within groups of %d" % args.merge_within)
+    print("%-10s %12s %12s %8s %9s %12s %8s %12s %8s" % ("order", "executed", "ideal", "excess", "makespan", "mean finish", "spans", "later draws", "merges"))
     for name, order in orders.items():
-        r = replay(it, order, args.waves, args.late_draw)
-        print("%-10s %12d %12.1f %7.2f%% %9d %12.1f %8d %12d" % (name, r["executed"], r["ideal"], 100 * r["excess"], r["makespan"], r["mean_finish"], r["spans"], r["later_draws"]))
+        r = replay(it, order, args.waves, args.late_draw, args.merge_within)
+        print("%-10s %12d %12.1f %7.2f%% %9d %12.1f %8d %12d %8d"
+              % (name, r["executed"], r["ideal"], 100 * r["excess"], r["makespan"], r["mean_finish"], r["spans"], r["later_draws"], r["merges"]))
 
 
 if __name__ == "__main__":

@@ -679,6 +679,35 @@ int pilot_ot_nb_rlog(const void *Y, int Y_is_device, int dtype, long long m, int
                      const double *dispersion, double prior_var, void *out, int out_is_device, long long ld_out, double *intercept,
                      int *steps, int *flags, int *n_not_converged, long long *bad_row, int *bad_col);
 
+/* pilot_ot_nb_cooks (K25): the Cook's distances behind the outlier handling of `DESeq(dds)` and `results(dds)`
+ * (plot/pseudobulk_DE_analysis.py:140-145): replaceOutliers and the cooksCutoff filter.  THIS LIBRARY'S STATEMENT, unpinned
+ * (restated in tests/nb_cooks_restatement.py).  Y, codes, n_groups = k, size_factors, dtype, ld as
+ * pilot_ot_nb_group_fits; dispersion: the gene's FINAL dispersion alpha (host; NaN leaves the gene out); q: n_genes x k, that call's
+ * fits at it.  With c = rint(Y), q_j = c_j / s_j and tm(x, d) the mean of the sorted x without its d lowest and d highest values
+ * (R's mean(x, trim = r) with d = floor(n r)), per gene:
+ *     trimmed_base = tm(q of all m samples, floor(m / 5))
+ *     per group of n_g >= 3 samples, (r, scale) = (1/3, 2.04) for n_g <= 3, (1/4, 1.86) for n_g <= 23, else (1/8, 1.51) and
+ *     d = floor(n_g r):    v_g = scale tm((q_g - tm(q_g, d))^2, d)
+ *     alpha_robust = max((max_g v_g - mean_j q_j) / (mean_j q_j)^2, 0.04)
+ *     mu_j = max(s_j q[g(j)], minmu),  w_j = mu_j / (1 + alpha mu_j),  h_j = w_j / sum_{i in g(j)} w_i
+ *     D_j = (c_j - mu_j)^2 / (mu_j + alpha_robust mu_j^2)  h_j / (k (1 - h_j)^2),    NaN where n_g(j) = 1
+ *     max_cooks = max of D_j over the samples of groups with n_g >= 3; arg_max the lowest sample index that attains it;
+ *     n_above = #{j: c_j > c_arg_max};  n_replace = #{j: D_j > cutoff and n_g(j) >= min_replace}
+ * Without a group of n_g >= 3: alpha_robust = max_cooks = NaN, every D_j NaN, arg_max = -1, n_above = n_replace = 0 (trimmed_base
+ * is still computed).  A gene of zeros or with a NaN dispersion: NaN in every float result, arg_max = -1, counts 0.
+ * One wave per gene; the order statistics by a bitonic sort in LDS; every sum a per-lane partial in sorted-sample order closed by
+ * one fixed butterfly.  Same bits as stated above for the K22 calls, and for a gene alone or in any batch.
+ * Out (host, n_genes): alpha_robust, max_cooks, arg_max, n_above, n_replace, trimmed_base.  D: nullable; m x n_genes float64 with
+ * leading dimension ld_D >= n_genes, on the host or in HBM (D_is_device), D[j, gene] = D_j.
+ * PILOT_OT_EINVAL (before any HIP call): the cases of pilot_ot_nb_group_fits, a cutoff not positive and finite, min_replace < 3,
+ * ld_D < n_genes with a D, a q not positive and finite where the gene's dispersion is not NaN; after the check pass a negative or
+ * non-finite count (*bad_row / *bad_col as pilot_ot_nb_dispersions).  PILOT_OT_ENOTSUP: m > pilot_ot_nb_glm_max_samples() (a gene's
+ * counts, normalised counts and the sort buffer are staged in LDS: 8 (2 m + P) bytes, P the power of two >= m). */
+int pilot_ot_nb_cooks(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes, int n_groups,
+                      const double *size_factors, const double *dispersion, const double *q, double cutoff, int min_replace,
+                      double *alpha_robust, double *max_cooks, int *arg_max, int *n_above, int *n_replace, double *trimmed_base, void *D,
+                      int D_is_device, long long ld_D, long long *bad_row, int *bad_col);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

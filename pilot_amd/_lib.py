@@ -55,7 +55,7 @@ SYMBOLS = [
     "pilot_ot_rank_sums", "pilot_ot_csr_rank_sums", "pilot_ot_rank_sums_wave_max", "pilot_ot_rank_sums_wg_max",
     "pilot_ot_rank_sums_sort_tile",
     "pilot_ot_nb_dispersions", "pilot_ot_nb_group_fits", "pilot_ot_nb_glm_max_samples", "pilot_ot_nb_shrink",
-    "pilot_ot_nb_dispersions_blind", "pilot_ot_nb_rlog",
+    "pilot_ot_nb_dispersions_blind", "pilot_ot_nb_rlog", "pilot_ot_nb_cooks",
     "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain", "pilot_ot_leiden",
     "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
     "pilot_ot_elastic_fit_batch", "pilot_ot_point_moments", "pilot_ot_tree_projection",
@@ -203,6 +203,8 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_nb_dispersions_blind.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, dp, dp, dp, dp, llp, ip]
     L.pilot_ot_nb_rlog.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, dp, dp, c_dbl, c_vp, c_int,
                                    ctypes.c_longlong, dp, ip, ip, ip, llp, ip]
+    L.pilot_ot_nb_cooks.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, dp, dp, dp, c_dbl, c_int,
+                                    dp, dp, ip, ip, ip, dp, c_vp, c_int, ctypes.c_longlong, llp, ip]
     L.pilot_ot_csr_pca.argtypes = [c_vp, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_pca.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_knn_rows.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, ctypes.c_longlong,

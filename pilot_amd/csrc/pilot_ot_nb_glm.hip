@@ -1,5 +1,5 @@
 // C ABI of the negative-binomial GLM for a one-factor design (include/pilot_ot.h, section "negative-binomial GLM"; kernels:
-// nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
+// nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp, nb_cooks_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
 // codes, size factors, dispersions and the results are host arrays.  The host orders the samples by group once per call.
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "abi_common.hpp"
+#include "nb_cooks_kernel.hpp"
 #include "nb_glm_kernels.hpp"
 #include "nb_rlog_kernel.hpp"
 #include "nb_shrink_kernel.hpp"
@@ -201,6 +202,37 @@ int rlog(const void *y, long long ld, int m, int n_genes, const double *sf, cons
     return PILOT_OT_OK;
 }
 
+template <typename T>
+int cooks(const void *y, long long ld, int m, int n_genes, int k, const DevDesign &dd, const double *dispersion, const double *q, double cutoff,
+          int min_replace, double *alpha_robust, double *max_cooks, int *arg_max, int *n_above, int *n_replace, double *trimmed_base, void *D,
+          int D_is_device, long long ld_D, long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    const size_t G = (size_t)n_genes, M = (size_t)m, n_q = G * (size_t)k;
+    size_t P = 1;                                            // the sort buffer: the power of two >= m
+    while (P < M) P <<= 1;
+    double *d_in, *d_out;                                    // dispersion | q;  the three double results | packed D for a host D
+    int *d_int;
+    HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G + n_q, &d_in));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, 3 * G + (D && !D_is_device ? M * G : 0), &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 3 * G, &d_int));
+    HIP_TRY(hipMemcpy(d_in, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in + G, q, sizeof(double) * n_q, hipMemcpyHostToDevice));
+    double *d_D = !D ? nullptr : (D_is_device ? static_cast<double *>(D) : d_out + 3 * G);
+    const long long ld_dev = D_is_device ? ld_D : (long long)n_genes;
+    if (int rc = launch_wave_per_gene(pilot::nb_cooks_kernel<T>, n_genes, 2 * M + P, static_cast<const T *>(y), ld, m, k, dd.order, dd.gof, dd.ss,
+                                      dd.gstart, d_in, d_in + G, cutoff, min_replace, n_genes, d_out, d_int, d_D, ld_dev))
+        return rc;
+    HIP_TRY(hipMemcpy(alpha_robust, d_out, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(max_cooks, d_out + G, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(trimmed_base, d_out + 2 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(arg_max, d_int, sizeof(int) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_above, d_int + G, sizeof(int) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_replace, d_int + 2 * G, sizeof(int) * G, hipMemcpyDeviceToHost));
+    if (D && !D_is_device)
+        HIP_TRY(hipMemcpy2D(D, sizeof(double) * (size_t)ld_D, d_D, sizeof(double) * G, sizeof(double) * G, M, hipMemcpyDeviceToHost));
+    return PILOT_OT_OK;
+}
+
 // a dispersion is NaN (the gene is left out) or within [minDisp, maxDisp]
 int check_dispersions(const double *dispersion, int n_genes, long long m) {
     const double max_disp = pilot::nb_max_disp(m);
@@ -370,4 +402,38 @@ PILOT_API int pilot_ot_nb_rlog(const void *Y, int Y_is_device, int dtype, long l
         return rc;
     count_flag(flags, n_genes, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
     return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_nb_cooks(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const int *codes, int n_groups,
+                                const double *size_factors, const double *dispersion, const double *q, double cutoff, int min_replace,
+                                double *alpha_robust, double *max_cooks, int *arg_max, int *n_above, int *n_replace, double *trimmed_base,
+                                void *D, int D_is_device, long long ld_D, long long *bad_row, int *bad_col) {
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, true, codes, n_groups, dispersion, "counts, normalised counts and sort buffer"};
+    if (int rc = prologue(
+            c, !Y || !codes || !size_factors || !dispersion || !q || !alpha_robust || !max_cooks || !arg_max || !n_above || !n_replace ||
+                   !trimmed_base,
+            bad_row, bad_col,
+            [&] {
+                if (int rc = positive_finite("cutoff", cutoff)) return rc;
+                if (min_replace < pilot::NB_COOKS_MIN_GROUP)
+                    return fail(PILOT_OT_EINVAL, "min_replace=%d: at least %d (smaller groups have no Cook's distance to compare)", min_replace,
+                                pilot::NB_COOKS_MIN_GROUP);
+                return D && ld_D < n_genes ? fail(PILOT_OT_EINVAL, "ld_D=%lld is smaller than n_genes=%d", ld_D, n_genes) : PILOT_OT_OK;
+            },
+            [&] {
+                for (int j = 0; j < n_genes; ++j) {
+                    if (std::isnan(dispersion[j])) continue;
+                    for (int g = 0; g < n_groups; ++g) {
+                        const double v = q[(long long)j * n_groups + g];
+                        if (!(std::isfinite(v) && v > 0.0))
+                            return fail(PILOT_OT_EINVAL, "q[%d, %d]=%g must be positive and finite where the gene has a dispersion", j, g, v);
+                    }
+                }
+                return PILOT_OT_OK;
+            }))
+        return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return cooks<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, n_groups, c.dd, dispersion, q, cutoff, min_replace, alpha_robust, max_cooks, arg_max,
+                                  n_above, n_replace, trimmed_base, D, D_is_device, ld_D, bad_row, bad_col);
+    });
 }

@@ -1658,6 +1658,216 @@ def nb_rlog(counts, size_factors, dispersion, prior_var, on_device=False, return
     return (out, {"intercept": intercept, "steps": steps, "flags": flags, "n_not_converged": bad.value}) if return_info else out
 
 
+# ---- Cook's distances, outlier replacement and independent filtering (K25; DESeq(dds) and results(dds) of compute_pseudobulk_DE) -
+NB_COOKS_MIN_REPLACE = 7
+NB_COOKS_MIN_GROUP = 3
+NB_COOKS_QUANTILE = 0.99
+
+
+def nb_cooks_cutoff(m, p):
+    """DESeq2's default ``cooksCutoff``: ``qf(0.99, p, m - p)`` of m samples and p coefficients."""
+    from scipy import stats
+    if isinstance(m, bool) or isinstance(p, bool) or int(m) != m or int(p) != p or p < 1 or m - p < 1:
+        raise ValueError("nb_cooks_cutoff: m=%r samples and p=%r coefficients must be integers with p >= 1 and m - p >= 1" % (m, p))
+    return float(stats.f.ppf(NB_COOKS_QUANTILE, int(p), int(m) - int(p)))
+
+
+def _nb_cutoff_arg(cutoff):
+    if isinstance(cutoff, (str, bytes, bool)) or not np.isscalar(cutoff) or not (np.isfinite(cutoff) and cutoff > 0):
+        raise ValueError("cutoff=%r must be positive and finite" % (cutoff,))
+    return float(cutoff)
+
+
+def _nb_min_replace_arg(min_replace):
+    if isinstance(min_replace, bool) or int(min_replace) != min_replace or min_replace < NB_COOKS_MIN_GROUP:
+        raise ValueError("min_replace=%r must be an integer >= %d" % (min_replace, NB_COOKS_MIN_GROUP))
+    return int(min_replace)
+
+
+def nb_cooks(counts, codes, n_groups, size_factors, dispersion, q, cutoff, min_replace=NB_COOKS_MIN_REPLACE, return_distances=False):
+    """K25: per gene (column) of ``counts`` the Cook's distances of the negative-binomial group fits, as DESeq2's outlier handling
+    reads them (include/pilot_ot.h, pilot_ot_nb_cooks; the rule is this library's statement, unpinned).
+    ``counts``, ``codes``, ``n_groups`` and ``size_factors`` as :func:`nb_group_fits`; ``dispersion``: the gene's final dispersion
+    (NaN leaves the gene out); ``q``: genes x groups, :func:`nb_group_fits`' fits at it (positive where the gene has a
+    dispersion).  The variance in the distance comes from a ROBUST dispersion -- the largest trimmed variance of ``c / s`` over
+    the groups of at least 3 samples -- so that the outlier does not hide itself; the hat diagonal is
+    ``w_j / sum_{group} w`` at the final dispersion.  ``cutoff`` (:func:`nb_cooks_cutoff`) and ``min_replace`` only count.
+    Returns a dict of per-gene arrays: ``alpha_robust``, ``max_cooks`` (over the samples of groups with at least 3),
+    ``arg_max`` (the lowest sample that attains it, -1 without one), ``n_above`` (samples with a larger count than that one),
+    ``n_replace`` (samples above ``cutoff`` in groups of at least ``min_replace``), ``trimmed_base`` (the 0.2-trimmed mean of
+    ``c / s`` over all samples); with ``return_distances`` also ``D``, samples x genes (``"device"``: a :class:`DeviceMatrix`).
+    One wave per gene, a bitonic sort in LDS.  The same bits from a repeated call, from float32 and float64 storage, from host and
+    device matrices, and for a gene alone or in any batch.  Errors as :func:`nb_dispersions`."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    codes, n_groups, sf = _nb_args(Y.rows, Y.cols, codes, n_groups, size_factors)
+    alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if q.shape != (Y.cols, n_groups):
+        raise ValueError("q has shape %s for %d genes in %d groups" % (q.shape, Y.cols, n_groups))
+    fitted = q[~np.isnan(alpha)]
+    if not (np.isfinite(fitted).all() and (fitted > 0).all()):
+        raise ValueError("q must be positive and finite where the gene has a dispersion")
+    cutoff, min_replace = _nb_cutoff_arg(cutoff), _nb_min_replace_arg(min_replace)
+    if return_distances not in (False, True, "device"):
+        raise ValueError("return_distances=%r must be False, True or 'device'" % (return_distances,))
+    _nb_sample_limit("nb_cooks", Y.rows)
+    out = {name: np.empty(Y.cols) for name in ("alpha_robust", "max_cooks", "trimmed_base")}
+    out.update({name: np.empty(Y.cols, dtype=np.int32) for name in ("arg_max", "n_above", "n_replace")})
+    on_device = return_distances == "device"
+    D = None
+    if return_distances:
+        D = _device_result(Y.rows, Y.cols) if on_device else np.empty((Y.rows, Y.cols), dtype=np.float64)
+    _nb_call(_lib.load().pilot_ot_nb_cooks,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), n_groups, _lib.dptr(sf), _lib.dptr(alpha),
+             _lib.dptr(q), cutoff, min_replace, _lib.dptr(out["alpha_robust"]), _lib.dptr(out["max_cooks"]), _lib.iptr(out["arg_max"]),
+             _lib.iptr(out["n_above"]), _lib.iptr(out["n_replace"]), _lib.dptr(out["trimmed_base"]),
+             None if D is None else ctypes.c_void_p(D.ptr if on_device else D.ctypes.data), int(on_device), Y.cols)
+    if D is not None:
+        out["D"] = D
+    return out
+
+
+def nb_replacements(counts, codes, size_factors, D, cutoff, trimmed_base, min_replace=NB_COOKS_MIN_REPLACE):
+    """DESeq2's ``replaceOutliers`` as tidy rows; pure numpy.  ``counts`` (samples x genes, host; c = rint), ``D`` (samples x
+    genes, :func:`nb_cooks`' distances) and ``trimmed_base`` (one per gene) describe the same genes.  A count is replaced where
+    ``D > cutoff`` in a group of at least ``min_replace`` samples, by ``trunc(trimmed_base * s_j)`` (R's ``as.integer``).  Returns
+    a structured array with the fields ``gene`` and ``sample`` (positions), ``count`` and ``replacement`` (float64), ordered by
+    gene, then sample."""
+    c = np.rint(np.asarray(counts, dtype=np.float64))
+    D, base = np.asarray(D, dtype=np.float64), np.asarray(trimmed_base, dtype=np.float64)
+    if c.ndim != 2 or D.shape != c.shape or base.shape != (c.shape[1],):
+        raise ValueError("counts %s, D %s and trimmed_base %s: samples x genes, the same, and one per gene" % (c.shape, D.shape, base.shape))
+    codes = np.asarray(codes)
+    if codes.shape != (c.shape[0],) or codes.dtype.kind not in "iu" or (codes.size and codes.min() < 0):
+        raise ValueError("codes: one non-negative integer per sample")
+    sf = np.asarray(size_factors, dtype=np.float64)
+    if sf.shape != (c.shape[0],) or not (np.isfinite(sf).all() and (sf > 0).all()):
+        raise ValueError("size_factors: one positive finite value per sample")
+    cutoff, min_replace = _nb_cutoff_arg(cutoff), _nb_min_replace_arg(min_replace)
+    big = np.bincount(codes)[codes] >= min_replace
+    with np.errstate(invalid="ignore"):
+        sample, gene = np.nonzero((D > cutoff) & big[:, None])
+    at = np.lexsort((sample, gene))
+    sample, gene = sample[at], gene[at]
+    rows = np.empty(gene.size, dtype=[("gene", np.int64), ("sample", np.int64), ("count", np.float64), ("replacement", np.float64)])
+    rows["gene"], rows["sample"], rows["count"] = gene, sample, c[sample, gene]
+    rows["replacement"] = np.trunc(base[gene] * sf[sample])
+    return rows
+
+
+def bh_adjust(p):
+    """Benjamini-Hochberg adjusted p-values (statsmodels' multipletests(method='fdr_bh')[1])."""
+    p = np.asarray(p, dtype=np.float64)
+    m = p.size
+    if m == 0:
+        return p.copy()
+    order = np.argsort(p, kind="stable")
+    scaled = p[order] * m / np.arange(1, m + 1)
+    adj = np.minimum(np.minimum.accumulate(scaled[::-1])[::-1], 1.0)
+    out = np.empty(m)
+    out[order] = adj
+    return out
+
+
+def lowess(x, y, f=2.0 / 3.0, iters=3):
+    """R's ``lowess(x, y, f, iter = iters, delta = 0)`` restated (Cleveland 1979, as in R's clowess.c, from memory; statsmodels is
+    not available where this library is tested, so the rule is UNPINNED): every point is fitted, there is no ``delta``
+    skipping.  ``x`` ascending.  Per point the window of ``ns = max(min(n, floor(f n + 1e-7)), 2)`` nearest points, tricube
+    weights over its half-width h (1 within 0.001 h, 0 beyond 0.999 h; points beyond the window that tie its edge are kept), a
+    weighted line (a weighted mean where the weighted spread of x is below 0.001 of its range); after each of ``iters`` passes
+    the bisquare robustness weights ``(1 - (r / 6 MAD)^2)^2`` of the residuals r (1 within 0.001, 0 beyond 0.999 of 6 MAD),
+    stopping early once 6 MAD is below 1e-7 of the mean absolute residual.  Returns the fitted values."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.ndim != 1 or x.shape != y.shape or x.size < 2:
+        raise ValueError("lowess: x %s and y %s must be two vectors of one length >= 2" % (x.shape, y.shape))
+    if not (np.isfinite(x).all() and np.isfinite(y).all() and (np.diff(x) >= 0).all()):
+        raise ValueError("lowess: x and y must be finite and x ascending")
+    if isinstance(f, bool) or not np.isscalar(f) or not 0 < f <= 1:
+        raise ValueError("lowess: f=%r must be in (0, 1]" % (f,))
+    if isinstance(iters, bool) or int(iters) != iters or iters < 0:
+        raise ValueError("lowess: iters=%r must be a non-negative integer" % (iters,))
+    n = x.size
+    ns = max(min(n, int(f * n + 1e-7)), 2)
+    span = x[-1] - x[0]
+    rw = np.ones(n)
+    fit = np.empty(n)
+    for it in range(int(iters) + 1):
+        nleft, nright = 0, ns - 1
+        for i in range(n):
+            while nright < n - 1 and x[nright + 1] - x[i] < x[i] - x[nleft]:
+                nleft, nright = nleft + 1, nright + 1
+            h = max(x[i] - x[nleft], x[nright] - x[i])
+            stop = nright + 1
+            while stop < n and x[stop] - x[i] <= 0.999 * h:          # ties with the edge of the window
+                stop += 1
+            xs, r = x[nleft:stop], np.abs(x[nleft:stop] - x[i])
+            w = np.where(r <= 0.999 * h, np.where(r <= 0.001 * h, 1.0, (1.0 - (r / h) ** 3) ** 3 if h > 0 else 1.0), 0.0) * rw[nleft:stop]
+            a = w.sum()
+            if not a > 0:
+                fit[i] = y[i]
+                continue
+            w = w / a
+            if h > 0:
+                centre = (w * xs).sum()
+                c = (w * (xs - centre) ** 2).sum()
+                if np.sqrt(c) > 0.001 * span:
+                    w = w * ((x[i] - centre) / c * (xs - centre) + 1.0)
+            fit[i] = (w * y[nleft:stop]).sum()
+        if it == iters:
+            break
+        res = np.abs(y - fit)
+        part = np.sort(res)
+        cmad = 3.0 * (part[n // 2] + part[n - n // 2 - 1])
+        if cmad < 1e-7 * res.mean():
+            break
+        with np.errstate(invalid="ignore"):                          # (cmad = 0: every residual is 0 and keeps weight 1)
+            u = res / cmad
+        rw = np.where(res <= 0.001 * cmad, 1.0, np.where(res <= 0.999 * cmad, (1.0 - u * u) ** 2, 0.0))
+    return fit
+
+
+NB_FILTER_THETAS = 50
+NB_FILTER_UPPER = 0.95
+NB_FILTER_LOWESS_F = 0.2
+
+
+def independent_filtering(pvalue, base_mean, alpha=0.05):
+    """DESeq2's ``pvalueAdjustment`` with independent filtering on the mean (Bourgon, Gentleman, Huber 2010; genefilter's
+    ``filtered_p``), restated; numpy on the host, UNPINNED.  The filter statistic is ``base_mean`` (NaN reads as 0);
+    ``lo = mean(filter == 0)``; ``theta`` = 50 points from lo to 0.95 (``[0]`` if lo >= 0.95); for each theta Benjamini-Hochberg runs
+    over the genes with ``filter >= quantile(filter, theta)`` (linear interpolation, R's type 7) that have a p-value, and
+    ``num_rej`` counts ``padj < alpha``.  If ``max(num_rej) <= 10`` the first column is taken; otherwise
+    ``fit = lowess(theta, num_rej, f = 1/5)``, ``thresh = max(fit) - sqrt(mean(residual^2))`` over the columns with rejections,
+    and the first column with ``num_rej > thresh`` (the first column if there is none).  Returns ``(padj, info)``: ``padj`` is NaN
+    below the cutoff and without a p-value; ``info`` holds ``theta``, ``num_rej``, ``lowess`` (None if not fitted), ``chosen``
+    and ``filter_threshold``."""
+    p, mean = np.asarray(pvalue, dtype=np.float64), np.asarray(base_mean, dtype=np.float64)
+    if p.ndim != 1 or p.shape != mean.shape or p.size < 1:
+        raise ValueError("independent_filtering: pvalue %s and base_mean %s: one of each per gene" % (p.shape, mean.shape))
+    if isinstance(alpha, (str, bytes, bool)) or not np.isscalar(alpha) or not 0 < alpha < 1:
+        raise ValueError("independent_filtering: alpha=%r must be in (0, 1)" % (alpha,))
+    filt = np.where(np.isnan(mean), 0.0, mean)
+    lo = float(np.mean(filt == 0))
+    theta = np.linspace(lo, NB_FILTER_UPPER, NB_FILTER_THETAS) if lo < NB_FILTER_UPPER else np.zeros(1)
+    cutoffs = np.quantile(filt, theta)
+    has_p = ~np.isnan(p)
+    columns = np.full((theta.size, p.size), np.nan)
+    for i, cut in enumerate(cutoffs):
+        use = has_p & (filt >= cut)
+        columns[i, use] = bh_adjust(p[use])
+    with np.errstate(invalid="ignore"):
+        num_rej = (columns < alpha).sum(axis=1)
+    fit, chosen = None, 0
+    if num_rej.max() > 10:
+        fit = lowess(theta, num_rej.astype(np.float64), f=NB_FILTER_LOWESS_F)
+        residual = (num_rej - fit)[num_rej > 0]
+        thresh = fit.max() - np.sqrt(np.mean(residual ** 2))
+        above = np.flatnonzero(num_rej > thresh)
+        chosen = int(above[0]) if above.size else 0
+    return columns[chosen].copy(), {"theta": theta, "num_rej": num_rej.astype(np.int64), "lowess": fit, "chosen": chosen,
+                                    "filter_threshold": float(cutoffs[chosen])}
+
+
 # ---- principal components (K15; scanpy's scale + tl.pca(svd_solver='arpack') of pilotpy's extract_annot_expression) ----------
 PCA_MAX_COMPS = 64
 

@@ -674,16 +674,7 @@ _PATTERNS = {0: ("linear up", "linear down"),
 
 def _bh_adjust(p):
     """Benjamini-Hochberg adjusted p-values (statsmodels' multipletests(method='fdr_bh')[1])."""
-    p = np.asarray(p, dtype=np.float64)
-    m = p.size
-    if m == 0:
-        return p.copy()
-    order = np.argsort(p, kind="stable")
-    scaled = p[order] * m / np.arange(1, m + 1)
-    adj = np.minimum(np.minimum.accumulate(scaled[::-1])[::-1], 1.0)
-    out = np.empty(m)
-    out[order] = adj
-    return out
+    return engine.bh_adjust(p)
 
 
 def _fits_table(fits, names, id_col, p_val, modify_r2):
@@ -2382,7 +2373,8 @@ def deseq2_dispersions(cluster_counts, groups, size_factors=None, fit_type="para
     ``var_log_disp``.
 
     Deviations from DESeq2: the dispersion search is global (six rounds of a 64-point grid) where DESeq2 runs a line search from a
-    moments start, so on a multimodal gene the two can differ; no Cook's-distance handling; for ``m - k <= 3`` the same
+    moments start, so on a multimodal gene the two can differ; the Cook's-distance handling is
+    :func:`compute_pseudobulk_DE`'s ``outliers="deseq2"`` (K25), which refits the genes it replaces counts in; for ``m - k <= 3`` the same
     prior-variance formula is used, where DESeq2 simulates."""
     c, genes = _nb_counts(cluster_counts, "deseq2_dispersions")
     uniq, codes = np.unique(np.asarray(groups), return_inverse=True)
@@ -2393,20 +2385,138 @@ def deseq2_dispersions(cluster_counts, groups, size_factors=None, fit_type="para
     return _nb_dispersion_table(c, genes, codes.astype(np.int32), len(uniq), sf, fit_type)
 
 
-def _nb_wald_table(genes, table, q, w):
-    """the host tail of the Wald test: group 1 over group 0 of the fits (q, w), rows ordered by padj (NaN last, stable)"""
+def _nb_padj(p, base_mean, filtering_alpha):
+    """``padj`` of the p-values in gene order: plain BH over the genes with one, or with ``filtering_alpha``
+    ``engine.independent_filtering``; ``(padj, info or None)``"""
+    if filtering_alpha is not None:
+        return engine.independent_filtering(p, base_mean, filtering_alpha)
+    padj = np.full(p.shape, np.nan)
+    ok = ~np.isnan(p)
+    padj[ok] = _bh_adjust(p[ok])
+    return padj, None
+
+
+def _nb_wald_table(genes, table, q, w, cooks=None, filtering_alpha=None):
+    """the host tail of the Wald test: group 1 over group 0 of the fits (q, w), rows ordered by padj (NaN last, stable).
+    ``cooks``: the columns maxCooks, cooksOutlier and replace in gene order (a flagged gene loses its p-value before the
+    adjustment); ``filtering_alpha``: independent filtering instead of plain BH (its info dict goes to attrs)"""
     from scipy import stats
     with np.errstate(divide="ignore", invalid="ignore"):
         lfc = np.log2(q[:, 1]) - np.log2(q[:, 0])                   # (as a difference: swapping the groups negates it exactly)
         se = np.log2(np.e) * np.sqrt(1.0 / w[:, 0] + 1.0 / w[:, 1])
         stat = lfc / se
     p = 2.0 * stats.norm.sf(np.abs(stat))
-    padj = np.full(p.shape, np.nan)
-    ok = ~np.isnan(p)
-    padj[ok] = _bh_adjust(p[ok])
+    if cooks is not None:
+        p[cooks["cooksOutlier"]] = np.nan
+    padj, filtering = _nb_padj(p, table["baseMean"].to_numpy(), filtering_alpha)
     out = pd.DataFrame({"gene": np.asarray(genes), "baseMean": table["baseMean"].to_numpy(), "log2FoldChange": lfc, "lfcSE": se,
                         "stat": stat, "pvalue": p, "padj": padj, "dispersion": table["dispersion"].to_numpy()})
-    return out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
+    if cooks is not None:
+        for name in ("maxCooks", "cooksOutlier", "replace"):
+            out[name] = cooks[name]
+    out = out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
+    if filtering is not None:
+        out.attrs["independent_filtering"] = filtering
+    return out
+
+
+_DE_OUTLIERS = (None, "deseq2")
+_REPLACED_COLUMNS = ["gene", "sample", "count", "replacement"]
+
+
+def _check_de_options(outliers, independent_filtering, alpha, who):
+    if not (outliers is None or (isinstance(outliers, str) and outliers in _DE_OUTLIERS)):
+        raise ValueError("%s: outliers=%r must be None or 'deseq2'" % (who, outliers))
+    if not isinstance(independent_filtering, (bool, np.bool_)):
+        raise ValueError("%s: independent_filtering=%r must be True or False" % (who, independent_filtering))
+    if isinstance(alpha, (str, bytes, bool)) or not np.isscalar(alpha) or not 0 < alpha < 1:
+        raise ValueError("%s: alpha=%r must be in (0, 1)" % (who, alpha))
+
+
+def _apply_replaced(c, genes, samples, replaced, who):
+    """a float64 copy of rint(c) (samples x genes) with the rows of a ``replaced`` frame (gene, sample, count, replacement) written"""
+    new = np.rint(np.asarray(c, dtype=np.float64))
+    if replaced is None or len(replaced) == 0:
+        return new
+    col, row = pd.Index(genes).get_indexer(replaced["gene"]), pd.Index(samples).get_indexer(replaced["sample"])
+    if (col < 0).any() or (row < 0).any():
+        raise ValueError("%s: de.attrs['replaced'] names a gene or a sample that cluster_counts lacks" % who)
+    if not np.array_equal(new[row, col], replaced["count"].to_numpy(dtype=np.float64)):
+        raise ValueError("%s: de.attrs['replaced'] records other counts than cluster_counts holds" % who)
+    new[row, col] = replaced["replacement"].to_numpy(dtype=np.float64)
+    return new
+
+
+def _nb_refit_max_cooks(new, codes, D, min_replace):
+    """step 5 of DESIGN.md K25 for the refitted genes: the largest distance over the samples of groups with 3 <= n_g <
+    min_replace (NaN without one) and how many samples have a larger count than the lowest sample that attains it"""
+    size = np.bincount(codes)[codes]
+    small = np.flatnonzero((size >= engine.NB_COOKS_MIN_GROUP) & (size < min_replace))
+    max_cooks, n_above = np.full(new.shape[1], np.nan), np.zeros(new.shape[1], dtype=np.int32)
+    if small.size:
+        for j in range(new.shape[1]):
+            d = D[small, j]
+            if np.isnan(d).all():
+                continue
+            at = small[int(np.nanargmax(d))]                     # (the first largest: the lowest sample)
+            max_cooks[j], n_above[j] = D[at, j], np.count_nonzero(new[:, j] > new[at, j])
+    return max_cooks, n_above
+
+
+def _nb_outliers(c, genes, samples, codes, sf, table, q, w, flags, min_replace=engine.NB_COOKS_MIN_REPLACE):
+    """steps 1-6 of DESIGN.md K25 after the fit of :func:`compute_pseudobulk_DE`: the distances, the replacements and the refit
+    of the genes that had one.  Returns ``(table, q, w, flags, cooks, extra)``: the first four with the refitted genes' rows
+    replaced (copies), ``cooks`` the gene-order columns maxCooks / cooksOutlier / replace, ``extra`` the new attrs."""
+    m = c.shape[0]
+    cutoff = engine.nb_cooks_cutoff(m, 2)
+    ck = engine.nb_cooks(c, codes, 2, sf, table["dispersion"].to_numpy(), q, cutoff, min_replace)
+    max_cooks, n_above = ck["max_cooks"].copy(), ck["n_above"].copy()
+    rep = np.flatnonzero(ck["n_replace"] > 0)
+    replaced = pd.DataFrame({name: [] for name in _REPLACED_COLUMNS})
+    extra = {"cooks_cutoff": cutoff}
+    if rep.size:
+        sub = np.ascontiguousarray(c[:, rep])
+        ck2 = engine.nb_cooks(sub, codes, 2, sf, table["dispersion"].to_numpy()[rep], q[rep], cutoff, min_replace, return_distances=True)
+        rows = engine.nb_replacements(sub, codes, sf, ck2["D"], cutoff, ck2["trimmed_base"], min_replace)
+        new = np.rint(sub.astype(np.float64))
+        new[rows["sample"], rows["gene"]] = rows["replacement"]
+        replaced = pd.DataFrame({"gene": np.asarray(genes)[rep[rows["gene"]]], "sample": np.asarray(samples)[rows["sample"]],
+                                 "count": rows["count"], "replacement": rows["replacement"]})
+        # the refit: the gene-wise and MAP estimates anew, the trend and both prior widths as they were
+        x_gene = engine.nb_dispersions(new, codes, 2, sf)
+        qn = new / sf[:, None]
+        base_mean, base_var = qn.mean(axis=0), qn.var(axis=0, ddof=1)
+        base_mean[np.isnan(x_gene)] = np.nan
+        base_var[np.isnan(x_gene)] = np.nan
+        disp_gene = engine.nb_clip(np.exp(x_gene), m)
+        a0, a1 = table.attrs["trend"]["coefficients"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            fit = a0 + a1 / base_mean if table.attrs["trend"]["fit_type"] == "parametric" else np.where(np.isfinite(base_mean), a0, np.nan)
+        log_fit = np.log(fit)
+        x_map = engine.nb_dispersions(new, codes, 2, sf, log_prior_mean=log_fit, prior_var=table.attrs["prior_var"])
+        with np.errstate(invalid="ignore"):
+            outlier = x_gene > log_fit + 2.0 * np.sqrt(table.attrs["var_log_disp"])
+        disp_map = engine.nb_clip(np.exp(x_map), m)
+        disp = np.where(outlier, disp_gene, disp_map)
+        q2, w2, info2 = engine.nb_group_fits(new, codes, 2, sf, disp, return_info=True)
+        table, q, w, flags = table.copy(), q.copy(), w.copy(), flags.copy()
+        for name, values in (("baseMean", base_mean), ("baseVar", base_var), ("dispGeneEst", disp_gene), ("dispFit", fit),
+                             ("dispMAP", disp_map), ("dispersion", disp), ("dispOutlier", outlier)):
+            table.iloc[rep, table.columns.get_loc(name)] = values
+        q[rep], w[rep], flags[rep] = q2, w2, info2["flags"]
+        live = ~np.isnan(disp)
+        if live.any():
+            ck3 = engine.nb_cooks(np.ascontiguousarray(new[:, live]), codes, 2, sf, disp[live], q2[live], cutoff, min_replace,
+                                  return_distances=True)
+            mc, na = _nb_refit_max_cooks(new[:, live], codes, ck3["D"], min_replace)
+            max_cooks[rep[live]], n_above[rep[live]] = mc, na
+        max_cooks[rep[~live]], n_above[rep[~live]] = np.nan, 0
+    with np.errstate(invalid="ignore"):
+        flagged = (max_cooks > cutoff) & (n_above < 3)
+    replace = np.zeros(len(genes), dtype=bool)
+    replace[rep] = True
+    extra["replaced"] = replaced
+    return table, q, w, flags, {"maxCooks": max_cooks, "cooksOutlier": flagged, "replace": replace}, extra
 
 
 def _check_shrink(shrink, who):
@@ -2427,7 +2537,9 @@ def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
     ``log2FoldChange = beta1 / ln 2`` and ``lfcSE = sd / ln 2`` (NaN where the posterior is not log-concave at its mode); the
     new columns ``lfcMLE`` and ``lfcMLESE`` keep the old values; ``stat``, ``pvalue``, ``padj`` and the row order are unchanged,
     as ``lfcShrink`` keeps the unshrunken Wald test.  ``attrs`` gains ``shrink='apeglm'``, ``prior_scale``, ``prior_var``,
-    ``n_at_bound`` (genes whose mode sits at the end of the searched interval; none is expected).
+    ``n_at_bound`` (genes whose mode sits at the end of the searched interval; none is expected).  A frame made with
+    ``outliers="deseq2"`` carries ``attrs['replaced']``: those counts are replaced in ``cluster_counts`` before the fit, and the
+    dispersions are the refitted ones.
 
     Not covered: s-values, other coefficients or more than two groups, apeglm's other likelihoods.  The intercept prior sits
     on group 0, as in apeglm, so swapping the groups moves the estimate slightly instead of negating it."""
@@ -2463,6 +2575,8 @@ def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
         S, A = engine.nb_prior_scale(lfc, se, use=~floored)
     else:
         S, A = float(prior_scale), float(prior_scale) ** 2
+    if "replaced" in de.attrs:                                   # (outliers="deseq2": the fit is of the replaced counts)
+        c = _apply_replaced(c, genes, getattr(cluster_counts, "index", np.arange(c.shape[0])), de.attrs["replaced"], "lfc_shrink")
     b0, b1, info = engine.nb_shrink(c, codes, sf, disp, engine.nb_far_end(lfc, floored), S, return_info=True)
     sd = engine.nb_posterior_sd(b1, info["w0"], info["w1"], S)
     row = genes.get_indexer(de["gene"])                          # the table's column of every row of the frame
@@ -2474,7 +2588,7 @@ def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
 
 
 def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=None, group2=None, cluster_col=None, fit_type="parametric",
-                          shrink=None, prior_scale=None):
+                          shrink=None, prior_scale=None, outliers=None, independent_filtering=False, alpha=0.05):
     """The reference's ``compute_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:96-159) without R: the negative-binomial Wald
     test of DESeq2 for the design ``~ stage`` between two patient sub-groups, on the device.  Takes :func:`pseudobulk_inputs`'
     pair unchanged; the samples of ``group1`` and ``group2`` (by ``cluster_metadata[cluster_col]``) are selected first, as the
@@ -2492,13 +2606,30 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     standard deviation under apeglm's prior, beside the unchanged Wald columns, with ``lfcMLE`` / ``lfcMLESE`` keeping the
     maximum-likelihood values.  Anything else: ValueError before any device work.
 
+    ``outliers``: ``None`` (the default) or ``"deseq2"``, the outlier handling of ``DESeq(dds)`` and ``results(dds)`` (DESIGN.md
+    K25; ``engine.nb_cooks``): after the fit, every sample's Cook's distance with a robust dispersion in its variance; in a group
+    of at least 7 samples a count whose distance passes ``cooks_cutoff = qf(0.99, 2, m - 2)`` is replaced by
+    ``trunc(trimmed mean of c / s  *  s_j)`` and the genes with a replacement are fitted again on the replaced counts (the size
+    factors, the trend and the prior widths stay; a gene the replacement empties becomes all NaN); a gene whose largest distance
+    over the samples that could NOT be replaced (groups of 3 to 6) passes the cutoff loses ``pvalue`` and ``padj`` unless three or
+    more samples have a larger count than the one at the maximum.  New columns: ``maxCooks``, ``cooksOutlier``, ``replace``;
+    new ``attrs``: ``cooks_cutoff``, ``replaced`` (a frame ``gene, sample, count, replacement``); ``attrs['dispersions']`` holds
+    the refitted rows.  ``independent_filtering=True`` (with or without ``outliers``) adjusts the p-values as ``results(dds,
+    alpha = alpha)`` does (``engine.independent_filtering``): BH over the genes whose ``baseMean`` passes the quantile that
+    maximises the rejections at ``alpha``; ``padj`` is NaN below it, and ``attrs['independent_filtering']`` records the choice.
+    With the defaults the frame is what it was without these arguments, bit for bit.  Any other ``outliers``, or an ``alpha``
+    outside (0, 1): ValueError before any device work.
+
     Deviations from the reference's call, which is unpinned here (no DESeq2 or apeglm where this library is tested): the
-    shrinkage is opt-in (``shrink="apeglm"``) and its mode comes from a global grid search, not apeglm's local optimiser; no
-    s-values; ``rlog`` is :func:`compute_pseudobulk_PCA`'s; no Cook's-distance outlier handling; no independent filtering, ``padj`` is plain BH; no beta
+    shrinkage, the outlier handling and the independent filtering are opt-in (``shrink="apeglm"``, ``outliers="deseq2"``,
+    ``independent_filtering=True``; the reference's call has all three on) and the shrunken mode comes from a global grid
+    search, not apeglm's local optimiser; no s-values; ``rlog`` is :func:`compute_pseudobulk_PCA`'s; the deviations of the outlier
+    rule are DESIGN.md K25's; no beta
     ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the formula where DESeq2 simulates; the
     reference returns R's list (the frame at index 1), this returns the frame.  Fewer than three selected samples, or a group
     without samples: ValueError before any device work."""
     _check_shrink(shrink, "compute_pseudobulk_DE")
+    _check_de_options(outliers, independent_filtering, alpha, "compute_pseudobulk_DE")
     if cluster_col is None or cluster_col not in cluster_metadata.columns:
         raise ValueError("compute_pseudobulk_DE: cluster_col=%r is not a column of cluster_metadata" % (cluster_col,))
     stage = cluster_metadata[cluster_col]
@@ -2516,11 +2647,75 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     sf = _nb_size_factors(counts, None, c.shape[0])
     table = _nb_dispersion_table(c, genes, codes, 2, sf, fit_type)
     q, w, info = engine.nb_group_fits(c, codes, 2, sf, table["dispersion"].to_numpy(), return_info=True)
-    out = _nb_wald_table(genes, table, q, w)
-    floored = pd.Series(((info["flags"] & engine._lib.NB_FLOORED) != 0).any(axis=1), index=genes)
-    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=info["n_not_converged"],
-                     floored=floored)
+    flags, n_not_converged, cooks, extra = info["flags"], info["n_not_converged"], None, {}
+    if outliers:
+        table, q, w, flags, cooks, extra = _nb_outliers(c, genes, counts.index, codes, sf, table, q, w, flags)
+        n_not_converged = int(np.count_nonzero(flags & engine._lib.NB_NOT_CONVERGED))
+    out = _nb_wald_table(genes, table, q, w, cooks, float(alpha) if independent_filtering else None)
+    floored = pd.Series(((flags & engine._lib.NB_FLOORED) != 0).any(axis=1), index=genes)
+    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=n_not_converged,
+                     floored=floored, **extra)
     return lfc_shrink(counts, codes, out, prior_scale) if shrink else out
+
+
+def deseq2_cooks(cluster_counts, groups, de, min_replace=engine.NB_COOKS_MIN_REPLACE):
+    """The per-gene Cook's-distance table behind ``outliers="deseq2"`` (``engine.nb_cooks``), for looking at what
+    the rule saw.  ``cluster_counts`` and ``groups`` (0 / 1 or boolean per sample) as :func:`lfc_shrink` takes them; ``de``: the
+    frame :func:`compute_pseudobulk_DE` returned for those samples, which supplies the dispersions and the size factors.  A frame
+    made with ``outliers="deseq2"`` has its replacements applied first, so the table describes the refitted state.  The group
+    means are fitted again at the frame's dispersions (``engine.nb_group_fits``).  Returns a frame indexed by gene, in the
+    table's column order: ``alpha_robust``, ``max_cooks``, ``arg_max`` (the sample's label; None without one), ``n_above``,
+    ``n_replace``, ``trimmed_base``; ``attrs['cooks_cutoff']``."""
+    c, genes = _nb_counts(cluster_counts, "deseq2_cooks")
+    min_replace = engine._nb_min_replace_arg(min_replace)
+    codes = np.asarray(groups)
+    if codes.shape != (c.shape[0],):
+        raise ValueError("deseq2_cooks: groups has shape %s for %d samples" % (codes.shape, c.shape[0]))
+    if codes.dtype.kind not in "biu" or not np.isin(codes, (0, 1)).all():
+        raise ValueError("deseq2_cooks: groups must be 0 / 1 or boolean")
+    codes = codes.astype(np.int32)
+    if not hasattr(de, "columns") or any(col not in de.columns for col in ("gene", "dispersion")) or "size_factors" not in de.attrs:
+        raise ValueError("deseq2_cooks: de must be a frame of compute_pseudobulk_DE (columns gene, dispersion; attrs size_factors)")
+    named = pd.Index(de["gene"])
+    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)
+    if len(de) != len(genes) or (at < 0).any():
+        raise ValueError("deseq2_cooks: the genes of de are not the columns of cluster_counts")
+    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
+    samples = getattr(cluster_counts, "index", pd.RangeIndex(c.shape[0]))
+    if "replaced" in de.attrs:
+        c = _apply_replaced(c, genes, samples, de.attrs["replaced"], "deseq2_cooks")
+    disp = de["dispersion"].to_numpy(dtype=np.float64)[at]
+    cutoff = engine.nb_cooks_cutoff(c.shape[0], 2)
+    q, _ = engine.nb_group_fits(c, codes, 2, sf, disp)
+    ck = engine.nb_cooks(c, codes, 2, sf, disp, q, cutoff, min_replace)
+    labels = np.asarray(samples, dtype=object)
+    out = pd.DataFrame({"alpha_robust": ck["alpha_robust"], "max_cooks": ck["max_cooks"],
+                        "arg_max": [labels[i] if i >= 0 else None for i in ck["arg_max"]], "n_above": ck["n_above"],
+                        "n_replace": ck["n_replace"], "trimmed_base": ck["trimmed_base"]}, index=genes)
+    out.attrs["cooks_cutoff"] = cutoff
+    return out
+
+
+def independent_filtering(de, alpha=0.05):
+    """``engine.independent_filtering`` on a frame :func:`compute_pseudobulk_DE` already made: a copy whose ``padj`` comes from
+    its ``pvalue`` and ``baseMean`` columns, ordered by the new ``padj`` (NaN last, ties in gene order where
+    ``attrs['dispersions']`` tells it, else in the frame's), with ``attrs['independent_filtering']`` the info dict."""
+    if not hasattr(de, "columns") or any(col not in de.columns for col in ("gene", "baseMean", "pvalue", "padj")):
+        raise ValueError("independent_filtering: de must be a frame of compute_pseudobulk_DE (columns gene, baseMean, pvalue, padj)")
+    if isinstance(alpha, (str, bytes, bool)) or not np.isscalar(alpha) or not 0 < alpha < 1:
+        raise ValueError("independent_filtering: alpha=%r must be in (0, 1)" % (alpha,))
+    out = de.copy()
+    table = de.attrs.get("dispersions")
+    if table is not None and len(table) == len(de) and table.index.is_unique:
+        at = pd.Index(de["gene"]).get_indexer(table.index)
+        if (at >= 0).all():
+            out = out.iloc[at].reset_index(drop=True)
+    padj, info = engine.independent_filtering(out["pvalue"].to_numpy(dtype=np.float64), out["baseMean"].to_numpy(dtype=np.float64), float(alpha))
+    out["padj"] = padj
+    out = out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
+    out.attrs.update(de.attrs)
+    out.attrs["independent_filtering"] = info
+    return out
 
 
 # ---- regularised log transform and its PCA: rlog(dds, blind = TRUE), plotPCA_subgroups (plot/pseudobulk_DE_analysis.py:161-233) ---
@@ -2609,19 +2804,21 @@ def pseudobulk_pca(rld, variance_threshold=0.2, n_components=2):
 
 
 def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
-                      remove_samples=(), shrink=None):
+                      remove_samples=(), shrink=None, outliers=None, independent_filtering=False, alpha=0.05):
     """The numbers of the reference's ``get_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:506-666) in one process with no R:
     :func:`pseudobulk_inputs` of ``cell_type``, then :func:`compute_pseudobulk_DE` for every pair of
     ``itertools.combinations(np.unique(proportion_df[cluster_col]), 2)``.  Returns ``{"<g2>vs<g1>": frame}`` (the names of the
     reference's ``_DE.csv`` files; the fold change is g2 over g1).  ``shrink`` is :func:`compute_pseudobulk_DE`'s (``"apeglm"``:
-    the shrunken fold changes the reference writes).  No plots, no files, no enrichment; the rlog PCA the reference draws first is
+    the shrunken fold changes the reference writes), and so are ``outliers``, ``independent_filtering`` and ``alpha``.  No plots, no files, no enrichment; the rlog PCA the reference draws first is
     :func:`compute_pseudobulk_PCA` / :func:`pseudobulk_pca` on :func:`pseudobulk_inputs`' pair; the deviations of
     :func:`compute_pseudobulk_DE` apply."""
     import itertools
     _check_shrink(shrink, "get_pseudobulk_DE")
+    _check_de_options(outliers, independent_filtering, alpha, "get_pseudobulk_DE")
     cluster_counts, cluster_metadata = pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col, sample_col, cluster_col, remove_samples)
     out = {}
     for g1, g2 in itertools.combinations(np.unique(proportion_df[cluster_col]), 2):
         out["%svs%s" % (g2, g1)] = compute_pseudobulk_DE(cluster_counts, cluster_metadata, group1=g1, group2=g2, cluster_col=cluster_col,
-                                                         shrink=shrink)
+                                                         shrink=shrink, outliers=outliers, independent_filtering=independent_filtering,
+                                                         alpha=alpha)
     return out

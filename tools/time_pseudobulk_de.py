@@ -24,7 +24,16 @@ both are one wave per gene over LDS-staged samples; the dispersion pass evaluate
 nb_rlog about (iterations + halvings) x m terms in three passes, spread over the lanes.  The dispersions are the trend of one
 blind pass (engine.nb_dispersions_blind, engine.nb_trend), the prior variance engine.nb_rlog_prior_var's.  ``nb_dispersions`` and
 ``nb_rlog`` alternate in one loop, best of --reps each; the mean iterations a gene go beside the times.  Host: the vectorised
-restatement of the same iteration (tests/nb_rlog_restatement.py) on --host-genes genes, scaled.  Writes OUT/rlog_rate.txt."""
+restatement of the same iteration (tests/nb_rlog_restatement.py) on --host-genes genes, scaled.  Writes OUT/rlog_rate.txt.
+
+--cooks: instead, the Cook's-distance pass (K25: engine.nb_cooks on the whole table, no distances returned) beside the dispersion
+pass on the same tables: both are one wave per gene over LDS-staged samples; nb_cooks is one staged pass plus five bitonic sorts a
+gene (all samples, and each group's values and squared deviations).  --outlier-share of the genes (default 2 %) get one count
+x 200, so that the refit has something to do.  The dispersions come from one MAP-less pass, the fits from
+nb_group_fits.  ``nb_dispersions`` and ``nb_cooks`` alternate in one loop, best of --reps each.  Then, once, what
+``outliers="deseq2"`` adds for the genes with a replacement: the gathered call with distances, the replacements, two dispersion
+passes, the group fits and the last distance call on those genes only, with the share of genes that took part.  Host: the
+restatement (tests/nb_cooks_restatement.py) on --host-genes genes, scaled.  Writes OUT/cooks_rate.txt."""
 import argparse
 import os
 import sys
@@ -46,9 +55,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shrink", action="store_true")
     ap.add_argument("--rlog", action="store_true")
+    ap.add_argument("--cooks", action="store_true")
+    ap.add_argument("--outlier-share", type=float, default=0.02, help="--cooks: the share of genes that get one count x 200")
     a = ap.parse_args()
-    if a.shrink and a.rlog:
-        ap.error("--shrink and --rlog are separate runs")
+    if a.shrink + a.rlog + a.cooks > 1:
+        ap.error("--shrink, --rlog and --cooks are separate runs")
     import nb_glm_restatement as RR
     from pilot_amd import _lib, engine
 
@@ -142,7 +153,62 @@ def main():
         say("  host restatement (vectorised numpy) on %d genes: %.1f ms; scaled by %d / %d: %.2f s; device against it: rlog off by at most "
             "%.2g" % (h, 1e3 * t_host, a.genes, h, t_host * a.genes / h, np.abs(got - ref["rlog"]).max()))
         del D, R
-    for m in (() if a.shrink or a.rlog else a.samples):
+    for m in (a.samples if a.cooks else ()):
+        import nb_cooks_restatement as CR
+        rng = np.random.default_rng(m)
+        s = RR.size_factors(rng, m)
+        codes = (np.arange(m) % 2).astype(np.int32)
+        c = RR.nb_class(rng, s, codes, 2, a.genes)
+        planted = rng.choice(a.genes, int(round(a.outlier_share * a.genes)), replace=False)      # one count x 200 in each of these genes
+        at = rng.integers(0, m, planted.size)
+        c[at, planted] = np.maximum(c[at, planted], 5.0) * 200.0
+        D = engine.DeviceMatrix.upload(c.astype(np.float32))
+        x = engine.nb_dispersions(D, codes, 2, s)
+        alpha = engine.nb_clip(np.exp(x), m)
+        q, _ = engine.nb_group_fits(D, codes, 2, s, alpha)
+        cut = engine.nb_cooks_cutoff(m, 2)
+        engine.nb_cooks(D, codes, 2, s, alpha, q, cut)
+        t_disp = t_cooks = np.inf
+        for _ in range(a.reps):                                         # the two calls alternate
+            t0 = time.perf_counter()
+            engine.nb_dispersions(D, codes, 2, s)
+            t1 = time.perf_counter()
+            ck = engine.nb_cooks(D, codes, 2, s, alpha, q, cut)
+            t2 = time.perf_counter()
+            t_disp, t_cooks = min(t_disp, t1 - t0), min(t_cooks, t2 - t1)
+        say("case %d genes x %d samples, float32 in HBM, 2 groups, one count x 200 planted in %d genes; cutoff qf(0.99, 2, %d) = %.4g"
+            % (a.genes, m, planted.size, m - 2, cut))
+        say("  nb_cooks %.2f ms, nb_dispersions (gene-wise) %.2f ms beside it: ratio %.3f; best of %d, alternating"
+            % (1e3 * t_cooks, 1e3 * t_disp, t_cooks / t_disp, a.reps))
+        with np.errstate(invalid="ignore"):
+            say("  %d genes with max_cooks past the cutoff, %d with a replacement (%.2f %% of the table)"
+                % ((ck["max_cooks"] > cut).sum(), (ck["n_replace"] > 0).sum(), 100.0 * (ck["n_replace"] > 0).mean()))
+        rep = np.flatnonzero(ck["n_replace"] > 0)
+        if rep.size:
+            t0 = time.perf_counter()
+            sub = np.ascontiguousarray(c[:, rep])
+            second = engine.nb_cooks(sub, codes, 2, s, alpha[rep], q[rep], cut, return_distances=True)
+            rows = engine.nb_replacements(sub, codes, s, second["D"], cut, second["trimmed_base"])
+            new = sub.copy()
+            new[rows["sample"], rows["gene"]] = rows["replacement"]
+            xn = engine.nb_dispersions(new, codes, 2, s)
+            engine.nb_dispersions(new, codes, 2, s, log_prior_mean=np.where(np.isnan(xn), np.nan, x[rep]), prior_var=0.6)
+            an = engine.nb_clip(np.exp(xn), m)
+            qn, _ = engine.nb_group_fits(new, codes, 2, s, an)
+            engine.nb_cooks(new, codes, 2, s, an, qn, cut, return_distances=True)
+            say("  the refit of those %d genes (host table; gathered distances, %d replacements, two dispersion passes, group fits, "
+                "distances again): %.2f ms, once" % (rep.size, rows.size, 1e3 * (time.perf_counter() - t0)))
+        h = min(a.host_genes, a.genes)
+        t0 = time.perf_counter()
+        ref = CR.cooks(c[:, :h], codes, 2, s, alpha[:h], q[:h], cut)
+        t_host = time.perf_counter() - t0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            off = np.abs(ck["max_cooks"][:h] - ref["max_cooks"]) / ref["max_cooks"]
+        say("  host restatement (numpy, a loop over genes) on %d genes: %.1f ms; scaled by %d / %d: %.2f s; device against it: max_cooks off "
+            "by at most %.2g relative, arg_max equal on %d of %d"
+            % (h, 1e3 * t_host, a.genes, h, t_host * a.genes / h, np.nanmax(off), (ck["arg_max"][:h] == ref["arg_max"]).sum(), h))
+        del D
+    for m in (() if a.shrink or a.rlog or a.cooks else a.samples):
         rng = np.random.default_rng(m)
         s = RR.size_factors(rng, m)
         codes = (np.arange(m) % 2).astype(np.int32)
@@ -177,7 +243,7 @@ def main():
                np.abs(np.expm1(x[:h][res] - xh[res])).max(initial=0)))
         del D, Z
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

@@ -91,6 +91,28 @@ template <typename... P, typename... A> int launch_wave_per_gene(void (*kern)(P.
     return PILOT_OT_OK;
 }
 
+// n elements from HBM to the host
+template <typename T> hipError_t fetch(T *dst, const T *src, size_t n) { return hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyDeviceToHost); }
+
+// An m x G float64 result the caller takes in HBM (its buffer, its leading dimension) or on the host.  For the host the kernel
+// writes it packed behind the call's other doubles in the WS_NB_OUT slot -- the call asks for tail() more and says where with
+// place() -- and fetch() copies it out.  out == NULL: the call returns no such matrix.
+struct ResultMatrix {
+    void *out;
+    int on_device;
+    long long ld_out;
+    size_t m, G;
+    double *dev = nullptr;                                   // where the kernel writes, with the leading dimension ld()
+    bool staged() const { return out && !on_device; }
+    size_t tail() const { return staged() ? m * G : 0; }
+    long long ld() const { return on_device ? ld_out : (long long)G; }
+    void place(double *slot_tail) { dev = staged() ? slot_tail : static_cast<double *>(out); }
+    hipError_t fetch() const {
+        if (!staged()) return hipSuccess;
+        return hipMemcpy2D(out, sizeof(double) * (size_t)ld_out, dev, sizeof(double) * G, sizeof(double) * G, m, hipMemcpyDeviceToHost);
+    }
+};
+
 // the first negative or non-finite count of Y, if any, as PILOT_OT_EINVAL
 template <typename T> int check_counts(const void *y, long long ld, long long m, int n_genes, long long *bad_row, int *bad_col) {
     nb_u64 *d_bad, bad = 0;
@@ -99,7 +121,7 @@ template <typename T> int check_counts(const void *y, long long ld, long long m,
     hipLaunchKernelGGL(pilot::nb_check_kernel<T>, dim3((unsigned)pilot::grid_for((long)(m * n_genes), 256, pilot::cu_count())), dim3(256), 0,
                        nullptr, static_cast<const T *>(y), ld, m, n_genes, d_bad);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+    HIP_TRY(fetch(&bad, d_bad, 1));
     if (bad == pilot::NB_NO_BAD) return PILOT_OT_OK;
     const int col = (int)(bad >> 32);
     const long long row = (long long)(bad & 0xFFFFFFFFull);
@@ -123,9 +145,9 @@ int dispersions(const void *y, long long ld, int m, int n_genes, int k, const De
                                       dd.order, dd.gof, dd.ss, dd.gstart, d_prior, prior_var, d_out, d_out + G,
                                       fitted_mean ? d_out + 2 * G : nullptr))
         return rc;
-    HIP_TRY(hipMemcpy(log_disp, d_out, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(objective, d_out + G, sizeof(double) * G, hipMemcpyDeviceToHost));
-    if (fitted_mean) HIP_TRY(hipMemcpy(fitted_mean, d_out + 2 * G, sizeof(double) * G * k, hipMemcpyDeviceToHost));
+    HIP_TRY(fetch(log_disp, d_out, G));
+    HIP_TRY(fetch(objective, d_out + G, G));
+    if (fitted_mean) HIP_TRY(fetch(fitted_mean, d_out + 2 * G, G * k));
     return PILOT_OT_OK;
 }
 
@@ -142,10 +164,10 @@ int group_fits(const void *y, long long ld, long long m, int n_genes, int k, con
     hipLaunchKernelGGL(pilot::nb_group_fit_kernel<T>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, nullptr, static_cast<const T *>(y), ld,
                        n_genes, k, dd.order, dd.ss, dd.gstart, d_dbl, d_dbl + G, d_dbl + G + n_out, d_int, d_int + n_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(q, d_dbl + G, sizeof(double) * n_out, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(w, d_dbl + G + n_out, sizeof(double) * n_out, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(steps, d_int, sizeof(int) * n_out, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags, d_int + n_out, sizeof(int) * n_out, hipMemcpyDeviceToHost));
+    HIP_TRY(fetch(q, d_dbl + G, n_out));
+    HIP_TRY(fetch(w, d_dbl + G + n_out, n_out));
+    HIP_TRY(fetch(steps, d_int, n_out));
+    HIP_TRY(fetch(flags, d_int + n_out, n_out));
     return PILOT_OT_OK;
 }
 
@@ -165,17 +187,17 @@ int shrink(const void *y, long long ld, int m, int n_genes, const DevDesign &dd,
                                       d_dbl, d_dbl + G, prior_scale, intercept_scale, d_dbl + 2 * G, d_dbl + 3 * G, d_dbl + 4 * G, d_dbl + 5 * G,
                                       d_flags))
         return rc;
-    HIP_TRY(hipMemcpy(beta0, d_dbl + 2 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(beta1, d_dbl + 3 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(objective, d_dbl + 4 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(info, d_dbl + 5 * G, sizeof(double) * 2 * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags, d_flags, sizeof(int) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(fetch(beta0, d_dbl + 2 * G, G));
+    HIP_TRY(fetch(beta1, d_dbl + 3 * G, G));
+    HIP_TRY(fetch(objective, d_dbl + 4 * G, G));
+    HIP_TRY(fetch(info, d_dbl + 5 * G, 2 * G));
+    HIP_TRY(fetch(flags, d_flags, G));
     return PILOT_OT_OK;
 }
 
 template <typename T>
-int rlog(const void *y, long long ld, int m, int n_genes, const double *sf, const double *dispersion, double prior_var, void *out,
-         int out_is_device, long long ld_out, double *intercept, int *steps, int *flags, long long *bad_row, int *bad_col) {
+int rlog(const void *y, long long ld, int m, int n_genes, const double *sf, const double *dispersion, double prior_var, ResultMatrix res,
+         double *intercept, int *steps, int *flags, long long *bad_row, int *bad_col) {
     if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
     const size_t G = (size_t)n_genes, M = (size_t)m;
     std::vector<double> s(2 * M);                            // the size factors, then their logarithms
@@ -184,28 +206,26 @@ int rlog(const void *y, long long ld, int m, int n_genes, const double *sf, cons
     int *d_int;                                              // steps, flags
     HIP_TRY(pilot::ws(pilot::WS_NB_SF, 2 * M, &d_sf));
     HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G, &d_disp));
-    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, G + (out_is_device ? 0 : M * G), &d_dbl));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, G + res.tail(), &d_dbl));
     HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 2 * G, &d_int));
     HIP_TRY(hipMemcpy(d_sf, s.data(), sizeof(double) * 2 * M, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_disp, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
-    double *d_res = out_is_device ? static_cast<double *>(out) : d_dbl + G;
-    const long long ld_res = out_is_device ? ld_out : (long long)n_genes;
+    res.place(d_dbl + G);
     const double ln2 = pilot::NB_RLOG_LN2, lambda = ln2 * ln2 / prior_var, lambda0 = pilot::NB_RLOG_INTERCEPT_RIDGE * ln2 * ln2;
     if (int rc = launch_wave_per_gene(pilot::nb_rlog_kernel<T>, n_genes, 3 * M, static_cast<const T *>(y), ld, m, d_sf, d_disp, lambda, lambda0,
-                                      d_res, ld_res, d_dbl, d_int, d_int + G))
+                                      res.dev, res.ld(), d_dbl, d_int, d_int + G))
         return rc;
-    if (!out_is_device)
-        HIP_TRY(hipMemcpy2D(out, sizeof(double) * (size_t)ld_out, d_res, sizeof(double) * G, sizeof(double) * G, M, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(intercept, d_dbl, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(steps, d_int, sizeof(int) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags, d_int + G, sizeof(int) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(res.fetch());
+    HIP_TRY(fetch(intercept, d_dbl, G));
+    HIP_TRY(fetch(steps, d_int, G));
+    HIP_TRY(fetch(flags, d_int + G, G));
     return PILOT_OT_OK;
 }
 
 template <typename T>
 int cooks(const void *y, long long ld, int m, int n_genes, int k, const DevDesign &dd, const double *dispersion, const double *q, double cutoff,
-          int min_replace, double *alpha_robust, double *max_cooks, int *arg_max, int *n_above, int *n_replace, double *trimmed_base, void *D,
-          int D_is_device, long long ld_D, long long *bad_row, int *bad_col) {
+          int min_replace, double *alpha_robust, double *max_cooks, int *arg_max, int *n_above, int *n_replace, double *trimmed_base,
+          ResultMatrix D, long long *bad_row, int *bad_col) {
     if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
     const size_t G = (size_t)n_genes, M = (size_t)m, n_q = G * (size_t)k;
     size_t P = 1;                                            // the sort buffer: the power of two >= m
@@ -213,23 +233,21 @@ int cooks(const void *y, long long ld, int m, int n_genes, int k, const DevDesig
     double *d_in, *d_out;                                    // dispersion | q;  the three double results | packed D for a host D
     int *d_int;
     HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G + n_q, &d_in));
-    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, 3 * G + (D && !D_is_device ? M * G : 0), &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, 3 * G + D.tail(), &d_out));
     HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 3 * G, &d_int));
     HIP_TRY(hipMemcpy(d_in, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_in + G, q, sizeof(double) * n_q, hipMemcpyHostToDevice));
-    double *d_D = !D ? nullptr : (D_is_device ? static_cast<double *>(D) : d_out + 3 * G);
-    const long long ld_dev = D_is_device ? ld_D : (long long)n_genes;
+    D.place(d_out + 3 * G);
     if (int rc = launch_wave_per_gene(pilot::nb_cooks_kernel<T>, n_genes, 2 * M + P, static_cast<const T *>(y), ld, m, k, dd.order, dd.gof, dd.ss,
-                                      dd.gstart, d_in, d_in + G, cutoff, min_replace, n_genes, d_out, d_int, d_D, ld_dev))
+                                      dd.gstart, d_in, d_in + G, cutoff, min_replace, n_genes, d_out, d_int, D.dev, D.ld()))
         return rc;
-    HIP_TRY(hipMemcpy(alpha_robust, d_out, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(max_cooks, d_out + G, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(trimmed_base, d_out + 2 * G, sizeof(double) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(arg_max, d_int, sizeof(int) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(n_above, d_int + G, sizeof(int) * G, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(n_replace, d_int + 2 * G, sizeof(int) * G, hipMemcpyDeviceToHost));
-    if (D && !D_is_device)
-        HIP_TRY(hipMemcpy2D(D, sizeof(double) * (size_t)ld_D, d_D, sizeof(double) * G, sizeof(double) * G, M, hipMemcpyDeviceToHost));
+    HIP_TRY(fetch(alpha_robust, d_out, G));
+    HIP_TRY(fetch(max_cooks, d_out + G, G));
+    HIP_TRY(fetch(trimmed_base, d_out + 2 * G, G));
+    HIP_TRY(fetch(arg_max, d_int, G));
+    HIP_TRY(fetch(n_above, d_int + G, G));
+    HIP_TRY(fetch(n_replace, d_int + 2 * G, G));
+    HIP_TRY(D.fetch());
     return PILOT_OT_OK;
 }
 
@@ -396,8 +414,8 @@ PILOT_API int pilot_ot_nb_rlog(const void *Y, int Y_is_device, int dtype, long l
             }))
         return rc;
     if (int rc = by_dtype(dtype, [&](auto t) {
-            return rlog<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, size_factors, dispersion, prior_var, out, out_is_device, ld_out, intercept, steps,
-                                     flags, bad_row, bad_col);
+            return rlog<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, size_factors, dispersion, prior_var,
+                                     ResultMatrix{out, out_is_device, ld_out, (size_t)m, (size_t)n_genes}, intercept, steps, flags, bad_row, bad_col);
         }))
         return rc;
     count_flag(flags, n_genes, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
@@ -434,6 +452,6 @@ PILOT_API int pilot_ot_nb_cooks(const void *Y, int Y_is_device, int dtype, long 
         return rc;
     return by_dtype(dtype, [&](auto t) {
         return cooks<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, n_groups, c.dd, dispersion, q, cutoff, min_replace, alpha_robust, max_cooks, arg_max,
-                                  n_above, n_replace, trimmed_base, D, D_is_device, ld_D, bad_row, bad_col);
+                                  n_above, n_replace, trimmed_base, ResultMatrix{D, D_is_device, ld_D, (size_t)m, (size_t)n_genes}, bad_row, bad_col);
     });
 }

@@ -884,6 +884,13 @@ def _device_result(rows, cols):
     return DeviceMatrix(buf.ptr, rows, owner=buf, shape=(rows, cols), dtype=np.float64)
 
 
+def _result_matrix(rows, cols, on_device):
+    """a rows x cols float64 result for a call that writes either to the host or into HBM: ``(numpy array or DeviceMatrix, the
+    pointer the call is given)``"""
+    out = _device_result(rows, cols) if on_device else np.empty((rows, cols), dtype=np.float64)
+    return out, ctypes.c_void_p(out.ptr if on_device else out.ctypes.data)
+
+
 def download(D):
     """The contents of a :class:`DeviceMatrix` as a numpy array."""
     out = np.empty(D.shape, dtype=D.dtype)
@@ -906,10 +913,10 @@ def segment_std(Y, offsets, cols=None, device=False):
     if cols is not None:
         cols = np.ascontiguousarray(np.ravel(cols), dtype=np.int32)
     n_sel = n_cols if cols is None else cols.size
-    out = _device_result(S, n_sel) if device else np.empty((S, n_sel), dtype=np.float64)
+    out, out_ptr = _result_matrix(S, n_sel, device)
     _lib.check(_lib.load().pilot_ot_segment_std(
         Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, n_cols, Y.ld, _lib.lptr(offsets), S,
-        None if cols is None else _lib.iptr(cols), n_sel, ctypes.c_void_p(out.ptr if device else out.ctypes.data), int(device)))
+        None if cols is None else _lib.iptr(cols), n_sel, out_ptr, int(device)))
     return out
 
 
@@ -1316,6 +1323,13 @@ def _nb_dispersion_arg(dispersion, n_genes, m, shape_checked=False):
     return alpha
 
 
+def _positive_finite_arg(name, v):
+    """the scalar ``v`` as a float: a positive finite number, no string, bool or array"""
+    if isinstance(v, (str, bytes, bool)) or not np.isscalar(v) or not (np.isfinite(v) and v > 0):
+        raise ValueError("%s=%r must be positive and finite" % (name, v))
+    return float(v)
+
+
 def _nb_sample_limit(name, m):
     """``name``'s refusal of more samples than a gene can stage in LDS (the first call that loads the library)"""
     limit = nb_glm_limits()
@@ -1410,8 +1424,8 @@ def nb_trend(base_mean, disp, fit_type="parametric"):
     if not use.any():
         raise ValueError("fit_type=%r: no gene has a dispersion estimate of at least %g" % (fit_type, 100 * NB_MIN_DISP))
     if fit_type == "mean":
-        a0 = float(disp[use].mean())
-        return np.where(np.isfinite(mean), a0, np.nan), {"fit_type": "mean", "coefficients": (a0, 0.0), "used": use, "passes": 0}
+        info = {"fit_type": "mean", "coefficients": (float(disp[use].mean()), 0.0), "used": use, "passes": 0}
+        return nb_trend_at(info, mean), info
     failed = "fit_type='parametric': the dispersion trend a0 + a1 / mean did not fit (%s); use fit_type='mean'"
     inv = np.zeros_like(mean)
     inv[use] = 1.0 / mean[use]
@@ -1444,9 +1458,23 @@ def nb_trend(base_mean, disp, fit_type="parametric"):
             break
     else:
         raise ValueError(failed % "more than 10 passes")
+    info = {"fit_type": "parametric", "coefficients": (float(coefs[0]), float(coefs[1])), "used": good, "passes": passes}
+    return nb_trend_at(info, mean), info
+
+
+def nb_trend_at(info, base_mean):
+    """The trend :func:`nb_trend` fitted (its ``info``: ``fit_type`` and ``coefficients`` (a0, a1) are read) at every
+    ``base_mean``; pure numpy.  ``"parametric"``: ``a0 + a1 / base_mean`` (infinite at 0); ``"mean"``: a0 wherever the mean is
+    finite; NaN for a NaN mean.  What :func:`nb_trend` returns as ``fitted``, and what a refit of some genes reads when the trend
+    of the first fit stays."""
+    mean = np.asarray(base_mean, dtype=np.float64)
+    a0, a1 = info["coefficients"]
+    if info["fit_type"] == "mean":
+        return np.where(np.isfinite(mean), a0, np.nan)
+    if info["fit_type"] != "parametric":
+        raise ValueError("fit_type=%r must be 'parametric' or 'mean'" % (info["fit_type"],))
     with np.errstate(divide="ignore", invalid="ignore"):
-        fitted = coefs[0] + coefs[1] / mean
-    return fitted, {"fit_type": "parametric", "coefficients": (float(coefs[0]), float(coefs[1])), "used": good, "passes": passes}
+        return a0 + a1 / mean
 
 
 def nb_prior_var(log_disp, log_trend, m, k):
@@ -1644,17 +1672,15 @@ def nb_rlog(counts, size_factors, dispersion, prior_var, on_device=False, return
     Y = _dense_arg(counts, "counts", mode="strict")
     sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
     alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
-    if isinstance(prior_var, (str, bytes, bool)) or not np.isscalar(prior_var) or not (np.isfinite(prior_var) and prior_var > 0):
-        raise ValueError("prior_var=%r must be positive and finite" % (prior_var,))
+    prior_var = _positive_finite_arg("prior_var", prior_var)
     _nb_sample_limit("nb_rlog", Y.rows)
-    out = _device_result(Y.rows, Y.cols) if on_device else np.empty((Y.rows, Y.cols), dtype=np.float64)
+    out, out_ptr = _result_matrix(Y.rows, Y.cols, on_device)
     intercept = np.empty(Y.cols)
     steps, flags = np.empty(Y.cols, dtype=np.int32), np.empty(Y.cols, dtype=np.int32)
     bad = ctypes.c_int(0)
     _nb_call(_lib.load().pilot_ot_nb_rlog,
-             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(alpha), float(prior_var),
-             ctypes.c_void_p(out.ptr if on_device else out.ctypes.data), int(bool(on_device)), Y.cols, _lib.dptr(intercept),
-             _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad))
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(sf), _lib.dptr(alpha), prior_var, out_ptr,
+             int(bool(on_device)), Y.cols, _lib.dptr(intercept), _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad))
     return (out, {"intercept": intercept, "steps": steps, "flags": flags, "n_not_converged": bad.value}) if return_info else out
 
 
@@ -1673,9 +1699,7 @@ def nb_cooks_cutoff(m, p):
 
 
 def _nb_cutoff_arg(cutoff):
-    if isinstance(cutoff, (str, bytes, bool)) or not np.isscalar(cutoff) or not (np.isfinite(cutoff) and cutoff > 0):
-        raise ValueError("cutoff=%r must be positive and finite" % (cutoff,))
-    return float(cutoff)
+    return _positive_finite_arg("cutoff", cutoff)
 
 
 def _nb_min_replace_arg(min_replace):
@@ -1714,14 +1738,11 @@ def nb_cooks(counts, codes, n_groups, size_factors, dispersion, q, cutoff, min_r
     out = {name: np.empty(Y.cols) for name in ("alpha_robust", "max_cooks", "trimmed_base")}
     out.update({name: np.empty(Y.cols, dtype=np.int32) for name in ("arg_max", "n_above", "n_replace")})
     on_device = return_distances == "device"
-    D = None
-    if return_distances:
-        D = _device_result(Y.rows, Y.cols) if on_device else np.empty((Y.rows, Y.cols), dtype=np.float64)
+    D, D_ptr = _result_matrix(Y.rows, Y.cols, on_device) if return_distances else (None, None)
     _nb_call(_lib.load().pilot_ot_nb_cooks,
              Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.iptr(codes), n_groups, _lib.dptr(sf), _lib.dptr(alpha),
              _lib.dptr(q), cutoff, min_replace, _lib.dptr(out["alpha_robust"]), _lib.dptr(out["max_cooks"]), _lib.iptr(out["arg_max"]),
-             _lib.iptr(out["n_above"]), _lib.iptr(out["n_replace"]), _lib.dptr(out["trimmed_base"]),
-             None if D is None else ctypes.c_void_p(D.ptr if on_device else D.ctypes.data), int(on_device), Y.cols)
+             _lib.iptr(out["n_above"]), _lib.iptr(out["n_replace"]), _lib.dptr(out["trimmed_base"]), D_ptr, int(on_device), Y.cols)
     if D is not None:
         out["D"] = D
     return out
@@ -2175,9 +2196,8 @@ def fitted_curves(params, model, times, noise=None, device=False):
         if (noise.rows, noise.cols) != (T, G):
             raise ValueError("noise must be T x G = %d x %d, got %d x %d" % (T, G, noise.rows, noise.cols))
         sp, s_dev = noise.ptr, noise.on_dev
-    out = _device_result(G, T) if device else np.empty((G, T), dtype=np.float64)
-    _lib.check(_lib.load().pilot_ot_fitted_curves(_lib.dptr(params), _lib.iptr(model), G, _lib.dptr(times), T, sp, s_dev,
-                                                  ctypes.c_void_p(out.ptr if device else out.ctypes.data), int(device)))
+    out, out_ptr = _result_matrix(G, T, device)
+    _lib.check(_lib.load().pilot_ot_fitted_curves(_lib.dptr(params), _lib.iptr(model), G, _lib.dptr(times), T, sp, s_dev, out_ptr, int(device)))
     return out
 
 

@@ -2328,8 +2328,16 @@ def _nb_counts(cluster_counts, who):
     return np.ascontiguousarray(c), pd.Index(names if names is not None else np.arange(c.shape[1]))
 
 
-def _nb_dispersion_table(c, genes, codes, k, sf, fit_type):
-    """steps 1-5 of DESIGN.md K22 for the samples x genes array c: the frame of :func:`deseq2_dispersions`"""
+def _estimated_or_positive(who, name, v):
+    """``v`` is None (the caller estimates it) or a positive finite number that is no bool"""
+    if v is not None and not (isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v) and v > 0):
+        raise ValueError("%s: %s=%r must be positive and finite (None: estimated)" % (who, name, v))
+
+
+def _nb_dispersion_table(c, genes, codes, k, sf, fit_type, frozen=None):
+    """steps 1-5 of DESIGN.md K22 for the samples x genes array c: the frame of :func:`deseq2_dispersions`.  ``frozen``: the attrs
+    of an earlier table, whose trend (``engine.nb_trend_at``) and two prior widths are used as they are instead of estimated
+    (``fit_type`` is not read): the refit of DESIGN.md K25.  On the counts of that table it returns the table again, bit for bit."""
     m = c.shape[0]
     x_gene = engine.nb_dispersions(c, codes, k, sf)
     q = np.rint(c.astype(np.float64)) / sf[:, None]
@@ -2337,9 +2345,14 @@ def _nb_dispersion_table(c, genes, codes, k, sf, fit_type):
     base_mean[np.isnan(x_gene)] = np.nan
     base_var[np.isnan(x_gene)] = np.nan
     disp_gene = engine.nb_clip(np.exp(x_gene), m)               # (the grid's end points are the bounds up to an ulp)
-    fit, trend = engine.nb_trend(base_mean, disp_gene, fit_type)
-    log_fit = np.log(fit)
-    prior_var, var_log_disp = engine.nb_prior_var(x_gene, log_fit, m, k)
+    if frozen is None:
+        fit, trend = engine.nb_trend(base_mean, disp_gene, fit_type)
+        log_fit = np.log(fit)
+        prior_var, var_log_disp = engine.nb_prior_var(x_gene, log_fit, m, k)
+    else:
+        trend, prior_var, var_log_disp = frozen["trend"], frozen["prior_var"], frozen["var_log_disp"]
+        fit = engine.nb_trend_at(trend, base_mean)
+        log_fit = np.log(fit)
     x_map = engine.nb_dispersions(c, codes, k, sf, log_prior_mean=log_fit, prior_var=prior_var)
     with np.errstate(invalid="ignore"):
         outlier = x_gene > log_fit + 2.0 * np.sqrt(var_log_disp)
@@ -2385,6 +2398,29 @@ def deseq2_dispersions(cluster_counts, groups, size_factors=None, fit_type="para
     return _nb_dispersion_table(c, genes, codes.astype(np.int32), len(uniq), sf, fit_type)
 
 
+class _NBFit:
+    """One fit of the two-group model: the frame of :func:`deseq2_dispersions` and, genes x groups at its final dispersions, the
+    normalised means ``q``, their information ``w`` and the ``flags`` of ``engine.nb_group_fits``."""
+
+    def __init__(self, table, q, w, flags):
+        self.table, self.q, self.w, self.flags = table, q, w, flags
+
+    def with_rows(self, rep, sub):
+        """a copy with the rows of ``sub``, a fit of the genes at the positions ``rep``, written over its own"""
+        table, q, w, flags = self.table.copy(), self.q.copy(), self.w.copy(), self.flags.copy()
+        for j, name in enumerate(table.columns):
+            table.iloc[rep, j] = sub.table[name].to_numpy()
+        q[rep], w[rep], flags[rep] = sub.q, sub.w, sub.flags
+        return _NBFit(table, q, w, flags)
+
+
+def _nb_fit(c, genes, codes, sf, fit_type, frozen=None):
+    """the :class:`_NBFit` of two groups: :func:`_nb_dispersion_table` (which reads ``frozen``) and the group fits at its dispersions"""
+    table = _nb_dispersion_table(c, genes, codes, 2, sf, fit_type, frozen)
+    q, w, info = engine.nb_group_fits(c, codes, 2, sf, table["dispersion"].to_numpy(), return_info=True)
+    return _NBFit(table, q, w, info["flags"])
+
+
 def _nb_padj(p, base_mean, filtering_alpha):
     """``padj`` of the p-values in gene order: plain BH over the genes with one, or with ``filtering_alpha``
     ``engine.independent_filtering``; ``(padj, info or None)``"""
@@ -2396,11 +2432,12 @@ def _nb_padj(p, base_mean, filtering_alpha):
     return padj, None
 
 
-def _nb_wald_table(genes, table, q, w, cooks=None, filtering_alpha=None):
-    """the host tail of the Wald test: group 1 over group 0 of the fits (q, w), rows ordered by padj (NaN last, stable).
+def _nb_wald_table(genes, fit, cooks=None, filtering_alpha=None):
+    """the host tail of the Wald test: group 1 over group 0 of the :class:`_NBFit` ``fit``, rows ordered by padj (NaN last, stable).
     ``cooks``: the columns maxCooks, cooksOutlier and replace in gene order (a flagged gene loses its p-value before the
     adjustment); ``filtering_alpha``: independent filtering instead of plain BH (its info dict goes to attrs)"""
     from scipy import stats
+    table, q, w = fit.table, fit.q, fit.w
     with np.errstate(divide="ignore", invalid="ignore"):
         lfc = np.log2(q[:, 1]) - np.log2(q[:, 0])                   # (as a difference: swapping the groups negates it exactly)
         se = np.log2(np.e) * np.sqrt(1.0 / w[:, 0] + 1.0 / w[:, 1])
@@ -2424,13 +2461,18 @@ _DE_OUTLIERS = (None, "deseq2")
 _REPLACED_COLUMNS = ["gene", "sample", "count", "replacement"]
 
 
+def _alpha_arg(who, alpha):
+    if isinstance(alpha, (str, bytes, bool)) or not np.isscalar(alpha) or not 0 < alpha < 1:
+        raise ValueError("%s: alpha=%r must be in (0, 1)" % (who, alpha))
+    return float(alpha)
+
+
 def _check_de_options(outliers, independent_filtering, alpha, who):
     if not (outliers is None or (isinstance(outliers, str) and outliers in _DE_OUTLIERS)):
         raise ValueError("%s: outliers=%r must be None or 'deseq2'" % (who, outliers))
     if not isinstance(independent_filtering, (bool, np.bool_)):
         raise ValueError("%s: independent_filtering=%r must be True or False" % (who, independent_filtering))
-    if isinstance(alpha, (str, bytes, bool)) or not np.isscalar(alpha) or not 0 < alpha < 1:
-        raise ValueError("%s: alpha=%r must be in (0, 1)" % (who, alpha))
+    _alpha_arg(who, alpha)
 
 
 def _apply_replaced(c, genes, samples, replaced, who):
@@ -2463,50 +2505,31 @@ def _nb_refit_max_cooks(new, codes, D, min_replace):
     return max_cooks, n_above
 
 
-def _nb_outliers(c, genes, samples, codes, sf, table, q, w, flags, min_replace=engine.NB_COOKS_MIN_REPLACE):
-    """steps 1-6 of DESIGN.md K25 after the fit of :func:`compute_pseudobulk_DE`: the distances, the replacements and the refit
-    of the genes that had one.  Returns ``(table, q, w, flags, cooks, extra)``: the first four with the refitted genes' rows
-    replaced (copies), ``cooks`` the gene-order columns maxCooks / cooksOutlier / replace, ``extra`` the new attrs."""
-    m = c.shape[0]
-    cutoff = engine.nb_cooks_cutoff(m, 2)
-    ck = engine.nb_cooks(c, codes, 2, sf, table["dispersion"].to_numpy(), q, cutoff, min_replace)
+def _nb_outliers(c, genes, samples, codes, sf, fit, min_replace=engine.NB_COOKS_MIN_REPLACE):
+    """steps 1-6 of DESIGN.md K25 after the fit of :func:`compute_pseudobulk_DE` (``fit``, an :class:`_NBFit`): the distances,
+    the replacements and the refit of the genes that had one.  Returns ``(fit, cooks, extra)``: the fit with the refitted genes'
+    rows replaced (a copy), ``cooks`` the gene-order columns maxCooks / cooksOutlier / replace, ``extra`` the new attrs."""
+    cutoff = engine.nb_cooks_cutoff(c.shape[0], 2)
+    disp = fit.table["dispersion"].to_numpy()
+    ck = engine.nb_cooks(c, codes, 2, sf, disp, fit.q, cutoff, min_replace)
     max_cooks, n_above = ck["max_cooks"].copy(), ck["n_above"].copy()
     rep = np.flatnonzero(ck["n_replace"] > 0)
     replaced = pd.DataFrame({name: [] for name in _REPLACED_COLUMNS})
-    extra = {"cooks_cutoff": cutoff}
     if rep.size:
         sub = np.ascontiguousarray(c[:, rep])
-        ck2 = engine.nb_cooks(sub, codes, 2, sf, table["dispersion"].to_numpy()[rep], q[rep], cutoff, min_replace, return_distances=True)
+        ck2 = engine.nb_cooks(sub, codes, 2, sf, disp[rep], fit.q[rep], cutoff, min_replace, return_distances=True)
         rows = engine.nb_replacements(sub, codes, sf, ck2["D"], cutoff, ck2["trimmed_base"], min_replace)
         new = np.rint(sub.astype(np.float64))
         new[rows["sample"], rows["gene"]] = rows["replacement"]
         replaced = pd.DataFrame({"gene": np.asarray(genes)[rep[rows["gene"]]], "sample": np.asarray(samples)[rows["sample"]],
                                  "count": rows["count"], "replacement": rows["replacement"]})
-        # the refit: the gene-wise and MAP estimates anew, the trend and both prior widths as they were
-        x_gene = engine.nb_dispersions(new, codes, 2, sf)
-        qn = new / sf[:, None]
-        base_mean, base_var = qn.mean(axis=0), qn.var(axis=0, ddof=1)
-        base_mean[np.isnan(x_gene)] = np.nan
-        base_var[np.isnan(x_gene)] = np.nan
-        disp_gene = engine.nb_clip(np.exp(x_gene), m)
-        a0, a1 = table.attrs["trend"]["coefficients"]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            fit = a0 + a1 / base_mean if table.attrs["trend"]["fit_type"] == "parametric" else np.where(np.isfinite(base_mean), a0, np.nan)
-        log_fit = np.log(fit)
-        x_map = engine.nb_dispersions(new, codes, 2, sf, log_prior_mean=log_fit, prior_var=table.attrs["prior_var"])
-        with np.errstate(invalid="ignore"):
-            outlier = x_gene > log_fit + 2.0 * np.sqrt(table.attrs["var_log_disp"])
-        disp_map = engine.nb_clip(np.exp(x_map), m)
-        disp = np.where(outlier, disp_gene, disp_map)
-        q2, w2, info2 = engine.nb_group_fits(new, codes, 2, sf, disp, return_info=True)
-        table, q, w, flags = table.copy(), q.copy(), w.copy(), flags.copy()
-        for name, values in (("baseMean", base_mean), ("baseVar", base_var), ("dispGeneEst", disp_gene), ("dispFit", fit),
-                             ("dispMAP", disp_map), ("dispersion", disp), ("dispOutlier", outlier)):
-            table.iloc[rep, table.columns.get_loc(name)] = values
-        q[rep], w[rep], flags[rep] = q2, w2, info2["flags"]
+        # the refit: the same fit of the replaced counts, the trend and both prior widths as they were
+        refit = _nb_fit(new, genes[rep], codes, sf, None, frozen=fit.table.attrs)
+        fit = fit.with_rows(rep, refit)
+        disp = refit.table["dispersion"].to_numpy()
         live = ~np.isnan(disp)
         if live.any():
-            ck3 = engine.nb_cooks(np.ascontiguousarray(new[:, live]), codes, 2, sf, disp[live], q2[live], cutoff, min_replace,
+            ck3 = engine.nb_cooks(np.ascontiguousarray(new[:, live]), codes, 2, sf, disp[live], refit.q[live], cutoff, min_replace,
                                   return_distances=True)
             mc, na = _nb_refit_max_cooks(new[:, live], codes, ck3["D"], min_replace)
             max_cooks[rep[live]], n_above[rep[live]] = mc, na
@@ -2515,13 +2538,45 @@ def _nb_outliers(c, genes, samples, codes, sf, table, q, w, flags, min_replace=e
         flagged = (max_cooks > cutoff) & (n_above < 3)
     replace = np.zeros(len(genes), dtype=bool)
     replace[rep] = True
-    extra["replaced"] = replaced
-    return table, q, w, flags, {"maxCooks": max_cooks, "cooksOutlier": flagged, "replace": replace}, extra
+    return fit, {"maxCooks": max_cooks, "cooksOutlier": flagged, "replace": replace}, {"cooks_cutoff": cutoff, "replaced": replaced}
 
 
 def _check_shrink(shrink, who):
     if shrink not in (None, "apeglm"):
         raise ValueError("%s: shrink=%r must be None or 'apeglm'" % (who, shrink))
+
+
+def _nb_de_intake(who, cluster_counts, groups, de, columns, attrs=(), groups_are="", both_groups=False, first=None, unless=None):
+    """``(cluster_counts, groups, de)`` as :func:`lfc_shrink` and :func:`deseq2_cooks` take them apart, every refusal in ``who``'s
+    name and in the order the two have always made them (which one comes first is behaviour).  ``groups_are`` ends the refusal of
+    the groups in ``who``'s words; ``first()``, ``both_groups`` and ``unless()`` are the checks only one of them makes, each in its
+    old place.  Returns ``(c, genes, samples, codes, sf, at, dispersion)``: the counts with ``attrs['replaced']`` applied, the
+    table's labels, int32 codes, float64 size factors, the frame's row of every gene of the table, its dispersions in that order."""
+    c, genes = _nb_counts(cluster_counts, who)
+    if first:
+        first()
+    codes = np.asarray(groups)
+    if codes.shape != (c.shape[0],):
+        raise ValueError("%s: groups has shape %s for %d samples" % (who, codes.shape, c.shape[0]))
+    if codes.dtype.kind not in "biu" or not np.isin(codes, (0, 1)).all():
+        raise ValueError("%s: groups must be 0 / 1 or boolean%s" % (who, groups_are))
+    codes = codes.astype(np.int32)
+    if both_groups and codes.min() == codes.max():
+        raise ValueError("%s: every sample is in group %d" % (who, codes[0]))
+    if not hasattr(de, "columns") or any(col not in de.columns for col in columns) or any(name not in de.attrs for name in attrs):
+        needed = "; ".join(kind + " " + ", ".join(names) for kind, names in (("columns", columns), ("attrs", attrs)) if names)
+        raise ValueError("%s: de must be a frame of compute_pseudobulk_DE (%s)" % (who, needed))
+    if unless:
+        unless()
+    named = pd.Index(de["gene"])
+    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)
+    if len(de) != len(genes) or (at < 0).any():
+        raise ValueError("%s: the genes of de are not the columns of cluster_counts" % who)
+    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
+    samples = getattr(cluster_counts, "index", pd.RangeIndex(c.shape[0]))
+    if "replaced" in de.attrs:                                   # (outliers="deseq2": the fit is of the replaced counts)
+        c = _apply_replaced(c, genes, samples, de.attrs["replaced"], who)
+    return c, genes, samples, codes, sf, at, de["dispersion"].to_numpy(dtype=np.float64)[at]
 
 
 def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
@@ -2543,40 +2598,22 @@ def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
 
     Not covered: s-values, other coefficients or more than two groups, apeglm's other likelihoods.  The intercept prior sits
     on group 0, as in apeglm, so swapping the groups moves the estimate slightly instead of negating it."""
-    c, genes = _nb_counts(cluster_counts, "lfc_shrink")
-    codes = np.asarray(groups)
-    if codes.shape != (c.shape[0],):
-        raise ValueError("lfc_shrink: groups has shape %s for %d samples" % (codes.shape, c.shape[0]))
-    if codes.dtype.kind not in "biu" or not np.isin(codes, (0, 1)).all():
-        raise ValueError("lfc_shrink: groups must be 0 / 1 or boolean, 1 for the numerator group")
-    codes = codes.astype(np.int32)
-    if codes.min() == codes.max():
-        raise ValueError("lfc_shrink: every sample is in group %d" % codes[0])
-    needed = ["gene", "log2FoldChange", "lfcSE", "dispersion"]
-    if not hasattr(de, "columns") or any(col not in de.columns for col in needed):
-        raise ValueError("lfc_shrink: de must be a frame of compute_pseudobulk_DE (columns %s)" % ", ".join(needed))
-    if "lfcMLE" in de.columns:
-        raise ValueError("lfc_shrink: de is already shrunken (it has a column lfcMLE)")
-    if "size_factors" not in de.attrs or "floored" not in de.attrs:
-        raise ValueError("lfc_shrink: de.attrs lacks 'size_factors' / 'floored': pass the frame compute_pseudobulk_DE returned")
-    if prior_scale is not None and not (isinstance(prior_scale, (int, float, np.integer, np.floating)) and not isinstance(prior_scale, bool)
-                                        and np.isfinite(prior_scale) and prior_scale > 0):
-        raise ValueError("lfc_shrink: prior_scale=%r must be positive and finite (None: estimated)" % (prior_scale,))
-    named = pd.Index(de["gene"])
-    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)      # the frame's row of every gene of the table
-    if len(de) != len(genes) or (at < 0).any():
-        raise ValueError("lfc_shrink: the genes of de are not the columns of cluster_counts")
-    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
+    def shrunken_or_bare():
+        if "lfcMLE" in de.columns:
+            raise ValueError("lfc_shrink: de is already shrunken (it has a column lfcMLE)")
+        if "size_factors" not in de.attrs or "floored" not in de.attrs:
+            raise ValueError("lfc_shrink: de.attrs lacks 'size_factors' / 'floored': pass the frame compute_pseudobulk_DE returned")
+        _estimated_or_positive("lfc_shrink", "prior_scale", prior_scale)
+
+    c, genes, _, codes, sf, at, disp = _nb_de_intake("lfc_shrink", cluster_counts, groups, de, ["gene", "log2FoldChange", "lfcSE", "dispersion"],
+                                                     groups_are=", 1 for the numerator group", both_groups=True, unless=shrunken_or_bare)
     ln2 = np.log(2.0)
-    disp = de["dispersion"].to_numpy(dtype=np.float64)[at]
     lfc, se = de["log2FoldChange"].to_numpy(dtype=np.float64)[at] * ln2, de["lfcSE"].to_numpy(dtype=np.float64)[at] * ln2
     floored = np.asarray(de.attrs["floored"].reindex(genes), dtype=bool)
     if prior_scale is None:
         S, A = engine.nb_prior_scale(lfc, se, use=~floored)
     else:
         S, A = float(prior_scale), float(prior_scale) ** 2
-    if "replaced" in de.attrs:                                   # (outliers="deseq2": the fit is of the replaced counts)
-        c = _apply_replaced(c, genes, getattr(cluster_counts, "index", np.arange(c.shape[0])), de.attrs["replaced"], "lfc_shrink")
     b0, b1, info = engine.nb_shrink(c, codes, sf, disp, engine.nb_far_end(lfc, floored), S, return_info=True)
     sd = engine.nb_posterior_sd(b1, info["w0"], info["w1"], S)
     row = genes.get_indexer(de["gene"])                          # the table's column of every row of the frame
@@ -2624,10 +2661,9 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     shrinkage, the outlier handling and the independent filtering are opt-in (``shrink="apeglm"``, ``outliers="deseq2"``,
     ``independent_filtering=True``; the reference's call has all three on) and the shrunken mode comes from a global grid
     search, not apeglm's local optimiser; no s-values; ``rlog`` is :func:`compute_pseudobulk_PCA`'s; the deviations of the outlier
-    rule are DESIGN.md K25's; no beta
-    ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the formula where DESeq2 simulates; the
-    reference returns R's list (the frame at index 1), this returns the frame.  Fewer than three selected samples, or a group
-    without samples: ValueError before any device work."""
+    rule are DESIGN.md K25's; no beta ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the
+    formula where DESeq2 simulates; the reference returns R's list (the frame at index 1), this returns the frame.  Fewer than
+    three selected samples, or a group without samples: ValueError before any device work."""
     _check_shrink(shrink, "compute_pseudobulk_DE")
     _check_de_options(outliers, independent_filtering, alpha, "compute_pseudobulk_DE")
     if cluster_col is None or cluster_col not in cluster_metadata.columns:
@@ -2645,16 +2681,13 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
         raise ValueError("compute_pseudobulk_DE: %d samples in two groups leave no residual degree of freedom" % codes.size)
     c, genes = _nb_counts(counts, "compute_pseudobulk_DE")
     sf = _nb_size_factors(counts, None, c.shape[0])
-    table = _nb_dispersion_table(c, genes, codes, 2, sf, fit_type)
-    q, w, info = engine.nb_group_fits(c, codes, 2, sf, table["dispersion"].to_numpy(), return_info=True)
-    flags, n_not_converged, cooks, extra = info["flags"], info["n_not_converged"], None, {}
+    fit, cooks, extra = _nb_fit(c, genes, codes, sf, fit_type), None, {}
     if outliers:
-        table, q, w, flags, cooks, extra = _nb_outliers(c, genes, counts.index, codes, sf, table, q, w, flags)
-        n_not_converged = int(np.count_nonzero(flags & engine._lib.NB_NOT_CONVERGED))
-    out = _nb_wald_table(genes, table, q, w, cooks, float(alpha) if independent_filtering else None)
-    floored = pd.Series(((flags & engine._lib.NB_FLOORED) != 0).any(axis=1), index=genes)
-    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=n_not_converged,
-                     floored=floored, **extra)
+        fit, cooks, extra = _nb_outliers(c, genes, counts.index, codes, sf, fit)
+    out = _nb_wald_table(genes, fit, cooks, float(alpha) if independent_filtering else None)
+    floored = pd.Series(((fit.flags & engine._lib.NB_FLOORED) != 0).any(axis=1), index=genes)
+    out.attrs.update(dispersions=fit.table, size_factors=pd.Series(sf, index=counts.index),
+                     n_not_converged=int(np.count_nonzero(fit.flags & engine._lib.NB_NOT_CONVERGED)), floored=floored, **extra)
     return lfc_shrink(counts, codes, out, prior_scale) if shrink else out
 
 
@@ -2666,25 +2699,8 @@ def deseq2_cooks(cluster_counts, groups, de, min_replace=engine.NB_COOKS_MIN_REP
     means are fitted again at the frame's dispersions (``engine.nb_group_fits``).  Returns a frame indexed by gene, in the
     table's column order: ``alpha_robust``, ``max_cooks``, ``arg_max`` (the sample's label; None without one), ``n_above``,
     ``n_replace``, ``trimmed_base``; ``attrs['cooks_cutoff']``."""
-    c, genes = _nb_counts(cluster_counts, "deseq2_cooks")
-    min_replace = engine._nb_min_replace_arg(min_replace)
-    codes = np.asarray(groups)
-    if codes.shape != (c.shape[0],):
-        raise ValueError("deseq2_cooks: groups has shape %s for %d samples" % (codes.shape, c.shape[0]))
-    if codes.dtype.kind not in "biu" or not np.isin(codes, (0, 1)).all():
-        raise ValueError("deseq2_cooks: groups must be 0 / 1 or boolean")
-    codes = codes.astype(np.int32)
-    if not hasattr(de, "columns") or any(col not in de.columns for col in ("gene", "dispersion")) or "size_factors" not in de.attrs:
-        raise ValueError("deseq2_cooks: de must be a frame of compute_pseudobulk_DE (columns gene, dispersion; attrs size_factors)")
-    named = pd.Index(de["gene"])
-    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)
-    if len(de) != len(genes) or (at < 0).any():
-        raise ValueError("deseq2_cooks: the genes of de are not the columns of cluster_counts")
-    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
-    samples = getattr(cluster_counts, "index", pd.RangeIndex(c.shape[0]))
-    if "replaced" in de.attrs:
-        c = _apply_replaced(c, genes, samples, de.attrs["replaced"], "deseq2_cooks")
-    disp = de["dispersion"].to_numpy(dtype=np.float64)[at]
+    c, genes, samples, codes, sf, _, disp = _nb_de_intake("deseq2_cooks", cluster_counts, groups, de, ["gene", "dispersion"], ["size_factors"],
+                                                          first=lambda: engine._nb_min_replace_arg(min_replace))
     cutoff = engine.nb_cooks_cutoff(c.shape[0], 2)
     q, _ = engine.nb_group_fits(c, codes, 2, sf, disp)
     ck = engine.nb_cooks(c, codes, 2, sf, disp, q, cutoff, min_replace)
@@ -2702,15 +2718,14 @@ def independent_filtering(de, alpha=0.05):
     ``attrs['dispersions']`` tells it, else in the frame's), with ``attrs['independent_filtering']`` the info dict."""
     if not hasattr(de, "columns") or any(col not in de.columns for col in ("gene", "baseMean", "pvalue", "padj")):
         raise ValueError("independent_filtering: de must be a frame of compute_pseudobulk_DE (columns gene, baseMean, pvalue, padj)")
-    if isinstance(alpha, (str, bytes, bool)) or not np.isscalar(alpha) or not 0 < alpha < 1:
-        raise ValueError("independent_filtering: alpha=%r must be in (0, 1)" % (alpha,))
+    alpha = _alpha_arg("independent_filtering", alpha)
     out = de.copy()
     table = de.attrs.get("dispersions")
     if table is not None and len(table) == len(de) and table.index.is_unique:
         at = pd.Index(de["gene"]).get_indexer(table.index)
         if (at >= 0).all():
             out = out.iloc[at].reset_index(drop=True)
-    padj, info = engine.independent_filtering(out["pvalue"].to_numpy(dtype=np.float64), out["baseMean"].to_numpy(dtype=np.float64), float(alpha))
+    padj, info = engine.independent_filtering(out["pvalue"].to_numpy(dtype=np.float64), out["baseMean"].to_numpy(dtype=np.float64), alpha)
     out["padj"] = padj
     out = out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
     out.attrs.update(de.attrs)
@@ -2742,9 +2757,7 @@ def rlog(cluster_counts, size_factors=None, fit_type="parametric", prior_var=Non
         raise ValueError("rlog: the table has no genes")
     if fit_type not in ("parametric", "mean"):
         raise ValueError("rlog: fit_type=%r must be 'parametric' or 'mean'" % (fit_type,))
-    if prior_var is not None and not (isinstance(prior_var, (int, float, np.integer, np.floating)) and not isinstance(prior_var, bool)
-                                      and np.isfinite(prior_var) and prior_var > 0):
-        raise ValueError("rlog: prior_var=%r must be positive and finite (None: estimated)" % (prior_var,))
+    _estimated_or_positive("rlog", "prior_var", prior_var)
     sf = _nb_size_factors(cluster_counts, size_factors, m)
     if not (np.isfinite(sf).all() and (sf > 0).all()):
         raise ValueError("rlog: size_factors must be positive and finite")
@@ -2809,9 +2822,9 @@ def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types"
     :func:`pseudobulk_inputs` of ``cell_type``, then :func:`compute_pseudobulk_DE` for every pair of
     ``itertools.combinations(np.unique(proportion_df[cluster_col]), 2)``.  Returns ``{"<g2>vs<g1>": frame}`` (the names of the
     reference's ``_DE.csv`` files; the fold change is g2 over g1).  ``shrink`` is :func:`compute_pseudobulk_DE`'s (``"apeglm"``:
-    the shrunken fold changes the reference writes), and so are ``outliers``, ``independent_filtering`` and ``alpha``.  No plots, no files, no enrichment; the rlog PCA the reference draws first is
-    :func:`compute_pseudobulk_PCA` / :func:`pseudobulk_pca` on :func:`pseudobulk_inputs`' pair; the deviations of
-    :func:`compute_pseudobulk_DE` apply."""
+    the shrunken fold changes the reference writes), and so are ``outliers``, ``independent_filtering`` and ``alpha``.  No plots,
+    no files, no enrichment; the rlog PCA the reference draws first is :func:`compute_pseudobulk_PCA` / :func:`pseudobulk_pca` on
+    :func:`pseudobulk_inputs`' pair; the deviations of :func:`compute_pseudobulk_DE` apply."""
     import itertools
     _check_shrink(shrink, "get_pseudobulk_DE")
     _check_de_options(outliers, independent_filtering, alpha, "get_pseudobulk_DE")

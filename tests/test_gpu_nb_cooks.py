@@ -18,7 +18,7 @@ import pytest
 import nb_cooks_restatement as CR
 import nb_glm_restatement as RR
 from pilot_amd import engine, tl
-from test_nb_cooks_args import check_planted, outliers_by_hand, planted_table
+from test_nb_cooks_args import check_planted, frozen_fit_is_the_identity, outliers_by_hand, planted_table
 
 pytestmark = pytest.mark.gpu
 
@@ -205,6 +205,13 @@ def test_compute_pseudobulk_DE_with_outliers_is_the_host_tail_of_the_engine_call
     alone = tl.compute_pseudobulk_DE(counts, meta, independent_filtering=True, **ARGS)
     pd.testing.assert_frame_equal(alone, tl.independent_filtering(plain), check_exact=True)
     assert list(alone.columns) == list(plain.columns) and "independent_filtering" in alone.attrs
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_a_frozen_fit_of_the_same_counts_is_the_first_fit(monkeypatch, dtype):
+    # 8 + 8 samples x 60 genes: the smallest table of the suite with a replaceable group (min_replace = 7), genes of zeros included
+    counts, meta, _ = planted_table(8, 8, G=60)
+    frozen_fit_is_the_identity(counts.astype(dtype), meta, monkeypatch)
 
 
 def test_lfc_shrink_with_outliers_is_lfc_shrink_on_the_replaced_counts():

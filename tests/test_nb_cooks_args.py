@@ -340,6 +340,73 @@ def test_tl_outliers_on_the_restatement(monkeypatch, n0, n1):
         np.testing.assert_array_equal(per_gene["max_cooks"].to_numpy(), out.set_index("gene").loc[counts.columns, "maxCooks"].to_numpy())
 
 
+def frozen_fit_is_the_identity(counts, meta, monkeypatch):
+    """the property that lets the refit be the first fit's own function: fitted again on the SAME counts with the trend and the
+    two prior widths of the first table frozen, every column of the table, q, w and the flags come back bit for bit -- and neither
+    the trend nor the prior variance is estimated on the way.  (Also run on the device: tests/test_gpu_nb_cooks.py.)"""
+    codes = (meta["Predicted_Labels"] == "T2").to_numpy().astype(np.int32)
+    counts = counts.copy()
+    counts[["g040", "g041"]] = 0                                        # (the planted table has no gene of zeros: two all-NaN rows)
+    c, genes = tl._nb_counts(counts, "frozen_fit")
+    sf = tl.deseq2_size_factors(counts).to_numpy()
+    first = tl._nb_fit(c, genes, codes, sf, "parametric")
+    assert first.table.loc[["g040", "g041"]].drop(columns="dispOutlier").isna().all(axis=None) and np.isnan(first.q[[40, 41]]).all()
+    assert first.table["dispersion"].notna().sum() == 58 and first.table["dispOutlier"].any()    # both kinds of final value
+
+    def estimated(*a, **k):
+        raise AssertionError("the frozen fit estimated its trend or its prior variance")
+    monkeypatch.setattr(engine, "nb_trend", estimated)
+    monkeypatch.setattr(engine, "nb_prior_var", estimated)
+    again = tl._nb_fit(c, genes, codes, sf, None, frozen=first.table.attrs)
+    pd.testing.assert_frame_equal(again.table, first.table, check_exact=True)
+    assert list(again.table.dtypes) == list(first.table.dtypes)
+    for name in ("q", "w", "flags"):
+        np.testing.assert_array_equal(getattr(again, name), getattr(first, name))
+    assert again.table.attrs["trend"] is first.table.attrs["trend"]
+    assert (again.table.attrs["prior_var"], again.table.attrs["var_log_disp"]) == (first.table.attrs["prior_var"], first.table.attrs["var_log_disp"])
+    # and written over its own rows, at any positions, it changes nothing
+    rep = np.array([1, 25, 40])
+    sub = tl._NBFit(first.table.iloc[rep], first.q[rep], first.w[rep], first.flags[rep])
+    patched = first.with_rows(rep, sub)
+    pd.testing.assert_frame_equal(patched.table, first.table, check_exact=True)
+    assert patched.table is not first.table and patched.q is not first.q and np.array_equal(patched.q, first.q, equal_nan=True)
+
+
+def test_a_frozen_fit_of_the_same_counts_is_the_first_fit(monkeypatch):
+    _fakes(monkeypatch)
+    counts, meta, _ = planted_table(8, 8, G=60)
+    frozen_fit_is_the_identity(counts, meta, monkeypatch)
+
+
+@pytest.mark.parametrize("n0,n1", [(5, 5), (8, 8)])
+def test_outliers_make_no_device_call_they_did_not_make_before(monkeypatch, n0, n1):
+    """the device calls of compute_pseudobulk_DE(outliers="deseq2"), in order, with the number of genes each is given: the first
+    fit, the distances, and -- where a gene has a replacement -- the distances of those r genes, their refit, and the distances of
+    the l of them that still have a dispersion"""
+    _fakes(monkeypatch)
+    calls = []
+
+    def recording(name, fake):
+        def call(counts, *a, **kw):
+            calls.append((name, np.shape(counts)[1]) + ((kw.get("return_distances", False),) if name == "nb_cooks" else ()))
+            return fake(counts, *a, **kw)
+        return call
+    for name in ("nb_dispersions", "nb_group_fits", "nb_cooks"):
+        monkeypatch.setattr(engine, name, recording(name, getattr(engine, name)))
+    counts, meta, _ = planted_table(n0, n1, G=60)
+    out = tl.compute_pseudobulk_DE(counts, meta, group1="T1", group2="T2", cluster_col="Predicted_Labels", outliers="deseq2")
+    G = 60
+    want = [("nb_dispersions", G), ("nb_dispersions", G), ("nb_group_fits", G), ("nb_cooks", G, False)]
+    r = int(out["replace"].sum())
+    live = int((out["replace"] & out["dispersion"].notna()).sum())
+    if n0 < 7:
+        assert r == 0
+    else:
+        assert 1 <= live < r                                            # (g025 is emptied by its replacement)
+        want += [("nb_cooks", r, True), ("nb_dispersions", r), ("nb_dispersions", r), ("nb_group_fits", r), ("nb_cooks", live, True)]
+    assert calls == want
+
+
 # ---- the C entry point --------------------------------------------------------------------------------------------------------------------
 GOOD = dict(y=True, dtype=1, m=6, genes=5, ld=5, codes=[0, 1, 0, 1, 1, 0], ng=2, sf=[1.0, 0.5, 2.0, 1.0, 1.5, 0.7], disp=[0.1] * 5,
             q=[[1.0, 2.0]] * 5, cutoff=3.0, min_replace=7, out=True, D=False, ld_D=5)
@@ -465,12 +532,69 @@ def test_tl_refuses_before_the_library(no_library):
         a.update(bad)
         with pytest.raises(ValueError):
             tl.independent_filtering(**a)
-    codes = np.array([0, 1, 0, 1, 1, 0])
+
+
+def _intake_inputs():
+    counts = pd.DataFrame(np.arange(1.0, 31.0).reshape(6, 5), index=list("abcdef"), columns=["g%d" % j for j in range(5)])
+    frame = pd.DataFrame({"gene": counts.columns, "baseMean": 1.0, "log2FoldChange": np.linspace(-1, 1, 5), "lfcSE": 0.3, "stat": 0.0,
+                          "pvalue": 0.5, "padj": 0.5, "dispersion": [0.1, 0.2, 0.3, 0.4, 0.5]})
+    frame.attrs.update(size_factors=pd.Series(np.ones(6), index=counts.index), floored=pd.Series(np.zeros(5, dtype=bool), index=counts.columns))
+    return counts, np.array([0, 1, 0, 1, 1, 0]), frame
+
+
+def _with(frame, **attrs):
+    out = frame.copy()
+    out.attrs.update(attrs)
+    return out
+
+
+def _renamed(frame, names):
+    out = frame.copy()
+    out["gene"] = names
+    return out
+
+
+@pytest.mark.parametrize("who", ["lfc_shrink", "deseq2_cooks"])
+def test_both_readers_of_a_de_frame_refuse_it_the_same_way(no_library, who):
+    """what tl.lfc_shrink and tl.deseq2_cooks check of (cluster_counts, groups, de) alike: each refusal in the caller's own name,
+    before the library is touched.  (The cases deseq2_cooks had in test_tl_refuses_before_the_library live here; what only
+    lfc_shrink refuses is in tests/test_nb_shrink_args.py.)"""
+    counts, codes, frame = _intake_inputs()
+    fn = getattr(tl, who)
     bare = frame.copy()
     bare.attrs = {}
-    for bad in (dict(groups=codes[:5]), dict(groups=codes + 1), dict(groups=codes.astype(float)), dict(de=frame.drop(columns="dispersion")),
-                dict(de=frame.iloc[:4]), dict(de=bare), dict(min_replace=2)):
-        a = dict(cluster_counts=counts, groups=codes, de=frame)
-        a.update(bad)
-        with pytest.raises(ValueError):
-            tl.deseq2_cooks(**a)
+    replaced = lambda **kw: pd.DataFrame({**dict(gene=["g1"], sample=["c"], count=[12.0], replacement=[3.0]), **kw})
+    bad = [
+        (dict(groups=codes[:5]), "groups has shape"), (dict(groups=codes + 1), "groups must be 0 / 1 or boolean"),
+        (dict(groups=codes.astype(float)), "groups must be 0 / 1 or boolean"),
+        (dict(de=frame.drop(columns="dispersion")), "de must be a frame of compute_pseudobulk_DE"),
+        (dict(de=None), "de must be a frame of compute_pseudobulk_DE"),
+        (dict(de=bare), "de.attrs lacks 'size_factors'" if who == "lfc_shrink" else "de must be a frame of compute_pseudobulk_DE"),
+        (dict(de=frame.iloc[:4]), "the genes of de are not the columns"),
+        (dict(de=_renamed(frame, ["g0", "g1", "g2", "g3", "g9"])), "the genes of de are not the columns"),
+        (dict(de=_renamed(frame, ["g0", "g1", "g2", "g3", "g3"])), "the genes of de are not the columns"),
+        (dict(cluster_counts=counts.rename(columns={"g4": "g3"})), "the genes of de are not the columns"),
+        (dict(de=_with(frame, replaced=replaced(sample=["z"]))), "names a gene or a sample"),
+        (dict(de=_with(frame, replaced=replaced(gene=["g7"]))), "names a gene or a sample"),
+        (dict(de=_with(frame, replaced=replaced(count=[13.0]))), "records other counts"),
+    ]
+    for change, text in bad:
+        with pytest.raises(ValueError) as err:
+            fn(**{**dict(cluster_counts=counts, groups=codes, de=frame), **change})
+        assert str(err.value).startswith(who + ": ") and text in str(err.value), (change, str(err.value))
+    with pytest.raises(ValueError, match="size_factors has shape"):
+        fn(counts, codes, _with(frame, size_factors=np.ones(5)))
+    if who == "deseq2_cooks":
+        with pytest.raises(ValueError, match="min_replace=2"):
+            fn(counts, codes, frame, min_replace=2)
+        with pytest.raises(ValueError, match="a samples x genes frame"):     # the table is looked at before min_replace
+            fn(np.ones(6), codes, frame, min_replace=2)
+    # a frame in another row order is no refusal (compute_pseudobulk_DE orders its rows by padj): every check passes, with the
+    # recorded replacement too, and the dispersions are read in the table's order
+    shuffled = _with(frame.iloc[[3, 0, 4, 2, 1]].reset_index(drop=True), replaced=replaced())
+    with pytest.raises(AssertionError, match="the library was touched"):
+        fn(counts, codes, shuffled)
+    c, genes, samples, got_codes, sf, at, disp = tl._nb_de_intake(who, counts, codes, shuffled, ["gene", "dispersion"], ["size_factors"])
+    assert disp.tolist() == [0.1, 0.2, 0.3, 0.4, 0.5] and shuffled["gene"].to_numpy()[at].tolist() == list(counts.columns)
+    assert c[2, 1] == 3.0 and c.sum() == counts.to_numpy().sum() - 9.0 and got_codes.dtype == np.int32 and sf.dtype == np.float64
+    assert list(genes) == list(counts.columns) and list(samples) == list(counts.index)

@@ -185,6 +185,24 @@ def test_trend_mean_and_refusals():
         engine.nb_trend(base_mean[:-1], disp, "mean")
 
 
+@pytest.mark.parametrize("fit_type", ["parametric", "mean"])
+def test_trend_at_is_the_trend_the_fit_returned(fit_type):
+    c, s, x, base_mean = _trend_inputs()
+    disp = np.exp(x)
+    base_mean[[0, 7]], base_mean[[3, 11]] = np.nan, 0.0                # genes without an estimate: the table's NaN mean, and a mean of 0
+    disp[[0, 7, 3, 11]] = np.nan
+    fitted, info = engine.nb_trend(base_mean, disp, fit_type)
+    np.testing.assert_array_equal(engine.nb_trend_at(info, base_mean), fitted)
+    assert np.isnan(fitted[[0, 7]]).all() and np.isfinite(np.delete(fitted, [0, 7, 3, 11])).all()
+    assert (fitted[[3, 11]] == (np.inf if fit_type == "parametric" else info["coefficients"][0])).all()
+    # only the fit type and the coefficients are read, and every mean is evaluated on its own
+    bare = {"fit_type": info["fit_type"], "coefficients": info["coefficients"]}
+    np.testing.assert_array_equal(engine.nb_trend_at(bare, base_mean[::-1]), fitted[::-1])
+    np.testing.assert_array_equal(engine.nb_trend_at(bare, base_mean[5:6]), fitted[5:6])
+    with pytest.raises(ValueError, match="fit_type"):
+        engine.nb_trend_at({"fit_type": "local", "coefficients": (0.1, 1.0)}, base_mean)
+
+
 def test_prior_variance_equals_the_restatement():
     c, s, x, base_mean = _trend_inputs()
     fitted, _ = engine.nb_trend(base_mean, np.exp(x), "parametric")

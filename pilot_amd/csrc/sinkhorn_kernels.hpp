@@ -654,6 +654,20 @@ template <int RT, int NP> struct SplitImage { u32x4_t a[NP][split_kblocks(RT)][R
 #ifndef PILOT_SCALAR_QUOT
 #define PILOT_SCALAR_QUOT 1   // (round 9: the quotient multiplies of the fp16-split update as single v_mul_f32; c3 kernel 0.5694 -> 0.5563 ms, c2 unchanged)
 #endif
+// Round 10, fp16-split fast stream kernels (profiles/r10/loop_control.md).
+// PILOT_TAU_AT_TEST: a column's tau test moves from every update to the updates that test the column's error.  The per-lane packed
+// fp16 maximum runs on across updates (one VGPR: it seeds the first v_pk_maximum3_f16 of an update, and that instruction keeps a NaN a
+// NaN); where a column is pending or capped the maximum is converted and compared, and a column over tau is handed over before its
+// error is looked at.  INVARIANT: the set of handed-over pairs is the one the per-update test finds -- a pair is handed over exactly
+// when one of its updates up to its last test is over tau (or NaN), and over goes before converged, NaN and capped, as it did with
+// the hand-over in front of the test of the same iteration.  Only the update at which such a pair leaves is later, by up to one
+// period (19 wasted updates), and every output of such a pair comes from the tracking kernel, which restarts it from its first update.
+#ifndef PILOT_TAU_AT_TEST
+#define PILOT_TAU_AT_TEST 1
+#endif
+// (Tried with it and taken out: the stop test on the squared error against a precomputed bound, with the square root formed once where
+// a pair retires -- 19 vector instructions and 5 s_nop fewer in the error block, same bits, and c3's kernel 0.8 % SLOWER, alone and on
+// top of this; profiles/r10/loop_control.md.)
 // a * b as ONE v_mul_f32.  The SLP vectoriser pairs the quotient multiplies of adjacent slots (v = b rcp(acc), u = a rcp(acc)) into
 // v_pk_mul_f32 -- 9 of them per update at four row-tiles -- and a packed f32 instruction beside MFMAs holds the SIMD's vector issue for
 // longer than the two plain ones it replaces: 9 instructions more per update and 2 % less time (profiles/r09/loop_stalls.md).  The
@@ -1325,6 +1339,9 @@ sinkhorn_stream_kernel(GridParams p) {
     bool active = false;
     int q = 0, ii = 0, chk = 1, flags = 0, abs_at = -1;
     T errv = T(1), thr = T(0);
+    // fp16-split configuration (see PILOT_TAU_AT_TEST): mrun is the lane's packed fp16 maximum over the column's updates so far
+    constexpr bool TAU_LATE = C::HALF && !TRACK && PILOT_TAU_AT_TEST;
+    unsigned int mrun = 0u;
 #pragma unroll
     for (int t = 0; t < RT; ++t)
 #pragma unroll
@@ -1477,6 +1494,7 @@ sinkhorn_stream_kernel(GridParams p) {
 #pragma unroll
                             for (int h = 0; h < 4; ++h) { PU.p[part][kb][h] = 0u; PV.p[part][kb][h] = 0u; }
                 }
+                if constexpr (TAU_LATE) mrun = 0u;
             }
             if (take) {
                 want = false;
@@ -1515,6 +1533,7 @@ sinkhorn_stream_kernel(GridParams p) {
                 }
                 chk = 1;
                 ii = 0; flags = 0; abs_at = -1; errv = T(1);
+                if constexpr (TAU_LATE) mrun = 0u;     // (a column that idles an update between two pairs runs it on the old pair's pieces)
             }
             if constexpr (C::HALF) {
                 // Histograms of unequal mass (never PILOT's proportions; the ABI takes any P): u grows and v shrinks by the
@@ -1550,7 +1569,7 @@ sinkhorn_stream_kernel(GridParams p) {
                 for (int r = 0; r < NREG; ++r) V[t][r] = dead(t, r) ? T(0) : T(mul_unpacked<QUOT1>(float(B[t][r]), float(M::rcp(ACC[t][r]))));
             quot_panel(V, PV);
             // max(v) over the leading pieces, two elements per instruction; PV is dead once the product below is issued
-            unsigned int m2 = 0u;
+            unsigned int m2 = TAU_LATE ? mrun : 0u;
             {
                 unsigned int pend = 0u;
                 bool have = false;
@@ -1588,9 +1607,13 @@ sinkhorn_stream_kernel(GridParams p) {
                         }
                 if (have) m2 = pk_max3_f16(m2, pend, pend);
             }
+            if constexpr (TAU_LATE) {
+                mrun = m2;                       // (compared where the column is tested, below)
+            } else {
             const f16x2_t mh = __builtin_bit_cast(f16x2_t, m2);
             const float m0 = float(mh[0]), m1 = float(mh[1]);
             mx = (m0 <= tau && m1 <= tau) ? fmax(m0, m1) : __builtin_inff();      // a NaN half counts as over (see below)
+            }
         } else {
         // ---- v = b / (G^T u) --------------------------------------------------------------------------
 #pragma unroll
@@ -1621,8 +1644,10 @@ sinkhorn_stream_kernel(GridParams p) {
         // end at its next error test as "numerical errors" and take the POT-literal kernel, one workgroup per pair -- 65 of the
         // 67 ms of a 600 x 2 call.  There a NaN maximum counts as over (mx = inf, above): the tracking kernel, which iterates
         // f32 values, restarts the pair.)
-        const unsigned long long omask = column_any_mask<C>(active && mx > tau);
-        const bool over = (omask >> col) & 1ull;
+        // (TAU_LATE: not here -- the columns that are pending or capped are tested in front of their error, below)
+        // (omask, over: set again by that late test, for the hand-over code below)
+        unsigned long long omask = TAU_LATE ? 0ull : column_any_mask<C>(active && mx > tau);
+        bool over = (omask >> col) & 1ull;
         if constexpr (TRACK) {
             if (over) {
                 // POT: alpha += reg log u, beta += reg log v, u = v = 1/K.  In total-scaling terms
@@ -1675,13 +1700,14 @@ sinkhorn_stream_kernel(GridParams p) {
         // (fp16-split configuration: the hand-over -- a wave-uniform branch -- waits until the second product is issued, so that
         // quotients, both products and the tau maximum are ONE basic block and the scheduler may run the element-wise work of
         // the first tiles under the MFMAs of the later ones; the product of a column that is being handed over is wasted work)
-        if constexpr (!TRACK && !(C::HALF && PILOT_DEFER_HANDOVER)) hand_over();
+        // (TAU_LATE: no hand-over in the update at all; PILOT_DEFER_HANDOVER then has nothing to defer)
+        if constexpr (!TRACK && !TAU_LATE && !(C::HALF && PILOT_DEFER_HANDOVER)) hand_over();
         ++ii;   // ii updates of (v, u) are done for this column
 
         // ---- ACC = G^T u: feeds the stopping test of this update and the next v ----------------------
         if constexpr (C::HALF) product_h(a_gt.img, PU, ACC);
         else product(a_gt, w_gt, U, ACC, PADC);
-        if constexpr (!TRACK && C::HALF && PILOT_DEFER_HANDOVER) hand_over();
+        if constexpr (!TRACK && !TAU_LATE && C::HALF && PILOT_DEFER_HANDOVER) hand_over();
 
         // ---- POT's stopping rule: the error of update ii-1 is evaluated when (ii-1) % period == 0 ---
         const bool pending = active && ii == chk;
@@ -1738,11 +1764,21 @@ sinkhorn_stream_kernel(GridParams p) {
         if (ballot_b(pending || capped)) {
             T sc = T(1);
             if constexpr (TRACK) sc = (abs_at == ii - 1) ? T(1) / kk : T(1);  // u, v were just reset to 1/K each
+            // TAU_LATE: the tau test of the columns this block tests, on the maximum over all their updates so far (a NaN half counts as
+            // over, as above).  A column over tau is handed over and leaves the test: no iters, no err, no ring slot, no flag.
+            bool fin = capped, tested = pending;
+            if constexpr (TAU_LATE) {
+                const f16x2_t mh = __builtin_bit_cast(f16x2_t, mrun);
+                const float m0 = float(mh[0]), m1 = float(mh[1]);
+                omask = column_any_mask<C>((pending || capped) && !(m0 <= tau && m1 <= tau));
+                over = (omask >> col) & 1ull;
+                hand_over();
+                fin = capped && !over; tested = pending && !over;
+            }
             T e2 = E2_EARLY ? e2_early : lane_e2(sc);
             e2 = group_sum<C>(e2);
             const T e = sqrt(e2);
-            bool fin = capped;
-            if (pending) {
+            if (tested) {
                 errv = e;
                 if (e <= thr) { fin = true; flags |= FLAG_CONVERGED; }
                 else if (e != e) { fin = true; flags |= FLAG_NAN; }   // POT: "Numerical errors at iteration"

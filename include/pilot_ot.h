@@ -708,6 +708,49 @@ int pilot_ot_nb_cooks(const void *Y, int Y_is_device, int dtype, long long m, in
                       double *alpha_robust, double *max_cooks, int *arg_max, int *n_above, int *n_replace, double *trimmed_base, void *D,
                       int D_is_device, long long ld_D, long long *bad_row, int *bad_col);
 
+/* ---- negative-binomial GLM for a general design (K26): the model above with covariates beside the group, `~ batch + stage`.
+ * THIS LIBRARY'S STATEMENT, unpinned (restated in tests/nb_design_restatement.py).  Y, dtype, ld, size_factors and
+ * the same-bits statement as above.  X: m x p, row-major float64 (host), its first column ones, 2 <= p <=
+ * pilot_ot_nb_design_max_cols() = 8, m - p >= 1; the caller vouches for its full column rank.  lambda = 1e-6, the ridge on every
+ * coefficient (natural-log scale).  With a covariate nothing decouples by group: mu_j = s_j exp(x_j^T beta).
+ *
+ * The inner fit, at a dispersion alpha: beta^(alpha) = the maximiser of
+ *     l(beta) = sum_j nbinom.logpmf(c_j; mean mu_j, dispersion alpha) - lambda/2 |beta|^2,
+ * which is strictly concave, so the result is the optimum whatever the path.  The path: Newton steps with the observed information
+ * sum_j w_j x_j x_j^T + lambda I, w = mu (1 + alpha c) / (1 + alpha mu)^2, by a Cholesky solve, the step halved (at most 30 times) while l
+ * would fall (read from the change of l summed term by term, as pilot_ot_nb_rlog's); stopped once max_k |step_k| <= 1e-10, or after
+ * 100 steps with PILOT_OT_NB_NOT_CONVERGED.  A cold fit starts from (log max(mean_j c_j / s_j, minmu), 0, ...).
+ *
+ * pilot_ot_nb_design_dispersions: per gene x = log(alpha) maximising the adjusted PROFILE likelihood (beta is re-solved at every x)
+ *     L(x) = sum_j [lgamma(c_j + r) - lgamma(r) - (c_j + r) log1p(alpha mu~_j) + c_j log(alpha mu~_j)] - 1/2 log det(X^T W X)
+ *            [- (x - log_prior_mean)^2 / (2 prior_var)],  r = 1 / alpha,  mu~_j = max(s_j exp(x_j^T beta^(alpha)), minmu),
+ *            W = diag(mu~_j / (1 + alpha mu~_j))
+ * BY THE SEARCH of pilot_ot_nb_dispersions (six rounds of the 64-point grid from [log minDisp, log maxDisp]).  One wave per gene, a
+ * lane is a grid point; round 0 fits cold, a later round from the coefficients of the round before's winner.  No floating-point sum
+ * crosses lanes: a gene gives the same bits alone and in any batch.
+ * Out (host, n_genes): log_disp, objective; beta (nullable, n_genes x p: the coefficients at the winner); steps (the Newton steps of
+ * all 384 inner fits), flags (PILOT_OT_NB_NOT_CONVERGED if any of them did not converge); *n_not_converged (nullable).  A gene of
+ * zeros, or one whose log_prior_mean is not finite: NaN, steps = flags = 0.
+ * pilot_ot_nb_design_fits: with the gene's dispersion alpha (host; NaN, or a gene of zeros, leaves the gene out: NaN, steps = flags = 0),
+ * one lane per gene: beta (n_genes x p) = beta^(alpha) from a cold start; cov (n_genes x p (p + 1) / 2): the upper triangle, row by
+ * row, of Sigma = (X^T W X + lambda I)^-1 with W at mu~ as above (the plain inverse, not DESeq2's sandwich); loglik = sum_j
+ * nbinom.logpmf(c_j; mu_j, alpha), unpenalised, at the unfloored mu; steps, flags; *n_not_converged (nullable).
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, n_genes < 1, dtype, ld < n_genes, m < 2, a size factor not positive and
+ * finite, with a prior a prior_var not positive and finite, a dispersion outside [minDisp, maxDisp], p outside [2, 8], m - p < 1, a
+ * first column that is not ones, a non-finite X; after the check pass a negative or non-finite count (*bad_row / *bad_col as
+ * pilot_ot_nb_dispersions).  PILOT_OT_ENOTSUP: m > INT_MAX; of pilot_ot_nb_design_dispersions m > pilot_ot_nb_design_max_samples(p)
+ * (a gene's counts, log size factors and design rows are staged in LDS, 8 m (2 + p) bytes of 96 KiB: 1228 samples at p = 8).
+ * pilot_ot_nb_design_max_samples: that limit, or PILOT_OT_EINVAL for a p outside [2, 8]. */
+int pilot_ot_nb_design_max_cols(void);
+int pilot_ot_nb_design_max_samples(int p);
+int pilot_ot_nb_design_dispersions(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                                   const double *size_factors, const double *log_prior_mean, double prior_var, double *log_disp,
+                                   double *objective, double *beta, int *steps, int *flags, int *n_not_converged, long long *bad_row,
+                                   int *bad_col);
+int pilot_ot_nb_design_fits(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                            const double *size_factors, const double *dispersion, double *beta, double *cov, double *loglik, int *steps,
+                            int *flags, int *n_not_converged, long long *bad_row, int *bad_col);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

@@ -1,15 +1,17 @@
-// C ABI of the negative-binomial GLM for a one-factor design (include/pilot_ot.h, section "negative-binomial GLM"; kernels:
-// nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp, nb_cooks_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
+// C ABI of the negative-binomial GLM for a one-factor design and, at the end, for a general one (include/pilot_ot.h, section
+// "negative-binomial GLM"; kernels: nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp, nb_cooks_kernel.hpp, nb_design_kernels.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
 // codes, size factors, dispersions and the results are host arrays.  The host orders the samples by group once per call.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "abi_common.hpp"
 #include "nb_cooks_kernel.hpp"
+#include "nb_design_kernels.hpp"
 #include "nb_glm_kernels.hpp"
 #include "nb_rlog_kernel.hpp"
 #include "nb_shrink_kernel.hpp"
@@ -454,4 +456,151 @@ PILOT_API int pilot_ot_nb_cooks(const void *Y, int Y_is_device, int dtype, long 
         return cooks<decltype(t)>(c.y, c.y_ld, (int)m, n_genes, n_groups, c.dd, dispersion, q, cutoff, min_replace, alpha_robust, max_cooks, arg_max,
                                   n_above, n_replace, trimmed_base, ResultMatrix{D, D_is_device, ld_D, (size_t)m, (size_t)n_genes}, bad_row, bad_col);
     });
+}
+
+// ---- K26: a general design (nb_design_kernels.hpp) ---------------------------------------------------------------------------------
+namespace {
+
+// every check of the design matrix; no HIP call
+int check_design_matrix(const double *X, long long m, int p) {
+    if (p < 2 || p > pilot::NB_DESIGN_MAX_COLS)
+        return fail(PILOT_OT_EINVAL, "p=%d design columns must be in [2, %d]", p, pilot::NB_DESIGN_MAX_COLS);
+    if (m - p < 1) return fail(PILOT_OT_EINVAL, "m=%lld samples and p=%d columns leave no residual degree of freedom", m, p);
+    for (long long j = 0; j < m; ++j) {
+        if (X[j * p] != 1.0) return fail(PILOT_OT_EINVAL, "X[%lld, 0]=%g: the first design column is ones", j, X[j * p]);
+        for (int k = 1; k < p; ++k)
+            if (!std::isfinite(X[j * p + k])) return fail(PILOT_OT_EINVAL, "X[%lld, %d]=%g must be finite", j, k, X[j * p + k]);
+    }
+    return PILOT_OT_OK;
+}
+
+int check_design_samples(long long m, int p) {
+    const int limit = pilot::nb_design_max_samples(p);
+    return m > limit ? fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts, log size factors and design rows are staged in LDS, at most %d for p=%d",
+                            m, limit, p)
+                     : PILOT_OT_OK;
+}
+
+// the size factors, their logarithms and X (m x p) behind each other in HBM: what both kernels read as `sf`
+int upload_design_matrix(const double *sf, const double *X, size_t m, int p, double **dev) {
+    std::vector<double> h((2 + (size_t)p) * m);
+    for (size_t j = 0; j < m; ++j) { h[j] = sf[j]; h[m + j] = std::log(sf[j]); }
+    for (size_t t = 0; t < m * (size_t)p; ++t) h[2 * m + t] = X[t];
+    HIP_TRY(pilot::ws(pilot::WS_NB_SF, h.size(), dev));
+    HIP_TRY(hipMemcpy(*dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+    return PILOT_OT_OK;
+}
+
+// body(std::integral_constant<int, P>()) for the P that is p (checked: 2 .. NB_DESIGN_MAX_COLS)
+template <int P = 2, typename Body> int by_columns(int p, Body body) {
+    if constexpr (P > pilot::NB_DESIGN_MAX_COLS) return fail(PILOT_OT_EINVAL, "p=%d", p);
+    else return p == P ? body(std::integral_constant<int, P>()) : by_columns<P + 1>(p, body);
+}
+
+template <typename T, int P>
+int design_dispersions(const void *y, long long ld, int m, int n_genes, const double *d_sf, const double *log_prior_mean, double prior_var,
+                       double *log_disp, double *objective, double *beta, int *steps, int *flags, long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    const size_t G = (size_t)n_genes;
+    double *d_out, *d_prior = nullptr;
+    int *d_int;
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, (2 + (size_t)P) * G, &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 2 * G, &d_int));
+    if (log_prior_mean) {
+        HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G, &d_prior));
+        HIP_TRY(hipMemcpy(d_prior, log_prior_mean, sizeof(double) * G, hipMemcpyHostToDevice));
+    }
+    if (int rc = launch_wave_per_gene(pilot::nb_design_dispersion_kernel<T, P>, n_genes, (2 + (size_t)P) * (size_t)m, static_cast<const T *>(y), ld,
+                                      m, d_sf, d_prior, prior_var, d_out, d_out + G, d_out + 2 * G, d_int, d_int + G))
+        return rc;
+    HIP_TRY(fetch(log_disp, d_out, G));
+    HIP_TRY(fetch(objective, d_out + G, G));
+    if (beta) HIP_TRY(fetch(beta, d_out + 2 * G, G * P));
+    HIP_TRY(fetch(steps, d_int, G));
+    HIP_TRY(fetch(flags, d_int + G, G));
+    return PILOT_OT_OK;
+}
+
+template <typename T, int P>
+int design_fits(const void *y, long long ld, int m, int n_genes, const double *d_sf, const double *dispersion, double *beta, double *cov,
+                double *loglik, int *steps, int *flags, long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    constexpr size_t TRI = pilot::NB_TRI<P>;
+    const size_t G = (size_t)n_genes;
+    double *d_disp, *d_out;                                  // d_out: beta | cov | loglik
+    int *d_int;
+    HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, G, &d_disp));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, (P + TRI + 1) * G, &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 2 * G, &d_int));
+    HIP_TRY(hipMemcpy(d_disp, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((pilot::nb_design_fit_kernel<T, P>), dim3((unsigned)((G + 255) / 256)), dim3(256), 0, nullptr, static_cast<const T *>(y), ld,
+                       m, n_genes, d_sf, d_disp, d_out, d_out + P * G, d_out + (P + TRI) * G, d_int, d_int + G);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(fetch(beta, d_out, P * G));
+    HIP_TRY(fetch(cov, d_out + P * G, TRI * G));
+    HIP_TRY(fetch(loglik, d_out + (P + TRI) * G, G));
+    HIP_TRY(fetch(steps, d_int, G));
+    HIP_TRY(fetch(flags, d_int + G, G));
+    return PILOT_OT_OK;
+}
+
+}  // namespace
+
+PILOT_API int pilot_ot_nb_design_max_cols(void) { return pilot::NB_DESIGN_MAX_COLS; }
+
+PILOT_API int pilot_ot_nb_design_max_samples(int p) {
+    if (p < 2 || p > pilot::NB_DESIGN_MAX_COLS)
+        return fail(PILOT_OT_EINVAL, "p=%d design columns must be in [2, %d]", p, pilot::NB_DESIGN_MAX_COLS);
+    return pilot::nb_design_max_samples(p);
+}
+
+PILOT_API int pilot_ot_nb_design_dispersions(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X,
+                                             int p, const double *size_factors, const double *log_prior_mean, double prior_var,
+                                             double *log_disp, double *objective, double *beta, int *steps, int *flags,
+                                             int *n_not_converged, long long *bad_row, int *bad_col) {
+    if (n_not_converged) *n_not_converged = 0;
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, false, nullptr, 1, nullptr, nullptr};
+    if (int rc = prologue(
+            c, !Y || !X || !size_factors || !log_disp || !objective || !steps || !flags, bad_row, bad_col,
+            [&] { return log_prior_mean ? positive_finite("prior_var", prior_var, " when a prior is given") : PILOT_OT_OK; },
+            [&] {
+                if (int rc = check_design_matrix(X, m, p)) return rc;
+                return check_design_samples(m, p);
+            }))
+        return rc;
+    double *d_sf;
+    if (int rc = upload_design_matrix(size_factors, X, (size_t)m, p, &d_sf)) return rc;
+    if (int rc = by_dtype(dtype, [&](auto t) {
+            return by_columns(p, [&](auto P) {
+                return design_dispersions<decltype(t), decltype(P)::value>(c.y, c.y_ld, (int)m, n_genes, d_sf, log_prior_mean, prior_var, log_disp,
+                                                                           objective, beta, steps, flags, bad_row, bad_col);
+            });
+        }))
+        return rc;
+    count_flag(flags, n_genes, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
+    return PILOT_OT_OK;
+}
+
+PILOT_API int pilot_ot_nb_design_fits(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                                      const double *size_factors, const double *dispersion, double *beta, double *cov, double *loglik,
+                                      int *steps, int *flags, int *n_not_converged, long long *bad_row, int *bad_col) {
+    if (n_not_converged) *n_not_converged = 0;
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, false, nullptr, 1, nullptr, nullptr};
+    if (int rc = prologue(c, !Y || !X || !size_factors || !dispersion || !beta || !cov || !loglik || !steps || !flags, bad_row, bad_col, no_check,
+                          [&] {
+                              if (int rc = check_dispersions(dispersion, n_genes, m)) return rc;
+                              return check_design_matrix(X, m, p);
+                          }))
+        return rc;
+    double *d_sf;
+    if (int rc = upload_design_matrix(size_factors, X, (size_t)m, p, &d_sf)) return rc;
+    if (int rc = by_dtype(dtype, [&](auto t) {
+            return by_columns(p, [&](auto P) {
+                return design_fits<decltype(t), decltype(P)::value>(c.y, c.y_ld, (int)m, n_genes, d_sf, dispersion, beta, cov, loglik, steps, flags,
+                                                                    bad_row, bad_col);
+            });
+        }))
+        return rc;
+    count_flag(flags, n_genes, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
+    return PILOT_OT_OK;
 }

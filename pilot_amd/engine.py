@@ -1497,6 +1497,115 @@ def nb_prior_var(log_disp, log_trend, m, k):
     return max(var_log_disp - float(special.polygamma(1, (m - k) / 2.0)), 0.25), var_log_disp
 
 
+# ---- negative-binomial GLM for a general design (K26; covariates beside the group: `~ batch + stage`) -------------------------------
+NB_DESIGN_MAX_COLS = 8
+NB_DESIGN_RIDGE = 1e-6
+NB_DESIGN_MAX_COND = 1e8
+
+
+def nb_design_limits():
+    """What the K26 calls take: ``{"max_cols": the most design columns, "max_samples": {p: the most samples
+    :func:`nb_design_dispersions` takes with p columns}}`` (a gene's counts, log size factors and design rows are staged in LDS)."""
+    L = _lib.load()
+    max_cols = int(L.pilot_ot_nb_design_max_cols())
+    return {"max_cols": max_cols, "max_samples": {p: int(L.pilot_ot_nb_design_max_samples(p)) for p in range(2, max_cols + 1)}}
+
+
+def _nb_design_arg(design, m):
+    """the design matrix of a K26 call checked on the host: C-contiguous float64 m x p, its first column ones, ``2 <= p <=
+    NB_DESIGN_MAX_COLS``, ``m - p >= 1``, full column rank and a condition number of at most 1e8"""
+    X = np.asarray(design)
+    if X.ndim != 2 or X.shape[0] != m:
+        raise ValueError("design has shape %s for %d samples: one row per sample" % (X.shape, m))
+    if X.dtype.kind not in "biuf":
+        raise ValueError("design must be numeric, got %s" % X.dtype)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    p = X.shape[1]
+    if not 2 <= p <= NB_DESIGN_MAX_COLS:
+        raise ValueError("design has %d columns: an intercept and 1 to %d more" % (p, NB_DESIGN_MAX_COLS - 1))
+    if m - p < 1:
+        raise ValueError("m=%d samples and p=%d design columns leave no residual degree of freedom" % (m, p))
+    if not np.isfinite(X).all():
+        raise ValueError("design holds a non-finite value")
+    if not (X[:, 0] == 1.0).all():
+        raise ValueError("the first design column must be ones (the intercept)")
+    rank = int(np.linalg.matrix_rank(X))
+    if rank != p:
+        raise ValueError("design has rank %d, fewer than its %d columns" % (rank, p))
+    cond = float(np.linalg.cond(X))
+    if not cond <= NB_DESIGN_MAX_COND:
+        raise ValueError("design has condition number %.3g, more than %g: rescale its columns" % (cond, NB_DESIGN_MAX_COND))
+    return X
+
+
+def nb_design_dispersions(counts, design, size_factors, log_prior_mean=None, prior_var=None, return_info=False):
+    """K26: :func:`nb_dispersions` for a general ``design`` (m x p, the first column ones, ``2 <= p <= NB_DESIGN_MAX_COLS``,
+    ``m - p >= 1``, full column rank, condition number <= 1e8) instead of groups: per gene (column) of ``counts`` the log dispersion
+    that maximises, by the same six rounds of a 64-point grid, the Cox-Reid adjusted PROFILE likelihood (include/pilot_ot.h,
+    "negative-binomial GLM for a general design") -- at every grid point the coefficients are fitted again (the maximiser of the
+    negative-binomial likelihood with the ridge 1e-6 on every coefficient, ``mu_j = s_j exp(x_j^T beta)``), the likelihood is taken at
+    ``max(mu_j, 0.5)`` and the adjustment is ``1/2 log det X^T W X``; with ``log_prior_mean`` and ``prior_var`` the MAP estimate.
+    Returns the float64 log dispersions; with ``return_info`` also a dict: ``objective``, ``beta`` (genes x p, the coefficients at
+    the maximiser), ``steps`` (the Newton steps of all 384 inner fits of a gene), ``flags`` (``_lib.NB_NOT_CONVERGED``) and
+    ``n_not_converged``.  A gene of zeros gives NaN.  The same bits from a repeated call, from float32 and float64 storage, from
+    host and device matrices and for a gene alone or in any batch.  More samples than :func:`nb_design_limits` allows for p:
+    NotImplementedError; a negative or non-finite count: ValueError naming its row and column; every other argument is checked
+    before any device work (ValueError)."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
+    X = _nb_design_arg(design, Y.rows)
+    if (log_prior_mean is None) != (prior_var is None):
+        raise ValueError("log_prior_mean and prior_var come together")
+    if log_prior_mean is not None:
+        log_prior_mean = np.ascontiguousarray(log_prior_mean, dtype=np.float64)
+        if log_prior_mean.shape != (Y.cols,):
+            raise ValueError("log_prior_mean has shape %s for %d genes" % (log_prior_mean.shape, Y.cols))
+        prior_var = float(prior_var)
+        if not (np.isfinite(prior_var) and prior_var > 0):
+            raise ValueError("prior_var=%r must be positive and finite" % (prior_var,))
+    p = X.shape[1]
+    limit = nb_design_limits()["max_samples"][p]
+    if Y.rows > limit:
+        raise NotImplementedError("nb_design_dispersions: %d samples; a gene is staged in LDS, at most %d with %d design columns"
+                                  % (Y.rows, limit, p))
+    x, objective, beta = np.empty(Y.cols), np.empty(Y.cols), np.empty((Y.cols, p))
+    steps, flags = np.empty(Y.cols, dtype=np.int32), np.empty(Y.cols, dtype=np.int32)
+    bad = ctypes.c_int(0)
+    _nb_call(_lib.load().pilot_ot_nb_design_dispersions,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(X), p, _lib.dptr(sf),
+             None if log_prior_mean is None else _lib.dptr(log_prior_mean), 0.0 if prior_var is None else prior_var, _lib.dptr(x),
+             _lib.dptr(objective), _lib.dptr(beta), _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad))
+    info = {"objective": objective, "beta": beta, "steps": steps, "flags": flags, "n_not_converged": bad.value}
+    return (x, info) if return_info else x
+
+
+def nb_design_fits(counts, design, size_factors, dispersion, return_info=False):
+    """K26: per gene the coefficients of the negative-binomial GLM ``mu_j = s_j exp(x_j^T beta)`` at the gene's ``dispersion`` (one
+    per gene in [1e-8, max(10, m)]; NaN, or a gene of zeros, leaves the gene out: NaN results) -- the maximiser of the likelihood with
+    the ridge 1e-6 on every coefficient, natural-log scale (include/pilot_ot.h).  ``counts``, ``design`` and ``size_factors`` are
+    :func:`nb_design_dispersions`'s.  Returns ``(beta, cov, loglik)``: genes x p; genes x p x p, ``(X^T W X + 1e-6 I)^-1`` with
+    ``W = diag(mu~ / (1 + alpha mu~))``, ``mu~ = max(mu, 0.5)`` (the plain inverse, not DESeq2's sandwich); and the unpenalised
+    log likelihood at the unfloored means.  With ``return_info`` also a dict: ``steps``, ``flags`` (``_lib.NB_NOT_CONVERGED``)
+    and ``n_not_converged``.  Errors as :func:`nb_design_dispersions` (no limit on the samples)."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
+    X = _nb_design_arg(design, Y.rows)
+    alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
+    p = X.shape[1]
+    beta, packed, loglik = np.empty((Y.cols, p)), np.empty((Y.cols, p * (p + 1) // 2)), np.empty(Y.cols)
+    steps, flags = np.empty(Y.cols, dtype=np.int32), np.empty(Y.cols, dtype=np.int32)
+    bad = ctypes.c_int(0)
+    _nb_call(_lib.load().pilot_ot_nb_design_fits,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(X), p, _lib.dptr(sf), _lib.dptr(alpha),
+             _lib.dptr(beta), _lib.dptr(packed), _lib.dptr(loglik), _lib.iptr(steps), _lib.iptr(flags), ctypes.byref(bad))
+    iu = np.triu_indices(p)
+    cov = np.empty((Y.cols, p, p))
+    cov[:, iu[0], iu[1]] = packed
+    cov[:, iu[1], iu[0]] = packed
+    info = {"steps": steps, "flags": flags, "n_not_converged": bad.value}
+    return (beta, cov, loglik, info) if return_info else (beta, cov, loglik)
+
+
 # ---- shrunken fold changes (K23; apeglm's posterior mode for the two groups of pilotpy's compute_pseudobulk_DE) ----------------
 NB_INTERCEPT_SCALE = 15.0
 NB_FAR_END_FLOORED = 30.0

@@ -2272,18 +2272,39 @@ def pseudobulk_counts(adata, cell_type=None, celltype_col="cell_types", sample_c
     return out
 
 
+def _sample_constant_obs(adata, sample_col, columns, samples):
+    """the ``adata.obs`` columns ``columns`` as a frame indexed by ``samples``: the one value every cell of a sample carries"""
+    missing = [col for col in columns if col not in adata.obs.columns]
+    if missing:
+        raise ValueError("pseudobulk_inputs: obs_columns %r are not columns of adata.obs" % (missing,))
+    out = {}
+    for col in columns:
+        per_sample = adata.obs.groupby(sample_col, observed=True)[col]
+        spread = per_sample.nunique(dropna=False).reindex(samples)
+        if (spread > 1).any():
+            raise ValueError("pseudobulk_inputs: obs[%r] is not constant within sample %r" % (col, spread.index[(spread > 1).to_numpy()][0]))
+        out[col] = per_sample.first().reindex(samples).to_numpy()
+    return pd.DataFrame(out, index=samples)
+
+
 def pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
-                      remove_samples=()):
+                      remove_samples=(), obs_columns=()):
     """``(cluster_counts, cluster_metadata)`` as ``get_pseudobulk_DE`` hands them to DESeq2 (plot/pseudobulk_DE_analysis.py:
     597-610): the samples x genes sums of ``cell_type`` (:func:`pseudobulk_counts`), the rows of ``proportion_df`` for those
     samples with the ``stage`` column (a copy of ``cluster_col``), ``remove_samples`` dropped from both, the metadata in the
     counts' order, and the genes that are zero in every remaining sample dropped.  No plots, CSV files or R: this pair is what the
     reference's ``compute_pseudobulk_DE`` takes, unchanged, and :func:`compute_pseudobulk_DE` here takes it too.  A sample of the
-    cell type that ``proportion_df`` lacks raises KeyError, as in the reference."""
+    cell type that ``proportion_df`` lacks raises KeyError, as in the reference.  ``obs_columns``: columns of ``adata.obs`` that are
+    constant within every sample (batch, sex, age, centre: the covariates of :func:`compute_pseudobulk_DE`), copied into the metadata
+    by sample; one that varies within a sample raises ValueError naming the sample.  The default returns the pair as it always was."""
     cluster_counts = pseudobulk_counts(adata, cell_type, celltype_col, sample_col)
     n_cells = cluster_counts.attrs["n_cells"]
     cluster_metadata = proportion_df.loc[cluster_counts.index.values].copy()
     cluster_metadata["stage"] = cluster_metadata[cluster_col].values
+    if obs_columns is not None and len(obs_columns):
+        extra = _sample_constant_obs(adata, sample_col, list(obs_columns), cluster_metadata.index)
+        for col in extra.columns:
+            cluster_metadata[col] = extra[col].to_numpy()
     for sample in (remove_samples if remove_samples is not None else ()):
         if sample in cluster_metadata.index:
             cluster_metadata = cluster_metadata.drop(index=sample)
@@ -2334,12 +2355,21 @@ def _estimated_or_positive(who, name, v):
         raise ValueError("%s: %s=%r must be positive and finite (None: estimated)" % (who, name, v))
 
 
-def _nb_dispersion_table(c, genes, codes, k, sf, fit_type, frozen=None):
+def _nb_dispersion_table(c, genes, codes, k, sf, fit_type, frozen=None, design=None):
     """steps 1-5 of DESIGN.md K22 for the samples x genes array c: the frame of :func:`deseq2_dispersions`.  ``frozen``: the attrs
     of an earlier table, whose trend (``engine.nb_trend_at``) and two prior widths are used as they are instead of estimated
-    (``fit_type`` is not read): the refit of DESIGN.md K25.  On the counts of that table it returns the table again, bit for bit."""
+    (``fit_type`` is not read): the refit of DESIGN.md K25.  On the counts of that table it returns the table again, bit for bit.
+    ``design``: an m x p design matrix instead of ``codes`` and ``k`` (neither is read): the same steps with the searches of
+    DESIGN.md K26 (``engine.nb_design_dispersions``) and p coefficients in the prior width."""
+    if design is not None:
+        return _nb_table_from(c, genes, lambda **prior: engine.nb_design_dispersions(c, design, sf, **prior), design.shape[1], sf, fit_type, frozen)
+    return _nb_table_from(c, genes, lambda **prior: engine.nb_dispersions(c, codes, k, sf, **prior), k, sf, fit_type, frozen)
+
+
+def _nb_table_from(c, genes, search, k, sf, fit_type, frozen):
+    """:func:`_nb_dispersion_table` around ``search(**prior)``, the log dispersions of the model with k coefficients"""
     m = c.shape[0]
-    x_gene = engine.nb_dispersions(c, codes, k, sf)
+    x_gene = search()
     q = np.rint(c.astype(np.float64)) / sf[:, None]
     base_mean, base_var = q.mean(axis=0), q.var(axis=0, ddof=1)
     base_mean[np.isnan(x_gene)] = np.nan
@@ -2353,7 +2383,7 @@ def _nb_dispersion_table(c, genes, codes, k, sf, fit_type, frozen=None):
         trend, prior_var, var_log_disp = frozen["trend"], frozen["prior_var"], frozen["var_log_disp"]
         fit = engine.nb_trend_at(trend, base_mean)
         log_fit = np.log(fit)
-    x_map = engine.nb_dispersions(c, codes, k, sf, log_prior_mean=log_fit, prior_var=prior_var)
+    x_map = search(log_prior_mean=log_fit, prior_var=prior_var)
     with np.errstate(invalid="ignore"):
         outlier = x_gene > log_fit + 2.0 * np.sqrt(var_log_disp)
     disp_map = engine.nb_clip(np.exp(x_map), m)
@@ -2371,7 +2401,7 @@ def _nb_size_factors(cluster_counts, size_factors, m):
     return sf
 
 
-def deseq2_dispersions(cluster_counts, groups, size_factors=None, fit_type="parametric"):
+def deseq2_dispersions(cluster_counts, groups=None, size_factors=None, fit_type="parametric", design=None):
     """DESeq2's dispersion estimates (``estimateDispersions``; Love, Huber, Anders 2014) of a samples x genes count frame under
     the one-factor design ``~ groups`` (one label per sample; at least two groups and one residual degree of freedom), on the
     device (``engine.nb_dispersions``).  DESeq2 is not installed where this library is built and tested: the rule
@@ -2388,8 +2418,18 @@ def deseq2_dispersions(cluster_counts, groups, size_factors=None, fit_type="para
     Deviations from DESeq2: the dispersion search is global (six rounds of a 64-point grid) where DESeq2 runs a line search from a
     moments start, so on a multimodal gene the two can differ; the Cook's-distance handling is
     :func:`compute_pseudobulk_DE`'s ``outliers="deseq2"`` (K25), which refits the genes it replaces counts in; for ``m - k <= 3`` the same
-    prior-variance formula is used, where DESeq2 simulates."""
+    prior-variance formula is used, where DESeq2 simulates.
+
+    ``design``: an m x p design matrix (:func:`deseq2_design`; ``groups`` must then be None) for a model with covariates: the same
+    frame by the route of DESIGN.md K26 (``engine.nb_design_dispersions``), where ``dispGeneEst`` and ``dispMAP`` maximise the
+    adjusted profile likelihood with the coefficients fitted again at every dispersion, and the prior width counts p coefficients."""
     c, genes = _nb_counts(cluster_counts, "deseq2_dispersions")
+    if design is not None:
+        if groups is not None:
+            raise ValueError("deseq2_dispersions: groups and design are given, pass one (the design has its group column)")
+        X = engine._nb_design_arg(getattr(design, "values", design), c.shape[0])
+        sf = _nb_size_factors(cluster_counts, size_factors, c.shape[0])
+        return _nb_dispersion_table(c, genes, None, None, sf, fit_type, design=X)
     uniq, codes = np.unique(np.asarray(groups), return_inverse=True)
     codes = np.ravel(codes)
     if codes.shape != (c.shape[0],):
@@ -2624,8 +2664,118 @@ def lfc_shrink(cluster_counts, groups, de, prior_scale=None):
     return out
 
 
+_DE_TESTS = ("wald", "lrt")
+
+
+def _check_design_options(who, covariates, test, shrink, outliers):
+    """the K26 arguments of :func:`compute_pseudobulk_DE`, refused before any device work; the covariates as a list (empty: none)"""
+    if not (isinstance(test, str) and test in _DE_TESTS):
+        raise ValueError("%s: test=%r must be 'wald' or 'lrt'" % (who, test))
+    if covariates is None:
+        covariates = []
+    if isinstance(covariates, (str, bytes)) or not all(isinstance(name, str) for name in covariates):
+        raise ValueError("%s: covariates=%r must be a list of column names" % (who, covariates))
+    covariates = list(covariates)
+    if len(set(covariates)) != len(covariates):
+        raise ValueError("%s: covariates=%r names a column twice" % (who, covariates))
+    if covariates and (shrink or outliers):
+        raise NotImplementedError("%s: covariates with %s: the shrinkage (K23) and the outlier handling (K25) are rules for the design "
+                                  "`~ group`" % (who, "shrink=%r" % (shrink,) if shrink else "outliers=%r" % (outliers,)))
+    if test == "lrt" and not covariates:
+        raise ValueError("%s: test='lrt' is the test of the design with covariates, pass covariates" % who)
+    return covariates
+
+
+def deseq2_design(cluster_metadata, cluster_col, group1, group2, covariates):
+    """The design matrix of ``~ covariates + group`` for the samples of ``group1`` and ``group2`` (by
+    ``cluster_metadata[cluster_col]``), as :func:`compute_pseudobulk_DE` builds it.  Returns ``(X, column_names,
+    selected_index)``: X is float64, one row per selected sample in the metadata's order.  The intercept comes first; then, in the
+    order of ``covariates``, for a categorical one (object, category or bool dtype) an indicator per level except the first in
+    Python string order (``<covariate>_<level>``), and a numeric one centred and scaled to unit ddof-1 standard deviation over the
+    selected samples (DESeq2 does not scale; the scaling changes only that nuisance coefficient); the indicator of ``group2``
+    (``<cluster_col>_<group2>_vs_<group1>``) comes last.  ValueError: an unknown column, a missing value, a covariate that is
+    constant over the selected samples, or one that is confounded with the columns before it (the message names it; a group
+    indicator that the covariates already determine names the group column)."""
+    who = "deseq2_design"
+    if cluster_col is None or cluster_col not in cluster_metadata.columns:
+        raise ValueError("%s: cluster_col=%r is not a column of cluster_metadata" % (who, cluster_col))
+    if group1 == group2:
+        raise ValueError("%s: group1 and group2 are both %r" % (who, group1))
+    stage = cluster_metadata[cluster_col]
+    meta = cluster_metadata[(stage == group1) | (stage == group2)]
+    if len(meta) == 0:
+        raise ValueError("%s: no sample of %r or %r" % (who, group1, group2))
+    columns, names = [np.ones(len(meta))], ["Intercept"]
+
+    def full_rank():
+        return np.linalg.matrix_rank(np.stack(columns, axis=1)) == len(columns)
+
+    for cov in covariates:
+        if cov not in meta.columns or cov == cluster_col:
+            raise ValueError("%s: covariate %r is not a column of cluster_metadata beside %r" % (who, cov, cluster_col))
+        values, before = meta[cov], len(names)
+        if values.isna().any():
+            raise ValueError("%s: covariate %r has a missing value in sample %r" % (who, cov, values.index[values.isna().to_numpy()][0]))
+        if values.dtype == object or values.dtype == bool or isinstance(values.dtype, pd.CategoricalDtype):
+            labels = np.array([str(v) for v in values])
+            levels = sorted(set(labels))
+            if len(levels) < 2:
+                raise ValueError("%s: covariate %r is constant (%r) over the selected samples" % (who, cov, levels[0]))
+            for level in levels[1:]:
+                columns.append((labels == level).astype(np.float64))
+                names.append("%s_%s" % (cov, level))
+        else:
+            v = values.to_numpy(dtype=np.float64)
+            sd = v.std(ddof=1) if v.size > 1 else 0.0
+            if not (np.isfinite(sd) and sd > 0):
+                raise ValueError("%s: covariate %r is constant over the selected samples" % (who, cov))
+            columns.append((v - v.mean()) / sd)
+            names.append(cov)
+        if not full_rank():
+            raise ValueError("%s: covariate %r is confounded with the columns before it (%s)" % (who, cov, ", ".join(names[:before])))
+    columns.append((meta[cluster_col] == group2).to_numpy().astype(np.float64))
+    names.append("%s_%s_vs_%s" % (cluster_col, group2, group1))
+    if not full_rank():
+        raise ValueError("%s: the group column %r is confounded with the covariates %r" % (who, cluster_col, list(covariates)))
+    return np.stack(columns, axis=1), names, meta.index
+
+
+def _nb_design_de(counts, X, names, fit_type, test, filtering_alpha):
+    """:func:`compute_pseudobulk_DE` by the route of DESIGN.md K26: the dispersion table, the final fit and the host tail for the
+    last design column"""
+    from scipy import stats
+    c, genes = _nb_counts(counts, "compute_pseudobulk_DE")
+    sf = _nb_size_factors(counts, None, c.shape[0])
+    table = _nb_dispersion_table(c, genes, None, None, sf, fit_type, design=X)
+    disp = table["dispersion"].to_numpy()
+    beta, cov, loglik, info = engine.nb_design_fits(c, X, sf, disp, return_info=True)
+    n_bad = info["n_not_converged"]
+    log2e = np.log2(np.e)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lfc, se = log2e * beta[:, -1], log2e * np.sqrt(cov[:, -1, -1])
+        stat = lfc / se
+    p = 2.0 * stats.norm.sf(np.abs(stat))
+    if test == "lrt":
+        _, _, reduced, info0 = engine.nb_design_fits(c, np.ascontiguousarray(X[:, :-1]), sf, disp, return_info=True)
+        n_bad += info0["n_not_converged"]
+        stat = 2.0 * (loglik - reduced)
+        p = stats.chi2.sf(stat, 1)
+    base_mean = table["baseMean"].to_numpy()
+    padj, filtering = _nb_padj(p, base_mean, filtering_alpha)
+    out = pd.DataFrame({"gene": np.asarray(genes), "baseMean": base_mean, "log2FoldChange": lfc, "lfcSE": se, "stat": stat, "pvalue": p,
+                        "padj": padj, "dispersion": disp})
+    out = out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
+    if filtering is not None:
+        out.attrs["independent_filtering"] = filtering
+    out.attrs.update(dispersions=table, size_factors=pd.Series(sf, index=counts.index), n_not_converged=int(n_bad),
+                     design=pd.DataFrame(X, index=counts.index, columns=names), coefficients=pd.DataFrame(beta, index=genes, columns=names),
+                     test=test)
+    return out
+
+
 def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=None, group2=None, cluster_col=None, fit_type="parametric",
-                          shrink=None, prior_scale=None, outliers=None, independent_filtering=False, alpha=0.05):
+                          shrink=None, prior_scale=None, outliers=None, independent_filtering=False, alpha=0.05, covariates=None,
+                          test="wald"):
     """The reference's ``compute_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:96-159) without R: the negative-binomial Wald
     test of DESeq2 for the design ``~ stage`` between two patient sub-groups, on the device.  Takes :func:`pseudobulk_inputs`'
     pair unchanged; the samples of ``group1`` and ``group2`` (by ``cluster_metadata[cluster_col]``) are selected first, as the
@@ -2663,9 +2813,27 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     search, not apeglm's local optimiser; no s-values; ``rlog`` is :func:`compute_pseudobulk_PCA`'s; the deviations of the outlier
     rule are DESIGN.md K25's; no beta ridge; the dispersion search is global; for ``m - 2 <= 3`` the prior variance uses the
     formula where DESeq2 simulates; the reference returns R's list (the frame at index 1), this returns the frame.  Fewer than
-    three selected samples, or a group without samples: ValueError before any device work."""
+    three selected samples, or a group without samples: ValueError before any device work.
+
+    ``covariates``: ``None`` (the default; an empty list is the same) is the design ``~ stage`` described above, untouched.  A list
+    of columns of ``cluster_metadata`` (batch, sex, age, centre; :func:`pseudobulk_inputs` copies them from ``adata.obs`` with
+    ``obs_columns``) makes the design ``~ covariates + stage`` (:func:`deseq2_design`) and takes the route of DESIGN.md K26: the
+    dispersions from the adjusted profile likelihood with the coefficients fitted again at every dispersion
+    (``engine.nb_design_dispersions``), the trend, prior and outlier rule as above with p coefficients, then the coefficients, their
+    covariance ``(X^T W X + 1e-6 I)^-1`` and the log likelihood at the final dispersion (``engine.nb_design_fits``).
+    ``log2FoldChange = log2(e) beta_group``, ``lfcSE = log2(e) sqrt(Sigma_group,group)`` and, with ``test="wald"``, ``stat`` their
+    ratio and ``pvalue = 2 norm.sf(|stat|)``; with ``test="lrt"`` a second fit without the group column at the same dispersions,
+    ``stat = 2 (loglik_full - loglik_reduced)`` and ``pvalue = chi2.sf(stat, 1)`` (the fold change and its error stay the Wald
+    ones).  The frame has the same columns; ``attrs`` gain ``design`` (the frame of X), ``coefficients`` (genes x p, natural log)
+    and ``test``, and have no ``floored``.  ``independent_filtering`` works as above.  ``shrink="apeglm"`` or ``outliers="deseq2"``
+    with covariates: NotImplementedError before any device work -- K23 and K25 are rules for the group design.  Any other
+    ``test``, ``test="lrt"`` without covariates, an unknown, constant or confounded covariate, more than
+    ``engine.NB_DESIGN_MAX_COLS`` design columns or no residual degree of freedom: ValueError before any device work.  Deviations
+    from DESeq2 under a design: the profile re-solves the coefficients where DESeq2 holds the means of one rough
+    fit; the global search; the plain inverse instead of the sandwich covariance; numeric covariates are scaled; no betaPrior."""
     _check_shrink(shrink, "compute_pseudobulk_DE")
     _check_de_options(outliers, independent_filtering, alpha, "compute_pseudobulk_DE")
+    covariates = _check_design_options("compute_pseudobulk_DE", covariates, test, shrink, outliers)
     if cluster_col is None or cluster_col not in cluster_metadata.columns:
         raise ValueError("compute_pseudobulk_DE: cluster_col=%r is not a column of cluster_metadata" % (cluster_col,))
     stage = cluster_metadata[cluster_col]
@@ -2679,6 +2847,10 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
         raise ValueError("compute_pseudobulk_DE: no sample of %r" % ((group2 if n2 == 0 else group1),))
     if codes.size < 3:
         raise ValueError("compute_pseudobulk_DE: %d samples in two groups leave no residual degree of freedom" % codes.size)
+    if covariates:
+        X, names, _ = deseq2_design(cluster_metadata, cluster_col, group1, group2, covariates)
+        X = engine._nb_design_arg(X, codes.size)
+        return _nb_design_de(counts, X, names, fit_type, test, float(alpha) if independent_filtering else None)
     c, genes = _nb_counts(counts, "compute_pseudobulk_DE")
     sf = _nb_size_factors(counts, None, c.shape[0])
     fit, cooks, extra = _nb_fit(c, genes, codes, sf, fit_type), None, {}
@@ -2817,21 +2989,25 @@ def pseudobulk_pca(rld, variance_threshold=0.2, n_components=2):
 
 
 def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types", sample_col="sampleID", cluster_col="Predicted_Labels",
-                      remove_samples=(), shrink=None, outliers=None, independent_filtering=False, alpha=0.05):
+                      remove_samples=(), shrink=None, outliers=None, independent_filtering=False, alpha=0.05, covariates=None, test="wald"):
     """The numbers of the reference's ``get_pseudobulk_DE`` (plot/pseudobulk_DE_analysis.py:506-666) in one process with no R:
     :func:`pseudobulk_inputs` of ``cell_type``, then :func:`compute_pseudobulk_DE` for every pair of
     ``itertools.combinations(np.unique(proportion_df[cluster_col]), 2)``.  Returns ``{"<g2>vs<g1>": frame}`` (the names of the
     reference's ``_DE.csv`` files; the fold change is g2 over g1).  ``shrink`` is :func:`compute_pseudobulk_DE`'s (``"apeglm"``:
     the shrunken fold changes the reference writes), and so are ``outliers``, ``independent_filtering`` and ``alpha``.  No plots,
     no files, no enrichment; the rlog PCA the reference draws first is :func:`compute_pseudobulk_PCA` / :func:`pseudobulk_pca` on
-    :func:`pseudobulk_inputs`' pair; the deviations of :func:`compute_pseudobulk_DE` apply."""
+    :func:`pseudobulk_inputs`' pair; the deviations of :func:`compute_pseudobulk_DE` apply.  ``covariates`` and ``test`` are
+    :func:`compute_pseudobulk_DE`'s too; a covariate that ``proportion_df`` lacks is taken from ``adata.obs``, where
+    it must be constant within every sample (:func:`pseudobulk_inputs`' ``obs_columns``)."""
     import itertools
     _check_shrink(shrink, "get_pseudobulk_DE")
     _check_de_options(outliers, independent_filtering, alpha, "get_pseudobulk_DE")
-    cluster_counts, cluster_metadata = pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col, sample_col, cluster_col, remove_samples)
+    covariates = _check_design_options("get_pseudobulk_DE", covariates, test, shrink, outliers)
+    cluster_counts, cluster_metadata = pseudobulk_inputs(adata, proportion_df, cell_type, celltype_col, sample_col, cluster_col, remove_samples,
+                                                         obs_columns=[name for name in covariates if name not in proportion_df.columns])
     out = {}
     for g1, g2 in itertools.combinations(np.unique(proportion_df[cluster_col]), 2):
         out["%svs%s" % (g2, g1)] = compute_pseudobulk_DE(cluster_counts, cluster_metadata, group1=g1, group2=g2, cluster_col=cluster_col,
                                                          shrink=shrink, outliers=outliers, independent_filtering=independent_filtering,
-                                                         alpha=alpha)
+                                                         alpha=alpha, covariates=covariates or None, test=test)
     return out

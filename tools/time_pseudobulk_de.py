@@ -33,7 +33,15 @@ x 200, so that the refit has something to do.  The dispersions come from one MAP
 nb_group_fits.  ``nb_dispersions`` and ``nb_cooks`` alternate in one loop, best of --reps each.  Then, once, what
 ``outliers="deseq2"`` adds for the genes with a replacement: the gathered call with distances, the replacements, two dispersion
 passes, the group fits and the last distance call on those genes only, with the share of genes that took part.  Host: the
-restatement (tests/nb_cooks_restatement.py) on --host-genes genes, scaled.  Writes OUT/cooks_rate.txt."""
+restatement (tests/nb_cooks_restatement.py) on --host-genes genes, scaled.  Writes OUT/cooks_rate.txt.
+
+--design: instead, the GLM for a general design (K26: engine.nb_design_dispersions, engine.nb_design_fits) at --design-cols columns
+(default 4: intercept, batch, scaled age, group; the tests' generator with planted coefficients) beside K22's pass for the group
+column alone on the same table: both searches are one wave per gene and six 64-point rounds over LDS-staged samples;
+nb_design_dispersions adds an inner Newton fit of p coefficients at every grid point (two passes over the samples a step, one for
+the normal equations and one for the line search).  ``nb_dispersions`` and ``nb_design_dispersions`` alternate in one loop, and so
+do ``nb_group_fits`` and ``nb_design_fits``, best of --reps each; the mean inner steps a lane and round go beside the ratio.  Host:
+the vectorised restatement (tests/nb_design_restatement.py) on --host-genes genes, scaled.  Writes OUT/design_rate.txt."""
 import argparse
 import os
 import sys
@@ -56,10 +64,12 @@ def main():
     ap.add_argument("--shrink", action="store_true")
     ap.add_argument("--rlog", action="store_true")
     ap.add_argument("--cooks", action="store_true")
+    ap.add_argument("--design", action="store_true")
+    ap.add_argument("--design-cols", type=int, default=4, help="--design: the columns of the design matrix")
     ap.add_argument("--outlier-share", type=float, default=0.02, help="--cooks: the share of genes that get one count x 200")
     a = ap.parse_args()
-    if a.shrink + a.rlog + a.cooks > 1:
-        ap.error("--shrink, --rlog and --cooks are separate runs")
+    if a.shrink + a.rlog + a.cooks + a.design > 1:
+        ap.error("--shrink, --rlog, --cooks and --design are separate runs")
     import nb_glm_restatement as RR
     from pilot_amd import _lib, engine
 
@@ -208,7 +218,49 @@ def main():
             "by at most %.2g relative, arg_max equal on %d of %d"
             % (h, 1e3 * t_host, a.genes, h, t_host * a.genes / h, np.nanmax(off), (ck["arg_max"][:h] == ref["arg_max"]).sum(), h))
         del D
-    for m in (() if a.shrink or a.rlog or a.cooks else a.samples):
+    for m in (a.samples if a.design else ()):
+        import nb_design_restatement as DR
+        rng = np.random.default_rng(m)
+        s = RR.size_factors(rng, m)
+        X, kinds = DR.make_design(rng, m, a.design_cols)
+        codes = X[:, -1].astype(np.int32)
+        c = DR.nb_class(rng, s, X, kinds, a.genes)
+        D = engine.DeviceMatrix.upload(c.astype(np.float32))
+        x22 = engine.nb_dispersions(D, codes, 2, s)
+        x26, info = engine.nb_design_dispersions(D, X, s, return_info=True)
+        a22, a26 = engine.nb_clip(np.exp(x22), m), engine.nb_clip(np.exp(x26), m)
+        engine.nb_group_fits(D, codes, 2, s, a22)
+        engine.nb_design_fits(D, X, s, a26)
+        t = np.full(4, np.inf)
+        for _ in range(a.reps):                                         # the calls alternate
+            t0 = time.perf_counter()
+            engine.nb_dispersions(D, codes, 2, s)
+            t1 = time.perf_counter()
+            engine.nb_design_dispersions(D, X, s)
+            t2 = time.perf_counter()
+            engine.nb_group_fits(D, codes, 2, s, a22)
+            t3 = time.perf_counter()
+            beta, cov, ll, fit = engine.nb_design_fits(D, X, s, a26, return_info=True)
+            t4 = time.perf_counter()
+            t = np.minimum(t, [t1 - t0, t2 - t1, t3 - t2, t4 - t3])
+        live = ~np.isnan(x26)
+        say("case %d genes x %d samples, float32 in HBM, design of %d columns (%s)" % (a.genes, m, a.design_cols, ", ".join(kinds)))
+        say("  nb_design_dispersions %.2f ms, nb_dispersions (gene-wise, the group column alone) %.2f ms beside it: ratio %.2f; best of %d, "
+            "alternating" % (1e3 * t[1], 1e3 * t[0], t[1] / t[0], a.reps))
+        say("  inner Newton steps a lane and round: mean %.2f, largest gene mean %.2f; %d genes with a fit that did not converge"
+            % (info["steps"][live].mean() / 384.0, info["steps"][live].max() / 384.0, info["n_not_converged"]))
+        say("  nb_design_fits %.2f ms, nb_group_fits %.2f ms beside it: ratio %.2f; steps a gene: mean %.1f, largest %d; %d not converged"
+            % (1e3 * t[3], 1e3 * t[2], t[3] / t[2], fit["steps"][live].mean(), fit["steps"].max(), fit["n_not_converged"]))
+        h = min(a.host_genes, a.genes)
+        t0 = time.perf_counter()
+        xh = DR.dispersions(c[:, :h], X, s)[0]
+        t_host = time.perf_counter() - t0
+        res = DR.resolved(c[:, :h], X, s, xh)
+        say("  host restatement (vectorised numpy) on %d genes: dispersions %.2f s; scaled by %d / %d: %.0f s; device against it on the "
+            "resolved genes (%d): dispersion off by at most %.2g relative"
+            % (h, t_host, a.genes, h, t_host * a.genes / h, res.sum(), np.abs(np.expm1(x26[:h][res] - xh[res])).max(initial=0)))
+        del D
+    for m in (() if a.shrink or a.rlog or a.cooks or a.design else a.samples):
         rng = np.random.default_rng(m)
         s = RR.size_factors(rng, m)
         codes = (np.arange(m) % 2).astype(np.int32)
@@ -243,7 +295,7 @@ def main():
                np.abs(np.expm1(x[:h][res] - xh[res])).max(initial=0)))
         del D, Z
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "design_rate.txt" if a.design else "rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

@@ -668,6 +668,21 @@ template <int RT, int NP> struct SplitImage { u32x4_t a[NP][split_kblocks(RT)][R
 // (Tried with it and taken out: the stop test on the squared error against a precomputed bound, with the square root formed once where
 // a pair retires -- 19 vector instructions and 5 s_nop fewer in the error block, same bits, and c3's kernel 0.8 % SLOWER, alone and on
 // top of this; profiles/r10/loop_control.md.)
+// Round 11, fp16-split fast stream kernels up to four row-tiles (profiles/r11/wave_masks.md).
+// PILOT_WAVE_MASKS: the two per-column flags of the persistent loop, `active` and `want`, are 64-bit wave masks in scalar registers
+// instead of per-lane bools: every change is a scalar and / or with a ballot, formed in front of or behind the divergent branch it
+// belongs to and never inside it, and a lane reads its bit through inverse_ballot where it needs it.  Same pairs, same bits.
+#ifndef PILOT_WAVE_MASKS
+#define PILOT_WAVE_MASKS 1    // (round 11: 20 of the function's 1 121 vector instructions off the vector pipe, VGPRs 231 -> 229; c3 kernel 0.5432 -> 0.5331 ms, 600 x 2 -5.6 %, c2 unchanged)
+#endif
+// PILOT_TEST_MASK (with PILOT_WAVE_MASKS): the branch into the error block tests a mask formed from the two comparisons and active_m
+// instead of the ballot of `pending || capped`: two vector instructions fewer in every update; the late tau test forms its column mask
+// from the same mask.
+// (Tried and taken out: the two quotient blocks spaced over the MFMA gaps with __builtin_amdgcn_sched_group_barrier -- the groups are
+// honoured at the price of the accumulator chains' interleave, 36 s_nop in the update block instead of 9, c3's kernel 6.5 % SLOWER.)
+#ifndef PILOT_TEST_MASK
+#define PILOT_TEST_MASK 1     // (round 11: update block 125 -> 123 vector instructions; c3 kernel 0.5331 -> 0.5294 ms, 0.5350 -> 0.5321 in a repeat: at the edge of the bench's resolution; c2 unchanged)
+#endif
 // a * b as ONE v_mul_f32.  The SLP vectoriser pairs the quotient multiplies of adjacent slots (v = b rcp(acc), u = a rcp(acc)) into
 // v_pk_mul_f32 -- 9 of them per update at four row-tiles -- and a packed f32 instruction beside MFMAs holds the SIMD's vector issue for
 // longer than the two plain ones it replaces: 9 instructions more per update and 2 % less time (profiles/r09/loop_stalls.md).  The
@@ -1370,6 +1385,18 @@ sinkhorn_stream_kernel(GridParams p) {
     const int n_tile_waves = ((int)gridDim.x - (solo_in_stream<C, RT, SYM, TRACK, TV>() ? p.solo_blocks : 0)) * WAVES_PER_WG;
     const int queue_start = (solo_in_stream<C, RT, SYM, TRACK, TV>() && p.solo_len && p.solo_blocks > 0) ? *p.solo_len : 0;
     bool want = true;  // column asks for a (new) pair
+    // PILOT_WAVE_MASKS (fp16-split fast kernels up to four row-tiles): the two flags as wave masks, bit = lane, the lane groups of a
+    // column alike as the bools are.  RULE: no per-lane copy of either flag may live across an update of its mask -- a column that has
+    // just retired asks for a pair through want_m, and a view taken before that update ranks it in the batch without handing it its
+    // item: the pair is lost.  Every point of use (refill, pending / capped, the reload behind the parked flush) takes its own view
+    // through inverse_ballot; `active` and `want` above serve as those views there, set in front of the reads and holding nothing
+    // between two points of use (loop head, retire and hand-over work on the masks themselves).  A mask is only assigned under
+    // wave-uniform control flow: assigned inside a divergent branch it would become a per-lane value again.  (The other
+    // instantiations keep every statement they had, copied under the gate rather than shared: read through a helper, all 118 tracking
+    // instantiations changed registers.)
+    constexpr bool WMASK = C::HALF && !TRACK && PILOT_TAU_AT_TEST && PILOT_WAVE_MASKS && RT <= 4;
+    constexpr bool TMASK = WMASK && PILOT_TEST_MASK;
+    unsigned long long active_m = 0ull, want_m = ~0ull;
     constexpr bool SHARDED_QUEUE = RT <= QUEUE_SHARD_MAX_RT;
     int qc = wave_id % QUEUE_SHARDS, q_tries = 0;                       // (sharded queue: the counter this wave draws from)
     const int q_max_tries = n_tile_waves >= QUEUE_SHARDS ? 4 : QUEUE_SHARDS;
@@ -1390,8 +1417,10 @@ sinkhorn_stream_kernel(GridParams p) {
         // 1 / 2 / 4, K = 20 .. 32 +2 .. +7 %): profiles/r06/ab_experiments.md sections 3 and 8)
         // (the same feed as PairBatch, split_tile.hpp, kept inline here: through that struct 74 of these kernels' instantiations change
         // registers or scratch and two lose a wave per SIMD -- profiles/split_tile/stream_feed_resources.diff)
-        const unsigned long long wmask = ballot_b(want) & colmask;
+        const unsigned long long wmask = (WMASK ? want_m : ballot_b(want)) & colmask;
         if (wmask) {
+            // (wave masks: this block's view of want, taken behind the retire block's update; want_m does not change before its last use)
+            if constexpr (WMASK) want = __builtin_amdgcn_inverse_ballot_w64(want_m);
             // SPAN (fp16-split configuration from PILOT_BOUNDARY_DRAW row-tiles on): items go to the wanting columns from the wave's
             // current batch first; where that batch has fewer left than columns that want one (none at all, usually) and the queue has
             // not ended, the next batch is drawn HERE, once, and serves the remaining columns in the same iteration.  Otherwise the draw
@@ -1480,8 +1509,9 @@ sinkhorn_stream_kernel(GridParams p) {
                 isel = __builtin_amdgcn_ds_bpermute(bsel, ibatch), jsel = __builtin_amdgcn_ds_bpermute(bsel, jbatch);
                 res_next = __builtin_amdgcn_readfirstlane(res_next + (n_want < avail ? n_want : avail));
             }
+            if constexpr (WMASK) want_m &= ~ballot_b(want && !take && exhausted);
             if (want && !take && exhausted) {   // no work left: the slot goes dark
-                want = false;
+                if constexpr (!WMASK) want = false;
 #pragma unroll
                 for (int t = 0; t < RT; ++t)
 #pragma unroll
@@ -1496,9 +1526,9 @@ sinkhorn_stream_kernel(GridParams p) {
                 }
                 if constexpr (TAU_LATE) mrun = 0u;
             }
+            if constexpr (WMASK) { const unsigned long long tk = ballot_b(take); want_m &= ~tk; active_m |= tk; }
             if (take) {
-                want = false;
-                active = true;
+                if constexpr (!WMASK) { want = false; active = true; }
                 q = qsel;
                 const int i = isel, j = jsel;
                 const T *pa = Pt + (size_t)i * KP + grp * NREG, *pb = Pt + (size_t)j * KP + grp * NREG;
@@ -1548,11 +1578,13 @@ sinkhorn_stream_kernel(GridParams p) {
                         base = __builtin_amdgcn_readfirstlane(base);
                         if (take && grp == 0) p.track_list[base + __popcll(tm & ((1ull << col) - 1ull))] = q;
                     }
-                    if (take) { active = false; want = true; }
+                    if constexpr (WMASK) { const unsigned long long tk = ballot_b(take); active_m &= ~tk; want_m |= tk; }
+                    else if (take) { active = false; want = true; }
                 }
             }
         }
-        if (ballot_b(active || want) == 0ull) break;
+        if constexpr (WMASK) { if ((active_m | want_m) == 0ull) break; }
+        else if (ballot_b(active || want) == 0ull) break;
 
         T mx = T(0);
         if constexpr (C::HALF) {
@@ -1690,9 +1722,9 @@ sinkhorn_stream_kernel(GridParams p) {
             if (omask) {
                 if (over) {
                     if (grp == 0) hb[hb_cnt + (int)__popcll(omask & ((1ull << col) - 1ull))] = q;
-                    active = false;
-                    want = true;
+                    if constexpr (!WMASK) { active = false; want = true; }
                 }
+                if constexpr (WMASK) { const unsigned long long ov = ballot_b(over); active_m &= ~ov; want_m |= ov; }
                 hb_cnt += (int)__popcll(omask);                         // (wave-uniform; <= HANDOVER_FLUSH - 1 + TILE <= HANDOVER_BUF)
                 if (hb_cnt >= HANDOVER_FLUSH) hb_flush();
             }
@@ -1710,6 +1742,11 @@ sinkhorn_stream_kernel(GridParams p) {
         if constexpr (!TRACK && !TAU_LATE && C::HALF && PILOT_DEFER_HANDOVER) hand_over();
 
         // ---- POT's stopping rule: the error of update ii-1 is evaluated when (ii-1) % period == 0 ---
+        if constexpr (WMASK) active = __builtin_amdgcn_inverse_ballot_w64(active_m);   // (the view of pending / capped alone: the hand-over below changes the mask)
+        // PILOT_TEST_MASK: "some column is pending or capped" from the two comparisons' own masks and active_m (ballot of a comparison is
+        // the comparison; ballot of the combined bool costs a select and a second comparison in every update)
+        unsigned long long test_m = 0ull;
+        if constexpr (TMASK) test_m = (ballot_b(ii == chk) | ballot_b(ii >= p.max_iter)) & active_m;
         const bool pending = active && ii == chk;
         if (pending) chk += p.period;
         const bool capped = active && ii >= p.max_iter;
@@ -1761,7 +1798,7 @@ sinkhorn_stream_kernel(GridParams p) {
         constexpr bool E2_EARLY = C::SPLIT && !TRACK && PILOT_E2_EARLY;
         T e2_early = T(0);
         if constexpr (E2_EARLY) e2_early = lane_e2(T(1));
-        if (ballot_b(pending || capped)) {
+        if (TMASK ? test_m : ballot_b(pending || capped)) {
             T sc = T(1);
             if constexpr (TRACK) sc = (abs_at == ii - 1) ? T(1) / kk : T(1);  // u, v were just reset to 1/K each
             // TAU_LATE: the tau test of the columns this block tests, on the maximum over all their updates so far (a NaN half counts as
@@ -1770,6 +1807,12 @@ sinkhorn_stream_kernel(GridParams p) {
             if constexpr (TAU_LATE) {
                 const f16x2_t mh = __builtin_bit_cast(f16x2_t, mrun);
                 const float m0 = float(mh[0]), m1 = float(mh[1]);
+                if constexpr (TMASK) {       // (column_any_mask on masks: the tested columns are test_m already)
+                    const unsigned long long m = ballot_b(!(m0 <= tau && m1 <= tau)) & test_m;
+                    unsigned long long f = m | (m >> 32);
+                    if constexpr (C::NGRP == 4) f |= f >> 16;
+                    omask = f & colmask;
+                } else
                 omask = column_any_mask<C>((pending || capped) && !(m0 <= tau && m1 <= tau));
                 over = (omask >> col) & 1ull;
                 hand_over();
@@ -1837,6 +1880,7 @@ sinkhorn_stream_kernel(GridParams p) {
                             // interleaved under a condition per row-tile, one way had b's first row-tile as the last load issued: a wait
                             // for everything)
                             if constexpr (C::HALF) {
+                                if constexpr (WMASK) active = __builtin_amdgcn_inverse_ballot_w64(active_m);     // (behind the hand-over's update)
                                 if (active) {
 #pragma unroll
                                     for (int t = 0; t < RT; ++t) load_row(pb, t, B[t]);
@@ -1884,7 +1928,8 @@ sinkhorn_stream_kernel(GridParams p) {
                         if (ring_cnt >= p.ring) { flush(ring_cnt); ring_cnt = 0; }
                     }
                 }
-                if (fin) { active = false; want = true; }
+                if constexpr (WMASK) { const unsigned long long fm = ballot_b(fin); active_m &= ~fm; want_m |= fm; }
+                else if (fin) { active = false; want = true; }
             }
         }
     }

@@ -751,6 +751,34 @@ int pilot_ot_nb_design_fits(const void *Y, int Y_is_device, int dtype, long long
                             const double *size_factors, const double *dispersion, double *beta, double *cov, double *loglik, int *steps,
                             int *flags, int *n_not_converged, long long *bad_row, int *bad_col);
 
+/* pilot_ot_nb_design_shrink (K27): pilot_ot_nb_shrink for the general design, the `lfcShrink(type = "apeglm")` step after a fit with
+ * covariates.  THIS LIBRARY'S STATEMENT, unpinned (restated in tests/nb_design_shrink_restatement.py).  Y, X, p,
+ * size_factors, dispersion as pilot_ot_nb_design_fits.  coef in [1, p - 1]: the column k of X that is shrunk.  With S = prior_scale,
+ * sigma0 = other_scale, eta_j = x_j^T beta + log s_j and mu_j = e^{eta_j}, per gene
+ *     P(beta) = sum_j [c_j log(alpha mu_j) - (c_j + 1/alpha) log1p(alpha mu_j)] - sum_{l != k} beta_l^2 / (2 sigma0^2)
+ *               - log1p(beta_k^2 / S^2)
+ * a Cauchy of scale S on beta_k and a normal of scale sigma0 on EVERY other coefficient, the intercept included (what lfcShrink hands
+ * apeglm as no.shrink); no further ridge.  For X = [1, indicator] this is pilot_ot_nb_shrink's P(b0, b1).  The estimate is DEFINED by
+ * that call's search: the profile p(b) = max over beta_{-k} of P at beta_k = b, over t in [0, asinh(E / S)] with b = sg S sinh t and
+ * far_end[gene] = sg E (from pilot_ot_nb_design_fits' coefficient: sg its sign, + for 0, E = |beta_k| + 1; 1 for a gene left out), by six
+ * rounds of the 64-point grid, the first largest value winning.  At every grid point the p - 1 other coefficients are fitted by the
+ * Newton iteration of the inner fit above with the ridge 1 / sigma0^2 (to 1e-10, at most 100 steps): round 0 from beta_mle
+ * (n_genes x p, that call's coefficients), a later round from the lane's own last point.  One wave per gene, a lane is a grid point;
+ * no floating-point sum crosses lanes: a gene gives the same bits alone and in any batch.
+ * Out (host): beta (n_genes x p, X's column order) at the winning point; objective = P there; info (n_genes x p (p + 1) / 2): the
+ * upper triangle, row by row in X's column order, of X^T W X with w_j = mu_j (1 + alpha c_j) / (1 + alpha mu_j)^2; flags:
+ * PILOT_OT_NB_NOT_CONVERGED (an inner fit did not converge), PILOT_OT_NB_AT_BOUND, and above PILOT_OT_NB_SHRINK_STEPS_SHIFT the
+ * gene's inner Newton steps over all grid points and rounds; *n_at_bound (nullable).  A NaN dispersion, a gene of zeros or a
+ * non-finite beta_mle in an unshrunk column leaves the gene out: NaN everywhere, flags 0.
+ * PILOT_OT_EINVAL (before any HIP call): the cases of pilot_ot_nb_design_fits, coef outside [1, p - 1], a prior_scale or other_scale
+ * not positive and finite, a non-finite far_end; after the check pass a negative or non-finite count (*bad_row / *bad_col as
+ * pilot_ot_nb_dispersions).  PILOT_OT_ENOTSUP: m > INT_MAX; m > pilot_ot_nb_design_max_samples(p) (the staging of
+ * pilot_ot_nb_design_dispersions). */
+int pilot_ot_nb_design_shrink(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                              int coef, const double *size_factors, const double *dispersion, const double *beta_mle,
+                              const double *far_end, double prior_scale, double other_scale, double *beta, double *objective, double *info,
+                              int *flags, int *n_at_bound, long long *bad_row, int *bad_col);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

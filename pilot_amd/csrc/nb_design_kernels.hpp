@@ -156,10 +156,11 @@ template <int P> __device__ inline void nb_design_rank1(double (&M)[NB_TRI<P>], 
 }
 
 // The inner fit from `beta` (in: the start, out: the maximiser).  sample(j, c, ls, x): the count, log size factor and design row of
-// sample j.  Returns the Newton steps taken; converged = false after NB_DESIGN_MAX_ITERS of them.
+// sample j.  lambda: the ridge on every coefficient (K26: NB_DESIGN_RIDGE; K27: 1 / sigma0^2, the normal prior of the coefficients
+// that are not shrunk).  Returns the Newton steps taken; converged = false after NB_DESIGN_MAX_ITERS of them.
 template <int P, typename Sample>
-__device__ inline int nb_design_solve(int m, double alpha, double (&beta)[P], bool &converged, Sample sample) {
-    const double inv_alpha = 1.0 / alpha, lambda = NB_DESIGN_RIDGE;
+__device__ inline int nb_design_solve(int m, double alpha, double lambda, double (&beta)[P], bool &converged, Sample sample) {
+    const double inv_alpha = 1.0 / alpha;
     converged = false;
     int it = 0;
     while (it < NB_DESIGN_MAX_ITERS) {
@@ -276,7 +277,7 @@ __global__ void __launch_bounds__(64) nb_design_dispersion_kernel(const T *__res
 #pragma unroll
         for (int k = 0; k < P; ++k) beta[k] = start[k];
         bool done;
-        steps += nb_design_solve<P>(m, alpha, beta, done, sample);
+        steps += nb_design_solve<P>(m, alpha, NB_DESIGN_RIDGE, beta, done, sample);
         if (!done) flags |= NB_FLAG_NOT_CONVERGED;
         double M[NB_TRI<P>];
 #pragma unroll
@@ -347,7 +348,7 @@ __global__ void __launch_bounds__(256) nb_design_fit_kernel(const T *__restrict_
     }
     nb_design_start<P>(m, sf, beta, sample);
     bool done;
-    const int steps = nb_design_solve<P>(m, alpha, beta, done, sample);
+    const int steps = nb_design_solve<P>(m, alpha, NB_DESIGN_RIDGE, beta, done, sample);
 
     const double r = 1.0 / alpha, lg_r = lgamma(r);
     double M[NB_TRI<P>], loglik = 0.0;

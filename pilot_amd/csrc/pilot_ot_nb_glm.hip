@@ -1,5 +1,6 @@
 // C ABI of the negative-binomial GLM for a one-factor design and, at the end, for a general one (include/pilot_ot.h, section
-// "negative-binomial GLM"; kernels: nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp, nb_cooks_kernel.hpp, nb_design_kernels.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
+// "negative-binomial GLM"; kernels: nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp, nb_cooks_kernel.hpp, nb_design_kernels.hpp,
+// nb_design_shrink_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
 // codes, size factors, dispersions and the results are host arrays.  The host orders the samples by group once per call.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include "abi_common.hpp"
 #include "nb_cooks_kernel.hpp"
 #include "nb_design_kernels.hpp"
+#include "nb_design_shrink_kernel.hpp"
 #include "nb_glm_kernels.hpp"
 #include "nb_rlog_kernel.hpp"
 #include "nb_shrink_kernel.hpp"
@@ -544,6 +546,33 @@ int design_fits(const void *y, long long ld, int m, int n_genes, const double *d
     return PILOT_OT_OK;
 }
 
+// K27.  d_sf and beta_mle have the shrunk column last; beta comes back in the caller's column order, info packed in the kernel's.
+template <typename T, int P>
+int design_shrink(const void *y, long long ld, int m, int n_genes, const double *d_sf, const double *dispersion, const double *beta_mle,
+                  const double *far_end, double prior_scale, double other_scale, int coef, double *beta, double *objective, double *info,
+                  int *flags, long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    constexpr size_t TRI = pilot::NB_TRI<P>;
+    const size_t G = (size_t)n_genes;
+    double *d_in, *d_out;                                    // d_in: dispersion | far_end | beta_mle;  d_out: beta | objective | info
+    int *d_flags;
+    HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, (2 + (size_t)P) * G, &d_in));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, (P + 1 + TRI) * G, &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, G, &d_flags));
+    HIP_TRY(hipMemcpy(d_in, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in + G, far_end, sizeof(double) * G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in + 2 * G, beta_mle, sizeof(double) * P * G, hipMemcpyHostToDevice));
+    if (int rc = launch_wave_per_gene(pilot::nb_design_shrink_kernel<T, P>, n_genes, (2 + (size_t)P) * (size_t)m, static_cast<const T *>(y), ld, m,
+                                      d_sf, d_in, d_in + 2 * G, d_in + G, prior_scale, 1.0 / (other_scale * other_scale), coef, d_out,
+                                      d_out + P * G, d_out + (P + 1) * G, d_flags))
+        return rc;
+    HIP_TRY(fetch(beta, d_out, P * G));
+    HIP_TRY(fetch(objective, d_out + P * G, G));
+    HIP_TRY(fetch(info, d_out + (P + 1) * G, TRI * G));
+    HIP_TRY(fetch(flags, d_flags, G));
+    return PILOT_OT_OK;
+}
+
 }  // namespace
 
 PILOT_API int pilot_ot_nb_design_max_cols(void) { return pilot::NB_DESIGN_MAX_COLS; }
@@ -602,5 +631,61 @@ PILOT_API int pilot_ot_nb_design_fits(const void *Y, int Y_is_device, int dtype,
         }))
         return rc;
     count_flag(flags, n_genes, pilot::NB_FLAG_NOT_CONVERGED, n_not_converged);
+    return PILOT_OT_OK;
+}
+
+// ---- K27: the shrunken coefficient under a general design (nb_design_shrink_kernel.hpp) ----------------------------------------------
+PILOT_API int pilot_ot_nb_design_shrink(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                                        int coef, const double *size_factors, const double *dispersion, const double *beta_mle,
+                                        const double *far_end, double prior_scale, double other_scale, double *beta, double *objective,
+                                        double *info, int *flags, int *n_at_bound, long long *bad_row, int *bad_col) {
+    if (n_at_bound) *n_at_bound = 0;
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, false, nullptr, 1, dispersion, nullptr};
+    if (int rc = prologue(
+            c, !Y || !X || !size_factors || !dispersion || !beta_mle || !far_end || !beta || !objective || !info || !flags, bad_row, bad_col,
+            [&] {
+                if (int rc = positive_finite("prior_scale", prior_scale)) return rc;
+                return positive_finite("other_scale", other_scale);
+            },
+            [&] {
+                if (int rc = check_design_matrix(X, m, p)) return rc;
+                if (coef < 1 || coef > p - 1)
+                    return fail(PILOT_OT_EINVAL, "coef=%d must be in [1, p - 1 = %d] (the intercept is not shrunk)", coef, p - 1);
+                for (int j = 0; j < n_genes; ++j)
+                    if (!std::isfinite(far_end[j])) return fail(PILOT_OT_EINVAL, "far_end[%d]=%g must be finite", j, far_end[j]);
+                return check_design_samples(m, p);
+            }))
+        return rc;
+    // the shrunk column goes last: of X and of beta_mle (the kernel's column `at` is the caller's `from(at)`)
+    const size_t M = (size_t)m, G = (size_t)n_genes, P = (size_t)p;
+    const auto from = [&](size_t at) { return at == P - 1 ? (size_t)coef : at < (size_t)coef ? at : at + 1; };
+    std::vector<double> Xk(M * P), mle(G * P);
+    for (size_t j = 0; j < M; ++j)
+        for (size_t k = 0; k < P; ++k) Xk[j * P + k] = X[j * P + from(k)];
+    for (size_t g = 0; g < G; ++g)
+        for (size_t k = 0; k < P; ++k) mle[g * P + k] = beta_mle[g * P + from(k)];
+    double *d_sf;
+    if (int rc = upload_design_matrix(size_factors, Xk.data(), M, p, &d_sf)) return rc;
+    if (int rc = by_dtype(dtype, [&](auto t) {
+            return by_columns(p, [&](auto Pc) {
+                return design_shrink<decltype(t), decltype(Pc)::value>(c.y, c.y_ld, (int)m, n_genes, d_sf, dispersion, mle.data(), far_end,
+                                                                       prior_scale, other_scale, coef, beta, objective, info, flags, bad_row,
+                                                                       bad_col);
+            });
+        }))
+        return rc;
+    // the information back in the caller's column order (packed upper triangle, row by row)
+    const size_t tri = P * (P + 1) / 2;
+    const auto packed = [&](size_t i, size_t j) { return i * P - i * (i - 1) / 2 + (j - i); };
+    std::vector<size_t> to(P);                               // the kernel's column of the caller's
+    for (size_t k = 0; k < P; ++k) to[from(k)] = k;
+    std::vector<double> row(tri);
+    for (size_t g = 0; g < G; ++g) {
+        double *mine = info + g * tri;
+        for (size_t i = 0; i < P; ++i)
+            for (size_t j = i; j < P; ++j) row[packed(i, j)] = mine[to[i] < to[j] ? packed(to[i], to[j]) : packed(to[j], to[i])];
+        for (size_t t = 0; t < tri; ++t) mine[t] = row[t];
+    }
+    count_flag(flags, n_genes, pilot::NB_FLAG_AT_BOUND, n_at_bound);
     return PILOT_OT_OK;
 }

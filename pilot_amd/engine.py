@@ -1711,6 +1711,109 @@ def nb_posterior_sd(beta1, w0, w1, prior_scale, intercept_scale=NB_INTERCEPT_SCA
         return np.where(det > 0, np.sqrt(h00 / det), np.nan)
 
 
+# ---- shrunken coefficient under a general design (K27; lfcShrink(type = "apeglm") after `~ covariates + stage`) -------------------
+def nb_design_far_end(beta_k):
+    """``sg * E`` of :func:`nb_design_shrink`'s search from :func:`nb_design_fits`' coefficient ``beta_k`` (natural log): sg its
+    sign (+ for 0), ``E = |beta_k| + 1`` (that fit's ridge keeps the coefficient finite, so there is no floored case as in
+    :func:`nb_far_end`).  A NaN (a gene left out) gives 1."""
+    return nb_far_end(beta_k, np.zeros(np.shape(beta_k), dtype=bool))
+
+
+def _nb_coef_arg(coef, p):
+    """the shrunk design column as an index in [1, p - 1]; a negative ``coef`` counts from the end"""
+    if isinstance(coef, (bool, np.bool_)) or not isinstance(coef, (int, np.integer)):
+        raise ValueError("coef=%r must be an integer" % (coef,))
+    k = int(coef) + p if coef < 0 else int(coef)
+    if not 1 <= k <= p - 1:
+        raise ValueError("coef=%r must name one of the design columns 1 .. %d (the intercept is not shrunk)" % (coef, p - 1))
+    return k
+
+
+def nb_design_shrink(counts, design, size_factors, dispersion, beta_mle, far_end, prior_scale, coef=-1, other_scale=NB_INTERCEPT_SCALE,
+                     return_info=False):
+    """K27: :func:`nb_shrink` for a general ``design`` (:func:`nb_design_fits`' m x p matrix): per gene (column) of ``counts`` the
+    posterior mode ``beta`` (genes x p, natural log) of ``log mu_j = x_j^T beta + log s_j`` at the gene's ``dispersion`` under a
+    Cauchy prior of scale ``prior_scale`` on the coefficient of column ``coef`` (default: the last, the group) and a normal of
+    scale ``other_scale`` on EVERY other coefficient, the intercept included (include/pilot_ot.h, pilot_ot_nb_design_shrink;
+    DESIGN.md K27; the rule is this library's statement, unpinned).  The profile over the other coefficients can have two local
+    maxima, so the mode is found by six rounds of a 64-point grid over ``t in [0, asinh(E / S)]``, ``beta_coef = sg S sinh(t)``,
+    with ``far_end = sg E`` per gene (:func:`nb_design_far_end`); at every grid point the p - 1 other coefficients are fitted by
+    Newton steps, round 0 from ``beta_mle`` (genes x p, :func:`nb_design_fits`' coefficients).  For ``design = [1, codes]`` the
+    rule is :func:`nb_shrink`'s.  A NaN dispersion, a gene of zeros or a non-finite ``beta_mle`` leaves the gene out (NaN results,
+    no flags).  Returns ``beta``; with ``return_info`` also a dict: ``objective`` (the log posterior up to constants there),
+    ``information`` (genes x p x p, ``X^T W X`` with ``w = mu (1 + alpha c) / (1 + alpha mu)^2``, for
+    :func:`nb_design_posterior_sd`), ``flags`` (``_lib.NB_NOT_CONVERGED``, ``_lib.NB_AT_BOUND``), ``steps`` (the gene's inner
+    Newton steps over all grid points and rounds), ``n_at_bound``, ``n_not_converged``.  The same bits from a repeated call, from
+    float32 and float64 storage, from host and device matrices, from column windows and for a gene alone or in any batch.  Errors
+    as :func:`nb_design_dispersions`."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
+    X = _nb_design_arg(design, Y.rows)
+    p = X.shape[1]
+    k = _nb_coef_arg(coef, p)
+    alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
+    mle, far = np.ascontiguousarray(beta_mle, dtype=np.float64), np.ascontiguousarray(far_end, dtype=np.float64)
+    if mle.shape != (Y.cols, p):
+        raise ValueError("beta_mle has shape %s for %d genes and %d design columns" % (mle.shape, Y.cols, p))
+    if far.shape != (Y.cols,):
+        raise ValueError("far_end has shape %s for %d genes" % (far.shape, Y.cols))
+    if not np.isfinite(far).all():
+        raise ValueError("far_end must be finite")
+    prior_scale, other_scale = _positive_finite_arg("prior_scale", prior_scale), _positive_finite_arg("other_scale", other_scale)
+    limit = nb_design_limits()["max_samples"][p]
+    if Y.rows > limit:
+        raise NotImplementedError("nb_design_shrink: %d samples; a gene is staged in LDS, at most %d with %d design columns"
+                                  % (Y.rows, limit, p))
+    beta, objective, packed = np.empty((Y.cols, p)), np.empty(Y.cols), np.empty((Y.cols, p * (p + 1) // 2))
+    raw = np.empty(Y.cols, dtype=np.int32)
+    at_bound = ctypes.c_int(0)
+    _nb_call(_lib.load().pilot_ot_nb_design_shrink,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(X), p, k, _lib.dptr(sf), _lib.dptr(alpha),
+             _lib.dptr(mle), _lib.dptr(far), prior_scale, other_scale, _lib.dptr(beta), _lib.dptr(objective), _lib.dptr(packed),
+             _lib.iptr(raw), ctypes.byref(at_bound))
+    if not return_info:
+        return beta
+    iu = np.triu_indices(p)
+    information = np.empty((Y.cols, p, p))
+    information[:, iu[0], iu[1]] = packed
+    information[:, iu[1], iu[0]] = packed
+    flags = raw & ((1 << _lib.NB_SHRINK_STEPS_SHIFT) - 1)
+    return beta, {"objective": objective, "information": information, "flags": flags, "steps": raw >> _lib.NB_SHRINK_STEPS_SHIFT,
+                  "n_at_bound": at_bound.value, "n_not_converged": int(np.count_nonzero(flags & _lib.NB_NOT_CONVERGED))}
+
+
+def nb_design_posterior_sd(beta, information, prior_scale, coef=-1, other_scale=NB_INTERCEPT_SCALE):
+    """The Laplace approximation of the posterior standard deviation of the shrunk coefficient at :func:`nb_design_shrink`'s mode;
+    numpy.  With the Hessian of minus the log posterior, ``H = information + diag(1 / other_scale^2 for every other column;
+    2 (S^2 - b^2) / (S^2 + b^2)^2 for column coef)``, ``b = beta[:, coef]``: ``sd = sqrt((H^-1)[coef, coef])``; NaN where H is not
+    positive definite (the Cauchy prior is not log-concave beyond ``|b| = S``) and where an input is NaN.  With two columns this is
+    :func:`nb_posterior_sd`'s formula."""
+    beta, info = np.asarray(beta, dtype=np.float64), np.asarray(information, dtype=np.float64)
+    if beta.ndim != 2 or info.shape != beta.shape + beta.shape[1:]:
+        raise ValueError("beta %s and information %s: genes x p and genes x p x p" % (beta.shape, info.shape))
+    p = beta.shape[1]
+    k = _nb_coef_arg(coef, p)
+    S2 = _positive_finite_arg("prior_scale", prior_scale) ** 2
+    b = beta[:, k]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        prior = np.full(beta.shape, 1.0 / _positive_finite_arg("other_scale", other_scale) ** 2)
+        prior[:, k] = 2.0 * (S2 - b * b) / (S2 + b * b) ** 2
+    H = info.copy()
+    H[:, np.arange(p), np.arange(p)] += prior
+    sd = np.full(beta.shape[0], np.nan)
+    for g in np.flatnonzero(np.isfinite(H).all(axis=(1, 2))):
+        try:
+            np.linalg.cholesky(H[g])
+        except np.linalg.LinAlgError:
+            continue
+        e = np.zeros(p)
+        e[k] = 1.0
+        v = np.linalg.solve(H[g], e)[k]
+        if v > 0:
+            sd[g] = np.sqrt(v)
+    return sd
+
+
 # ---- regularised log transform (K24; DESeq2's rlog(blind = TRUE) of pilotpy's compute_pseudobulk_PCA) ---------------------------
 def nb_dispersions_blind(counts, size_factors, return_info=False):
     """K24: :func:`nb_dispersions` for the design ``~ 1`` (DESeq2's ``blind = TRUE``): ONE group of all the samples, which that call

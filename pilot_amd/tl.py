@@ -2680,7 +2680,8 @@ def _check_design_options(who, covariates, test, shrink, outliers):
         raise ValueError("%s: covariates=%r names a column twice" % (who, covariates))
     if covariates and (shrink or outliers):
         raise NotImplementedError("%s: covariates with %s: the shrinkage (K23) and the outlier handling (K25) are rules for the design "
-                                  "`~ group`" % (who, "shrink=%r" % (shrink,) if shrink else "outliers=%r" % (outliers,)))
+                                  "`~ group`%s" % (who, "shrink=%r" % (shrink,) if shrink else "outliers=%r" % (outliers,),
+                                                   "; shrink the frame afterwards with tl.lfc_shrink_design" if shrink else ""))
     if test == "lrt" and not covariates:
         raise ValueError("%s: test='lrt' is the test of the design with covariates, pass covariates" % who)
     return covariates
@@ -2773,6 +2774,68 @@ def _nb_design_de(counts, X, names, fit_type, test, filtering_alpha):
     return out
 
 
+def lfc_shrink_design(cluster_counts, de, prior_scale=None):
+    """:func:`lfc_shrink` for a frame that :func:`compute_pseudobulk_DE` made WITH ``covariates``: the reference's
+    ``lfcShrink(dds, coef, res, type = "apeglm")`` step under the design ``~ covariates + stage``, on the device
+    (``engine.nb_design_shrink``; apeglm is not installed where this library is built and tested, so the rule is
+    this library's statement, UNPINNED).  ``cluster_counts``: the samples x genes counts of the selected samples; ``de``: the
+    frame, whose ``attrs`` supply the design matrix (``design``), the maximum-likelihood coefficients (``coefficients``), the size
+    factors and the dispersions.  The group column, the last of the design, is shrunk: per gene the posterior mode under a Cauchy
+    prior of scale ``prior_scale`` on it (default: ``engine.nb_prior_scale`` of the maximum-likelihood coefficients and their
+    standard errors over the genes with ``|beta| < 10``, at most 1) and a normal of scale 15 on every other coefficient, and its
+    Laplace standard deviation (``engine.nb_design_posterior_sd``).  Returns a copy of ``de`` with ``log2FoldChange = beta_group /
+    ln 2`` and ``lfcSE = sd / ln 2`` (NaN where the posterior is not log-concave at its mode); ``lfcMLE`` and ``lfcMLESE`` keep the
+    old values; ``stat``, ``pvalue``, ``padj`` and the row order are unchanged, for ``test="lrt"`` frames too.  ``attrs`` gain
+    ``shrink='apeglm'``, ``prior_scale``, ``prior_var``, ``n_at_bound`` (none is expected) and ``coefficients_shrunk`` (genes x p
+    at the mode, natural log).  ValueError before any device work: a frame without ``attrs['design']`` (the design ``~ stage``:
+    use :func:`lfc_shrink`), a frame already shrunken, genes or samples that are not the table's.
+
+    Deviations, unpinned: the global grid search instead of apeglm's local optimiser; the normal prior sits on every unshrunk
+    coefficient; ``|beta| < 10`` stands in for K23's "no floored group fit" when the prior scale is estimated; numeric covariates
+    are scaled (:func:`deseq2_design`); no s-values."""
+    who = "lfc_shrink_design"
+    c, genes = _nb_counts(cluster_counts, who)
+    columns = ["gene", "log2FoldChange", "lfcSE", "dispersion"]
+    if not hasattr(de, "columns") or any(col not in de.columns for col in columns) or "size_factors" not in de.attrs:
+        raise ValueError("%s: de must be a frame of compute_pseudobulk_DE (columns %s; attrs size_factors, design, coefficients)"
+                         % (who, ", ".join(columns)))
+    if "design" not in de.attrs or "coefficients" not in de.attrs:
+        raise ValueError("%s: de.attrs has no 'design': the frame is of the design `~ group` (no covariates); use lfc_shrink" % who)
+    if "lfcMLE" in de.columns:
+        raise ValueError("%s: de is already shrunken (it has a column lfcMLE)" % who)
+    _estimated_or_positive(who, "prior_scale", prior_scale)
+    named = pd.Index(de["gene"])
+    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)
+    if len(de) != len(genes) or (at < 0).any():
+        raise ValueError("%s: the genes of de are not the columns of cluster_counts" % who)
+    design, coefficients = de.attrs["design"], de.attrs["coefficients"]
+    samples = getattr(cluster_counts, "index", pd.RangeIndex(c.shape[0]))
+    if len(design) != c.shape[0] or not pd.Index(design.index).equals(pd.Index(samples)):
+        raise ValueError("%s: the samples of de.attrs['design'] are not the rows of cluster_counts" % who)
+    if list(coefficients.columns) != list(design.columns) or (pd.Index(coefficients.index).get_indexer(genes) < 0).any():
+        raise ValueError("%s: de.attrs['coefficients'] is not genes x design columns of this table" % who)
+    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
+    X = engine._nb_design_arg(design.to_numpy(dtype=np.float64), c.shape[0])
+    mle = np.ascontiguousarray(coefficients.reindex(genes).to_numpy(dtype=np.float64))
+    disp = de["dispersion"].to_numpy(dtype=np.float64)[at]
+    ln2 = np.log(2.0)
+    bk, se = mle[:, -1], de["lfcSE"].to_numpy(dtype=np.float64)[at] * ln2
+    if prior_scale is None:
+        with np.errstate(invalid="ignore"):
+            S, A = engine.nb_prior_scale(bk, se, use=np.isfinite(bk) & (np.abs(bk) < 10.0))
+    else:
+        S, A = float(prior_scale), float(prior_scale) ** 2
+    beta, info = engine.nb_design_shrink(c, X, sf, disp, mle, engine.nb_design_far_end(bk), S, return_info=True)
+    sd = engine.nb_design_posterior_sd(beta, info["information"], S)
+    row = genes.get_indexer(de["gene"])                          # the table's column of every row of the frame
+    out = de.copy()
+    out["lfcMLE"], out["lfcMLESE"] = de["log2FoldChange"], de["lfcSE"]
+    out["log2FoldChange"], out["lfcSE"] = (beta[:, -1] / ln2)[row], (sd / ln2)[row]
+    out.attrs.update(shrink="apeglm", prior_scale=S, prior_var=A, n_at_bound=info["n_at_bound"],
+                     coefficients_shrunk=pd.DataFrame(beta, index=genes, columns=list(design.columns)))
+    return out
+
+
 def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=None, group2=None, cluster_col=None, fit_type="parametric",
                           shrink=None, prior_scale=None, outliers=None, independent_filtering=False, alpha=0.05, covariates=None,
                           test="wald"):
@@ -2826,7 +2889,8 @@ def compute_pseudobulk_DE(cluster_counts=None, cluster_metadata=None, group1=Non
     ``stat = 2 (loglik_full - loglik_reduced)`` and ``pvalue = chi2.sf(stat, 1)`` (the fold change and its error stay the Wald
     ones).  The frame has the same columns; ``attrs`` gain ``design`` (the frame of X), ``coefficients`` (genes x p, natural log)
     and ``test``, and have no ``floored``.  ``independent_filtering`` works as above.  ``shrink="apeglm"`` or ``outliers="deseq2"``
-    with covariates: NotImplementedError before any device work -- K23 and K25 are rules for the group design.  Any other
+    with covariates: NotImplementedError before any device work -- K23 and K25 are rules for the group design (for the shrinkage,
+    pass the returned frame to :func:`lfc_shrink_design`).  Any other
     ``test``, ``test="lrt"`` without covariates, an unknown, constant or confounded covariate, more than
     ``engine.NB_DESIGN_MAX_COLS`` design columns or no residual degree of freedom: ValueError before any device work.  Deviations
     from DESeq2 under a design: the profile re-solves the coefficients where DESeq2 holds the means of one rough

@@ -41,7 +41,15 @@ column alone on the same table: both searches are one wave per gene and six 64-p
 nb_design_dispersions adds an inner Newton fit of p coefficients at every grid point (two passes over the samples a step, one for
 the normal equations and one for the line search).  ``nb_dispersions`` and ``nb_design_dispersions`` alternate in one loop, and so
 do ``nb_group_fits`` and ``nb_design_fits``, best of --reps each; the mean inner steps a lane and round go beside the ratio.  Host:
-the vectorised restatement (tests/nb_design_restatement.py) on --host-genes genes, scaled.  Writes OUT/design_rate.txt."""
+the vectorised restatement (tests/nb_design_restatement.py) on --host-genes genes, scaled.  Writes OUT/design_rate.txt.
+
+--design-shrink: instead, the shrunken coefficient under a general design (K27: engine.nb_design_shrink) at --design-cols columns
+beside K26's dispersion pass on the same table: both are one wave per gene and six 64-point rounds over LDS-staged samples with an
+inner Newton fit at every grid point -- of p coefficients there, of p - 1 here, warm-started from the lane's own last point.  The
+dispersions are one MAP-less pass, the maximum-likelihood coefficients nb_design_fits', the prior scale nb_prior_scale's.
+``nb_design_dispersions`` and ``nb_design_shrink`` alternate in one loop, best of --reps each; the mean inner steps a lane and
+round of both go beside the ratio.  Host: the restatement (tests/nb_design_shrink_restatement.py) on --host-genes genes, scaled.
+Writes OUT/design_shrink_rate.txt."""
 import argparse
 import os
 import sys
@@ -65,11 +73,12 @@ def main():
     ap.add_argument("--rlog", action="store_true")
     ap.add_argument("--cooks", action="store_true")
     ap.add_argument("--design", action="store_true")
-    ap.add_argument("--design-cols", type=int, default=4, help="--design: the columns of the design matrix")
+    ap.add_argument("--design-shrink", action="store_true")
+    ap.add_argument("--design-cols", type=int, default=4, help="--design, --design-shrink: the columns of the design matrix")
     ap.add_argument("--outlier-share", type=float, default=0.02, help="--cooks: the share of genes that get one count x 200")
     a = ap.parse_args()
-    if a.shrink + a.rlog + a.cooks + a.design > 1:
-        ap.error("--shrink, --rlog, --cooks and --design are separate runs")
+    if a.shrink + a.rlog + a.cooks + a.design + a.design_shrink > 1:
+        ap.error("--shrink, --rlog, --cooks, --design and --design-shrink are separate runs")
     import nb_glm_restatement as RR
     from pilot_amd import _lib, engine
 
@@ -260,7 +269,50 @@ def main():
             "resolved genes (%d): dispersion off by at most %.2g relative"
             % (h, t_host, a.genes, h, t_host * a.genes / h, res.sum(), np.abs(np.expm1(x26[:h][res] - xh[res])).max(initial=0)))
         del D
-    for m in (() if a.shrink or a.rlog or a.cooks or a.design else a.samples):
+    for m in (a.samples if a.design_shrink else ()):
+        import nb_design_restatement as DR
+        import nb_design_shrink_restatement as KR
+        rng = np.random.default_rng(m)
+        s = RR.size_factors(rng, m)
+        X, kinds = DR.make_design(rng, m, a.design_cols)
+        c = DR.nb_class(rng, s, X, kinds, a.genes)
+        D = engine.DeviceMatrix.upload(c.astype(np.float32))
+        x26, disp = engine.nb_design_dispersions(D, X, s, return_info=True)
+        alpha = engine.nb_clip(np.exp(x26), m)
+        mle, cov, _ = engine.nb_design_fits(D, X, s, alpha)
+        bk = mle[:, -1]
+        with np.errstate(invalid="ignore"):
+            S, A = engine.nb_prior_scale(bk, np.sqrt(cov[:, -1, -1]), use=np.isfinite(bk) & (np.abs(bk) < 10))
+        far = engine.nb_design_far_end(bk)
+        engine.nb_design_shrink(D, X, s, alpha, mle, far, S)
+        t = np.full(2, np.inf)
+        for _ in range(a.reps):                                         # the calls alternate
+            t0 = time.perf_counter()
+            engine.nb_design_dispersions(D, X, s)
+            t1 = time.perf_counter()
+            beta, info = engine.nb_design_shrink(D, X, s, alpha, mle, far, S, return_info=True)
+            t2 = time.perf_counter()
+            t = np.minimum(t, [t1 - t0, t2 - t1])
+        live = ~np.isnan(beta[:, -1])
+        say("case %d genes x %d samples, float32 in HBM, design of %d columns (%s), prior scale %.3f"
+            % (a.genes, m, a.design_cols, ", ".join(kinds), S))
+        say("  nb_design_shrink %.2f ms, nb_design_dispersions (gene-wise) %.2f ms beside it: ratio %.2f; best of %d, alternating"
+            % (1e3 * t[1], 1e3 * t[0], t[1] / t[0], a.reps))
+        say("  inner Newton steps a lane and round: nb_design_shrink mean %.2f, largest gene mean %.2f; nb_design_dispersions mean %.2f; "
+            "%d genes at the bound, %d with a fit that did not converge"
+            % (info["steps"][live].mean() / 384.0, info["steps"][live].max() / 384.0, disp["steps"][live].mean() / 384.0, info["n_at_bound"],
+               info["n_not_converged"]))
+        h = min(a.host_genes, a.genes)
+        t0 = time.perf_counter()
+        found = KR.search(c[:, :h], X, s, alpha[:h], far[:h], S, a.design_cols - 1, start=mle[:h])
+        t_host = time.perf_counter() - t0
+        res = KR.resolved(c[:, :h], X, s, alpha[:h], far[:h], S, a.design_cols - 1, found)
+        say("  host restatement (vectorised numpy) on %d genes: %.2f s; scaled by %d / %d: %.0f s; device against it on the resolved genes "
+            "(%d): t off by at most %.2g"
+            % (h, t_host, a.genes, h, t_host * a.genes / h, res.sum(),
+               np.abs(KR.t_of(beta[:h, -1], S) - found["t"])[res].max(initial=0)))
+        del D
+    for m in (() if a.shrink or a.rlog or a.cooks or a.design or a.design_shrink else a.samples):
         rng = np.random.default_rng(m)
         s = RR.size_factors(rng, m)
         codes = (np.arange(m) % 2).astype(np.int32)
@@ -295,7 +347,7 @@ def main():
                np.abs(np.expm1(x[:h][res] - xh[res])).max(initial=0)))
         del D, Z
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "design_rate.txt" if a.design else "rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "design_rate.txt" if a.design else "design_shrink_rate.txt" if a.design_shrink else "rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

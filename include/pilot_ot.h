@@ -779,6 +779,39 @@ int pilot_ot_nb_design_shrink(const void *Y, int Y_is_device, int dtype, long lo
                               const double *far_end, double prior_scale, double other_scale, double *beta, double *objective, double *info,
                               int *flags, int *n_at_bound, long long *bad_row, int *bad_col);
 
+/* pilot_ot_nb_design_cooks (K28): pilot_ot_nb_cooks for the general design, the outlier handling of `DESeq(dds)` and `results(dds)`
+ * after a fit with covariates.  THIS LIBRARY'S STATEMENT, unpinned (restated in tests/nb_design_cooks_restatement.py).
+ * Y, X, p, size_factors as pilot_ot_nb_design_fits; dispersion: the gene's FINAL dispersion alpha (host; NaN leaves the gene out); beta:
+ * n_genes x p, that call's coefficients at it; lambda = 1e-6, its ridge.  cells (host, m codes in [0, n_cells)): DESeq2's
+ * nOrMoreInCell -- a cell is a maximal set of samples whose rows of X are bit-identical, numbered by first appearance; for
+ * X = [1, indicator] the cells are pilot_ot_nb_cooks' groups, with a numeric covariate usually singletons.  With c, q_j, tm as there:
+ *     trimmed_base = tm(q of all m samples, floor(m / 5))
+ *     v = max over the cells of n >= 3 samples of pilot_ot_nb_cooks' v_g (the same r, scale and d by the cell's size);
+ *         without such a cell v = 1.51 tm((q - tm(q, d))^2, d) over all samples, d = floor(m / 8) (DESeq2's trimmedVariance)
+ *     alpha_robust = max((v - mean_j q_j) / (mean_j q_j)^2, 0.04)
+ *     mu_j = max(s_j exp(x_j^T beta), minmu),  w_j = mu_j / (1 + alpha mu_j),  M = X^T W X + lambda I (the matrix whose inverse
+ *     pilot_ot_nb_design_fits reports),  h_j = w_j x_j^T M^-1 x_j
+ *     D_j = (c_j - mu_j)^2 / (mu_j + alpha_robust mu_j^2)  h_j / (p (1 - h_j)^2)      (h_j < 1 with the ridge: no NaN rule)
+ *     max_cooks = max of D_j over the samples of cells with n >= 3; arg_max the lowest sample index that attains it;
+ *     n_above = #{j: c_j > c_arg_max};  n_replace = #{j: D_j > cutoff and n_cell(j) >= min_replace}
+ * Without a cell of n >= 3: max_cooks = NaN, arg_max = -1, n_above = 0, and no sample can be replaced or flagged; alpha_robust, D and H
+ * are still computed.  A gene of zeros, with a NaN dispersion or a non-finite beta: NaN in every float result, arg_max = -1, counts 0.
+ * One wave per gene; c and q staged in LDS in (cell, sample) order beside the bitonic sort buffer; a lane reads the rows of X of its
+ * own samples from global memory; M as per-lane partials of the packed upper triangle closed by one fixed butterfly each, factored
+ * and inverted in registers.  Same bits as stated above for the K22 calls, and for a gene alone or in any batch.
+ * Out (host, n_genes): alpha_robust, max_cooks, arg_max, n_above, n_replace, trimmed_base.  D, H: nullable; m x n_genes float64 with
+ * leading dimensions ld_D, ld_H >= n_genes, each on the host or in HBM (D_is_device, H_is_device): D[j, gene] = D_j, H[j, gene] = h_j.
+ * PILOT_OT_EINVAL (before any HIP call): the cases of pilot_ot_nb_design_fits, a cutoff not positive and finite, min_replace < 3,
+ * ld_D or ld_H < n_genes with that matrix, n_cells outside [1, m], a cell code outside [0, n_cells), a row of X that differs from the
+ * first row of its cell, a cell without a sample, a non-finite beta where the gene's dispersion is not NaN; after the check pass a
+ * negative or non-finite count (*bad_row / *bad_col as pilot_ot_nb_dispersions).  PILOT_OT_ENOTSUP: m > INT_MAX; m >
+ * pilot_ot_nb_design_max_samples(p) (which keeps the LDS, 8 (2 m + P') bytes with P' the power of two >= m, within 96 KiB). */
+int pilot_ot_nb_design_cooks(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                             const int *cells, int n_cells, const double *size_factors, const double *dispersion, const double *beta,
+                             double cutoff, int min_replace, double *alpha_robust, double *max_cooks, int *arg_max, int *n_above,
+                             int *n_replace, double *trimmed_base, void *D, int D_is_device, long long ld_D, void *H, int H_is_device,
+                             long long ld_H, long long *bad_row, int *bad_col);
+
 /* ---- principal components (K15): the PCA that pilotpy's extract_annot_expression(reduction=True) and reclustering_data take from
  * scanpy (tools/Trajectory.py:199-208, 1035-1044: scale(max_value) then tl.pca(svd_solver='arpack')), of a matrix that is never
  * standardised in memory.  Y: n rows x the n_sel selected columns (cols: host, distinct, any order; NULL: every column).

@@ -57,7 +57,7 @@ SYMBOLS = [
     "pilot_ot_nb_dispersions", "pilot_ot_nb_group_fits", "pilot_ot_nb_glm_max_samples", "pilot_ot_nb_shrink",
     "pilot_ot_nb_dispersions_blind", "pilot_ot_nb_rlog", "pilot_ot_nb_cooks",
     "pilot_ot_nb_design_max_cols", "pilot_ot_nb_design_max_samples", "pilot_ot_nb_design_dispersions", "pilot_ot_nb_design_fits",
-    "pilot_ot_nb_design_shrink",
+    "pilot_ot_nb_design_shrink", "pilot_ot_nb_design_cooks",
     "pilot_ot_csr_pca", "pilot_ot_pca", "pilot_ot_knn_rows", "pilot_ot_knn_smooth", "pilot_ot_louvain", "pilot_ot_leiden",
     "pilot_ot_silhouette_points", "pilot_ot_silhouette_points_geometry",
     "pilot_ot_elastic_fit_batch", "pilot_ot_point_moments", "pilot_ot_tree_projection",
@@ -215,6 +215,9 @@ def load() -> ctypes.CDLL:
                                           ip, ip, ip, llp, ip]
     L.pilot_ot_nb_design_shrink.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, dp, c_int, c_int, dp, dp, dp, dp,
                                             c_dbl, c_dbl, dp, dp, dp, ip, ip, llp, ip]
+    L.pilot_ot_nb_design_cooks.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, dp, c_int, ip, c_int, dp, dp, dp,
+                                           c_dbl, c_int, dp, dp, ip, ip, ip, dp, c_vp, c_int, ctypes.c_longlong, c_vp, c_int,
+                                           ctypes.c_longlong, llp, ip]
     L.pilot_ot_csr_pca.argtypes = [c_vp, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_pca.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, c_int, c_dbl, c_int, dp, dp, dp, dp, ip]
     L.pilot_ot_knn_rows.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_int, ctypes.c_longlong,

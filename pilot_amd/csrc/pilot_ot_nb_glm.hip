@@ -1,17 +1,19 @@
 // C ABI of the negative-binomial GLM for a one-factor design and, at the end, for a general one (include/pilot_ot.h, section
 // "negative-binomial GLM"; kernels: nb_glm_kernels.hpp, nb_shrink_kernel.hpp, nb_rlog_kernel.hpp, nb_cooks_kernel.hpp, nb_design_kernels.hpp,
-// nb_design_shrink_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
+// nb_design_shrink_kernel.hpp, nb_design_cooks_kernel.hpp).  Y is a host array (copied whole, packed) or a row-major buffer in HBM with its own leading dimension;
 // codes, size factors, dispersions and the results are host arrays.  The host orders the samples by group once per call.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
 #include "abi_common.hpp"
 #include "nb_cooks_kernel.hpp"
+#include "nb_design_cooks_kernel.hpp"
 #include "nb_design_kernels.hpp"
 #include "nb_design_shrink_kernel.hpp"
 #include "nb_glm_kernels.hpp"
@@ -42,15 +44,13 @@ int check_samples(long long m, const double *sf, const int *codes = nullptr, int
     return PILOT_OT_OK;
 }
 
-// check_samples, then the sorted design.  Without codes: the design `~ 1` of m samples (blind), one group (n_groups = 1), the
-// samples in their own order.
-int make_design(long long m, const int *codes, int n_groups, const double *sf, Design &d) {
-    if (int rc = check_samples(m, sf, codes, n_groups)) return rc;
+// the samples ordered by their code (every one of [0, n_groups), checked by the caller; NULL: all 0), `what` names a code in a refusal
+int sort_samples(long long m, const int *codes, int n_groups, const double *sf, const char *what, Design &d) {
     const auto code = [codes](long long i) { return codes ? codes[i] : 0; };
     d.gstart.assign((size_t)n_groups + 1, 0);
     for (long long i = 0; i < m; ++i) ++d.gstart[(size_t)code(i) + 1];
     for (int g = 0; g < n_groups; ++g) {
-        if (d.gstart[(size_t)g + 1] == 0) return fail(PILOT_OT_EINVAL, "group %d has no sample", g);
+        if (d.gstart[(size_t)g + 1] == 0) return fail(PILOT_OT_EINVAL, "%s %d has no sample", what, g);
         d.gstart[(size_t)g + 1] += d.gstart[g];
     }
     std::vector<int> at(d.gstart.begin(), d.gstart.end() - 1);
@@ -66,22 +66,36 @@ int make_design(long long m, const int *codes, int n_groups, const double *sf, D
     return PILOT_OT_OK;
 }
 
+// check_samples, then the sorted design.  Without codes: the design `~ 1` of m samples (blind), one group (n_groups = 1), the
+// samples in their own order.
+int make_design(long long m, const int *codes, int n_groups, const double *sf, Design &d) {
+    if (int rc = check_samples(m, sf, codes, n_groups)) return rc;
+    return sort_samples(m, codes, n_groups, sf, "group", d);
+}
+
 struct DevDesign {
     int *order, *gof, *gstart;
     double *ss;
 };
 
-int upload_design(const Design &d, DevDesign &dev) {
+// order, gof and gstart of the sorted samples
+int upload_order(const Design &d, DevDesign &dev) {
     const size_t m = d.order.size(), k1 = d.gstart.size();
     int *ints;
     HIP_TRY(pilot::ws(pilot::WS_NB_INT, 2 * m + k1, &ints));
-    HIP_TRY(pilot::ws(pilot::WS_NB_SF, m, &dev.ss));
     dev.order = ints;
     dev.gof = ints + m;
     dev.gstart = dev.gof + m;
     HIP_TRY(hipMemcpy(dev.order, d.order.data(), sizeof(int) * m, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dev.gof, d.gof.data(), sizeof(int) * m, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dev.gstart, d.gstart.data(), sizeof(int) * k1, hipMemcpyHostToDevice));
+    return PILOT_OT_OK;
+}
+
+int upload_design(const Design &d, DevDesign &dev) {
+    const size_t m = d.order.size();
+    if (int rc = upload_order(d, dev)) return rc;
+    HIP_TRY(pilot::ws(pilot::WS_NB_SF, m, &dev.ss));
     HIP_TRY(hipMemcpy(dev.ss, d.ss.data(), sizeof(double) * m, hipMemcpyHostToDevice));
     return PILOT_OT_OK;
 }
@@ -476,11 +490,10 @@ int check_design_matrix(const double *X, long long m, int p) {
     return PILOT_OT_OK;
 }
 
-int check_design_samples(long long m, int p) {
+// `staged`: what of a gene the call's kernel stages in LDS
+int check_design_samples(long long m, int p, const char *staged = "counts, log size factors and design rows") {
     const int limit = pilot::nb_design_max_samples(p);
-    return m > limit ? fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's counts, log size factors and design rows are staged in LDS, at most %d for p=%d",
-                            m, limit, p)
-                     : PILOT_OT_OK;
+    return m > limit ? fail(PILOT_OT_ENOTSUP, "m=%lld samples: a gene's %s are staged in LDS, at most %d for p=%d", m, staged, limit, p) : PILOT_OT_OK;
 }
 
 // the size factors, their logarithms and X (m x p) behind each other in HBM: what both kernels read as `sf`
@@ -688,4 +701,100 @@ PILOT_API int pilot_ot_nb_design_shrink(const void *Y, int Y_is_device, int dtyp
     }
     count_flag(flags, n_genes, pilot::NB_FLAG_AT_BOUND, n_at_bound);
     return PILOT_OT_OK;
+}
+
+// ---- K28: Cook's distances under a general design (nb_design_cooks_kernel.hpp) -------------------------------------------------------
+namespace {
+
+// cells are codes in [0, n_cells), and every row of a cell is bit-identical to the cell's first; no HIP call
+int check_cells(const double *X, long long m, int p, const int *cells, int n_cells) {
+    if (n_cells < 1 || n_cells > m) return fail(PILOT_OT_EINVAL, "n_cells=%d must be in [1, m = %lld]", n_cells, m);
+    std::vector<long long> first((size_t)n_cells, -1);
+    for (long long j = 0; j < m; ++j) {
+        if (cells[j] < 0 || cells[j] >= n_cells) return fail(PILOT_OT_EINVAL, "cells[%lld]=%d outside [0, %d)", j, cells[j], n_cells);
+        long long &f = first[(size_t)cells[j]];
+        if (f < 0) f = j;
+        else if (std::memcmp(X + j * p, X + f * p, sizeof(double) * (size_t)p) != 0)
+            return fail(PILOT_OT_EINVAL, "cells[%lld]=%d: row %lld of X differs from row %lld, the first of that cell", j, cells[j], j, f);
+    }
+    return PILOT_OT_OK;
+}
+
+template <typename T, int P>
+int design_cooks(const void *y, long long ld, int m, int n_genes, int n_cells, const DevDesign &dd, const double *d_sf, const double *dispersion,
+                 const double *beta, double cutoff, int min_replace, double *alpha_robust, double *max_cooks, int *arg_max, int *n_above,
+                 int *n_replace, double *trimmed_base, ResultMatrix D, ResultMatrix H, long long *bad_row, int *bad_col) {
+    if (int rc = check_counts<T>(y, ld, m, n_genes, bad_row, bad_col)) return rc;
+    const size_t G = (size_t)n_genes, M = (size_t)m;
+    size_t Psort = 1;                                        // the sort buffer: the power of two >= m
+    while (Psort < M) Psort <<= 1;
+    double *d_in, *d_out;                                    // dispersion | beta;  the three double results | packed D | packed H (host ones)
+    int *d_int;
+    HIP_TRY(pilot::ws(pilot::WS_NB_PRIOR, (1 + (size_t)P) * G, &d_in));
+    HIP_TRY(pilot::ws(pilot::WS_NB_OUT, 3 * G + D.tail() + H.tail(), &d_out));
+    HIP_TRY(pilot::ws(pilot::WS_NB_FIT_INT, 3 * G, &d_int));
+    HIP_TRY(hipMemcpy(d_in, dispersion, sizeof(double) * G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in + G, beta, sizeof(double) * P * G, hipMemcpyHostToDevice));
+    D.place(d_out + 3 * G);
+    H.place(d_out + 3 * G + D.tail());
+    if (int rc = launch_wave_per_gene(pilot::nb_design_cooks_kernel<T, P>, n_genes, 2 * M + Psort, static_cast<const T *>(y), ld, m, n_cells,
+                                      dd.order, dd.gof, dd.gstart, d_sf, d_in, d_in + G, cutoff, min_replace, n_genes, d_out, d_int, D.dev,
+                                      D.ld(), H.dev, H.ld()))
+        return rc;
+    HIP_TRY(fetch(alpha_robust, d_out, G));
+    HIP_TRY(fetch(max_cooks, d_out + G, G));
+    HIP_TRY(fetch(trimmed_base, d_out + 2 * G, G));
+    HIP_TRY(fetch(arg_max, d_int, G));
+    HIP_TRY(fetch(n_above, d_int + G, G));
+    HIP_TRY(fetch(n_replace, d_int + 2 * G, G));
+    HIP_TRY(D.fetch());
+    HIP_TRY(H.fetch());
+    return PILOT_OT_OK;
+}
+
+}  // namespace
+
+PILOT_API int pilot_ot_nb_design_cooks(const void *Y, int Y_is_device, int dtype, long long m, int n_genes, long long ld, const double *X, int p,
+                                       const int *cells, int n_cells, const double *size_factors, const double *dispersion, const double *beta,
+                                       double cutoff, int min_replace, double *alpha_robust, double *max_cooks, int *arg_max, int *n_above,
+                                       int *n_replace, double *trimmed_base, void *D, int D_is_device, long long ld_D, void *H, int H_is_device,
+                                       long long ld_H, long long *bad_row, int *bad_col) {
+    Call c{Y, Y_is_device, dtype, m, n_genes, ld, size_factors, false, nullptr, 1, dispersion, nullptr};
+    if (int rc = prologue(
+            c, !Y || !X || !cells || !size_factors || !dispersion || !beta || !alpha_robust || !max_cooks || !arg_max || !n_above || !n_replace ||
+                   !trimmed_base,
+            bad_row, bad_col,
+            [&] {
+                if (int rc = positive_finite("cutoff", cutoff)) return rc;
+                if (min_replace < pilot::NB_COOKS_MIN_GROUP)
+                    return fail(PILOT_OT_EINVAL, "min_replace=%d: at least %d (smaller cells have no Cook's distance to compare)", min_replace,
+                                pilot::NB_COOKS_MIN_GROUP);
+                if (D && ld_D < n_genes) return fail(PILOT_OT_EINVAL, "ld_D=%lld is smaller than n_genes=%d", ld_D, n_genes);
+                return H && ld_H < n_genes ? fail(PILOT_OT_EINVAL, "ld_H=%lld is smaller than n_genes=%d", ld_H, n_genes) : PILOT_OT_OK;
+            },
+            [&] {
+                if (int rc = check_design_matrix(X, m, p)) return rc;
+                if (int rc = check_cells(X, m, p, cells, n_cells)) return rc;
+                if (int rc = sort_samples(m, cells, n_cells, size_factors, "cell", c.d)) return rc;
+                for (int j = 0; j < n_genes; ++j) {
+                    if (std::isnan(dispersion[j])) continue;
+                    for (int t = 0; t < p; ++t) {
+                        const double v = beta[(long long)j * p + t];
+                        if (!std::isfinite(v)) return fail(PILOT_OT_EINVAL, "beta[%d, %d]=%g must be finite where the gene has a dispersion", j, t, v);
+                    }
+                }
+                return check_design_samples(m, p, "counts, normalised counts and sort buffer");
+            }))
+        return rc;
+    if (int rc = upload_order(c.d, c.dd)) return rc;
+    double *d_sf;
+    if (int rc = upload_design_matrix(size_factors, X, (size_t)m, p, &d_sf)) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return by_columns(p, [&](auto P) {
+            return design_cooks<decltype(t), decltype(P)::value>(
+                c.y, c.y_ld, (int)m, n_genes, n_cells, c.dd, d_sf, dispersion, beta, cutoff, min_replace, alpha_robust, max_cooks, arg_max, n_above,
+                n_replace, trimmed_base, ResultMatrix{D, D_is_device, ld_D, (size_t)m, (size_t)n_genes},
+                ResultMatrix{H, H_is_device, ld_H, (size_t)m, (size_t)n_genes}, bad_row, bad_col);
+        });
+    });
 }

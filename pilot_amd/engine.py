@@ -1988,6 +1988,68 @@ def nb_replacements(counts, codes, size_factors, D, cutoff, trimmed_base, min_re
     return rows
 
 
+# ---- Cook's distances under a general design (K28; the outlier handling of K25 for the model with covariates of K26) -----------------
+def nb_design_cells(design):
+    """DESeq2's ``nOrMoreInCell`` grouping of a design matrix; pure numpy.  A cell is a maximal set of samples whose rows of
+    ``design`` (m x p) are bit-identical; cells are numbered by first appearance.  Returns ``(codes int32, n_cells)``.  For
+    ``[1, indicator]`` the cells are the two groups; with a numeric covariate every cell is usually one sample."""
+    X = np.asarray(design)
+    if X.ndim != 2 or X.shape[0] < 1 or X.dtype.kind not in "biuf":
+        raise ValueError("design must be a numeric samples x columns matrix, got shape %s of %s" % (X.shape, X.dtype))
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    seen, codes = {}, np.empty(X.shape[0], dtype=np.int32)
+    for j in range(X.shape[0]):
+        codes[j] = seen.setdefault(X[j].tobytes(), len(seen))
+    return codes, len(seen)
+
+
+def nb_design_cooks(counts, design, size_factors, dispersion, beta, cutoff, min_replace=NB_COOKS_MIN_REPLACE, return_distances=False):
+    """K28: :func:`nb_cooks` for a general ``design`` (as :func:`nb_design_fits` takes it): per gene (column) of ``counts`` the Cook's
+    distances of the negative-binomial GLM with covariates (include/pilot_ot.h, pilot_ot_nb_design_cooks; the rule is
+    this library's statement, unpinned).  ``dispersion``: the gene's final dispersion (NaN leaves the gene out); ``beta``: genes x p,
+    :func:`nb_design_fits`' coefficients at it (finite where the gene has a dispersion).  K25's groups become CELLS
+    (:func:`nb_design_cells`: samples with identical design rows).  The robust dispersion comes from the largest trimmed variance of
+    ``c / s`` over the cells of at least 3 samples, or, without one, from the 1/8-trimmed variance over all samples; the hat diagonal is
+    ``h_j = w_j x_j^T (X^T W X + 1e-6 I)^-1 x_j`` at the fitted means and the final dispersion, and the distance divides by p.
+    Returns the dict of :func:`nb_cooks` (``max_cooks`` and ``arg_max`` over the samples of cells with at least 3, ``n_replace`` over
+    those of at least ``min_replace``); with ``return_distances`` also ``D`` and ``H`` (the hat diagonal), samples x genes
+    (``"device"``: :class:`DeviceMatrix`).  Under a design whose cells are all below 3 (a numeric covariate) the distances are
+    computed but nothing can be replaced or flagged: ``max_cooks`` is NaN and ``n_replace`` 0, as in DESeq2.  One wave per gene.  The
+    same bits from a repeated call, from float32 and float64 storage, from host and device matrices, and for a gene alone or in any
+    batch.  More samples than :func:`nb_design_limits` allows for p: NotImplementedError; errors otherwise as
+    :func:`nb_design_fits`."""
+    Y = _dense_arg(counts, "counts", mode="strict")
+    sf = _nb_blind_args(Y.rows, Y.cols, size_factors)
+    X = _nb_design_arg(design, Y.rows)
+    alpha = _nb_dispersion_arg(dispersion, Y.cols, Y.rows)
+    p = X.shape[1]
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    if beta.shape != (Y.cols, p):
+        raise ValueError("beta has shape %s for %d genes and %d design columns" % (beta.shape, Y.cols, p))
+    if not np.isfinite(beta[~np.isnan(alpha)]).all():
+        raise ValueError("beta must be finite where the gene has a dispersion")
+    cutoff, min_replace = _nb_cutoff_arg(cutoff), _nb_min_replace_arg(min_replace)
+    if return_distances not in (False, True, "device"):
+        raise ValueError("return_distances=%r must be False, True or 'device'" % (return_distances,))
+    cells, n_cells = nb_design_cells(X)
+    limit = nb_design_limits()["max_samples"][p]
+    if Y.rows > limit:
+        raise NotImplementedError("nb_design_cooks: %d samples; a gene is staged in LDS, at most %d with %d design columns" % (Y.rows, limit, p))
+    out = {name: np.empty(Y.cols) for name in ("alpha_robust", "max_cooks", "trimmed_base")}
+    out.update({name: np.empty(Y.cols, dtype=np.int32) for name in ("arg_max", "n_above", "n_replace")})
+    on_device = return_distances == "device"
+    D, D_ptr = _result_matrix(Y.rows, Y.cols, on_device) if return_distances else (None, None)
+    H, H_ptr = _result_matrix(Y.rows, Y.cols, on_device) if return_distances else (None, None)
+    _nb_call(_lib.load().pilot_ot_nb_design_cooks,
+             Y.ptr, Y.on_dev, _lib.dtype_code(Y.dtype), Y.rows, Y.cols, Y.ld, _lib.dptr(X), p, _lib.iptr(cells), n_cells, _lib.dptr(sf),
+             _lib.dptr(alpha), _lib.dptr(beta), cutoff, min_replace, _lib.dptr(out["alpha_robust"]), _lib.dptr(out["max_cooks"]),
+             _lib.iptr(out["arg_max"]), _lib.iptr(out["n_above"]), _lib.iptr(out["n_replace"]), _lib.dptr(out["trimmed_base"]),
+             D_ptr, int(on_device), Y.cols, H_ptr, int(on_device), Y.cols)
+    if D is not None:
+        out["D"], out["H"] = D, H
+    return out
+
+
 def bh_adjust(p):
     """Benjamini-Hochberg adjusted p-values (statsmodels' multipletests(method='fdr_bh')[1])."""
     p = np.asarray(p, dtype=np.float64)

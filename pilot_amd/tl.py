@@ -2681,7 +2681,8 @@ def _check_design_options(who, covariates, test, shrink, outliers):
     if covariates and (shrink or outliers):
         raise NotImplementedError("%s: covariates with %s: the shrinkage (K23) and the outlier handling (K25) are rules for the design "
                                   "`~ group`%s" % (who, "shrink=%r" % (shrink,) if shrink else "outliers=%r" % (outliers,),
-                                                   "; shrink the frame afterwards with tl.lfc_shrink_design" if shrink else ""))
+                                                   "; shrink the frame afterwards with tl.lfc_shrink_design" if shrink
+                                                   else "; pass the frame to tl.outliers_design afterwards (K28)"))
     if test == "lrt" and not covariates:
         raise ValueError("%s: test='lrt' is the test of the design with covariates, pass covariates" % who)
     return covariates
@@ -2741,14 +2742,10 @@ def deseq2_design(cluster_metadata, cluster_col, group1, group2, covariates):
     return np.stack(columns, axis=1), names, meta.index
 
 
-def _nb_design_de(counts, X, names, fit_type, test, filtering_alpha):
-    """:func:`compute_pseudobulk_DE` by the route of DESIGN.md K26: the dispersion table, the final fit and the host tail for the
-    last design column"""
+def _nb_design_tests(c, X, sf, disp, test):
+    """the final fit of DESIGN.md K26 at the dispersions ``disp`` and the test of the last design column: ``(beta, log2FoldChange,
+    lfcSE, stat, pvalue, fits that did not converge)``; ``test="lrt"`` runs the reduced fit too"""
     from scipy import stats
-    c, genes = _nb_counts(counts, "compute_pseudobulk_DE")
-    sf = _nb_size_factors(counts, None, c.shape[0])
-    table = _nb_dispersion_table(c, genes, None, None, sf, fit_type, design=X)
-    disp = table["dispersion"].to_numpy()
     beta, cov, loglik, info = engine.nb_design_fits(c, X, sf, disp, return_info=True)
     n_bad = info["n_not_converged"]
     log2e = np.log2(np.e)
@@ -2761,6 +2758,17 @@ def _nb_design_de(counts, X, names, fit_type, test, filtering_alpha):
         n_bad += info0["n_not_converged"]
         stat = 2.0 * (loglik - reduced)
         p = stats.chi2.sf(stat, 1)
+    return beta, lfc, se, stat, p, int(n_bad)
+
+
+def _nb_design_de(counts, X, names, fit_type, test, filtering_alpha):
+    """:func:`compute_pseudobulk_DE` by the route of DESIGN.md K26: the dispersion table, the final fit and the host tail for the
+    last design column"""
+    c, genes = _nb_counts(counts, "compute_pseudobulk_DE")
+    sf = _nb_size_factors(counts, None, c.shape[0])
+    table = _nb_dispersion_table(c, genes, None, None, sf, fit_type, design=X)
+    disp = table["dispersion"].to_numpy()
+    beta, lfc, se, stat, p, n_bad = _nb_design_tests(c, X, sf, disp, test)
     base_mean = table["baseMean"].to_numpy()
     padj, filtering = _nb_padj(p, base_mean, filtering_alpha)
     out = pd.DataFrame({"gene": np.asarray(genes), "baseMean": base_mean, "log2FoldChange": lfc, "lfcSE": se, "stat": stat, "pvalue": p,
@@ -2772,6 +2780,45 @@ def _nb_design_de(counts, X, names, fit_type, test, filtering_alpha):
                      design=pd.DataFrame(X, index=counts.index, columns=names), coefficients=pd.DataFrame(beta, index=genes, columns=names),
                      test=test)
     return out
+
+
+def _shrunken_or_bad_scale(who, de, prior_scale):
+    if "lfcMLE" in de.columns:
+        raise ValueError("%s: de is already shrunken (it has a column lfcMLE)" % who)
+    _estimated_or_positive(who, "prior_scale", prior_scale)
+
+
+def _nb_design_intake(who, cluster_counts, de, columns, no_design, unless=None):
+    """``(cluster_counts, de)`` as the readers of a frame that :func:`compute_pseudobulk_DE` made WITH covariates take them apart
+    (:func:`lfc_shrink_design`, :func:`outliers_design`, :func:`deseq2_cooks_design`), every refusal in ``who``'s name and in one
+    order: the frame's columns, its design (``no_design`` ends that refusal in ``who``'s words), ``unless()`` (what only ``who``
+    checks), the genes, the samples, the coefficients.  Returns ``(c, genes, samples, sf, X, beta, at, dispersion)``: the counts
+    with ``attrs['replaced']`` applied, the table's labels, float64 size factors, the design matrix, the coefficients in the table's
+    gene order, the frame's row of every gene of the table and its dispersions in that order."""
+    c, genes = _nb_counts(cluster_counts, who)
+    if not hasattr(de, "columns") or any(col not in de.columns for col in columns) or "size_factors" not in de.attrs:
+        raise ValueError("%s: de must be a frame of compute_pseudobulk_DE (columns %s; attrs size_factors, design, coefficients)"
+                         % (who, ", ".join(columns)))
+    if "design" not in de.attrs or "coefficients" not in de.attrs:
+        raise ValueError("%s: de.attrs has no 'design': %s" % (who, no_design))
+    if unless:
+        unless()
+    named = pd.Index(de["gene"])
+    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)
+    if len(de) != len(genes) or (at < 0).any():
+        raise ValueError("%s: the genes of de are not the columns of cluster_counts" % who)
+    design, coefficients = de.attrs["design"], de.attrs["coefficients"]
+    samples = getattr(cluster_counts, "index", pd.RangeIndex(c.shape[0]))
+    if len(design) != c.shape[0] or not pd.Index(design.index).equals(pd.Index(samples)):
+        raise ValueError("%s: the samples of de.attrs['design'] are not the rows of cluster_counts" % who)
+    if list(coefficients.columns) != list(design.columns) or (pd.Index(coefficients.index).get_indexer(genes) < 0).any():
+        raise ValueError("%s: de.attrs['coefficients'] is not genes x design columns of this table" % who)
+    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
+    X = engine._nb_design_arg(design.to_numpy(dtype=np.float64), c.shape[0])
+    if "replaced" in de.attrs:                                   # (outliers_design: the fit is of the replaced counts)
+        c = _apply_replaced(c, genes, samples, de.attrs["replaced"], who)
+    beta = np.ascontiguousarray(coefficients.reindex(genes).to_numpy(dtype=np.float64))
+    return c, genes, samples, sf, X, beta, at, de["dispersion"].to_numpy(dtype=np.float64)[at]
 
 
 def lfc_shrink_design(cluster_counts, de, prior_scale=None):
@@ -2788,36 +2835,17 @@ def lfc_shrink_design(cluster_counts, de, prior_scale=None):
     old values; ``stat``, ``pvalue``, ``padj`` and the row order are unchanged, for ``test="lrt"`` frames too.  ``attrs`` gain
     ``shrink='apeglm'``, ``prior_scale``, ``prior_var``, ``n_at_bound`` (none is expected) and ``coefficients_shrunk`` (genes x p
     at the mode, natural log).  ValueError before any device work: a frame without ``attrs['design']`` (the design ``~ stage``:
-    use :func:`lfc_shrink`), a frame already shrunken, genes or samples that are not the table's.
+    use :func:`lfc_shrink`), a frame already shrunken, genes or samples that are not the table's.  A frame that went through
+    :func:`outliers_design` carries ``attrs['replaced']``: those counts are replaced in ``cluster_counts`` before the fit, and the
+    dispersions and coefficients are the refitted ones.
 
     Deviations, unpinned: the global grid search instead of apeglm's local optimiser; the normal prior sits on every unshrunk
     coefficient; ``|beta| < 10`` stands in for K23's "no floored group fit" when the prior scale is estimated; numeric covariates
     are scaled (:func:`deseq2_design`); no s-values."""
-    who = "lfc_shrink_design"
-    c, genes = _nb_counts(cluster_counts, who)
-    columns = ["gene", "log2FoldChange", "lfcSE", "dispersion"]
-    if not hasattr(de, "columns") or any(col not in de.columns for col in columns) or "size_factors" not in de.attrs:
-        raise ValueError("%s: de must be a frame of compute_pseudobulk_DE (columns %s; attrs size_factors, design, coefficients)"
-                         % (who, ", ".join(columns)))
-    if "design" not in de.attrs or "coefficients" not in de.attrs:
-        raise ValueError("%s: de.attrs has no 'design': the frame is of the design `~ group` (no covariates); use lfc_shrink" % who)
-    if "lfcMLE" in de.columns:
-        raise ValueError("%s: de is already shrunken (it has a column lfcMLE)" % who)
-    _estimated_or_positive(who, "prior_scale", prior_scale)
-    named = pd.Index(de["gene"])
-    at = named.get_indexer(genes) if named.is_unique and genes.is_unique else np.full(1, -1)
-    if len(de) != len(genes) or (at < 0).any():
-        raise ValueError("%s: the genes of de are not the columns of cluster_counts" % who)
-    design, coefficients = de.attrs["design"], de.attrs["coefficients"]
-    samples = getattr(cluster_counts, "index", pd.RangeIndex(c.shape[0]))
-    if len(design) != c.shape[0] or not pd.Index(design.index).equals(pd.Index(samples)):
-        raise ValueError("%s: the samples of de.attrs['design'] are not the rows of cluster_counts" % who)
-    if list(coefficients.columns) != list(design.columns) or (pd.Index(coefficients.index).get_indexer(genes) < 0).any():
-        raise ValueError("%s: de.attrs['coefficients'] is not genes x design columns of this table" % who)
-    sf = _nb_size_factors(cluster_counts, de.attrs["size_factors"], c.shape[0])
-    X = engine._nb_design_arg(design.to_numpy(dtype=np.float64), c.shape[0])
-    mle = np.ascontiguousarray(coefficients.reindex(genes).to_numpy(dtype=np.float64))
-    disp = de["dispersion"].to_numpy(dtype=np.float64)[at]
+    c, genes, _, sf, X, mle, at, disp = _nb_design_intake(
+        "lfc_shrink_design", cluster_counts, de, ["gene", "log2FoldChange", "lfcSE", "dispersion"],
+        "the frame is of the design `~ group` (no covariates); use lfc_shrink", lambda: _shrunken_or_bad_scale("lfc_shrink_design", de, prior_scale))
+    design = de.attrs["design"]
     ln2 = np.log(2.0)
     bk, se = mle[:, -1], de["lfcSE"].to_numpy(dtype=np.float64)[at] * ln2
     if prior_scale is None:
@@ -2833,6 +2861,128 @@ def lfc_shrink_design(cluster_counts, de, prior_scale=None):
     out["log2FoldChange"], out["lfcSE"] = (beta[:, -1] / ln2)[row], (sd / ln2)[row]
     out.attrs.update(shrink="apeglm", prior_scale=S, prior_var=A, n_at_bound=info["n_at_bound"],
                      coefficients_shrunk=pd.DataFrame(beta, index=genes, columns=list(design.columns)))
+    return out
+
+
+_DE_COLUMNS = ["gene", "baseMean", "log2FoldChange", "lfcSE", "stat", "pvalue", "padj", "dispersion"]
+
+
+def outliers_design(cluster_counts, de, min_replace=engine.NB_COOKS_MIN_REPLACE, independent_filtering=None, alpha=0.05):
+    """The outlier handling of ``DESeq(dds)`` and ``results(dds)`` (:func:`compute_pseudobulk_DE`'s ``outliers="deseq2"``, DESIGN.md
+    K25) for a frame that :func:`compute_pseudobulk_DE` made WITH ``covariates``, Wald or LRT, on the device
+    (``engine.nb_design_cooks``; the rule is this library's statement, UNPINNED).  ``cluster_counts``: the samples x
+    genes counts of the selected samples; ``de``: the frame, whose ``attrs`` supply the design, the coefficients, the size factors
+    and the dispersion table with its trend and prior widths.  K25's groups become CELLS, the sets of samples with identical design
+    rows (``engine.nb_design_cells``; DESeq2's ``nOrMoreInCell``); the hat diagonal comes from the whole design and the cutoff is
+    ``qf(0.99, p, m - p)``.  The steps are K25's: every sample's Cook's distance; in a cell of at least ``min_replace`` samples a
+    count whose distance passes the cutoff is replaced by ``trunc(trimmed mean of c / s  *  s_j)``; the genes with a replacement are
+    fitted again on the replaced counts (size factors, trend and prior widths stay; for ``test="lrt"`` the reduced fit too); a gene
+    whose largest distance over the samples of cells of 3 to ``min_replace - 1`` passes the cutoff loses ``pvalue`` unless three or
+    more samples have a larger count.  ``padj`` is recomputed by plain BH, or by ``engine.independent_filtering`` at ``alpha``;
+    ``independent_filtering=None`` means as the frame was made (on iff ``attrs['independent_filtering']`` exists; pass the ``alpha``
+    it was made with).  Returns a new frame ordered by ``padj`` with the columns ``maxCooks``, ``cooksOutlier``, ``replace`` and the
+    attrs ``cooks_cutoff`` and ``replaced`` (``gene, sample, count, replacement``); ``attrs['dispersions']`` and
+    ``attrs['coefficients']`` hold the refitted rows and ``n_not_converged`` grows by the refit's.  A gene that the replacement
+    empties becomes all NaN.  A frame in which nothing is replaced or flagged keeps every old column bit for bit.
+
+    Under a design whose cells are all below 3 samples (a numeric covariate) the distances are computed but nothing is replaced or
+    flagged, as in DESeq2: ``maxCooks`` is NaN throughout.  ValueError before any device work: a frame without ``attrs['design']``
+    (use ``compute_pseudobulk_DE(outliers="deseq2")`` for the design ``~ group``), a frame already handled (it has ``maxCooks``), a
+    shrunken frame (it has ``lfcMLE``: shrink afterwards, :func:`lfc_shrink_design` reads ``attrs['replaced']``), genes or samples
+    that are not the table's.  Deviations beyond K25's: DESIGN.md K28."""
+    who = "outliers_design"
+
+    def handled_or_shrunken():
+        if "maxCooks" in de.columns:
+            raise ValueError("%s: de has been through the outlier handling already (it has a column maxCooks)" % who)
+        if "lfcMLE" in de.columns:
+            raise ValueError("%s: de is shrunken (it has a column lfcMLE): handle the outliers first and shrink afterwards with "
+                             "lfc_shrink_design, which reads attrs['replaced']" % who)
+        if "dispersions" not in de.attrs or de.attrs.get("test") not in _DE_TESTS:
+            raise ValueError("%s: de.attrs lacks 'dispersions' / 'test': pass the frame compute_pseudobulk_DE returned" % who)
+        engine._nb_min_replace_arg(min_replace)
+        if not (independent_filtering is None or isinstance(independent_filtering, (bool, np.bool_))):
+            raise ValueError("%s: independent_filtering=%r must be None, True or False" % (who, independent_filtering))
+        _alpha_arg(who, alpha)
+
+    c, genes, samples, sf, X, beta, at, disp = _nb_design_intake(
+        who, cluster_counts, de, _DE_COLUMNS, "the frame is of the design `~ group` (no covariates); use compute_pseudobulk_DE(outliers=\"deseq2\")",
+        handled_or_shrunken)
+    table, test = de.attrs["dispersions"], de.attrs["test"]
+    if not pd.Index(table.index).equals(genes):
+        raise ValueError("%s: de.attrs['dispersions'] is not the table of these genes" % who)
+    if independent_filtering is None:
+        independent_filtering = "independent_filtering" in de.attrs
+    m, p = X.shape
+    cells, _ = engine.nb_design_cells(X)
+    cutoff = engine.nb_cooks_cutoff(m, p)
+    ck = engine.nb_design_cooks(c, X, sf, disp, beta, cutoff, min_replace)
+    max_cooks, n_above = ck["max_cooks"].copy(), ck["n_above"].copy()
+    cols = {name: de[name].to_numpy()[at].copy() for name in _DE_COLUMNS[1:]}       # the frame's columns in the table's gene order
+    beta, table, n_bad = beta.copy(), table.copy(), int(de.attrs.get("n_not_converged", 0))
+    rep = np.flatnonzero(ck["n_replace"] > 0)
+    replaced = pd.DataFrame({name: [] for name in _REPLACED_COLUMNS})
+    if rep.size:
+        sub = np.ascontiguousarray(c[:, rep])
+        ck2 = engine.nb_design_cooks(sub, X, sf, disp[rep], beta[rep], cutoff, min_replace, return_distances=True)
+        rows = engine.nb_replacements(sub, cells, sf, ck2["D"], cutoff, ck2["trimmed_base"], min_replace)
+        new = np.rint(sub.astype(np.float64))
+        new[rows["sample"], rows["gene"]] = rows["replacement"]
+        replaced = pd.DataFrame({"gene": np.asarray(genes)[rep[rows["gene"]]], "sample": np.asarray(samples)[rows["sample"]],
+                                 "count": rows["count"], "replacement": rows["replacement"]})
+        # the refit: the same fit of the replaced counts, the trend and both prior widths as they were
+        refit = _nb_dispersion_table(new, genes[rep], None, None, sf, None, frozen=table.attrs, design=X)
+        ndisp = refit["dispersion"].to_numpy()
+        beta[rep], lfc, se, stat, pv, bad = _nb_design_tests(new, X, sf, ndisp, test)
+        n_bad += bad
+        for j, name in enumerate(table.columns):
+            table.iloc[rep, j] = refit[name].to_numpy()
+        for name, v in (("baseMean", refit["baseMean"].to_numpy()), ("log2FoldChange", lfc), ("lfcSE", se), ("stat", stat), ("pvalue", pv),
+                        ("dispersion", ndisp)):
+            cols[name][rep] = v
+        live = ~np.isnan(ndisp)
+        max_cooks[rep], n_above[rep] = np.nan, 0
+        if live.any():
+            ck3 = engine.nb_design_cooks(np.ascontiguousarray(new[:, live]), X, sf, ndisp[live], beta[rep[live]], cutoff, min_replace,
+                                         return_distances=True)
+            max_cooks[rep[live]], n_above[rep[live]] = _nb_refit_max_cooks(new[:, live], cells, ck3["D"], min_replace)
+    with np.errstate(invalid="ignore"):
+        flagged = (max_cooks > cutoff) & (n_above < 3)
+    cols["pvalue"][flagged] = np.nan
+    padj, filtering = _nb_padj(cols["pvalue"], cols["baseMean"], float(alpha) if independent_filtering else None)
+    cols["padj"] = padj
+    replace = np.zeros(len(genes), dtype=bool)
+    replace[rep] = True
+    out = pd.DataFrame({"gene": np.asarray(genes), **{name: cols[name] for name in _DE_COLUMNS[1:]}, "maxCooks": max_cooks,
+                        "cooksOutlier": flagged, "replace": replace})
+    out = out.iloc[np.argsort(padj, kind="stable")].reset_index(drop=True)
+    out.attrs.update({k: v for k, v in de.attrs.items() if k != "independent_filtering"})
+    if filtering is not None:
+        out.attrs["independent_filtering"] = filtering
+    names = list(de.attrs["design"].columns)
+    out.attrs.update(dispersions=table, coefficients=pd.DataFrame(beta, index=genes, columns=names), n_not_converged=n_bad, cooks_cutoff=cutoff,
+                     replaced=replaced)
+    return out
+
+
+def deseq2_cooks_design(cluster_counts, de, min_replace=engine.NB_COOKS_MIN_REPLACE):
+    """The per-gene Cook's-distance table behind :func:`outliers_design` (``engine.nb_design_cooks``), for looking at
+    what the rule saw: :func:`deseq2_cooks` for a frame made WITH covariates.  ``de`` supplies the design, the size factors, the
+    dispersions and the coefficients; a frame that went through :func:`outliers_design` has its replacements applied first, so
+    the table describes the refitted state.  Returns a frame indexed by gene, in the table's column order: ``alpha_robust``,
+    ``max_cooks``, ``arg_max`` (the sample's label; None without one), ``n_above``, ``n_replace``, ``trimmed_base``;
+    ``attrs['cooks_cutoff']`` and ``attrs['cells']`` (per sample its cell, ``engine.nb_design_cells``)."""
+    who = "deseq2_cooks_design"
+    c, genes, samples, sf, X, beta, _, disp = _nb_design_intake(
+        who, cluster_counts, de, ["gene", "dispersion"], "the frame is of the design `~ group` (no covariates); use deseq2_cooks",
+        lambda: engine._nb_min_replace_arg(min_replace))
+    cutoff = engine.nb_cooks_cutoff(*X.shape)
+    ck = engine.nb_design_cooks(c, X, sf, disp, beta, cutoff, min_replace)
+    labels = np.asarray(samples, dtype=object)
+    out = pd.DataFrame({"alpha_robust": ck["alpha_robust"], "max_cooks": ck["max_cooks"],
+                        "arg_max": [labels[i] if i >= 0 else None for i in ck["arg_max"]], "n_above": ck["n_above"],
+                        "n_replace": ck["n_replace"], "trimmed_base": ck["trimmed_base"]}, index=genes)
+    out.attrs.update(cooks_cutoff=cutoff, cells=pd.Series(engine.nb_design_cells(X)[0], index=samples))
     return out
 
 

@@ -49,7 +49,15 @@ inner Newton fit at every grid point -- of p coefficients there, of p - 1 here, 
 dispersions are one MAP-less pass, the maximum-likelihood coefficients nb_design_fits', the prior scale nb_prior_scale's.
 ``nb_design_dispersions`` and ``nb_design_shrink`` alternate in one loop, best of --reps each; the mean inner steps a lane and
 round of both go beside the ratio.  Host: the restatement (tests/nb_design_shrink_restatement.py) on --host-genes genes, scaled.
-Writes OUT/design_shrink_rate.txt."""
+Writes OUT/design_shrink_rate.txt.
+
+--design-cooks: instead, the Cook's-distance pass under a general design (K28: engine.nb_design_cooks on the whole table, no
+distances returned) at 4 columns beside K25's ``nb_cooks`` for the group column alone and beside ``nb_design_fits`` on the same
+table: K28 is K25's staged pass and sorts plus one pass for the Gram matrix, a Cholesky inverse and the hat diagonals, with the rows
+of X read from global memory.  Two designs a shape: (intercept, batch, scaled age, group), whose cells are single samples (two
+sorts of all samples a gene), and (intercept, batch, centre, group), all indicators, whose eight cells are sorted one by one.
+--outlier-share of the genes get one count x 200.  The three calls alternate in one loop, best of --reps each.  Host: the
+restatement (tests/nb_design_cooks_restatement.py) on --host-genes genes, scaled.  Writes OUT/design_cooks_rate.txt."""
 import argparse
 import os
 import sys
@@ -74,11 +82,12 @@ def main():
     ap.add_argument("--cooks", action="store_true")
     ap.add_argument("--design", action="store_true")
     ap.add_argument("--design-shrink", action="store_true")
+    ap.add_argument("--design-cooks", action="store_true")
     ap.add_argument("--design-cols", type=int, default=4, help="--design, --design-shrink: the columns of the design matrix")
     ap.add_argument("--outlier-share", type=float, default=0.02, help="--cooks: the share of genes that get one count x 200")
     a = ap.parse_args()
-    if a.shrink + a.rlog + a.cooks + a.design + a.design_shrink > 1:
-        ap.error("--shrink, --rlog, --cooks, --design and --design-shrink are separate runs")
+    if a.shrink + a.rlog + a.cooks + a.design + a.design_shrink + a.design_cooks > 1:
+        ap.error("--shrink, --rlog, --cooks, --design, --design-shrink and --design-cooks are separate runs")
     import nb_glm_restatement as RR
     from pilot_amd import _lib, engine
 
@@ -312,7 +321,59 @@ def main():
             % (h, t_host, a.genes, h, t_host * a.genes / h, res.sum(),
                np.abs(KR.t_of(beta[:h, -1], S) - found["t"])[res].max(initial=0)))
         del D
-    for m in (() if a.shrink or a.rlog or a.cooks or a.design or a.design_shrink else a.samples):
+    for m, kinds in ((m, kinds) for m in (a.samples if a.design_cooks else ()) for kinds in (("intercept", "batch", "age", "group"),
+                                                                                             ("intercept", "batch", "centre", "group"))):
+        import nb_design_cooks_restatement as KR
+        import nb_design_restatement as DR
+        rng = np.random.default_rng(m)
+        s = RR.size_factors(rng, m)
+        age = rng.normal(0.0, 1.0, m)
+        cols = {"intercept": np.ones(m), "batch": rng.permutation(np.arange(m) % 2).astype(np.float64), "age": (age - age.mean()) / age.std(ddof=1),
+                "centre": rng.permutation(np.arange(m) // 2 % 2).astype(np.float64), "group": rng.permutation(np.arange(m) >= (m + 1) // 2).astype(np.float64)}
+        X = np.ascontiguousarray(np.stack([cols[k] for k in kinds], axis=1))
+        codes = X[:, -1].astype(np.int32)
+        c = DR.nb_class(rng, s, X, ["batch" if k == "centre" else k for k in kinds], a.genes)
+        hit = rng.choice(a.genes, int(round(a.outlier_share * a.genes)), replace=False)
+        row = rng.integers(0, m, hit.size)
+        c[row, hit] = np.maximum(c[row, hit], 5.0) * 200.0
+        D = engine.DeviceMatrix.upload(c.astype(np.float32))
+        a22 = engine.nb_clip(np.exp(engine.nb_dispersions(D, codes, 2, s)), m)
+        a26 = engine.nb_clip(np.exp(engine.nb_design_dispersions(D, X, s)), m)
+        q, _ = engine.nb_group_fits(D, codes, 2, s, a22)
+        beta, _, _ = engine.nb_design_fits(D, X, s, a26)
+        cut2, cutp = engine.nb_cooks_cutoff(m, 2), engine.nb_cooks_cutoff(m, X.shape[1])
+        engine.nb_cooks(D, codes, 2, s, a22, q, cut2)
+        engine.nb_design_cooks(D, X, s, a26, beta, cutp)
+        t = np.full(3, np.inf)
+        for _ in range(a.reps):                                         # the calls alternate
+            t0 = time.perf_counter()
+            engine.nb_cooks(D, codes, 2, s, a22, q, cut2)
+            t1 = time.perf_counter()
+            engine.nb_design_fits(D, X, s, a26)
+            t2 = time.perf_counter()
+            ck = engine.nb_design_cooks(D, X, s, a26, beta, cutp)
+            t3 = time.perf_counter()
+            t = np.minimum(t, [t1 - t0, t2 - t1, t3 - t2])
+        n_cells = engine.nb_design_cells(X)[1]
+        say("case %d genes x %d samples, float32 in HBM, design of %d columns (%s): %d cells; one count x 200 planted in %d genes; cutoff "
+            "qf(0.99, %d, %d) = %.3f" % (a.genes, m, X.shape[1], ", ".join(kinds), n_cells, hit.size, X.shape[1], m - X.shape[1], cutp))
+        say("  nb_design_cooks %.2f ms; nb_cooks (the group column alone) %.2f ms beside it: ratio %.2f; nb_design_fits %.2f ms: "
+            "nb_design_cooks / (nb_cooks + nb_design_fits) = %.2f; best of %d, alternating"
+            % (1e3 * t[2], 1e3 * t[0], t[2] / t[0], 1e3 * t[1], t[2] / (t[0] + t[1]), a.reps))
+        with np.errstate(invalid="ignore"):
+            say("  %d genes with max_cooks past the cutoff, %d with a replacement" % ((ck["max_cooks"] > cutp).sum(), (ck["n_replace"] > 0).sum()))
+        h = min(a.host_genes, a.genes)
+        t0 = time.perf_counter()
+        want = KR.cooks(c[:, :h], X, s, a26[:h], np.nan_to_num(beta[:h]), cutp)
+        t_host = time.perf_counter() - t0
+        live = ~np.isnan(want["alpha_robust"])
+        say("  host restatement (numpy, a loop over genes) on %d genes: %.1f ms; scaled by %d / %d: %.2f s; device against it: alpha_robust "
+            "off by at most %.2g relative, arg_max equal on %d of %d"
+            % (h, 1e3 * t_host, a.genes, h, t_host * a.genes / h,
+               np.abs(ck["alpha_robust"][:h][live] / want["alpha_robust"][live] - 1.0).max(initial=0),
+               (ck["arg_max"][:h] == want["arg_max"]).sum(), h))
+        del D
+    for m in (() if a.shrink or a.rlog or a.cooks or a.design or a.design_shrink or a.design_cooks else a.samples):
         rng = np.random.default_rng(m)
         s = RR.size_factors(rng, m)
         codes = (np.arange(m) % 2).astype(np.int32)
@@ -347,7 +408,7 @@ def main():
                np.abs(np.expm1(x[:h][res] - xh[res])).max(initial=0)))
         del D, Z
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "design_rate.txt" if a.design else "design_shrink_rate.txt" if a.design_shrink else "rate.txt"), "w") as f:
+    with open(os.path.join(a.out, "shrink_rate.txt" if a.shrink else "rlog_rate.txt" if a.rlog else "cooks_rate.txt" if a.cooks else "design_rate.txt" if a.design else "design_shrink_rate.txt" if a.design_shrink else "design_cooks_rate.txt" if a.design_cooks else "rate.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

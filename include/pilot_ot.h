@@ -578,6 +578,34 @@ int pilot_ot_rank_sums_wave_max(void);
 int pilot_ot_rank_sums_wg_max(void);
 int pilot_ot_rank_sums_sort_tile(void);
 
+/* ---- PERMANOVA (K29): the permutation test of "does this variable explain the distances between samples" on the distance matrix
+ * itself (Anderson 2001; vegan's adonis2, marginal terms).  vegan is not installed where this library is built, so the rule is THIS
+ * LIBRARY'S STATEMENT, unpinned.
+ * D: N x N, dtype 0 float32 / 1 float64, leading dimension ld, on the host or in HBM.  rows: the n used samples, ascending (NULL: all,
+ * n == N).  s_ij = (D_ij + D_ji) / 2 (i != j), s_ii = 0, A_ij = -0.5 s_ij s_ij, in float64; *ss_total = -(1/n) sum_ij A_ij.
+ * Q (host, n x c, packed): the model terms, term t being columns term_off[t] .. term_off[t + 1] - 1 (term_off: n_terms + 1 ints from
+ * 0 to c); the columns are centred and orthonormal within a term (only the centring is checked).
+ * Permutation 0 is the identity.  For b >= 1, row i's key is the first two words of Philox4x32-10(counter (i, b mod 2^32, b div 2^32, 0),
+ * key (seed mod 2^32, seed div 2^32)), w0 2^32 + w1; with s_0, s_1, ... the rows ordered by (stratum, key, i) and r_0, r_1, ... by
+ * (stratum, i), the permuted design is Z_b[r_t, :] = Q[s_t, :] (strata NULL: one stratum).  A function of (seed, b, n, strata) alone.
+ * Out (host): ss[(b - start) * n_terms + t] = sum over the term's columns, in column order, of Z_b[:, c]^T A Z_b[:, c], for
+ * b = start .. start + count - 1.  Permutation b's values have the same bits in any batch, at any start, under any chunking; no
+ * floating-point atomics.  Device memory does not grow with count: permutations are processed pilot_ot_permanova_limits' chunk at a
+ * time.  kernel_ms (nullable, 3 floats): device milliseconds of the prepare, permute and quadratic-form kernels.
+ * A NaN or infinity between two used samples: PILOT_OT_EINVAL with *bad_row / *bad_col (nullable; -1 otherwise) one such entry of D.
+ * PILOT_OT_EINVAL (before any HIP call): a NULL pointer, N < 1, ld < N, dtype not 0 / 1, n < 1 (or != N without rows), rows not
+ * ascending inside [0, N), c outside [1, 4096], n_terms outside [1, c], term_off not strictly ascending from 0 to c, a column of Q
+ * whose sum is not 0 to 1e-8 (1 + sum |q|), a negative stratum, start or count.  PILOT_OT_ENOTSUP (before any HIP call): n > 8192,
+ * the LDS sort's limit. */
+int pilot_ot_permanova(const void *D, int D_is_device, int dtype, int N, long long ld, const int *rows, int n, const double *Q, int c,
+                       const int *term_off, int n_terms, const int *strata, unsigned long long seed, long long start, long long count,
+                       double *ss_total, double *ss, long long *bad_row, long long *bad_col, float *kernel_ms);
+/* The permutations themselves: perm[(b - start) * n + r_t] = s_t (host, count x n int32).  Same checks. */
+int pilot_ot_permanova_permutations(int n, const int *strata, unsigned long long seed, long long start, long long count, int *perm);
+/* Every pointer nullable: the largest n, the permutations per pass (at most 65536 / c when that is fewer), the columns a workgroup
+ * of the quadratic-form kernel owns and the rows of A it reads. */
+int pilot_ot_permanova_limits(int *max_n, int *chunk, int *tile_cols, int *row_block);
+
 /* ---- negative-binomial GLM (K22): DESeq2's model (Love, Huber, Anders 2014) for the one design pilotpy's compute_pseudobulk_DE
  * uses, `~ stage` (plot/pseudobulk_DE_analysis.py:96-159): an intercept plus a group indicator, for which every piece decouples by
  * group.  DESeq2 is not installed where this library is built, so the rule is THIS LIBRARY'S STATEMENT, unpinned (DESIGN.md K22;

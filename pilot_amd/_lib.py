@@ -54,6 +54,7 @@ SYMBOLS = [
     "pilot_ot_group_sums", "pilot_ot_csr_group_sums", "pilot_ot_group_sums_slice_rows", "pilot_ot_group_sums_col_block",
     "pilot_ot_rank_sums", "pilot_ot_csr_rank_sums", "pilot_ot_rank_sums_wave_max", "pilot_ot_rank_sums_wg_max",
     "pilot_ot_rank_sums_sort_tile",
+    "pilot_ot_permanova", "pilot_ot_permanova_permutations", "pilot_ot_permanova_limits",
     "pilot_ot_nb_dispersions", "pilot_ot_nb_group_fits", "pilot_ot_nb_glm_max_samples", "pilot_ot_nb_shrink",
     "pilot_ot_nb_dispersions_blind", "pilot_ot_nb_rlog", "pilot_ot_nb_cooks",
     "pilot_ot_nb_design_max_cols", "pilot_ot_nb_design_max_samples", "pilot_ot_nb_design_dispersions", "pilot_ot_nb_design_fits",
@@ -196,6 +197,10 @@ def load() -> ctypes.CDLL:
     L.pilot_ot_rank_sums_wave_max.argtypes = []
     L.pilot_ot_rank_sums_wg_max.argtypes = []
     L.pilot_ot_rank_sums_sort_tile.argtypes = []
+    L.pilot_ot_permanova.argtypes = [c_vp, c_int, c_int, c_int, ctypes.c_longlong, ip, c_int, dp, c_int, ip, c_int, ip, ctypes.c_ulonglong,
+                                     ctypes.c_longlong, ctypes.c_longlong, dp, dp, llp, llp, ctypes.POINTER(ctypes.c_float)]
+    L.pilot_ot_permanova_permutations.argtypes = [c_int, ip, ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_longlong, ip]
+    L.pilot_ot_permanova_limits.argtypes = [ip, ip, ip, ip]
     L.pilot_ot_nb_dispersions.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, dp, dp, c_dbl, dp, dp,
                                           dp, llp, ip]
     L.pilot_ot_nb_group_fits.argtypes = [c_vp, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_longlong, ip, c_int, dp, dp, dp, dp, ip, ip, ip]

@@ -1249,6 +1249,168 @@ def kruskal_h(count, rank_sums, ties):
     return H, stats.chi2.sf(H, df), df
 
 
+# ---- PERMANOVA (K29; Anderson 2001, vegan's adonis2 with marginal terms: DESIGN.md K29) ------------------------------------------
+PERMANOVA_EPS = float(np.sqrt(2.0 ** -52))
+PERMANOVA_RANK_TOL = 1e-10
+
+
+def permanova_limits():
+    """``(max_n, chunk, tile_cols, row_block)`` of :func:`permanova_ss`: the most samples the LDS sort of the permutation kernel
+    takes, the permutations one pass processes (fewer when ``65536 / columns`` is fewer; the test switch
+    ``PILOT_OT_PERMANOVA_CHUNK`` lowers it), the columns a workgroup of the quadratic-form kernel owns and the rows of A it reads."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    _lib.check(_lib.load().pilot_ot_permanova_limits(*[ctypes.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+def permanova_basis(X):
+    """The model terms of :func:`permanova_ss` from variables: ``X`` maps a name to one value per sample (a dict, a pandas
+    DataFrame, or a list of arrays named "0", "1", ...).  A variable of a numeric or boolean dtype is itself; any other is
+    categorical and becomes the indicators of all its levels but the first, the levels being ``sorted`` as Python strings.
+    Every term is centred and replaced by the Q of its thin QR (numpy); a column whose R diagonal is below ``1e-10 max |R_ii|``
+    is dropped.  A term with no variation (``max |R_ii| <= 1e-10`` times the norm of its uncentred columns: one level, a constant)
+    has rank 0 and raises ValueError naming it, as does a missing or non-finite value.  Returns ``(Q, terms)``: ``n x c`` float64
+    and the ``len(X) + 1`` int32 column offsets of the terms."""
+    if hasattr(X, "columns") and hasattr(X, "__getitem__") and not isinstance(X, dict):
+        X = {str(c): np.asarray(X[c]) for c in X.columns}
+    elif not isinstance(X, dict):
+        X = {str(i): np.asarray(v) for i, v in enumerate(X)}
+    if not X:
+        raise ValueError("permanova_basis: no variable")
+    blocks, terms, n = [], [0], None
+    for name, values in X.items():
+        v = np.asarray(values)
+        if v.ndim != 1 or (n is not None and v.shape[0] != n) or v.shape[0] < 1:
+            raise ValueError("permanova_basis: %r must hold one value per sample, got shape %s" % (name, v.shape))
+        n = v.shape[0]
+        if v.dtype.kind in "biuf":
+            M = v.astype(np.float64).reshape(n, 1)
+            if not np.all(np.isfinite(M)):
+                raise ValueError("permanova_basis: %r has a missing or non-finite value" % (name,))
+        else:
+            if any(x is None or (isinstance(x, float) and x != x) for x in v.tolist()):
+                raise ValueError("permanova_basis: %r has a missing value" % (name,))
+            labels = np.array([str(x) for x in v.tolist()], dtype=object)
+            levels = sorted(set(labels.tolist()))
+            M = np.stack([(labels == lev).astype(np.float64) for lev in levels[1:]], axis=1) if len(levels) > 1 else np.zeros((n, 0))
+        scale = float(np.sqrt((M * M).sum()))
+        Mc = M - M.mean(axis=0, keepdims=True) if M.shape[1] else M
+        Qt, R = np.linalg.qr(Mc) if M.shape[1] else (Mc, np.zeros((0, 0)))
+        d = np.abs(np.diag(R))
+        if d.size == 0 or not d.max() > PERMANOVA_RANK_TOL * scale:
+            raise ValueError("permanova_basis: term %r has rank 0 (a single level or a constant)" % (name,))
+        Qt = Qt[:, d >= PERMANOVA_RANK_TOL * d.max()]
+        blocks.append(Qt)
+        terms.append(terms[-1] + Qt.shape[1])
+    return np.ascontiguousarray(np.concatenate(blocks, axis=1)), np.asarray(terms, dtype=np.int32)
+
+
+def _permanova_window(n_perm, seed, start):
+    n_perm, seed, start = int(n_perm), int(seed), int(start)
+    if n_perm < 0:
+        raise ValueError("n_perm=%d permutations" % n_perm)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed=%d must be in [0, 2^64)" % seed)
+    if not 0 <= start <= n_perm:
+        raise ValueError("start=%d must be in [0, n_perm=%d]" % (start, n_perm))
+    return n_perm, seed, start
+
+
+def _permanova_samples(n, strata, who):
+    n = int(n)
+    if n < 1:
+        raise ValueError("%s: n=%d samples" % (who, n))
+    max_n = permanova_limits()[0]
+    if n > max_n:
+        raise ValueError("%s: n=%d samples do not fit the LDS sort of the permutation kernel (at most %d)" % (who, n, max_n))
+    if strata is None:
+        return n, None
+    codes, _ = _label_codes(strata, n)
+    return n, codes
+
+
+def permanova_permutations(n, n_perm, seed=0, strata=None, start=0):
+    """K29's permutations ``start .. n_perm`` of ``n`` samples, generated on the device: an ``(n_perm + 1 - start) x n`` int32
+    array whose row ``b - start`` is the permutation ``p`` with ``Z_b[i, :] = Q[p[i], :]``.  Permutation 0 is the identity; for
+    b >= 1 the rows are ordered by ``(stratum, Philox4x32-10 key, index)`` and dealt to the rows ordered by ``(stratum, index)``
+    (DESIGN.md K29), so a permutation is uniform within ``strata`` (one label per sample; None: one stratum) and a function of
+    ``(seed, b, n, strata)`` alone.  ValueError before any device work: n outside 1 .. ``permanova_limits()[0]``, a negative seed
+    or one beyond 2^64 - 1, ``start`` outside ``[0, n_perm]``, strata of another length."""
+    n_perm, seed, start = _permanova_window(n_perm, seed, start)
+    n, codes = _permanova_samples(n, strata, "permanova_permutations")
+    out = np.empty((n_perm + 1 - start, n), dtype=np.int32)
+    _lib.check(_lib.load().pilot_ot_permanova_permutations(n, None if codes is None else _lib.iptr(codes), seed, start, out.shape[0],
+                                                           _lib.iptr(out)))
+    return out
+
+
+def permanova_ss(D, Q, terms, n_perm, seed=0, rows=None, strata=None, start=0, return_times=False):
+    """K29: the sums of squares of PERMANOVA's model terms under permutations ``start .. n_perm`` (0 is the observed design).
+    ``D``: an N x N float32 / float64 numpy array or :class:`DeviceMatrix` of dissimilarities; ``rows``: the ascending indices
+    of the n samples used (None: all).  ``s_ij = (D_ij + D_ji) / 2``, ``s_ii = 0``, ``A_ij = -0.5 s_ij s_ij`` in float64.
+    ``Q`` (n x c float64) and ``terms`` (offsets) are :func:`permanova_basis`'s: centred columns, orthonormal within a term.
+    Returns ``(ss_total, ss)``: ``-(1/n) sum_ij A_ij`` and the ``(n_perm + 1 - start) x terms`` array ``ss[b - start, t] = sum
+    over the term's columns of Z_b[:, c]^T A Z_b[:, c]`` with :func:`permanova_permutations`' ``Z_b``.  Permutation b's values
+    have the same bits alone, in any batch, at any ``start`` and under any chunking.  ``return_times=True`` adds a dict of the
+    device milliseconds of the ``prepare``, ``permute`` and ``quadratic`` kernels.
+    ValueError before any device work: D not square, rows not ascending inside it, more than ``permanova_limits()[0]`` samples, Q
+    not n x c float64, terms not strictly ascending offsets from 0 to c, a column of Q that is not centred, a bad seed or
+    ``start``, strata of another length.  ValueError naming the entry: a NaN or infinity between two used samples."""
+    n_perm, seed, start = _permanova_window(n_perm, seed, start)
+    Dm = _dense_arg(D, "D", mode="strided")
+    if Dm.rows != Dm.cols:
+        raise ValueError("D must be samples x samples, got %d x %d" % (Dm.rows, Dm.cols))
+    if rows is not None:
+        rows = np.ascontiguousarray(rows)
+        if rows.ndim != 1 or rows.dtype.kind not in "iu" or rows.size < 1:
+            raise ValueError("rows: a 1-D array of at least one integer index, got %s %s" % (rows.shape, rows.dtype))
+        if rows.min() < 0 or rows.max() >= Dm.rows or np.any(np.diff(rows.astype(np.int64)) <= 0):
+            raise ValueError("rows must be ascending indices inside [0, %d)" % Dm.rows)
+        rows = rows.astype(np.int32)
+    n, codes = _permanova_samples(Dm.rows if rows is None else rows.size, strata, "permanova_ss")
+    if not isinstance(Q, np.ndarray) or Q.ndim != 2 or Q.dtype != np.float64 or Q.shape[0] != n or Q.shape[1] < 1:
+        raise ValueError("Q: an n x c float64 array with n=%d rows, got %s %s" % (n, getattr(Q, "shape", type(Q).__name__),
+                                                                                  getattr(Q, "dtype", "")))
+    Q = np.ascontiguousarray(Q)
+    terms = np.ascontiguousarray(terms, dtype=np.int32)
+    c = Q.shape[1]
+    if terms.ndim != 1 or terms.size < 2 or terms[0] != 0 or terms[-1] != c or np.any(np.diff(terms) <= 0):
+        raise ValueError("terms: strictly ascending column offsets from 0 to c=%d, got %s" % (c, terms.tolist()))
+    if not np.all(np.isfinite(Q)):
+        raise ValueError("Q has a NaN or an infinity")
+    off = np.abs(Q.sum(axis=0)) > 1e-8 * (1.0 + np.abs(Q).sum(axis=0))
+    if off.any():
+        raise ValueError("column %d of Q is not centred (sum %g): permanova_basis centres the terms" % (int(np.flatnonzero(off)[0]),
+                                                                                                       Q.sum(axis=0)[off][0]))
+    n_terms, count = terms.size - 1, n_perm + 1 - start
+    ss_total = ctypes.c_double(0.0)
+    ss = np.empty((count, n_terms), dtype=np.float64)
+    bad_row, bad_col = ctypes.c_longlong(-1), ctypes.c_longlong(-1)
+    ms = (ctypes.c_float * 3)()
+    _lib.check(_lib.load().pilot_ot_permanova(
+        Dm.ptr, Dm.on_dev, _lib.dtype_code(Dm.dtype), Dm.rows, Dm.ld, None if rows is None else _lib.iptr(rows), n, _lib.dptr(Q), c,
+        _lib.iptr(terms), n_terms, None if codes is None else _lib.iptr(codes), seed, start, count, ctypes.byref(ss_total), _lib.dptr(ss),
+        ctypes.byref(bad_row), ctypes.byref(bad_col), ms if return_times else None))
+    if return_times:
+        return ss_total.value, ss, dict(zip(("prepare", "permute", "quadratic"), (float(v) for v in ms)))
+    return ss_total.value, ss
+
+
+def permanova_f(ss_total, ss, terms, n):
+    """``F[b, t] = (ss / q_t) / ((ss_total - ss) / (n - q_t - 1))`` of :func:`permanova_ss`'s result, ``q_t`` the columns of term t."""
+    q = np.diff(np.asarray(terms, dtype=np.int64)).astype(np.float64)
+    ss = np.asarray(ss, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (ss / q) / ((float(ss_total) - ss) / (float(n) - q - 1.0))
+
+
+def permanova_p(F):
+    """``p_t = (1 + #{b >= 1: F[b, t] >= F[0, t] - EPS}) / (1 + n_perm)`` with ``EPS = sqrt(2^-52)``, every term against the same
+    permutations; ``F`` from :func:`permanova_f` of a run with ``start=0``."""
+    F = np.asarray(F, dtype=np.float64)
+    return (1.0 + np.count_nonzero(F[1:] >= F[0] - PERMANOVA_EPS, axis=0)) / float(F.shape[0])
+
+
 # ---- negative-binomial GLM (K22; DESeq2's model for the one-factor design of pilotpy's compute_pseudobulk_DE) ------------------
 NB_MIN_DISP = 1e-8
 NB_MIN_MU = 0.5

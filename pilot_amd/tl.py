@@ -3225,3 +3225,191 @@ def get_pseudobulk_DE(adata, proportion_df, cell_type, celltype_col="cell_types"
                                                          shrink=shrink, outliers=outliers, independent_filtering=independent_filtering,
                                                          alpha=alpha, covariates=covariates or None, test=test)
     return out
+
+
+# ---- clinical variables (Trajectory.py:1361-1609: the four correlation_* tests; PERMANOVA of uns['EMD']: DESIGN.md K29) ---------
+def _converts_to_float(value):
+    try:
+        float(value)
+    except ValueError:
+        return False
+    return True
+
+
+def _clinical_values(adata, left, sample_col, feature):
+    """``left`` (a frame with a ``sampleID`` column) with the feature's value of every sample beside it: the value of the sample's
+    first row of ``adata.obs``, NaN for a sample obs does not have"""
+    values = adata.obs[[sample_col, feature]].rename(columns={sample_col: "sampleID"})
+    return left.merge(values, on="sampleID", how="left").drop_duplicates(subset="sampleID")
+
+
+def _drop_numbers(frame, feature):
+    """a categorical test's cleaning: the rows whose value is among the floats the column's values convert to are dropped -- real
+    numbers and NaN go, a numeric STRING stays (it is not equal to its float) and is a level"""
+    numbers = [float(v) for v in frame[feature] if _converts_to_float(v)]
+    return frame[~frame[feature].isin(numbers)]
+
+
+def _drop_labels(frame, feature):
+    """a numeric test's cleaning: the rows whose value does not convert to a float are dropped; NaN converts, and stays"""
+    labels = np.unique([v for v in frame[feature] if not _converts_to_float(v)])
+    return frame[~frame[feature].isin(list(labels))]
+
+
+def _significant(rows, p_column, sort_column):
+    """the reference's last three lines: the features with p < 0.05, sorted"""
+    table = pd.DataFrame(rows)
+    table = table[table[p_column].astype(float) < 0.05]
+    return table.sort_values(by=sort_column)
+
+
+def correlation_categorical_with_trajectory(adata, sample_col="sampleID", features=[], sort_column="ANOVA_PValue"):
+    """The reference's test of categorical clinical variables against the pseudotime (Trajectory.py:1377-1427), host only:
+    per feature, ``scipy.stats.f_oneway`` of ``uns['orders'].Time_score`` over the feature's levels, one value per sample (its
+    first row of ``adata.obs``), after dropping real numbers and missing values.  Returns the reference's frame ``Feature,
+    ANOVA_FStatistic, ANOVA_PValue``: only the features with p < 0.05, sorted by ``sort_column``.  The Kruskal-Wallis statistic
+    the reference computes and discards is not computed.  :func:`permanova` tests the same question on the distances themselves."""
+    from scipy import stats
+    rows = []
+    for feature in features:
+        frame = _drop_numbers(_clinical_values(adata, adata.uns["orders"], sample_col, feature), feature)
+        frame = frame.dropna(subset=["Time_score", feature])
+        stat, p = stats.f_oneway(*[group["Time_score"] for _, group in frame.groupby(feature)])
+        rows.append({"Feature": feature, "ANOVA_FStatistic": stat, "ANOVA_PValue": float(p)})
+    return _significant(rows, "ANOVA_PValue", sort_column)
+
+
+def correlation_numeric_with_trajectory(adata, sample_col="sampleID", features=[], sort_column="Spearman_PValue"):
+    """The reference's test of numeric clinical variables against the pseudotime (Trajectory.py:1444-1492), host only: per
+    feature, ``scipy.stats.spearmanr`` of ``uns['orders'].Time_score`` and the feature, one value per sample, after dropping the
+    values that are no numbers.  A missing value is NOT dropped, as in the reference: the correlation is NaN and the feature
+    fails the filter.  Returns ``Feature, Spearman_Correlation, Spearman_PValue`` for p < 0.05, sorted by ``sort_column``
+    (Kendall's tau, computed and discarded by the reference, is not computed)."""
+    from scipy import stats
+    rows = []
+    for feature in features:
+        frame = _drop_labels(_clinical_values(adata, adata.uns["orders"], sample_col, feature), feature)
+        corr, p = stats.spearmanr(frame["Time_score"], frame[feature])
+        rows.append({"Feature": feature, "Spearman_Correlation": corr, "Spearman_PValue": float(p)})
+    return _significant(rows, "Spearman_PValue", sort_column)
+
+
+def correlation_categorical_with_clustering(adata, proportion_df, sample_col="sampleID", features=[], sort_column="ChiSquared_PValue"):
+    """The reference's test of categorical clinical variables against the samples' sub-groups (Trajectory.py:1497-1549), host
+    only: per feature, ``scipy.stats.chi2_contingency`` of the table ``Predicted_Labels`` x levels.  ``proportion_df`` is what
+    :func:`clustering_emd` returns.  Returns ``Feature, ChiSquared_Statistic, ChiSquared_PValue`` for p < 0.05, sorted."""
+    from scipy import stats
+    groups = proportion_df[["sampleID", "Predicted_Labels"]]
+    rows = []
+    for feature in features:
+        frame = _drop_numbers(_clinical_values(adata, groups, sample_col, feature), feature)
+        table = pd.crosstab(frame["Predicted_Labels"].astype(str), frame[feature])
+        stat, p = stats.chi2_contingency(table)[:2]
+        rows.append({"Feature": feature, "ChiSquared_Statistic": stat, "ChiSquared_PValue": float(p)})
+    return _significant(rows, "ChiSquared_PValue", sort_column)
+
+
+def correlation_numeric_with_clustering(adata, proportion_df, sample_col="sampleID", features=[], sort_column="ANOVA_P_Value"):
+    """The reference's test of numeric clinical variables against the samples' sub-groups (Trajectory.py:1551-1609), host only:
+    per feature, ``scipy.stats.f_oneway`` of the feature over the ``Predicted_Labels``, in their order of first appearance.
+    Returns ``Feature, ANOVA_F_Statistic, ANOVA_P_Value`` for p < 0.05, sorted (no Kruskal-Wallis statistic)."""
+    from scipy import stats
+    groups = proportion_df[["sampleID", "Predicted_Labels"]]
+    rows = []
+    for feature in features:
+        frame = _drop_labels(_clinical_values(adata, groups, sample_col, feature), feature)
+        labels = frame["Predicted_Labels"].astype(str)
+        result = stats.f_oneway(*[frame[labels == g][feature].values for g in labels.unique()])
+        rows.append({"Feature": feature, "ANOVA_F_Statistic": result.statistic, "ANOVA_P_Value": float(result.pvalue)})
+    return _significant(rows, "ANOVA_P_Value", sort_column)
+
+
+_PERMANOVA_COLUMNS = ["Feature", "kind", "n", "df", "SS_model", "SS_total", "R2", "pseudo_F", "p_value", "p_adj"]
+
+
+def _permanova_variable(values):
+    """One value per sample -> ``(kind, used, x)``: the reference's cleaning.  A missing value (None, NaN) drops its sample.  If
+    every other value converts with ``float()`` the variable is numeric (``detect_values_to_remove`` would remove nothing) and
+    ``x`` the floats; else it is categorical, the real numbers among its values are dropped as ``detect_numeric_values`` drops
+    them (a numeric string stays, and is a level), and ``x`` the values as strings."""
+    present = np.array([not (v is None or (isinstance(v, (float, np.floating)) and v != v)) for v in values], dtype=bool)
+    if all(_converts_to_float(v) for v, ok in zip(values, present) if ok):
+        return "numeric", present, np.array([float(v) for v, ok in zip(values, present) if ok], dtype=np.float64)
+    numbers = [float(v) for v, ok in zip(values, present) if ok and _converts_to_float(v)]
+    used = present & ~pd.Series(list(values), dtype=object).isin(numbers).to_numpy()
+    return "categorical", used, np.array([str(v) for v, ok in zip(values, used) if ok], dtype=object)
+
+
+def permanova(adata, features, sample_col="sampleID", permutations=9999, seed=0, strata=None, D=None):
+    """PERMANOVA of the samples' distance matrix against clinical variables (Anderson 2001; the rule is this library's, DESIGN.md
+    K29): does the variable explain the distances between the samples?  Where the reference tests a variable against the
+    one-dimensional pseudotime or the sub-group labels, this is the permutation test on ``uns['EMD']`` itself.
+
+    ``D`` (default ``adata.uns['EMD']``): a samples x samples array or ``engine.DeviceMatrix``, in the order of
+    ``uns['proportions']``.  Per feature: one value per sample (its first row of ``adata.obs``); numeric if every value present
+    converts with ``float()``, else categorical (real numbers among the values are dropped, numeric strings are levels), as the
+    reference's ``detect_values_to_remove`` / ``detect_numeric_values`` decide; a sample with a missing value is dropped.  The
+    features with the same used samples share one ``engine.permanova_ss`` call: every feature is a marginal term, tested
+    against the same ``permutations`` permutations of ``seed`` (within the levels of the obs column ``strata``, if given).
+    Returns a frame, one row per feature in the order given: ``Feature, kind, n, df, SS_model, SS_total, R2, pseudo_F, p_value,
+    p_adj``; ``p_value = (1 + #{F_b >= F_0 - sqrt(2^-52)}) / (1 + permutations)`` and ``p_adj`` its Benjamini-Hochberg
+    adjustment over the features.  ``attrs``: ``permutations``, ``seed``, ``strata``.  No 0.05 filter, no plots, no files.
+
+    Not covered / deviations: sequential or adjusted terms (every term is tested alone), PERMDISP, pairwise post-hoc tests.
+    ValueError before any device work: no ``uns['EMD']`` / ``['proportions']``, a matrix of another size, an unknown feature or
+    strata column, a missing stratum, a feature with one level or no variation, fewer than ``df + 2`` samples left."""
+    if D is None:
+        if "EMD" not in adata.uns:
+            raise ValueError("adata.uns has no 'EMD': run tl.wasserstein_distance first, or pass D")
+        D = adata.uns["EMD"]
+    if "proportions" not in adata.uns:
+        raise ValueError("adata.uns has no 'proportions': run tl.wasserstein_distance first")
+    samples = list(adata.uns["proportions"].keys())
+    N = len(samples)
+    if tuple(getattr(D, "shape", np.shape(D))) != (N, N):
+        raise ValueError("D is %s, uns['proportions'] has %d samples" % (tuple(getattr(D, "shape", np.shape(D))), N))
+    features = list(features)
+    if not features:
+        raise ValueError("permanova: no feature")
+    for name in features + ([strata] if strata is not None else []):
+        if name not in adata.obs.columns:
+            raise ValueError("adata.obs has no column %r" % (name,))
+    permutations = int(permutations)
+    if permutations < 1:
+        raise ValueError("permutations=%d" % permutations)
+    first = adata.obs.drop_duplicates(subset=sample_col).set_index(sample_col)
+
+    def per_sample(name):
+        return [first.at[s, name] if s in first.index else None for s in samples]
+
+    strata_values = None
+    if strata is not None:
+        strata_values = np.array([str(v) for v in per_sample(strata)], dtype=object)
+        if any(v is None or (isinstance(v, float) and v != v) for v in per_sample(strata)):
+            raise ValueError("strata column %r has a missing value" % (strata,))
+    calls = {}
+    for position, name in enumerate(features):
+        kind, used, x = _permanova_variable(per_sample(name))
+        calls.setdefault(used.tobytes(), (used, []))[1].append((position, name, kind, x))
+    bases = []
+    for used, members in calls.values():
+        Q, terms = engine.permanova_basis({name: x for _, name, _, x in members})
+        n = int(used.sum())
+        if n - int(np.diff(terms).max()) - 1 < 1:
+            raise ValueError("permanova: %d samples are too few for a term of %d columns" % (n, int(np.diff(terms).max())))
+        bases.append((Q, terms, n))
+    records = [None] * len(features)
+    for (used, members), (Q, terms, n) in zip(calls.values(), bases):
+        rows = None if used.all() else np.flatnonzero(used).astype(np.int32)
+        ss_total, ss = engine.permanova_ss(D, Q, terms, permutations, seed=seed, rows=rows,
+                                           strata=None if strata_values is None else strata_values[used])
+        F = engine.permanova_f(ss_total, ss, terms, n)
+        p = engine.permanova_p(F)
+        for t, (position, name, kind, _) in enumerate(members):
+            records[position] = {"Feature": name, "kind": kind, "n": n, "df": int(terms[t + 1] - terms[t]), "SS_model": ss[0, t],
+                                 "SS_total": ss_total, "R2": ss[0, t] / ss_total, "pseudo_F": F[0, t], "p_value": p[t]}
+    table = pd.DataFrame(records)
+    table["p_adj"] = _bh_adjust(table["p_value"].to_numpy())
+    table = table[_PERMANOVA_COLUMNS]
+    table.attrs.update(permutations=permutations, seed=int(seed), strata=strata)
+    return table
